@@ -517,6 +517,19 @@ def bench_nsde(args, reg_type=None):
                          "us_per_attempt": us_att}}
 
 
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: each value as out_dir/<name>.npy -- device tensors as float32 (the dtype they have), host scalars (reg, nfe) in float64."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        if isinstance(v, torch.Tensor):
+            a = v.detach().to("cpu", torch.float32).numpy()
+        else:
+            a = np.asarray(float(v), dtype=np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def spawn_multi_gpu(args):
     """`python bench.py --gpus N` without a launcher: start the N ranks as a fresh torchrun child (nothing here has touched the GPU
     yet, and the child is a child process, not an exec) and pass its JSON line through."""
@@ -549,7 +562,13 @@ def main():
     ap.add_argument("--nsde-type", default="error_est", choices=["error_est", "stiff_est"], help="--workload nsde: the regulariser (experiments/configs/mnist_nsde.yml `type`; the reference ships stiff_est)")
     ap.add_argument("--workload", default="mnist", choices=["mnist", "latent", "latent_e2e", "nsde"], help="mnist = BASELINE.json's metric (default); latent = config 4 (dynamics only); "
                     "latent_e2e = config 4 with the whole model around the solve; nsde = config 5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="--workload mnist: after the timed steps, write what the LAST timed training step "
+                    "gave its caller (loss, cross entropy, regulariser, NFE, the p2 / p3 gradients) and the weights after its update as DIR/<name>.npy "
+                    "(float32 / float64; rank 0; e.g. DIR = bench_outputs).  Under --gpus N the gradients are the all-reduced SUMS over the ranks (the 1 / N "
+                    "rides in the optimiser update).  Inputs and initial weights are seeded: the same arguments give the same inputs on every run")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "mnist":
+        raise SystemExit("--dump-outputs: only the default workload (mnist) writes its outputs")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_multi_gpu(args))
@@ -626,6 +645,7 @@ def main():
         model.node.set_coupling(reducer.comm, world * B)
     nfes = []
     saved = [p.detach().clone() for p in model.trainable()]
+    dump = {} if args.dump_outputs else None      # --dump-outputs: references to what the latest step returned (read after the timed steps)
 
     def train_step(restore=False):
         if args.autograd:
@@ -636,6 +656,12 @@ def main():
                 reducer.allreduce_(mean=False)
         else:   # loss stays on the device; with a reducer the two gradient all-reduces (RCCL over xGMI, 166,418 fp32 in all) are queued inside
             loss, ce, reg, nfe = rn.fused_loss_and_grad(model, x, y, lam=1.0e2, sync=False, flat=fg, reducer=reducer)
+        if dump is not None:
+            # references, not copies (no extra device work in the timed steps).  They stay what this step returned because FluxOptimiser.step
+            # only reads the gradient (rnde_momentum_step_scaled: const g) and then drops p.grad instead of zeroing it in place, and the next step writes its gradients into fresh tensors (one GPU) or
+            # into the flat buffer (--gpus N) -- which nothing touches between the last timed step and write_outputs below.  If either changes,
+            # take copies here.
+            dump.update(loss=loss, cross_entropy=ce, reg=reg, nfe=nfe, grad_p2=model.p2.grad, grad_p3=model.p3.grad)
         opt.step(grad_scale=reducer.grad_scale if use_dist else 1.0)
         if restore:                                                       # fixed-weights leg: the update ran, its effect is undone
             with torch.no_grad():
@@ -680,6 +706,8 @@ def main():
     for _ in range(args.warmup):
         train_step()
     elapsed, mean_nfe, last_loss = timed(False)
+    if dump is not None and rank == 0:
+        write_outputs(args.dump_outputs, dict(dump, p2_after_step=model.p2, p3_after_step=model.p3))
 
     # ---- N > 1 diagnostics (every rank takes part): per-rank NFE and persistent-kernel fallbacks, and the all-reduce on its own (HIP events) ----
     dist_diag = None

@@ -115,19 +115,32 @@ def test_in_process_group_allreduce(world):
         L.rnde_comm_destroy(C.c_void_p(c))
 
 
-@pytest.mark.parametrize("world,mean", [(2, 0), (4, 1), (8, 1)])      # (8: config 3's world size -- 7 peer windows per rank, 8-way flags -- rehearsed on the one GPU there is)
+def _need_gpus_for_ranks(world):
+    """Up to 4 ranks share device 0 (with this process: at most 5 processes on one GPU).  A world of more ranks runs one rank per device,
+    as on config 3's 8-GPU node: the test looks at the device count before it starts anything and skips without enough devices.
+    Returns True when the ranks are to get a device each."""
+    import torch
+    n = torch.cuda.device_count()
+    if world > 4 and n < world:
+        pytest.skip(f"needs {world} GPUs (one per rank), found {n}")
+    return world > 4
+
+
+@pytest.mark.parametrize("world,mean", [(2, 0), (4, 1), (8, 1)])      # (8: config 3's world size -- 7 peer windows per rank, 8-way flags -- one rank per device, on 8 GPUs)
 def test_one_shot_allreduce_between_processes(world, mean, tmp_path):
     """rnde_comm_window_create / rnde_comm_create_peers: `world` PROCESSES (tools/oneshot_worker.py), each with its own window, mapped
-    into every peer through hipIpc -- on the one GPU of the test box all ranks sit on device 0, the mapping and the kernel are the ones
-    a multi-GPU node runs.  Every rank checks every all-reduce bit for bit against the rank-order fp32 sum: sizes 1 .. 300,001 floats
+    into every peer through hipIpc -- up to 4 ranks sit on device 0 of the test box (the mapping and the kernel are the ones a multi-GPU
+    node runs); world 8 puts rank r on device r and needs 8 GPUs.  Every rank checks every all-reduce bit for bit against the rank-order fp32 sum: sizes 1 .. 300,001 floats
     (above one window slot: pieces), aligned and unaligned buffers, both slot sets, with and without the 1 / world scale."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    own_gpu = _need_gpus_for_ranks(world)          # world 8: rank r on device r, as on a multi-GPU node
     procs = [subprocess.Popen([sys.executable, os.path.join(root, "tools", "oneshot_worker.py"), "--rank", str(r), "--world", str(world),
-                               "--dir", str(tmp_path), "--mean", str(mean)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+                               "--dir", str(tmp_path), "--mean", str(mean), "--device", str(r if own_gpu else 0)],
+                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
              for r in range(world)]
     outs = []
     try:
@@ -299,33 +312,44 @@ def test_one_shot_allreduce_reports_an_absent_rank(tmp_path):
     assert r0["nan_frac"] == 1.0 and r0["next_enqueue"] != 0 and "gave up after 0.3 s" in r0["next_error"] and "failed for good" in r0["next_error"]
 
 
-def test_bench_runs_eight_ranks_of_512_on_one_gpu_config3_rehearsal():
-    """Config 3 as the driver will launch it (`torchrun --nproc-per-node 8 bench.py --gpus 8 ...`, 8 x 512 = global batch 4096, one gradient all-reduce per
-    step), rehearsed on the ONE GPU there is: `--share-gpu --global-batch 4096` puts all eight ranks on device 0 (gloo + the one-shot collective over
-    eight peer-mapped windows; RCCL refuses two ranks on one device).  What this covers of config 3: the command line, rank / shard arithmetic, eight
-    B = 512 solves and reverse sweeps whose persistent kernels take turns on the 256 CUs, the 8-way all-reduce of the 166,418-float buffer, the barrier
-    + max-over-ranks timing, the `dist` diagnostics.  What it does NOT cover: RCCL at world > 1, xGMI, any throughput figure."""
+def test_bench_runs_eight_ranks_of_512_on_one_gpu_config3_rehearsal(share_gpu=False):
+    """Config 3 as the driver launches it (`torchrun --nproc-per-node 8 bench.py --gpus 8 --global-batch 4096 ...`, 8 x 512 = global batch 4096, one
+    gradient all-reduce per step): eight ranks, rank r on device r (RCCL, persistent kernels on every rank); it needs the 8 GPUs of config 3 and skips
+    before it starts anything without them.  What it covers: the command line, rank / shard arithmetic, eight B = 512 solves and reverse sweeps, the
+    8-way all-reduce of the 166,418-float buffer, the barrier + max-over-ranks timing, the `dist` diagnostics.  Not: any throughput figure.
+    share_gpu=True is the one-device rig of the same run (`--share-gpu`: all eight ranks on device 0, gloo + the one-shot collective over eight
+    peer-mapped windows, RCCL refusing two ranks on one device) -- nine processes on one GPU, so the suite does not run it; its assertions are kept
+    for a hand run on a device that may hold them."""
     import json
     import socket
     import subprocess
     import sys
+    if not share_gpu:
+        _need_gpus_for_ranks(8)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     with socket.socket() as so:
         so.bind(("127.0.0.1", 0))
         port = so.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--share-gpu", "--global-batch", "4096", "--no-cpu-baseline", "--no-extras"]
+           os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--global-batch", "4096", "--no-cpu-baseline", "--no-extras"]
+    cmd += ["--share-gpu"] if share_gpu else []
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     o = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     d = o["dist"]
     print(json.dumps({k: o[k] for k in ("value", "ms_per_step", "mean_nfe", "n_gpus", "scaling")}), d)
     assert o["n_gpus"] == 8 and o["scaling"] == "strong" and o["config"]["global_batch"] == 4096 and o["value"] > 0
-    assert "one-shot" in d["collective_path"] and d["allreduce_floats"] == 166418 and len(d["nfe_per_rank"]) == 8
+    assert d["allreduce_floats"] == 166418 and len(d["nfe_per_rank"]) == 8
     assert all(n > 0 for n in d["nfe_per_rank"])
-    # eight persistent 224-workgroup kernels cannot be co-resident on the 256 CUs of ONE device: the rig runs these ranks launch by launch (7 launches per
-    # attempted step, stated in the line) -- a rank that owns its GPU keeps the one-launch kernels; persist_fallback_count is then 0 by construction
-    assert "persistent kernels OFF" in o["rig"] and d["launches_per_attempt_per_rank"] == [7] * 8 and d["persist_fallback_count_per_rank"] == [0] * 8
+    if share_gpu:
+        # eight persistent 224-workgroup kernels cannot be co-resident on the 256 CUs of ONE device: the rig runs these ranks launch by launch (7 launches per
+        # attempted step, stated in the line); persist_fallback_count is then 0 by construction
+        assert "one-shot" in d["collective_path"]
+        assert "persistent kernels OFF" in o["rig"] and d["launches_per_attempt_per_rank"] == [7] * 8 and d["persist_fallback_count_per_rank"] == [0] * 8
+    else:
+        # a rank that owns its GPU: RCCL, no rig, and the one-launch persistent kernels on every rank with no fallback
+        assert o["rig"] is None and d["collective_library"] and d["collective_fallback"] is None
+        assert not o["persist_fallback"] and d["launches_per_attempt_per_rank"] == [1] * 8 and d["persist_fallback_count_per_rank"] == [0] * 8
     assert np.isfinite(o["final_loss"])
 
 
