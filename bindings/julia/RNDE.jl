@@ -288,6 +288,21 @@ struct NsdeConfig   # mirrors rnde_nsde_config
     stability_size::Float32      # RNDE_REG_STIFF: 0 = alg_stability_size(SOSRI2()) = 10.6
 end
 
+# The leading element-wise map of a dynamics chain (include/rnde.h: rnde_pre_act): `x -> tanh.(x)` (experiments/latent_ode.jl:114) or `x -> x .^ 3`
+# (experiments/sde_toy_problem.jl:45), recognised by its values at fixed points -- the rule of regneuralde_jl_amd/layers.py::pre_act_of.  Anything else is
+# refused: a map the kernels do not apply must not be replaced by another one silently.
+const PRE_NONE, PRE_TANH, PRE_CUBE = Int32(0), Int32(1), Int32(2)
+# Same probes, same test as the Python rule: Float64 points, each value within 1e-9 relative (of max(1, |want|)) of the map's value there.
+const _PRE_PROBES = Float64[-1.5, -0.3, 0.0, 0.7, 2.0]
+_pre_match(v, want) = all(abs(Float64(a) - b) <= 1e-9 * max(1.0, abs(b)) for (a, b) in zip(v, want))
+function pre_act_code(l)
+    v = try l(_PRE_PROBES) catch; nothing end
+    v isa AbstractVector && length(v) == length(_PRE_PROBES) || error("RNDE: the leading element of the chain is not an element-wise map; got ", l)
+    _pre_match(v, tanh.(_PRE_PROBES)) && return PRE_TANH
+    _pre_match(v, _PRE_PROBES .^ 3) && return PRE_CUBE
+    error("RNDE: the leading element of the chain is neither tanh nor x -> x .^ 3 (the maps the kernels apply); got ", l)
+end
+
 mutable struct NsdeHandle
     ptr::Ptr{Cvoid}
     cfg::NsdeConfig
@@ -421,6 +436,13 @@ rnde_nsde_solve_saveat(h::NsdeHandle, x::TrackedArray, p::TrackedArray, tspan, s
 end
 
 # config from the two Flux chains of TrackedNeuralDSDE (neural_sde.jl:13-41): Dense sizes and activations, tolerances from kwargs
+# the chains' leading element-wise maps (PRE_NONE / PRE_TANH / PRE_CUBE) of a handle that holds no tape
+function nsde_set_pre_act!(h::NsdeHandle, drift_pre::Integer, diff_pre::Integer)
+    st = ccall((:rnde_nsde_set_pre_act, LIB), Cint, (Ptr{Cvoid}, Int32, Int32), h.ptr, drift_pre, diff_pre)
+    st == 0 || error("rnde_nsde_set_pre_act status $st: ", unsafe_string(ccall((:rnde_nsde_last_error, LIB), Cstring, (Ptr{Cvoid},), h.ptr)))
+    return h
+end
+
 function nsde_config_for(drift_dims::Vector{Int}, drift_acts::Vector{Int}, diff_dims::Vector{Int}, diff_acts::Vector{Int}; max_batch, reltol, abstol,
                          regularize, solver = 0, max_attempts = 256, device = 0)
     t9(v) = ntuple(i -> Int32(i <= length(v) ? v[i] : 0), 9)

@@ -21,16 +21,17 @@ const TSIT5_STABILITY_SIZE = 3.5068      # OrdinaryDiffEq.alg_stability_size(Tsi
 
 # Dense sizes / activations of the dynamics (TDChain or Chain of Dense layers; a leading `x -> tanh.(x)` is latent_ode.jl:114's pre-activation).
 # Anything the library cannot represent is REFUSED here -- a layer that is silently skipped would integrate another vector field:
-# every layer must be a Flux.Dense with tanh or identity, except ONE leading element-wise function that is tanh (checked on a probe vector).
+# every layer must be a Flux.Dense with tanh or identity, except ONE leading element-wise function that is tanh or the cube (RNDE.pre_act_code).
 _act_code(σ) = σ === tanh ? 1 : (σ === identity ? 0 : error("RNDE: Dense activation ", σ, " is not served (tanh / identity)"))
 _is_tanh_layer(l) = !(l isa Flux.Dense) && (v = Float32[-0.7, 0.1, 0.9]; try l(v) ≈ tanh.(v) catch; false end)
 function _dense_layout(model)
     layers = collect(model.layers)
     td = model isa TDChain
-    pre = !(first(layers) isa Flux.Dense)
-    pre && (!td && _is_tanh_layer(first(layers)) ||
-            error("RNDE: the dynamics may start with ONE element-wise tanh (experiments/latent_ode.jl:114), nothing else in front of the Dense layers; got ", first(layers)))
-    ds = layers[(pre ? 2 : 1):end]
+    lead = !(first(layers) isa Flux.Dense)
+    lead && td && error("RNDE: a TDChain starts with a Dense layer; got ", first(layers))
+    # one leading tanh (latent_ode.jl:114) or cube (sde_toy_problem.jl:45); RNDE.pre_act_code refuses anything else
+    pre = !lead ? RNDE.PRE_NONE : (_is_tanh_layer(first(layers)) ? RNDE.PRE_TANH : RNDE.pre_act_code(first(layers)))
+    ds = layers[(lead ? 2 : 1):end]
     all(l -> l isa Flux.Dense, ds) || error("RNDE: the dynamics must be a chain of Flux.Dense layers; got ", [typeof(l) for l in ds if !(l isa Flux.Dense)])
     dims = Int[size(ds[1].W, 2) - (td ? 1 : 0)]
     acts = Int[]

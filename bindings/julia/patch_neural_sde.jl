@@ -11,17 +11,19 @@ const SOSRI2_STABILITY_SIZE = 10.6       # StochasticDiffEq.alg_stability_size(S
 const _SDE_SOLVERS = Dict(:SOSRI => 0, :SRIW1 => 1, :SOSRI2 => 2)      # rnde_sde_solver (include/rnde.h)
 const RNDE_SDE_CALLS = Ref(0)      # one Philox stream per call: seed = a counter (pass `seed = ...` for a reproducible run)
 
-# drift / diffusion as the library holds them: chains of Flux.Dense (tanh / identity), nothing else.  A layer that cannot be represented is REFUSED,
-# never skipped (experiments/sde_toy_problem.jl's drift starts with `x -> x .^ 3`: that script is not served by this patch and now says so).
+# drift / diffusion as the library holds them: chains of Flux.Dense (tanh / identity) after at most ONE leading element-wise map, tanh or the cube
+# (experiments/sde_toy_problem.jl:45: `x -> x .^ 3`, recognised by RNDE.pre_act_code).  A layer that cannot be represented is REFUSED, never skipped.
 function _chain_layout(model)
     ls = model isa Flux.Dense ? [model] : collect(model.layers)
+    pre = first(ls) isa Flux.Dense ? RNDE.PRE_NONE : RNDE.pre_act_code(first(ls))
+    ls = ls[(pre == RNDE.PRE_NONE ? 1 : 2):end]
     all(l -> l isa Flux.Dense, ls) || error("RNDE: drift and diffusion of the SDE layer must be chains of Flux.Dense layers; got ", [typeof(l) for l in ls if !(l isa Flux.Dense)])
     dims = Int[size(ls[1].W, 2)]; acts = Int[]
     for l in ls
         push!(dims, size(l.W, 1))
         push!(acts, l.σ === tanh ? 1 : (l.σ === identity ? 0 : error("RNDE: Dense activation ", l.σ, " is not served (tanh / identity)")))
     end
-    return dims, acts
+    return dims, acts, pre
 end
 
 # solver + regularize codes of include/rnde.h from the solver object the layer holds (n.args: SOSRI() / AutoSOSRI2(SOSRI2()), mnist_nsde.jl:49,:60),
@@ -41,9 +43,10 @@ function rnde_handle(n::TrackedNeuralDSDE, B::Int, func)
     solver, reg = _sde_codes(n, func)
     tab = get!(() -> Dict{Tuple{Int,Int},RNDE.NsdeHandle}(), RNDE_SDE_HANDLES, n)
     get!(tab, (B, reg)) do
-        d1, a1 = _chain_layout(n.model1); d2, a2 = _chain_layout(n.model2)
-        RNDE.NsdeHandle(RNDE.nsde_config_for(d1, a1, d2, a2; max_batch = B, reltol = Float32(get(n.kwargs, :reltol, 1f-2)),
-                                             abstol = Float32(get(n.kwargs, :abstol, 1f-2)), regularize = reg, solver = solver))
+        d1, a1, pre1 = _chain_layout(n.model1); d2, a2, pre2 = _chain_layout(n.model2)
+        RNDE.nsde_set_pre_act!(RNDE.NsdeHandle(RNDE.nsde_config_for(d1, a1, d2, a2; max_batch = B, reltol = Float32(get(n.kwargs, :reltol, 1f-2)),
+                                                                     abstol = Float32(get(n.kwargs, :abstol, 1f-2)), regularize = reg, solver = solver)),
+                               pre1, pre2)
     end
 end
 

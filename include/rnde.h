@@ -47,6 +47,11 @@ typedef enum {
 } rnde_status;
 
 typedef enum { RNDE_ACT_IDENTITY = 0, RNDE_ACT_TANH = 1 } rnde_act;
+/* rnde_node_config.pre_act (and rnde_nsde_set_pre_act): the element-wise map in front of the first Dense layer.  RNDE_PRE_TANH is the
+ * leading tanh of experiments/latent_ode.jl:114, RNDE_PRE_CUBE the leading x -> x .^ 3 of experiments/sde_toy_problem.jl:45.  Any other value
+ * is RNDE_ERR_BAD_ARG at create.  The kernels with compile-time shapes that skip the generic chain evaluation (the SDE layer's 32 -> 64 -> 32
+ * drift, rnde_nsde_config.generic = 0) apply no map: a handle with a nonzero selector runs the generic kernels instead. */
+typedef enum { RNDE_PRE_NONE = 0, RNDE_PRE_TANH = 1, RNDE_PRE_CUBE = 2 } rnde_pre_act;
 /* RNDE_SOLVER_TSIT5: every reference call site (experiments/mnist_node.jl:62-103, latent_ode.jl:131-136), all engines.
  * RNDE_SOLVER_DP5: Dormand-Prince 5(4), the second 7-stage first-same-as-last pair, through the tableau-as-data kernels of the chain
  * engine (Dense chains of width <= 64; callbacks none / EEst*dt): there a pair of that shape is a table, not a kernel. */
@@ -67,7 +72,7 @@ typedef struct {
     int32_t dims[RNDE_MAX_LAYERS + 1]; /* dims[0] = dims[n_layers] = D */
     int32_t act[RNDE_MAX_LAYERS];
     int32_t time_dep;
-    int32_t pre_act;       /* leading tanh (experiments/latent_ode.jl:114) */
+    int32_t pre_act;       /* rnde_pre_act: leading tanh (experiments/latent_ode.jl:114) or cube (sde_toy_problem.jl:45) */
     int32_t max_batch;     /* largest B any call will pass */
     int32_t solver;        /* rnde_solver */
     float   reltol, abstol;
@@ -281,6 +286,13 @@ rnde_status rnde_momentum_step_scaled(float* p_dev, const float* g_dev, float* v
  * scaled by gscale first (1 / world after a sum-all-reduce).  t = 1, 2, ... is the step being taken; m, v start at zero. */
 rnde_status rnde_adam_step(float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t len, int64_t t, float eta, float beta1,
                            float beta2, float eps, float gscale, void* stream);
+/* Flux.Optimise.AdaBelief(eta, (beta1, beta2)) (the optimiser of reference experiments/sde_toy_problem.jl:65, Flux 0.11.6 as pinned by the
+ * reference's Manifest) on one flat parameter group, one launch, g scaled by gscale first:
+ *     m = beta1 m + (1 - beta1) g ;  s = beta2 s + (1 - beta2) (g - m)^2 ;  p -= eta m / (sqrt(s) + eps)
+ * with the m of this step inside (g - m), no bias correction, eps = 1e-8 there.  [RECALL] Flux 0.11.6's apply! for AdaBelief, as recalled:
+ * its source is not available offline to check against.  m, s start at zero.  No handle, asynchronous. */
+rnde_status rnde_adabelief_step(float* p_dev, const float* g_dev, float* m_dev, float* s_dev, int64_t len, float eta, float beta1, float beta2,
+                                float eps, float gscale, void* stream);
 
 /* ======================================================================================================================
  * Data parallelism: the one collective of a training step.  The reference is single-process; with the
@@ -451,6 +463,27 @@ rnde_status rnde_nsde_classifier_grad(rnde_nsde* h, const float* x_dev, const fl
                                       int32_t B, int32_t n_classes, float t0, float t1, const float* noise_dev, int32_t n_pool,
                                       uint64_t seed, float lambda, float* p2_bar_dev, float* p3_bar_dev, float* x_bar_dev,
                                       float* ce_out_dev, float* reg_out_host, int64_t* nfe1_out, int64_t* nfe2_out, void* stream);
+/* The moment-matching loss of reference experiments/sde_toy_problem.jl:27-40 on a D x T x B array of saved states (B trajectories):
+ *     mu = mean over b of u[:, :, b],  var = sum over b of (u[:, :, b] - mu)^2 / (B - 1)   (Julia's var(...; dims = 3, mean = means): unbiased)
+ *     loss_out_dev[0] = l2_means = mean((data_mean - mu)^2),  loss_out_dev[1] = l2_vars = mean((data_var - var)^2)   (means over D x T)
+ * data_mean, data_var: D x T.  u_bar_dev (may be NULL): D x T x B, the cotangent of l2_means + l2_vars with respect to u_saved.  B >= 2.
+ * Every sum runs in a fixed order (results are the same bits run to run).  ONE launch of one workgroup, asynchronous on `stream`; no handle.
+ * That workgroup walks the D x T pairs serially (512 at a time): right for the toy's 2 x 30 x 100, slow for large arrays. */
+rnde_status rnde_moment_loss(const float* u_saved_dev, const float* data_mean_dev, const float* data_var_dev, int32_t D, int32_t T, int32_t B,
+                             float* loss_out_dev, float* u_bar_dev, void* stream);
+/* The training step of reference experiments/sde_toy_problem.jl (loss_function :27-40 and Tracker.gradient) in one call:
+ *     u = TrackedNeuralDSDE(x, p) at the n_saveat times of saveat_host  ->  rnde_moment_loss  ->  loss = l2_means + l2_vars + c * sum(sv.saveval)
+ * = rnde_nsde_forward_saveat (taped; noise as there) + rnde_moment_loss + rnde_nsde_backward_async (every saved value's cotangent is c when
+ * c != 0 and the handle records a callback).  Outputs: p_bar_dev (P), x_bar_dev (D x B, may be NULL), loss_out_dev[2] = (l2_means, l2_vars)
+ * (device, stream order), *reg_out_host = c * sum(saveval), *nfe1_out, *nfe2_out (host, valid on return). */
+rnde_status rnde_nsde_moment_grad(rnde_nsde* h, const float* x_dev, const float* p_dev, int32_t B, float t0, float t1, const float* noise_dev,
+                                  int32_t n_pool, uint64_t seed, const float* saveat_host, int32_t n_saveat, const float* data_mean_dev,
+                                  const float* data_var_dev, float c, float* p_bar_dev, float* x_bar_dev, float* loss_out_dev, float* reg_out_host,
+                                  int64_t* nfe1_out, int64_t* nfe2_out, void* stream);
+/* The pre-activation (rnde_pre_act) of the drift and of the diffusion chain; new handles have none.  Allowed only while the handle holds no
+ * tape (RNDE_ERR_BAD_ARG otherwise: the tape's reverse pass must see the map its forward ran).  Applies to every later solve and to
+ * rnde_nsde_debug_attempt.  A nonzero selector takes the handle off the kernels with the reference's shape as compile-time constants. */
+rnde_status rnde_nsde_set_pre_act(rnde_nsde* h, int32_t drift_pre, int32_t diff_pre);
 /* Per-attempt log of the last forward: 4 floats per attempt (t, dt, EEst, accepted); draws_out = noise draws consumed. */
 rnde_status rnde_nsde_steps(rnde_nsde* h, float* steps_host, int32_t capacity, int32_t* n_attempts_out, int32_t* draws_out);
 /* Kernel-level parity entry: ONE attempted step from (uprev, dt, dW, dZ), all D x B device arrays: kg_out_dev receives

@@ -220,6 +220,35 @@ class FluxADAM:
             p.grad = None
 
 
+class FluxAdaBelief:
+    """Flux.Optimise.AdaBelief(eta, (beta1, beta2)) (reference experiments/sde_toy_problem.jl:65: AdaBelief(0.01)), group by group, one launch per
+    group through the C ABI (rnde_adabelief_step): m = beta1 m + (1 - beta1) g; s = beta2 s + (1 - beta2) (g - m)^2; p -= eta m / (sqrt(s) + eps),
+    no bias correction (Flux 0.11.6 as recalled, include/rnde.h)."""
+
+    def __init__(self, params, eta=0.001, beta=(0.9, 0.999), eps=1.0e-8):
+        self.params = [p for p in params if p.numel() > 0]
+        self.eta, self.beta, self.eps = eta, beta, eps
+        self.m = [torch.zeros_like(p) for p in self.params]
+        self.s = [torch.zeros_like(p) for p in self.params]
+
+    @torch.no_grad()
+    def step(self, grad_scale=1.0):
+        import ctypes as C
+        from . import _lib
+        for i, p in enumerate(self.params):
+            g = p.grad
+            if g is None:
+                continue
+            if not p.is_cuda:
+                raise RuntimeError("FluxAdaBelief runs on the device only")
+            g = g.contiguous()
+            st = _lib.lib().rnde_adabelief_step(p.data_ptr(), g.data_ptr(), self.m[i].data_ptr(), self.s[i].data_ptr(), p.numel(), self.eta,
+                                                self.beta[0], self.beta[1], self.eps, float(grad_scale),
+                                                C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream))
+            _lib.check(None, st)
+            p.grad = None
+
+
 def sample_tspan_ubound(b=0.5, generator=None):
     """STEER (experiments/mnist_node.jl:104-105,:133): integrate to t1 ~ U(1 - b, 1 + b) instead of 1."""
     r = float(torch.rand((), generator=generator))

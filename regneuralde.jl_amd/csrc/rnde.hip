@@ -35,7 +35,7 @@ StepParams make_params(rnde_node* h, const float* x, int B, float t0, float t1, 
 static_assert(kCMaxL == RNDE_MAX_LAYERS, "chain engine layer limit");
 static bool chain_geo(const rnde_node_config* c, ChainGeo& G) {
     G = ChainGeo{};
-    G.n_layers = c->n_layers; G.time_dep = c->time_dep ? 1 : 0; G.pre_act = c->pre_act ? 1 : 0;
+    G.n_layers = c->n_layers; G.time_dep = c->time_dep ? 1 : 0; G.pre_act = c->pre_act;   // rnde_pre_act, checked by rnde_node_create
     int po = 0, fo = 0, bo = 0, to = 0;
     for (int l = 0; l <= c->n_layers; ++l) {
         if (c->dims[l] < 1 || c->dims[l] > 4 * kCMaxKs) return false;
@@ -318,6 +318,9 @@ extern "C" rnde_status rnde_node_create(const rnde_node_config* c, rnde_node** o
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= c->device) { g_create_err = "no HIP device"; return RNDE_ERR_NO_DEVICE; }
     if ((c->solver != RNDE_SOLVER_TSIT5 && c->solver != RNDE_SOLVER_DP5 && c->solver != RNDE_SOLVER_DOP853) || c->n_layers < 1 || c->n_layers > RNDE_MAX_LAYERS || c->dims[0] != c->dims[c->n_layers]) {
         g_create_err = "unsupported configuration: Tsit5 (or DP5) over a Dense chain with dims[0] == dims[n_layers]"; return RNDE_ERR_BAD_ARG;
+    }
+    if (c->pre_act != RNDE_PRE_NONE && c->pre_act != RNDE_PRE_TANH && c->pre_act != RNDE_PRE_CUBE) {
+        g_create_err = "pre_act: RNDE_PRE_NONE, RNDE_PRE_TANH or RNDE_PRE_CUBE"; return RNDE_ERR_BAD_ARG;
     }
     const bool mnist_form = c->n_layers == 2 && c->time_dep && !c->pre_act && c->act[0] == RNDE_ACT_TANH;
     if ((c->solver == RNDE_SOLVER_DP5 || c->solver == RNDE_SOLVER_DOP853) && ((mnist_form && c->col_tile != 65) || c->col_tile == 64 || c->regularize >= RNDE_REG_STIFF)) {

@@ -73,7 +73,7 @@ __device__ __forceinline__ void chain_fbwd(const BChainParams& Q, const float* F
     const ChainGeo& G = Q.G;
     float a[kCMaxKs];
 #pragma unroll
-    for (int k = 0; k < kCMaxKs; ++k) a[k] = (k < NKD) ? (G.pre_act ? tanh_fast(g[k < NKD ? k : 0]) : g[k < NKD ? k : 0]) : 0.f;
+    for (int k = 0; k < kCMaxKs; ++k) a[k] = (k < NKD) ? pre_fwd(G.pre_act, g[k < NKD ? k : 0]) : 0.f;
     // forward recompute: every layer's input goes to the slab; the last layer's output is kout (taped)
 #pragma unroll 1
     for (int l = 0; l < G.n_layers; ++l) {
@@ -129,9 +129,7 @@ __device__ __forceinline__ void chain_fbwd(const BChainParams& Q, const float* F
     }
 #pragma unroll
     for (int k = 0; k < NKD; ++k) {
-        float v = ab[k];
-        if (G.pre_act) { const float a0 = tanh_fast(g[k]); v *= (1.f - a0 * a0); }
-        gb[k] = v;
+        gb[k] = pre_bwd(G.pre_act, g[k], ab[k]);
     }
     tau += tl;
 }

@@ -108,8 +108,7 @@ __device__ __forceinline__ void mw_fbwd(const MwGeo& G, const float* FRt, const 
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
         float v = ((tid + 256 * r) >> 4) < 16 * G.mt[0] ? Zc[tid + 256 * r] : 0.f;   // (rows past the last tile were never written)
-        if (G.pre_act) { const float a0 = tanh_fast(gin[r]); v *= (1.f - a0 * a0); }
-        gb[r] = v;
+        gb[r] = pre_bwd(G.pre_act, gin[r], v);
     }
     __syncthreads();
     tau += tl;
@@ -187,8 +186,7 @@ __device__ __forceinline__ void mw_fbwd_lat(const MwGeo& G, const LatWeightsT& W
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
         float v = ((tid + 256 * r) >> 4) < 16 * lat_mt(0) ? Zc[tid + 256 * r] : 0.f;
-        if (G.pre_act) { const float a0 = tanh_fast(gin[r]); v *= (1.f - a0 * a0); }
-        gb[r] = v;
+        gb[r] = pre_bwd(G.pre_act, gin[r], v);
     }
     __syncthreads();
 }

@@ -307,7 +307,7 @@ template <int NKD, int ALT = 0>
 __device__ __forceinline__ void chain_eval(const ChainGeo& G, const float* FR, const float* BF, float ts, const float (&g)[NKD], float (&out)[NKD], int lane, unsigned long long* dbg = nullptr) {
     float a[kCMaxKs];
 #pragma unroll
-    for (int k = 0; k < kCMaxKs; ++k) a[k] = (k < NKD) ? (G.pre_act ? tanh_fast(g[k < NKD ? k : 0]) : g[k < NKD ? k : 0]) : 0.f;
+    for (int k = 0; k < kCMaxKs; ++k) a[k] = (k < NKD) ? pre_fwd(G.pre_act, g[k < NKD ? k : 0]) : 0.f;
 #pragma unroll 1
     for (int l = 0; l < G.n_layers; ++l) chain_layer<ALT>(G, FR, BF, l, ts, a, lane, dbg);
 #pragma unroll

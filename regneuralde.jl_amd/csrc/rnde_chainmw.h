@@ -239,7 +239,7 @@ __device__ __forceinline__ void mw_eval(const MwGeo& G, const float* FRm, const 
                                         unsigned long long* dbg = nullptr) {
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
-        const float a = G.pre_act ? tanh_fast(gv[r]) : gv[r];
+        const float a = pre_fwd(G.pre_act, gv[r]);
         XB[tid + 256 * r] = a;
         if (sl) sl[(size_t)G.hrow[0] * 64 + tid + 256 * r] = a;
     }
@@ -289,7 +289,7 @@ __device__ __forceinline__ void mw_eval_lat(const MwGeo& G, const LatWeights& W,
                                             float* __restrict__ sl, int tid, int wave, int lane) {
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
-        const float a = G.pre_act ? tanh_fast(gv[r]) : gv[r];
+        const float a = pre_fwd(G.pre_act, gv[r]);
         XB[tid + 256 * r] = a;
         if (sl) sl[(size_t)G.hrow[0] * 64 + tid + 256 * r] = a;
     }

@@ -359,4 +359,14 @@ __device__ __forceinline__ f32x2 tanh_fast2(f32x2 x) {
 }
 __device__ __forceinline__ float act_apply_fast(int act, float v) { return act ? tanh_fast(v) : v; }
 
+// The element-wise map in front of a Dense chain (rnde_node_config.pre_act, include/rnde.h: rnde_pre_act): 0 none, 1 tanh
+// (experiments/latent_ode.jl:114), 2 the cube x .^ 3 (experiments/sde_toy_problem.jl:45).  pre_fwd is what the first layer reads
+// (and what the reverse pass tapes as that layer's input); pre_bwd multiplies a cotangent of that value by the map's derivative at g.
+__device__ __forceinline__ float pre_fwd(int sel, float g) { return sel == 1 ? tanh_fast(g) : (sel == 2 ? g * g * g : g); }
+__device__ __forceinline__ float pre_bwd(int sel, float g, float v) {
+    if (sel == 1) { const float a = tanh_fast(g); return v * (1.f - a * a); }
+    if (sel == 2) return v * (3.f * g * g);
+    return v;
+}
+
 }  // namespace rnde

@@ -7,6 +7,7 @@
 #include "rnde_sde.h"
 #include "rnde_sdemw.h"
 #include "rnde_head.h"
+#include "rnde_moment.h"
 
 #include <algorithm>
 #include <cmath>
@@ -34,6 +35,7 @@ struct rnde_nsde {
     unsigned *xcc = nullptr, *h_xcc = nullptr;
     int pool_pred = 0;      // library noise: draws the next solve's pool is filled with (0 = all of max_attempts + 1); grows back on demand
     int fix = 0;   // 1: the reference's own shape (drift 8 -> 16 -> 8 k-steps, one-layer diffusion): kernels with compile-time shapes
+    int fix_shape = 0, mw_shape = 0;   // what fix / mw are without a pre-activation (those kernels apply none: rnde_nsde_set_pre_act)
     ChainGeo Gf{}, Gg{};
     SriTableau T{};
     float order = 1.5f, beta1 = 0, beta2 = 0, gamma = 0, qmin = 0, qmax = 0, qoldinit = 0, delta = 0;
@@ -84,11 +86,11 @@ extern "C" int32_t rnde_nsde_param_count(const rnde_nsde_config* c, int32_t* len
     return a + b;
 }
 
-// geometry of one time-independent Dense chain for the fragment engine (as chain_geo in rnde.hip)
-static bool sde_geo(int n_layers, const int32_t* dims, const int32_t* act, ChainGeo& G) {
+// geometry of one time-independent Dense chain for the fragment engine (as chain_geo in rnde.hip); pre = rnde_pre_act
+static bool sde_geo(int n_layers, const int32_t* dims, const int32_t* act, int pre, ChainGeo& G) {
     G = ChainGeo{};
     if (n_layers < 1 || n_layers > kCMaxL) return false;
-    G.n_layers = n_layers; G.time_dep = 0; G.pre_act = 0;
+    G.n_layers = n_layers; G.time_dep = 0; G.pre_act = pre;
     int po = 0, fo = 0, bo = 0, to = 0;
     for (int l = 0; l <= n_layers; ++l) {
         if (dims[l] < 1 || dims[l] > 4 * kCMaxKs) return false;
@@ -145,7 +147,7 @@ extern "C" rnde_status rnde_nsde_create(const rnde_nsde_config* c, rnde_nsde** o
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= c->device) { g_nsde_create_err = "no HIP device"; return RNDE_ERR_NO_DEVICE; }
     ChainGeo Gf, Gg;
-    if (!sde_geo(c->drift_layers, c->drift_dims, c->drift_act, Gf) || !sde_geo(c->diff_layers, c->diff_dims, c->diff_act, Gg)) {
+    if (!sde_geo(c->drift_layers, c->drift_dims, c->drift_act, RNDE_PRE_NONE, Gf) || !sde_geo(c->diff_layers, c->diff_dims, c->diff_act, RNDE_PRE_NONE, Gg)) {
         g_nsde_create_err = "unsupported networks: Dense chains of 1..8 layers, every width 1..64"; return RNDE_ERR_BAD_ARG;
     }
     const int D = c->drift_dims[0];
@@ -169,6 +171,7 @@ extern "C" rnde_status rnde_nsde_create(const rnde_nsde_config* c, rnde_nsde** o
     h->NKD = D <= 16 ? 4 : (D <= 32 ? 8 : 16);
     h->fix = (c->drift_layers == 2 && c->diff_layers == 1 && Gf.nks[0] == 8 && Gf.nks[1] == 16 && c->generic == 0) ? 1 : 0;
     { const char* e = getenv("RNDE_SDE_MW"); h->mw = (h->fix && !(e && e[0] == '0')) ? 1 : 0; }
+    h->fix_shape = h->fix; h->mw_shape = h->mw;
     float ddef = 1.f;
     sde_tableau(c->solver, h->T, ddef);
     h->order = 1.5f;
@@ -699,6 +702,79 @@ extern "C" rnde_status rnde_nsde_classifier_grad(rnde_nsde* h, const float* x_de
     }
     if (reg_out_host) *reg_out_host = (float)reg;
     return nsde_backward_impl(h, ubar, regularize ? h->cg_sv.data() : nullptr, x_bar_dev, p2_bar_dev, stream, false);
+}
+
+// The leading element-wise map of each chain (include/rnde.h: rnde_pre_act; experiments/sde_toy_problem.jl:45 drifts through x -> x .^ 3).  The generic
+// kernels read it from the geometry (chain_eval / chain_fbwd: pre_fwd, pre_bwd); the kernels with the reference's shape as compile-time constants
+// (FIXH = 16: sde_layer_fixed, and the four-waves-per-tile rnde_sdemw.h) apply none, so a nonzero selector takes the handle off them.
+extern "C" rnde_status rnde_nsde_set_pre_act(rnde_nsde* h, int32_t drift_pre, int32_t diff_pre) {
+    if (!h) return RNDE_ERR_BAD_ARG;
+    auto ok = [](int32_t v) { return v == RNDE_PRE_NONE || v == RNDE_PRE_TANH || v == RNDE_PRE_CUBE; };
+    if (!ok(drift_pre) || !ok(diff_pre)) { h->err = "pre_act: RNDE_PRE_NONE, RNDE_PRE_TANH or RNDE_PRE_CUBE"; return RNDE_ERR_BAD_ARG; }
+    if (h->have_tape) { h->err = "rnde_nsde_set_pre_act while a tape is held: run or release the reverse pass first"; return RNDE_ERR_BAD_ARG; }
+    h->Gf.pre_act = drift_pre; h->Gg.pre_act = diff_pre;
+    const bool plain = drift_pre == RNDE_PRE_NONE && diff_pre == RNDE_PRE_NONE;
+    h->fix = plain ? h->fix_shape : 0;
+    h->mw = plain ? h->mw_shape : 0;
+    return RNDE_OK;
+}
+
+extern "C" rnde_status rnde_moment_loss(const float* u_saved_dev, const float* data_mean_dev, const float* data_var_dev, int32_t D, int32_t T, int32_t B,
+                                        float* loss_out_dev, float* u_bar_dev, void* stream) {
+    if (!u_saved_dev || !data_mean_dev || !data_var_dev || !loss_out_dev || D < 1 || T < 1 || B < 2) return RNDE_ERR_BAD_ARG;
+    hipLaunchKernelGGL(rnde_moment_loss_kernel, dim3(1), dim3(kMomThreads), 0, (hipStream_t)stream, u_saved_dev, data_mean_dev, data_var_dev, D * T, B,
+                       loss_out_dev, u_bar_dev);
+    return hipGetLastError() == hipSuccess ? RNDE_OK : RNDE_ERR_HIP;
+}
+
+extern "C" rnde_status rnde_adabelief_step(float* p_dev, const float* g_dev, float* m_dev, float* s_dev, int64_t len, float eta, float beta1, float beta2,
+                                           float eps, float gscale, void* stream) {
+    if (!p_dev || !g_dev || !m_dev || !s_dev || len < 0) return RNDE_ERR_BAD_ARG;
+    if (len == 0) return RNDE_OK;
+    hipLaunchKernelGGL(rnde_adabelief_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p_dev, g_dev, m_dev, s_dev,
+                       (long long)len, gscale, eta, beta1, beta2, eps);
+    return hipGetLastError() == hipSuccess ? RNDE_OK : RNDE_ERR_HIP;
+}
+
+// The toy experiment's training step (experiments/sde_toy_problem.jl: loss_function :27-40 + Tracker.gradient) in ONE call: the taped saveat solve, the
+// moment loss queued before the forward's host wait (as rnde_nsde_classifier_grad queues the head), then the reverse sweep.
+extern "C" rnde_status rnde_nsde_moment_grad(rnde_nsde* h, const float* x_dev, const float* p_dev, int32_t B, float t0, float t1, const float* noise_dev,
+                                             int32_t n_pool, uint64_t seed, const float* saveat_host, int32_t n_saveat, const float* data_mean_dev,
+                                             const float* data_var_dev, float c, float* p_bar_dev, float* x_bar_dev, float* loss_out_dev, float* reg_out_host,
+                                             int64_t* nfe1_out, int64_t* nfe2_out, void* stream) {
+    if (!h || !x_dev || !p_dev || !saveat_host || n_saveat < 1 || !data_mean_dev || !data_var_dev || !p_bar_dev || !loss_out_dev) return RNDE_ERR_BAD_ARG;
+    if (B < 2 || B > h->cfg.max_batch) { h->err = "moment loss: 2 <= B <= max_batch"; return RNDE_ERR_BAD_ARG; }
+    SCHK(h, hipSetDevice(h->cfg.device));
+    const size_t A = (size_t)h->D * n_saveat * B, X = (size_t)h->D * B;
+    const size_t need = 2 * A + (x_bar_dev ? 0 : X);
+    if (h->cg_ws_floats < need) {
+        if (h->cg_ws) (void)hipFree(h->cg_ws);
+        h->cg_ws = nullptr; h->cg_ws_floats = 0;
+        SCHK(h, hipMalloc((void**)&h->cg_ws, need * 4));
+        h->cg_ws_floats = need;
+    }
+    if (!h->ev_host) SCHK(h, hipEventCreateWithFlags(&h->ev_host, hipEventDisableTiming));
+    float* u = h->cg_ws; float* ubar = h->cg_ws + A;
+    float* xbar = x_bar_dev ? x_bar_dev : h->cg_ws + 2 * A;
+    h->cg_sv.resize((size_t)h->cfg.max_attempts + 1);
+    int32_t nsv = 0;
+    const int32_t D = h->D;
+    h->after_solve = [&](hipStream_t s) -> rnde_status {
+        return rnde_moment_loss(u, data_mean_dev, data_var_dev, D, n_saveat, B, loss_out_dev, ubar, s);
+    };
+    rnde_status st = nsde_forward_impl(h, x_dev, p_dev, B, t0, t1, noise_dev, n_pool, seed, nullptr, 0, nullptr, nfe1_out, nfe2_out, h->cg_sv.data(), &nsv, 1,
+                                       stream, saveat_host, n_saveat, u);
+    h->after_solve = nullptr;
+    if (st != RNDE_OK) return st;
+    double reg = 0.0;
+    const bool regularize = c != 0.f && nsv > 0 && h->cfg.regularize != RNDE_REG_NONE;
+    if (regularize) {   // c * sum(sv.saveval) (sde_toy_problem.jl:37): every saved value carries the cotangent c
+        for (int i = 0; i < nsv; ++i) reg += h->cg_sv[i];
+        reg *= (double)c;
+        for (int i = 0; i < nsv; ++i) h->cg_sv[i] = c;
+    }
+    if (reg_out_host) *reg_out_host = (float)reg;
+    return nsde_backward_impl(h, ubar, regularize ? h->cg_sv.data() : nullptr, xbar, p_bar_dev, stream, false);
 }
 
 extern "C" rnde_status rnde_nsde_timing(rnde_nsde* h, float* solve_ms, float* rev_sweep_ms, int32_t* attempts, int32_t* accepted) {

@@ -41,12 +41,48 @@ def MLPDynamics(n_in, hidden, generator=None):
     return TDChain(Dense(n_in + 1, hidden, "tanh", generator), Dense(hidden + 1, n_in, "tanh", generator))
 
 
+# The leading element-wise maps the kernels apply in front of a Dense chain (include/rnde.h: rnde_pre_act), by name
+PRE_ACT = {None: 0, False: 0, "tanh": 1, True: 1, "cube": 2}
+_PRE_PROBES = (-1.5, -0.3, 0.0, 0.7, 2.0)      # (bindings/julia/RNDE.jl::pre_act_code: the same points, fp64, the same pointwise 1e-9 test)
+_PRE_WANT = {"tanh": math.tanh, "cube": lambda v: v * v * v}
+
+
+def pre_act_of(f):
+    """Name of a leading element-wise callable as the reference writes it -- `x -> tanh.(x)` (experiments/latent_ode.jl:114) or `x -> x .^ 3`
+    (experiments/sde_toy_problem.jl:45): its values at a few fixed points are matched against tanh and the cube (the rule node.py::reg_code applies
+    to callbacks; the same rule as bindings/julia/RNDE.jl::pre_act_code).  Raises ValueError for anything else: a map the kernels do not apply must
+    not be replaced by another one silently."""
+    x = torch.tensor(_PRE_PROBES, dtype=torch.float64)
+    try:
+        got = [float(v) for v in torch.as_tensor(f(x), dtype=torch.float64).reshape(-1)]
+    except Exception as e:
+        raise ValueError(f"leading element of the Chain: calling it on a tensor failed ({e})") from e
+    if len(got) == len(_PRE_PROBES):
+        for name, want in _PRE_WANT.items():
+            if all(abs(g - want(p)) <= 1e-9 * max(1.0, abs(want(p))) for g, p in zip(got, _PRE_PROBES)):
+                return name
+    raise ValueError(f"leading element of the Chain is neither tanh nor x -> x ** 3 (the element-wise maps the kernels apply): on {_PRE_PROBES} it "
+                     f"returned {got}")
+
+
 class Chain:
-    """Time-independent Flux.Chain of Dense layers, optional leading tanh (experiments/latent_ode.jl:113-124)."""
+    """Time-independent Flux.Chain of Dense layers, optional leading element-wise map: tanh (experiments/latent_ode.jl:113-124) or the cube
+    (experiments/sde_toy_problem.jl:45).  The map is given as the reference writes it -- a leading callable, Chain(lambda x: x ** 3, Dense(2, 50,
+    "tanh"), Dense(50, 2)) -- or as pre_act = True (tanh) / "tanh" / "cube".  It is kept in `pre_act`, not in `layers` (it has no parameters:
+    destructure and dims() see the Dense layers only)."""
     time_dep = False
 
     def __init__(self, *layers, pre_act=False):
-        self.layers = list(layers)
+        layers = list(layers)
+        if layers and callable(layers[0]) and not isinstance(layers[0], Dense):
+            if pre_act:
+                raise ValueError("Chain: a leading callable and pre_act together")
+            pre_act = pre_act_of(layers.pop(0))
+        if not all(isinstance(l, Dense) for l in layers):
+            raise ValueError("Chain: an optional leading element-wise map (tanh or x -> x ** 3), then Dense layers only")
+        if pre_act not in PRE_ACT:
+            raise ValueError(f"pre_act: one of {list(PRE_ACT)}")
+        self.layers = layers
         self.pre_act = pre_act
 
     def dims(self):

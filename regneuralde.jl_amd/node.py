@@ -21,7 +21,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .layers import destructure
+from .layers import PRE_ACT, destructure
 
 _ACT = {"identity": 0, "tanh": 1}
 _FUNCS = {None: 1, "none": 0, "error_est": 1, "stiff_est": 2, "error_stiff_est": 3, "stiff_est_dt": 4}      # None: the layer's default callback (neural_ode.jl:116)
@@ -228,7 +228,7 @@ class TrackedNeuralODE:
         for i, l in enumerate(self.model.layers):
             cfg.act[i] = _ACT[l.act]
         cfg.time_dep = int(self.time_dep)
-        cfg.pre_act = int(getattr(self.model, "pre_act", False))
+        cfg.pre_act = PRE_ACT[getattr(self.model, "pre_act", False)]
         cfg.max_batch = self.max_batch
         cfg.solver = _lib.ODE_SOLVER[self.solver]
         cfg.reltol = float(self.kwargs.get("reltol", 1e-3))   # OrdinaryDiffEq defaults when not given

@@ -23,17 +23,18 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .layers import Chain, Dense, destructure
+from .layers import PRE_ACT, Chain, Dense, destructure
 from .node import MAX_HANDLES_PER_KEY, SOSRI2_STABILITY_SIZE, SavedValues, _check_f32, _TapeToken, effective_reg, reg_code
 
 _ACT = {"identity": 0, "tanh": 1}
 
 
 class _NsdeHandle:
-    def __init__(self, cfg):
+    def __init__(self, cfg, pre=(0, 0)):
         self.ptr = C.c_void_p()
         _lib.check_nsde(None, _lib.lib().rnde_nsde_create(C.byref(cfg), C.byref(self.ptr)))
         self.busy = False
+        _lib.check_nsde(self.ptr, _lib.lib().rnde_nsde_set_pre_act(self.ptr, *pre))     # the chains' leading element-wise maps (rnde_pre_act)
 
     def __del__(self):
         try:
@@ -155,7 +156,7 @@ class TrackedNeuralDSDE:
                 return h
         if len(hs) >= MAX_HANDLES_PER_KEY:
             raise RuntimeError(f"{len(hs)} taped forwards of this layer are pending without a backward pass")
-        h = _NsdeHandle(self._config(key))
+        h = _NsdeHandle(self._config(key), (PRE_ACT[getattr(self.model1, "pre_act", False)], PRE_ACT[getattr(self.model2, "pre_act", False)]))
         hs.append(h)
         return h
 
@@ -335,3 +336,100 @@ def fused_nsde_loss_and_grad(model, x, y, trajectories=1, lam=1.0e2, regularize=
         model._keep = (ubar, hbar, u, h)          # buffers the enqueued kernels still use
         model.p1.grad, model.p2.grad, model.p3.grad = p1bar, p2bar, p3bar
     return ce + reg, ce, reg, int(n1.value), int(n2.value)
+
+
+def _check_on_device(ref, **tensors):
+    """The kernels read every pointer they are given on ref's GPU: a host tensor (or one on another device) is an error here, not a
+    memory fault there."""
+    if not ref.is_cuda:
+        raise ValueError("the toy-problem kernels run on the MI355X only: pass cuda tensors")
+    for name, t in tensors.items():
+        if not t.is_cuda or t.device != ref.device:
+            raise ValueError(f"{name} must be a cuda tensor on {ref.device} (got {t.device})")
+
+
+class _MomentLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sol, data_mean, data_var):
+        B, T, D = sol.shape
+        out = torch.empty(2, dtype=torch.float32, device=sol.device)
+        ubar = torch.empty_like(sol)
+        stream = C.c_void_p(torch.cuda.current_stream(sol.device).cuda_stream)
+        _lib.check(None, _lib.lib().rnde_moment_loss(sol.data_ptr(), data_mean.data_ptr(), data_var.data_ptr(), D, T, B, out.data_ptr(), ubar.data_ptr(),
+                                                     stream))
+        ctx.save_for_backward(ubar)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (ubar,) = ctx.saved_tensors
+        gm, gv = g[0], g[1]
+        if bool(gm == gv):               # the reference's loss: l2_means + l2_vars
+            return ubar * gm, None, None
+        # separate weights: the l2_means part of the kernel's cotangent is constant over the trajectories of each (d, t) and the l2_vars part
+        # sums to zero over them (it is proportional to u - mean), so the trajectory mean splits the two exactly
+        um = ubar.mean(dim=0, keepdim=True)
+        return um * gm + (ubar - um) * gv, None, None
+
+
+def moment_loss(sol, data_mean, data_var):
+    """The moment-matching loss of reference experiments/sde_toy_problem.jl:27-40 through rnde_moment_loss: sol is the (B, T, D) output of a
+    saveat call (the Julia D x T x B array), data_mean / data_var the (T, D) tensors of the Julia D x T arrays.  Returns the device tensor
+    (l2_means, l2_vars) = (mean((data_mean - mean_b sol)^2), mean((data_var - var_b sol)^2)) with var unbiased (B - 1), differentiable in sol."""
+    for name, t in (("sol", sol), ("data_mean", data_mean), ("data_var", data_var)):
+        _check_f32(name, t)
+    _check_on_device(sol, data_mean=data_mean, data_var=data_var)
+    if sol.dim() != 3 or sol.shape[0] < 2 or tuple(data_mean.shape) != tuple(sol.shape[1:]) or tuple(data_var.shape) != tuple(sol.shape[1:]):
+        raise ValueError("moment_loss: sol (B >= 2, T, D), data_mean and data_var (T, D)")
+    return _MomentLoss.apply(sol.contiguous(), data_mean.contiguous(), data_var.contiguous())
+
+
+def fused_moment_loss_and_grad(nsde, u0, data_mean, data_var, c=0.2, regularize=None, p=None, noise=None):
+    """One training-step gradient of the toy experiment's loss (reference experiments/sde_toy_problem.jl:27-40 + Tracker.gradient) in ONE library
+    call, rnde_nsde_moment_grad: the taped saveat solve of `nsde` (built with saveat=, a regularised layer when the loss is), moment_loss, and the
+    reverse sweep with every saved callback value carrying the cotangent c.  regularize (default: the layer's flag) adds c * sum(sv.saveval).
+    Sets p.grad (p defaults to nsde.p) and returns (loss, l2_means, l2_vars, reg, nfe1, nfe2): loss, l2_means and l2_vars as device tensors (stream
+    order, nothing waits for them), reg and the counters as host numbers.  Same arithmetic as moment_loss over the layer call with autograd."""
+    regularize = nsde.regularize if regularize is None else bool(regularize)
+    if regularize and not nsde.regularize:
+        raise ValueError("regularize: the layer was built with regularize = false, it records no saved values")
+    if "saveat" not in nsde.kwargs:
+        raise ValueError("fused_moment_loss_and_grad: the layer must be built with saveat= (the {R,true} call, sde_toy_problem.jl:50-60)")
+    p = nsde.p if p is None else p
+    for name, t in (("u0", u0), ("p", p), ("data_mean", data_mean), ("data_var", data_var)):
+        _check_f32(name, t)
+    if not u0.is_cuda:
+        raise ValueError("fused_moment_loss_and_grad runs on the MI355X only: u0 must be a cuda tensor")
+    _check_on_device(u0, p=p, data_mean=data_mean, data_var=data_var)
+    from .node import TrackedNeuralODE
+    times = TrackedNeuralODE._saveat_times(nsde.kwargs["saveat"], nsde.tspan)
+    B, D = u0.shape
+    if tuple(data_mean.shape) != (len(times), D) or tuple(data_var.shape) != (len(times), D):
+        raise ValueError("data_mean, data_var: (T, D) with T = the number of save times")
+    nptr, npool = None, 0
+    if noise is not None:
+        _check_f32("noise", noise)
+        if tuple(noise.shape[1:]) != (2, B, D) or not noise.is_cuda:
+            raise ValueError("noise: cuda tensor of shape (n_pool, 2, B, D)")
+        _check_on_device(u0, noise=noise)
+        noise = noise.contiguous()
+        nptr, npool = noise.data_ptr(), noise.shape[0]
+    nsde._reg = nsde.reg_of(None)                  # EEst*dt, the layer's default callback (neural_sde.jl:87)
+    with torch.no_grad():
+        x, pc = u0.contiguous(), p.detach().contiguous()
+        dm, dv = data_mean.contiguous(), data_var.contiguous()
+        hd = nsde._acquire(x)
+        pbar = torch.empty_like(pc)
+        loss2 = torch.empty(2, dtype=torch.float32, device=x.device)
+        n1, n2, reg_h = C.c_int64(0), C.c_int64(0), C.c_float(0.0)
+        sa = (C.c_float * len(times))(*times)
+        stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        nsde.seed += 1
+        _lib.check_nsde(hd.ptr, _lib.lib().rnde_nsde_moment_grad(
+            hd.ptr, x.data_ptr(), pc.data_ptr(), B, nsde.tspan[0], nsde.tspan[1], nptr, npool, nsde.seed, sa, len(times), dm.data_ptr(), dv.data_ptr(),
+            float(c) if regularize else 0.0, pbar.data_ptr(), None, loss2.data_ptr(), C.byref(reg_h), C.byref(n1), C.byref(n2), stream))
+        nsde.last_nfe = (int(n1.value), int(n2.value))
+        nsde._keep = (x, pc, dm, dv, noise)          # buffers the enqueued kernels still use
+        p.grad = pbar
+        reg = float(reg_h.value)
+        return loss2[0] + loss2[1] + reg, loss2[0], loss2[1], reg, int(n1.value), int(n2.value)

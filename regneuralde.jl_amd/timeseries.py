@@ -19,7 +19,7 @@ import math
 
 import torch
 
-from .layers import Chain, Dense, destructure
+from .layers import PRE_ACT, Chain, Dense, destructure
 from .node import TrackedNeuralODE
 
 _ACTS = {"identity": lambda v: v, "tanh": torch.tanh, "sigmoid": torch.sigmoid}
@@ -28,8 +28,11 @@ _ACTS = {"identity": lambda v: v, "tanh": torch.tanh, "sigmoid": torch.sigmoid}
 def _apply_chain(chain, p, x):
     """re(p)(x) for a Chain of Dense layers; x is (B, n_in)."""
     o = 0
-    if getattr(chain, "pre_act", False):
+    pre = PRE_ACT[getattr(chain, "pre_act", False)]
+    if pre == 1:
         x = torch.tanh(x)
+    elif pre == 2:
+        x = x ** 3
     for l in chain.layers:
         W = p[o:o + l.n_in * l.n_out].view(l.n_in, l.n_out)        # (in, out) row-major == out x in column-major
         o += l.n_in * l.n_out
