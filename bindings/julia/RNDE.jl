@@ -565,4 +565,87 @@ function set_matrix_mode!(h::Handle, mode::Integer)
 end
 matrix_mode(h::Handle) = Int(ccall((:rnde_node_matrix_mode, LIB), Cint, (Ptr{Cvoid},), h.ptr))
 
+# ---- TrackedFFJORD with the ConcatSquash MLPDynamics (include/rnde.h, "TrackedFFJORD") ----
+struct FfjordConfig
+    in_dims::Int32; hidden::Int32; dynamics::Int32; time_dep::Int32; regularize::Int32; kinetic_reg::Int32
+    max_batch::Int32; solver::Int32; reltol::Float32; abstol::Float32; cb_save_start::Int32; max_attempts::Int32; device::Int32
+end
+ffjord_param_count(cfg::FfjordConfig) = Int(ccall((:rnde_ffjord_param_count, LIB), Int32, (Ref{FfjordConfig},), cfg))
+_fferr(p) = unsafe_string(ccall((:rnde_ffjord_last_error, LIB), Cstring, (Ptr{Cvoid},), p))
+
+mutable struct FfjordHandle
+    ptr::Ptr{Cvoid}
+    cfg::FfjordConfig
+    function FfjordHandle(cfg::FfjordConfig)
+        out = Ref{Ptr{Cvoid}}(C_NULL)
+        st = ccall((:rnde_ffjord_create, LIB), Cint, (Ref{FfjordConfig}, Ref{Ptr{Cvoid}}), cfg, out)
+        st == 0 || error("rnde_ffjord_create: ", _fferr(C_NULL))
+        h = new(out[], cfg)
+        finalizer(h -> ccall((:rnde_ffjord_destroy, LIB), Cvoid, (Ptr{Cvoid},), h.ptr), h)
+        return h
+    end
+end
+
+# forward: x, e (D x B) -> logpx (B), nfe, saved values (EEst * dt per accepted step, {true} only); keeps the tape for ffjord_backward
+function ffjord_forward(h::FfjordHandle, x::ROCMatrix{Float32}, p::ROCVector{Float32}, e::ROCMatrix{Float32}, tspan; keep_tape::Bool = true)
+    B = size(x, 2)
+    logpx = similar(x, B)
+    nfe = Ref{Int64}(0); nsv = Ref{Int32}(0)
+    sv = Vector{Float32}(undef, h.cfg.max_attempts + 1)
+    GC.@preserve x p e logpx begin
+        st = ccall((:rnde_ffjord_forward, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float32, Float32, UInt64, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int64}, Ptr{Float32}, Ref{Int32}, Int32, Ptr{Cvoid}),
+                   h.ptr, devptr(x), devptr(p), devptr(e), B, Float32(tspan[1]), Float32(tspan[2]), UInt64(0), devptr(logpx), C_NULL, nfe, sv, nsv,
+                   keep_tape ? 1 : 0, _stream())
+        st == 0 || error("rnde_ffjord_forward status $st: ", _fferr(h.ptr))
+    end
+    return logpx, Int(nfe[]), sv[1:nsv[]]
+end
+
+# reverse of the last taped forward: cotangents of logpx and of the saved values -> (p-bar, x-bar)
+function ffjord_backward(h::FfjordHandle, logpx_bar::ROCVector{Float32}, svbar::Vector{Float32}, np::Int, D::Int)
+    B = length(logpx_bar)
+    pbar = similar(logpx_bar, np)
+    xbar = similar(logpx_bar, D, B)
+    GC.@preserve logpx_bar pbar xbar svbar begin
+        st = ccall((:rnde_ffjord_backward, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                   h.ptr, devptr(logpx_bar), isempty(svbar) ? C_NULL : pointer(svbar), devptr(pbar), devptr(xbar), _stream())
+        st == 0 || error("rnde_ffjord_backward status $st: ", _fferr(h.ptr))
+    end
+    return pbar, xbar
+end
+
+# Tracker glue: one tape node per forward, (logpx, saveval) -> (x-bar, p-bar).  A handle holds ONE tape and only a taped forward replaces it
+# (untaped calls leave it alone): the node's backward must run before the next tracked call on the same handle, as Tracker.gradient does.
+const FFJORD_NFE = IdDict{FfjordHandle,Int}()
+ffjord_solve(h::FfjordHandle, x::TrackedArray, p::TrackedArray, e, tspan) = track(ffjord_solve, h, x, p, e, tspan)
+ffjord_solve(h::FfjordHandle, x, p::TrackedArray, e, tspan) = track(ffjord_solve, h, x, p, e, tspan)
+function ffjord_solve(h::FfjordHandle, x, p, e, tspan)          # nothing tracked: no tape
+    logpx, nfe, sv = ffjord_forward(h, data(x), data(p), e, tspan; keep_tape = false)
+    FFJORD_NFE[h] = nfe
+    return logpx, sv
+end
+@grad function ffjord_solve(h::FfjordHandle, x, p, e, tspan)
+    logpx, nfe, sv = ffjord_forward(h, data(x), data(p), e, data.(tspan); keep_tape = true)
+    FFJORD_NFE[h] = nfe
+    return (logpx, sv), function (Δ)
+        lb, svb = Δ
+        lbar = lb === nothing ? fill!(similar(logpx), 0f0) : ROCArray{Float32}(data(lb))
+        svbar = svb === nothing ? Float32[] : Vector{Float32}(data(svb))
+        pbar, xbar = ffjord_backward(h, lbar, svbar, length(p), size(x, 1))
+        return (nothing, xbar, pbar, nothing, nothing)
+    end
+end
+
+# sample: z (D x n) solved from t1 back to t0 with the exact trace -> x (D x n)
+function ffjord_sample(h::FfjordHandle, p::ROCVector{Float32}, z::ROCMatrix{Float32}, tspan)
+    x = similar(z)
+    GC.@preserve p z x begin
+        st = ccall((:rnde_ffjord_sample, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float32, Float32, UInt64, Ptr{Cvoid}, Ptr{Cvoid}),
+                   h.ptr, devptr(p), devptr(z), size(z, 2), Float32(tspan[1]), Float32(tspan[2]), UInt64(0), devptr(x), _stream())
+        st == 0 || error("rnde_ffjord_sample status $st: ", _fferr(h.ptr))
+    end
+    return x
+end
+
 end # module

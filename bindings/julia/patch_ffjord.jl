@@ -1,0 +1,48 @@
+# patch_ffjord.jl -- the two call methods of TrackedFFJORD the FFJORD experiments use (reference src/models/ffjord.jl:68-135) and `sample`
+# (:160-167), with their `solve` replaced by librnde.so.  SOURCE ONLY (no Julia in the build image).  Usage: include RNDE.jl, then this
+# file, after `using RegNeuralDE` (see patch_neural_ode.jl).  Served: `dynamics = forw_n_back` of the ConcatSquash MLPDynamics of
+# experiments/ffjord_gaussian.jl:48-107 with in_dims + 1 <= 64 and hsize <= 64, Tsit5.  Refused with an error that names the limit: the
+# default forw_n_back (Tracker.forward), wider models (the tabular experiment), the {false} method's regularize = true rows.
+# Both call methods are one Tracker node (RNDE.ffjord_solve): Tracker.gradient through the patched layer runs RNDE.ffjord_backward.
+using Tracker, Flux, AMDGPU
+using RegNeuralDE: TrackedFFJORD, _convert_tspan
+
+const RNDE_FFJORD_HANDLES = IdDict{Any,Dict{Int,RNDE.FfjordHandle}}()
+
+# MLPDynamics(in, h) recognised by its three ConcatSquashLinear fields (layer_W of the first and second layer give in and h)
+function _ffjord_dims(n::TrackedFFJORD)
+    m = n.model
+    hasproperty(m, :csl1) && hasproperty(m.csl1, :layer_W) ||
+        error("RNDE: only the ConcatSquash MLPDynamics of experiments/ffjord_gaussian.jl (dynamics = forw_n_back) is served; the default forw_n_back (Tracker.forward) is not")
+    h, d = size(m.csl1.layer_W)
+    (d + 1 <= 64 && h <= 64) || error("RNDE: widths above the chain engine's limit of 64 are not served (in_dims + 1 <= 64, hidden <= 64); got ", (d, h))
+    return d, h
+end
+
+function _ffjord_handle(n::TrackedFFJORD{R}, B::Int) where {R}
+    d, h = _ffjord_dims(n)
+    hs = get!(RNDE_FFJORD_HANDLES, n, Dict{Int,RNDE.FfjordHandle}())
+    get!(hs, B) do
+        kw = n.kwargs
+        RNDE.FfjordHandle(RNDE.FfjordConfig(d, h, 0, n.time_dep, R ? 1 : 0, 0, B, 0, Float32(get(kw, :reltol, 1.4f-8)), Float32(get(kw, :abstol, 1.4f-8)),
+                                            1, 4096, 0))
+    end
+end
+
+function _ffjord_call(n::TrackedFFJORD{R}, x, p, e) where {R}
+    H = _ffjord_handle(n, size(x, 2))
+    logpx, sv = RNDE.ffjord_solve(H, x, p, e, _convert_tspan(n.tspan, p))
+    z = zeros(Float32, 1, size(x, 2))
+    return logpx, z, z, RNDE.FFJORD_NFE[H], (R ? (saveval = sv,) : nothing)      # (sv.saveval, as a SavedValues reads)
+end
+
+(n::TrackedFFJORD{false})(x, p = n.p, e = RNDE_randn(size(x)...); regularize = false) =
+    regularize ? error("RNDE: TrackedFFJORD{false} with regularize = true (kinetic energy and Jacobian norm rows) is not served") : _ffjord_call(n, x, p, e)
+(n::TrackedFFJORD{true})(x, p = n.p, e = RNDE_randn(size(x)...); regularize = false) = _ffjord_call(n, x, p, e)
+
+function RegNeuralDE.sample(n::TrackedFFJORD, indims::Int, p = n.p; nsamples::Int = 1)
+    H = _ffjord_handle(n, nsamples)
+    return RNDE.ffjord_sample(H, Tracker.data(p), RNDE_randn(indims, nsamples), _convert_tspan(n.tspan, p))
+end
+
+RNDE_randn(dims...) = AMDGPU.randn(Float32, dims...)

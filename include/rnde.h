@@ -532,6 +532,60 @@ rnde_status rnde_adamax_step(float* p_dev, const float* g_dev, float* m_dev, flo
 rnde_status rnde_latent_encode_backward(rnde_latent* h, const float* z0_bar_dev, float lambda_k, const float* p1_dev, const float* p2_dev,
                                         const float* x_dev, float* p1_bar_out_dev, float* p2_bar_out_dev, void* stream);
 
+/* ======================================================================================================================
+ * TrackedFFJORD (reference src/models/ffjord.jl:1-167, exported at src/RegNeuralDE.jl:88) with the ConcatSquash MLPDynamics of
+ * experiments/ffjord_gaussian.jl:48-107: three ConcatSquashLinear layers in -> hidden -> hidden -> in, softplus between them, per layer
+ * h = (W x + b) .* sig(gw t) + (bw t + bb).  State [z; l], dl/dt = -e . eJ (Hutchinson probe e, D x B, drawn once per call), Tsit5 with
+ * the chain engine's controller over the D + 1 augmented rows.  logpx = sum -(log 2 pi + z^2) / 2 - l.
+ *   regularize = 0: TrackedFFJORD{false} with regularize = false (:68-112)
+ *   regularize = 1: TrackedFFJORD{true} (:114-135): SavingCallback EEst * dt per accepted step (and 0 at init with cb_save_start)
+ * Parameters in Flux.destructure order: per layer layer_W (out x in, column-major), layer_B, bias_W, bias_B, gate_W (each out).
+ * Refused at create with a message naming the limit: dynamics other than ConcatSquash (the default forw_n_back through Tracker.forward),
+ * in_dims + 1 > 64 or hidden > 64, kinetic_reg != 0 (the {false} method's regularize = true rows).
+ * ====================================================================================================================== */
+typedef enum { RNDE_FFJORD_CONCAT_SQUASH = 0, RNDE_FFJORD_TRACKER_FORWARD = 1 } rnde_ffjord_dynamics;
+typedef struct {
+    int32_t in_dims, hidden;       /* MLPDynamics(in_dims, hidden) */
+    int32_t dynamics;              /* rnde_ffjord_dynamics */
+    int32_t time_dep;              /* the layer's time_dep flag (the ConcatSquash layers always read t) */
+    int32_t regularize;            /* 0: {false}, 1: {true} */
+    int32_t kinetic_reg;           /* {false} called with regularize = true: refused */
+    int32_t max_batch, solver;     /* solver: RNDE_SOLVER_TSIT5 */
+    float reltol, abstol;
+    int32_t cb_save_start;         /* 1: the saving callback also fires at init (value 0) */
+    int32_t max_attempts, device;
+} rnde_ffjord_config;
+typedef struct rnde_ffjord rnde_ffjord;
+int32_t     rnde_ffjord_param_count(const rnde_ffjord_config* cfg);     /* 456 for (2, 16); any widths (counted, not checked) */
+rnde_status rnde_ffjord_create(const rnde_ffjord_config* cfg, rnde_ffjord** out);
+void        rnde_ffjord_destroy(rnde_ffjord* h);
+const char* rnde_ffjord_last_error(const rnde_ffjord* h);      /* h may be NULL: last create error of this thread */
+/* Forward solve on [t0, t1].  x_dev, e_dev: D x B (e_dev NULL: standard normals from (seed) by the library's generator).  logpx_dev: B.
+ * z_out_dev: the end state's data rows, D x B (may be NULL).  saveval_host: room for max_attempts + 1 floats.  keep_tape != 0 records what
+ * rnde_ffjord_backward needs; x, p and e must then stay valid until the backward call. */
+rnde_status rnde_ffjord_forward(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0, float t1,
+                                uint64_t seed, float* logpx_dev, float* z_out_dev, int64_t* nfe_out, float* saveval_host,
+                                int32_t* n_saveval_out, int32_t keep_tape, void* stream);
+/* Parity instrument (as rnde_node_forward_replay): the solve along n_steps given (dt, accepted != 0) pairs. */
+rnde_status rnde_ffjord_forward_replay(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0, float t1,
+                                       uint64_t seed, const float* steps_host, int32_t n_steps, float* logpx_dev, float* z_out_dev,
+                                       int64_t* nfe_out, float* saveval_host, int32_t* n_saveval_out, int32_t keep_tape, void* stream);
+/* (dt, accepted) of every attempt of the last solve, as rnde_node_steps. */
+rnde_status rnde_ffjord_steps(rnde_ffjord* h, float* steps_host, int32_t capacity, int32_t* n_attempts_out);
+/* Reverse pass of the last taped forward (discretise-then-optimise; step sizes are constants): logpx_bar_dev (B) and saveval_bar_host
+ * (one per saved value, NULL = zeros) -> p_bar_dev (P, overwritten), x_bar_dev (D x B, may be NULL).  Deterministic. */
+rnde_status rnde_ffjord_backward(rnde_ffjord* h, const float* logpx_bar_dev, const float* saveval_bar_host, float* p_bar_dev, float* x_bar_dev,
+                                 void* stream);
+/* sample (ffjord.jl:137-167): z ~ N(0, I) (z_dev, D x n, or NULL: the library's normals from seed), solved from t1 back to t0 with the exact
+ * trace (D VJPs with unit probes), i.e. tau in [0, t1 - t0] on -F(u, t1 - tau).  x_out_dev: D x n.  Forward only; drops a held tape. */
+rnde_status rnde_ffjord_sample(rnde_ffjord* h, const float* p_dev, const float* z_dev, int32_t n, float t0, float t1, uint64_t seed,
+                               float* x_out_dev, void* stream);
+/* One evaluation of the augmented right-hand side: out_dev (D + 1) x B = [f(x, t); -e . eJ] (exact != 0: the exact trace, e unused). */
+rnde_status rnde_ffjord_debug_feval(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t, int32_t exact,
+                                    float* out_dev, void* stream);
+/* HIP-event durations (ms) of the last solve launch and the last reverse sweep (+ reduction), with that solve's attempt counts. */
+rnde_status rnde_ffjord_timing(rnde_ffjord* h, float* solve_ms, float* reverse_ms, int32_t* attempts, int32_t* accepted);
+
 #ifdef __cplusplus
 }
 #endif

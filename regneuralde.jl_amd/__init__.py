@@ -10,3 +10,5 @@ from .nsde import ClassifierNSDE, TrackedNeuralDSDE, fused_moment_loss_and_grad,
 from .classifier import ClassifierNODE, FluxADAM, FluxAdaBelief, FluxOptimiser, accuracy, fused_loss_and_grad, REGULARISERS, lambda_schedule, logitcrossentropy, loss_function, sample_tspan_ubound  # noqa: F401
 from .dataparallel import FlatGrads, GradientAllReducer, shard_columns  # noqa: F401
 from .timeseries import FluxAdaMax, fused_latent_loss_and_grad, LatentGRU, LatentTimeSeriesModel, build_latent_ode, get_t_saveat, kl_divergence, lambda_k, latent_loss_function, log_likelihood, sample_tbounds  # noqa: F401
+from . import ffjord  # noqa: F401
+from .ffjord import ConcatSquashLinear, TrackedFFJORD, load_gaussian_mixture, loglikelihood, sample  # noqa: F401

@@ -27,6 +27,12 @@ class NsdeConfig(C.Structure):
                 ("qoldinit", C.c_float), ("delta", C.c_float), ("generic", C.c_int32), ("stability_size", C.c_float)]
 
 
+class FfjordConfig(C.Structure):
+    _fields_ = [("in_dims", C.c_int32), ("hidden", C.c_int32), ("dynamics", C.c_int32), ("time_dep", C.c_int32), ("regularize", C.c_int32),
+                ("kinetic_reg", C.c_int32), ("max_batch", C.c_int32), ("solver", C.c_int32), ("reltol", C.c_float), ("abstol", C.c_float),
+                ("cb_save_start", C.c_int32), ("max_attempts", C.c_int32), ("device", C.c_int32)]
+
+
 class LatentConfig(C.Structure):
     _fields_ = [("max_batch", C.c_int32), ("max_T", C.c_int32), ("device", C.c_int32)]
 
@@ -163,6 +169,20 @@ def lib():
     L.rnde_latent_decode_loss.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
     L.rnde_latent_encode_backward.argtypes = [vp, vp, f, vp, vp, vp, vp, vp, vp]
     L.rnde_adamax_step.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, f, f, f, f, f, f, vp]
+    L.rnde_ffjord_param_count.restype = i32
+    L.rnde_ffjord_param_count.argtypes = [C.POINTER(FfjordConfig)]
+    L.rnde_ffjord_create.argtypes = [C.POINTER(FfjordConfig), C.POINTER(vp)]
+    L.rnde_ffjord_destroy.argtypes = [vp]
+    L.rnde_ffjord_destroy.restype = None
+    L.rnde_ffjord_last_error.argtypes = [vp]
+    L.rnde_ffjord_last_error.restype = C.c_char_p
+    L.rnde_ffjord_forward.argtypes = [vp, vp, vp, vp, i32, f, f, u64, vp, vp, i64p, fp, i32p, i32, vp]
+    L.rnde_ffjord_forward_replay.argtypes = [vp, vp, vp, vp, i32, f, f, u64, fp, i32, vp, vp, i64p, fp, i32p, i32, vp]
+    L.rnde_ffjord_steps.argtypes = [vp, fp, i32, i32p]
+    L.rnde_ffjord_backward.argtypes = [vp, vp, fp, vp, vp, vp]
+    L.rnde_ffjord_sample.argtypes = [vp, vp, vp, i32, f, f, u64, vp, vp]
+    L.rnde_ffjord_debug_feval.argtypes = [vp, vp, vp, vp, i32, f, i32, vp, vp]
+    L.rnde_ffjord_timing.argtypes = [vp, fp, fp, i32p, i32p]
     _lib = L
     return L
 
@@ -175,7 +195,10 @@ EXPORTS = ["rnde_version", "rnde_last_error", "rnde_param_count", "rnde_node_cre
            "rnde_comm_unique_id", "rnde_comm_create", "rnde_comm_destroy", "rnde_comm_world", "rnde_comm_last_error", "rnde_comm_library", "rnde_comm_allreduce", "rnde_comm_create_local_group", "rnde_comm_health", "rnde_comm_window_create", "rnde_comm_window_destroy", "rnde_comm_create_peers", "rnde_comm_path", "rnde_node_set_coupling", "rnde_tapes_create", "rnde_tapes_destroy", "rnde_tapes_last_error", "rnde_tapes_in_use", "rnde_tapes_node", "rnde_tapes_forward", "rnde_tapes_backward", "rnde_tapes_release",
            "rnde_nsde_param_count", "rnde_nsde_create", "rnde_nsde_destroy", "rnde_nsde_last_error", "rnde_nsde_forward",
            "rnde_nsde_forward_saveat", "rnde_nsde_forward_everystep", "rnde_nsde_forward_replay", "rnde_nsde_backward", "rnde_nsde_backward_async", "rnde_nsde_classifier_head", "rnde_nsde_classifier_grad", "rnde_nsde_steps", "rnde_nsde_debug_attempt", "rnde_nsde_set_pre_act", "rnde_nsde_moment_grad", "rnde_moment_loss", "rnde_adabelief_step", "rnde_nsde_timing", "rnde_normal_fill", "rnde_latent_create", "rnde_latent_destroy", "rnde_latent_last_error", "rnde_latent_param_counts", "rnde_latent_encode",
-           "rnde_latent_decode_loss", "rnde_latent_encode_backward", "rnde_adamax_step"]
+           "rnde_latent_decode_loss", "rnde_latent_encode_backward", "rnde_adamax_step",
+           "rnde_ffjord_param_count", "rnde_ffjord_create", "rnde_ffjord_destroy", "rnde_ffjord_last_error", "rnde_ffjord_forward",
+           "rnde_ffjord_forward_replay", "rnde_ffjord_steps", "rnde_ffjord_backward", "rnde_ffjord_sample", "rnde_ffjord_debug_feval",
+           "rnde_ffjord_timing"]
 
 
 def check(h, status):
@@ -187,6 +210,11 @@ def check(h, status):
 def check_latent(h, status):
     if status != OK:
         raise RndeError(status, lib().rnde_latent_last_error(h if h else None).decode())
+
+
+def check_ffjord(h, status):
+    if status != OK:
+        raise RndeError(status, lib().rnde_ffjord_last_error(h if h else None).decode())
 
 
 def check_nsde(h, status):

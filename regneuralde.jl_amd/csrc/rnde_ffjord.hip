@@ -1,0 +1,281 @@
+// rnde_ffjord.hip -- C ABI of TrackedFFJORD (include/rnde.h, "TrackedFFJORD" section): create / forward / replay / backward / sample
+// over the kernels of rnde_ffjord.h (one-launch solve) and rnde_bffjord.h (one-launch reverse sweep).
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../../include/rnde.h"
+#include "rnde_bffjord.h"
+
+using namespace rnde;
+
+static thread_local std::string g_ff_create_err;
+
+struct rnde_ffjord {
+    rnde_ffjord_config cfg;
+    FfGeo G;
+    std::string err;
+    int Bp = 0, T = 0, R = 0;
+    size_t lds_bytes = 0;
+    float *ws = nullptr, *tape = nullptr, *norm = nullptr, *e_buf = nullptr, *replay = nullptr;
+    float *rws = nullptr, *pacc = nullptr;
+    StepState* ctl = nullptr;        // [3]: the two live states, then the final one
+    StepMeta* meta = nullptr;        // [max_attempts]
+    InitRec* initrec = nullptr;
+    FfStepRec* rec = nullptr;        // [max_attempts]
+    std::vector<StepMeta> h_meta;    // step log of the last solve (rnde_ffjord_steps / _timing)
+    int n_att = 0, n_acc = 0, B = 0;
+    // the taped forward, kept apart from the last solve: an untaped call (an inference probe, sample) between a taped forward and its
+    // backward leaves the tape, its step log and its operands as they were
+    struct Tape {
+        bool valid = false;
+        std::vector<StepMeta> meta;
+        int n_att = 0, n_acc = 0, B = 0;
+        float reltol = 0.f, abstol = 0.f;
+        const float* e = nullptr;    // the probe (the caller's, or e_tape)
+        const float* p = nullptr;
+    } tp;
+    float* e_tape = nullptr;         // the library's probe of a taped forward (e_buf serves untaped calls)
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    float fwd_ms = -1.f, rev_ms = -1.f;
+};
+
+#define FCHK(h, x)                                                                                  \
+    do {                                                                                            \
+        hipError_t e_ = (x);                                                                        \
+        if (e_ != hipSuccess) { (h)->err = std::string("HIP: ") + hipGetErrorString(e_); return RNDE_ERR_HIP; } \
+    } while (0)
+
+extern "C" const char* rnde_ffjord_last_error(const rnde_ffjord* h) { return h ? h->err.c_str() : g_ff_create_err.c_str(); }
+
+extern "C" int32_t rnde_ffjord_param_count(const rnde_ffjord_config* c) {
+    if (!c || c->in_dims < 1 || c->hidden < 1) return -1;
+    const int D = c->in_dims, H = c->hidden;
+    return ff_layer_params(D, H) + ff_layer_params(H, H) + ff_layer_params(H, D);
+}
+
+// What the kernels serve; a message that names the limit otherwise.
+static const char* ff_refusal(const rnde_ffjord_config* c) {
+    if (c->dynamics != RNDE_FFJORD_CONCAT_SQUASH)
+        return "TrackedFFJORD: only the ConcatSquash MLPDynamics of experiments/ffjord_gaussian.jl (dynamics = forw_n_back) is served; the default "
+               "forw_n_back (TDChain / Dense dynamics through Tracker.forward) is not";
+    if (c->in_dims < 1 || c->in_dims + 1 > kFfMaxW || c->hidden < 1 || c->hidden > kFfMaxW)
+        return "TrackedFFJORD: widths above the chain engine's limit of 64 are not served (in_dims + 1 <= 64 and hidden <= 64)";
+    if (c->kinetic_reg)
+        return "TrackedFFJORD{false} with regularize = true (kinetic energy and Jacobian norm rows) is not served";
+    if (c->regularize != 0 && c->regularize != 1) return "TrackedFFJORD: regularize is 0 ({false}) or 1 ({true}: EEst * dt per accepted step)";
+    if (c->solver != RNDE_SOLVER_TSIT5) return "TrackedFFJORD: only Tsit5 is served";
+    if (c->max_batch < 1 || c->max_attempts < 1 || !(c->reltol > 0.f) || !(c->abstol > 0.f)) return "TrackedFFJORD: bad max_batch / max_attempts / tolerances";
+    return nullptr;
+}
+
+extern "C" rnde_status rnde_ffjord_create(const rnde_ffjord_config* c, rnde_ffjord** out) {
+    if (!c || !out) { g_ff_create_err = "null argument"; return RNDE_ERR_BAD_ARG; }
+    *out = nullptr;
+    if (const char* why = ff_refusal(c)) { g_ff_create_err = why; return RNDE_ERR_BAD_ARG; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= c->device) { g_ff_create_err = "no HIP device"; return RNDE_ERR_NO_DEVICE; }
+    if (hipSetDevice(c->device) != hipSuccess) { g_ff_create_err = "hipSetDevice failed"; return RNDE_ERR_NO_DEVICE; }
+    rnde_ffjord* h = new rnde_ffjord();
+    h->cfg = *c;
+    h->G = ff_geo(c->in_dims, c->hidden);
+    const int D = c->in_dims, R = D + 1, HS = std::max(c->hidden, D), HR = std::max(c->hidden, R);
+    h->R = R;
+    h->Bp = (c->max_batch + 63) / 64 * 64;
+    // threads of the solve workgroup: the most (<= 512) whose LDS vectors fit next to the parameters
+    for (int T = kFfMaxThreads; T >= 64; T /= 2) {
+        const size_t bytes = ((size_t)h->G.P + 32 + (size_t)3 * HS * T) * 4;
+        if (bytes <= 160 * 1024 && (T <= h->Bp || T == 64)) { h->T = T; h->lds_bytes = bytes; break; }
+    }
+    auto fail = [&](hipError_t e) { g_ff_create_err = std::string("HIP: ") + hipGetErrorString(e); rnde_ffjord_destroy(h); return RNDE_ERR_HIP; };
+    hipError_t e;
+    if (!h->T) { g_ff_create_err = "TrackedFFJORD: parameters and per-column vectors do not fit in LDS"; delete h; return RNDE_ERR_BAD_ARG; }
+    const size_t RB = (size_t)R * h->Bp, MA = (size_t)c->max_attempts;
+    if ((e = hipMalloc(&h->ws, 10 * RB * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->tape, (MA + 1) * RB * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->norm, 512 * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMemset(h->norm, 0, 512 * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->e_buf, (size_t)D * h->Bp * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->e_tape, (size_t)D * h->Bp * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->replay, 2 * MA * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->rws, (size_t)(24 + kFfVjpVecs) * HR * h->Bp * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->pacc, (size_t)h->G.P * h->Bp * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->ctl, 3 * sizeof(StepState))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->meta, MA * sizeof(StepMeta))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->initrec, sizeof(InitRec))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->rec, MA * sizeof(FfStepRec))) != hipSuccess) return fail(e);
+    if ((e = hipFuncSetAttribute((const void*)rnde_ffjord_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes)) != hipSuccess) return fail(e);
+    for (auto& v : h->ev) if ((e = hipEventCreate(&v)) != hipSuccess) return fail(e);
+    *out = h;
+    return RNDE_OK;
+}
+
+extern "C" void rnde_ffjord_destroy(rnde_ffjord* h) {
+    if (!h) return;
+    for (void* p : {(void*)h->ws, (void*)h->tape, (void*)h->norm, (void*)h->e_buf, (void*)h->e_tape, (void*)h->replay, (void*)h->rws, (void*)h->pacc,
+                    (void*)h->ctl, (void*)h->meta, (void*)h->initrec, (void*)h->rec})
+        if (p) (void)hipFree(p);
+    for (auto& v : h->ev) if (v) (void)hipEventDestroy(v);
+    delete h;
+}
+
+// One solve: dir = +1 the forward (logpx; Hutchinson probe e), dir = -1 sampling (exact trace, tau = t1 - t).
+static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0, float t1,
+                            uint64_t seed, const float* steps_host, int32_t n_steps, float* logpx_dev, float* x_out_dev, int32_t keep_tape,
+                            hipStream_t s) {
+    if (!x_dev || !p_dev || B < 1 || B > h->cfg.max_batch) { h->err = "bad argument (B must be 1..max_batch)"; return RNDE_ERR_BAD_ARG; }
+    if (!(t1 > t0)) { h->err = "TrackedFFJORD: tspan must satisfy t1 > t0 (sample() integrates t1 -> t0 itself)"; return RNDE_ERR_BAD_ARG; }
+    if (steps_host && (n_steps < 1 || n_steps > h->cfg.max_attempts)) { h->err = "replay: n_steps must be 1..max_attempts"; return RNDE_ERR_BAD_ARG; }
+    const bool taped = dir > 0 && keep_tape;
+    if (taped) h->tp.valid = false;            // (only a taped forward replaces the tape)
+    const int D = h->G.D;
+    if (dir > 0 && !e_dev) {   // the library's normal stream, drawn once per call (the reference's default argument)
+        float* eb = taped ? h->e_tape : h->e_buf;
+        rnde_status st = rnde_normal_fill(eb, (int64_t)D * B, seed, 0x46464A4FULL, s);
+        if (st != RNDE_OK) { h->err = "rnde_normal_fill failed"; return st; }
+        e_dev = eb;
+    }
+    if (steps_host) FCHK(h, hipMemcpyAsync(h->replay, steps_host, (size_t)2 * n_steps * 4, hipMemcpyHostToDevice, s));
+    FfSolveParams Q{};
+    StepParams& P = Q.F;
+    P.x = x_dev; P.D = h->R; P.B = B; P.Bn = B; P.Bpad = h->Bp; P.nwg = 1;
+    P.ctl = h->ctl; P.ctl_final = h->ctl + 2; P.meta = h->meta; P.initrec = h->initrec; P.initpart = h->norm;
+    P.reltol = h->cfg.reltol; P.abstol = h->cfg.abstol;
+    P.t0 = dir > 0 ? t0 : 0.f; P.t1 = dir > 0 ? t1 : t1 - t0;
+    P.tape = 1; P.max_attempts = h->cfg.max_attempts; P.reg_kind = 0; P.nsave = 0;
+    P.replay = steps_host ? h->replay : nullptr; P.n_replay = steps_host ? n_steps : 0;
+    P.beta1 = kBeta1; P.beta2 = kBeta2; P.rk_order = 5.f;
+    Q.G = h->G; Q.p = p_dev; Q.x = x_dev; Q.e = dir > 0 ? e_dev : nullptr; Q.ws = h->ws;
+    Q.tape = taped ? h->tape : nullptr; Q.logpx = dir > 0 ? logpx_dev : nullptr; Q.x_out = x_out_dev; Q.norm = h->norm;
+    Q.dir = dir; Q.T = h->T; Q.Bp = h->Bp; Q.tbase = t1;
+    FCHK(h, hipEventRecord(h->ev[0], s));
+    hipLaunchKernelGGL(rnde_ffjord_solve_kernel, dim3(1), dim3(h->T), h->lds_bytes, s, Q);
+    FCHK(h, hipGetLastError());
+    FCHK(h, hipEventRecord(h->ev[1], s));
+    StepState fin;
+    FCHK(h, hipMemcpyAsync(&fin, h->ctl + 2, sizeof(StepState), hipMemcpyDeviceToHost, s));
+    FCHK(h, hipStreamSynchronize(s));
+    (void)hipEventElapsedTime(&h->fwd_ms, h->ev[0], h->ev[1]);
+    h->n_att = fin.n_att; h->n_acc = fin.n_acc; h->B = B;
+    h->h_meta.resize(fin.n_att);
+    if (fin.n_att) FCHK(h, hipMemcpy(h->h_meta.data(), h->meta, (size_t)fin.n_att * sizeof(StepMeta), hipMemcpyDeviceToHost));
+    switch (fin.status) {
+        case 0: break;
+        case 2: h->err = "max_attempts reached"; return RNDE_ERR_MAX_ATTEMPTS;
+        case 3: h->err = "dt underflow"; return RNDE_ERR_DT_UNDERFLOW;
+        default: h->err = "non-finite error estimate or dt"; return RNDE_ERR_NONFINITE;
+    }
+    if (taped) {
+        rnde_ffjord::Tape& T = h->tp;
+        T.meta = h->h_meta; T.n_att = h->n_att; T.n_acc = h->n_acc; T.B = B;
+        T.reltol = P.reltol; T.abstol = P.abstol; T.e = e_dev; T.p = p_dev; T.valid = true;
+    }
+    return RNDE_OK;
+}
+
+static rnde_status ff_forward(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0, float t1, uint64_t seed,
+                              const float* steps_host, int32_t n_steps, float* logpx_dev, float* z_out_dev, int64_t* nfe_out, float* saveval_host,
+                              int32_t* n_saveval_out, int32_t keep_tape, void* stream) {
+    if (!h) return RNDE_ERR_BAD_ARG;
+    if (!logpx_dev) { h->err = "logpx_dev is required"; return RNDE_ERR_BAD_ARG; }
+    rnde_status st = ff_solve(h, +1, x_dev, p_dev, e_dev, B, t0, t1, seed, steps_host, n_steps, logpx_dev, z_out_dev, keep_tape, (hipStream_t)stream);
+    if (st != RNDE_OK) return st;
+    if (nfe_out) *nfe_out = 3 + 6 * (int64_t)h->n_att;      // 2 (initial dt) + 1 (fsalfirst) + 6 per attempt, as rnde_node_forward
+    int nsv = 0;
+    if (h->cfg.regularize) {       // SavingCallback(EEst * dt) (ffjord.jl:116): 0 at init when it fires there, then one per accepted step
+        if (h->cfg.cb_save_start) { if (saveval_host) saveval_host[nsv] = 0.f; ++nsv; }
+        for (int i = 0; i < h->n_att; ++i)
+            if (h->h_meta[i].flags & F_ACCEPT) { if (saveval_host) saveval_host[nsv] = h->h_meta[i].eest * h->h_meta[i].dt; ++nsv; }
+    }
+    if (n_saveval_out) *n_saveval_out = nsv;
+    return RNDE_OK;
+}
+
+extern "C" rnde_status rnde_ffjord_forward(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0, float t1,
+                                           uint64_t seed, float* logpx_dev, float* z_out_dev, int64_t* nfe_out, float* saveval_host,
+                                           int32_t* n_saveval_out, int32_t keep_tape, void* stream) {
+    return ff_forward(h, x_dev, p_dev, e_dev, B, t0, t1, seed, nullptr, 0, logpx_dev, z_out_dev, nfe_out, saveval_host, n_saveval_out, keep_tape, stream);
+}
+
+extern "C" rnde_status rnde_ffjord_forward_replay(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0,
+                                                  float t1, uint64_t seed, const float* steps_host, int32_t n_steps, float* logpx_dev, float* z_out_dev,
+                                                  int64_t* nfe_out, float* saveval_host, int32_t* n_saveval_out, int32_t keep_tape, void* stream) {
+    if (!steps_host) { if (h) h->err = "replay: steps_host is required"; return RNDE_ERR_BAD_ARG; }
+    return ff_forward(h, x_dev, p_dev, e_dev, B, t0, t1, seed, steps_host, n_steps, logpx_dev, z_out_dev, nfe_out, saveval_host, n_saveval_out, keep_tape, stream);
+}
+
+extern "C" rnde_status rnde_ffjord_steps(rnde_ffjord* h, float* steps_host, int32_t capacity, int32_t* n_attempts_out) {
+    if (!h || !n_attempts_out) return RNDE_ERR_BAD_ARG;
+    *n_attempts_out = h->n_att;
+    if (steps_host) {
+        if (capacity < h->n_att) { h->err = "steps: capacity below the attempt count"; return RNDE_ERR_BAD_ARG; }
+        for (int i = 0; i < h->n_att; ++i) { steps_host[2 * i] = h->h_meta[i].dt; steps_host[2 * i + 1] = (h->h_meta[i].flags & F_ACCEPT) ? 1.f : 0.f; }
+    }
+    return RNDE_OK;
+}
+
+extern "C" rnde_status rnde_ffjord_backward(rnde_ffjord* h, const float* logpx_bar_dev, const float* saveval_bar_host, float* p_bar_dev,
+                                            float* x_bar_dev, void* stream) {
+    if (!h) return RNDE_ERR_BAD_ARG;
+    const rnde_ffjord::Tape& T = h->tp;
+    if (!T.valid) { h->err = "backward without a taped forward"; return RNDE_ERR_NO_TAPE; }
+    if (!logpx_bar_dev || !p_bar_dev) { h->err = "logpx_bar_dev and p_bar_dev are required"; return RNDE_ERR_BAD_ARG; }
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<FfStepRec> rec;
+    rec.reserve(T.n_acc);
+    int k = (h->cfg.regularize && h->cfg.cb_save_start) ? 1 : 0;       // (the value saved at init is a constant)
+    for (int i = 0; i < T.n_att; ++i) {
+        const StepMeta& m = T.meta[i];
+        if (!(m.flags & F_ACCEPT)) continue;
+        FfStepRec r{m.t, m.dt, m.eest, 0.f};
+        if (h->cfg.regularize && saveval_bar_host) r.svb = saveval_bar_host[k];
+        ++k;
+        rec.push_back(r);
+    }
+    if ((int)rec.size() != T.n_acc) { h->err = "internal: accepted-step count mismatch"; return RNDE_ERR_BAD_ARG; }
+    if (!rec.empty()) FCHK(h, hipMemcpyAsync(h->rec, rec.data(), rec.size() * sizeof(FfStepRec), hipMemcpyHostToDevice, s));
+    FfRevParams Q{};
+    Q.G = h->G; Q.p = T.p; Q.e = T.e; Q.tape = h->tape; Q.rec = h->rec; Q.logpx_bar = logpx_bar_dev;
+    Q.ws = h->rws; Q.pacc = h->pacc; Q.x_bar = x_bar_dev; Q.n_acc = T.n_acc; Q.B = T.B; Q.Bp = h->Bp; Q.reltol = T.reltol; Q.abstol = T.abstol;
+    FCHK(h, hipEventRecord(h->ev[2], s));
+    hipLaunchKernelGGL(rnde_ffjord_reverse_kernel, dim3((T.B + 255) / 256), dim3(256), 0, s, Q);
+    FCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(rnde_ffjord_reduce_kernel, dim3((h->G.P + 255) / 256), dim3(256), 0, s, (const float*)h->pacc, h->G.P, T.B, h->Bp, p_bar_dev);
+    FCHK(h, hipGetLastError());
+    FCHK(h, hipEventRecord(h->ev[3], s));
+    FCHK(h, hipEventSynchronize(h->ev[3]));
+    (void)hipEventElapsedTime(&h->rev_ms, h->ev[2], h->ev[3]);
+    return RNDE_OK;
+}
+
+extern "C" rnde_status rnde_ffjord_sample(rnde_ffjord* h, const float* p_dev, const float* z_dev, int32_t n, float t0, float t1, uint64_t seed,
+                                          float* x_out_dev, void* stream) {
+    if (!h) return RNDE_ERR_BAD_ARG;
+    if (!x_out_dev) { h->err = "x_out_dev is required"; return RNDE_ERR_BAD_ARG; }
+    hipStream_t s = (hipStream_t)stream;
+    if (!z_dev) {      // z ~ N(0, I) from the library's normal stream
+        if (n < 1 || n > h->cfg.max_batch) { h->err = "bad argument (n must be 1..max_batch)"; return RNDE_ERR_BAD_ARG; }
+        rnde_status st = rnde_normal_fill(h->e_buf, (int64_t)h->G.D * n, seed, 0x53414D50ULL, s);
+        if (st != RNDE_OK) { h->err = "rnde_normal_fill failed"; return st; }
+        z_dev = h->e_buf;
+    }
+    return ff_solve(h, -1, z_dev, p_dev, nullptr, n, t0, t1, seed, nullptr, 0, nullptr, x_out_dev, 0, s);
+}
+
+extern "C" rnde_status rnde_ffjord_debug_feval(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t,
+                                               int32_t exact, float* out_dev, void* stream) {
+    if (!h || !x_dev || !p_dev || !out_dev || B < 1 || B > h->cfg.max_batch || (!exact && !e_dev)) { if (h) h->err = "bad argument"; return RNDE_ERR_BAD_ARG; }
+    hipLaunchKernelGGL(rnde_ffjord_feval_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->G, p_dev, x_dev, e_dev, t, B, exact,
+                       h->rws, out_dev);
+    FCHK(h, hipGetLastError());
+    return RNDE_OK;
+}
+
+extern "C" rnde_status rnde_ffjord_timing(rnde_ffjord* h, float* solve_ms, float* reverse_ms, int32_t* attempts, int32_t* accepted) {
+    if (!h) return RNDE_ERR_BAD_ARG;
+    if (solve_ms) *solve_ms = h->fwd_ms;
+    if (reverse_ms) *reverse_ms = h->rev_ms;
+    if (attempts) *attempts = h->n_att;
+    if (accepted) *accepted = h->n_acc;
+    return RNDE_OK;
+}

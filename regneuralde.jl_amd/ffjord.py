@@ -1,0 +1,351 @@
+"""TrackedFFJORD (reference src/models/ffjord.jl) with the ConcatSquash MLPDynamics of experiments/ffjord_gaussian.jl:48-107, the `solve`
+calls replaced by librnde.so (rnde_ffjord_*: one launch per adaptive solve, one per reverse sweep).
+
+    model = MLPDynamics(2, 16)
+    ffjord = TrackedFFJORD(model, [0.0, 1.0], True, True, "Tsit5", reltol=1.4e-8, abstol=1.4e-8, max_batch=1024)
+    logpx, l1, l2, nfe, sv = ffjord(x)          # x: (B, D) cuda tensor == Julia D x B; sv.saveval: tensor ({true}) or None
+    xs = sample(ffjord, 2, nsamples=1024)
+
+Served: the two call methods the FFJORD experiments use -- TrackedFFJORD{false} with regularize = false and TrackedFFJORD{true}
+(EEst * dt saved per accepted step) -- for widths in_dims + 1 <= 64 and hidden <= 64, and sample().  Refused with a message that names
+the limit: any other dynamics (the default forw_n_back through Tracker.forward), wider models (the tabular experiment's 43 -> 100), and
+the {false} method's regularize = true rows.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+
+MAX_WIDTH = 64
+
+
+def _glorot(rows, cols, gen):
+    """Flux.glorot_uniform(rows, cols): U(-l, l), l = sqrt(6 / (rows + cols))."""
+    lim = math.sqrt(6.0 / (rows + cols))
+    return (torch.rand(rows, cols, generator=gen, dtype=torch.float64) * 2 - 1).mul_(lim).to(torch.float32)
+
+
+class ConcatSquashLinear:
+    """(W x + b) .* sig(gw t) + (bw t + bb) (ffjord_gaussian.jl:48-82).  Parameters as Flux holds them: W (out, in), b / bw / bb / gw (out,)."""
+
+    def __init__(self, in_dims, out_dims, generator=None):
+        self.in_dims, self.out_dims = in_dims, out_dims
+        self.W = _glorot(out_dims, in_dims, generator)
+        self.b = torch.zeros(out_dims)
+        self.bw = _glorot(out_dims, 1, generator).reshape(-1)
+        self.bb = torch.zeros(out_dims)
+        self.gw = _glorot(out_dims, 1, generator).reshape(-1)
+
+    def param_count(self):
+        return self.out_dims * self.in_dims + 4 * self.out_dims
+
+    def flat(self):
+        """Flux.destructure order: layer_W (column-major), layer_B, bias_W, bias_B, gate_W."""
+        return torch.cat([self.W.t().reshape(-1), self.b, self.bw, self.bb, self.gw])
+
+
+class MLPDynamics:
+    """The experiments' MLPDynamics(in_dims, hsize): ConcatSquashLinear in -> h -> h -> in, softplus between them (ffjord_gaussian.jl:84-96)."""
+
+    def __init__(self, in_dims, hsize, generator=None):
+        self.in_dims, self.hidden = in_dims, hsize
+        self.layers = [ConcatSquashLinear(in_dims, hsize, generator), ConcatSquashLinear(hsize, hsize, generator),
+                       ConcatSquashLinear(hsize, in_dims, generator)]
+
+    def param_count(self):
+        return sum(l.param_count() for l in self.layers)
+
+    def destructure(self):
+        return torch.cat([l.flat() for l in self.layers]).to(torch.float32).contiguous()
+
+
+def param_count(in_dims, hidden):
+    """Length of Flux.destructure(MLPDynamics(in_dims, hidden)) (from the library when it is built, else the same formula here)."""
+    return (hidden * in_dims + 4 * hidden) + (hidden * hidden + 4 * hidden) + (in_dims * hidden + 4 * in_dims)
+
+
+def check_served(model, regularize_kinetic=False):
+    """ValueError naming the limit for what the kernels do not serve."""
+    if not isinstance(model, MLPDynamics):
+        raise ValueError("TrackedFFJORD: only the ConcatSquash MLPDynamics of experiments/ffjord_gaussian.jl (dynamics = forw_n_back) is served; "
+                         "the default forw_n_back (TDChain / Dense dynamics through Tracker.forward) is not")
+    if model.in_dims + 1 > MAX_WIDTH or model.hidden > MAX_WIDTH:
+        raise ValueError(f"TrackedFFJORD: widths above the chain engine's limit of {MAX_WIDTH} are not served (in_dims + 1 <= 64 and hidden <= 64; "
+                         f"got in_dims = {model.in_dims}, hidden = {model.hidden})")
+    if regularize_kinetic:
+        raise ValueError("TrackedFFJORD{false} with regularize = true (kinetic energy and Jacobian norm rows) is not served")
+
+
+class SavedValues:
+    def __init__(self, saveval):
+        self.saveval = saveval
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+class _Handle:
+    """One rnde_ffjord handle.  A handle holds ONE tape: `gen` counts the taped forwards run on it, `busy` is set while a taped forward
+    waits for its backward (or for its graph to be dropped)."""
+
+    def __init__(self, cfg):
+        self.h = C.c_void_p()
+        _lib.check_ffjord(None, _lib.lib().rnde_ffjord_create(C.byref(cfg), C.byref(self.h)))
+        self.gen, self.busy = 0, False
+
+    def __del__(self):
+        try:
+            if self.h:
+                _lib.lib().rnde_ffjord_destroy(self.h)
+        except Exception:
+            pass
+
+
+class _TapeToken:
+    """Lifetime of one taped forward: it lives in the autograd node's ctx and hands its handle back to the layer's pool after the backward
+    pass, or when the graph is dropped without one (an inference call with tracking on)."""
+
+    def __init__(self, hd):
+        self.hd, self.gen, self.done = hd, hd.gen, False
+
+    def finish(self):
+        if not self.done:
+            self.done = True
+            self.hd.busy = False
+
+    def __del__(self):
+        try:
+            self.finish()
+        except Exception:
+            pass
+
+
+MAX_TAPES = 4     # taped forwards that may wait for their backward at the same time, per layer
+
+
+class _Solve(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, p, e, layer, t0, t1, steps, keep):
+        L = _lib.lib()
+        hd = layer._taped_handle() if keep else layer._handle()
+        h = hd.h
+        B = x.shape[0]
+        logpx = torch.empty(B, device=x.device, dtype=torch.float32)
+        nfe = C.c_int64()
+        sv = (C.c_float * (layer.max_attempts + 1))()
+        nsv = C.c_int32()
+        if keep:
+            hd.busy, hd.gen = True, hd.gen + 1
+        if steps is None:
+            st = L.rnde_ffjord_forward(h, x.data_ptr(), p.data_ptr(), e.data_ptr(), B, t0, t1, 0, logpx.data_ptr(), None, C.byref(nfe), sv, C.byref(nsv),
+                                       keep, _stream(x.device))
+        else:
+            arr = (C.c_float * len(steps))(*steps)
+            st = L.rnde_ffjord_forward_replay(h, x.data_ptr(), p.data_ptr(), e.data_ptr(), B, t0, t1, 0, arr, len(steps) // 2, logpx.data_ptr(), None,
+                                              C.byref(nfe), sv, C.byref(nsv), keep, _stream(x.device))
+        layer._last = hd
+        if st != _lib.OK:
+            hd.busy = False
+            _lib.check_ffjord(h, st)
+        ctx.layer, ctx.nsv = layer, nsv.value
+        ctx.token = _TapeToken(hd) if keep else None
+        ctx.save_for_backward(x, p, e)
+        layer.last_nfe = int(nfe.value)
+        saveval = torch.tensor(list(sv[:nsv.value]), dtype=torch.float32, device=x.device)
+        return logpx, saveval
+
+    @staticmethod
+    def backward(ctx, g_logpx, g_sv):
+        x, p, e = ctx.saved_tensors
+        tok = ctx.token
+        if tok is None:
+            raise RuntimeError("TrackedFFJORD: this forward was not taped (it ran with grad disabled or with no input requiring grad)")
+        if tok.done or tok.hd.gen != tok.gen:
+            raise RuntimeError("TrackedFFJORD: the tape of this forward has been released (a second backward through the same graph)")
+        L, h = _lib.lib(), tok.hd.h
+        g_logpx = (torch.zeros(x.shape[0], device=x.device) if g_logpx is None else g_logpx).contiguous().float()
+        svb = None
+        if g_sv is not None and ctx.nsv:
+            svb = (C.c_float * ctx.nsv)(*g_sv.detach().float().cpu().tolist())
+        pb = torch.empty_like(p)
+        xb = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        st = L.rnde_ffjord_backward(h, g_logpx.data_ptr(), svb, pb.data_ptr(), xb.data_ptr() if xb is not None else None, _stream(x.device))
+        ctx.layer._last_bwd = tok.hd
+        tok.finish()
+        _lib.check_ffjord(h, st)
+        return xb, pb, None, None, None, None, None, None
+
+
+class TrackedFFJORD:
+    """TrackedFFJORD(model, tspan, time_dep, regularize, solver; reltol, abstol, ...) (ffjord.jl:1-51).  regularize selects the call
+    method: False -> TrackedFFJORD{false} (returns logpx, 0, 0, nfe, None), True -> TrackedFFJORD{true} (returns logpx, 0, 0, nfe, sv with
+    sv.saveval = EEst * dt per accepted step, differentiable)."""
+
+    def __init__(self, model, tspan, time_dep, regularize, solver="Tsit5", *, reltol=1.4e-8, abstol=1.4e-8, max_batch=1024, max_attempts=4096,
+                 cb_save_start=True, device=0, dynamics=None, **kwargs):
+        if dynamics is not None and dynamics != "forw_n_back":
+            raise ValueError("TrackedFFJORD: only dynamics = forw_n_back of the ConcatSquash MLPDynamics is served")
+        check_served(model)
+        if solver != "Tsit5":
+            raise ValueError("TrackedFFJORD: only Tsit5 is served")
+        self.model, self.tspan, self.time_dep, self.regularize = model, (float(tspan[0]), float(tspan[1])), bool(time_dep), bool(regularize)
+        self.reltol, self.abstol, self.max_batch, self.max_attempts = float(reltol), float(abstol), int(max_batch), int(max_attempts)
+        self.cb_save_start, self.device = bool(cb_save_start), int(device)
+        self.p = model.destructure().cuda(self.device)
+        self._h = None          # untaped calls: inference, sample, steps of those, feval
+        self._pool = []         # handles for taped forwards (one tape each)
+        self._last = self._last_bwd = None
+        self.last_nfe = 0
+        self._seed = 0x5EED
+
+    def config(self):
+        cfg = _lib.FfjordConfig()
+        cfg.in_dims, cfg.hidden, cfg.dynamics, cfg.time_dep = self.model.in_dims, self.model.hidden, 0, int(self.time_dep)
+        cfg.regularize, cfg.kinetic_reg, cfg.max_batch, cfg.solver = int(self.regularize), 0, self.max_batch, 0
+        cfg.reltol, cfg.abstol, cfg.cb_save_start, cfg.max_attempts, cfg.device = self.reltol, self.abstol, int(self.cb_save_start), self.max_attempts, self.device
+        return cfg
+
+    def _handle(self):
+        if self._h is None:
+            self._h = _Handle(self.config())
+        return self._h
+
+    def _taped_handle(self):
+        for hd in self._pool:
+            if not hd.busy:
+                return hd
+        if len(self._pool) >= MAX_TAPES:
+            raise RuntimeError(f"TrackedFFJORD: {MAX_TAPES} taped forwards are waiting for their backward pass; run backward (or drop the graphs) "
+                               "before taping more")
+        self._pool.append(_Handle(self.config()))
+        return self._pool[-1]
+
+    def draw_normal(self, rows, cols, device):
+        """(cols, rows) standard normals from the library's stream (a fresh seed per call: the reference's CUDA.randn default argument)."""
+        out = torch.empty(cols, rows, device=device, dtype=torch.float32)
+        self._seed += 1
+        _lib.check(None, _lib.lib().rnde_normal_fill(out.data_ptr(), out.numel(), self._seed, 0x46464A4F, _stream(device)))
+        return out
+
+    def __call__(self, x, p=None, e=None, regularize=False, steps=None):
+        if regularize and not self.regularize:
+            check_served(self.model, regularize_kinetic=True)
+        p = self.p if p is None else p
+        if not (x.is_cuda and p.is_cuda):
+            raise RuntimeError("TrackedFFJORD runs on the device only: x and p must be cuda tensors")
+        x = x.contiguous().float()
+        if x.dim() != 2 or x.shape[1] != self.model.in_dims:
+            raise ValueError(f"x must be (B, {self.model.in_dims})")
+        if e is None:
+            e = self.draw_normal(self.model.in_dims, x.shape[0], x.device)
+        elif tuple(e.shape) != tuple(x.shape) or not e.is_cuda:
+            raise ValueError(f"e must be a cuda tensor of x's shape {tuple(x.shape)} (B, D); got {tuple(e.shape)}")
+        e = e.contiguous().float()
+        p = p.contiguous()
+        if p.numel() != self.model.param_count():
+            raise ValueError(f"p must hold {self.model.param_count()} parameters; got {p.numel()}")
+        # tape only when a gradient can be asked for: an inference call must not occupy (or replace) a tape
+        keep = torch.is_grad_enabled() and (x.requires_grad or p.requires_grad)
+        logpx, saveval = _Solve.apply(x, p, e, self, self.tspan[0], self.tspan[1], steps, keep)
+        zero = torch.zeros(x.shape[0], device=x.device)
+        return logpx, zero, zero, self.last_nfe, (SavedValues(saveval) if self.regularize else None)
+
+    def steps(self):
+        """[(dt, accepted), ...] of every attempt of the last solve (rnde_ffjord_steps), flattened."""
+        h, n = (self._last or self._handle()).h, C.c_int32()
+        _lib.check_ffjord(h, _lib.lib().rnde_ffjord_steps(h, None, 0, C.byref(n)))
+        arr = (C.c_float * max(2 * n.value, 1))()
+        _lib.check_ffjord(h, _lib.lib().rnde_ffjord_steps(h, arr, n.value, C.byref(n)))
+        return list(arr[:2 * n.value])
+
+    def timing(self):
+        """(solve ms, attempts, accepted) of the last solve and the reverse ms of the last backward (HIP events): (solve, reverse, n, m)."""
+        a, b, n, m = C.c_float(), C.c_float(), C.c_int32(), C.c_int32()
+        h = (self._last or self._handle()).h
+        _lib.check_ffjord(h, _lib.lib().rnde_ffjord_timing(h, C.byref(a), None, C.byref(n), C.byref(m)))
+        if self._last_bwd is not None:
+            _lib.check_ffjord(self._last_bwd.h, _lib.lib().rnde_ffjord_timing(self._last_bwd.h, None, C.byref(b), None, None))
+        return a.value, (b.value if self._last_bwd is not None else -1.0), n.value, m.value
+
+    def feval(self, x, t, e=None, p=None):
+        """[f(x, t); -e . eJ] as (B, D + 1) (e = None: the exact trace)."""
+        p = self.p if p is None else p
+        if x.dim() != 2 or x.shape[1] != self.model.in_dims or (e is not None and tuple(e.shape) != tuple(x.shape)):
+            raise ValueError(f"x and e must be (B, {self.model.in_dims})")
+        h = self._handle().h
+        out = torch.empty(x.shape[0], self.model.in_dims + 1, device=x.device)
+        _lib.check_ffjord(h, _lib.lib().rnde_ffjord_debug_feval(h, x.contiguous().data_ptr(), p.contiguous().data_ptr(),
+                                                                e.contiguous().data_ptr() if e is not None else None, x.shape[0], float(t),
+                                                                int(e is None), out.data_ptr(), _stream(x.device)))
+        return out
+
+
+@torch.no_grad()
+def sample(ffjord, indims, p=None, nsamples=1, z=None):
+    """sample(ffjord, indims, p; nsamples) (ffjord.jl:160-167): z ~ N(0, I), solved from t1 back to t0 with the exact trace.  Returns x (nsamples, D)."""
+    if indims != ffjord.model.in_dims:
+        raise ValueError("indims must equal the model's in_dims")
+    p = ffjord.p if p is None else p
+    hd = ffjord._handle()
+    h = hd.h
+    dev = p.device
+    if z is None:
+        z = ffjord.draw_normal(indims, nsamples, dev)
+    elif z.dim() != 2 or z.shape[1] != indims or not z.is_cuda:
+        raise ValueError(f"z must be a cuda tensor of shape (nsamples, {indims}); got {tuple(z.shape)}")
+    z = z.contiguous().float()
+    out = torch.empty(z.shape[0], indims, device=dev)
+    _lib.check_ffjord(h, _lib.lib().rnde_ffjord_sample(h, p.contiguous().data_ptr(), z.data_ptr(), z.shape[0], ffjord.tspan[0], ffjord.tspan[1], 0,
+                                                       out.data_ptr(), _stream(dev)))
+    ffjord._last = hd
+    return out
+
+
+@torch.no_grad()
+def loglikelihood(model, batches, p=None):
+    """src/metrics.jl:20-33: sum of logpx over the batches / the number of columns."""
+    total, n = 0.0, 0
+    for xb in batches:
+        x = torch.as_tensor(xb, dtype=torch.float32).cuda(model.device)
+        total += float(model(x, p)[0].sum())
+        n += x.shape[0]
+    return total / n
+
+
+class _Loader:
+    """Flux.Data.DataLoader(X; batchsize, shuffle): (B, D) float32 batches; a shuffling loader draws a new order each pass (seeded)."""
+
+    def __init__(self, X, batchsize, shuffle, seed):
+        self.X, self.batchsize, self.shuffle = X, batchsize, shuffle
+        self.rng = np.random.default_rng(seed)
+
+    def __len__(self):
+        return (self.X.shape[0] + self.batchsize - 1) // self.batchsize
+
+    def __iter__(self):
+        idx = self.rng.permutation(self.X.shape[0]) if self.shuffle else np.arange(self.X.shape[0])
+        for i in range(0, len(idx), self.batchsize):
+            yield self.X[idx[i:i + self.batchsize]]
+
+
+def load_gaussian_mixture(batchsize, train_test_split=0.75, *, nsamples=1000, ngaussians=6, dim=2, radius=5.0, sigma=0.1, noise=0.3, seed=0):
+    """src/dataset.jl:159-199: ngaussians isotropic gaussians (std sigma) on a circle of `radius`, plus N(0, noise^2) noise, nsamples // ngaussians
+    each; shuffled, split train / test.  The reference's distribution and shapes from a seeded numpy generator (not its draws)."""
+    if dim != 2:
+        raise ValueError("the reference generator places the means on a circle: dim = 2")
+    rng = np.random.default_rng(seed)
+    per = nsamples // ngaussians
+    X = np.empty((per * ngaussians, dim), dtype=np.float32)
+    theta = np.float32(0.0)
+    for i in range(ngaussians):
+        theta = np.float32(theta + np.float32(2 * np.pi / ngaussians))
+        mu = np.array([np.cos(theta) * radius, np.sin(theta) * radius], dtype=np.float32)
+        samples = mu[None, :] + sigma * rng.standard_normal((per, dim))
+        X[i * per:(i + 1) * per] = (samples + noise * rng.standard_normal((per, dim))).astype(np.float32)
+    X = X[rng.permutation(X.shape[0])]
+    ntrain = int(math.floor(train_test_split * X.shape[0]))
+    return _Loader(X[:ntrain].copy(), batchsize, True, seed + 1), _Loader(X[ntrain:].copy(), batchsize, False, seed + 2)
