@@ -570,16 +570,24 @@ struct FfjordConfig
     in_dims::Int32; hidden::Int32; dynamics::Int32; time_dep::Int32; regularize::Int32; kinetic_reg::Int32
     max_batch::Int32; solver::Int32; reltol::Float32; abstol::Float32; cb_save_start::Int32; max_attempts::Int32; device::Int32
 end
+ffjord_engine(h) = Int(ccall((:rnde_ffjord_engine, LIB), Int32, (Ptr{Cvoid},), h.ptr))     # 0: one workgroup, 1: tiled
 ffjord_param_count(cfg::FfjordConfig) = Int(ccall((:rnde_ffjord_param_count, LIB), Int32, (Ref{FfjordConfig},), cfg))
 _fferr(p) = unsafe_string(ccall((:rnde_ffjord_last_error, LIB), Cstring, (Ptr{Cvoid},), p))
 
 mutable struct FfjordHandle
     ptr::Ptr{Cvoid}
     cfg::FfjordConfig
-    function FfjordHandle(cfg::FfjordConfig)
+    # engine = :workgroup (rnde_ffjord_create: in + 1 <= 64, h <= 64) or :tiled (rnde_ffjord_create_tiled: in <= 64, h <= 112), as Python's engine=
+    function FfjordHandle(cfg::FfjordConfig; engine::Symbol = :workgroup)
         out = Ref{Ptr{Cvoid}}(C_NULL)
-        st = ccall((:rnde_ffjord_create, LIB), Cint, (Ref{FfjordConfig}, Ref{Ptr{Cvoid}}), cfg, out)
-        st == 0 || error("rnde_ffjord_create: ", _fferr(C_NULL))
+        if engine === :tiled
+            st = ccall((:rnde_ffjord_create_tiled, LIB), Cint, (Ref{FfjordConfig}, Ref{Ptr{Cvoid}}), cfg, out)
+        elseif engine === :workgroup
+            st = ccall((:rnde_ffjord_create, LIB), Cint, (Ref{FfjordConfig}, Ref{Ptr{Cvoid}}), cfg, out)
+        else
+            error("RNDE: engine must be :workgroup or :tiled; got ", engine)
+        end
+        st == 0 || error("rnde_ffjord_create ($engine): ", _fferr(C_NULL))
         h = new(out[], cfg)
         finalizer(h -> ccall((:rnde_ffjord_destroy, LIB), Cvoid, (Ptr{Cvoid},), h.ptr), h)
         return h

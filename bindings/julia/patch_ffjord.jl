@@ -1,13 +1,16 @@
 # patch_ffjord.jl -- the two call methods of TrackedFFJORD the FFJORD experiments use (reference src/models/ffjord.jl:68-135) and `sample`
 # (:160-167), with their `solve` replaced by librnde.so.  SOURCE ONLY (no Julia in the build image).  Usage: include RNDE.jl, then this
 # file, after `using RegNeuralDE` (see patch_neural_ode.jl).  Served: `dynamics = forw_n_back` of the ConcatSquash MLPDynamics of
-# experiments/ffjord_gaussian.jl:48-107 with in_dims + 1 <= 64 and hsize <= 64, Tsit5.  Refused with an error that names the limit: the
-# default forw_n_back (Tracker.forward), wider models (the tabular experiment), the {false} method's regularize = true rows.
+# experiments/ffjord_gaussian.jl:48-107 with in_dims + 1 <= 64 and hsize <= 64, Tsit5; with RNDE_FFJORD_ENGINE[] = :tiled, in_dims <= 64 and
+# hsize <= 112 (experiments/ffjord_tabular.jl's 43 -> 100).  Refused with an error that names the limit: the default forw_n_back
+# (Tracker.forward), widths above the engine's limit, the {false} method's regularize = true rows.
 # Both call methods are one Tracker node (RNDE.ffjord_solve): Tracker.gradient through the patched layer runs RNDE.ffjord_backward.
 using Tracker, Flux, AMDGPU
 using RegNeuralDE: TrackedFFJORD, _convert_tspan
 
 const RNDE_FFJORD_HANDLES = IdDict{Any,Dict{Int,RNDE.FfjordHandle}}()
+# which engine new handles use: :workgroup (default) or :tiled (the tabular experiment's MLPDynamics(43, 100)); set before the first call
+const RNDE_FFJORD_ENGINE = Ref(:workgroup)
 
 # MLPDynamics(in, h) recognised by its three ConcatSquashLinear fields (layer_W of the first and second layer give in and h)
 function _ffjord_dims(n::TrackedFFJORD)
@@ -15,7 +18,12 @@ function _ffjord_dims(n::TrackedFFJORD)
     hasproperty(m, :csl1) && hasproperty(m.csl1, :layer_W) ||
         error("RNDE: only the ConcatSquash MLPDynamics of experiments/ffjord_gaussian.jl (dynamics = forw_n_back) is served; the default forw_n_back (Tracker.forward) is not")
     h, d = size(m.csl1.layer_W)
-    (d + 1 <= 64 && h <= 64) || error("RNDE: widths above the chain engine's limit of 64 are not served (in_dims + 1 <= 64, hidden <= 64); got ", (d, h))
+    if RNDE_FFJORD_ENGINE[] === :tiled
+        (d <= 64 && h <= 112) || error("RNDE: widths above the tiled engine's LDS limit are not served (in_dims <= 64, hidden <= 112); got ", (d, h))
+    else
+        (d + 1 <= 64 && h <= 64) || error("RNDE: widths above the chain engine's limit of 64 are not served (in_dims + 1 <= 64, hidden <= 64; ",
+                                          "RNDE_FFJORD_ENGINE[] = :tiled serves wider models); got ", (d, h))
+    end
     return d, h
 end
 
@@ -25,7 +33,7 @@ function _ffjord_handle(n::TrackedFFJORD{R}, B::Int) where {R}
     get!(hs, B) do
         kw = n.kwargs
         RNDE.FfjordHandle(RNDE.FfjordConfig(d, h, 0, n.time_dep, R ? 1 : 0, 0, B, 0, Float32(get(kw, :reltol, 1.4f-8)), Float32(get(kw, :abstol, 1.4f-8)),
-                                            1, 4096, 0))
+                                            1, 4096, 0); engine = RNDE_FFJORD_ENGINE[])
     end
 end
 

@@ -541,7 +541,8 @@ rnde_status rnde_latent_encode_backward(rnde_latent* h, const float* z0_bar_dev,
  *   regularize = 1: TrackedFFJORD{true} (:114-135): SavingCallback EEst * dt per accepted step (and 0 at init with cb_save_start)
  * Parameters in Flux.destructure order: per layer layer_W (out x in, column-major), layer_B, bias_W, bias_B, gate_W (each out).
  * Refused at create with a message naming the limit: dynamics other than ConcatSquash (the default forw_n_back through Tracker.forward),
- * in_dims + 1 > 64 or hidden > 64, kinetic_reg != 0 (the {false} method's regularize = true rows).
+ * in_dims + 1 > 64 or hidden > 64 (rnde_ffjord_create; rnde_ffjord_create_tiled below serves wider models), kinetic_reg != 0 (the
+ * {false} method's regularize = true rows), solvers other than Tsit5.
  * ====================================================================================================================== */
 typedef enum { RNDE_FFJORD_CONCAT_SQUASH = 0, RNDE_FFJORD_TRACKER_FORWARD = 1 } rnde_ffjord_dynamics;
 typedef struct {
@@ -585,6 +586,16 @@ rnde_status rnde_ffjord_debug_feval(rnde_ffjord* h, const float* x_dev, const fl
                                     float* out_dev, void* stream);
 /* HIP-event durations (ms) of the last solve launch and the last reverse sweep (+ reduction), with that solve's attempt counts. */
 rnde_status rnde_ffjord_timing(rnde_ffjord* h, float* solve_ms, float* reverse_ms, int32_t* attempts, int32_t* accepted);
+/* The tiled engine (opt-in; the same config struct, every other rnde_ffjord_* entry dispatches on the handle): one workgroup per 16 batch
+ * columns, the layer products on the matrix cores (v_mfma_f32_16x16x4_f32, exact fp32 products), the padded parameters resident in LDS, the
+ * workgroups meeting once per attempt for the error norm (bounded; a meeting that times out fails the call with a message naming it).
+ * Serves what rnde_ffjord_create serves, at widths up to its LDS limit:
+ *   in_dims <= 64 and hidden <= 112 (weights and activations of a tile within 160 KB of LDS; (43, 100) fits),
+ *   max_batch <= 4096 (256 tiles: one meeting holds only resident workgroups), max_attempts <= 8000.
+ * sample() and the exact trace of rnde_ffjord_debug_feval use the closed form tr J = a2' (W2 .* M') a1, M(t) = W1 diag(g3(t)) W3, with
+ * a_l = sig(h_l) .* g_l: the same value as the D unit-probe VJPs, rounded differently. */
+rnde_status rnde_ffjord_create_tiled(const rnde_ffjord_config* cfg, rnde_ffjord** out);
+int32_t     rnde_ffjord_engine(const rnde_ffjord* h);          /* 0: one workgroup (rnde_ffjord_create), 1: tiled; -1 for NULL */
 
 #ifdef __cplusplus
 }

@@ -183,6 +183,9 @@ def lib():
     L.rnde_ffjord_sample.argtypes = [vp, vp, vp, i32, f, f, u64, vp, vp]
     L.rnde_ffjord_debug_feval.argtypes = [vp, vp, vp, vp, i32, f, i32, vp, vp]
     L.rnde_ffjord_timing.argtypes = [vp, fp, fp, i32p, i32p]
+    L.rnde_ffjord_create_tiled.argtypes = [C.POINTER(FfjordConfig), C.POINTER(vp)]
+    L.rnde_ffjord_engine.restype = i32
+    L.rnde_ffjord_engine.argtypes = [vp]
     _lib = L
     return L
 
@@ -198,7 +201,7 @@ EXPORTS = ["rnde_version", "rnde_last_error", "rnde_param_count", "rnde_node_cre
            "rnde_latent_decode_loss", "rnde_latent_encode_backward", "rnde_adamax_step",
            "rnde_ffjord_param_count", "rnde_ffjord_create", "rnde_ffjord_destroy", "rnde_ffjord_last_error", "rnde_ffjord_forward",
            "rnde_ffjord_forward_replay", "rnde_ffjord_steps", "rnde_ffjord_backward", "rnde_ffjord_sample", "rnde_ffjord_debug_feval",
-           "rnde_ffjord_timing"]
+           "rnde_ffjord_timing", "rnde_ffjord_create_tiled", "rnde_ffjord_engine"]
 
 
 def check(h, status):

@@ -1,11 +1,13 @@
 // rnde_ffjord.hip -- C ABI of TrackedFFJORD (include/rnde.h, "TrackedFFJORD" section): create / forward / replay / backward / sample
-// over the kernels of rnde_ffjord.h (one-launch solve) and rnde_bffjord.h (one-launch reverse sweep).
+// over the kernels of rnde_ffjord.h (one-launch solve) and rnde_bffjord.h (one-launch reverse sweep), or, on a handle made by
+// rnde_ffjord_create_tiled, over those of rnde_ffjordt.h / rnde_bffjordt.h (the tiled engine).
 #include <algorithm>
 #include <string>
 #include <vector>
 
 #include "../../include/rnde.h"
 #include "rnde_bffjord.h"
+#include "rnde_bffjordt.h"
 
 using namespace rnde;
 
@@ -38,6 +40,19 @@ struct rnde_ffjord {
     float* e_tape = nullptr;         // the library's probe of a taped forward (e_buf serves untaped calls)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float fwd_ms = -1.f, rev_ms = -1.f;
+    // the tiled engine (engine = 1): one workgroup per 16 columns, the workgroups meeting once per attempt
+    int engine = 0;
+    FtGeo TG{};
+    int ntiles_max = 0;
+    float* qt = nullptr;             // [ntiles][HP][HP]: the exact trace's matrix, per tile
+    InitRec* initrec_t = nullptr;    // [ntiles] (initrec = initrec_t)
+    StepState* ctl_t = nullptr;      // [ntiles]
+    unsigned long long* xch = nullptr;
+    unsigned* xcc = nullptr;         // [kMwMeetMax]
+    unsigned* abort_word = nullptr;
+    unsigned epoch = 0;
+    int xcd_slot = 0;
+    std::vector<unsigned> h_chk;     // abort word, then each tile's XCC
 };
 
 #define FCHK(h, x)                                                                                  \
@@ -54,20 +69,88 @@ extern "C" int32_t rnde_ffjord_param_count(const rnde_ffjord_config* c) {
     return ff_layer_params(D, H) + ff_layer_params(H, H) + ff_layer_params(H, D);
 }
 
-// What the kernels serve; a message that names the limit otherwise.
-static const char* ff_refusal(const rnde_ffjord_config* c) {
+// What the kernels serve; a message that names the limit otherwise (tiled: the tiled engine's limits).
+static const char* ff_refusal(const rnde_ffjord_config* c, bool tiled = false) {
     if (c->dynamics != RNDE_FFJORD_CONCAT_SQUASH)
         return "TrackedFFJORD: only the ConcatSquash MLPDynamics of experiments/ffjord_gaussian.jl (dynamics = forw_n_back) is served; the default "
                "forw_n_back (TDChain / Dense dynamics through Tracker.forward) is not";
-    if (c->in_dims < 1 || c->in_dims + 1 > kFfMaxW || c->hidden < 1 || c->hidden > kFfMaxW)
-        return "TrackedFFJORD: widths above the chain engine's limit of 64 are not served (in_dims + 1 <= 64 and hidden <= 64)";
+    if (!tiled && (c->in_dims < 1 || c->in_dims + 1 > kFfMaxW || c->hidden < 1 || c->hidden > kFfMaxW))
+        return "TrackedFFJORD: widths above the chain engine's limit of 64 are not served (in_dims + 1 <= 64 and hidden <= 64; "
+               "rnde_ffjord_create_tiled / engine = \"tiled\" serves wider models)";
+    if (tiled && (c->in_dims < 1 || c->in_dims > kFtMaxD || c->hidden < 1 || c->hidden > kFtMaxH))
+        return "TrackedFFJORD tiled engine: widths above its LDS limit are not served (in_dims <= 64 and hidden <= 112: the resident weights "
+               "and activations of a tile within 160 KB of LDS)";
     if (c->kinetic_reg)
         return "TrackedFFJORD{false} with regularize = true (kinetic energy and Jacobian norm rows) is not served";
     if (c->regularize != 0 && c->regularize != 1) return "TrackedFFJORD: regularize is 0 ({false}) or 1 ({true}: EEst * dt per accepted step)";
     if (c->solver != RNDE_SOLVER_TSIT5) return "TrackedFFJORD: only Tsit5 is served";
     if (c->max_batch < 1 || c->max_attempts < 1 || !(c->reltol > 0.f) || !(c->abstol > 0.f)) return "TrackedFFJORD: bad max_batch / max_attempts / tolerances";
+    if (tiled && c->max_batch > 16 * kMwMeetMax)
+        return "TrackedFFJORD tiled engine: max_batch above 4096 is not served (one meeting holds kMwMeetMax = 256 resident tiles of 16 columns)";
+    if (tiled && c->max_attempts > kFtMaxAttempts) return "TrackedFFJORD tiled engine: max_attempts above 8000 is not served (meeting tags)";
     return nullptr;
 }
+
+// The tiled engine's buffers and kernel attributes (the config is validated).
+static rnde_status ft_create(const rnde_ffjord_config* c, rnde_ffjord** out) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= c->device) { g_ff_create_err = "no HIP device"; return RNDE_ERR_NO_DEVICE; }
+    if (hipSetDevice(c->device) != hipSuccess) { g_ff_create_err = "hipSetDevice failed"; return RNDE_ERR_NO_DEVICE; }
+    rnde_ffjord* h = new rnde_ffjord();
+    h->cfg = *c;
+    h->engine = 1;
+    h->G = ff_geo(c->in_dims, c->hidden);
+    h->TG = ft_geo(c->in_dims, c->hidden);
+    const FtGeo& G = h->TG;
+    const int D = c->in_dims, R = D + 1;
+    h->R = R;
+    h->ntiles_max = (c->max_batch + 15) / 16;
+    h->Bp = 16 * h->ntiles_max;
+    h->T = kFtThreads;
+    h->lds_bytes = (size_t)ft_lds_floats(G) * 4;
+    if (h->lds_bytes > (size_t)kFtLdsBytes) { g_ff_create_err = "TrackedFFJORD tiled engine: a tile does not fit in LDS"; delete h; return RNDE_ERR_BAD_ARG; }
+    auto fail = [&](hipError_t e) { g_ff_create_err = std::string("HIP: ") + hipGetErrorString(e); rnde_ffjord_destroy(h); return RNDE_ERR_HIP; };
+    hipError_t e;
+    const size_t RB = (size_t)R * h->Bp, MA = (size_t)c->max_attempts, NT = (size_t)h->ntiles_max;
+    const size_t xb = (MA + 4) * 3 * kMwMeetMax * 8;
+    if ((e = hipMalloc(&h->ws, 10 * RB * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->tape, (MA + 1) * RB * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->norm, (8 * NT + 512) * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMemset(h->norm, 0, (8 * NT + 512) * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->e_buf, (size_t)D * h->Bp * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->e_tape, (size_t)D * h->Bp * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->replay, 2 * MA * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->rws, NT * ft_rev_ws_floats(G) * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->pacc, NT * G.P * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->qt, NT * G.HP * G.HP * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->ctl, 3 * sizeof(StepState))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->ctl_t, NT * sizeof(StepState))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->meta, MA * sizeof(StepMeta))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->initrec_t, NT * sizeof(InitRec))) != hipSuccess) return fail(e);
+    h->initrec = h->initrec_t;
+    if ((e = hipMalloc(&h->rec, MA * sizeof(FfStepRec))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->xch, xb)) != hipSuccess) return fail(e);
+    if ((e = hipMemset(h->xch, 0, xb)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->xcc, kMwMeetMax * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->abort_word, 8)) != hipSuccess) return fail(e);
+    if ((e = hipMemset(h->abort_word, 0, 8)) != hipSuccess) return fail(e);
+    for (const void* k : {(const void*)rnde_ffjordt_solve_kernel, (const void*)rnde_ffjordt_reverse_kernel, (const void*)rnde_ffjordt_feval_kernel})
+        if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes)) != hipSuccess) return fail(e);
+    for (auto& v : h->ev) if ((e = hipEventCreate(&v)) != hipSuccess) return fail(e);
+    { static std::atomic<int> next_slot{0}; h->xcd_slot = next_slot.fetch_add(1) & 7; }
+    h->h_chk.assign(2 + kMwMeetMax, 0u);
+    *out = h;
+    return RNDE_OK;
+}
+
+extern "C" rnde_status rnde_ffjord_create_tiled(const rnde_ffjord_config* c, rnde_ffjord** out) {
+    if (!c || !out) { g_ff_create_err = "null argument"; return RNDE_ERR_BAD_ARG; }
+    *out = nullptr;
+    if (const char* why = ff_refusal(c, true)) { g_ff_create_err = why; return RNDE_ERR_BAD_ARG; }
+    return ft_create(c, out);
+}
+
+extern "C" int32_t rnde_ffjord_engine(const rnde_ffjord* h) { return h ? h->engine : -1; }
 
 extern "C" rnde_status rnde_ffjord_create(const rnde_ffjord_config* c, rnde_ffjord** out) {
     if (!c || !out) { g_ff_create_err = "null argument"; return RNDE_ERR_BAD_ARG; }
@@ -113,7 +196,8 @@ extern "C" rnde_status rnde_ffjord_create(const rnde_ffjord_config* c, rnde_ffjo
 extern "C" void rnde_ffjord_destroy(rnde_ffjord* h) {
     if (!h) return;
     for (void* p : {(void*)h->ws, (void*)h->tape, (void*)h->norm, (void*)h->e_buf, (void*)h->e_tape, (void*)h->replay, (void*)h->rws, (void*)h->pacc,
-                    (void*)h->ctl, (void*)h->meta, (void*)h->initrec, (void*)h->rec})
+                    (void*)h->ctl, (void*)h->meta, (void*)h->initrec, (void*)h->rec, (void*)h->qt, (void*)h->ctl_t, (void*)h->xch, (void*)h->xcc,
+                    (void*)h->abort_word})
         if (p) (void)hipFree(p);
     for (auto& v : h->ev) if (v) (void)hipEventDestroy(v);
     delete h;
@@ -148,14 +232,42 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
     Q.G = h->G; Q.p = p_dev; Q.x = x_dev; Q.e = dir > 0 ? e_dev : nullptr; Q.ws = h->ws;
     Q.tape = taped ? h->tape : nullptr; Q.logpx = dir > 0 ? logpx_dev : nullptr; Q.x_out = x_out_dev; Q.norm = h->norm;
     Q.dir = dir; Q.T = h->T; Q.Bp = h->Bp; Q.tbase = t1;
+    const int nt = (B + 15) / 16;
+    FtSolveParams TQ{};
+    if (h->engine == 1) {      // the tiled engine: every tile resident, one meeting per attempt (one XCD up to 32 tiles, agent scope above)
+        if (++h->epoch >= 500000u) { h->epoch = 1; FCHK(h, hipMemsetAsync(h->xch, 0, ((size_t)h->cfg.max_attempts + 4) * 3 * kMwMeetMax * 8, s)); }
+        TQ.F = P; TQ.G = h->TG; TQ.p = p_dev; TQ.x = x_dev; TQ.e = Q.e; TQ.ws = h->ws; TQ.tape = Q.tape; TQ.logpx = Q.logpx; TQ.x_out = x_out_dev;
+        TQ.norm = h->norm; TQ.initrec_t = h->initrec_t; TQ.ctl_t = h->ctl_t; TQ.qt = dir < 0 ? h->qt : nullptr;
+        TQ.meet = MwMeet{h->xch, h->abort_word, h->epoch, nt, nt > 32 ? 1 : 0};
+        TQ.xcc = h->xcc; TQ.xcd_slot = h->xcd_slot; TQ.dir = dir; TQ.Bp = h->Bp; TQ.ntiles = nt; TQ.tbase = t1;
+    }
     FCHK(h, hipEventRecord(h->ev[0], s));
-    hipLaunchKernelGGL(rnde_ffjord_solve_kernel, dim3(1), dim3(h->T), h->lds_bytes, s, Q);
+    if (h->engine == 1) hipLaunchKernelGGL(rnde_ffjordt_solve_kernel, dim3(TQ.meet.global ? nt : 8 * nt), dim3(kFtThreads), h->lds_bytes, s, TQ);
+    else hipLaunchKernelGGL(rnde_ffjord_solve_kernel, dim3(1), dim3(h->T), h->lds_bytes, s, Q);
     FCHK(h, hipGetLastError());
     FCHK(h, hipEventRecord(h->ev[1], s));
     StepState fin;
     FCHK(h, hipMemcpyAsync(&fin, h->ctl + 2, sizeof(StepState), hipMemcpyDeviceToHost, s));
+    if (h->engine == 1) {
+        FCHK(h, hipMemcpyAsync(h->h_chk.data(), h->abort_word, 4, hipMemcpyDeviceToHost, s));
+        if (!TQ.meet.global) FCHK(h, hipMemcpyAsync(h->h_chk.data() + 2, h->xcc, (size_t)nt * 4, hipMemcpyDeviceToHost, s));
+    }
     FCHK(h, hipStreamSynchronize(s));
     (void)hipEventElapsedTime(&h->fwd_ms, h->ev[0], h->ev[1]);
+    if (h->engine == 1) {
+        bool split = false;
+        for (int i = 1; i < nt && !TQ.meet.global; ++i) split |= h->h_chk[2 + i] != h->h_chk[2];
+        if (h->h_chk[0] != 0u || split) {      // no fall-back to other arithmetic: the call fails and says why
+            FCHK(h, hipMemsetAsync(h->abort_word, 0, 8, s));
+            FCHK(h, hipStreamSynchronize(s));
+            h->n_att = h->n_acc = 0; h->h_meta.clear();
+            h->err = split ? "TrackedFFJORD tiled engine: a workgroup meeting of the solve timed out (the tiles pinned to one XCD by block index "
+                             "landed on different XCDs); the solve was abandoned"
+                           : "TrackedFFJORD tiled engine: a workgroup meeting of the solve timed out (not every tile was resident); the solve was "
+                             "abandoned";
+            return RNDE_ERR_HIP;
+        }
+    }
     h->n_att = fin.n_att; h->n_acc = fin.n_acc; h->B = B;
     h->h_meta.resize(fin.n_att);
     if (fin.n_att) FCHK(h, hipMemcpy(h->h_meta.data(), h->meta, (size_t)fin.n_att * sizeof(StepMeta), hipMemcpyDeviceToHost));
@@ -238,9 +350,19 @@ extern "C" rnde_status rnde_ffjord_backward(rnde_ffjord* h, const float* logpx_b
     Q.G = h->G; Q.p = T.p; Q.e = T.e; Q.tape = h->tape; Q.rec = h->rec; Q.logpx_bar = logpx_bar_dev;
     Q.ws = h->rws; Q.pacc = h->pacc; Q.x_bar = x_bar_dev; Q.n_acc = T.n_acc; Q.B = T.B; Q.Bp = h->Bp; Q.reltol = T.reltol; Q.abstol = T.abstol;
     FCHK(h, hipEventRecord(h->ev[2], s));
-    hipLaunchKernelGGL(rnde_ffjord_reverse_kernel, dim3((T.B + 255) / 256), dim3(256), 0, s, Q);
-    FCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(rnde_ffjord_reduce_kernel, dim3((h->G.P + 255) / 256), dim3(256), 0, s, (const float*)h->pacc, h->G.P, T.B, h->Bp, p_bar_dev);
+    if (h->engine == 1) {
+        FtRevParams TQ{};
+        TQ.G = h->TG; TQ.p = T.p; TQ.e = T.e; TQ.tape = h->tape; TQ.rec = h->rec; TQ.logpx_bar = logpx_bar_dev; TQ.ws = h->rws; TQ.pacc = h->pacc;
+        TQ.x_bar = x_bar_dev; TQ.n_acc = T.n_acc; TQ.B = T.B; TQ.Bp = h->Bp; TQ.reltol = T.reltol; TQ.abstol = T.abstol;
+        const int nt = (T.B + 15) / 16;
+        hipLaunchKernelGGL(rnde_ffjordt_reverse_kernel, dim3(nt), dim3(kFtThreads), h->lds_bytes, s, TQ);
+        FCHK(h, hipGetLastError());
+        hipLaunchKernelGGL(rnde_ffjordt_reduce_kernel, dim3((h->G.P + 255) / 256), dim3(256), 0, s, (const float*)h->pacc, h->G.P, nt, p_bar_dev);
+    } else {
+        hipLaunchKernelGGL(rnde_ffjord_reverse_kernel, dim3((T.B + 255) / 256), dim3(256), 0, s, Q);
+        FCHK(h, hipGetLastError());
+        hipLaunchKernelGGL(rnde_ffjord_reduce_kernel, dim3((h->G.P + 255) / 256), dim3(256), 0, s, (const float*)h->pacc, h->G.P, T.B, h->Bp, p_bar_dev);
+    }
     FCHK(h, hipGetLastError());
     FCHK(h, hipEventRecord(h->ev[3], s));
     FCHK(h, hipEventSynchronize(h->ev[3]));
@@ -265,8 +387,12 @@ extern "C" rnde_status rnde_ffjord_sample(rnde_ffjord* h, const float* p_dev, co
 extern "C" rnde_status rnde_ffjord_debug_feval(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t,
                                                int32_t exact, float* out_dev, void* stream) {
     if (!h || !x_dev || !p_dev || !out_dev || B < 1 || B > h->cfg.max_batch || (!exact && !e_dev)) { if (h) h->err = "bad argument"; return RNDE_ERR_BAD_ARG; }
-    hipLaunchKernelGGL(rnde_ffjord_feval_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->G, p_dev, x_dev, e_dev, t, B, exact,
-                       h->rws, out_dev);
+    if (h->engine == 1)
+        hipLaunchKernelGGL(rnde_ffjordt_feval_kernel, dim3((B + 15) / 16), dim3(kFtThreads), h->lds_bytes, (hipStream_t)stream, h->TG, p_dev, x_dev, e_dev,
+                           t, B, exact, h->rws, h->qt, out_dev);
+    else
+        hipLaunchKernelGGL(rnde_ffjord_feval_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->G, p_dev, x_dev, e_dev, t, B, exact,
+                           h->rws, out_dev);
     FCHK(h, hipGetLastError());
     return RNDE_OK;
 }

@@ -7,9 +7,12 @@ calls replaced by librnde.so (rnde_ffjord_*: one launch per adaptive solve, one 
     xs = sample(ffjord, 2, nsamples=1024)
 
 Served: the two call methods the FFJORD experiments use -- TrackedFFJORD{false} with regularize = false and TrackedFFJORD{true}
-(EEst * dt saved per accepted step) -- for widths in_dims + 1 <= 64 and hidden <= 64, and sample().  Refused with a message that names
-the limit: any other dynamics (the default forw_n_back through Tracker.forward), wider models (the tabular experiment's 43 -> 100), and
-the {false} method's regularize = true rows.
+(EEst * dt saved per accepted step) -- and sample(), on one of two engines:
+    engine="workgroup" (default): the whole batch in one workgroup, widths in_dims + 1 <= 64 and hidden <= 64;
+    engine="tiled": one workgroup per 16 columns, layer products on the matrix cores, in_dims <= 64 and hidden <= 112 (the tabular
+                    experiment's MLPDynamics(43, 100)), max_batch <= 4096.
+Refused with a message that names the limit: any other dynamics (the default forw_n_back through Tracker.forward), widths above the
+engine's limit, and the {false} method's regularize = true rows.
 """
 import ctypes as C
 import math
@@ -20,6 +23,8 @@ import torch
 from . import _lib
 
 MAX_WIDTH = 64
+TILED_MAX_IN, TILED_MAX_HIDDEN, TILED_MAX_BATCH = 64, 112, 4096
+ENGINES = ("workgroup", "tiled")
 
 
 def _glorot(rows, cols, gen):
@@ -67,14 +72,19 @@ def param_count(in_dims, hidden):
     return (hidden * in_dims + 4 * hidden) + (hidden * hidden + 4 * hidden) + (in_dims * hidden + 4 * in_dims)
 
 
-def check_served(model, regularize_kinetic=False):
-    """ValueError naming the limit for what the kernels do not serve."""
+def check_served(model, regularize_kinetic=False, engine="workgroup"):
+    """ValueError naming the limit for what the kernels of `engine` do not serve."""
+    if engine not in ENGINES:
+        raise ValueError(f"TrackedFFJORD: engine must be one of {ENGINES}; got {engine!r}")
     if not isinstance(model, MLPDynamics):
         raise ValueError("TrackedFFJORD: only the ConcatSquash MLPDynamics of experiments/ffjord_gaussian.jl (dynamics = forw_n_back) is served; "
                          "the default forw_n_back (TDChain / Dense dynamics through Tracker.forward) is not")
-    if model.in_dims + 1 > MAX_WIDTH or model.hidden > MAX_WIDTH:
+    if engine == "workgroup" and (model.in_dims + 1 > MAX_WIDTH or model.hidden > MAX_WIDTH):
         raise ValueError(f"TrackedFFJORD: widths above the chain engine's limit of {MAX_WIDTH} are not served (in_dims + 1 <= 64 and hidden <= 64; "
-                         f"got in_dims = {model.in_dims}, hidden = {model.hidden})")
+                         f"got in_dims = {model.in_dims}, hidden = {model.hidden}; engine=\"tiled\" serves wider models)")
+    if engine == "tiled" and (model.in_dims > TILED_MAX_IN or model.hidden > TILED_MAX_HIDDEN):
+        raise ValueError(f"TrackedFFJORD tiled engine: widths above its LDS limit are not served (in_dims <= {TILED_MAX_IN} and hidden <= "
+                         f"{TILED_MAX_HIDDEN}; got in_dims = {model.in_dims}, hidden = {model.hidden})")
     if regularize_kinetic:
         raise ValueError("TrackedFFJORD{false} with regularize = true (kinetic energy and Jacobian norm rows) is not served")
 
@@ -92,9 +102,10 @@ class _Handle:
     """One rnde_ffjord handle.  A handle holds ONE tape: `gen` counts the taped forwards run on it, `busy` is set while a taped forward
     waits for its backward (or for its graph to be dropped)."""
 
-    def __init__(self, cfg):
+    def __init__(self, cfg, engine="workgroup"):
         self.h = C.c_void_p()
-        _lib.check_ffjord(None, _lib.lib().rnde_ffjord_create(C.byref(cfg), C.byref(self.h)))
+        create = _lib.lib().rnde_ffjord_create_tiled if engine == "tiled" else _lib.lib().rnde_ffjord_create
+        _lib.check_ffjord(None, create(C.byref(cfg), C.byref(self.h)))
         self.gen, self.busy = 0, False
 
     def __del__(self):
@@ -183,13 +194,16 @@ class _Solve(torch.autograd.Function):
 class TrackedFFJORD:
     """TrackedFFJORD(model, tspan, time_dep, regularize, solver; reltol, abstol, ...) (ffjord.jl:1-51).  regularize selects the call
     method: False -> TrackedFFJORD{false} (returns logpx, 0, 0, nfe, None), True -> TrackedFFJORD{true} (returns logpx, 0, 0, nfe, sv with
-    sv.saveval = EEst * dt per accepted step, differentiable)."""
+    sv.saveval = EEst * dt per accepted step, differentiable).  engine: "workgroup" (default) or "tiled" (see the module docstring)."""
 
     def __init__(self, model, tspan, time_dep, regularize, solver="Tsit5", *, reltol=1.4e-8, abstol=1.4e-8, max_batch=1024, max_attempts=4096,
-                 cb_save_start=True, device=0, dynamics=None, **kwargs):
+                 cb_save_start=True, device=0, dynamics=None, engine="workgroup", **kwargs):
         if dynamics is not None and dynamics != "forw_n_back":
             raise ValueError("TrackedFFJORD: only dynamics = forw_n_back of the ConcatSquash MLPDynamics is served")
-        check_served(model)
+        check_served(model, engine=engine)
+        if engine == "tiled" and int(max_batch) > TILED_MAX_BATCH:
+            raise ValueError(f"TrackedFFJORD tiled engine: max_batch above {TILED_MAX_BATCH} is not served (one meeting holds 256 resident tiles)")
+        self.engine = engine
         if solver != "Tsit5":
             raise ValueError("TrackedFFJORD: only Tsit5 is served")
         self.model, self.tspan, self.time_dep, self.regularize = model, (float(tspan[0]), float(tspan[1])), bool(time_dep), bool(regularize)
@@ -211,7 +225,7 @@ class TrackedFFJORD:
 
     def _handle(self):
         if self._h is None:
-            self._h = _Handle(self.config())
+            self._h = _Handle(self.config(), self.engine)
         return self._h
 
     def _taped_handle(self):
@@ -221,7 +235,7 @@ class TrackedFFJORD:
         if len(self._pool) >= MAX_TAPES:
             raise RuntimeError(f"TrackedFFJORD: {MAX_TAPES} taped forwards are waiting for their backward pass; run backward (or drop the graphs) "
                                "before taping more")
-        self._pool.append(_Handle(self.config()))
+        self._pool.append(_Handle(self.config(), self.engine))
         return self._pool[-1]
 
     def draw_normal(self, rows, cols, device):
@@ -233,7 +247,7 @@ class TrackedFFJORD:
 
     def __call__(self, x, p=None, e=None, regularize=False, steps=None):
         if regularize and not self.regularize:
-            check_served(self.model, regularize_kinetic=True)
+            check_served(self.model, regularize_kinetic=True, engine=self.engine)
         p = self.p if p is None else p
         if not (x.is_cuda and p.is_cuda):
             raise RuntimeError("TrackedFFJORD runs on the device only: x and p must be cuda tensors")
@@ -347,5 +361,18 @@ def load_gaussian_mixture(batchsize, train_test_split=0.75, *, nsamples=1000, ng
         samples = mu[None, :] + sigma * rng.standard_normal((per, dim))
         X[i * per:(i + 1) * per] = (samples + noise * rng.standard_normal((per, dim))).astype(np.float32)
     X = X[rng.permutation(X.shape[0])]
+    ntrain = int(math.floor(train_test_split * X.shape[0]))
+    return _Loader(X[:ntrain].copy(), batchsize, True, seed + 1), _Loader(X[ntrain:].copy(), batchsize, False, seed + 2)
+
+
+def load_miniboone(batchsize, path, train_test_split=0.8, seed=0):
+    """src/dataset.jl:33-56: MiniBooNE from a (N, 43) array file (miniboone.npy), each feature standardised with its mean and its corrected
+    standard deviation, the samples shuffled, then split train / test.  Returns (train loader, test loader) of (B, 43) float32 batches."""
+    X = np.load(path).astype(np.float64)
+    if X.ndim != 2:
+        raise ValueError(f"expected a 2-d array (samples, features); got shape {X.shape}")
+    X = (X - X.mean(0, keepdims=True)) / X.std(0, ddof=1, keepdims=True)
+    rng = np.random.default_rng(seed)
+    X = X[rng.permutation(X.shape[0])].astype(np.float32)
     ntrain = int(math.floor(train_test_split * X.shape[0]))
     return _Loader(X[:ntrain].copy(), batchsize, True, seed + 1), _Loader(X[ntrain:].copy(), batchsize, False, seed + 2)
