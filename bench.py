@@ -7,13 +7,19 @@ update -- on one batch of 512 synthetic MNIST-shaped images per GPU, already res
 N > 1: one process per GPU (torchrun), batch sharded 512 per rank (weak scaling, config "batch 4096 sharded
 8xMI355X"), one RCCL all-reduce of the flat gradient (166,418 fp32) per step.
 
-Prints ONE JSON line on rank 0.  Besides the contract's keys:
+A plain run sets up, steps through the fixed-weights leg (the headline has always been timed behind it; main() says why), warms up, times
+the steps, writes --dump-outputs and prints ONE JSON line on rank 0: the contract's keys with mean_nfe, final_loss and the run's configuration.
+`--full` also measures, on the same line:
   value_fixed_weights   the same K steps with the weights restored after every update (the optimiser still runs): NFE does not
                         drift with the number of steps, so this number is comparable across --steps/--warmup choices
   attempts_per_step, us_per_attempt_fwd / _rev, rev_rest_ms, persist_fallback   NFE-independent companions (HIP events)
   roofline      the dominant kernel (the TAPED attempted-step kernel, as a training step runs it) timed live with HIP events
   cpu_baseline  the CPU restatement (oracle/, OpenMP) timed on a bounded sample of the same workload
-  other_workloads   N = 1 only: config 4 (latent-ODE dynamics, chain engine) and config 5 (MNIST neural SDE) records
+  roofline_B4096, other_workloads   N = 1 only: the roofline unit at B = 4096, config 4 (latent-ODE dynamics, chain engine),
+                config 5 (MNIST neural SDE) and the full step at a batch of 4096 (global4096) records
+  dist          N > 1 only: per-rank NFE and fallbacks, the all-reduce timed alone, and the other collective path beside it
+--no-extras (which also drops the fixed-weights leg from a plain run) and --no-cpu-baseline trim a --full run.  --full does not change the
+--workload runs other than mnist.
 """
 import argparse
 import ctypes as C
@@ -548,8 +554,10 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=512, help="per-GPU batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the fixed-weights leg and the config 4 / config 5 records")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the fixed-weights leg, the per-attempt companions and roofline, the CPU "
+                    "baseline, the B = 4096 and config 4 / config 5 records (N = 1), the dist diagnostics and the other collective path (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="skip the fixed-weights leg and (--full) the B = 4096 / config 4 / config 5 records")
     ap.add_argument("--col-tile", type=int, default=0)
     ap.add_argument("--autograd", action="store_true", help="head + loss through torch.autograd instead of the fused C-ABI head")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (RCCL) and run the gradient all-reduce even at world size 1: exercises the N > 1 code path on a 1-GPU box")
@@ -694,13 +702,16 @@ def main():
             mean_nfe = sum(nfes) / len(nfes)
         return el, mean_nfe, float(last)
 
-    # fixed-weights leg FIRST (from the initial weights: stationary by construction), then the real training leg
+    # fixed-weights leg FIRST (from the initial weights: stationary by construction), then the real training leg.  A plain run steps through this
+    # leg too and reports it only under --full: the headline has always been timed behind it, and without it the first timed steps run up to
+    # 0.1 ms slower (per-step HIP events at B = 512; the gap closes over ~10 steps), 1.4 % of the 20-step headline at bit-identical outputs
     fixed = None
     if not args.no_extras:
         for _ in range(args.warmup):
             train_step(True)
         el_f, nfe_f, _ = timed(True)
-        fixed = {"value": world * B * args.steps / el_f, "ms_per_step": 1e3 * el_f / args.steps, "mean_nfe": nfe_f}
+        if args.full:
+            fixed = {"value": world * B * args.steps / el_f, "ms_per_step": 1e3 * el_f / args.steps, "mean_nfe": nfe_f}
         opt = rn.FluxOptimiser(model.trainable())                         # fresh optimiser state for the training leg
     quiet_gc()
     for _ in range(args.warmup):
@@ -709,9 +720,9 @@ def main():
     if dump is not None and rank == 0:
         write_outputs(args.dump_outputs, dict(dump, p2_after_step=model.p2, p3_after_step=model.p3))
 
-    # ---- N > 1 diagnostics (every rank takes part): per-rank NFE and persistent-kernel fallbacks, and the all-reduce on its own (HIP events) ----
+    # ---- --full, N > 1 diagnostics (every rank takes part): per-rank NFE and persistent-kernel fallbacks, and the all-reduce on its own (HIP events) ----
     dist_diag = None
-    if use_dist:
+    if use_dist and args.full:
         hh = model.node._acquire(x.reshape(B, -1), True)
         mine = torch.tensor([float(sum(nfes) / max(1, len(nfes))), float(L.rnde_node_fallback_count(hh.ptr)), float(L.rnde_node_launches_per_attempt(hh.ptr))],
                             device=ddev, dtype=torch.float64)
@@ -743,9 +754,29 @@ def main():
                      "collective_fallback": getattr(reducer, "fallback_reason", None) if reducer is not None else None}
 
     out = None
+    if rank == 0:
+        out = {"metric": "training-step samples/sec + mean NFE, MNIST Neural ODE bs=512",
+               "value": world * B * args.steps / elapsed, "unit": "samples/s", "n_gpus": world, "steps": args.steps,
+               "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
+               "scaling": "strong" if args.global_batch else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+               "mean_nfe": mean_nfe, "final_loss": last_loss,
+               # what this line can NOT say (no Julia runtime, no MNIST files, no network where it is built or run): the device is checked against the builder's
+               # CPU restatement of the published algorithms, never against a run of the reference itself
+               "parity_vs_reference": "unpinned (device == oracle/ restatement at the reference tolerance; no Julia-produced vector exists: SURVEY 8c, DESIGN.md 2)",
+               "accuracy_vs_reference": "unmeasured (no MNIST, no Julia; synthetic learnable set only: DESIGN.md 7)",
+               "controller": "coupled (one controller for all ranks, SURVEY 8e mode 2)" if args.coupled else "independent per rank (SURVEY 8e mode 1)",
+               "collective": (None if not use_dist else "rnde_comm_allreduce (librnde.so; path: dist.collective_path of --full): ONE sum-all-reduce of the flat gradient buffer [p2-bar | p3-bar] "
+                              "behind the reverse pass, on the compute stream; 1/world folded into the optimiser launch"),
+               "rig": rig_note,
+               "config": {"workload": f"MNIST NODE regularized (error_est), Tsit5 reltol=abstol=1.4e-8, batch {B} per GPU, "
+                                      "1xMI355X per rank; step = loss fwd + reverse pass through the solver + "
+                                      "InvDecay/Momentum update; the weights train during the timed steps (mean_nfe drifts with "
+                                      "--steps: value_fixed_weights of --full is the stationary companion)"
+                                      + (f"; STRONG scaling: global batch {args.global_batch} split over {world} rank(s)" if args.global_batch else ""), "global_batch": world * B,
+                          "parallelism": f"dp{world}" if world > 1 else "single"}}
     if args.coupled:
         model.node.set_coupling(None, 0)     # the legs below run on rank 0 alone: a shared controller would wait there for the other ranks
-    if rank == 0:
+    if rank == 0 and args.full:
         h = model.node._acquire(x.reshape(B, -1), True)
         # --- NFE-independent companions: HIP events around the attempted steps of the forward and the reverse sweep, 3 steps ---
         L.rnde_node_set_timing(h.ptr, 1)
@@ -833,33 +864,14 @@ def main():
                     roof["ceiling_source"] = "profiles/" + ABLATION_ROUND + "_attempt_ablation.csv: the fp32-input-MFMA attempt kernel's MFMAs alone (matrix mode 0: operands in registers, no polls / tanh / LDS / tape), same launch geometry, back to back -- NOT a bound of matrix mode 1, whose products run on the matrix cores"
         except Exception:
             pass
-        out = {"metric": "training-step samples/sec + mean NFE, MNIST Neural ODE bs=512",
-               "value": world * B * args.steps / elapsed, "unit": "samples/s", "n_gpus": world, "steps": args.steps,
-               "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
-               "scaling": "strong" if args.global_batch else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-               "mean_nfe": mean_nfe, "final_loss": last_loss,
-               # what this line can NOT say (no Julia runtime, no MNIST files, no network in the build or on the GPU box): the device is checked against the builder's
-               # CPU restatement of the published algorithms, never against a run of the reference itself
-               "parity_vs_reference": "unpinned (device == oracle/ restatement at the reference tolerance; no Julia-produced vector exists: SURVEY 8c, DESIGN.md 2)",
-               "accuracy_vs_reference": "unmeasured (no MNIST, no Julia; synthetic learnable set only: DESIGN.md 7)",
-               "value_fixed_weights": None if fixed is None else fixed["value"],
-               "fixed_weights": fixed,
-               "attempts_per_step": sum(atts) / len(atts),
-               "us_per_attempt_fwd": 1e3 * sum(fa) / max(1, sum(atts)),
-               "us_per_attempt_rev": 1e3 * sum(rs) / max(1, sum(atts)),
-               "rev_rest_ms": sum(rr) / len(rr),
-               "persist_fallback": bool(stage_engine and nl != 1), "persist_fallback_count": int(L.rnde_node_fallback_count(h.ptr)),
-               "controller": "coupled (one controller for all ranks, SURVEY 8e mode 2)" if args.coupled else "independent per rank (SURVEY 8e mode 1)",
-               "collective": (None if not use_dist else "rnde_comm_allreduce (librnde.so; path: see dist.collective_path): ONE sum-all-reduce of the flat gradient buffer [p2-bar | p3-bar] "
-                              "behind the reverse pass, on the compute stream; 1/world folded into the optimiser launch"),
-               "rig": rig_note,
-               "config": {"workload": f"MNIST NODE regularized (error_est), Tsit5 reltol=abstol=1.4e-8, batch {B} per GPU, "
-                                      "1xMI355X per rank; step = loss fwd + reverse pass through the solver + "
-                                      "InvDecay/Momentum update; the weights train during the timed steps (mean_nfe drifts with "
-                                      "--steps: value_fixed_weights is the stationary companion)"
-                                      + (f"; STRONG scaling: global batch {args.global_batch} split over {world} rank(s)" if args.global_batch else ""), "global_batch": world * B,
-                          "parallelism": f"dp{world}" if world > 1 else "single"},
-               "roofline": roof}
+        out.update({"value_fixed_weights": None if fixed is None else fixed["value"],
+                    "fixed_weights": fixed,
+                    "attempts_per_step": sum(atts) / len(atts),
+                    "us_per_attempt_fwd": 1e3 * sum(fa) / max(1, sum(atts)),
+                    "us_per_attempt_rev": 1e3 * sum(rs) / max(1, sum(atts)),
+                    "rev_rest_ms": sum(rr) / len(rr),
+                    "persist_fallback": bool(stage_engine and nl != 1), "persist_fallback_count": int(L.rnde_node_fallback_count(h.ptr)),
+                    "roofline": roof})
         if dist_diag is not None:
             out["dist"] = dist_diag
         if world == 1 and not args.no_cpu_baseline:

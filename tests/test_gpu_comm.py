@@ -173,7 +173,7 @@ def test_bench_runs_two_ranks_on_one_gpu_through_the_one_shot_collective(coupled
         so.bind(("127.0.0.1", 0))
         port = so.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "64", "--share-gpu", "--no-cpu-baseline"] + ([] if strong else ["--no-extras"]) + (["--coupled"] if coupled else []) + (["--global-batch", "96"] if strong else [])
+           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "64", "--share-gpu", "--full", "--no-cpu-baseline"] + ([] if strong else ["--no-extras"]) + (["--coupled"] if coupled else []) + (["--global-batch", "96"] if strong else [])
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -331,7 +331,7 @@ def test_bench_runs_eight_ranks_of_512_on_one_gpu_config3_rehearsal(share_gpu=Fa
         so.bind(("127.0.0.1", 0))
         port = so.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--global-batch", "4096", "--no-cpu-baseline", "--no-extras"]
+           os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--global-batch", "4096", "--full", "--no-cpu-baseline", "--no-extras"]
     cmd += ["--share-gpu"] if share_gpu else []
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]

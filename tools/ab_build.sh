@@ -17,6 +17,6 @@ sp = importlib.util.spec_from_file_location('_b', 'regneuralde.jl_amd/build.py')
 fi
 for rep in 1 2 3; do
   for v in "$@"; do
-    RNDE_LIB=$(libof $v) timeout 300 python bench.py --steps 10 --warmup 3 --no-extras --no-cpu-baseline ${AB_ARGS} 2>/dev/null | tail -1 | python -c "import sys, json; d = json.loads(sys.stdin.read()); print('$N=$v', round(d['value']), 'samples/s', round(d['ms_per_step'], 3), 'ms  fwd', round(d.get('us_per_attempt_fwd', 0), 2), 'rev', round(d.get('us_per_attempt_rev', 0), 2), 'nfe', d.get('mean_nfe'))"
+    RNDE_LIB=$(libof $v) timeout 300 python bench.py --steps 10 --warmup 3 --full --no-extras --no-cpu-baseline ${AB_ARGS} 2>/dev/null | tail -1 | python -c "import sys, json; d = json.loads(sys.stdin.read()); print('$N=$v', round(d['value']), 'samples/s', round(d['ms_per_step'], 3), 'ms  fwd', round(d.get('us_per_attempt_fwd', 0), 2), 'rev', round(d.get('us_per_attempt_rev', 0), 2), 'nfe', d.get('mean_nfe'))"
   done
 done

@@ -32,12 +32,12 @@ pmc() {     # name, bench arguments: HBM traffic, two separate passes
 for w in $WHAT; do
   case $w in
     stats)
-      stats bench --steps 20 --warmup 5 --no-cpu-baseline --no-extras
+      stats bench --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras
       stats latent --workload latent --steps 20 --warmup 5
       stats latent_e2e --workload latent_e2e --steps 20 --warmup 5
       stats nsde --workload nsde --steps 20 --warmup 5 ;;
-    pmc) pmc "" --steps 3 --warmup 1 --no-cpu-baseline --no-extras ;;
-    pmc4096) pmc _B4096 --batch 4096 --steps 2 --warmup 1 --no-cpu-baseline --no-extras ;;
+    pmc) pmc "" --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras ;;
+    pmc4096) pmc _B4096 --batch 4096 --steps 2 --warmup 1 --full --no-cpu-baseline --no-extras ;;
     sq) R=$R bash tools/gpu_pmc_sq.sh > $O/sq.log 2>&1; cp gpurun_out/${R}sq/${R}_pmc_sq_attempt.csv $O/ 2>/dev/null; cat $O/${R}_pmc_sq_attempt.csv | cut -c1-160 ;;
     ablation) timeout 600 python3 tools/experiments/attempt_ablation/ablate_attempt.py > $O/${R}_attempt_ablation.csv 2> $O/ablation.err; cat $O/${R}_attempt_ablation.csv ;;
   esac

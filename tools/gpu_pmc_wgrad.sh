@@ -6,7 +6,7 @@ rocprofv3 --list-avail 2>/dev/null | grep -o "SQ_[A-Z_0-9]*\(MFMA\|LDS\|WAIT\|BU
 for c in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES" "SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" "SQ_WAIT_INST_ANY SQ_WAVE_CYCLES" "SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_LDS"; do
   d=gpurun_out/pmcw/$(echo $c | tr ' ' '+')
   rm -rf $d
-  timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $d -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras > $d.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $d -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-extras > $d.log 2>&1
   python3 - "$d" <<'PY'
 import csv, glob, sys, collections
 d = sys.argv[1]

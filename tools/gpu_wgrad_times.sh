@@ -11,7 +11,7 @@ for v in "$@"; do
     "") ;;
     *) export RNDE_LIB=$GRAFT_REPO_ROOT/regneuralde.jl_amd/lib/librnde_$v.so;;
   esac
-  if [ -n "$PROBE" ]; then timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/wprof -- python3 tools/wgrad_probe.py > /tmp/wprof_bench.log 2>&1; else timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/wprof -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras > /tmp/wprof_bench.log 2>&1; fi
+  if [ -n "$PROBE" ]; then timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/wprof -- python3 tools/wgrad_probe.py > /tmp/wprof_bench.log 2>&1; else timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/wprof -- python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-extras > /tmp/wprof_bench.log 2>&1; fi
   python3 - "$v" <<'P'
 import csv, glob, sys, json
 f = glob.glob("/tmp/wprof/*/*kernel_trace.csv")[0]

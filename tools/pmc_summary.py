@@ -11,7 +11,7 @@ def load(d, name):
     return agg
 F, W = load(fetch_dir, "FETCH_SIZE"), load(write_dir, "WRITE_SIZE")
 import datetime, os
-print("# rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- " + os.environ.get("PMC_CMD", "python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras"))
+print("# rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- " + os.environ.get("PMC_CMD", "python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extras"))
 print("# collected " + datetime.datetime.utcnow().strftime("%Y-%m-%d %H:%M UTC") + (" at " + os.environ["RNDE_COMMIT"] if os.environ.get("RNDE_COMMIT") else ""))
 print("# corrected bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024 : FETCH_SIZE under-reports wide reads 2x on gfx950 (MI355X_MICROARCH.md, HBM)")
 print("kernel,dispatches,FETCH_SIZE_mean_KiB,WRITE_SIZE_mean_KiB,hbm_bytes_per_launch_corrected")
