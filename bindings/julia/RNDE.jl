@@ -14,6 +14,7 @@
 module RNDE
 
 import AMDGPU                                   # (binds the module name too: AMDGPU.stream(), AMDGPU.synchronize() below)
+import Flux                                     # (NNlib's activations as Flux re-exports them: act_code below)
 using AMDGPU: ROCArray, ROCVector, ROCMatrix
 using Tracker
 using Tracker: TrackedArray, data, track, @grad
@@ -286,6 +287,20 @@ struct NsdeConfig   # mirrors rnde_nsde_config
     beta1::Float32; beta2::Float32; gamma::Float32; qmin::Float32; qmax::Float32; qoldinit::Float32; delta::Float32
     generic::Int32
     stability_size::Float32      # RNDE_REG_STIFF: 0 = alg_stability_size(SOSRI2()) = 10.6
+end
+
+# The activation of a Dense layer (include/rnde.h: rnde_act), recognised by identity (===) with NNlib's functions as Flux re-exports them:
+# Dense(in, out, relu) holds `relu` itself.  A closure such as `x -> elu(x, 0.5)` or an activation whose derivative needs the pre-activation
+# (swish, gelu) is refused -- a layer that ran another map would integrate another vector field.  Shared by patch_neural_ode.jl and patch_neural_sde.jl.
+const ACT_IDENTITY, ACT_TANH, ACT_RELU, ACT_SIGMOID, ACT_SOFTPLUS, ACT_ELU = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4), Int32(5)
+function act_code(f)
+    f === identity && return ACT_IDENTITY
+    f === tanh && return ACT_TANH
+    f === Flux.relu && return ACT_RELU
+    f === Flux.σ && return ACT_SIGMOID
+    f === Flux.softplus && return ACT_SOFTPLUS
+    f === Flux.elu && return ACT_ELU
+    error("RNDE: Dense activation ", f, " is not served (identity, tanh, relu, σ, softplus, elu)")
 end
 
 # The leading element-wise map of a dynamics chain (include/rnde.h: rnde_pre_act): `x -> tanh.(x)` (experiments/latent_ode.jl:114) or `x -> x .^ 3`

@@ -21,8 +21,9 @@ const TSIT5_STABILITY_SIZE = 3.5068      # OrdinaryDiffEq.alg_stability_size(Tsi
 
 # Dense sizes / activations of the dynamics (TDChain or Chain of Dense layers; a leading `x -> tanh.(x)` is latent_ode.jl:114's pre-activation).
 # Anything the library cannot represent is REFUSED here -- a layer that is silently skipped would integrate another vector field:
-# every layer must be a Flux.Dense with tanh or identity, except ONE leading element-wise function that is tanh or the cube (RNDE.pre_act_code).
-_act_code(σ) = σ === tanh ? 1 : (σ === identity ? 0 : error("RNDE: Dense activation ", σ, " is not served (tanh / identity)"))
+# every layer must be a Flux.Dense with a served activation (RNDE.act_code: identity, tanh, relu, σ, softplus, elu), except ONE leading
+# element-wise function that is tanh or the cube (RNDE.pre_act_code).
+_act_code(σ) = RNDE.act_code(σ)
 _is_tanh_layer(l) = !(l isa Flux.Dense) && (v = Float32[-0.7, 0.1, 0.9]; try l(v) ≈ tanh.(v) catch; false end)
 function _dense_layout(model)
     layers = collect(model.layers)

@@ -11,7 +11,7 @@ const SOSRI2_STABILITY_SIZE = 10.6       # StochasticDiffEq.alg_stability_size(S
 const _SDE_SOLVERS = Dict(:SOSRI => 0, :SRIW1 => 1, :SOSRI2 => 2)      # rnde_sde_solver (include/rnde.h)
 const RNDE_SDE_CALLS = Ref(0)      # one Philox stream per call: seed = a counter (pass `seed = ...` for a reproducible run)
 
-# drift / diffusion as the library holds them: chains of Flux.Dense (tanh / identity) after at most ONE leading element-wise map, tanh or the cube
+# drift / diffusion as the library holds them: chains of Flux.Dense (activations: RNDE.act_code) after at most ONE leading element-wise map, tanh or the cube
 # (experiments/sde_toy_problem.jl:45: `x -> x .^ 3`, recognised by RNDE.pre_act_code).  A layer that cannot be represented is REFUSED, never skipped.
 function _chain_layout(model)
     ls = model isa Flux.Dense ? [model] : collect(model.layers)
@@ -21,7 +21,7 @@ function _chain_layout(model)
     dims = Int[size(ls[1].W, 2)]; acts = Int[]
     for l in ls
         push!(dims, size(l.W, 1))
-        push!(acts, l.σ === tanh ? 1 : (l.σ === identity ? 0 : error("RNDE: Dense activation ", l.σ, " is not served (tanh / identity)")))
+        push!(acts, RNDE.act_code(l.σ))
     end
     return dims, acts, pre
 end

@@ -46,7 +46,20 @@ typedef enum {
     RNDE_ERR_NO_DEVICE = 7      /* no gfx950 device visible                                    */
 } rnde_status;
 
-typedef enum { RNDE_ACT_IDENTITY = 0, RNDE_ACT_TANH = 1 } rnde_act;
+/* rnde_node_config.act[l], rnde_nsde_config.drift_act[l] / diff_act[l]: the activation of Dense layer l (Flux's Dense(in, out, sigma)), NNlib's
+ * identity, tanh, relu, sigma, softplus and elu (alpha = 1).  The kernels compute, in fp32, with t = exp(-|z|):
+ *   relu      z < 0 ? 0 : z                                   (max(z, 0); a NaN stays NaN)
+ *   sigmoid   z >= 0 ? 1 / (1 + t) : t / (1 + t)
+ *   softplus  log1p(t) + max(z, 0)
+ *   elu       z > 0 ? z : expm1(z)
+ * and tanh with a polynomial / exp2 formula of at most 1.65 ulp.  Each derivative is taken from the layer's OUTPUT y, which is what the reverse pass
+ * keeps: tanh 1 - y^2, relu y > 0 ? 1 : 0, sigmoid y (1 - y), softplus -expm1(-y), elu y > 0 ? 1 : y + 1.  An activation whose derivative needs the
+ * pre-activation (swish, gelu) is not served.  These are the textbook formulas; agreement with NNlib's own code at rounding level is not pinned
+ * (it has not been compared).  Any other code is RNDE_ERR_BAD_ARG at create.  Where each is served: every Dense chain of width <= 64 (the chain
+ * engine, the SDE layer).  The stage engine (the two-layer TDChain form with act[0] = tanh, col_tile 0 / 16) serves identity or tanh in act[1] and
+ * refuses the rest by name.  The kernels with compile-time shapes (the latent-ODE widths, the SDE layer's 32 -> 64 -> 32 drift) serve identity
+ * and tanh: a chain with any other activation runs a separately compiled variant of the generic kernels. */
+typedef enum { RNDE_ACT_IDENTITY = 0, RNDE_ACT_TANH = 1, RNDE_ACT_RELU = 2, RNDE_ACT_SIGMOID = 3, RNDE_ACT_SOFTPLUS = 4, RNDE_ACT_ELU = 5 } rnde_act;
 /* rnde_node_config.pre_act (and rnde_nsde_set_pre_act): the element-wise map in front of the first Dense layer.  RNDE_PRE_TANH is the
  * leading tanh of experiments/latent_ode.jl:114, RNDE_PRE_CUBE the leading x -> x .^ 3 of experiments/sde_toy_problem.jl:45.  Any other value
  * is RNDE_ERR_BAD_ARG at create.  The kernels with compile-time shapes that skip the generic chain evaluation (the SDE layer's 32 -> 64 -> 32

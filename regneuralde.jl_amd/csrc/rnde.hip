@@ -33,6 +33,8 @@ StepParams make_params(rnde_node* h, const float* x, int B, float t0, float t1, 
 }
 
 static_assert(kCMaxL == RNDE_MAX_LAYERS, "chain engine layer limit");
+static_assert(ACT_IDENTITY == RNDE_ACT_IDENTITY && ACT_TANH == RNDE_ACT_TANH && ACT_RELU == RNDE_ACT_RELU && ACT_SIGMOID == RNDE_ACT_SIGMOID &&
+              ACT_SOFTPLUS == RNDE_ACT_SOFTPLUS && ACT_ELU == RNDE_ACT_ELU, "rnde_act codes of the kernels (rnde_device.h)");
 static bool chain_geo(const rnde_node_config* c, ChainGeo& G) {
     G = ChainGeo{};
     G.n_layers = c->n_layers; G.time_dep = c->time_dep ? 1 : 0; G.pre_act = c->pre_act;   // rnde_pre_act, checked by rnde_node_create
@@ -64,8 +66,12 @@ static rnde_status chain_create(const rnde_node_config* c, rnde_node** out) {
     h->cfg = *c; h->engine = 3; h->cg = G;
     h->D = c->dims[0]; h->H = 0; h->P = rnde_param_count(c); h->BT = 16;
     h->NKD = G.nksD <= 4 ? 4 : (G.nksD <= 8 ? 8 : 16);
+    // the kernels with compile-time shapes below (ALT, mw_lat) serve identity / tanh only: any other activation takes the generic kernels' variant
+    bool plain_acts = true;
+    for (int l = 0; l < G.n_layers; ++l) plain_acts = plain_acts && (G.act[l] == RNDE_ACT_IDENTITY || G.act[l] == RNDE_ACT_TANH);
+    h->chain_ga = plain_acts ? 0 : 1;      // (the identity / tanh kernels are compiled without the other maps: ALT / LAT = 2 serve them)
     {   // compile-time shape specialisation for the reference's own latent-ODE widths (rnde_chain.h: ALT)
-        bool alt = G.nksD == kAltA && !getenv("RNDE_CHAIN_GENERIC");
+        bool alt = plain_acts && G.nksD == kAltA && !getenv("RNDE_CHAIN_GENERIC");
         for (int l = 0; l <= G.n_layers && alt; ++l) alt = G.nks[l] == ((l & 1) ? kAltB : kAltA);
         h->chain_alt = alt ? 1 : 0;
     }
@@ -94,7 +100,7 @@ static rnde_status chain_create(const rnde_node_config* c, rnde_node** out) {
         if (c->col_tile == 65 && !fits) { g_create_err = "col_tile 65: the multi-wave kernels need the padded weight fragments in 160 KB of LDS"; delete h; return RNDE_ERR_BAD_ARG; }
         if (h->mw) h->nwg_max = ntiles;
         {   // experiments/latent_ode.jl:113-124 exactly: eight time-independent layers of widths 20 <-> 50
-            bool lat = h->mw && c->n_layers == kLatLayers && !c->time_dep && h->NKD == 8;
+            bool lat = plain_acts && h->mw && c->n_layers == kLatLayers && !c->time_dep && h->NKD == 8;
             for (int i = 0; i <= kLatLayers && lat; ++i) lat = c->dims[i] == lat_width(i);      // (the kernels leave out the k-steps of the padding: exact widths)
             const char* e = getenv("RNDE_CHAIN_LAT");
             h->mw_lat = (lat && !(e && e[0] == '0')) ? 1 : 0;
@@ -213,6 +219,11 @@ static hipError_t launch_chain_t(rnde_node* h, const ChainParams& Q, int n, floa
 }
 template <int MODE>
 static hipError_t launch_chain(rnde_node* h, const ChainParams& Q, int n, float* u_out, hipStream_t s) {
+    if (h->chain_ga) switch (h->NKD) {     // (any served activation: the ALT = 2 kernels)
+        case 4: return launch_chain_t<4, MODE, 2>(h, Q, n, u_out, s);
+        case 8: return launch_chain_t<8, MODE, 2>(h, Q, n, u_out, s);
+        default: return launch_chain_t<16, MODE, 2>(h, Q, n, u_out, s);
+    }
     switch (h->NKD) {
         case 4: return launch_chain_t<4, MODE>(h, Q, n, u_out, s);
         case 8: return h->chain_alt ? launch_chain_t<8, MODE, 1>(h, Q, n, u_out, s) : launch_chain_t<8, MODE>(h, Q, n, u_out, s);
@@ -239,6 +250,14 @@ static hipError_t launch_mw_t(rnde_node* h, const MwParams& Q, int n, hipStream_
 }
 template <int MODE>
 static hipError_t launch_mw(rnde_node* h, const MwParams& Q, int n, hipStream_t s) {
+    if (h->chain_ga) {     // any served activation: the LAT = 2 kernels
+        const int tab = h->rk_tab;
+        switch (h->NKD) {
+            case 4: return tab == 2 ? launch_mw_t<1, MODE, 2, 2>(h, Q, n, s) : (tab ? launch_mw_t<1, MODE, 1, 2>(h, Q, n, s) : launch_mw_t<1, MODE, 0, 2>(h, Q, n, s));
+            case 8: return tab == 2 ? launch_mw_t<2, MODE, 2, 2>(h, Q, n, s) : (tab ? launch_mw_t<2, MODE, 1, 2>(h, Q, n, s) : launch_mw_t<2, MODE, 0, 2>(h, Q, n, s));
+            default: return tab == 2 ? launch_mw_t<4, MODE, 2, 2>(h, Q, n, s) : (tab ? launch_mw_t<4, MODE, 1, 2>(h, Q, n, s) : launch_mw_t<4, MODE, 0, 2>(h, Q, n, s));
+        }
+    }
     if (h->rk_tab == 2) {      // S-stage table
         switch (h->NKD) {
             case 4: return launch_mw_t<1, MODE, 2>(h, Q, n, s);
@@ -322,7 +341,14 @@ extern "C" rnde_status rnde_node_create(const rnde_node_config* c, rnde_node** o
     if (c->pre_act != RNDE_PRE_NONE && c->pre_act != RNDE_PRE_TANH && c->pre_act != RNDE_PRE_CUBE) {
         g_create_err = "pre_act: RNDE_PRE_NONE, RNDE_PRE_TANH or RNDE_PRE_CUBE"; return RNDE_ERR_BAD_ARG;
     }
+    if (!rnde_check_acts(c->n_layers, c->act, "act", g_create_err)) return RNDE_ERR_BAD_ARG;
     const bool mnist_form = c->n_layers == 2 && c->time_dep && !c->pre_act && c->act[0] == RNDE_ACT_TANH;
+    if (mnist_form && c->col_tile != 64 && c->col_tile != 65 && c->act[1] != RNDE_ACT_IDENTITY && c->act[1] != RNDE_ACT_TANH) {
+        // (not handed to the chain engine instead: this form is the one for widths beyond its limit of 64)
+        g_create_err = std::string("act[1] = ") + rnde_act_name(c->act[1]) + ": the stage engine (two time-dependent layers, act[0] = tanh, no pre_act, col_tile 0 / 16) "
+                       "serves identity or tanh in its second layer; a chain of width <= 64 runs any served activation on the chain engine (col_tile 64 / 65)";
+        return RNDE_ERR_BAD_ARG;
+    }
     if ((c->solver == RNDE_SOLVER_DP5 || c->solver == RNDE_SOLVER_DOP853) && ((mnist_form && c->col_tile != 65) || c->col_tile == 64 || c->regularize >= RNDE_REG_STIFF)) {
         g_create_err = "DP5 / DOP853 run on the tableau-as-data kernels of the chain engine (col_tile 0 for Dense chains of width <= 64, or 65), callbacks none / EEst*dt";
         return RNDE_ERR_BAD_ARG;

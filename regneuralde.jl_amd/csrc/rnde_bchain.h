@@ -63,6 +63,45 @@ __device__ __forceinline__ void chain_zstage_t(const float (&ab)[kCMaxKs], bool 
     }
 }
 
+// the same for any served activation (the ALT = 2 kernels): the derivative is taken from the taped output by code (rnde_device.h: act_dy),
+// one straight-line loop per code; identity reads no output
+template <int MT, int CODE>
+__device__ __forceinline__ void chain_zscale_t(const float* op, float (&v)[4 * MT]) {
+    float o[4 * MT];
+#pragma unroll
+    for (int ks = 0; ks < 4 * MT; ++ks) o[ks] = op[ks * 64];
+#pragma unroll
+    for (int ks = 0; ks < 4 * MT; ++ks) v[ks] *= act_dy(CODE, o[ks]);
+}
+template <int MT>
+__device__ __forceinline__ void chain_zstage_act_t(const float (&ab)[kCMaxKs], int act, const float* op, float* zp, const float* wt, int td,
+                                                   float (&z)[kCMaxKs], float& tl) {
+    float v[4 * MT];
+#pragma unroll
+    for (int ks = 0; ks < 4 * MT; ++ks) v[ks] = ab[ks];
+    switch (act) {
+        case ACT_IDENTITY: break;
+        case ACT_TANH: chain_zscale_t<MT, ACT_TANH>(op, v); break;
+        case ACT_RELU: chain_zscale_t<MT, ACT_RELU>(op, v); break;
+        case ACT_SIGMOID: chain_zscale_t<MT, ACT_SIGMOID>(op, v); break;
+        case ACT_SOFTPLUS: chain_zscale_t<MT, ACT_SOFTPLUS>(op, v); break;
+        default: chain_zscale_t<MT, ACT_ELU>(op, v); break;
+    }
+#pragma unroll
+    for (int ks = 0; ks < kCMaxKs; ++ks) {
+        const float w = ks < 4 * MT ? v[ks < 4 * MT ? ks : 0] : 0.f;
+        if (ks < 4 * MT) zp[ks * 64] = w;
+        z[ks] = w;
+    }
+    if (td) {
+        float w[4 * MT];
+#pragma unroll
+        for (int ks = 0; ks < 4 * MT; ++ks) w[ks] = wt[ks * 64];
+#pragma unroll
+        for (int ks = 0; ks < 4 * MT; ++ks) tl = fmaf(z[ks], w[ks], tl);
+    }
+}
+
 // J_f^T product for the wave's 16 columns at the point (g, ts) whose value kout = f(g, ts) is on the tape.
 // Dumps every layer's input and pre-activation cotangent for the weight-gradient kernel; returns gbar and adds the
 // cotangent of the time input (TDChain layers) to tau.
@@ -112,7 +151,14 @@ __device__ __forceinline__ void chain_fbwd(const BChainParams& Q, const float* F
             }
             continue;
         }
-        switch (mto) {
+        if constexpr (ALT == 2) {
+            switch (mto) {
+                case 1: chain_zstage_act_t<1>(ab, G.act[l], op, zp, wt, G.time_dep, z, tl); break;
+                case 2: chain_zstage_act_t<2>(ab, G.act[l], op, zp, wt, G.time_dep, z, tl); break;
+                case 3: chain_zstage_act_t<3>(ab, G.act[l], op, zp, wt, G.time_dep, z, tl); break;
+                default: chain_zstage_act_t<4>(ab, G.act[l], op, zp, wt, G.time_dep, z, tl); break;
+            }
+        } else switch (mto) {
             case 1: chain_zstage_t<1>(ab, th, op, zp, wt, G.time_dep, z, tl); break;
             case 2: chain_zstage_t<2>(ab, th, op, zp, wt, G.time_dep, z, tl); break;
             case 3: chain_zstage_t<3>(ab, th, op, zp, wt, G.time_dep, z, tl); break;

@@ -29,7 +29,25 @@ struct BMwParams {
 
 // J_f^T product at a taped evaluation.  kout = f's value (element-wise), kbar its cotangent; returns gbar (element-wise) and adds
 // this lane's share of the time cotangent to tau.  ZA, ZB: 64 x 16 LDS buffers.  sl: slab base of this (evaluation, tile).
-template <int NR>
+// GA = 1 (the LAT = 2 kernels): the derivative of any served activation, from the taped output (rnde_device.h: act_dy), one loop per code;
+// GA = 0 serves identity and tanh.
+template <int N, int CODE>
+__device__ __forceinline__ void mw_dy_t(float* v, const float* y) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] *= act_dy(CODE, y[i]);
+}
+template <int N>
+__device__ __forceinline__ void mw_dy(int act, float* v, const float* y) {
+    switch (act) {
+        case ACT_IDENTITY: break;
+        case ACT_TANH: mw_dy_t<N, ACT_TANH>(v, y); break;
+        case ACT_RELU: mw_dy_t<N, ACT_RELU>(v, y); break;
+        case ACT_SIGMOID: mw_dy_t<N, ACT_SIGMOID>(v, y); break;
+        case ACT_SOFTPLUS: mw_dy_t<N, ACT_SOFTPLUS>(v, y); break;
+        default: mw_dy_t<N, ACT_ELU>(v, y); break;
+    }
+}
+template <int NR, int GA = 0>
 __device__ __forceinline__ void mw_fbwd(const MwGeo& G, const float* FRt, const float* TV, float* ZA, float* ZB, float* __restrict__ sl,
                                         const float (&gin)[NR], const float (&kout)[NR], const float (&kbar)[NR], float (&gb)[NR], float& tau,
                                         int tid, int wave, int lane) {
@@ -46,11 +64,15 @@ __device__ __forceinline__ void mw_fbwd(const MwGeo& G, const float* FRt, const 
     }
     float tl = 0.f;
     // z of the last layer, element-wise
+    float zl[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) zl[r] = kbar[r];
+    if constexpr (GA) mw_dy<NR>(G.act[Lr - 1], zl, kout);
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
         const int e = tid + 256 * r;
-        float v = kbar[r];
-        if (G.act[Lr - 1] != 0) v *= (1.f - kout[r] * kout[r]);
+        float v = zl[r];
+        if (!GA && G.act[Lr - 1] != 0) v *= (1.f - kout[r] * kout[r]);
         if (e < 16 * 16 * G.mt[Lr]) { ZA[e] = v; sl[(size_t)G.zrow[Lr - 1] * 64 + e] = v; }
         if (G.time_dep) tl = fmaf(v, TV[(Lr - 1) * 64 + (e >> 4)], tl);
     }
@@ -84,7 +106,12 @@ __device__ __forceinline__ void mw_fbwd(const MwGeo& G, const float* FRt, const 
                 f32x4 o = acc0 + acc1;
                 float* zp = Zn + (16 * mi + 4 * g) * 16 + col;
                 if (l > 0) {     // z_{l-1} = (W_l^T z_l) .* act'_{l-1}(out_{l-1})
-                    if (G.act[l - 1] != 0) {
+                    if constexpr (GA) {
+                        float ov[4] = {o[0], o[1], o[2], o[3]};
+                        const float yv[4] = {oo[l][0], oo[l][1], oo[l][2], oo[l][3]};
+                        mw_dy<4>(G.act[l - 1], ov, yv);
+                        o = (f32x4){ov[0], ov[1], ov[2], ov[3]};
+                    } else if (G.act[l - 1] != 0) {
 #pragma unroll
                         for (int i = 0; i < 4; ++i) o[i] *= (1.f - oo[l][i] * oo[l][i]);
                     }
@@ -221,7 +248,7 @@ __global__ __launch_bounds__(kMwThreads) void rnde_bchainmw_kernel(const BMwPara
     BState bprev{}; StepMeta mprev = m_arg; double xs[3] = {0.0, 0.0, 0.0};
     LatWeightsT LT;
     if constexpr (SWEEP) {   // weights once per sweep (a launch per attempt requests its cold tape arrays in front of them instead, see below)
-        if constexpr (LAT) lat_load_t(G, Q.tab, LT, wave, lane);
+        if constexpr (LAT == 1) lat_load_t(G, Q.tab, LT, wave, lane);
         else mw_fill_lds(Q.tab + (size_t)G.nfrag_f * 64, smem, (G.nfrag_t >> 2) + 4, wave, lane);
     }
     // SWEEP: the record of the next attempt to reverse is read COLD from HBM; its nine arrays are requested at the end of the attempt before it,
@@ -263,12 +290,12 @@ __global__ __launch_bounds__(kMwThreads) void rnde_bchainmw_kernel(const BMwPara
         }
     }
     if constexpr (!SWEEP) {
-        if constexpr (LAT) lat_load_t(G, Q.tab, LT, wave, lane);      // (the latent-ODE shape: transposed fragments in registers, no LDS fill)
+        if constexpr (LAT == 1) lat_load_t(G, Q.tab, LT, wave, lane);      // (the latent-ODE shape: transposed fragments in registers, no LDS fill)
         else mw_fill_lds(Q.tab + (size_t)G.nfrag_f * 64, smem, (G.nfrag_t >> 2) + 4, wave, lane);
     }
     auto fbwd = [&](float* slp, const float (&gin_)[NR], const float (&kout_)[NR], const float (&kbar_)[NR], float (&gb_)[NR], float& tau_) {
-        if constexpr (LAT) mw_fbwd_lat<NR>(G, LT, ZA, ZB, slp, gin_, kout_, kbar_, gb_, tid, wave, lane);
-        else mw_fbwd<NR>(G, FRt, TV, ZA, ZB, slp, gin_, kout_, kbar_, gb_, tau_, tid, wave, lane);
+        if constexpr (LAT == 1) mw_fbwd_lat<NR>(G, LT, ZA, ZB, slp, gin_, kout_, kbar_, gb_, tid, wave, lane);
+        else mw_fbwd<NR, LAT == 2>(G, FRt, TV, ZA, ZB, slp, gin_, kout_, kbar_, gb_, tau_, tid, wave, lane);
     };
     // ---- scalar chain, identical in every wave; same arithmetic as rnde_bchain_kernel ----
     double tb = 0, dtpb = 0, qoldb = 0, t1b = 0, t0b = 0;
@@ -502,7 +529,7 @@ __global__ __launch_bounds__(kMwThreads) void rnde_bchainmw_kernel(const BMwPara
 
 // Reverse of the initialisation (mirror of rnde_bchain_init_kernel): PHASE 1 = f1 = f(u1, t0 + dt0) of the initial-step
 // heuristic (slab evaluation 1), PHASE 2 = f0 = f(u0, t0) (evaluation 0) and x-bar.
-template <int NR, int PHASE>
+template <int NR, int PHASE, int GA = 0>
 __global__ __launch_bounds__(kMwThreads) void rnde_bchainmw_init_kernel(const BMwParams Q) {
     const BwdParams& Bq = Q.B;
     const StepParams& P = Bq.F;
@@ -554,7 +581,7 @@ __global__ __launch_bounds__(kMwThreads) void rnde_bchainmw_init_kernel(const BM
             f1b[r] = 0.f;
             if (valid(r)) { const float sk = P.abstol + fabsf(xv) * P.reltol; f1b[r] = cw * ((f1v[r] - f0v[r]) / sk) / sk; }
         }
-        mw_fbwd<NR>(G, FRt, TV, ZA, ZB, sl, u1v, f1v, f1b, gb, tau, tid, wave, lane);
+        mw_fbwd<NR, GA>(G, FRt, TV, ZA, ZB, sl, u1v, f1v, f1b, gb, tau, tid, wave, lane);
 #pragma unroll
         for (int r = 0; r < NR; ++r) { Bq.UB1[fo + 256 * r] = gb[r]; dot += gb[r] * f0v[r]; }
         dot = wave_sum_f(dot); tau = wave_sum_f(tau);
@@ -596,7 +623,7 @@ __global__ __launch_bounds__(kMwThreads) void rnde_bchainmw_init_kernel(const BM
                 if (Bq.sv_ubar0) u0b[r] += Bq.sv_ubar0[((size_t)gcol * Bq.sv_T) * P.D + feat(r)];
             }
         }
-        mw_fbwd<NR>(G, FRt, TV, ZA, ZB, sl, xq, f0v, f0b, gb, tau, tid, wave, lane);
+        mw_fbwd<NR, GA>(G, FRt, TV, ZA, ZB, sl, xq, f0v, f0b, gb, tau, tid, wave, lane);
 #pragma unroll
         for (int r = 0; r < NR; ++r) if (valid(r)) Bq.xbar[(size_t)gcol * P.D + feat(r)] = u0b[r] + gb[r];
         tau = wave_sum_f(tau);

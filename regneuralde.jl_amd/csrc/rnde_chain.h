@@ -23,6 +23,7 @@
 // behind its own s_waitcnt: 260 cycles per MFMA measured, against 46 for the dependent chain itself).
 // Caller arrays (x, u_out, the saveat output, cotangents) stay D x B column-major as the ABI says.
 #pragma once
+#include <string>
 #include "rnde_fwd.h"
 #include "rnde_stage.h"   // mfma16
 
@@ -40,6 +41,25 @@ struct ChainGeo {
     int foff[kCMaxL], toff[kCMaxL], boff[kCMaxL];      // fragment offsets (units of 64 floats) in the three tables
     int nfrag_f, nfrag_b, nfrag_t;                     // forward A fragments | bias (+ time column) | transposed A fragments
 };
+
+// rnde_act codes (include/rnde.h; rnde_device.h: ACT_*) by name, and the create-time check of a chain's activations (rnde_node_create,
+// rnde_nsde_create): an unknown code is refused, never run as another map
+inline const char* rnde_act_name(int code) {
+    switch (code) {
+        case ACT_IDENTITY: return "identity";   case ACT_TANH: return "tanh";         case ACT_RELU: return "relu";
+        case ACT_SIGMOID: return "sigmoid";     case ACT_SOFTPLUS: return "softplus"; case ACT_ELU: return "elu";
+        default: return "unknown";
+    }
+}
+inline bool rnde_check_acts(int n_layers, const int32_t* act, const char* field, std::string& err) {
+    for (int l = 0; l < n_layers; ++l)
+        if (act[l] < ACT_IDENTITY || act[l] > ACT_ELU) {
+            err = std::string(field) + "[" + std::to_string(l) + "] = " + std::to_string(act[l]) +
+                  ": not a served activation (rnde_act: 0 identity, 1 tanh, 2 relu, 3 sigmoid, 4 softplus, 5 elu)";
+            return false;
+        }
+    return true;
+}
 
 struct ChainParams {
     StepParams F;          // shared controller / tape parameters (H and the packed-weight fields are unused)
@@ -214,6 +234,24 @@ __device__ __forceinline__ void chain_act_t(const f32x4 (&acc)[4], bool th, floa
         for (int ks = 0; ks < 16; ++ks) a[ks] = ks < 4 * MT ? acc[ks >> 2][ks & 3] : 0.f;
     }
 }
+// any other served activation (rnde_device.h: act_fwd) on a layer of width n (the ALT = 2 kernels).  Unlike identity and tanh these need not
+// map 0 to 0 (sigmoid, softplus), so the features past n -- the padding of the last k-step and tile -- are set to 0 explicitly: the padding
+// of a layer's output is read as state rows and as the next layer's input, and the kernels rely on it being zero.  The mask also covers the
+// tiles past the layer's own (their accumulators hold the zeros chain_bias_t put there), so one straight-line loop per code serves every width.
+template <int CODE>
+__device__ __forceinline__ void chain_act_code(const f32x4 (&acc)[4], int n, int lane, float (&a)[kCMaxKs]) {
+    const int g = lane >> 4;
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) a[ks] = 4 * ks + g < n ? act_fwd(CODE, acc[ks >> 2][ks & 3]) : 0.f;
+}
+__device__ __forceinline__ void chain_act_gen(const f32x4 (&acc)[4], int code, int n, int lane, float (&a)[kCMaxKs]) {
+    switch (code) {
+        case ACT_RELU: chain_act_code<ACT_RELU>(acc, n, lane, a); break;
+        case ACT_SIGMOID: chain_act_code<ACT_SIGMOID>(acc, n, lane, a); break;
+        case ACT_SOFTPLUS: chain_act_code<ACT_SOFTPLUS>(acc, n, lane, a); break;
+        default: chain_act_code<ACT_ELU>(acc, n, lane, a); break;
+    }
+}
 // tanh on exactly N k-steps, two per instruction (the rows past N are padding: zero)
 template <int N>
 __device__ __forceinline__ void chain_tanh_n(const f32x4 (&acc)[4], float (&a)[kCMaxKs]) {
@@ -243,7 +281,8 @@ __device__ __forceinline__ void chain_tanh(const f32x4 (&acc)[4], int n, float (
 // 16-register accumulator / activation arrays after every case (measured: 32.5 k cycles per latent-ODE evaluation
 // against 17.3 k with compile-time shapes, tools/micro/chain_eval.hip).  ALT = 1 therefore fixes the k-step pattern
 // of the reference's own latent-ODE dynamics at compile time (experiments/latent_ode.jl:113-124: widths 20 <-> 50,
-// i.e. 5 <-> 13 k-steps, alternating; depth, activations and flags stay run-time).
+// i.e. 5 <-> 13 k-steps, alternating; depth, activations and flags stay run-time).  ALT = 0 and 1 serve identity and tanh; ALT = 2 is ALT = 0
+// plus every other served activation, instantiated apart so that the identity / tanh kernels keep their registers (rnde.hip: chain_ga).
 constexpr int kAltA = 5, kAltB = 13;
 template <int ALT = 0>
 __device__ __forceinline__ void chain_layer(const ChainGeo& G, const float* FR, const float* BF, int l, float ts, float (&a)[kCMaxKs], int lane, unsigned long long* dbg = nullptr) {
@@ -286,6 +325,12 @@ __device__ __forceinline__ void chain_layer(const ChainGeo& G, const float* FR, 
 #ifdef RNDE_DIAG
     if (dbg) dbg[18 + 4 * l] = clock64();
 #endif
+    if constexpr (ALT == 2) {       // any served activation (rnde_device.h: act_fwd); identity and tanh below, as in the ALT = 0 kernels
+        if (G.act[l] != ACT_IDENTITY && G.act[l] != ACT_TANH) {
+            chain_act_gen(acc, G.act[l], G.width[l + 1], lane, a);
+            return;
+        }
+    }
 #ifdef CH_NO_TANH   // (ablation builds only: tools/micro/chain_eval.hip)
     if (false) {}
 #else

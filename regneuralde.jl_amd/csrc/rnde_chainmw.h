@@ -183,6 +183,13 @@ __device__ __forceinline__ void mw_fill_lds(const float* __restrict__ src, float
 
 // One Dense layer: X (LDS, [feature][16], rows < 16 mt[l] finite) -> Y.  Wave w computes output tile w.  Ends with a barrier.
 // hs != NULL: the layer's OUTPUT is also written to the slab rows hs (the next layer's input / the evaluation's value).
+// GA = 1 (the LAT = 2 kernels): any served activation besides identity and tanh (rnde_device.h: act_fwd); GA = 0 serves identity and tanh.
+template <int CODE>
+__device__ __forceinline__ void mw_act4(f32x4& o, int f0, int n) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = f0 + i < n ? act_fwd(CODE, o[i]) : 0.f;   // (the features past the width stay 0, as rnde_chain.h: chain_act_code)
+}
+template <int GA = 0>
 __device__ __forceinline__ void mw_layer(const MwGeo& G, const float* FRm, const float* BV, const float* TV, int l, float ts, const float* X, float* Y,
                                          float* __restrict__ hs, int wave, int lane) {
     const int mtin = G.mt[l], mtout = G.mt[l + 1];
@@ -209,7 +216,16 @@ __device__ __forceinline__ void mw_layer(const MwGeo& G, const float* FRm, const
             }
         }
         f32x4 o = acc0 + acc1;
-        if (G.act[l] != 0) {
+        const int act = G.act[l];
+        if (GA && act != ACT_IDENTITY && act != ACT_TANH) {
+            const int f0 = 16 * mo + 4 * g, n = G.width[l + 1];
+            switch (act) {
+                case ACT_RELU: mw_act4<ACT_RELU>(o, f0, n); break;
+                case ACT_SIGMOID: mw_act4<ACT_SIGMOID>(o, f0, n); break;
+                case ACT_SOFTPLUS: mw_act4<ACT_SOFTPLUS>(o, f0, n); break;
+                default: mw_act4<ACT_ELU>(o, f0, n); break;
+            }
+        } else if (act != 0) {
             const f32x2 t01 = tanh_fast2((f32x2){o[0], o[1]}), t23 = tanh_fast2((f32x2){o[2], o[3]});
             o = (f32x4){t01.x, t01.y, t23.x, t23.y};
         }
@@ -233,7 +249,7 @@ __device__ __forceinline__ void mw_layer(const MwGeo& G, const float* FRm, const
 
 // k = f(g, ts) for the workgroup's 16 columns.  gv / kv: element-wise registers (e = tid + 256 r).  XB, YB: 64 x 16 floats each.
 // sl: slab base of this (evaluation, tile) or NULL.
-template <int NR>
+template <int NR, int GA = 0>
 __device__ __forceinline__ void mw_eval(const MwGeo& G, const float* FRm, const float* BV, const float* TV, float* XB, float* YB, float ts,
                                         const float (&gv)[NR], float (&kv)[NR], float* __restrict__ sl, int tid, int wave, int lane,
                                         unsigned long long* dbg = nullptr) {
@@ -250,7 +266,7 @@ __device__ __forceinline__ void mw_eval(const MwGeo& G, const float* FRm, const 
 #pragma unroll 1
     for (int l = 0; l < G.n_layers; ++l) {
         MW_STAMP(16 + l);
-        mw_layer(G, FRm, BV, TV, l, ts, X, Y, sl ? sl + (size_t)G.hrow[l + 1] * 64 : nullptr, wave, lane);
+        mw_layer<GA>(G, FRm, BV, TV, l, ts, X, Y, sl ? sl + (size_t)G.hrow[l + 1] * 64 : nullptr, wave, lane);
         float* t_ = X; X = Y; Y = t_;
     }
     MW_STAMP(16 + G.n_layers);
@@ -390,12 +406,12 @@ __global__ __launch_bounds__(kMwThreads) void rnde_chainmw_kernel(const MwParams
     }
     // LAT: this wave's weight fragments in registers for the whole launch, nothing to fill (the LDS layout is kept: XB / YB sit where they sit)
     LatWeights LW;
-    if constexpr (MODE != MW_FINISH && LAT) lat_load(G, Q.tab, LW, wave, lane);
-    if constexpr (MODE != MW_FINISH && !LAT) mw_fill_lds(Q.tab, smem, (G.nfrag_f >> 2) + 4, wave, lane);
+    if constexpr (MODE != MW_FINISH && LAT == 1) lat_load(G, Q.tab, LW, wave, lane);
+    if constexpr (MODE != MW_FINISH && LAT != 1) mw_fill_lds(Q.tab, smem, (G.nfrag_f >> 2) + 4, wave, lane);
     MW_STAMP(1);
     auto eval = [&](float ts, const float (&gin)[NR], float (&kout)[NR], float* slp, unsigned long long* dbgp) {
-        if constexpr (LAT) mw_eval_lat<NR>(G, LW, XB, YB, gin, kout, slp, tid, wave, lane);
-        else mw_eval<NR>(G, FRm, BV, TV, XB, YB, ts, gin, kout, slp, tid, wave, lane, dbgp);
+        if constexpr (LAT == 1) mw_eval_lat<NR>(G, LW, XB, YB, gin, kout, slp, tid, wave, lane);
+        else mw_eval<NR, LAT == 2>(G, FRm, BV, TV, XB, YB, ts, gin, kout, slp, tid, wave, lane, dbgp);
     };
     // element (r): feature f = (tid + 256 r) >> 4, column gcol
     const int gcol = tile * 16 + (tid & 15);

@@ -369,4 +369,30 @@ __device__ __forceinline__ float pre_bwd(int sel, float g, float v) {
     return v;
 }
 
+// The Dense activations (rnde_node_config.act / rnde_nsde_config.*_act, include/rnde.h: rnde_act).  Each derivative is a function of the
+// layer's OUTPUT y, which is what the reverse passes read back from the tape (no pre-activation is ever kept): tanh 1 - y^2, relu y > 0,
+// sigmoid y (1 - y), softplus -expm1(-y) (= sigmoid(z)), elu (alpha = 1) y > 0 ? 1 : y + 1.  A NaN input stays NaN through every map.
+// The kernels keep their own paths for identity and tanh (tanh_fast2 on pairs); act_fwd / act_dy are what every other code runs through.
+enum { ACT_IDENTITY = 0, ACT_TANH = 1, ACT_RELU = 2, ACT_SIGMOID = 3, ACT_SOFTPLUS = 4, ACT_ELU = 5 };
+__device__ __forceinline__ float act_fwd(int code, float z) {
+    switch (code) {
+        case ACT_TANH: return tanh_fast(z);
+        case ACT_RELU: return z < 0.f ? 0.f : z;
+        case ACT_SIGMOID: { const float t = expf(-fabsf(z)); return z >= 0.f ? 1.f / (1.f + t) : t / (1.f + t); }
+        case ACT_SOFTPLUS: return log1pf(expf(-fabsf(z))) + fmaxf(z, 0.f);
+        case ACT_ELU: return z > 0.f ? z : expm1f(z);
+        default: return z;
+    }
+}
+__device__ __forceinline__ float act_dy(int code, float y) {
+    switch (code) {
+        case ACT_TANH: return 1.f - y * y;
+        case ACT_RELU: return y > 0.f ? 1.f : 0.f;
+        case ACT_SIGMOID: return y * (1.f - y);
+        case ACT_SOFTPLUS: return -expm1f(-y);
+        case ACT_ELU: return y > 0.f ? 1.f : y + 1.f;
+        default: return 1.f;
+    }
+}
+
 }  // namespace rnde

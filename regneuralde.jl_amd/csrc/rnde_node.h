@@ -52,6 +52,7 @@ struct rnde_node {
     // stage engine (rnde_stage.h)
     int engine = 1;                       // 1 column-owner, 2 stage kernels, 3 chain engine (rnde_chain.h)
     ChainGeo cg{}; float* cfrags = nullptr; int NKD = 0, chain_alt = 0;
+    int chain_ga = 0;             // a layer's activation is other than identity / tanh: the kernel variants that serve every rnde_act (ALT / LAT = 2)
     size_t chain_lds_f = 0, chain_lds_b = 0;
     // multi-wave kernels of the chain engine (rnde_chainmw.h): 4 waves per 16 columns, activations taped in the slab by the forward
     rnde_comm* couple = nullptr; int couple_batch = 0, couple_world = 1;   // SURVEY 8e mode 2 (rnde_node_set_coupling)

@@ -598,8 +598,8 @@ static rnde_status launch_bmw_t(rnde_node* h, const BMwParams& Q, const std::vec
     if (attr_set.need()) {
         hipError_t e = hipFuncSetAttribute((const void*)rnde_bchainmw_kernel<NR, TAB, LAT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void*)rnde_bchainmw_kernel<NR, TAB, LAT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)rnde_bchainmw_init_kernel<NR, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)rnde_bchainmw_init_kernel<NR, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)rnde_bchainmw_init_kernel<NR, 1, LAT == 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)rnde_bchainmw_init_kernel<NR, 2, LAT == 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         HIPCHK(h, e);
         attr_set.done();
     }
@@ -639,9 +639,9 @@ static rnde_status launch_bmw_t(rnde_node* h, const BMwParams& Q, const std::vec
         HIPCHK(h, hipMemcpyAsync(h->h_mw_bchk + 2, h->mw_xcc, (size_t)Q.ntiles * 4, hipMemcpyDeviceToHost, s));
         h->pending_bsweep = true; h->bsweep_nt = Q.ntiles; h->bsweep_global = W.xch_global != 0;
     }
-    hipLaunchKernelGGL((rnde_bchainmw_init_kernel<NR, 1>), grid, blk, lds, s, Q);
+    hipLaunchKernelGGL((rnde_bchainmw_init_kernel<NR, 1, LAT == 2>), grid, blk, lds, s, Q);
     if ((st = couple_sum(h, Q.B.ipart, 4LL * Q.B.F.nwg, s)) != RNDE_OK) return st;                        // dot, tau of the reversed second evaluation
-    hipLaunchKernelGGL((rnde_bchainmw_init_kernel<NR, 2>), grid, blk, lds, s, Q);
+    hipLaunchKernelGGL((rnde_bchainmw_init_kernel<NR, 2, LAT == 2>), grid, blk, lds, s, Q);
     if ((st = couple_sum(h, Q.B.ipart + 4LL * Q.B.F.nwg, 4LL * Q.B.F.nwg, s)) != RNDE_OK) return st;      // tau of the first
     hipLaunchKernelGGL(rnde_bfin_kernel, dim3(1), dim3(64), 0, s, Q.B);
     HIPCHK(h, hipGetLastError());
@@ -704,7 +704,11 @@ static rnde_status chain_mw_bwd_run(rnde_node* h, const float* u_bar_dev, const 
     }
     HIPCHK(h, hipMemcpyAsync(h->ev_t, h->h_ev_t, (size_t)n_evals * 4, hipMemcpyHostToDevice, s));
     rnde_status e;
-    if (h->rk_tab == 2) e = h->NKD == 4 ? launch_bmw_t<1, 2>(h, Q, sv_lo, sv_hi, s) : (h->NKD == 8 ? launch_bmw_t<2, 2>(h, Q, sv_lo, sv_hi, s) : launch_bmw_t<4, 2>(h, Q, sv_lo, sv_hi, s));
+    if (h->chain_ga) {     // (any served activation: the LAT = 2 kernels)
+        if (h->rk_tab == 2) e = h->NKD == 4 ? launch_bmw_t<1, 2, 2>(h, Q, sv_lo, sv_hi, s) : (h->NKD == 8 ? launch_bmw_t<2, 2, 2>(h, Q, sv_lo, sv_hi, s) : launch_bmw_t<4, 2, 2>(h, Q, sv_lo, sv_hi, s));
+        else if (h->rk_tab) e = h->NKD == 4 ? launch_bmw_t<1, 1, 2>(h, Q, sv_lo, sv_hi, s) : (h->NKD == 8 ? launch_bmw_t<2, 1, 2>(h, Q, sv_lo, sv_hi, s) : launch_bmw_t<4, 1, 2>(h, Q, sv_lo, sv_hi, s));
+        else e = h->NKD == 4 ? launch_bmw_t<1, 0, 2>(h, Q, sv_lo, sv_hi, s) : (h->NKD == 8 ? launch_bmw_t<2, 0, 2>(h, Q, sv_lo, sv_hi, s) : launch_bmw_t<4, 0, 2>(h, Q, sv_lo, sv_hi, s));
+    } else if (h->rk_tab == 2) e = h->NKD == 4 ? launch_bmw_t<1, 2>(h, Q, sv_lo, sv_hi, s) : (h->NKD == 8 ? launch_bmw_t<2, 2>(h, Q, sv_lo, sv_hi, s) : launch_bmw_t<4, 2>(h, Q, sv_lo, sv_hi, s));
     else if (h->mw_lat) e = h->rk_tab ? launch_bmw_t<2, 1, 1>(h, Q, sv_lo, sv_hi, s) : launch_bmw_t<2, 0, 1>(h, Q, sv_lo, sv_hi, s);   // latent-ODE shape: transposed weights register stationary
     else if (h->rk_tab) e = h->NKD == 4 ? launch_bmw_t<1, 1>(h, Q, sv_lo, sv_hi, s) : (h->NKD == 8 ? launch_bmw_t<2, 1>(h, Q, sv_lo, sv_hi, s) : launch_bmw_t<4, 1>(h, Q, sv_lo, sv_hi, s));
     else e = h->NKD == 4 ? launch_bmw_t<1, 0>(h, Q, sv_lo, sv_hi, s) : (h->NKD == 8 ? launch_bmw_t<2, 0>(h, Q, sv_lo, sv_hi, s) : launch_bmw_t<4, 0>(h, Q, sv_lo, sv_hi, s));
@@ -809,7 +813,11 @@ static rnde_status chain_bwd_run(rnde_node* h, const float* u_bar_dev, const flo
     }
     HIPCHK(h, hipMemcpyAsync(h->ev_t, h->h_ev_t, (size_t)n_evals * 4, hipMemcpyHostToDevice, s));
     hipError_t e;
-    switch (h->NKD) {
+    if (h->chain_ga) switch (h->NKD) {     // (any served activation: the ALT = 2 kernels)
+        case 4: e = launch_bchain_t<4, 2>(h, Q, sv_lo, sv_hi, s); break;
+        case 8: e = launch_bchain_t<8, 2>(h, Q, sv_lo, sv_hi, s); break;
+        default: e = launch_bchain_t<16, 2>(h, Q, sv_lo, sv_hi, s); break;
+    } else switch (h->NKD) {
         case 4: e = launch_bchain_t<4>(h, Q, sv_lo, sv_hi, s); break;
         case 8: e = h->chain_alt ? launch_bchain_t<8, 1>(h, Q, sv_lo, sv_hi, s) : launch_bchain_t<8>(h, Q, sv_lo, sv_hi, s); break;
         default: e = launch_bchain_t<16>(h, Q, sv_lo, sv_hi, s); break;

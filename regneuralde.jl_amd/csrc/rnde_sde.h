@@ -96,7 +96,8 @@ __device__ __forceinline__ void sde_net(const ChainGeo& G, const float* FR, cons
 // ---- compile-time shapes for the reference's own NSDE form (experiments/mnist_nsde.jl:73-74): drift = Dense(D, Hd, act0) -> Dense(Hd, D, act1),
 // diffusion = Dense(D, D, act).  Run-time shape dispatch costs a factor ~2 per layer (rnde_chain.h: the structurised switches merge
 // the 16-register accumulator / activation arrays after every case), and the whole solve is a chain of ~700 such layers.
-// FIXH = k-steps of the hidden width (0 = generic chains through chain_eval).
+// FIXH = k-steps of the hidden width (0 = generic chains through chain_eval, identity / tanh; -1 = the same for any served activation:
+// chain_eval's ALT = 2 variant, instantiated apart so that the identity / tanh kernels keep their registers).
 template <int NI, int NO>
 __device__ __forceinline__ void sde_layer_fixed(const ChainGeo& G, const float* FR, int l, const float (&in)[kCMaxKs], float (&out)[kCMaxKs], int lane) {
     constexpr int MT = (NO + 3) / 4;
@@ -107,7 +108,7 @@ __device__ __forceinline__ void sde_layer_fixed(const ChainGeo& G, const float* 
 }
 template <int NKD, int FIXH>
 __device__ __forceinline__ void sde_drift(const ChainGeo& G, const float* FR, const float (&in)[NKD], float (&out)[NKD], int lane) {
-    if constexpr (FIXH == 0) chain_eval<NKD, 0>(G, FR, FR + (size_t)G.nfrag_f * 64, 0.f, in, out, lane);
+    if constexpr (FIXH <= 0) chain_eval<NKD, FIXH < 0 ? 2 : 0>(G, FR, FR + (size_t)G.nfrag_f * 64, 0.f, in, out, lane);
     else {
         float a[kCMaxKs], b[kCMaxKs];
 #pragma unroll
@@ -120,7 +121,7 @@ __device__ __forceinline__ void sde_drift(const ChainGeo& G, const float* FR, co
 }
 template <int NKD, int FIXH>
 __device__ __forceinline__ void sde_diff(const ChainGeo& G, const float* FR, const float (&in)[NKD], float (&out)[NKD], int lane) {
-    if constexpr (FIXH == 0) chain_eval<NKD, 0>(G, FR, FR + (size_t)G.nfrag_f * 64, 0.f, in, out, lane);
+    if constexpr (FIXH <= 0) chain_eval<NKD, FIXH < 0 ? 2 : 0>(G, FR, FR + (size_t)G.nfrag_f * 64, 0.f, in, out, lane);
     else {
         float a[kCMaxKs], b[kCMaxKs];
 #pragma unroll
@@ -669,7 +670,7 @@ __global__ __launch_bounds__(64 * kCW) void rnde_sde_solve_kernel(const SdeParam
 }
 
 // ---- kernel-level parity entry: ONE attempt from (uprev, dt, dW, dZ) given in caller layout ----------------------------------
-template <int NKD>
+template <int NKD, int FIXH = 0>
 __global__ __launch_bounds__(64 * kCW) void rnde_sde_attempt_kernel(const SdeParams Q, const float* __restrict__ uprev, const float* __restrict__ dWc,
                                                                     const float* __restrict__ dZc, float dt, float* __restrict__ kg_out,
                                                                     float* __restrict__ unew_out, float* __restrict__ part_out) {
@@ -692,7 +693,7 @@ __global__ __launch_bounds__(64 * kCW) void rnde_sde_attempt_kernel(const SdePar
 #pragma unroll
     for (int q = 0; q < NKD; ++q) { up[q] = ldc(uprev, Q.D, gcol, 4 * q + gq, colok); dW[q] = ldc(dWc, Q.D, gcol, 4 * q + gq, colok); dZ[q] = ldc(dZc, Q.D, gcol, 4 * q + gq, colok); }
     float eig[2];
-    float part = sde_attempt<NKD>(Q, FRf, FRg, up, dt, sqrtf(fabsf(dt)), dW, dZ, k, g, un, colok, gq, lane, eig);
+    float part = sde_attempt<NKD, FIXH>(Q, FRf, FRg, up, dt, sqrtf(fabsf(dt)), dW, dZ, k, g, un, colok, gq, lane, eig);
     const size_t A = (size_t)Q.D * Q.B;
 #pragma unroll
     for (int q = 0; q < NKD; ++q) if (colok && 4 * q + gq < Q.D) {
@@ -732,9 +733,9 @@ template <int NKD, int FIXH>
 __device__ __forceinline__ void sde_drift_bwd(const BChainParams& C, const float* FR, const float (&hin)[NKD], const float (&kout)[NKD], const float (&kbar)[NKD],
                                               float (&gb)[NKD], float* __restrict__ sl, int lane) {
     const ChainGeo& G = C.G;
-    if constexpr (FIXH == 0) {
+    if constexpr (FIXH <= 0) {
         float tau = 0.f;
-        chain_fbwd<NKD, 0>(C, FR, FR + (size_t)G.nfrag_f * 64, FR + (size_t)(G.nfrag_f + G.nfrag_b) * 64, 0.f, hin, kout, kbar, gb, sl, tau, lane);
+        chain_fbwd<NKD, FIXH < 0 ? 2 : 0>(C, FR, FR + (size_t)G.nfrag_f * 64, FR + (size_t)(G.nfrag_f + G.nfrag_b) * 64, 0.f, hin, kout, kbar, gb, sl, tau, lane);
     } else {
         const float* TF = FR + (size_t)(G.nfrag_f + G.nfrag_b) * 64;
         float a[kCMaxKs], hmid[kCMaxKs], o[kCMaxKs], ab[kCMaxKs], z[kCMaxKs];
@@ -756,9 +757,9 @@ template <int NKD, int FIXH>
 __device__ __forceinline__ void sde_diff_bwd(const BChainParams& C, const float* FR, const float (&hin)[NKD], const float (&gout)[NKD], const float (&gbar)[NKD],
                                              float (&hb)[NKD], float* __restrict__ sl, int lane) {
     const ChainGeo& G = C.G;
-    if constexpr (FIXH == 0) {
+    if constexpr (FIXH <= 0) {
         float tau = 0.f;
-        chain_fbwd<NKD, 0>(C, FR, FR + (size_t)G.nfrag_f * 64, FR + (size_t)(G.nfrag_f + G.nfrag_b) * 64, 0.f, hin, gout, gbar, hb, sl, tau, lane);
+        chain_fbwd<NKD, FIXH < 0 ? 2 : 0>(C, FR, FR + (size_t)G.nfrag_f * 64, FR + (size_t)(G.nfrag_f + G.nfrag_b) * 64, 0.f, hin, gout, gbar, hb, sl, tau, lane);
     } else {
         const float* TF = FR + (size_t)(G.nfrag_f + G.nfrag_b) * 64;
         float a[kCMaxKs], o[kCMaxKs], ab[kCMaxKs], z[kCMaxKs];

@@ -36,6 +36,7 @@ struct rnde_nsde {
     int pool_pred = 0;      // library noise: draws the next solve's pool is filled with (0 = all of max_attempts + 1); grows back on demand
     int fix = 0;   // 1: the reference's own shape (drift 8 -> 16 -> 8 k-steps, one-layer diffusion): kernels with compile-time shapes
     int fix_shape = 0, mw_shape = 0;   // what fix / mw are without a pre-activation (those kernels apply none: rnde_nsde_set_pre_act)
+    int ga = 0;    // 1: an activation other than identity / tanh in either chain: the generic kernels' variant that serves every rnde_act (FIXH = -1)
     ChainGeo Gf{}, Gg{};
     SriTableau T{};
     float order = 1.5f, beta1 = 0, beta2 = 0, gamma = 0, qmin = 0, qmax = 0, qoldinit = 0, delta = 0;
@@ -150,6 +151,8 @@ extern "C" rnde_status rnde_nsde_create(const rnde_nsde_config* c, rnde_nsde** o
     if (!sde_geo(c->drift_layers, c->drift_dims, c->drift_act, RNDE_PRE_NONE, Gf) || !sde_geo(c->diff_layers, c->diff_dims, c->diff_act, RNDE_PRE_NONE, Gg)) {
         g_nsde_create_err = "unsupported networks: Dense chains of 1..8 layers, every width 1..64"; return RNDE_ERR_BAD_ARG;
     }
+    if (!rnde_check_acts(c->drift_layers, c->drift_act, "drift_act", g_nsde_create_err) || !rnde_check_acts(c->diff_layers, c->diff_act, "diff_act", g_nsde_create_err))
+        return RNDE_ERR_BAD_ARG;
     const int D = c->drift_dims[0];
     if (c->drift_dims[c->drift_layers] != D || c->diff_dims[0] != D || c->diff_dims[c->diff_layers] != D) {
         g_nsde_create_err = "drift and diffusion must map D -> D (diagonal noise)"; return RNDE_ERR_BAD_ARG;
@@ -169,7 +172,12 @@ extern "C" rnde_status rnde_nsde_create(const rnde_nsde_config* c, rnde_nsde** o
     h->cfg = *c; h->D = D; h->Gf = Gf; h->Gg = Gg;
     h->Pf = chain_params(c->drift_layers, c->drift_dims); h->Pg = chain_params(c->diff_layers, c->diff_dims); h->P = h->Pf + h->Pg;
     h->NKD = D <= 16 ? 4 : (D <= 32 ? 8 : 16);
-    h->fix = (c->drift_layers == 2 && c->diff_layers == 1 && Gf.nks[0] == 8 && Gf.nks[1] == 16 && c->generic == 0) ? 1 : 0;
+    // the kernels with the reference's shape as compile-time constants (rnde_sde.h: FIXH, rnde_sdemw.h) serve identity / tanh only
+    bool plain_acts = true;
+    for (int l = 0; l < c->drift_layers; ++l) plain_acts = plain_acts && (c->drift_act[l] == RNDE_ACT_IDENTITY || c->drift_act[l] == RNDE_ACT_TANH);
+    for (int l = 0; l < c->diff_layers; ++l) plain_acts = plain_acts && (c->diff_act[l] == RNDE_ACT_IDENTITY || c->diff_act[l] == RNDE_ACT_TANH);
+    h->ga = plain_acts ? 0 : 1;
+    h->fix = (plain_acts && c->drift_layers == 2 && c->diff_layers == 1 && Gf.nks[0] == 8 && Gf.nks[1] == 16 && c->generic == 0) ? 1 : 0;
     { const char* e = getenv("RNDE_SDE_MW"); h->mw = (h->fix && !(e && e[0] == '0')) ? 1 : 0; }
     h->fix_shape = h->fix; h->mw_shape = h->mw;
     float ddef = 1.f;
@@ -270,15 +278,15 @@ static hipError_t launch_solve(rnde_nsde* h, const SdeParams& Q, hipStream_t s) 
     hipLaunchKernelGGL((rnde_sde_solve_kernel<NKD, FIXH>), dim3(Q.nwg), dim3(64 * kCW), h->lds_fwd, s, Q);
     return hipGetLastError();
 }
-template <int NKD>
+template <int NKD, int FIXH = 0>
 static hipError_t launch_attempt(rnde_nsde* h, const SdeParams& Q, const float* up, const float* dW, const float* dZ, float dt, float* kg, float* un, hipStream_t s) {
     static DeviceOnce attr;
     if (attr.need()) {
-        hipError_t e = hipFuncSetAttribute((const void*)rnde_sde_attempt_kernel<NKD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void*)rnde_sde_attempt_kernel<NKD, FIXH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
         attr.done();
     }
-    hipLaunchKernelGGL(rnde_sde_attempt_kernel<NKD>, dim3(Q.nwg), dim3(64 * kCW), h->lds_fwd, s, Q, up, dW, dZ, dt, kg, un, h->part);
+    hipLaunchKernelGGL((rnde_sde_attempt_kernel<NKD, FIXH>), dim3(Q.nwg), dim3(64 * kCW), h->lds_fwd, s, Q, up, dW, dZ, dt, kg, un, h->part);
     return hipGetLastError();
 }
 template <int NKD, int FIXH = 0>
@@ -378,6 +386,7 @@ static rnde_status nsde_forward_impl(rnde_nsde* h, const float* x_dev, const flo
         if (local_xch && e == hipSuccess) e = hipMemcpyAsync(h->h_xcc, h->xcc, (size_t)ntiles * 4, hipMemcpyDeviceToHost, s);
     } else
         e = h->fix ? launch_solve<8, 16>(h, Q, s)
+                   : h->ga ? (h->NKD == 4 ? launch_solve<4, -1>(h, Q, s) : (h->NKD == 8 ? launch_solve<8, -1>(h, Q, s) : launch_solve<16, -1>(h, Q, s)))
                    : (h->NKD == 4 ? launch_solve<4>(h, Q, s) : (h->NKD == 8 ? launch_solve<8>(h, Q, s) : launch_solve<16>(h, Q, s)));
     SCHK(h, e);
     if (h->cfg.regularize == RNDE_REG_STIFF) {      // the two norms of every attempt's stiffness estimate -> meta[n].n1 / .n2 (fixed-order sums of the workgroups' partials)
@@ -512,7 +521,10 @@ extern "C" rnde_status rnde_nsde_debug_attempt(rnde_nsde* h, const float* uprev_
     rnde_status st = sde_pack(h, p_dev, s);
     if (st != RNDE_OK) return st;
     SdeParams Q = sde_params(h, uprev_dev, nullptr, 0, B, 0.f, 1.f, 0);
-    hipError_t e = h->NKD == 4 ? launch_attempt<4>(h, Q, uprev_dev, dW_dev, dZ_dev, dt, kg_out_dev, unew_out_dev, s)
+    hipError_t e = h->ga ? (h->NKD == 4 ? launch_attempt<4, -1>(h, Q, uprev_dev, dW_dev, dZ_dev, dt, kg_out_dev, unew_out_dev, s)
+                            : (h->NKD == 8 ? launch_attempt<8, -1>(h, Q, uprev_dev, dW_dev, dZ_dev, dt, kg_out_dev, unew_out_dev, s)
+                                           : launch_attempt<16, -1>(h, Q, uprev_dev, dW_dev, dZ_dev, dt, kg_out_dev, unew_out_dev, s)))
+                 : h->NKD == 4 ? launch_attempt<4>(h, Q, uprev_dev, dW_dev, dZ_dev, dt, kg_out_dev, unew_out_dev, s)
                  : (h->NKD == 8 ? launch_attempt<8>(h, Q, uprev_dev, dW_dev, dZ_dev, dt, kg_out_dev, unew_out_dev, s)
                                 : launch_attempt<16>(h, Q, uprev_dev, dW_dev, dZ_dev, dt, kg_out_dev, unew_out_dev, s));
     SCHK(h, e);
@@ -599,6 +611,7 @@ static rnde_status nsde_backward_impl(rnde_nsde* h, const float* u_bar_dev, cons
         e = hipGetLastError();
     } else
         e = h->fix ? launch_bwd<8, 16>(h, Bq, s)
+                   : h->ga ? (h->NKD == 4 ? launch_bwd<4, -1>(h, Bq, s) : (h->NKD == 8 ? launch_bwd<8, -1>(h, Bq, s) : launch_bwd<16, -1>(h, Bq, s)))
                    : (h->NKD == 4 ? launch_bwd<4>(h, Bq, s) : (h->NKD == 8 ? launch_bwd<8>(h, Bq, s) : launch_bwd<16>(h, Bq, s)));
     SCHK(h, e);
     SCHK(h, hipEventRecord(h->tev[3], s));

@@ -36,6 +36,19 @@ class TDChain:
         return d
 
 
+# Dense activations the kernels serve (include/rnde.h: rnde_act), by name: NNlib's identity, tanh, relu, σ, softplus and elu (alpha = 1).
+# Each derivative is a function of the layer's output (what the reverse pass keeps); swish / gelu and the like are not served.
+ACT = {"identity": 0, "tanh": 1, "relu": 2, "sigmoid": 3, "softplus": 4, "elu": 5}
+
+
+def act_code(name):
+    """rnde_act code of a Dense layer's activation name; ValueError for a name the kernels do not serve."""
+    try:
+        return ACT[name]
+    except (KeyError, TypeError):
+        raise ValueError(f"Dense activation {name!r} is not served: one of {list(ACT)}") from None
+
+
 def MLPDynamics(n_in, hidden, generator=None):
     """reference experiments/mnist_node.jl:41-54: Dense(in+1, hidden, tanh) -> Dense(hidden+1, in, tanh)."""
     return TDChain(Dense(n_in + 1, hidden, "tanh", generator), Dense(hidden + 1, n_in, "tanh", generator))

@@ -21,9 +21,8 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .layers import PRE_ACT, destructure
+from .layers import PRE_ACT, act_code, destructure
 
-_ACT = {"identity": 0, "tanh": 1}
 _FUNCS = {None: 1, "none": 0, "error_est": 1, "stiff_est": 2, "error_stiff_est": 3, "stiff_est_dt": 4}      # None: the layer's default callback (neural_ode.jl:116)
 _FUNC_NAMES = {0: "none", 1: "error_est", 2: "stiff_est", 3: "error_stiff_est", 4: "stiff_est_dt"}
 TSIT5_STABILITY_SIZE = 3.5068     # OrdinaryDiffEq.alg_stability_size(Tsit5()): what mnist_node.jl:73,:86 divides by
@@ -197,6 +196,8 @@ class TrackedNeuralODE:
                              "(a 13-stage table) run on the tableau-as-data kernels (Dense chains of width <= 64)")
         self.solver = solver
         self.model = model
+        for l in model.layers:
+            act_code(l.act)                              # (an activation the kernels do not serve is refused here, not at the first call)
         self.p = destructure(model)                      # Flux.destructure (neural_ode.jl:12)
         self.tspan = [float(tspan[0]), float(tspan[1])]
         self.time_dep = bool(time_dep)
@@ -226,7 +227,7 @@ class TrackedNeuralODE:
         for i, d in enumerate(dims):
             cfg.dims[i] = d
         for i, l in enumerate(self.model.layers):
-            cfg.act[i] = _ACT[l.act]
+            cfg.act[i] = act_code(l.act)
         cfg.time_dep = int(self.time_dep)
         cfg.pre_act = PRE_ACT[getattr(self.model, "pre_act", False)]
         cfg.max_batch = self.max_batch

@@ -23,10 +23,8 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .layers import PRE_ACT, Chain, Dense, destructure
+from .layers import PRE_ACT, Chain, Dense, act_code, destructure
 from .node import MAX_HANDLES_PER_KEY, SOSRI2_STABILITY_SIZE, SavedValues, _check_f32, _TapeToken, effective_reg, reg_code
-
-_ACT = {"identity": 0, "tanh": 1}
 
 
 class _NsdeHandle:
@@ -116,6 +114,8 @@ class TrackedNeuralDSDE:
         if model1.time_dep or model2.time_dep:
             raise ValueError("drift and diffusion are time independent (neural_sde.jl:45-52 call re(p)(u))")
         self.model1, self.model2 = model1, model2
+        for l in model1.layers + model2.layers:
+            act_code(l.act)                                # (an activation the kernels do not serve is refused here, not at the first call)
         p1, p2 = destructure(model1), destructure(model2)
         self.p = torch.cat([p1, p2])                       # neural_sde.jl:17
         self.len = p1.numel()                              # neural_sde.jl:38
@@ -137,7 +137,7 @@ class TrackedNeuralDSDE:
             for i, d in enumerate(dims):
                 getattr(cfg, f"{name}_dims")[i] = d
             for i, l in enumerate(model.layers):
-                getattr(cfg, f"{name}_act")[i] = _ACT[l.act]
+                getattr(cfg, f"{name}_act")[i] = act_code(l.act)
         cfg.max_batch = self.max_batch
         cfg.solver = _lib.SDE_SOLVER[self.solver]
         cfg.reltol = float(self.kwargs.get("reltol", 1e-2))   # StochasticDiffEq defaults when not given
