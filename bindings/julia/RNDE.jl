@@ -660,6 +660,53 @@ end
     end
 end
 
+# TrackedFFJORD{false} called with regularize = true: the state [z; l; lambda1; lambda2] (kinetic energy, Jacobian norm); reg is 2 x B
+function ffjord_forward_kinetic(h::FfjordHandle, x::ROCMatrix{Float32}, p::ROCVector{Float32}, e::ROCMatrix{Float32}, tspan; keep_tape::Bool = true)
+    B = size(x, 2)
+    logpx = similar(x, B)
+    reg = similar(x, B, 2)                                 # column-major B x 2 == the library's 2 x B rows
+    nfe = Ref{Int64}(0)
+    GC.@preserve x p e logpx reg begin
+        st = ccall((:rnde_ffjord_forward_kinetic, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float32, Float32, UInt64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int64}, Int32, Ptr{Cvoid}),
+                   h.ptr, devptr(x), devptr(p), devptr(e), B, Float32(tspan[1]), Float32(tspan[2]), UInt64(0), devptr(logpx), devptr(reg), C_NULL, nfe,
+                   keep_tape ? 1 : 0, _stream())
+        st == 0 || error("rnde_ffjord_forward_kinetic status $st: ", _fferr(h.ptr))
+    end
+    return logpx, reg[:, 1], reg[:, 2], Int(nfe[])
+end
+
+function ffjord_backward_kinetic(h::FfjordHandle, logpx_bar::ROCVector{Float32}, reg_bar::ROCMatrix{Float32}, np::Int, D::Int)
+    B = length(logpx_bar)
+    pbar = similar(logpx_bar, np)
+    xbar = similar(logpx_bar, D, B)
+    GC.@preserve logpx_bar reg_bar pbar xbar begin
+        st = ccall((:rnde_ffjord_backward_kinetic, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                   h.ptr, devptr(logpx_bar), devptr(reg_bar), devptr(pbar), devptr(xbar), _stream())
+        st == 0 || error("rnde_ffjord_backward_kinetic status $st: ", _fferr(h.ptr))
+    end
+    return pbar, xbar
+end
+
+# Tracker glue of the kinetic call: (logpx, lambda1, lambda2) -> (x-bar, p-bar); a missing cotangent counts as zeros
+ffjord_solve_kinetic(h::FfjordHandle, x::TrackedArray, p::TrackedArray, e, tspan) = track(ffjord_solve_kinetic, h, x, p, e, tspan)
+ffjord_solve_kinetic(h::FfjordHandle, x, p::TrackedArray, e, tspan) = track(ffjord_solve_kinetic, h, x, p, e, tspan)
+function ffjord_solve_kinetic(h::FfjordHandle, x, p, e, tspan)  # nothing tracked: no tape
+    logpx, l1, l2, nfe = ffjord_forward_kinetic(h, data(x), data(p), e, tspan; keep_tape = false)
+    FFJORD_NFE[h] = nfe
+    return logpx, l1, l2
+end
+@grad function ffjord_solve_kinetic(h::FfjordHandle, x, p, e, tspan)
+    logpx, l1, l2, nfe = ffjord_forward_kinetic(h, data(x), data(p), e, data.(tspan); keep_tape = true)
+    FFJORD_NFE[h] = nfe
+    return (logpx, l1, l2), function (Δ)
+        B = length(logpx)
+        col(d) = d === nothing ? fill!(similar(logpx), 0f0) : ROCArray{Float32}(data(d))
+        pbar, xbar = ffjord_backward_kinetic(h, col(Δ[1]), hcat(col(Δ[2]), col(Δ[3])), length(p), size(x, 1))
+        return (nothing, xbar, pbar, nothing, nothing)
+    end
+end
+
 # sample: z (D x n) solved from t1 back to t0 with the exact trace -> x (D x n)
 function ffjord_sample(h::FfjordHandle, p::ROCVector{Float32}, z::ROCMatrix{Float32}, tspan)
     x = similar(z)

@@ -3,7 +3,8 @@
 # file, after `using RegNeuralDE` (see patch_neural_ode.jl).  Served: `dynamics = forw_n_back` of the ConcatSquash MLPDynamics of
 # experiments/ffjord_gaussian.jl:48-107 with in_dims + 1 <= 64 and hsize <= 64, Tsit5; with RNDE_FFJORD_ENGINE[] = :tiled, in_dims <= 64 and
 # hsize <= 112 (experiments/ffjord_tabular.jl's 43 -> 100).  Refused with an error that names the limit: the default forw_n_back
-# (Tracker.forward), widths above the engine's limit, the {false} method's regularize = true rows.
+# (Tracker.forward) and widths above the engine's limit.  The {false} method's `regularize = true` (kinetic energy and Jacobian norm rows,
+# ffjord.jl:53-66) runs the library's kinetic entries: in_dims + 3 <= 64 on the one-workgroup engine, the tiled engine's limits unchanged.
 # Both call methods are one Tracker node (RNDE.ffjord_solve): Tracker.gradient through the patched layer runs RNDE.ffjord_backward.
 using Tracker, Flux, AMDGPU
 using RegNeuralDE: TrackedFFJORD, _convert_tspan
@@ -44,8 +45,19 @@ function _ffjord_call(n::TrackedFFJORD{R}, x, p, e) where {R}
     return logpx, z, z, RNDE.FFJORD_NFE[H], (R ? (saveval = sv,) : nothing)      # (sv.saveval, as a SavedValues reads)
 end
 
+# regularize = true: logpx, lambda1 (kinetic energy), lambda2 (Jacobian norm) as 1 x B rows, all three on the Tracker tape
+function _ffjord_call_kinetic(n::TrackedFFJORD{false}, x, p, e)
+    d, _ = _ffjord_dims(n)
+    (RNDE_FFJORD_ENGINE[] === :tiled || d + 3 <= 64) ||
+        error("RNDE: TrackedFFJORD{false} with regularize = true (kinetic energy and Jacobian norm rows): the chain engine's limit of 64 rows holds ",
+              "in_dims + 3 <= 64 (RNDE_FFJORD_ENGINE[] = :tiled serves in_dims <= 64); got in_dims = ", d)
+    H = _ffjord_handle(n, size(x, 2))
+    logpx, l1, l2 = RNDE.ffjord_solve_kinetic(H, x, p, e, _convert_tspan(n.tspan, p))
+    return logpx, reshape(l1, 1, :), reshape(l2, 1, :), RNDE.FFJORD_NFE[H], nothing
+end
+
 (n::TrackedFFJORD{false})(x, p = n.p, e = RNDE_randn(size(x)...); regularize = false) =
-    regularize ? error("RNDE: TrackedFFJORD{false} with regularize = true (kinetic energy and Jacobian norm rows) is not served") : _ffjord_call(n, x, p, e)
+    regularize ? _ffjord_call_kinetic(n, x, p, e) : _ffjord_call(n, x, p, e)
 (n::TrackedFFJORD{true})(x, p = n.p, e = RNDE_randn(size(x)...); regularize = false) = _ffjord_call(n, x, p, e)
 
 function RegNeuralDE.sample(n::TrackedFFJORD, indims::Int, p = n.p; nsamples::Int = 1)

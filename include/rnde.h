@@ -555,7 +555,8 @@ rnde_status rnde_latent_encode_backward(rnde_latent* h, const float* z0_bar_dev,
  * Parameters in Flux.destructure order: per layer layer_W (out x in, column-major), layer_B, bias_W, bias_B, gate_W (each out).
  * Refused at create with a message naming the limit: dynamics other than ConcatSquash (the default forw_n_back through Tracker.forward),
  * in_dims + 1 > 64 or hidden > 64 (rnde_ffjord_create; rnde_ffjord_create_tiled below serves wider models), kinetic_reg != 0 (the
- * {false} method's regularize = true rows), solvers other than Tsit5.
+ * {false} method's regularize = true rows at create: the keyword is a call-time one, served by the *_kinetic entries below on handles
+ * created with kinetic_reg = 0), solvers other than Tsit5.
  * ====================================================================================================================== */
 typedef enum { RNDE_FFJORD_CONCAT_SQUASH = 0, RNDE_FFJORD_TRACKER_FORWARD = 1 } rnde_ffjord_dynamics;
 typedef struct {
@@ -563,7 +564,7 @@ typedef struct {
     int32_t dynamics;              /* rnde_ffjord_dynamics */
     int32_t time_dep;              /* the layer's time_dep flag (the ConcatSquash layers always read t) */
     int32_t regularize;            /* 0: {false}, 1: {true} */
-    int32_t kinetic_reg;           /* {false} called with regularize = true: refused */
+    int32_t kinetic_reg;           /* must be 0: refused at create (regularize = true is a call-time keyword: the *_kinetic entries) */
     int32_t max_batch, solver;     /* solver: RNDE_SOLVER_TSIT5 */
     float reltol, abstol;
     int32_t cb_save_start;         /* 1: the saving callback also fires at init (value 0) */
@@ -609,6 +610,29 @@ rnde_status rnde_ffjord_timing(rnde_ffjord* h, float* solve_ms, float* reverse_m
  * a_l = sig(h_l) .* g_l: the same value as the D unit-probe VJPs, rounded differently. */
 rnde_status rnde_ffjord_create_tiled(const rnde_ffjord_config* cfg, rnde_ffjord** out);
 int32_t     rnde_ffjord_engine(const rnde_ffjord* h);          /* 0: one workgroup (rnde_ffjord_create), 1: tiled; -1 for NULL */
+/* TrackedFFJORD{false} called with regularize = true (ffjord.jl:53-66): the state grows to [z; l; lambda1; lambda2] (D + 3 rows, the last
+ * three starting at zero) with d lambda1 / dt = sum f^2 (the kinetic energy) and d lambda2 / dt = sum eJ^2 (the Hutchinson estimate of the
+ * Jacobian's Frobenius norm), eJ as the trace row builds it.  The controller (initial step, error norm, PI step) runs over all D + 3 rows;
+ * NFE is 3 + 6 per attempt as before.  reg_out_dev: 2 x B, the lambda1 row then the lambda2 row.  The other arguments are those of
+ * rnde_ffjord_forward / _replay without the saved values.  On handles created with regularize = 0 and kinetic_reg = 0, either engine; a
+ * handle's state, tape and reverse workspace grow to D + 3 rows at its first kinetic call, and plain calls on it are unaffected.
+ * Limits: one workgroup in_dims + 3 <= 64 and hidden <= 64; tiled in_dims <= 64 and hidden <= 112 (no LDS beyond the plain kernels').  A
+ * kinetic call outside them, or on a regularize = 1 handle, is RNDE_ERR_BAD_ARG with a message that names the limit. */
+rnde_status rnde_ffjord_forward_kinetic(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0, float t1,
+                                        uint64_t seed, float* logpx_dev, float* reg_out_dev, float* z_out_dev, int64_t* nfe_out,
+                                        int32_t keep_tape, void* stream);
+rnde_status rnde_ffjord_forward_kinetic_replay(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0,
+                                               float t1, uint64_t seed, const float* steps_host, int32_t n_steps, float* logpx_dev,
+                                               float* reg_out_dev, float* z_out_dev, int64_t* nfe_out, int32_t keep_tape, void* stream);
+/* Reverse pass of a taped kinetic forward: end-state cotangents (-z logpx_bar, -logpx_bar, reg_bar row 0, reg_bar row 1); reg_bar_dev is
+ * 2 x B (NULL = zeros).  rnde_ffjord_backward on a kinetic tape behaves as reg_bar_dev = NULL.  Deterministic. */
+rnde_status rnde_ffjord_backward_kinetic(rnde_ffjord* h, const float* logpx_bar_dev, const float* reg_bar_dev, float* p_bar_dev, float* x_bar_dev,
+                                         void* stream);
+/* One evaluation of the kinetic right-hand side: out_dev (D + 3) x B = [f(x, t); -e . eJ; sum f^2; sum eJ^2]. */
+rnde_status rnde_ffjord_debug_feval_kinetic(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t,
+                                            float* out_dev, void* stream);
+/* (t, dt, EEst, accepted) of every attempt of the last solve, plain or kinetic, as rnde_node_steps (log_host NULL: the count only). */
+rnde_status rnde_ffjord_step_log(rnde_ffjord* h, float* log_host, int32_t capacity, int32_t* n_attempts_out);
 
 #ifdef __cplusplus
 }

@@ -186,6 +186,11 @@ def lib():
     L.rnde_ffjord_create_tiled.argtypes = [C.POINTER(FfjordConfig), C.POINTER(vp)]
     L.rnde_ffjord_engine.restype = i32
     L.rnde_ffjord_engine.argtypes = [vp]
+    L.rnde_ffjord_forward_kinetic.argtypes = [vp, vp, vp, vp, i32, f, f, u64, vp, vp, vp, i64p, i32, vp]
+    L.rnde_ffjord_forward_kinetic_replay.argtypes = [vp, vp, vp, vp, i32, f, f, u64, fp, i32, vp, vp, vp, i64p, i32, vp]
+    L.rnde_ffjord_backward_kinetic.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.rnde_ffjord_debug_feval_kinetic.argtypes = [vp, vp, vp, vp, i32, f, vp, vp]
+    L.rnde_ffjord_step_log.argtypes = [vp, fp, i32, i32p]
     _lib = L
     return L
 
@@ -201,7 +206,8 @@ EXPORTS = ["rnde_version", "rnde_last_error", "rnde_param_count", "rnde_node_cre
            "rnde_latent_decode_loss", "rnde_latent_encode_backward", "rnde_adamax_step",
            "rnde_ffjord_param_count", "rnde_ffjord_create", "rnde_ffjord_destroy", "rnde_ffjord_last_error", "rnde_ffjord_forward",
            "rnde_ffjord_forward_replay", "rnde_ffjord_steps", "rnde_ffjord_backward", "rnde_ffjord_sample", "rnde_ffjord_debug_feval",
-           "rnde_ffjord_timing", "rnde_ffjord_create_tiled", "rnde_ffjord_engine"]
+           "rnde_ffjord_timing", "rnde_ffjord_create_tiled", "rnde_ffjord_engine", "rnde_ffjord_forward_kinetic",
+           "rnde_ffjord_forward_kinetic_replay", "rnde_ffjord_backward_kinetic", "rnde_ffjord_debug_feval_kinetic", "rnde_ffjord_step_log"]
 
 
 def check(h, status):

@@ -11,12 +11,18 @@
 // needs, and no meeting.  The trace row makes the VJP second order: its reverse differentiates W1' (s1 .* sig(h1) .* ...) and
 // sig'(h) = sig(h) (1 - sig(h)) enters.  Parameter cotangents go to a thread-private column of pacc ([P][Bp], plain read-modify-write,
 // no atomics); rnde_ffjord_reduce_kernel sums the columns in a fixed order.
+//
+// Kinetic variant (KIN): F = [f; -e . eJ; sum f^2; sum eJ^2] with the stage cotangent (lz, ll, l1, l2).  The cotangent of f becomes
+// lz + 2 l1 f and the cotangent of eJ becomes w = -ll e + 2 l2 eJ; the plain sweep is the case l1 = l2 = 0, where w = c e.  Wherever the
+// reverse of tr = e . W1' v1 uses c e the kinetic sweep uses w (v1-bar = W1 w, W1-bar += v1 w'); the rest of the second-order chain is
+// the same.  Two more per-column vectors (lz + 2 l1 f, and w) and one more D x H product (eJ) per stage.
 #pragma once
 #include "rnde_ffjord.h"
 
 namespace rnde {
 
 constexpr int kFfVjpVecs = 22;        // per-column vectors of one reverse evaluation (rows: max(H, D))
+constexpr int kFfVjpVecsKin = 24;     // the kinetic sweep: + lz + 2 l1 f, + w
 
 struct FfStepRec { float t, dt, eest, svb; };     // one accepted step, in forward order; svb = cotangent of its saved value EEst * dt
 
@@ -32,6 +38,7 @@ struct FfRevParams {
     float* x_bar;                     // D x B caller layout (may be NULL)
     int n_acc, B, Bp;
     float reltol, abstol;
+    const float* reg_bar;             // kinetic sweep: 2 x B cotangents of (lambda1, lambda2), or NULL (zeros)
 };
 
 __device__ __forceinline__ float ff_dsig(float s) { return s * (1.f - s); }
@@ -43,16 +50,19 @@ struct FfSlots {
 };
 
 // ybar[0:D] += (d F / d z)' lam and pacc += (d F / d p)' lam, F = [f(z, t); -e . eJ], lam = (lz; ll)
-__device__ inline void ff_vjp(const FfGeo& G, const float* p, float t, FfVec z, FfVec e, FfVec lz, float ll, FfVec zb, float* pacc, int Bp,
-                              const FfSlots V) {
+// KIN: F = [f; -e . eJ; sum f^2; sum eJ^2], lam = (lz; ll; l1; l2)
+template <bool KIN = false>
+__device__ inline void ff_vjp(const FfGeo& G, const float* p, float t, FfVec z, FfVec e, FfVec lz_in, float ll, FfVec zb, float* pacc, int Bp,
+                              const FfSlots V, float l1 = 0.f, float l2 = 0.f) {
     const FfLayer L[3] = {ff_layer(G, p, 0), ff_layer(G, p, 1), ff_layer(G, p, 2)};
     const int D = G.D, H = G.H;
     const FfVec P1 = V(0), H1 = V(1), X1 = V(2), P2 = V(3), H2 = V(4), X2 = V(5), P3 = V(6);
     const FfVec M2 = V(7), V2 = V(8), M1 = V(9), V1 = V(10);
     const FfVec Mb1 = V(11), Hb1 = V(12), SB1 = V(13), Mb2 = V(14), Hb2 = V(15), SB2 = V(16), SB3 = V(17), Pb2 = V(18), Pb1 = V(19);
     const FfVec V3 = V(20), Pb3 = V(21);            // s3 .* e and s3 .* lz (the last layer's gates, evaluated once)
+    const FfVec lz = KIN ? V(22) : lz_in, WV = KIN ? V(23) : e;      // KIN: the cotangent of f, and w (the cotangent of eJ)
     const float c = -ll;
-    for (int i = 0; i < D; ++i) { const float s3 = L[2].gate(i, t); V3[i] = s3 * e[i]; Pb3[i] = s3 * lz[i]; }
+    for (int i = 0; i < D; ++i) { const float s3 = L[2].gate(i, t); V3[i] = s3 * e[i]; if constexpr (!KIN) Pb3[i] = s3 * lz[i]; }
     // ---- primal and the trace's forward (the VJP of forw_n_back) ----
     for (int o = 0; o < H; ++o) {
         float acc = L[0].b(o);
@@ -68,6 +78,11 @@ __device__ inline void ff_vjp(const FfGeo& G, const float* p, float t, FfVec z, 
         float acc = L[2].b(i);
         for (int k = 0; k < H; ++k) acc = fmaf(L[2].W(i, k), X2[k], acc);
         P3[i] = acc;
+        if constexpr (KIN) {           // cotangent of f: lz + 2 l1 f
+            const float s3 = L[2].gate(i, t);
+            lz[i] = fmaf(2.f * l1, fmaf(acc, s3, L[2].shift(i, t)), lz_in[i]);
+            Pb3[i] = s3 * lz[i];
+        }
     }
     for (int k = 0; k < H; ++k) {
         float acc = 0.f;
@@ -79,11 +94,17 @@ __device__ inline void ff_vjp(const FfGeo& G, const float* p, float t, FfVec z, 
         for (int k = 0; k < H; ++k) acc = fmaf(L[1].W(k, j), V2[k], acc);
         M1[j] = acc; V1[j] = acc * ff_sig(H1[j]) * L[0].gate(j, t);
     }
-    // ---- reverse of tr = e . W1' v1 (cotangent c) ----
+    if constexpr (KIN)                 // w = c e + 2 l2 eJ, eJ = W1' v1
+        for (int i = 0; i < D; ++i) {
+            float ej = 0.f;
+            for (int j = 0; j < H; ++j) ej = fmaf(L[0].W(j, i), V1[j], ej);
+            WV[i] = fmaf(2.f * l2, ej, c * e[i]);
+        }
+    // ---- reverse of tr = e . W1' v1 (cotangent c; KIN: of eJ = W1' v1, cotangent w) ----
     for (int j = 0; j < H; ++j) {
         float acc = 0.f;
-        for (int i = 0; i < D; ++i) acc = fmaf(L[0].W(j, i), e[i], acc);
-        const float vb = c * acc, s = L[0].gate(j, t), sg = ff_sig(H1[j]);
+        for (int i = 0; i < D; ++i) acc = fmaf(L[0].W(j, i), WV[i], acc);
+        const float vb = KIN ? acc : c * acc, s = L[0].gate(j, t), sg = ff_sig(H1[j]);
         Mb1[j] = vb * sg * s; Hb1[j] = vb * M1[j] * s * ff_dsig(sg); SB1[j] = vb * M1[j] * sg;
     }
     for (int k = 0; k < H; ++k) {
@@ -126,7 +147,7 @@ __device__ inline void ff_vjp(const FfGeo& G, const float* p, float t, FfVec z, 
             else { pb = Pb3[o]; beta = lz[o]; sb = SB3[o]; }
             for (int i = 0; i < in; ++i) {
                 float w;
-                if (l == 0) w = c * V1[o] * e[i] + pb * z[i];
+                if (l == 0) w = (KIN ? V1[o] * WV[i] : c * V1[o] * e[i]) + pb * z[i];
                 else if (l == 1) w = V2[o] * Mb1[i] + pb * X1[i];
                 else w = V3[o] * Mb2[i] + pb * X2[i];
                 acc_p(off + i * out + o, w);
@@ -140,11 +161,12 @@ __device__ inline void ff_vjp(const FfGeo& G, const float* p, float t, FfVec z, 
     }
 }
 
+template <bool KIN>
 __global__ __launch_bounds__(256) void rnde_ffjord_reverse_kernel(const FfRevParams Q) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= Q.B) return;
     const FfGeo& G = Q.G;
-    const int D = G.D, R = D + 1, Bp = Q.Bp, HR = (G.H > R ? G.H : R);
+    const int D = G.D, R = D + (KIN ? 3 : 1), Bp = Q.Bp, HR = (G.H > R ? G.H : R);
     const FfSlots slot{Q.ws + b, (size_t)HR * Bp, Bp};
     const FfSlots Ys{slot.base, slot.step, Bp}, Ks{slot.base + 7 * slot.step, slot.step, Bp}, Kb{slot.base + 14 * slot.step, slot.step, Bp};
     const FfVec UB = slot(21), UBn = slot(22), Yb = slot(23);
@@ -158,6 +180,7 @@ __global__ __launch_bounds__(256) void rnde_ffjord_reverse_kernel(const FfRevPar
         const float* uT = Q.tape + (size_t)Q.n_acc * RB + b;
         for (int r = 0; r < D; ++r) UB[r] = -g * uT[(size_t)r * Bp];
         UB[D] = -g;
+        if constexpr (KIN) { UB[D + 1] = Q.reg_bar ? Q.reg_bar[b] : 0.f; UB[D + 2] = Q.reg_bar ? Q.reg_bar[(size_t)Q.B + b] : 0.f; }
     }
     const double N = (double)R * (double)Q.B;
     for (int n = Q.n_acc - 1; n >= 0; --n) {
@@ -172,7 +195,9 @@ __global__ __launch_bounds__(256) void rnde_ffjord_reverse_kernel(const FfRevPar
                 Ys(s)[r] = U[r] + dt * acc;
             }
             FfVec kk = Ks(s);
-            kk[D] = -ff_eval(G, Q.p, t + kTsC[s] * dt, Ys(s), e, -1, V(0), V(1), V(2), kk, true);
+            float kin[2];
+            kk[D] = -ff_eval<KIN>(G, Q.p, t + kTsC[s] * dt, Ys(s), e, -1, V(0), V(1), V(2), kk, true, kin);
+            if constexpr (KIN) { kk[D + 1] = kin[0]; kk[D + 2] = kin[1]; }
         }
         for (int s = 0; s < 7; ++s) for (int r = 0; r < R; ++r) Kb(s)[r] = 0.f;
         for (int r = 0; r < R; ++r) { UBn[r] = 0.f; Yb[r] = UB[r]; }        // Yb: cotangent of unew = stage-7 input
@@ -195,7 +220,8 @@ __global__ __launch_bounds__(256) void rnde_ffjord_reverse_kernel(const FfRevPar
         // ---- B: the stages, last to first ----
         for (int s = 6; s >= 0; --s) {
             if (s != 6) for (int r = 0; r < R; ++r) Yb[r] = 0.f;
-            ff_vjp(G, Q.p, t + kTsC[s] * dt, Ys(s), e, Kb(s), Kb(s)[D], Yb, pacc, Bp, V);
+            if constexpr (KIN) ff_vjp<true>(G, Q.p, t + kTsC[s] * dt, Ys(s), e, Kb(s), Kb(s)[D], Yb, pacc, Bp, V, Kb(s)[D + 1], Kb(s)[D + 2]);
+            else ff_vjp(G, Q.p, t + kTsC[s] * dt, Ys(s), e, Kb(s), Kb(s)[D], Yb, pacc, Bp, V);
             for (int r = 0; r < R; ++r) {
                 const float y = Yb[r];
                 UBn[r] += y;

@@ -9,6 +9,10 @@
 // L2-resident); no private scratch.  Every product, the weight cotangents included (outer products over the tile's 16 columns, k = 2 x 16),
 // runs on the matrix cores.  Parameter cotangents accumulate in the tile's own row of pacc ([ntiles][P], plain read-modify-write by one lane
 // per entry, no atomics); rnde_ffjordt_reduce_kernel sums the tiles in tile order in double.
+//
+// Kinetic variant (KIN; the arithmetic of rnde_bffjord.h): the stage cotangent is (lz, ll, l1, l2) over R = D + 3 rows.  The cotangent of f,
+// lz + 2 l1 f, is formed in the epilogue of the layer-3 product; w = -ll e + 2 l2 eJ needs eJ = W1' v1, one more transposed product once v1
+// is known, and W1 w replaces c (W1 e).  Both are two more vector slots of the per-tile global buffer: no LDS beyond the plain kernel's.
 #pragma once
 #include "rnde_bffjord.h"      // FfStepRec, ff_dsig
 #include "rnde_ffjordt.h"
@@ -16,6 +20,7 @@
 namespace rnde {
 
 constexpr int kFtVjpVecs = 27;
+constexpr int kFtVjpVecsKin = 28;      // + w (the cotangent of eJ)
 
 struct FtRevParams {
     FtGeo G;
@@ -29,11 +34,12 @@ struct FtRevParams {
     float* x_bar;                     // D x B caller layout (may be NULL)
     int n_acc, B, Bp;
     float reltol, abstol;
+    const float* reg_bar;             // kinetic sweep: 2 x B cotangents of (lambda1, lambda2), or NULL (zeros)
 };
 
-__host__ __device__ inline size_t ft_rev_ws_floats(const FtGeo& G) {
-    const int R = G.D + 1, FP = G.HP > G.DP ? G.HP : G.DP;
-    return (size_t)24 * R * 16 + (size_t)kFtVjpVecs * FP * 16;
+__host__ __device__ inline size_t ft_rev_ws_floats(const FtGeo& G, bool kin = false) {
+    const int R = G.D + (kin ? 3 : 1), FP = G.HP > G.DP ? G.HP : G.DP;
+    return (size_t)24 * R * 16 + (size_t)(kin ? kFtVjpVecsKin : kFtVjpVecs) * FP * 16;
 }
 
 // dW[o][i] += sum_c A1[o][c] B1[i][c] + A2[o][c] B2[i][c] (all [feature][16]) into pw[i * out + o]; output tiles dealt to the waves
@@ -60,6 +66,8 @@ __device__ __forceinline__ void ft_wgrad(const float* A1, const float* B1, const
 
 // yb[0:D] += (dF/dz)' lam and pacc += (dF/dp)' lam for the tile's 16 columns, F = [f(z, t); -e . eJ], lam = (lz; ll) = kb.
 // z: the stage input ([R][16]), kb: its cotangent ([R][16]), yb: [R][16], V: the tile's vector slots.  Ends behind a barrier.
+// KIN: F = [f; -e . eJ; sum f^2; sum eJ^2], lam = (lz; ll; l1; l2).
+template <bool KIN = false>
 __device__ __forceinline__ void ft_vjp(const FtGeo& G, const FtLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid) {
     const int lane = tid & 63, wave = tid >> 6, c = lane & 15, D = G.D, H = G.H, HP = G.HP, DP = G.DP;
     const int FP = HP > DP ? HP : DP;
@@ -68,6 +76,8 @@ __device__ __forceinline__ void ft_vjp(const FtGeo& G, const FtLds& L, float t, 
     float *P3 = vec(9), *V3 = vec(10), *Pb3 = vec(11), *T2 = vec(12), *M2 = vec(13), *V2 = vec(14), *M1 = vec(15), *V1 = vec(16);
     float *CV1 = vec(17), *Mb1 = vec(18), *Hb1 = vec(19), *SB1 = vec(20), *Mb2 = vec(21), *Hb2 = vec(22), *Pb2 = vec(23), *SB2 = vec(24);
     float *SB3 = vec(25), *Pb1 = vec(26);
+    float* WV = KIN ? vec(27) : nullptr;                 // w = c e + 2 l2 eJ
+    float *l1v = L.red + 96, *l2v = L.red + 112;        // per column: the cotangents of the two regulariser rows
     const float *W1 = L.W + G.woff[0], *W2 = L.W + G.woff[1], *W3 = L.W + G.woff[2];
     const float *g1 = L.GT, *g2 = L.GT + HP, *g3 = L.GT + 2 * HP;
     float* cv = L.red + 80;           // per column: c = -(cotangent of the trace row)
@@ -78,6 +88,8 @@ __device__ __forceinline__ void ft_vjp(const FtGeo& G, const FtLds& L, float t, 
         LZ[idx] = r < D ? kb[idx] : 0.f;
     }
     if (tid < 16) cv[tid] = -kb[D * 16 + tid];
+    if constexpr (KIN)
+        if (tid < 16) { l1v[tid] = kb[(D + 1) * 16 + tid]; l2v[tid] = kb[(D + 2) * 16 + tid]; }
     __syncthreads();
     // primal layer 1, and W1 e for the reverse of the trace
     ft_fwd(W1, G.ld[0], G.inp[0], G.outp[0], ZP, wave, lane, [&](int r0, f32x4 v) {
@@ -90,14 +102,15 @@ __device__ __forceinline__ void ft_vjp(const FtGeo& G, const FtLds& L, float t, 
             P1[ix] = p1; SG1[ix] = sg; X1[ix] = x1;
         }
     });
-    ft_fwd(W1, G.ld[0], G.inp[0], G.outp[0], L.E, wave, lane, [&](int r0, f32x4 v) {
+    if constexpr (!KIN)
+        ft_fwd(W1, G.ld[0], G.inp[0], G.outp[0], L.E, wave, lane, [&](int r0, f32x4 v) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) VB1[(r0 + j) * 16 + c] = cv[c] * v[j];
-    });
+            for (int j = 0; j < 4; ++j) VB1[(r0 + j) * 16 + c] = cv[c] * v[j];
+        });
     for (int idx = tid; idx < DP * 16; idx += kFtThreads) {
         const float s3 = g3[idx >> 4];
         V3[idx] = s3 * L.E[idx];
-        Pb3[idx] = s3 * LZ[idx];
+        if constexpr (!KIN) Pb3[idx] = s3 * LZ[idx];
     }
     __syncthreads();
     ft_fwd(W2, G.ld[1], G.inp[1], G.outp[1], X1, wave, lane, [&](int r0, f32x4 v) {
@@ -113,30 +126,64 @@ __device__ __forceinline__ void ft_vjp(const FtGeo& G, const FtLds& L, float t, 
     __syncthreads();
     // primal layer 3 (pre-gate), the trace's m2 = W3' (g3 .* e), and W3' (g3 .* lz) for the primal reverse
     ft_fwd(W3, G.ld[2], G.inp[2], G.outp[2], X2, wave, lane, [&](int r0, f32x4 v) {
-        const float* b = ft_vec(G, L.W, 2, 0);
+        const float *b = ft_vec(G, L.W, 2, 0), *bw = ft_vec(G, L.W, 2, 1), *bb = ft_vec(G, L.W, 2, 2);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { const int o = r0 + j; P3[o * 16 + c] = o < D ? v[j] + b[o] : 0.f; }
+        for (int j = 0; j < 4; ++j) {
+            const int o = r0 + j, ix = o * 16 + c;
+            const float p3 = o < D ? v[j] + b[o] : 0.f;
+            P3[ix] = p3;
+            if constexpr (KIN) {       // the cotangent of f: lz + 2 l1 f (this lane owns the entry)
+                const float lz = o < D ? fmaf(2.f * l1v[c], fmaf(p3, g3[o], fmaf(bw[o], t, bb[o])), LZ[ix]) : 0.f;
+                LZ[ix] = lz; Pb3[ix] = g3[o] * lz;
+            }
+        }
     });
     ft_tr(W3, G.ld[2], G.inp[2], G.outp[2], V3, wave, lane, [&](int r0, f32x4 v) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) { const int ix = (r0 + j) * 16 + c; M2[ix] = v[j]; V2[ix] = v[j] * SG2[ix] * g2[r0 + j]; }
     });
-    ft_tr(W3, G.ld[2], G.inp[2], G.outp[2], Pb3, wave, lane, [&](int r0, f32x4 v) {
+    if constexpr (!KIN)
+        ft_tr(W3, G.ld[2], G.inp[2], G.outp[2], Pb3, wave, lane, [&](int r0, f32x4 v) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) T2[(r0 + j) * 16 + c] = v[j];
-    });
+            for (int j = 0; j < 4; ++j) T2[(r0 + j) * 16 + c] = v[j];
+        });
     __syncthreads();
+    if constexpr (KIN)                 // (Pb3 was formed by the layer-3 epilogue above)
+        ft_tr(W3, G.ld[2], G.inp[2], G.outp[2], Pb3, wave, lane, [&](int r0, f32x4 v) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) T2[(r0 + j) * 16 + c] = v[j];
+        });
     // m1 = W2' v2; the reverse of tr = e . W1' v1 through layer 1
     ft_tr(W2, G.ld[1], G.inp[1], G.outp[1], V2, wave, lane, [&](int r0, f32x4 v) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int o = r0 + j, ix = o * 16 + c;
-            const float m1 = v[j], sg = SG1[ix], s = g1[o], vb = VB1[ix];
-            M1[ix] = m1; V1[ix] = m1 * sg * s; CV1[ix] = cv[c] * (m1 * sg * s);
-            Mb1[ix] = vb * sg * s; Hb1[ix] = vb * m1 * s * ff_dsig(sg); SB1[ix] = vb * m1 * sg;
+            const float m1 = v[j], sg = SG1[ix], s = g1[o];
+            M1[ix] = m1; V1[ix] = m1 * sg * s;
+            if constexpr (!KIN) {
+                const float vb = VB1[ix];
+                CV1[ix] = cv[c] * (m1 * sg * s);
+                Mb1[ix] = vb * sg * s; Hb1[ix] = vb * m1 * s * ff_dsig(sg); SB1[ix] = vb * m1 * sg;
+            }
         }
     });
     __syncthreads();
+    if constexpr (KIN) {               // w = c e + 2 l2 eJ (eJ = W1' v1), then v1-bar = W1 w where the plain sweep has c (W1 e)
+        ft_tr(W1, G.ld[0], G.inp[0], G.outp[0], V1, wave, lane, [&](int r0, f32x4 v) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { const int ix = (r0 + j) * 16 + c; WV[ix] = fmaf(2.f * l2v[c], v[j], cv[c] * L.E[ix]); }
+        });
+        __syncthreads();
+        ft_fwd(W1, G.ld[0], G.inp[0], G.outp[0], WV, wave, lane, [&](int r0, f32x4 v) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int o = r0 + j, ix = o * 16 + c;
+                const float vb = v[j], m1 = M1[ix], sg = SG1[ix], s = g1[o];
+                Mb1[ix] = vb * sg * s; Hb1[ix] = vb * m1 * s * ff_dsig(sg); SB1[ix] = vb * m1 * sg;
+            }
+        });
+        __syncthreads();
+    }
     // through layer 2 (trace), plus the primal's cotangent of h2
     ft_fwd(W2, G.ld[1], G.inp[1], G.outp[1], Mb1, wave, lane, [&](int r0, f32x4 v) {
 #pragma unroll
@@ -166,7 +213,7 @@ __device__ __forceinline__ void ft_vjp(const FtGeo& G, const FtLds& L, float t, 
         for (int j = 0; j < 4; ++j) { const int r = r0 + j; if (r < D) yb[r * 16 + c] += v[j]; }
     });
     // parameter cotangents
-    ft_wgrad(CV1, L.E, Pb1, ZP, G.outp[0], G.inp[0], G.out[0], G.in[0], pacc + G.off[0], wave, lane);
+    ft_wgrad(KIN ? V1 : CV1, KIN ? WV : L.E, Pb1, ZP, G.outp[0], G.inp[0], G.out[0], G.in[0], pacc + G.off[0], wave, lane);
     ft_wgrad(V2, Mb1, Pb2, X1, G.outp[1], G.inp[1], G.out[1], G.in[1], pacc + G.off[1], wave, lane);
     ft_wgrad(V3, Mb2, Pb3, X2, G.outp[2], G.inp[2], G.out[2], G.in[2], pacc + G.off[2], wave, lane);
     for (int q = tid; q < 2 * H + D; q += kFtThreads) {
@@ -185,10 +232,11 @@ __device__ __forceinline__ void ft_vjp(const FtGeo& G, const FtLds& L, float t, 
     __syncthreads();
 }
 
+template <bool KIN>
 __global__ __launch_bounds__(kFtThreads) void rnde_ffjordt_reverse_kernel(const FtRevParams Q) {
     extern __shared__ float ft_smem[];
     const FtGeo& G = Q.G;
-    const int tile = blockIdx.x, tid = threadIdx.x, D = G.D, R = D + 1, Bp = Q.Bp, col0 = tile * 16, nel = R * 16;
+    const int tile = blockIdx.x, tid = threadIdx.x, D = G.D, R = D + (KIN ? 3 : 1), Bp = Q.Bp, col0 = tile * 16, nel = R * 16;
     const FtLds L = ft_lds(G, ft_smem);
     ft_load_params(G, Q.p, L.W, tid);
     for (int idx = tid; idx < G.DP * 16; idx += kFtThreads) {
@@ -196,7 +244,7 @@ __global__ __launch_bounds__(kFtThreads) void rnde_ffjordt_reverse_kernel(const 
         L.E[idx] = (r < D && col < Q.B) ? Q.e[(size_t)col * D + r] : 0.f;
         L.X[idx] = 0.f;
     }
-    float* ws = Q.ws + (size_t)tile * ft_rev_ws_floats(G);
+    float* ws = Q.ws + (size_t)tile * ft_rev_ws_floats(G, KIN);
     const size_t RS = (size_t)R * 16;
     auto Ys = [&](int s) { return ws + (size_t)s * RS; };
     auto Ks = [&](int s) { return ws + (size_t)(7 + s) * RS; };
@@ -211,6 +259,8 @@ __global__ __launch_bounds__(kFtThreads) void rnde_ffjordt_reverse_kernel(const 
         if (col < Q.B) {
             const float g = Q.logpx_bar[col];
             v = r < D ? -g * Q.tape[(size_t)Q.n_acc * RB + (size_t)r * Bp + col] : -g;
+            if constexpr (KIN)
+                if (r > D) v = Q.reg_bar ? Q.reg_bar[(size_t)(r - D - 1) * Q.B + col] : 0.f;
         }
         UB[idx] = v;
     }
@@ -230,7 +280,7 @@ __global__ __launch_bounds__(kFtThreads) void rnde_ffjordt_reverse_kernel(const 
                 Ys(s)[idx] = y;
                 if (r < D) L.X[idx] = y;
             }
-            ft_eval(G, L, t + kTsC[s] * dt, Ks(s), 16, 0, 1.f, -1.f, nullptr, tid);
+            ft_eval<KIN>(G, L, t + kTsC[s] * dt, Ks(s), 16, 0, 1.f, -1.f, nullptr, tid);
         }
         for (int idx = tid; idx < nel; idx += kFtThreads) {
             for (int s = 0; s < 7; ++s) Kb(s)[idx] = 0.f;
@@ -261,7 +311,7 @@ __global__ __launch_bounds__(kFtThreads) void rnde_ffjordt_reverse_kernel(const 
                 for (int idx = tid; idx < nel; idx += kFtThreads) Yb[idx] = 0.f;
                 __syncthreads();
             }
-            ft_vjp(G, L, t + kTsC[s] * dt, Ys(s), Kb(s), Yb, V, pacc, tid);
+            ft_vjp<KIN>(G, L, t + kTsC[s] * dt, Ys(s), Kb(s), Yb, V, pacc, tid);
             for (int idx = tid; idx < nel; idx += kFtThreads) {
                 const float y = Yb[idx];
                 UBn[idx] += y;

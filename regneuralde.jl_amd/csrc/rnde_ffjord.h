@@ -15,6 +15,11 @@
 // The controller is the chain engine's (advance_state_t, rnde_fwd.h) on a StepParams whose D is the AUGMENTED row count D + 1, so the
 // initial-step rule, the PI controller, the step log (StepMeta) and the replay of a given (dt, accept) sequence are those of
 // rnde_node_forward / rnde_node_forward_replay.
+//
+// Kinetic variant (template parameter KIN; TrackedFFJORD{false} called with regularize = true, ffjord.jl:53-66): two more state rows,
+//     d lambda1 / dt = sum f^2 (kinetic energy),   d lambda2 / dt = sum eJ^2 (Hutchinson estimate of the Jacobian's Frobenius norm),
+// R = D + 3 rows under the same controller.  Both sums fall out of the loops that already form f and eJ: no extra network evaluation.
+// Limits: D + 3 <= 64, H <= 64.  The KIN = false instantiations are the code of the plain calls, unchanged.
 #pragma once
 #include "rnde_fwd.h"
 
@@ -69,9 +74,10 @@ struct FfVec {
 // One evaluation of the augmented right-hand side for one column.
 //   z: the column's D data rows; out: D rows of f, then the trace row -e . eJ (row D);  A, Bv, C: scratch (H, H, max(H, D) rows).
 // probe < 0: e is the caller's column (e[i]); probe >= 0: e is the unit vector of row `probe` (the exact trace, sample()).
-// Returns e . eJ.
+// Returns e . eJ.  KIN: kin[0] = sum f^2, kin[1] = sum eJ^2 (write_f must be set).
+template <bool KIN = false>
 __device__ inline float ff_eval(const FfGeo& G, const float* p, float t, FfVec z, FfVec e, int probe, FfVec A, FfVec Bv, FfVec C, FfVec out,
-                                bool write_f) {
+                                bool write_f, float* kin = nullptr) {
     const FfLayer L1 = ff_layer(G, p, 0), L2 = ff_layer(G, p, 1), L3 = ff_layer(G, p, 2);
     const int D = G.D, H = G.H;
     for (int o = 0; o < H; ++o) {
@@ -85,12 +91,15 @@ __device__ inline float ff_eval(const FfGeo& G, const float* p, float t, FfVec z
         for (int j = 0; j < H; ++j) acc = fmaf(L2.W(o, j), C[j], acc);
         Bv[o] = fmaf(acc, L2.gate(o, t), L2.shift(o, t));                // h2
     }
+    float ke = 0.f, jn = 0.f;
     if (write_f) {
         for (int k = 0; k < H; ++k) C[k] = ff_softplus(Bv[k]);
         for (int i = 0; i < D; ++i) {
             float acc = L3.b(i);
             for (int k = 0; k < H; ++k) acc = fmaf(L3.W(i, k), C[k], acc);
-            out[i] = fmaf(acc, L3.gate(i, t), L3.shift(i, t));
+            const float f = fmaf(acc, L3.gate(i, t), L3.shift(i, t));
+            out[i] = f;
+            if constexpr (KIN) ke = fmaf(f, f, ke);
         }
     }
     // VJP: v3 = s3 .* e ; v2 = s2 .* sig(h2) .* W3' v3 ; v1 = s1 .* sig(h1) .* W2' v2 ; eJ = W1' v1
@@ -110,7 +119,9 @@ __device__ inline float ff_eval(const FfGeo& G, const float* p, float t, FfVec z
         float ej = 0.f;
         for (int j = 0; j < H; ++j) ej = fmaf(L1.W(j, i), A[j], ej);
         tr = fmaf(probe < 0 ? e[i] : (i == probe ? 1.f : 0.f), ej, tr);
+        if constexpr (KIN) jn = fmaf(ej, ej, jn);
     }
+    if constexpr (KIN) { kin[0] = ke; kin[1] = jn; }
     return tr;
 }
 
@@ -129,6 +140,7 @@ struct FfSolveParams {
     float* norm;                     // [4]: scratch of the initial-step norms (d0, d1 and the third partial for sum_partials: padded to 260)
     int dir, T, Bp;
     float tbase;                     // dir = -1: t1 (the reference's time of tau = 0)
+    float* reg;                      // kinetic solves: 2 x B (lambda1 row, then lambda2 row); NULL otherwise
 };
 
 // fixed-order workgroup sum, carried in double: wave sums, then the waves in order (the same bits on every thread)
@@ -143,14 +155,17 @@ __device__ __forceinline__ double ff_block_sum(float v, float* red, int tid, int
     return s;
 }
 
-// one evaluation for column b: k(:, b) = F(y(:, b), time)
+// one evaluation for column b: k(:, b) = F(y(:, b), time)  (KIN: forward only, rows D + 1 and D + 2 the two regulariser rates)
+template <bool KIN = false>
 __device__ inline void ff_rhs(const FfSolveParams& Q, const float* ps, float time, const float* y, float* k, int b, FfVec A, FfVec Bv, FfVec C) {
     const int Bp = Q.Bp, D = Q.G.D;
     const FfVec z{const_cast<float*>(y) + b, Bp}, kk{k + b, Bp};
     if (Q.dir > 0) {
         const FfVec e{const_cast<float*>(Q.e) + (size_t)b * D, 1};
-        const float tr = ff_eval(Q.G, ps, time, z, e, -1, A, Bv, C, kk, true);
+        float kin[2];
+        const float tr = ff_eval<KIN>(Q.G, ps, time, z, e, -1, A, Bv, C, kk, true, kin);
         kk[D] = -tr;
+        if constexpr (KIN) { kk[D + 1] = kin[0]; kk[D + 2] = kin[1]; }
     } else {
         const float t = Q.tbase - time;
         float tr = 0.f;
@@ -161,10 +176,11 @@ __device__ inline void ff_rhs(const FfSolveParams& Q, const float* ps, float tim
 }
 
 // The whole adaptive solve in one launch (one workgroup, Q.T threads).
+template <bool KIN>
 __global__ __launch_bounds__(kFfMaxThreads) void rnde_ffjord_solve_kernel(const FfSolveParams Q) {
     extern __shared__ float ff_smem[];
     const StepParams& P = Q.F;
-    const int tid = threadIdx.x, T = Q.T, lane = tid & 63, Bp = Q.Bp, B = P.B, D = Q.G.D, R = D + 1;
+    const int tid = threadIdx.x, T = Q.T, lane = tid & 63, Bp = Q.Bp, B = P.B, D = Q.G.D, R = D + (KIN ? 3 : 1);
     const int HS = Q.G.H > D ? Q.G.H : D;
     float* ps = ff_smem;                                   // parameters
     float* red = ff_smem + Q.G.P;                          // 16 wave partials + 8 broadcast doubles
@@ -182,8 +198,8 @@ __global__ __launch_bounds__(kFfMaxThreads) void rnde_ffjord_solve_kernel(const 
     float pa = 0.f, pb = 0.f;
     for (int b = tid; b < B; b += T) {
         for (int r = 0; r < D; ++r) U[(size_t)r * Bp + b] = Q.x[(size_t)b * D + r];
-        U[(size_t)D * Bp + b] = 0.f;
-        ff_rhs(Q, ps, P.t0 + 0.f, U, K(0), b, A, Bv, C);
+        for (int r = D; r < R; ++r) U[(size_t)r * Bp + b] = 0.f;
+        ff_rhs<KIN>(Q, ps, P.t0 + 0.f, U, K(0), b, A, Bv, C);
         for (int r = 0; r < R; ++r) {
             const float xv = U[(size_t)r * Bp + b], kv = K(0)[(size_t)r * Bp + b], sk = at + fabsf(xv) * rt;
             const float a = xv / sk, c = kv / sk;
@@ -203,7 +219,7 @@ __global__ __launch_bounds__(kFfMaxThreads) void rnde_ffjord_solve_kernel(const 
     float pc = 0.f;
     for (int b = tid; b < B; b += T) {
         for (int r = 0; r < R; ++r) Y[(size_t)r * Bp + b] = U[(size_t)r * Bp + b] + dt0 * K(0)[(size_t)r * Bp + b];
-        ff_rhs(Q, ps, P.t0 + dt0, Y, K(1), b, A, Bv, C);
+        ff_rhs<KIN>(Q, ps, P.t0 + dt0, Y, K(1), b, A, Bv, C);
         for (int r = 0; r < R; ++r) {
             const float sk = at + fabsf(U[(size_t)r * Bp + b]) * rt;
             const float a = (K(1)[(size_t)r * Bp + b] - K(0)[(size_t)r * Bp + b]) / sk;
@@ -230,7 +246,7 @@ __global__ __launch_bounds__(kFfMaxThreads) void rnde_ffjord_solve_kernel(const 
                     Y[ix] = g;
                     if (s == 6) UN[ix] = g;
                 }
-                ff_rhs(Q, ps, t + kTsC[s] * dt, Y, K(s), b, A, Bv, C);
+                ff_rhs<KIN>(Q, ps, t + kTsC[s] * dt, Y, K(s), b, A, Bv, C);
             }
             for (int r = 0; r < R; ++r) {                  // embedded error estimate, SURVEY.md B.3
                 const size_t ix = (size_t)r * Bp + b;
@@ -269,25 +285,28 @@ __global__ __launch_bounds__(kFfMaxThreads) void rnde_ffjord_solve_kernel(const 
             }
         }
         if (Q.logpx) Q.logpx[b] = lp - U[(size_t)D * Bp + b];
+        if constexpr (KIN) { Q.reg[b] = U[(size_t)(D + 1) * Bp + b]; Q.reg[(size_t)B + b] = U[(size_t)(D + 2) * Bp + b]; }
     }
 }
 
 // One evaluation of the augmented right-hand side per column (the parity instrument of tests/test_gpu_ffjord.py):
-// out: (D + 1) x B caller layout.  probe < 0: Hutchinson with e; else the exact trace (as sample()).
+// out: (D + 1) x B caller layout.  probe < 0: Hutchinson with e; else the exact trace (as sample()).  KIN: (D + 3) x B, Hutchinson only.
+template <bool KIN>
 __global__ __launch_bounds__(256) void rnde_ffjord_feval_kernel(const FfGeo G, const float* __restrict__ p, const float* __restrict__ x,
                                                                 const float* __restrict__ e, float t, int B, int exact, float* __restrict__ ws,
                                                                 float* __restrict__ out) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
-    const int D = G.D, R = D + 1, HS = G.H > D ? G.H : D;
+    const int D = G.D, R = D + (KIN ? 3 : 1), HS = G.H > D ? G.H : D;
     float* w = ws + (size_t)b * (3 * HS + R);                 // per column: A, Bv, C, out
     const FfVec A{w, 1}, Bv{w + HS, 1}, C{w + 2 * HS, 1}, o{w + 3 * HS, 1};
     const FfVec z{const_cast<float*>(x) + (size_t)b * D, 1};
-    float tr = 0.f;
-    if (!exact) tr = ff_eval(G, p, t, z, FfVec{const_cast<float*>(e) + (size_t)b * D, 1}, -1, A, Bv, C, o, true);
+    float tr = 0.f, kin[2];
+    if (!exact) tr = ff_eval<KIN>(G, p, t, z, FfVec{const_cast<float*>(e) + (size_t)b * D, 1}, -1, A, Bv, C, o, true, kin);
     else for (int i = 0; i < D; ++i) tr += ff_eval(G, p, t, z, z, i, A, Bv, C, o, i == 0);
     for (int r = 0; r < D; ++r) out[(size_t)b * R + r] = o[r];
     out[(size_t)b * R + D] = -tr;
+    if constexpr (KIN) { out[(size_t)b * R + D + 1] = kin[0]; out[(size_t)b * R + D + 2] = kin[1]; }
 }
 
 }  // namespace rnde

@@ -1,6 +1,7 @@
 // rnde_ffjord.hip -- C ABI of TrackedFFJORD (include/rnde.h, "TrackedFFJORD" section): create / forward / replay / backward / sample
 // over the kernels of rnde_ffjord.h (one-launch solve) and rnde_bffjord.h (one-launch reverse sweep), or, on a handle made by
-// rnde_ffjord_create_tiled, over those of rnde_ffjordt.h / rnde_bffjordt.h (the tiled engine).
+// rnde_ffjord_create_tiled, over those of rnde_ffjordt.h / rnde_bffjordt.h (the tiled engine).  The *_kinetic entries run the KIN = true
+// instantiations of the same kernels over D + 3 rows (TrackedFFJORD{false} called with regularize = true).
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -36,7 +37,9 @@ struct rnde_ffjord {
         float reltol = 0.f, abstol = 0.f;
         const float* e = nullptr;    // the probe (the caller's, or e_tape)
         const float* p = nullptr;
+        bool kin = false;            // a kinetic forward: D + 3 rows per record
     } tp;
+    bool kin_ready = false;          // ws / tape / rws hold D + 3 rows (grown by the first kinetic call)
     float* e_tape = nullptr;         // the library's probe of a taped forward (e_buf serves untaped calls)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float fwd_ms = -1.f, rev_ms = -1.f;
@@ -134,7 +137,9 @@ static rnde_status ft_create(const rnde_ffjord_config* c, rnde_ffjord** out) {
     if ((e = hipMalloc(&h->xcc, kMwMeetMax * 4)) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&h->abort_word, 8)) != hipSuccess) return fail(e);
     if ((e = hipMemset(h->abort_word, 0, 8)) != hipSuccess) return fail(e);
-    for (const void* k : {(const void*)rnde_ffjordt_solve_kernel, (const void*)rnde_ffjordt_reverse_kernel, (const void*)rnde_ffjordt_feval_kernel})
+    for (const void* k : {(const void*)rnde_ffjordt_solve_kernel<false>, (const void*)rnde_ffjordt_reverse_kernel<false>,
+                          (const void*)rnde_ffjordt_feval_kernel<false>, (const void*)rnde_ffjordt_solve_kernel<true>,
+                          (const void*)rnde_ffjordt_reverse_kernel<true>, (const void*)rnde_ffjordt_feval_kernel<true>})
         if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes)) != hipSuccess) return fail(e);
     for (auto& v : h->ev) if ((e = hipEventCreate(&v)) != hipSuccess) return fail(e);
     { static std::atomic<int> next_slot{0}; h->xcd_slot = next_slot.fetch_add(1) & 7; }
@@ -187,7 +192,8 @@ extern "C" rnde_status rnde_ffjord_create(const rnde_ffjord_config* c, rnde_ffjo
     if ((e = hipMalloc(&h->meta, MA * sizeof(StepMeta))) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&h->initrec, sizeof(InitRec))) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&h->rec, MA * sizeof(FfStepRec))) != hipSuccess) return fail(e);
-    if ((e = hipFuncSetAttribute((const void*)rnde_ffjord_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes)) != hipSuccess) return fail(e);
+    for (const void* k : {(const void*)rnde_ffjord_solve_kernel<false>, (const void*)rnde_ffjord_solve_kernel<true>})
+        if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes)) != hipSuccess) return fail(e);
     for (auto& v : h->ev) if ((e = hipEventCreate(&v)) != hipSuccess) return fail(e);
     *out = h;
     return RNDE_OK;
@@ -203,10 +209,47 @@ extern "C" void rnde_ffjord_destroy(rnde_ffjord* h) {
     delete h;
 }
 
-// One solve: dir = +1 the forward (logpx; Hutchinson probe e), dir = -1 sampling (exact trace, tau = t1 - t).
+// The first kinetic call of a handle: the limits, then state, tape and reverse workspace for D + 3 rows.  Plain calls go on using the
+// same buffers with their own D + 1 row layout; a plain tape waiting for its backward is carried over.
+static rnde_status ff_kinetic_ready(rnde_ffjord* h) {
+    if (h->cfg.regularize) {
+        h->err = "TrackedFFJORD{true} has no kinetic energy rows: the reference's {true} method never passes regularize on (ffjord.jl:119); "
+                 "create the handle with regularize = 0";
+        return RNDE_ERR_BAD_ARG;
+    }
+    const int D = h->G.D, H = h->G.H, Rk = D + 3;
+    if (h->engine == 0 && (Rk > kFfMaxW || H > kFfMaxW)) {
+        h->err = "TrackedFFJORD kinetic energy rows: widths above the chain engine's limit of 64 are not served (in_dims + 3 <= 64 and hidden <= 64; "
+                 "rnde_ffjord_create_tiled / engine = \"tiled\" serves in_dims <= 64 and hidden <= 112)";
+        return RNDE_ERR_BAD_ARG;
+    }
+    if (h->kin_ready) return RNDE_OK;
+    const size_t RBk = (size_t)Rk * h->Bp, RB = (size_t)h->R * h->Bp, MA = (size_t)h->cfg.max_attempts;
+    const size_t rws = h->engine == 1 ? (size_t)h->ntiles_max * ft_rev_ws_floats(h->TG, true)
+                                      : (size_t)(24 + kFfVjpVecsKin) * std::max(H, Rk) * h->Bp;
+    FCHK(h, hipDeviceSynchronize());           // (rnde_ffjord_debug_feval does not wait for its launch)
+    float *ws = nullptr, *tape = nullptr, *rw = nullptr;
+    hipError_t e = hipMalloc(&ws, 10 * RBk * 4);
+    if (e == hipSuccess) e = hipMalloc(&tape, (MA + 1) * RBk * 4);
+    if (e == hipSuccess) e = hipMalloc(&rw, rws * 4);
+    if (e == hipSuccess && h->tp.valid) e = hipMemcpy(tape, h->tape, ((size_t)h->tp.n_acc + 1) * RB * 4, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) {
+        for (float* q : {ws, tape, rw}) if (q) (void)hipFree(q);
+        h->err = std::string("TrackedFFJORD kinetic energy rows: HIP: ") + hipGetErrorString(e);
+        return RNDE_ERR_HIP;
+    }
+    (void)hipFree(h->ws); (void)hipFree(h->tape); (void)hipFree(h->rws);
+    h->ws = ws; h->tape = tape; h->rws = rw;
+    h->kin_ready = true;
+    return RNDE_OK;
+}
+
+// One solve: dir = +1 the forward (logpx; Hutchinson probe e), dir = -1 sampling (exact trace, tau = t1 - t).  reg_out_dev != NULL: the
+// kinetic forward (D + 3 rows; ff_kinetic_ready has run).
 static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0, float t1,
                             uint64_t seed, const float* steps_host, int32_t n_steps, float* logpx_dev, float* x_out_dev, int32_t keep_tape,
-                            hipStream_t s) {
+                            hipStream_t s, float* reg_out_dev = nullptr) {
+    const bool kin = reg_out_dev != nullptr;
     if (!x_dev || !p_dev || B < 1 || B > h->cfg.max_batch) { h->err = "bad argument (B must be 1..max_batch)"; return RNDE_ERR_BAD_ARG; }
     if (!(t1 > t0)) { h->err = "TrackedFFJORD: tspan must satisfy t1 > t0 (sample() integrates t1 -> t0 itself)"; return RNDE_ERR_BAD_ARG; }
     if (steps_host && (n_steps < 1 || n_steps > h->cfg.max_attempts)) { h->err = "replay: n_steps must be 1..max_attempts"; return RNDE_ERR_BAD_ARG; }
@@ -222,7 +265,7 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
     if (steps_host) FCHK(h, hipMemcpyAsync(h->replay, steps_host, (size_t)2 * n_steps * 4, hipMemcpyHostToDevice, s));
     FfSolveParams Q{};
     StepParams& P = Q.F;
-    P.x = x_dev; P.D = h->R; P.B = B; P.Bn = B; P.Bpad = h->Bp; P.nwg = 1;
+    P.x = x_dev; P.D = kin ? h->G.D + 3 : h->R; P.B = B; P.Bn = B; P.Bpad = h->Bp; P.nwg = 1;
     P.ctl = h->ctl; P.ctl_final = h->ctl + 2; P.meta = h->meta; P.initrec = h->initrec; P.initpart = h->norm;
     P.reltol = h->cfg.reltol; P.abstol = h->cfg.abstol;
     P.t0 = dir > 0 ? t0 : 0.f; P.t1 = dir > 0 ? t1 : t1 - t0;
@@ -231,7 +274,7 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
     P.beta1 = kBeta1; P.beta2 = kBeta2; P.rk_order = 5.f;
     Q.G = h->G; Q.p = p_dev; Q.x = x_dev; Q.e = dir > 0 ? e_dev : nullptr; Q.ws = h->ws;
     Q.tape = taped ? h->tape : nullptr; Q.logpx = dir > 0 ? logpx_dev : nullptr; Q.x_out = x_out_dev; Q.norm = h->norm;
-    Q.dir = dir; Q.T = h->T; Q.Bp = h->Bp; Q.tbase = t1;
+    Q.dir = dir; Q.T = h->T; Q.Bp = h->Bp; Q.tbase = t1; Q.reg = reg_out_dev;
     const int nt = (B + 15) / 16;
     FtSolveParams TQ{};
     if (h->engine == 1) {      // the tiled engine: every tile resident, one meeting per attempt (one XCD up to 32 tiles, agent scope above)
@@ -240,10 +283,15 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
         TQ.norm = h->norm; TQ.initrec_t = h->initrec_t; TQ.ctl_t = h->ctl_t; TQ.qt = dir < 0 ? h->qt : nullptr;
         TQ.meet = MwMeet{h->xch, h->abort_word, h->epoch, nt, nt > 32 ? 1 : 0};
         TQ.xcc = h->xcc; TQ.xcd_slot = h->xcd_slot; TQ.dir = dir; TQ.Bp = h->Bp; TQ.ntiles = nt; TQ.tbase = t1;
+        TQ.reg = reg_out_dev;
     }
     FCHK(h, hipEventRecord(h->ev[0], s));
-    if (h->engine == 1) hipLaunchKernelGGL(rnde_ffjordt_solve_kernel, dim3(TQ.meet.global ? nt : 8 * nt), dim3(kFtThreads), h->lds_bytes, s, TQ);
-    else hipLaunchKernelGGL(rnde_ffjord_solve_kernel, dim3(1), dim3(h->T), h->lds_bytes, s, Q);
+    if (h->engine == 1) {
+        const dim3 grid(TQ.meet.global ? nt : 8 * nt);
+        if (kin) hipLaunchKernelGGL(rnde_ffjordt_solve_kernel<true>, grid, dim3(kFtThreads), h->lds_bytes, s, TQ);
+        else hipLaunchKernelGGL(rnde_ffjordt_solve_kernel<false>, grid, dim3(kFtThreads), h->lds_bytes, s, TQ);
+    } else if (kin) hipLaunchKernelGGL(rnde_ffjord_solve_kernel<true>, dim3(1), dim3(h->T), h->lds_bytes, s, Q);
+    else hipLaunchKernelGGL(rnde_ffjord_solve_kernel<false>, dim3(1), dim3(h->T), h->lds_bytes, s, Q);
     FCHK(h, hipGetLastError());
     FCHK(h, hipEventRecord(h->ev[1], s));
     StepState fin;
@@ -280,17 +328,22 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
     if (taped) {
         rnde_ffjord::Tape& T = h->tp;
         T.meta = h->h_meta; T.n_att = h->n_att; T.n_acc = h->n_acc; T.B = B;
-        T.reltol = P.reltol; T.abstol = P.abstol; T.e = e_dev; T.p = p_dev; T.valid = true;
+        T.reltol = P.reltol; T.abstol = P.abstol; T.e = e_dev; T.p = p_dev; T.kin = kin; T.valid = true;
     }
     return RNDE_OK;
 }
 
 static rnde_status ff_forward(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0, float t1, uint64_t seed,
                               const float* steps_host, int32_t n_steps, float* logpx_dev, float* z_out_dev, int64_t* nfe_out, float* saveval_host,
-                              int32_t* n_saveval_out, int32_t keep_tape, void* stream) {
+                              int32_t* n_saveval_out, int32_t keep_tape, void* stream, bool kin = false, float* reg_out_dev = nullptr) {
     if (!h) return RNDE_ERR_BAD_ARG;
     if (!logpx_dev) { h->err = "logpx_dev is required"; return RNDE_ERR_BAD_ARG; }
-    rnde_status st = ff_solve(h, +1, x_dev, p_dev, e_dev, B, t0, t1, seed, steps_host, n_steps, logpx_dev, z_out_dev, keep_tape, (hipStream_t)stream);
+    if (kin) {
+        if (!reg_out_dev) { h->err = "reg_out_dev (2 x B: the kinetic energy row, then the Jacobian norm row) is required"; return RNDE_ERR_BAD_ARG; }
+        if (rnde_status kst = ff_kinetic_ready(h)) return kst;
+    }
+    rnde_status st = ff_solve(h, +1, x_dev, p_dev, e_dev, B, t0, t1, seed, steps_host, n_steps, logpx_dev, z_out_dev, keep_tape, (hipStream_t)stream,
+                              kin ? reg_out_dev : nullptr);
     if (st != RNDE_OK) return st;
     if (nfe_out) *nfe_out = 3 + 6 * (int64_t)h->n_att;      // 2 (initial dt) + 1 (fsalfirst) + 6 per attempt, as rnde_node_forward
     int nsv = 0;
@@ -316,6 +369,35 @@ extern "C" rnde_status rnde_ffjord_forward_replay(rnde_ffjord* h, const float* x
     return ff_forward(h, x_dev, p_dev, e_dev, B, t0, t1, seed, steps_host, n_steps, logpx_dev, z_out_dev, nfe_out, saveval_host, n_saveval_out, keep_tape, stream);
 }
 
+extern "C" rnde_status rnde_ffjord_forward_kinetic(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0,
+                                                   float t1, uint64_t seed, float* logpx_dev, float* reg_out_dev, float* z_out_dev, int64_t* nfe_out,
+                                                   int32_t keep_tape, void* stream) {
+    return ff_forward(h, x_dev, p_dev, e_dev, B, t0, t1, seed, nullptr, 0, logpx_dev, z_out_dev, nfe_out, nullptr, nullptr, keep_tape, stream, true,
+                      reg_out_dev);
+}
+
+extern "C" rnde_status rnde_ffjord_forward_kinetic_replay(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B,
+                                                          float t0, float t1, uint64_t seed, const float* steps_host, int32_t n_steps,
+                                                          float* logpx_dev, float* reg_out_dev, float* z_out_dev, int64_t* nfe_out,
+                                                          int32_t keep_tape, void* stream) {
+    if (!steps_host) { if (h) h->err = "replay: steps_host is required"; return RNDE_ERR_BAD_ARG; }
+    return ff_forward(h, x_dev, p_dev, e_dev, B, t0, t1, seed, steps_host, n_steps, logpx_dev, z_out_dev, nfe_out, nullptr, nullptr, keep_tape, stream,
+                      true, reg_out_dev);
+}
+
+extern "C" rnde_status rnde_ffjord_step_log(rnde_ffjord* h, float* log_host, int32_t capacity, int32_t* n_attempts_out) {
+    if (!h || !n_attempts_out) return RNDE_ERR_BAD_ARG;
+    *n_attempts_out = h->n_att;
+    if (log_host) {
+        if (capacity < h->n_att) { h->err = "step_log: capacity below the attempt count"; return RNDE_ERR_BAD_ARG; }
+        for (int i = 0; i < h->n_att; ++i) {
+            const StepMeta& m = h->h_meta[i];
+            log_host[4 * i] = m.t; log_host[4 * i + 1] = m.dt; log_host[4 * i + 2] = m.eest; log_host[4 * i + 3] = (m.flags & F_ACCEPT) ? 1.f : 0.f;
+        }
+    }
+    return RNDE_OK;
+}
+
 extern "C" rnde_status rnde_ffjord_steps(rnde_ffjord* h, float* steps_host, int32_t capacity, int32_t* n_attempts_out) {
     if (!h || !n_attempts_out) return RNDE_ERR_BAD_ARG;
     *n_attempts_out = h->n_att;
@@ -326,8 +408,9 @@ extern "C" rnde_status rnde_ffjord_steps(rnde_ffjord* h, float* steps_host, int3
     return RNDE_OK;
 }
 
-extern "C" rnde_status rnde_ffjord_backward(rnde_ffjord* h, const float* logpx_bar_dev, const float* saveval_bar_host, float* p_bar_dev,
-                                            float* x_bar_dev, void* stream) {
+// The reverse sweep of the taped forward; a kinetic tape runs the KIN = true kernels with reg_bar_dev (NULL: zeros).
+static rnde_status ff_backward(rnde_ffjord* h, const float* logpx_bar_dev, const float* saveval_bar_host, const float* reg_bar_dev, float* p_bar_dev,
+                               float* x_bar_dev, void* stream) {
     if (!h) return RNDE_ERR_BAD_ARG;
     const rnde_ffjord::Tape& T = h->tp;
     if (!T.valid) { h->err = "backward without a taped forward"; return RNDE_ERR_NO_TAPE; }
@@ -349,17 +432,21 @@ extern "C" rnde_status rnde_ffjord_backward(rnde_ffjord* h, const float* logpx_b
     FfRevParams Q{};
     Q.G = h->G; Q.p = T.p; Q.e = T.e; Q.tape = h->tape; Q.rec = h->rec; Q.logpx_bar = logpx_bar_dev;
     Q.ws = h->rws; Q.pacc = h->pacc; Q.x_bar = x_bar_dev; Q.n_acc = T.n_acc; Q.B = T.B; Q.Bp = h->Bp; Q.reltol = T.reltol; Q.abstol = T.abstol;
+    Q.reg_bar = reg_bar_dev;
     FCHK(h, hipEventRecord(h->ev[2], s));
     if (h->engine == 1) {
         FtRevParams TQ{};
         TQ.G = h->TG; TQ.p = T.p; TQ.e = T.e; TQ.tape = h->tape; TQ.rec = h->rec; TQ.logpx_bar = logpx_bar_dev; TQ.ws = h->rws; TQ.pacc = h->pacc;
         TQ.x_bar = x_bar_dev; TQ.n_acc = T.n_acc; TQ.B = T.B; TQ.Bp = h->Bp; TQ.reltol = T.reltol; TQ.abstol = T.abstol;
+        TQ.reg_bar = reg_bar_dev;
         const int nt = (T.B + 15) / 16;
-        hipLaunchKernelGGL(rnde_ffjordt_reverse_kernel, dim3(nt), dim3(kFtThreads), h->lds_bytes, s, TQ);
+        if (T.kin) hipLaunchKernelGGL(rnde_ffjordt_reverse_kernel<true>, dim3(nt), dim3(kFtThreads), h->lds_bytes, s, TQ);
+        else hipLaunchKernelGGL(rnde_ffjordt_reverse_kernel<false>, dim3(nt), dim3(kFtThreads), h->lds_bytes, s, TQ);
         FCHK(h, hipGetLastError());
         hipLaunchKernelGGL(rnde_ffjordt_reduce_kernel, dim3((h->G.P + 255) / 256), dim3(256), 0, s, (const float*)h->pacc, h->G.P, nt, p_bar_dev);
     } else {
-        hipLaunchKernelGGL(rnde_ffjord_reverse_kernel, dim3((T.B + 255) / 256), dim3(256), 0, s, Q);
+        if (T.kin) hipLaunchKernelGGL(rnde_ffjord_reverse_kernel<true>, dim3((T.B + 255) / 256), dim3(256), 0, s, Q);
+        else hipLaunchKernelGGL(rnde_ffjord_reverse_kernel<false>, dim3((T.B + 255) / 256), dim3(256), 0, s, Q);
         FCHK(h, hipGetLastError());
         hipLaunchKernelGGL(rnde_ffjord_reduce_kernel, dim3((h->G.P + 255) / 256), dim3(256), 0, s, (const float*)h->pacc, h->G.P, T.B, h->Bp, p_bar_dev);
     }
@@ -368,6 +455,18 @@ extern "C" rnde_status rnde_ffjord_backward(rnde_ffjord* h, const float* logpx_b
     FCHK(h, hipEventSynchronize(h->ev[3]));
     (void)hipEventElapsedTime(&h->rev_ms, h->ev[2], h->ev[3]);
     return RNDE_OK;
+}
+
+extern "C" rnde_status rnde_ffjord_backward(rnde_ffjord* h, const float* logpx_bar_dev, const float* saveval_bar_host, float* p_bar_dev,
+                                            float* x_bar_dev, void* stream) {
+    return ff_backward(h, logpx_bar_dev, saveval_bar_host, nullptr, p_bar_dev, x_bar_dev, stream);
+}
+
+extern "C" rnde_status rnde_ffjord_backward_kinetic(rnde_ffjord* h, const float* logpx_bar_dev, const float* reg_bar_dev, float* p_bar_dev,
+                                                    float* x_bar_dev, void* stream) {
+    if (!h) return RNDE_ERR_BAD_ARG;
+    if (h->tp.valid && !h->tp.kin) { h->err = "backward_kinetic: the taped forward has no kinetic energy rows (use rnde_ffjord_backward)"; return RNDE_ERR_BAD_ARG; }
+    return ff_backward(h, logpx_bar_dev, nullptr, reg_bar_dev, p_bar_dev, x_bar_dev, stream);
 }
 
 extern "C" rnde_status rnde_ffjord_sample(rnde_ffjord* h, const float* p_dev, const float* z_dev, int32_t n, float t0, float t1, uint64_t seed,
@@ -388,10 +487,24 @@ extern "C" rnde_status rnde_ffjord_debug_feval(rnde_ffjord* h, const float* x_de
                                                int32_t exact, float* out_dev, void* stream) {
     if (!h || !x_dev || !p_dev || !out_dev || B < 1 || B > h->cfg.max_batch || (!exact && !e_dev)) { if (h) h->err = "bad argument"; return RNDE_ERR_BAD_ARG; }
     if (h->engine == 1)
-        hipLaunchKernelGGL(rnde_ffjordt_feval_kernel, dim3((B + 15) / 16), dim3(kFtThreads), h->lds_bytes, (hipStream_t)stream, h->TG, p_dev, x_dev, e_dev,
+        hipLaunchKernelGGL(rnde_ffjordt_feval_kernel<false>, dim3((B + 15) / 16), dim3(kFtThreads), h->lds_bytes, (hipStream_t)stream, h->TG, p_dev, x_dev, e_dev,
                            t, B, exact, h->rws, h->qt, out_dev);
     else
-        hipLaunchKernelGGL(rnde_ffjord_feval_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->G, p_dev, x_dev, e_dev, t, B, exact,
+        hipLaunchKernelGGL(rnde_ffjord_feval_kernel<false>, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->G, p_dev, x_dev, e_dev, t, B, exact,
+                           h->rws, out_dev);
+    FCHK(h, hipGetLastError());
+    return RNDE_OK;
+}
+
+extern "C" rnde_status rnde_ffjord_debug_feval_kinetic(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t,
+                                                       float* out_dev, void* stream) {
+    if (!h || !x_dev || !p_dev || !e_dev || !out_dev || B < 1 || B > h->cfg.max_batch) { if (h) h->err = "bad argument"; return RNDE_ERR_BAD_ARG; }
+    if (rnde_status kst = ff_kinetic_ready(h)) return kst;
+    if (h->engine == 1)
+        hipLaunchKernelGGL(rnde_ffjordt_feval_kernel<true>, dim3((B + 15) / 16), dim3(kFtThreads), h->lds_bytes, (hipStream_t)stream, h->TG, p_dev, x_dev,
+                           e_dev, t, B, 0, h->rws, h->qt, out_dev);
+    else
+        hipLaunchKernelGGL(rnde_ffjord_feval_kernel<true>, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->G, p_dev, x_dev, e_dev, t, B, 0,
                            h->rws, out_dev);
     FCHK(h, hipGetLastError());
     return RNDE_OK;

@@ -18,6 +18,10 @@
 //     tr J = a2' (W2 .* M') a1,   M(t) = W1 diag(g3(t)) W3   (H x H)
 // Each tile forms QT = (W2 .* M')' once per evaluation on the matrix cores into a tile-private global buffer; each column then costs one
 // H x H product.
+//
+// Kinetic variant (template parameter KIN; rnde_ffjord.h): R = D + 3 rows, the two regulariser rates sum f^2 and sum eJ^2 formed where the
+// trace is formed -- per-lane partials in the epilogues of the layer-3 product and of the last transposed product, then the same per-column
+// reduction.  No LDS beyond the plain kernels' (135 KB at (43, 100)), so the limits are the plain ones: in_dims <= 64, hidden <= 112.
 #pragma once
 #include "rnde_chainmw.h"     // MwMeet, mw_exchange3, kMwMeetMax, mfma16
 #include "rnde_ffjord.h"
@@ -151,7 +155,9 @@ __device__ __forceinline__ float ft_colsum(float v, float* red, int tid) {
 // One evaluation of the augmented right-hand side for the 16 columns of a tile.
 //   pre: L.X holds the data rows of the input ([DP][16], padded rows zero), L.E the probe (Hutchinson; zero columns where not valid).
 //   out: kout[r * ks + c] = fsign * f_r (r < D), kout[D * ks + c] = tsign * tr.  exact: the closed-form trace (QT: this tile's H x H buffer).
+//   KIN (Hutchinson only): kout[(D + 1) * ks + c] = sum f^2, kout[(D + 2) * ks + c] = sum eJ^2.
 //   Every thread of the workgroup calls it; it ends behind a barrier.
+template <bool KIN = false>
 __device__ __forceinline__ void ft_eval(const FtGeo& G, const FtLds& L, float t, float* kout, int ks, int exact, float fsign, float tsign, float* QT, int tid) {
     const int lane = tid & 63, wave = tid >> 6, c = lane & 15, D = G.D, H = G.H, HP = G.HP;
     const float *W1 = L.W + G.woff[0], *W2 = L.W + G.woff[1], *W3 = L.W + G.woff[2];
@@ -201,12 +207,17 @@ __device__ __forceinline__ void ft_eval(const FtGeo& G, const FtLds& L, float t,
     });
     __syncthreads();
     // layer 3 -> f;  Hutchinson: X <- g3 .* e;  exact: tr = a2 . (Q a1)
+    float pke = 0.f, pjn = 0.f;
     ft_fwd(W3, G.ld[2], G.inp[2], G.outp[2], L.S2, wave, lane, [&](int r0, f32x4 v) {
         const float *b = ft_vec(G, L.W, 2, 0), *bw = ft_vec(G, L.W, 2, 1), *bb = ft_vec(G, L.W, 2, 2);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int o = r0 + j;
-            if (o < D) kout[(size_t)o * ks + c] = fsign * fmaf(v[j] + b[o], g3[o], fmaf(bw[o], t, bb[o]));
+            if (o < D) {
+                const float f = fmaf(v[j] + b[o], g3[o], fmaf(bw[o], t, bb[o]));
+                kout[(size_t)o * ks + c] = fsign * f;
+                if constexpr (KIN) pke = fmaf(f, f, pke);
+            }
         }
     });
     float part = 0.f;
@@ -233,11 +244,19 @@ __device__ __forceinline__ void ft_eval(const FtGeo& G, const FtLds& L, float t,
         // tr = e . W1' v1
         ft_tr(W1, G.ld[0], G.inp[0], G.outp[0], L.S2, wave, lane, [&](int r0, f32x4 v) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) part = fmaf(L.E[(r0 + j) * 16 + c], v[j], part);
+            for (int j = 0; j < 4; ++j) {
+                part = fmaf(L.E[(r0 + j) * 16 + c], v[j], part);
+                if constexpr (KIN) pjn = fmaf(v[j], v[j], pjn);      // (rows >= D: W1's padded rows are zero)
+            }
         });
     }
     const float tr = ft_colsum(part, L.red, tid);
     if (tid < 16) kout[(size_t)D * ks + tid] = tsign * tr;
+    if constexpr (KIN) {
+        const float ke = ft_colsum(pke, L.red, tid);
+        const float jn = ft_colsum(pjn, L.red, tid);
+        if (tid < 16) { kout[(size_t)(D + 1) * ks + tid] = ke; kout[(size_t)(D + 2) * ks + tid] = jn; }
+    }
     __syncthreads();
 }
 
@@ -260,6 +279,7 @@ struct FtSolveParams {
     int xcd_slot;
     int dir, Bp, ntiles;
     float tbase;                     // dir = -1: t1
+    float* reg;                      // kinetic solves: 2 x B (lambda1 row, then lambda2 row); NULL otherwise
 };
 
 // Publish this tile's three partials (wave 0), collect everybody's sums in tile order; false when the meeting timed out (every thread).
@@ -284,13 +304,14 @@ __device__ __forceinline__ bool ft_meet(const FtSolveParams& Q, float* red, int 
 }
 
 // The whole adaptive solve in one launch: forward (dir = +1, Hutchinson), replay along P.replay, sampling (dir = -1, exact trace, tau = t1 - t).
+template <bool KIN>
 __global__ __launch_bounds__(kFtThreads) void rnde_ffjordt_solve_kernel(const FtSolveParams Q) {
     extern __shared__ float ft_smem[];
     if (!Q.meet.global && (int)(blockIdx.x & 7) != Q.xcd_slot) return;
     const int tile = Q.meet.global ? (int)blockIdx.x : (int)(blockIdx.x >> 3);
     const int tid = threadIdx.x, lane = tid & 63;
     const FtGeo& G = Q.G;
-    const int D = G.D, R = D + 1, Bp = Q.Bp, B = Q.F.B, col0 = tile * 16;
+    const int D = G.D, R = D + (KIN ? 3 : 1), Bp = Q.Bp, B = Q.F.B, col0 = tile * 16;
     if (!Q.meet.global && tid == 0) Q.xcc[tile] = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 15;
     StepParams P = Q.F;
     P.initpart = Q.norm + 8 * tile;
@@ -310,7 +331,7 @@ __global__ __launch_bounds__(kFtThreads) void rnde_ffjordt_solve_kernel(const Ft
     const int exact = Q.dir < 0 ? 1 : 0;
     const float fsign = Q.dir > 0 ? 1.f : -1.f, tsign = Q.dir > 0 ? -1.f : 1.f;
     float* qt = Q.qt ? Q.qt + (size_t)tile * G.HP * G.HP : nullptr;
-    auto eval = [&](float time, float* kout) { ft_eval(G, L, Q.dir > 0 ? time : Q.tbase - time, kout, Bp, exact, fsign, tsign, qt, tid); };
+    auto eval = [&](float time, float* kout) { ft_eval<KIN>(G, L, Q.dir > 0 ? time : Q.tbase - time, kout, Bp, exact, fsign, tsign, qt, tid); };
     const float rt = P.reltol, at = P.abstol;
     const double N = (double)R * (double)B;
     const int nel = R * 16;
@@ -422,15 +443,21 @@ __global__ __launch_bounds__(kFtThreads) void rnde_ffjordt_solve_kernel(const Ft
         }
         Q.logpx[col0 + tid] = lp - U[(size_t)D * Bp + tid];
     }
+    if constexpr (KIN)
+        if (tid < 16 && col0 + tid < B) {
+            Q.reg[col0 + tid] = U[(size_t)(D + 1) * Bp + tid];
+            Q.reg[(size_t)B + col0 + tid] = U[(size_t)(D + 2) * Bp + tid];
+        }
 }
 
 // One evaluation of the augmented right-hand side per column (the parity instrument): out (D + 1) x B caller layout, the trace row -e . eJ
-// (exact: -tr J).  One workgroup per tile; ws: [ntiles][R][16].
+// (exact: -tr J).  One workgroup per tile; ws: [ntiles][R][16].  KIN: (D + 3) x B, Hutchinson only.
+template <bool KIN>
 __global__ __launch_bounds__(kFtThreads) void rnde_ffjordt_feval_kernel(const FtGeo G, const float* __restrict__ p, const float* __restrict__ x,
                                                                        const float* __restrict__ e, float t, int B, int exact, float* __restrict__ ws,
                                                                        float* __restrict__ qt, float* __restrict__ out) {
     extern __shared__ float ft_smem[];
-    const int tile = blockIdx.x, tid = threadIdx.x, D = G.D, R = D + 1, col0 = tile * 16;
+    const int tile = blockIdx.x, tid = threadIdx.x, D = G.D, R = D + (KIN ? 3 : 1), col0 = tile * 16;
     const FtLds L = ft_lds(G, ft_smem);
     ft_load_params(G, p, L.W, tid);
     for (int idx = tid; idx < G.DP * 16; idx += kFtThreads) {
@@ -441,7 +468,7 @@ __global__ __launch_bounds__(kFtThreads) void rnde_ffjordt_feval_kernel(const Ft
     }
     __syncthreads();                                          // (ft_eval's gates read gate_W from LDS)
     float* k = ws + (size_t)tile * R * 16;
-    ft_eval(G, L, t, k, 16, exact, 1.f, -1.f, exact ? qt + (size_t)tile * G.HP * G.HP : nullptr, tid);
+    ft_eval<KIN>(G, L, t, k, 16, exact, 1.f, -1.f, exact ? qt + (size_t)tile * G.HP * G.HP : nullptr, tid);
     for (int idx = tid; idx < R * 16; idx += kFtThreads) {
         const int r = idx >> 4, col = col0 + (idx & 15);
         if (col < B) out[(size_t)col * R + r] = k[idx];

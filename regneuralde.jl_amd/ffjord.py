@@ -6,13 +6,17 @@ calls replaced by librnde.so (rnde_ffjord_*: one launch per adaptive solve, one 
     logpx, l1, l2, nfe, sv = ffjord(x)          # x: (B, D) cuda tensor == Julia D x B; sv.saveval: tensor ({true}) or None
     xs = sample(ffjord, 2, nsamples=1024)
 
-Served: the two call methods the FFJORD experiments use -- TrackedFFJORD{false} with regularize = false and TrackedFFJORD{true}
-(EEst * dt saved per accepted step) -- and sample(), on one of two engines:
+    logpx, ke, jn, nfe, _ = ffjord(x, regularize=True)   # {false} layers: the kinetic energy and Jacobian norm rows (RNODE), differentiable
+
+Served: the call methods of ffjord.jl -- TrackedFFJORD{false} with regularize = false or true (the state [z; l; lambda1; lambda2],
+d lambda1 / dt = sum f^2, d lambda2 / dt = sum eJ^2, under the same controller) and TrackedFFJORD{true} (EEst * dt saved per accepted
+step) -- and sample(), on one of two engines:
     engine="workgroup" (default): the whole batch in one workgroup, widths in_dims + 1 <= 64 and hidden <= 64;
     engine="tiled": one workgroup per 16 columns, layer products on the matrix cores, in_dims <= 64 and hidden <= 112 (the tabular
                     experiment's MLPDynamics(43, 100)), max_batch <= 4096.
-Refused with a message that names the limit: any other dynamics (the default forw_n_back through Tracker.forward), widths above the
-engine's limit, and the {false} method's regularize = true rows.
+The regularize = true rows add two state rows: engine="workgroup" serves them for in_dims + 3 <= 64, engine="tiled" at its own limits.
+Refused with a message that names the limit: any other dynamics (the default forw_n_back through Tracker.forward) and widths above the
+engine's limit.
 """
 import ctypes as C
 import math
@@ -87,6 +91,16 @@ def check_served(model, regularize_kinetic=False, engine="workgroup"):
                          f"{TILED_MAX_HIDDEN}; got in_dims = {model.in_dims}, hidden = {model.hidden})")
     if regularize_kinetic:
         raise ValueError("TrackedFFJORD{false} with regularize = true (kinetic energy and Jacobian norm rows) is not served")
+
+
+def check_kinetic_served(model, engine="workgroup"):
+    """ValueError naming the limit for the {false} method's regularize = true rows (kinetic energy, Jacobian norm) on `engine`: the limits
+    of check_served with two more state rows."""
+    check_served(model, engine=engine)
+    if engine == "workgroup" and model.in_dims + 3 > MAX_WIDTH:
+        raise ValueError(f"TrackedFFJORD{{false}} with regularize = true (kinetic energy and Jacobian norm rows): the chain engine's limit of "
+                         f"{MAX_WIDTH} rows holds in_dims + 3 <= 64 and hidden <= 64 (got in_dims = {model.in_dims}, hidden = {model.hidden}; "
+                         f"engine=\"tiled\" serves in_dims <= {TILED_MAX_IN} and hidden <= {TILED_MAX_HIDDEN})")
 
 
 class SavedValues:
@@ -191,9 +205,64 @@ class _Solve(torch.autograd.Function):
         return xb, pb, None, None, None, None, None, None
 
 
+class _SolveKinetic(torch.autograd.Function):
+    """The {false} method called with regularize = true: (logpx, lambda1, lambda2) from one solve over D + 3 rows, one reverse sweep for all
+    three cotangents.  Shares the layer's tape pool with _Solve."""
+
+    @staticmethod
+    def forward(ctx, x, p, e, layer, t0, t1, steps, keep):
+        L = _lib.lib()
+        hd = layer._taped_handle() if keep else layer._handle()
+        h = hd.h
+        B = x.shape[0]
+        logpx = torch.empty(B, device=x.device, dtype=torch.float32)
+        reg = torch.empty(2, B, device=x.device, dtype=torch.float32)
+        nfe = C.c_int64()
+        if keep:
+            hd.busy, hd.gen = True, hd.gen + 1
+        if steps is None:
+            st = L.rnde_ffjord_forward_kinetic(h, x.data_ptr(), p.data_ptr(), e.data_ptr(), B, t0, t1, 0, logpx.data_ptr(), reg.data_ptr(), None,
+                                               C.byref(nfe), keep, _stream(x.device))
+        else:
+            arr = (C.c_float * len(steps))(*steps)
+            st = L.rnde_ffjord_forward_kinetic_replay(h, x.data_ptr(), p.data_ptr(), e.data_ptr(), B, t0, t1, 0, arr, len(steps) // 2,
+                                                      logpx.data_ptr(), reg.data_ptr(), None, C.byref(nfe), keep, _stream(x.device))
+        layer._last = hd
+        if st != _lib.OK:
+            hd.busy = False
+            _lib.check_ffjord(h, st)
+        ctx.layer = layer
+        ctx.token = _TapeToken(hd) if keep else None
+        ctx.save_for_backward(x, p, e)
+        layer.last_nfe = int(nfe.value)
+        return logpx, reg[0].clone(), reg[1].clone()
+
+    @staticmethod
+    def backward(ctx, g_logpx, g_l1, g_l2):
+        x, p, e = ctx.saved_tensors
+        tok = ctx.token
+        if tok is None:
+            raise RuntimeError("TrackedFFJORD: this forward was not taped (it ran with grad disabled or with no input requiring grad)")
+        if tok.done or tok.hd.gen != tok.gen:
+            raise RuntimeError("TrackedFFJORD: the tape of this forward has been released (a second backward through the same graph)")
+        L, h, B = _lib.lib(), tok.hd.h, x.shape[0]
+        zeros = lambda: torch.zeros(B, device=x.device)                    # (an unused output's None gradient counts as zeros)
+        g_logpx = (zeros() if g_logpx is None else g_logpx).contiguous().float()
+        gr = torch.stack([zeros() if g is None else g.float() for g in (g_l1, g_l2)]).contiguous()
+        pb = torch.empty_like(p)
+        xb = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        st = L.rnde_ffjord_backward_kinetic(h, g_logpx.data_ptr(), gr.data_ptr(), pb.data_ptr(), xb.data_ptr() if xb is not None else None,
+                                            _stream(x.device))
+        ctx.layer._last_bwd = tok.hd
+        tok.finish()
+        _lib.check_ffjord(h, st)
+        return xb, pb, None, None, None, None, None, None
+
+
 class TrackedFFJORD:
     """TrackedFFJORD(model, tspan, time_dep, regularize, solver; reltol, abstol, ...) (ffjord.jl:1-51).  regularize selects the call
-    method: False -> TrackedFFJORD{false} (returns logpx, 0, 0, nfe, None), True -> TrackedFFJORD{true} (returns logpx, 0, 0, nfe, sv with
+    method: False -> TrackedFFJORD{false} (returns logpx, 0, 0, nfe, None; called with regularize=True: logpx, lambda1, lambda2, nfe, None with
+    the kinetic energy and the Jacobian norm rows, differentiable), True -> TrackedFFJORD{true} (returns logpx, 0, 0, nfe, sv with
     sv.saveval = EEst * dt per accepted step, differentiable).  engine: "workgroup" (default) or "tiled" (see the module docstring)."""
 
     def __init__(self, model, tspan, time_dep, regularize, solver="Tsit5", *, reltol=1.4e-8, abstol=1.4e-8, max_batch=1024, max_attempts=4096,
@@ -246,8 +315,9 @@ class TrackedFFJORD:
         return out
 
     def __call__(self, x, p=None, e=None, regularize=False, steps=None):
-        if regularize and not self.regularize:
-            check_served(self.model, regularize_kinetic=True, engine=self.engine)
+        kinetic = bool(regularize) and not self.regularize      # ({true} never passes the keyword on: ffjord.jl:119)
+        if kinetic:
+            check_kinetic_served(self.model, self.engine)
         p = self.p if p is None else p
         if not (x.is_cuda and p.is_cuda):
             raise RuntimeError("TrackedFFJORD runs on the device only: x and p must be cuda tensors")
@@ -264,6 +334,9 @@ class TrackedFFJORD:
             raise ValueError(f"p must hold {self.model.param_count()} parameters; got {p.numel()}")
         # tape only when a gradient can be asked for: an inference call must not occupy (or replace) a tape
         keep = torch.is_grad_enabled() and (x.requires_grad or p.requires_grad)
+        if kinetic:
+            logpx, l1, l2 = _SolveKinetic.apply(x, p, e, self, self.tspan[0], self.tspan[1], steps, keep)
+            return logpx, l1, l2, self.last_nfe, None
         logpx, saveval = _Solve.apply(x, p, e, self, self.tspan[0], self.tspan[1], steps, keep)
         zero = torch.zeros(x.shape[0], device=x.device)
         return logpx, zero, zero, self.last_nfe, (SavedValues(saveval) if self.regularize else None)
@@ -276,6 +349,14 @@ class TrackedFFJORD:
         _lib.check_ffjord(h, _lib.lib().rnde_ffjord_steps(h, arr, n.value, C.byref(n)))
         return list(arr[:2 * n.value])
 
+    def step_log(self):
+        """(n, 4) array of (t, dt, EEst, accepted) per attempt of the last solve (rnde_ffjord_step_log)."""
+        h, n = (self._last or self._handle()).h, C.c_int32()
+        _lib.check_ffjord(h, _lib.lib().rnde_ffjord_step_log(h, None, 0, C.byref(n)))
+        arr = (C.c_float * max(4 * n.value, 1))()
+        _lib.check_ffjord(h, _lib.lib().rnde_ffjord_step_log(h, arr, n.value, C.byref(n)))
+        return np.array(arr[:4 * n.value], dtype=np.float32).reshape(-1, 4)
+
     def timing(self):
         """(solve ms, attempts, accepted) of the last solve and the reverse ms of the last backward (HIP events): (solve, reverse, n, m)."""
         a, b, n, m = C.c_float(), C.c_float(), C.c_int32(), C.c_int32()
@@ -285,9 +366,19 @@ class TrackedFFJORD:
             _lib.check_ffjord(self._last_bwd.h, _lib.lib().rnde_ffjord_timing(self._last_bwd.h, None, C.byref(b), None, None))
         return a.value, (b.value if self._last_bwd is not None else -1.0), n.value, m.value
 
-    def feval(self, x, t, e=None, p=None):
-        """[f(x, t); -e . eJ] as (B, D + 1) (e = None: the exact trace)."""
+    def feval(self, x, t, e=None, p=None, regularize=False):
+        """[f(x, t); -e . eJ] as (B, D + 1) (e = None: the exact trace); regularize=True: [f; -e . eJ; sum f^2; sum eJ^2] as (B, D + 3)."""
         p = self.p if p is None else p
+        if regularize:
+            check_kinetic_served(self.model, self.engine)
+            if e is None or x.dim() != 2 or x.shape[1] != self.model.in_dims or tuple(e.shape) != tuple(x.shape):
+                raise ValueError(f"x and e must be (B, {self.model.in_dims}) (the kinetic rows use the Hutchinson probe)")
+            h = self._handle().h
+            out = torch.empty(x.shape[0], self.model.in_dims + 3, device=x.device)
+            _lib.check_ffjord(h, _lib.lib().rnde_ffjord_debug_feval_kinetic(h, x.contiguous().data_ptr(), p.contiguous().data_ptr(),
+                                                                            e.contiguous().data_ptr(), x.shape[0], float(t), out.data_ptr(),
+                                                                            _stream(x.device)))
+            return out
         if x.dim() != 2 or x.shape[1] != self.model.in_dims or (e is not None and tuple(e.shape) != tuple(x.shape)):
             raise ValueError(f"x and e must be (B, {self.model.in_dims})")
         h = self._handle().h

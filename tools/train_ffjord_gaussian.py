@@ -9,7 +9,12 @@ The restatement is tests/ffjord_ref.py (the fp64 reference of the test suite, ru
 tree, which it puts on sys.path itself.  Solve and reverse times per step come from the library's HIP events.  Output: one entry per
 --regularize setting in profiles/ffjord_gaussian.json.
 
+--kinetic LK LJ (opt-in; with --regularize 0) trains with the RNODE regulariser instead: the {false} method called with regularize = true,
+loss = -mean(logpx) + LK mean(lambda1) + LJ mean(lambda2) (kinetic energy, Jacobian norm); the entry "kinetic" goes to
+profiles/ffjord_gaussian_kinetic.json.
+
     python tools/train_ffjord_gaussian.py --regularize 1
+    python tools/train_ffjord_gaussian.py --regularize 0 --kinetic 0.01 0.01
 """
 import argparse
 import json
@@ -35,9 +40,17 @@ def main():
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--reps", type=int, default=7, help="timed runs of each side of the equal-work comparison (after 2 warm-up runs)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ffjord_gaussian.json"))
+    ap.add_argument("--kinetic", type=float, nargs=2, default=None, metavar=("LK", "LJ"),
+                    help="train with LK mean(lambda1) + LJ mean(lambda2) (kinetic energy, Jacobian norm); needs --regularize 0")
+    ap.add_argument("--out", default=None, help="default: profiles/ffjord_gaussian.json (profiles/ffjord_gaussian_kinetic.json with --kinetic)")
     a = ap.parse_args()
+    if a.kinetic and a.regularize:
+        ap.error("--kinetic needs --regularize 0 (the {true} method never passes regularize on)")
+    a.out = a.out or os.path.join(ROOT, "profiles", "ffjord_gaussian_kinetic.json" if a.kinetic else "ffjord_gaussian.json")
+    kin = bool(a.kinetic)
+    lk, lj = a.kinetic or (0.0, 0.0)
     import regneuralde_jl_amd as rn
+    from tests import ffjord_kinetic_ref as K
     from tests import ffjord_ref as R
 
     dev = torch.device("cuda", 0)
@@ -71,8 +84,10 @@ def main():
             x = torch.from_numpy(xb).to(dev)
             _sync()
             t0 = time.perf_counter()
-            logpx, _, _, nfe, sv = ff(x, p)
+            logpx, l1, l2, nfe, sv = ff(x, p, regularize=kin)
             loss = -logpx.mean() + (lam * sv.saveval.mean() if a.regularize else 0.0)
+            if kin:
+                loss = loss + lk * l1.mean() + lj * l2.mean()
             loss.backward()
             opt.step()
             _sync()
@@ -100,19 +115,23 @@ def main():
     lam_end = lam0 * np.exp(-k * (a.epochs - 1))
 
     def device_step():
-        logpx, _, _, _, sv = ff(x, p, e)
+        logpx, l1, l2, _, sv = ff(x, p, e, regularize=kin)
         loss = -logpx.mean() + (lam_end * sv.saveval.mean() if a.regularize else 0.0)
+        if kin:
+            loss = loss + lk * l1.mean() + lj * l2.mean()
         loss.backward()
         p.grad = None
 
     device_step()
     acc = [float(d) for d, f in np.array(ff.steps()).reshape(-1, 2) if f]
     pt = p.detach().clone().requires_grad_(True)
-    F = lambda u, t: R.rhs(pt, 2, 16, u, t, e)
+    F = (lambda u, t: K.rhs_kinetic(pt, 2, 16, u, t, e)) if kin else (lambda u, t: R.rhs(pt, 2, 16, u, t, e))
 
     def eager_step():
-        u, eests = R.replay(F, torch.cat([x, torch.zeros(a.batch, 1, device=dev)], 1), 0.0, acc, 1.4e-8, 1.4e-8)
+        u, eests = R.replay(F, torch.cat([x, torch.zeros(a.batch, 3 if kin else 1, device=dev)], 1), 0.0, acc, 1.4e-8, 1.4e-8)
         l2 = -R.logpx_of(u, 2).mean()
+        if kin:
+            l2 = l2 + lk * u[:, 3].mean() + lj * u[:, 4].mean()
         if a.regularize:
             l2 = l2 + lam_end * torch.stack([ee * d for ee, d in zip(eests, acc)]).sum() / (len(acc) + 1)
         l2.backward()
@@ -132,7 +151,7 @@ def main():
 
     dev_t = timed(device_step)
     eager_t = timed(eager_step)
-    res = dict(regularize=a.regularize, epochs=rows, sampling_time_s=min(samp), batch=a.batch,
+    res = dict(regularize=a.regularize, kinetic=list(a.kinetic) if kin else None, epochs=rows, sampling_time_s=min(samp), batch=a.batch,
                train_step_ms_median=float(np.median(step_ms)), solve_launch_ms_median=float(np.median(solve_ms)),
                reverse_ms_median=float(np.median(rev_ms)), attempts_median=float(np.median(att)), accepted_median=float(np.median(accd)),
                us_per_forward_attempt=float(np.median(np.array(solve_ms) / np.array(att)) * 1e3),
@@ -144,7 +163,7 @@ def main():
     if os.path.exists(a.out):
         with open(a.out) as f:
             out = json.load(f)
-    out["regularize_%d" % a.regularize] = res
+    out["kinetic" if kin else "regularize_%d" % a.regularize] = res
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)
