@@ -585,13 +585,27 @@ struct FfjordConfig
     in_dims::Int32; hidden::Int32; dynamics::Int32; time_dep::Int32; regularize::Int32; kinetic_reg::Int32
     max_batch::Int32; solver::Int32; reltol::Float32; abstol::Float32; cb_save_start::Int32; max_attempts::Int32; device::Int32
 end
-ffjord_engine(h) = Int(ccall((:rnde_ffjord_engine, LIB), Int32, (Ptr{Cvoid},), h.ptr))     # 0: one workgroup, 1: tiled
+# the default dynamics (Tracker.forward through a Dense chain, then back): rnde_ffjord_chain_config, served by rnde_ffjord_create_chain
+struct FfjordChainConfig
+    n_layers::Int32
+    dims::NTuple{9,Int32}
+    act::NTuple{8,Int32}
+    time_dep::Int32; regularize::Int32; max_batch::Int32; solver::Int32; reltol::Float32; abstol::Float32
+    cb_save_start::Int32; max_attempts::Int32; device::Int32
+end
+function ffjord_chain_config(dims::Vector{Int}, acts::Vector{Int}; time_dep, regularize, max_batch, reltol, abstol, max_attempts = 4096, device = 0)
+    d = ntuple(i -> Int32(i <= length(dims) ? dims[i] : 0), 9)
+    a = ntuple(i -> Int32(i <= length(acts) ? acts[i] : 0), 8)
+    FfjordChainConfig(length(acts), d, a, time_dep, regularize, max_batch, 0, reltol, abstol, 1, max_attempts, device)
+end
+ffjord_chain_param_count(cfg::FfjordChainConfig) = Int(ccall((:rnde_ffjord_chain_param_count, LIB), Int32, (Ref{FfjordChainConfig},), cfg))
+ffjord_engine(h) = Int(ccall((:rnde_ffjord_engine, LIB), Int32, (Ptr{Cvoid},), h.ptr))     # 0: one workgroup, 1: tiled, 2: chain dynamics
 ffjord_param_count(cfg::FfjordConfig) = Int(ccall((:rnde_ffjord_param_count, LIB), Int32, (Ref{FfjordConfig},), cfg))
 _fferr(p) = unsafe_string(ccall((:rnde_ffjord_last_error, LIB), Cstring, (Ptr{Cvoid},), p))
 
 mutable struct FfjordHandle
     ptr::Ptr{Cvoid}
-    cfg::FfjordConfig
+    cfg::Union{FfjordConfig,FfjordChainConfig}
     # engine = :workgroup (rnde_ffjord_create: in + 1 <= 64, h <= 64) or :tiled (rnde_ffjord_create_tiled: in <= 64, h <= 112), as Python's engine=
     function FfjordHandle(cfg::FfjordConfig; engine::Symbol = :workgroup)
         out = Ref{Ptr{Cvoid}}(C_NULL)
@@ -603,6 +617,15 @@ mutable struct FfjordHandle
             error("RNDE: engine must be :workgroup or :tiled; got ", engine)
         end
         st == 0 || error("rnde_ffjord_create ($engine): ", _fferr(C_NULL))
+        h = new(out[], cfg)
+        finalizer(h -> ccall((:rnde_ffjord_destroy, LIB), Cvoid, (Ptr{Cvoid},), h.ptr), h)
+        return h
+    end
+    # a Dense chain under the default dynamics: one engine (the tiled layout), every other ffjord_* call dispatches on the handle
+    function FfjordHandle(cfg::FfjordChainConfig)
+        out = Ref{Ptr{Cvoid}}(C_NULL)
+        st = ccall((:rnde_ffjord_create_chain, LIB), Cint, (Ref{FfjordChainConfig}, Ref{Ptr{Cvoid}}), cfg, out)
+        st == 0 || error("rnde_ffjord_create_chain: ", _fferr(C_NULL))
         h = new(out[], cfg)
         finalizer(h -> ccall((:rnde_ffjord_destroy, LIB), Cvoid, (Ptr{Cvoid},), h.ptr), h)
         return h

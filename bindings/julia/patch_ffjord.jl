@@ -2,12 +2,14 @@
 # (:160-167), with their `solve` replaced by librnde.so.  SOURCE ONLY (no Julia in the build image).  Usage: include RNDE.jl, then this
 # file, after `using RegNeuralDE` (see patch_neural_ode.jl).  Served: `dynamics = forw_n_back` of the ConcatSquash MLPDynamics of
 # experiments/ffjord_gaussian.jl:48-107 with in_dims + 1 <= 64 and hsize <= 64, Tsit5; with RNDE_FFJORD_ENGINE[] = :tiled, in_dims <= 64 and
-# hsize <= 112 (experiments/ffjord_tabular.jl's 43 -> 100).  Refused with an error that names the limit: the default forw_n_back
-# (Tracker.forward) and widths above the engine's limit.  The {false} method's `regularize = true` (kinetic energy and Jacobian norm rows,
+# hsize <= 112 (experiments/ffjord_tabular.jl's 43 -> 100).  Also served: the default forw_n_back (dynamics = nothing: Tracker.forward, then
+# back) when the model is a chain of Flux.Dense layers -- a TDChain with time_dep = true or a Chain with time_dep = false, up to 8 layers, no
+# width above 64, the six activations of RNDE.act_code -- through rnde_ffjord_create_chain (one engine, whatever RNDE_FFJORD_ENGINE[] says).
+# Refused with an error that names the limit: any other model under the default forw_n_back, and widths above the engine's limit.  The {false} method's `regularize = true` (kinetic energy and Jacobian norm rows,
 # ffjord.jl:53-66) runs the library's kinetic entries: in_dims + 3 <= 64 on the one-workgroup engine, the tiled engine's limits unchanged.
 # Both call methods are one Tracker node (RNDE.ffjord_solve): Tracker.gradient through the patched layer runs RNDE.ffjord_backward.
 using Tracker, Flux, AMDGPU
-using RegNeuralDE: TrackedFFJORD, _convert_tspan
+using RegNeuralDE: TrackedFFJORD, TDChain, _convert_tspan
 
 const RNDE_FFJORD_HANDLES = IdDict{Any,Dict{Int,RNDE.FfjordHandle}}()
 # which engine new handles use: :workgroup (default) or :tiled (the tabular experiment's MLPDynamics(43, 100)); set before the first call
@@ -28,9 +30,36 @@ function _ffjord_dims(n::TrackedFFJORD)
     return d, h
 end
 
+# a Dense chain under the default dynamics: (dims, acts, time dependent), or nothing for any other model
+_ffjord_is_chain(n::TrackedFFJORD) = (n.model isa TDChain || n.model isa Flux.Chain) && !hasproperty(n.model, :csl1)
+function _ffjord_chain_layout(n::TrackedFFJORD)
+    layers = collect(n.model.layers)
+    td = n.model isa TDChain
+    all(l -> l isa Flux.Dense, layers) ||
+        error("RNDE: under the default forw_n_back (Tracker.forward) the model must be a chain of Flux.Dense layers (no leading element-wise map); got ",
+              [typeof(l) for l in layers if !(l isa Flux.Dense)])
+    td == n.time_dep || error("RNDE: time_dep = ", n.time_dep, " with a ", td ? "TDChain" : "Chain", ": Tracker.forward would call the model with the wrong number of arguments")
+    dims = Int[size(layers[1].W, 2) - (td ? 1 : 0)]
+    acts = Int[]
+    for l in layers
+        push!(dims, size(l.W, 1)); push!(acts, RNDE.act_code(l.σ))
+    end
+    (length(acts) <= 8 && maximum(dims) <= 64 && dims[1] + 1 <= 64 && dims[1] == dims[end]) ||
+        error("RNDE: chain dynamics: up to 8 Dense layers, no width above the limit of 64, dims[1] + 1 <= 64 and dims[1] == dims[end]; got ", dims)
+    return dims, acts, td
+end
+
 function _ffjord_handle(n::TrackedFFJORD{R}, B::Int) where {R}
-    d, h = _ffjord_dims(n)
     hs = get!(RNDE_FFJORD_HANDLES, n, Dict{Int,RNDE.FfjordHandle}())
+    if _ffjord_is_chain(n)
+        return get!(hs, B) do
+            dims, acts, td = _ffjord_chain_layout(n)
+            kw = n.kwargs
+            RNDE.FfjordHandle(RNDE.ffjord_chain_config(dims, acts; time_dep = td ? 1 : 0, regularize = R ? 1 : 0, max_batch = B,
+                                                       reltol = Float32(get(kw, :reltol, 1.4f-8)), abstol = Float32(get(kw, :abstol, 1.4f-8))))
+        end
+    end
+    d, h = _ffjord_dims(n)
     get!(hs, B) do
         kw = n.kwargs
         RNDE.FfjordHandle(RNDE.FfjordConfig(d, h, 0, n.time_dep, R ? 1 : 0, 0, B, 0, Float32(get(kw, :reltol, 1.4f-8)), Float32(get(kw, :abstol, 1.4f-8)),
@@ -47,8 +76,10 @@ end
 
 # regularize = true: logpx, lambda1 (kinetic energy), lambda2 (Jacobian norm) as 1 x B rows, all three on the Tracker tape
 function _ffjord_call_kinetic(n::TrackedFFJORD{false}, x, p, e)
-    d, _ = _ffjord_dims(n)
-    (RNDE_FFJORD_ENGINE[] === :tiled || d + 3 <= 64) ||
+    chain = _ffjord_is_chain(n)
+    d = chain ? _ffjord_chain_layout(n)[1][1] : _ffjord_dims(n)[1]
+    chain && d + 3 > 64 && error("RNDE: chain dynamics with regularize = true: the state [z; l; lambda1; lambda2] must fit the limit of 64 rows; got in_dims = ", d)
+    (chain || RNDE_FFJORD_ENGINE[] === :tiled || d + 3 <= 64) ||
         error("RNDE: TrackedFFJORD{false} with regularize = true (kinetic energy and Jacobian norm rows): the chain engine's limit of 64 rows holds ",
               "in_dims + 3 <= 64 (RNDE_FFJORD_ENGINE[] = :tiled serves in_dims <= 64); got in_dims = ", d)
     H = _ffjord_handle(n, size(x, 2))

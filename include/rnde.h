@@ -553,7 +553,8 @@ rnde_status rnde_latent_encode_backward(rnde_latent* h, const float* z0_bar_dev,
  *   regularize = 0: TrackedFFJORD{false} with regularize = false (:68-112)
  *   regularize = 1: TrackedFFJORD{true} (:114-135): SavingCallback EEst * dt per accepted step (and 0 at init with cb_save_start)
  * Parameters in Flux.destructure order: per layer layer_W (out x in, column-major), layer_B, bias_W, bias_B, gate_W (each out).
- * Refused at create with a message naming the limit: dynamics other than ConcatSquash (the default forw_n_back through Tracker.forward),
+ * Refused at create with a message naming the limit: dynamics other than ConcatSquash (the default forw_n_back through Tracker.forward
+ * is not described by this config: rnde_ffjord_create_chain below serves it),
  * in_dims + 1 > 64 or hidden > 64 (rnde_ffjord_create; rnde_ffjord_create_tiled below serves wider models), kinetic_reg != 0 (the
  * {false} method's regularize = true rows at create: the keyword is a call-time one, served by the *_kinetic entries below on handles
  * created with kinetic_reg = 0), solvers other than Tsit5.
@@ -609,7 +610,7 @@ rnde_status rnde_ffjord_timing(rnde_ffjord* h, float* solve_ms, float* reverse_m
  * sample() and the exact trace of rnde_ffjord_debug_feval use the closed form tr J = a2' (W2 .* M') a1, M(t) = W1 diag(g3(t)) W3, with
  * a_l = sig(h_l) .* g_l: the same value as the D unit-probe VJPs, rounded differently. */
 rnde_status rnde_ffjord_create_tiled(const rnde_ffjord_config* cfg, rnde_ffjord** out);
-int32_t     rnde_ffjord_engine(const rnde_ffjord* h);          /* 0: one workgroup (rnde_ffjord_create), 1: tiled; -1 for NULL */
+int32_t     rnde_ffjord_engine(const rnde_ffjord* h);          /* 0: one workgroup (rnde_ffjord_create), 1: tiled, 2: chain dynamics; -1 for NULL */
 /* TrackedFFJORD{false} called with regularize = true (ffjord.jl:53-66): the state grows to [z; l; lambda1; lambda2] (D + 3 rows, the last
  * three starting at zero) with d lambda1 / dt = sum f^2 (the kinetic energy) and d lambda2 / dt = sum eJ^2 (the Hutchinson estimate of the
  * Jacobian's Frobenius norm), eJ as the trace row builds it.  The controller (initial step, error norm, PI step) runs over all D + 3 rows;
@@ -633,6 +634,32 @@ rnde_status rnde_ffjord_debug_feval_kinetic(rnde_ffjord* h, const float* x_dev, 
                                             float* out_dev, void* stream);
 /* (t, dt, EEst, accepted) of every attempt of the last solve, plain or kinetic, as rnde_node_steps (log_host NULL: the count only). */
 rnde_status rnde_ffjord_step_log(rnde_ffjord* h, float* log_host, int32_t capacity, int32_t* n_attempts_out);
+/* The default dynamics of TrackedFFJORD (dynamics = nothing, ffjord.jl:21-27: Tracker.forward(z -> m(z, t), z), then back(e)) for a chain of
+ * Dense layers, time dependent (TDChain: t appended to every layer's input) or plain: engine 2, on the tiled layout (one workgroup per 16
+ * columns, the padded weights resident in LDS, layer products on the matrix cores, one bounded meeting per attempt).  With y_0 = z,
+ *   a_l = W_l y_{l-1} + wt_l t + b_l,  y_l = phi_l(a_l),  f = y_n;   v_n = phi_n' .* e,  v_l = phi_l' .* (W_{l+1}' v_{l+1}),  eJ = W_1' v_1
+ * and the state rows are those of the ConcatSquash engines: [f; -e . eJ] and, through the *_kinetic entries, [f; -e . eJ; sum f^2; sum eJ^2].
+ * sample() and the exact trace are D unit-probe passes of the same VJP (the reference's jacobian_fn).  Parameters in Flux.destructure
+ * order: per layer W (out x (in [+ 1]), column-major, the t column last), then b -- the layout of rnde_node_config.  rnde_ffjord_config
+ * cannot describe a chain; every other rnde_ffjord_* entry dispatches on the handle and rnde_ffjord_engine returns 2.
+ * Refused at create (before a device is needed) with a message naming the limit: n_layers outside 1..RNDE_MAX_LAYERS; a layer output or a
+ * layer input above 64 (the time row is an epilogue vector and does not count: TD [48, 64, 64, 48] is served), or dims[0] + 1 > 64 (kinetic
+ * calls: dims[0] + 3 <= 64, on regularize = 0 handles);
+ * dims[0] != dims[n_layers]; an activation outside rnde_act; a solver other than Tsit5; max_batch > 4096 or max_attempts > 8000; weights plus
+ * the solve's activations above 160 KB of LDS (the message gives the need and the limit).  No leading element-wise map. */
+typedef struct {
+    int32_t n_layers;
+    int32_t dims[RNDE_MAX_LAYERS + 1]; /* dims[0] = dims[n_layers] = D */
+    int32_t act[RNDE_MAX_LAYERS];      /* rnde_act per layer */
+    int32_t time_dep;                  /* 1: TDChain, 0: Chain */
+    int32_t regularize;                /* 0: {false}, 1: {true} */
+    int32_t max_batch, solver;         /* solver: RNDE_SOLVER_TSIT5 */
+    float reltol, abstol;
+    int32_t cb_save_start;
+    int32_t max_attempts, device;
+} rnde_ffjord_chain_config;
+int32_t     rnde_ffjord_chain_param_count(const rnde_ffjord_chain_config* cfg);   /* 64 for TD [2, 10, 2]; -1 for a bad shape */
+rnde_status rnde_ffjord_create_chain(const rnde_ffjord_chain_config* cfg, rnde_ffjord** out);
 
 #ifdef __cplusplus
 }

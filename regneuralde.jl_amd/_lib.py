@@ -33,6 +33,12 @@ class FfjordConfig(C.Structure):
                 ("cb_save_start", C.c_int32), ("max_attempts", C.c_int32), ("device", C.c_int32)]
 
 
+class FfjordChainConfig(C.Structure):
+    _fields_ = [("n_layers", C.c_int32), ("dims", C.c_int32 * (MAX_LAYERS + 1)), ("act", C.c_int32 * MAX_LAYERS), ("time_dep", C.c_int32),
+                ("regularize", C.c_int32), ("max_batch", C.c_int32), ("solver", C.c_int32), ("reltol", C.c_float), ("abstol", C.c_float),
+                ("cb_save_start", C.c_int32), ("max_attempts", C.c_int32), ("device", C.c_int32)]
+
+
 class LatentConfig(C.Structure):
     _fields_ = [("max_batch", C.c_int32), ("max_T", C.c_int32), ("device", C.c_int32)]
 
@@ -191,6 +197,9 @@ def lib():
     L.rnde_ffjord_backward_kinetic.argtypes = [vp, vp, vp, vp, vp, vp]
     L.rnde_ffjord_debug_feval_kinetic.argtypes = [vp, vp, vp, vp, i32, f, vp, vp]
     L.rnde_ffjord_step_log.argtypes = [vp, fp, i32, i32p]
+    L.rnde_ffjord_chain_param_count.restype = i32
+    L.rnde_ffjord_chain_param_count.argtypes = [C.POINTER(FfjordChainConfig)]
+    L.rnde_ffjord_create_chain.argtypes = [C.POINTER(FfjordChainConfig), C.POINTER(vp)]
     _lib = L
     return L
 
@@ -207,7 +216,8 @@ EXPORTS = ["rnde_version", "rnde_last_error", "rnde_param_count", "rnde_node_cre
            "rnde_ffjord_param_count", "rnde_ffjord_create", "rnde_ffjord_destroy", "rnde_ffjord_last_error", "rnde_ffjord_forward",
            "rnde_ffjord_forward_replay", "rnde_ffjord_steps", "rnde_ffjord_backward", "rnde_ffjord_sample", "rnde_ffjord_debug_feval",
            "rnde_ffjord_timing", "rnde_ffjord_create_tiled", "rnde_ffjord_engine", "rnde_ffjord_forward_kinetic",
-           "rnde_ffjord_forward_kinetic_replay", "rnde_ffjord_backward_kinetic", "rnde_ffjord_debug_feval_kinetic", "rnde_ffjord_step_log"]
+           "rnde_ffjord_forward_kinetic_replay", "rnde_ffjord_backward_kinetic", "rnde_ffjord_debug_feval_kinetic", "rnde_ffjord_step_log",
+           "rnde_ffjord_chain_param_count", "rnde_ffjord_create_chain"]
 
 
 def check(h, status):

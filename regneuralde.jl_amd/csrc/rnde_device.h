@@ -394,5 +394,16 @@ __device__ __forceinline__ float act_dy(int code, float y) {
         default: return 1.f;
     }
 }
+// The second derivative, from the output as well (the reverse of a VJP through the layer: rnde_bffjordc.h): tanh -2 y (1 - y^2), sigmoid
+// y (1 - y) (1 - 2 y), softplus s (1 - s) with s = -expm1(-y), elu y > 0 ? 0 : y + 1, relu and identity 0.
+__device__ __forceinline__ float act_d2y(int code, float y) {
+    switch (code) {
+        case ACT_TANH: return -2.f * y * (1.f - y * y);
+        case ACT_SIGMOID: return y * (1.f - y) * (1.f - 2.f * y);
+        case ACT_SOFTPLUS: { const float s = -expm1f(-y); return s * (1.f - s); }
+        case ACT_ELU: return y > 0.f ? 0.f : y + 1.f;
+        default: return 0.f;
+    }
+}
 
 }  // namespace rnde

@@ -1,7 +1,8 @@
 // rnde_ffjord.hip -- C ABI of TrackedFFJORD (include/rnde.h, "TrackedFFJORD" section): create / forward / replay / backward / sample
 // over the kernels of rnde_ffjord.h (one-launch solve) and rnde_bffjord.h (one-launch reverse sweep), or, on a handle made by
 // rnde_ffjord_create_tiled, over those of rnde_ffjordt.h / rnde_bffjordt.h (the tiled engine).  The *_kinetic entries run the KIN = true
-// instantiations of the same kernels over D + 3 rows (TrackedFFJORD{false} called with regularize = true).
+// instantiations of the same kernels over D + 3 rows (TrackedFFJORD{false} called with regularize = true).  A handle made by
+// rnde_ffjord_create_chain (engine 2) runs the Dense-chain dynamics of rnde_ffjordc.h / rnde_bffjordc.h on the tiled layout.
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -9,6 +10,7 @@
 #include "../../include/rnde.h"
 #include "rnde_bffjord.h"
 #include "rnde_bffjordt.h"
+#include "rnde_bffjordc.h"
 
 using namespace rnde;
 
@@ -56,6 +58,7 @@ struct rnde_ffjord {
     unsigned epoch = 0;
     int xcd_slot = 0;
     std::vector<unsigned> h_chk;     // abort word, then each tile's XCC
+    FcGeo CG{};                      // engine = 2: the Dense-chain dynamics on the tiled layout (cfg holds the shared fields, in_dims = D)
 };
 
 #define FCHK(h, x)                                                                                  \
@@ -75,8 +78,9 @@ extern "C" int32_t rnde_ffjord_param_count(const rnde_ffjord_config* c) {
 // What the kernels serve; a message that names the limit otherwise (tiled: the tiled engine's limits).
 static const char* ff_refusal(const rnde_ffjord_config* c, bool tiled = false) {
     if (c->dynamics != RNDE_FFJORD_CONCAT_SQUASH)
-        return "TrackedFFJORD: only the ConcatSquash MLPDynamics of experiments/ffjord_gaussian.jl (dynamics = forw_n_back) is served; the default "
-               "forw_n_back (TDChain / Dense dynamics through Tracker.forward) is not";
+        return "TrackedFFJORD: this config describes the ConcatSquash MLPDynamics of experiments/ffjord_gaussian.jl (dynamics = forw_n_back) only; "
+               "the default forw_n_back (TDChain / Dense dynamics through Tracker.forward) is served by rnde_ffjord_create_chain "
+               "(rnde_ffjord_chain_config)";
     if (!tiled && (c->in_dims < 1 || c->in_dims + 1 > kFfMaxW || c->hidden < 1 || c->hidden > kFfMaxW))
         return "TrackedFFJORD: widths above the chain engine's limit of 64 are not served (in_dims + 1 <= 64 and hidden <= 64; "
                "rnde_ffjord_create_tiled / engine = \"tiled\" serves wider models)";
@@ -157,6 +161,114 @@ extern "C" rnde_status rnde_ffjord_create_tiled(const rnde_ffjord_config* c, rnd
 
 extern "C" int32_t rnde_ffjord_engine(const rnde_ffjord* h) { return h ? h->engine : -1; }
 
+// ---- the Dense-chain dynamics (rnde_ffjord_create_chain) ----
+static bool fc_shape_ok(const rnde_ffjord_chain_config* c) {
+    if (!c || c->n_layers < 1 || c->n_layers > RNDE_MAX_LAYERS) return false;
+    for (int l = 0; l <= c->n_layers; ++l) if (c->dims[l] < 1) return false;
+    return true;
+}
+
+extern "C" int32_t rnde_ffjord_chain_param_count(const rnde_ffjord_chain_config* c) {
+    if (!fc_shape_ok(c)) return -1;
+    int64_t P = 0;
+    for (int l = 0; l < c->n_layers; ++l) P += (int64_t)(c->dims[l] + (c->time_dep ? 1 : 0)) * c->dims[l + 1] + c->dims[l + 1];
+    return P > INT32_MAX ? -1 : (int32_t)P;
+}
+
+// What the chain kernels serve; a message that names the limit otherwise (no device needed).
+static const char* fc_refusal(const rnde_ffjord_chain_config* c) {
+    static thread_local std::string msg;
+    if (c->n_layers < 1 || c->n_layers > RNDE_MAX_LAYERS)
+        return "TrackedFFJORD chain dynamics: n_layers must be 1..RNDE_MAX_LAYERS (8 Dense layers)";
+    const int n = c->n_layers, td = c->time_dep ? 1 : 0;
+    for (int l = 0; l <= n; ++l) if (c->dims[l] < 1) return "TrackedFFJORD chain dynamics: every width must be at least 1";
+    if (c->dims[0] != c->dims[n])
+        return "TrackedFFJORD chain dynamics: dims[0] must equal dims[n_layers] (the dynamics map the state to its own rate)";
+    for (int l = 0; l < n; ++l)
+        if (c->dims[l + 1] > kFcMaxW || c->dims[l] > kFcMaxW)
+            return "TrackedFFJORD chain dynamics: widths above the limit of 64 are not served (no layer's output and no layer's input above 64; "
+                   "the time row of a TDChain layer is an epilogue vector and does not count)";
+    if (c->dims[0] + 1 > kFcMaxW)
+        return "TrackedFFJORD chain dynamics: the state [z; l] must fit the limit of 64 rows (dims[0] + 1 <= 64; dims[0] + 3 <= 64 for the "
+               "kinetic energy rows)";
+    for (int l = 0; l < n; ++l)
+        if (c->act[l] < RNDE_ACT_IDENTITY || c->act[l] > RNDE_ACT_ELU)
+            return "TrackedFFJORD chain dynamics: an activation code outside rnde_act (identity, tanh, relu, sigmoid, softplus, elu) is not served";
+    if (c->regularize != 0 && c->regularize != 1) return "TrackedFFJORD: regularize is 0 ({false}) or 1 ({true}: EEst * dt per accepted step)";
+    if (c->solver != RNDE_SOLVER_TSIT5) return "TrackedFFJORD: only Tsit5 is served";
+    if (c->max_batch < 1 || c->max_attempts < 1 || !(c->reltol > 0.f) || !(c->abstol > 0.f)) return "TrackedFFJORD: bad max_batch / max_attempts / tolerances";
+    if (c->max_batch > 16 * kMwMeetMax)
+        return "TrackedFFJORD chain dynamics: max_batch above 4096 is not served (one meeting holds kMwMeetMax = 256 resident tiles of 16 columns)";
+    if (c->max_attempts > kFtMaxAttempts) return "TrackedFFJORD chain dynamics: max_attempts above 8000 is not served (meeting tags)";
+    const FcGeo G = fc_geo(n, c->dims, c->act, td);
+    const size_t need = (size_t)fc_lds_floats(G) * 4;
+    if (need > (size_t)kFtLdsBytes) {
+        msg = "TrackedFFJORD chain dynamics: the resident weights and the activations of a tile need " + std::to_string(need) +
+              " bytes of LDS, above the limit of " + std::to_string(kFtLdsBytes) + " bytes (160 KB)";
+        return msg.c_str();
+    }
+    return nullptr;
+}
+
+extern "C" rnde_status rnde_ffjord_create_chain(const rnde_ffjord_chain_config* c, rnde_ffjord** out) {
+    if (!c || !out) { g_ff_create_err = "null argument"; return RNDE_ERR_BAD_ARG; }
+    *out = nullptr;
+    if (const char* why = fc_refusal(c)) { g_ff_create_err = why; return RNDE_ERR_BAD_ARG; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= c->device) { g_ff_create_err = "no HIP device"; return RNDE_ERR_NO_DEVICE; }
+    if (hipSetDevice(c->device) != hipSuccess) { g_ff_create_err = "hipSetDevice failed"; return RNDE_ERR_NO_DEVICE; }
+    rnde_ffjord* h = new rnde_ffjord();
+    h->engine = 2;
+    h->CG = fc_geo(c->n_layers, c->dims, c->act, c->time_dep);
+    const FcGeo& G = h->CG;
+    const int D = G.D, R = D + 1;
+    rnde_ffjord_config& k = h->cfg;        // the fields the shared entries read
+    k = rnde_ffjord_config{};
+    k.in_dims = D; k.hidden = 0; k.dynamics = RNDE_FFJORD_TRACKER_FORWARD; k.time_dep = c->time_dep; k.regularize = c->regularize;
+    k.max_batch = c->max_batch; k.solver = c->solver; k.reltol = c->reltol; k.abstol = c->abstol; k.cb_save_start = c->cb_save_start;
+    k.max_attempts = c->max_attempts; k.device = c->device;
+    h->G = FfGeo{};
+    h->G.D = D; h->G.H = 0; h->G.P = G.P;
+    h->R = R;
+    h->ntiles_max = (c->max_batch + 15) / 16;
+    h->Bp = 16 * h->ntiles_max;
+    h->T = kFtThreads;
+    h->lds_bytes = (size_t)fc_lds_floats(G) * 4;
+    auto fail = [&](hipError_t e) { g_ff_create_err = std::string("HIP: ") + hipGetErrorString(e); rnde_ffjord_destroy(h); return RNDE_ERR_HIP; };
+    hipError_t e;
+    const size_t RB = (size_t)R * h->Bp, MA = (size_t)c->max_attempts, NT = (size_t)h->ntiles_max;
+    const size_t xb = (MA + 4) * 3 * kMwMeetMax * 8;
+    if ((e = hipMalloc(&h->ws, 10 * RB * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->tape, (MA + 1) * RB * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->norm, (8 * NT + 512) * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMemset(h->norm, 0, (8 * NT + 512) * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->e_buf, (size_t)D * h->Bp * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->e_tape, (size_t)D * h->Bp * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->replay, 2 * MA * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->rws, NT * fc_rev_ws_floats(G) * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->pacc, NT * G.P * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->ctl, 3 * sizeof(StepState))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->ctl_t, NT * sizeof(StepState))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->meta, MA * sizeof(StepMeta))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->initrec_t, NT * sizeof(InitRec))) != hipSuccess) return fail(e);
+    h->initrec = h->initrec_t;
+    if ((e = hipMalloc(&h->rec, MA * sizeof(FfStepRec))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->xch, xb)) != hipSuccess) return fail(e);
+    if ((e = hipMemset(h->xch, 0, xb)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->xcc, kMwMeetMax * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->abort_word, 8)) != hipSuccess) return fail(e);
+    if ((e = hipMemset(h->abort_word, 0, 8)) != hipSuccess) return fail(e);
+    for (const void* kf : {(const void*)rnde_ffjordc_solve_kernel<false>, (const void*)rnde_ffjordc_reverse_kernel<false>,
+                           (const void*)rnde_ffjordc_feval_kernel<false>, (const void*)rnde_ffjordc_solve_kernel<true>,
+                           (const void*)rnde_ffjordc_reverse_kernel<true>, (const void*)rnde_ffjordc_feval_kernel<true>})
+        if ((e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes)) != hipSuccess) return fail(e);
+    for (auto& v : h->ev) if ((e = hipEventCreate(&v)) != hipSuccess) return fail(e);
+    { static std::atomic<int> next_slot{0}; h->xcd_slot = next_slot.fetch_add(1) & 7; }
+    h->h_chk.assign(2 + kMwMeetMax, 0u);
+    *out = h;
+    return RNDE_OK;
+}
+
 extern "C" rnde_status rnde_ffjord_create(const rnde_ffjord_config* c, rnde_ffjord** out) {
     if (!c || !out) { g_ff_create_err = "null argument"; return RNDE_ERR_BAD_ARG; }
     *out = nullptr;
@@ -223,10 +335,16 @@ static rnde_status ff_kinetic_ready(rnde_ffjord* h) {
                  "rnde_ffjord_create_tiled / engine = \"tiled\" serves in_dims <= 64 and hidden <= 112)";
         return RNDE_ERR_BAD_ARG;
     }
+    if (h->engine == 2 && Rk > kFcMaxW) {
+        h->err = "TrackedFFJORD kinetic energy rows on chain dynamics: the state [z; l; lambda1; lambda2] must fit the limit of 64 rows "
+                 "(dims[0] + 3 <= 64)";
+        return RNDE_ERR_BAD_ARG;
+    }
     if (h->kin_ready) return RNDE_OK;
     const size_t RBk = (size_t)Rk * h->Bp, RB = (size_t)h->R * h->Bp, MA = (size_t)h->cfg.max_attempts;
-    const size_t rws = h->engine == 1 ? (size_t)h->ntiles_max * ft_rev_ws_floats(h->TG, true)
-                                      : (size_t)(24 + kFfVjpVecsKin) * std::max(H, Rk) * h->Bp;
+    const size_t rws = h->engine == 2 ? (size_t)h->ntiles_max * fc_rev_ws_floats(h->CG, true)
+                       : h->engine == 1 ? (size_t)h->ntiles_max * ft_rev_ws_floats(h->TG, true)
+                                        : (size_t)(24 + kFfVjpVecsKin) * std::max(H, Rk) * h->Bp;
     FCHK(h, hipDeviceSynchronize());           // (rnde_ffjord_debug_feval does not wait for its launch)
     float *ws = nullptr, *tape = nullptr, *rw = nullptr;
     hipError_t e = hipMalloc(&ws, 10 * RBk * 4);
@@ -285,6 +403,20 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
         TQ.xcc = h->xcc; TQ.xcd_slot = h->xcd_slot; TQ.dir = dir; TQ.Bp = h->Bp; TQ.ntiles = nt; TQ.tbase = t1;
         TQ.reg = reg_out_dev;
     }
+    const bool tiles = h->engine >= 1;     // engines 1 and 2 share the tiled layout, the meeting and its checks
+    if (h->engine == 2) {      // the Dense-chain dynamics: the tiled engine's launch shape and meeting
+        if (++h->epoch >= 500000u) { h->epoch = 1; FCHK(h, hipMemsetAsync(h->xch, 0, ((size_t)h->cfg.max_attempts + 4) * 3 * kMwMeetMax * 8, s)); }
+        FcSolveParams CQ{};
+        CQ.F = P; CQ.G = h->CG; CQ.p = p_dev; CQ.x = x_dev; CQ.e = Q.e; CQ.ws = h->ws; CQ.tape = Q.tape; CQ.logpx = Q.logpx; CQ.x_out = x_out_dev;
+        CQ.norm = h->norm; CQ.initrec_t = h->initrec_t; CQ.ctl_t = h->ctl_t;
+        CQ.meet = MwMeet{h->xch, h->abort_word, h->epoch, nt, nt > 32 ? 1 : 0};
+        CQ.xcc = h->xcc; CQ.xcd_slot = h->xcd_slot; CQ.dir = dir; CQ.Bp = h->Bp; CQ.ntiles = nt; CQ.tbase = t1; CQ.reg = reg_out_dev;
+        TQ.meet = CQ.meet;
+        FCHK(h, hipEventRecord(h->ev[0], s));
+        const dim3 grid(CQ.meet.global ? nt : 8 * nt);
+        if (kin) hipLaunchKernelGGL(rnde_ffjordc_solve_kernel<true>, grid, dim3(kFtThreads), h->lds_bytes, s, CQ);
+        else hipLaunchKernelGGL(rnde_ffjordc_solve_kernel<false>, grid, dim3(kFtThreads), h->lds_bytes, s, CQ);
+    } else {
     FCHK(h, hipEventRecord(h->ev[0], s));
     if (h->engine == 1) {
         const dim3 grid(TQ.meet.global ? nt : 8 * nt);
@@ -292,17 +424,18 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
         else hipLaunchKernelGGL(rnde_ffjordt_solve_kernel<false>, grid, dim3(kFtThreads), h->lds_bytes, s, TQ);
     } else if (kin) hipLaunchKernelGGL(rnde_ffjord_solve_kernel<true>, dim3(1), dim3(h->T), h->lds_bytes, s, Q);
     else hipLaunchKernelGGL(rnde_ffjord_solve_kernel<false>, dim3(1), dim3(h->T), h->lds_bytes, s, Q);
+    }
     FCHK(h, hipGetLastError());
     FCHK(h, hipEventRecord(h->ev[1], s));
     StepState fin;
     FCHK(h, hipMemcpyAsync(&fin, h->ctl + 2, sizeof(StepState), hipMemcpyDeviceToHost, s));
-    if (h->engine == 1) {
+    if (tiles) {
         FCHK(h, hipMemcpyAsync(h->h_chk.data(), h->abort_word, 4, hipMemcpyDeviceToHost, s));
         if (!TQ.meet.global) FCHK(h, hipMemcpyAsync(h->h_chk.data() + 2, h->xcc, (size_t)nt * 4, hipMemcpyDeviceToHost, s));
     }
     FCHK(h, hipStreamSynchronize(s));
     (void)hipEventElapsedTime(&h->fwd_ms, h->ev[0], h->ev[1]);
-    if (h->engine == 1) {
+    if (tiles) {
         bool split = false;
         for (int i = 1; i < nt && !TQ.meet.global; ++i) split |= h->h_chk[2 + i] != h->h_chk[2];
         if (h->h_chk[0] != 0u || split) {      // no fall-back to other arithmetic: the call fails and says why
@@ -434,7 +567,17 @@ static rnde_status ff_backward(rnde_ffjord* h, const float* logpx_bar_dev, const
     Q.ws = h->rws; Q.pacc = h->pacc; Q.x_bar = x_bar_dev; Q.n_acc = T.n_acc; Q.B = T.B; Q.Bp = h->Bp; Q.reltol = T.reltol; Q.abstol = T.abstol;
     Q.reg_bar = reg_bar_dev;
     FCHK(h, hipEventRecord(h->ev[2], s));
-    if (h->engine == 1) {
+    if (h->engine == 2) {
+        FcRevParams CQ{};
+        CQ.G = h->CG; CQ.p = T.p; CQ.e = T.e; CQ.tape = h->tape; CQ.rec = h->rec; CQ.logpx_bar = logpx_bar_dev; CQ.ws = h->rws; CQ.pacc = h->pacc;
+        CQ.x_bar = x_bar_dev; CQ.n_acc = T.n_acc; CQ.B = T.B; CQ.Bp = h->Bp; CQ.reltol = T.reltol; CQ.abstol = T.abstol;
+        CQ.reg_bar = reg_bar_dev;
+        const int nt = (T.B + 15) / 16;
+        if (T.kin) hipLaunchKernelGGL(rnde_ffjordc_reverse_kernel<true>, dim3(nt), dim3(kFtThreads), h->lds_bytes, s, CQ);
+        else hipLaunchKernelGGL(rnde_ffjordc_reverse_kernel<false>, dim3(nt), dim3(kFtThreads), h->lds_bytes, s, CQ);
+        FCHK(h, hipGetLastError());
+        hipLaunchKernelGGL(rnde_ffjordt_reduce_kernel, dim3((h->G.P + 255) / 256), dim3(256), 0, s, (const float*)h->pacc, h->G.P, nt, p_bar_dev);
+    } else if (h->engine == 1) {
         FtRevParams TQ{};
         TQ.G = h->TG; TQ.p = T.p; TQ.e = T.e; TQ.tape = h->tape; TQ.rec = h->rec; TQ.logpx_bar = logpx_bar_dev; TQ.ws = h->rws; TQ.pacc = h->pacc;
         TQ.x_bar = x_bar_dev; TQ.n_acc = T.n_acc; TQ.B = T.B; TQ.Bp = h->Bp; TQ.reltol = T.reltol; TQ.abstol = T.abstol;
@@ -486,7 +629,10 @@ extern "C" rnde_status rnde_ffjord_sample(rnde_ffjord* h, const float* p_dev, co
 extern "C" rnde_status rnde_ffjord_debug_feval(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t,
                                                int32_t exact, float* out_dev, void* stream) {
     if (!h || !x_dev || !p_dev || !out_dev || B < 1 || B > h->cfg.max_batch || (!exact && !e_dev)) { if (h) h->err = "bad argument"; return RNDE_ERR_BAD_ARG; }
-    if (h->engine == 1)
+    if (h->engine == 2)
+        hipLaunchKernelGGL(rnde_ffjordc_feval_kernel<false>, dim3((B + 15) / 16), dim3(kFtThreads), h->lds_bytes, (hipStream_t)stream, h->CG, p_dev, x_dev, e_dev,
+                           t, B, exact, h->rws, out_dev);
+    else if (h->engine == 1)
         hipLaunchKernelGGL(rnde_ffjordt_feval_kernel<false>, dim3((B + 15) / 16), dim3(kFtThreads), h->lds_bytes, (hipStream_t)stream, h->TG, p_dev, x_dev, e_dev,
                            t, B, exact, h->rws, h->qt, out_dev);
     else
@@ -500,7 +646,10 @@ extern "C" rnde_status rnde_ffjord_debug_feval_kinetic(rnde_ffjord* h, const flo
                                                        float* out_dev, void* stream) {
     if (!h || !x_dev || !p_dev || !e_dev || !out_dev || B < 1 || B > h->cfg.max_batch) { if (h) h->err = "bad argument"; return RNDE_ERR_BAD_ARG; }
     if (rnde_status kst = ff_kinetic_ready(h)) return kst;
-    if (h->engine == 1)
+    if (h->engine == 2)
+        hipLaunchKernelGGL(rnde_ffjordc_feval_kernel<true>, dim3((B + 15) / 16), dim3(kFtThreads), h->lds_bytes, (hipStream_t)stream, h->CG, p_dev, x_dev,
+                           e_dev, t, B, 0, h->rws, out_dev);
+    else if (h->engine == 1)
         hipLaunchKernelGGL(rnde_ffjordt_feval_kernel<true>, dim3((B + 15) / 16), dim3(kFtThreads), h->lds_bytes, (hipStream_t)stream, h->TG, p_dev, x_dev,
                            e_dev, t, B, 0, h->rws, h->qt, out_dev);
     else

@@ -15,8 +15,14 @@ step) -- and sample(), on one of two engines:
     engine="tiled": one workgroup per 16 columns, layer products on the matrix cores, in_dims <= 64 and hidden <= 112 (the tabular
                     experiment's MLPDynamics(43, 100)), max_batch <= 4096.
 The regularize = true rows add two state rows: engine="workgroup" serves them for in_dims + 3 <= 64, engine="tiled" at its own limits.
-Refused with a message that names the limit: any other dynamics (the default forw_n_back through Tracker.forward) and widths above the
-engine's limit.
+The default dynamics (dynamics = nothing, ffjord.jl:21-27: Tracker.forward through any Flux model, then back(e)) are served for Dense chains
+on engine="tiled": a layers.TDChain with time_dep=True or a layers.Chain (no leading map) with time_dep=False, up to 8 layers, no layer output
+and no layer input above 64 (the time row apart), any of the six Dense activations (rnde_ffjord_create_chain):
+
+    model = TDChain(Dense(3, 10, "tanh"), Dense(11, 2))
+    ffjord = TrackedFFJORD(model, [0.0, 1.0], True, False, "Tsit5", reltol=1.4e-3, abstol=1.4e-3, engine="tiled")   # p = destructure(model)
+
+Refused with a message that names the limit: any other dynamics, a chain model on engine="workgroup", and widths above the engine's limit.
 """
 import ctypes as C
 import math
@@ -25,10 +31,12 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import layers as _layers
 
 MAX_WIDTH = 64
 TILED_MAX_IN, TILED_MAX_HIDDEN, TILED_MAX_BATCH = 64, 112, 4096
 ENGINES = ("workgroup", "tiled")
+CHAIN_MAX_WIDTH, CHAIN_LDS_BYTES = 64, 160 * 1024
 
 
 def _glorot(rows, cols, gen):
@@ -76,10 +84,59 @@ def param_count(in_dims, hidden):
     return (hidden * in_dims + 4 * hidden) + (hidden * hidden + 4 * hidden) + (in_dims * hidden + 4 * in_dims)
 
 
+def is_chain(model):
+    """A Dense chain of layers.py: the models the default dynamics (Tracker.forward, then back) are served for."""
+    return isinstance(model, (_layers.Chain, _layers.TDChain))
+
+
+def chain_lds_bytes(dims):
+    """LDS bytes of a tile of the chain kernels (rnde_ffjordc.h::fc_lds_floats): padded weights with the t column and bias vectors, the input
+    and the probe, every layer's output, two VJP vectors, reduction scratch."""
+    pad = lambda n: (n + 15) // 16 * 16
+    n = len(dims) - 1
+    w = sum(pad(dims[l]) * (pad(dims[l + 1]) + 1) + 2 * pad(dims[l + 1]) for l in range(n))
+    mp = max(pad(d) for d in dims)
+    return 4 * ((w + 3) // 4 * 4 + 2 * pad(dims[0]) * 16 + sum(pad(dims[l + 1]) * 16 for l in range(n)) + 2 * mp * 16 + 128)
+
+
+def check_chain_served(model, time_dep, engine="workgroup", kinetic=False):
+    """ValueError naming the limit for a Dense-chain model under the default dynamics."""
+    if engine != "tiled":
+        raise ValueError("TrackedFFJORD: the default forw_n_back (TDChain / Dense dynamics through Tracker.forward) is served on engine=\"tiled\" only; "
+                         f"got engine={engine!r}")
+    td = isinstance(model, _layers.TDChain)
+    if time_dep and not td:
+        raise ValueError("TrackedFFJORD: time_dep = true calls m(z, t) inside Tracker.forward, and a Chain takes one argument; pass a TDChain, or "
+                         "time_dep=False")
+    if td and not time_dep:
+        raise ValueError("TrackedFFJORD: a TDChain reads t at every layer; time_dep=False would call it with one argument")
+    if getattr(model, "pre_act", False):
+        raise ValueError("TrackedFFJORD: a leading element-wise map in front of the Dense chain is not served")
+    if not model.layers or len(model.layers) > _lib.MAX_LAYERS:
+        raise ValueError(f"TrackedFFJORD chain dynamics: 1..{_lib.MAX_LAYERS} Dense layers; got {len(model.layers)}")
+    dims = model.dims()
+    for l, lay in enumerate(model.layers):
+        if lay.n_in != dims[l] + (1 if td else 0):
+            raise ValueError(f"TrackedFFJORD chain dynamics: layer {l + 1} takes {lay.n_in} inputs where the chain hands it {dims[l] + (1 if td else 0)}")
+        _layers.act_code(lay.act)
+    if dims[0] != dims[-1]:
+        raise ValueError(f"TrackedFFJORD chain dynamics: the chain must map {dims[0]} rows to {dims[0]} rows; it ends in {dims[-1]}")
+    rows = dims[0] + (3 if kinetic else 1)
+    if max(dims) > CHAIN_MAX_WIDTH or rows > CHAIN_MAX_WIDTH:
+        raise ValueError(f"TrackedFFJORD chain dynamics: widths above the limit of {CHAIN_MAX_WIDTH} are not served (no layer's output, no layer's "
+                         f"input -- its time row apart -- and not the {rows} state rows; got dims = {dims})")
+    need = chain_lds_bytes(dims)
+    if need > CHAIN_LDS_BYTES:
+        raise ValueError(f"TrackedFFJORD chain dynamics: the resident weights and the activations of a tile need {need} bytes of LDS, above the "
+                         f"limit of {CHAIN_LDS_BYTES} bytes")
+
+
 def check_served(model, regularize_kinetic=False, engine="workgroup"):
     """ValueError naming the limit for what the kernels of `engine` do not serve."""
     if engine not in ENGINES:
         raise ValueError(f"TrackedFFJORD: engine must be one of {ENGINES}; got {engine!r}")
+    if is_chain(model):
+        return check_chain_served(model, isinstance(model, _layers.TDChain), engine, kinetic=bool(regularize_kinetic))
     if not isinstance(model, MLPDynamics):
         raise ValueError("TrackedFFJORD: only the ConcatSquash MLPDynamics of experiments/ffjord_gaussian.jl (dynamics = forw_n_back) is served; "
                          "the default forw_n_back (TDChain / Dense dynamics through Tracker.forward) is not")
@@ -96,6 +153,8 @@ def check_served(model, regularize_kinetic=False, engine="workgroup"):
 def check_kinetic_served(model, engine="workgroup"):
     """ValueError naming the limit for the {false} method's regularize = true rows (kinetic energy, Jacobian norm) on `engine`: the limits
     of check_served with two more state rows."""
+    if is_chain(model):
+        return check_chain_served(model, isinstance(model, _layers.TDChain), engine, kinetic=True)
     check_served(model, engine=engine)
     if engine == "workgroup" and model.in_dims + 3 > MAX_WIDTH:
         raise ValueError(f"TrackedFFJORD{{false}} with regularize = true (kinetic energy and Jacobian norm rows): the chain engine's limit of "
@@ -118,7 +177,10 @@ class _Handle:
 
     def __init__(self, cfg, engine="workgroup"):
         self.h = C.c_void_p()
-        create = _lib.lib().rnde_ffjord_create_tiled if engine == "tiled" else _lib.lib().rnde_ffjord_create
+        if isinstance(cfg, _lib.FfjordChainConfig):
+            create = _lib.lib().rnde_ffjord_create_chain
+        else:
+            create = _lib.lib().rnde_ffjord_create_tiled if engine == "tiled" else _lib.lib().rnde_ffjord_create
         _lib.check_ffjord(None, create(C.byref(cfg), C.byref(self.h)))
         self.gen, self.busy = 0, False
 
@@ -269,7 +331,16 @@ class TrackedFFJORD:
                  cb_save_start=True, device=0, dynamics=None, engine="workgroup", **kwargs):
         if dynamics is not None and dynamics != "forw_n_back":
             raise ValueError("TrackedFFJORD: only dynamics = forw_n_back of the ConcatSquash MLPDynamics is served")
-        check_served(model, engine=engine)
+        self.chain = is_chain(model)
+        if self.chain:
+            if engine not in ENGINES:
+                raise ValueError(f"TrackedFFJORD: engine must be one of {ENGINES}; got {engine!r}")
+            if dynamics is not None:
+                raise ValueError("TrackedFFJORD: dynamics = forw_n_back is the ConcatSquash MLPDynamics' own VJP; a Dense chain goes through the "
+                                 "default dynamics (dynamics=None)")
+            check_chain_served(model, bool(time_dep), engine)
+        else:
+            check_served(model, engine=engine)
         if engine == "tiled" and int(max_batch) > TILED_MAX_BATCH:
             raise ValueError(f"TrackedFFJORD tiled engine: max_batch above {TILED_MAX_BATCH} is not served (one meeting holds 256 resident tiles)")
         self.engine = engine
@@ -278,7 +349,9 @@ class TrackedFFJORD:
         self.model, self.tspan, self.time_dep, self.regularize = model, (float(tspan[0]), float(tspan[1])), bool(time_dep), bool(regularize)
         self.reltol, self.abstol, self.max_batch, self.max_attempts = float(reltol), float(abstol), int(max_batch), int(max_attempts)
         self.cb_save_start, self.device = bool(cb_save_start), int(device)
-        self.p = model.destructure().cuda(self.device)
+        self.in_dims = model.dims()[0] if self.chain else model.in_dims
+        self.p = (_layers.destructure(model) if self.chain else model.destructure()).cuda(self.device)
+        self.n_params = self.p.numel()
         self._h = None          # untaped calls: inference, sample, steps of those, feval
         self._pool = []         # handles for taped forwards (one tape each)
         self._last = self._last_bwd = None
@@ -286,8 +359,18 @@ class TrackedFFJORD:
         self._seed = 0x5EED
 
     def config(self):
+        if self.chain:
+            cfg, dims = _lib.FfjordChainConfig(), self.model.dims()
+            cfg.n_layers = len(self.model.layers)
+            for i, d in enumerate(dims):
+                cfg.dims[i] = d
+            for i, l in enumerate(self.model.layers):
+                cfg.act[i] = _layers.act_code(l.act)
+            cfg.time_dep, cfg.regularize, cfg.max_batch, cfg.solver = int(self.time_dep), int(self.regularize), self.max_batch, 0
+            cfg.reltol, cfg.abstol, cfg.cb_save_start, cfg.max_attempts, cfg.device = self.reltol, self.abstol, int(self.cb_save_start), self.max_attempts, self.device
+            return cfg
         cfg = _lib.FfjordConfig()
-        cfg.in_dims, cfg.hidden, cfg.dynamics, cfg.time_dep = self.model.in_dims, self.model.hidden, 0, int(self.time_dep)
+        cfg.in_dims, cfg.hidden, cfg.dynamics, cfg.time_dep = self.in_dims, self.model.hidden, 0, int(self.time_dep)
         cfg.regularize, cfg.kinetic_reg, cfg.max_batch, cfg.solver = int(self.regularize), 0, self.max_batch, 0
         cfg.reltol, cfg.abstol, cfg.cb_save_start, cfg.max_attempts, cfg.device = self.reltol, self.abstol, int(self.cb_save_start), self.max_attempts, self.device
         return cfg
@@ -322,16 +405,16 @@ class TrackedFFJORD:
         if not (x.is_cuda and p.is_cuda):
             raise RuntimeError("TrackedFFJORD runs on the device only: x and p must be cuda tensors")
         x = x.contiguous().float()
-        if x.dim() != 2 or x.shape[1] != self.model.in_dims:
-            raise ValueError(f"x must be (B, {self.model.in_dims})")
+        if x.dim() != 2 or x.shape[1] != self.in_dims:
+            raise ValueError(f"x must be (B, {self.in_dims})")
         if e is None:
-            e = self.draw_normal(self.model.in_dims, x.shape[0], x.device)
+            e = self.draw_normal(self.in_dims, x.shape[0], x.device)
         elif tuple(e.shape) != tuple(x.shape) or not e.is_cuda:
             raise ValueError(f"e must be a cuda tensor of x's shape {tuple(x.shape)} (B, D); got {tuple(e.shape)}")
         e = e.contiguous().float()
         p = p.contiguous()
-        if p.numel() != self.model.param_count():
-            raise ValueError(f"p must hold {self.model.param_count()} parameters; got {p.numel()}")
+        if p.numel() != self.n_params:
+            raise ValueError(f"p must hold {self.n_params} parameters; got {p.numel()}")
         # tape only when a gradient can be asked for: an inference call must not occupy (or replace) a tape
         keep = torch.is_grad_enabled() and (x.requires_grad or p.requires_grad)
         if kinetic:
@@ -371,18 +454,18 @@ class TrackedFFJORD:
         p = self.p if p is None else p
         if regularize:
             check_kinetic_served(self.model, self.engine)
-            if e is None or x.dim() != 2 or x.shape[1] != self.model.in_dims or tuple(e.shape) != tuple(x.shape):
-                raise ValueError(f"x and e must be (B, {self.model.in_dims}) (the kinetic rows use the Hutchinson probe)")
+            if e is None or x.dim() != 2 or x.shape[1] != self.in_dims or tuple(e.shape) != tuple(x.shape):
+                raise ValueError(f"x and e must be (B, {self.in_dims}) (the kinetic rows use the Hutchinson probe)")
             h = self._handle().h
-            out = torch.empty(x.shape[0], self.model.in_dims + 3, device=x.device)
+            out = torch.empty(x.shape[0], self.in_dims + 3, device=x.device)
             _lib.check_ffjord(h, _lib.lib().rnde_ffjord_debug_feval_kinetic(h, x.contiguous().data_ptr(), p.contiguous().data_ptr(),
                                                                             e.contiguous().data_ptr(), x.shape[0], float(t), out.data_ptr(),
                                                                             _stream(x.device)))
             return out
-        if x.dim() != 2 or x.shape[1] != self.model.in_dims or (e is not None and tuple(e.shape) != tuple(x.shape)):
-            raise ValueError(f"x and e must be (B, {self.model.in_dims})")
+        if x.dim() != 2 or x.shape[1] != self.in_dims or (e is not None and tuple(e.shape) != tuple(x.shape)):
+            raise ValueError(f"x and e must be (B, {self.in_dims})")
         h = self._handle().h
-        out = torch.empty(x.shape[0], self.model.in_dims + 1, device=x.device)
+        out = torch.empty(x.shape[0], self.in_dims + 1, device=x.device)
         _lib.check_ffjord(h, _lib.lib().rnde_ffjord_debug_feval(h, x.contiguous().data_ptr(), p.contiguous().data_ptr(),
                                                                 e.contiguous().data_ptr() if e is not None else None, x.shape[0], float(t),
                                                                 int(e is None), out.data_ptr(), _stream(x.device)))
@@ -392,7 +475,7 @@ class TrackedFFJORD:
 @torch.no_grad()
 def sample(ffjord, indims, p=None, nsamples=1, z=None):
     """sample(ffjord, indims, p; nsamples) (ffjord.jl:160-167): z ~ N(0, I), solved from t1 back to t0 with the exact trace.  Returns x (nsamples, D)."""
-    if indims != ffjord.model.in_dims:
+    if indims != ffjord.in_dims:
         raise ValueError("indims must equal the model's in_dims")
     p = ffjord.p if p is None else p
     hd = ffjord._handle()
