@@ -115,13 +115,26 @@ static rnde_status launch_wgrad_part(rnde_node* h, const EvalDesc* ev, int n_eva
             if ((size_t)(*chunk_cursor + sc4) * (size_t)len > h->bw.slab_floats) { h->err = "weight-gradient slab overflow"; return RNDE_ERR_BAD_ARG; }
             static DeviceOnce attr4;
             if (attr4.need()) {
-                HIPCHK(h, hipFuncSetAttribute((const void*)rnde_wgrad4x_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWx4LdsBytes));
-                HIPCHK(h, hipFuncSetAttribute((const void*)rnde_wgrad4x_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWx4LdsBytes));
+                HIPCHK(h, hipFuncSetAttribute((const void*)rnde_wgrad4x_kernel<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWx4LdsBytes));
+                HIPCHK(h, hipFuncSetAttribute((const void*)rnde_wgrad4x_kernel<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWx4LdsBytes));
+                HIPCHK(h, hipFuncSetAttribute((const void*)rnde_wgrad4x_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWx4fLdsBytes));
+                HIPCHK(h, hipFuncSetAttribute((const void*)rnde_wgrad4x_kernel<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWx4fLdsBytes));
                 attr4.done();
             }
             const dim3 g4(32 * ((sc4 + 7) / 8));
-            if (tall) hipLaunchKernelGGL((rnde_wgrad4x_kernel<true>), g4, dim3(448), kWx4LdsBytes, s, ev, n_evals, spc4, sc4, M, Nx, Bpad, dst);
-            else hipLaunchKernelGGL((rnde_wgrad4x_kernel<false>), g4, dim3(448), kWx4LdsBytes, s, ev, n_evals, spc4, sc4, M, Nx, Bpad, dst);
+#if RNDE_WX4_ABL == 7 || RNDE_WX4_ABL == 8      // (these two timing ablations exist in the first form only: such a build always launches it)
+            const bool q0 = true;
+#else
+            // which operand feed (rnde_wgradx.h; same chunks, same bits), read per call for A/B runs and tests: RNDE_X3_WGRAD_Q0=1 the quarter form as first built
+            // (FEED 0), RNDE_X3_WGRAD_FEED=1 the coalesced, unrepeated feed (FEED 1); neither set: kWx4DefaultFeed
+            const char* ef = getenv("RNDE_X3_WGRAD_FEED");
+            const bool q0 = getenv("RNDE_X3_WGRAD_Q0") != nullptr || (ef ? ef[0] == '0' : kWx4DefaultFeed == 0);
+#endif
+            if (q0) {
+                if (tall) hipLaunchKernelGGL((rnde_wgrad4x_kernel<true, 0>), g4, dim3(448), kWx4LdsBytes, s, ev, n_evals, spc4, sc4, M, Nx, Bpad, dst);
+                else hipLaunchKernelGGL((rnde_wgrad4x_kernel<false, 0>), g4, dim3(448), kWx4LdsBytes, s, ev, n_evals, spc4, sc4, M, Nx, Bpad, dst);
+            } else if (tall) hipLaunchKernelGGL((rnde_wgrad4x_kernel<true, 1>), g4, dim3(448), kWx4fLdsBytes, s, ev, n_evals, spc4, sc4, M, Nx, Bpad, dst);
+            else hipLaunchKernelGGL((rnde_wgrad4x_kernel<false, 1>), g4, dim3(448), kWx4fLdsBytes, s, ev, n_evals, spc4, sc4, M, Nx, Bpad, dst);
             HIPCHK(h, hipGetLastError());
             *chunk_cursor += sc4;
             return RNDE_OK;

@@ -172,15 +172,34 @@ __global__ __launch_bounds__(448) void rnde_wgrad3x_kernel(const EvalDesc* __res
 #ifndef RNDE_WX4_SB
 #define RNDE_WX4_SB 1
 #endif
-#ifndef RNDE_WX4_ABL      // timing ablations (wrong results): 1 no splitting, 2 no splitting and no loads, 3 B fragments read once per step, 4 matrix instructions only, 5 split without its LDS writes, 6 LDS writes without the split
-#define RNDE_WX4_ABL 0
+#ifndef RNDE_WX4_ABL      // timing ablations (wrong results): 1 no splitting, 2 no splitting and no loads, 3 B fragments read once per step, 4 matrix instructions only, 5 split without its LDS writes, 6 LDS writes without the split,
+#define RNDE_WX4_ABL 0    // 7 (FEED 0 only) the loads in FEED 1's lane order with the LDS destinations left alone, 8 (FEED 0 only) the repeated units load nothing and write into the rows' padding
 #endif
 constexpr int kWx4TallRows = 208;
 constexpr int kWx4PlaneT = kWx4TallRows * kWxRowShorts, kWx4PlaneS = kWxNarrowRows * kWxRowShorts;
 constexpr int kWx4ImageShorts = 3 * (kWx4PlaneT + kWx4PlaneS);      // 38,400 bf16
 constexpr size_t kWx4LdsBytes = (size_t)2 * kWx4ImageShorts * 2;    // 153,600 bytes: two images
+// ---- FEED = 1 (RNDE_X3_WGRAD_FEED=1; FEED = 0 is the kernel as first built, RNDE_X3_WGRAD_Q0=1; which one runs by default: kWx4DefaultFeed): the same loop fed differently.
+// (a) Thread t of the wide waves (t = tid) and of the narrow ones (t = tid - 256) owns unit (column octet t / nquad, row quad t mod nquad): neighbouring lanes read
+//     neighbouring 16-byte pieces of ONE column (a part's share of a column, 768-832 bytes, is one run of 48-52 lanes) where FEED 0 puts lanes 0..3 on four columns.
+// (b) Threads past the last unit own nothing: they load out of range (no memory request) and write into a dump line nobody reads, where FEED 0 has them repeat a unit.
+// (c) The image has no padding: row r = 16 T + 4 a + b (tile T, quad a, row b of the quad), k-octet o, is the 16-byte slot
+//         256 (4 T + a) + 64 ((b + a) & 3) + 16 (o ^ (-a & 3) ^ (T & 1))        [bytes from the operand's region of a plane]
+//     -- a quad of rows is one 256-byte line, the row inside the line rotated by the quad, the octet XORed with the quad and the tile's parity.  Reads: ds_read_b128 is
+//     served in the four lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ... (quads a = 0, 3 of octet o with quads 1, 2 of octet o ^ 1): the XOR gives the four (a, o)
+//     of a group four different slots of a 64-byte row, the rotation puts a quad's four rows on the four 64-byte quarters of the 256-byte bank row: conflict-free (the
+//     80-byte stride of FEED 0 is 2-way in these groups).  Writes: ds_write_b128 is served in eight groups of eight neighbouring lanes over 32 banks; a group is quads
+//     a = 0..3 of two neighbouring tiles at one octet and one b: (b + a) & 1 splits them over the two 64-byte halves, o ^ (-a & 3) ^ (T & 1) over the four slots of a half:
+//     conflict-free (where a group straddles two octets, too, unless the part has an even number of tiles -- then no group straddles).
+// A plane is [208 wide rows | dump line | 112 narrow rows | dump line] x 64 bytes, ONE plane stride for both operands (an immediate of the LDS writes).
+constexpr int kWx4fRowShorts = 32;
+constexpr int kWx4fWideShorts = (kWx4TallRows + 4) * kWx4fRowShorts;                   // the narrow operand's region starts here
+constexpr int kWx4fPlane = (kWx4TallRows + 4 + kWxNarrowRows + 4) * kWx4fRowShorts;     // 10,496 bf16
+constexpr int kWx4fImageShorts = 3 * kWx4fPlane;
+constexpr size_t kWx4fLdsBytes = (size_t)2 * kWx4fImageShorts * 2;   // 125,952 bytes: two images
+constexpr int kWx4DefaultFeed = 1;      // bit-identical (tests/test_gpu_wgrad_feed.py) and 11 % faster per launch (profiles/wgrad_feed_probe.csv)
 
-template <bool TALL_IS_Z>
+template <bool TALL_IS_Z, int FEED>
 __global__ __launch_bounds__(448) void rnde_wgrad4x_kernel(const EvalDesc* __restrict__ evals, int n_evals, int per_chunk, int n_chunks, int M, int Nx, int Bpad,
                                                            float* __restrict__ slab) {
     constexpr int KC = 32;
@@ -209,24 +228,55 @@ __global__ __launch_bounds__(448) void rnde_wgrad4x_kernel(const EvalDesc* __res
 
     // ---- units: FOUR consecutive rows x EIGHT consecutive columns of one operand per thread, i.e. eight 16-byte loads (one per column: the operands are
     // rows-contiguous) where the half form issues 24 four-byte ones -- a wave's load instruction costs the texture path the same 16 cycles whatever its width.
-    // Waves 0..3 split the wide operand (unit = tid mod nrow: quad tid >> 2 of the part's rows, column octet tid & 3), waves 4..6 the narrow one (unit =
-    // (tid - 256) mod 112); which operand is WAVE-uniform (one buffer descriptor per wave, scalar selects), threads past the last unit repeat an earlier one
-    // (same source, destination and values): the loop body has no branch of either kind.  Lane -> (quad, octet) makes the 16 lanes of a b128 LDS write cover
-    // the 64 banks exactly once (row stride 80 bytes: bank 20 r; 4 rows of a quad apart 16 banks, octets 4 banks).  Rows past the operand's end are the
+    // Waves 0..3 split the wide operand, waves 4..6 the narrow one; which operand is WAVE-uniform (one buffer descriptor per wave, scalar selects) and the loop
+    // body has no branch of either kind.  FEED 0 ONLY: unit = tid mod nrow (quad tid >> 2 of the part's rows, column octet tid & 3) / (tid - 256) mod 112, threads
+    // past the last unit repeat an earlier one (same source, destination and values); lane -> (quad, octet) was chosen for the b128 LDS writes of the 80-byte row
+    // stride (bank 20 r; 4 rows of a quad apart 16 banks, octets 4 banks).  FEED 1: unit, idle threads and image as in the header above.  Rows past the operand's end are the
     // synthetic {t, 1, 0, 0} quad or zeros: their loads are out of the descriptor's range (they return 0) and the values come from two per-thread constants.
     constexpr unsigned kNoSrc = 0x7FFFFF00u;
     const bool wide_wave = w < 4;
     const int Rp = wide_wave ? TRp : SRp;                                        // rows of this wave's operand in memory = its column stride
     const int nunit = wide_wave ? nrow : kWxNarrowRows;                          // 4 octets x (rows / 4) quads
-    const int uid = (wide_wave ? tid : tid - 256) % nunit;
-    const int uq = uid >> 2, uo = uid & 3;
-    const int u_gr = (wide_wave ? row_lo : 0) + 4 * uq;
-    const bool u_mem = u_gr < Rp;
+    const int ut = wide_wave ? tid : tid - 256;
+    const int nquad = nunit >> 2;
+    const bool u_real = ut < nunit;                                              // (FEED 1: the others own nothing)
+    const int uid = ut % nunit;
+    const int uq = FEED ? uid % nquad : uid >> 2, uo = FEED ? uid / nquad : uid & 3;
+#if RNDE_WX4_ABL == 7      // (timing ablation: FEED 1's loads into FEED 0's destinations)
+    const int lq = uid % nquad, lo8 = uid / nquad;
+#else
+    const int lq = uq, lo8 = uo;                                                 // (the unit that is loaded is the unit that is written)
+#endif
+    const int u_gr = (wide_wave ? row_lo : 0) + 4 * lq;
+#if RNDE_WX4_ABL == 8      // (timing ablation: no repeated units in FEED 0)
+    const bool u_mem = u_gr < Rp && u_real;
+#else
+    const bool u_mem = u_gr < Rp && (FEED == 0 || u_real);
+#endif
     const bool u_syn = u_gr == Rp && (wide_wave ? !TALL_IS_Z : TALL_IS_Z);     // the quad {t, 1, 0, 0}
     const float syn_f = u_syn ? 1.f : 0.f;
-    const unsigned u_voff = u_mem ? 4u * (unsigned)(u_gr + 8 * uo * Rp) : kNoSrc;
+    const unsigned u_voff = u_mem ? 4u * (unsigned)(u_gr + 8 * lo8 * Rp) : kNoSrc;
+#if RNDE_WX4_ABL == 8
+    const int u_dst = (wide_wave ? 0 : 3 * kWx4PlaneT) + 4 * uq * kWxRowShorts + (u_real ? 8 * uo : 32);      // (the padding of the unit's own rows)
+#else
     const int u_dst = (wide_wave ? 0 : 3 * kWx4PlaneT) + 4 * uq * kWxRowShorts + 8 * uo;
+#endif
     const int u_ps = wide_wave ? kWx4PlaneT : kWx4PlaneS;
+    // FEED 1: the slot of row b of the thread's quad (header above), one offset per b.  A thread without a unit takes the dump line behind its operand's region, at the
+    // slot its lane would have in a real line (quad lane & 3, tile parity lane >> 2, octet 0): the eight lanes of a write group on eight different slots there too.
+    int f_dst[4] = {0, 0, 0, 0};
+    // the fragment reads' per-lane offsets: row 16 T + mrow, octet kk -> [T & 1] + 512 T (+ the narrow region)
+    int f_frag[2] = {0, 0};
+    if (FEED) {
+        const int qa = u_real ? uq & 3 : lane & 3, qt = u_real ? (uq >> 2) & 1 : (lane >> 2) & 1, qo = u_real ? uo : 0;
+        const int line = (wide_wave ? 0 : kWx4fWideShorts) + 128 * (u_real ? uq : wide_wave ? kWx4TallRows / 4 : kWxNarrowRows / 4);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) f_dst[b] = line + 32 * ((b + qa) & 3) + 8 * ((qo ^ (4 - qa) ^ qt) & 3);
+        const int fa = mrow >> 2;
+        f_frag[0] = 128 * fa + 32 * ((mrow + fa) & 3) + 8 * ((kk ^ (4 - fa)) & 3);
+        f_frag[1] = f_frag[0] ^ 8;
+    }
+    const int f_a0 = f_frag[w & 1] + 512 * w, f_a1 = f_frag[tile1 & 1] + 512 * tile1;      // the wave's two wide tiles
     // (evaluation, 32-column step in it) of the next step to fetch; past the chunk's last step the last one is fetched again (harmless, never written to LDS)
     int e_nx = s_lo / steps_per_eval, cs_nx = s_lo - e_nx * steps_per_eval, left = total_steps;
     // two register sets: the set a step's splitting reads was requested a step and a half earlier (the operands are read once, cold from HBM: with ONE set,
@@ -267,18 +317,19 @@ __global__ __launch_bounds__(448) void rnde_wgrad4x_kernel(const EvalDesc* __res
 #pragma unroll
         for (int j = 0; j < 4; ++j) x3_split2(v[2 * j], v[2 * j + 1], hi[j], mid[j], lo[j]);
 #endif
-        unsigned short* d = img + u_dst + i * kWxRowShorts;
+        unsigned short* d = FEED ? img + f_dst[i] : img + u_dst + i * kWxRowShorts;
+        const int ps = FEED ? kWx4fPlane : u_ps;
 #if RNDE_WX4_ABL == 5      // (timing ablation: the split without its LDS writes -- the planes are folded into a register the epilogue stores)
         abl_sink ^= hi[0] ^ hi[1] ^ hi[2] ^ hi[3] ^ mid[0] ^ mid[1] ^ mid[2] ^ mid[3] ^ lo[0] ^ lo[1] ^ lo[2] ^ lo[3];
         (void)d;
 #else
         *(x3u4*)d = (x3u4){hi[0], hi[1], hi[2], hi[3]};
-        *(x3u4*)(d + u_ps) = (x3u4){mid[0], mid[1], mid[2], mid[3]};
-        *(x3u4*)(d + 2 * u_ps) = (x3u4){lo[0], lo[1], lo[2], lo[3]};
+        *(x3u4*)(d + ps) = (x3u4){mid[0], mid[1], mid[2], mid[3]};
+        *(x3u4*)(d + 2 * ps) = (x3u4){lo[0], lo[1], lo[2], lo[3]};
 #endif
     };
     unsigned short* const img0 = wxs;
-    unsigned short* const img1 = wxs + kWx4ImageShorts;
+    unsigned short* const img1 = wxs + (FEED ? kWx4fImageShorts : kWx4ImageShorts);
     if (total_steps == 0) return;      // (workgroup-uniform; the slab of such a chunk is never read: the host counts chunks from the steps)
     typedef std::integral_constant<int, 0> S0;
     typedef std::integral_constant<int, 1> S1;
@@ -292,12 +343,18 @@ __global__ __launch_bounds__(448) void rnde_wgrad4x_kernel(const EvalDesc* __res
     // of the blocks n = 0..3, in ONE basic block with that block's twelve matrix instructions -- and the set is refilled behind them with the step after next
     auto one_step = [&](const unsigned short* cur, unsigned short* nxt, auto more_c, auto set_c) {
         constexpr bool MORE = decltype(more_c)::value;
-        const unsigned short* SPc = cur + 3 * kWx4PlaneT;
-        auto fragT = [&](int tile, int pl) { return *(const x3u4*)(cur + pl * kWx4PlaneT + (16 * tile + mrow) * kWxRowShorts + 8 * kk); };
-        auto fragS = [&](int tile, int pl) { return *(const x3u4*)(SPc + pl * kWx4PlaneS + (16 * tile + mrow) * kWxRowShorts + 8 * kk); };
+        const unsigned short* SPc = cur + (FEED ? kWx4fWideShorts : 3 * kWx4PlaneT);
+        auto fragT = [&](int i, int pl) {      // the wave's wide tile i < 2
+            if (FEED) return *(const x3u4*)(cur + pl * kWx4fPlane + (i ? f_a1 : f_a0));
+            return *(const x3u4*)(cur + pl * kWx4PlaneT + (16 * (i ? tile1 : w) + mrow) * kWxRowShorts + 8 * kk);
+        };
+        auto fragS = [&](int tile, int pl) {
+            if (FEED) return *(const x3u4*)(SPc + pl * kWx4fPlane + f_frag[tile & 1] + 512 * tile);
+            return *(const x3u4*)(SPc + pl * kWx4PlaneS + (16 * tile + mrow) * kWxRowShorts + 8 * kk);
+        };
         x3u4 a[2][3];
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) { a[0][pl] = fragT(w, pl); a[1][pl] = fragT(tile1, pl); }
+        for (int pl = 0; pl < 3; ++pl) { a[0][pl] = fragT(0, pl); a[1][pl] = fragT(1, pl); }
         x3u4 bh = fragS(0, 0), bm = fragS(0, 1), bl = fragS(0, 2);
 #pragma unroll
         for (int n = 0; n < 7; ++n) {

@@ -8,7 +8,7 @@ L=regneuralde.jl_amd/lib
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value -Wno-undefined-internal -Wno-pass-failed"
 /opt/rocm/bin/hipcc $F "$@" -c regneuralde.jl_amd/csrc/$SRC -o $L/obj/${SRC%.hip}_$NAME.o
 OBJS=""
-for o in rnde rnde_reverse rnde_stage_solve rnde_latent rnde_sde rnde_comm rnde_tapes; do
+for o in rnde rnde_reverse rnde_stage_solve rnde_latent rnde_sde rnde_comm rnde_tapes rnde_ffjord; do
   if [ "$o.hip" == "$SRC" ]; then OBJS="$OBJS $L/obj/${o}_$NAME.o"; else OBJS="$OBJS $L/obj/$o.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $L/librnde_$NAME.so $OBJS -ldl

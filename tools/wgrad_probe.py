@@ -1,5 +1,6 @@
 """A fixed reverse pass for timing the weight-gradient kernels under rocprofv3: one natural forward solve at the headline shape (B = 512, tol 1.4e-8, Glorot
-weights x 3), then `--reps` identical reverse passes -- the same evaluations in every library variant, whatever its gradients are worth (tools/gpu_wgrad_times.sh)."""
+weights x 3), then `--reps` identical reverse passes -- the same evaluations in every library variant, whatever its gradients are worth (tools/gpu_wgrad_times.sh).
+RNDE_X3_WGRAD_Q0=1 times the quarter form as first built (FEED 0); the ablation builds RNDE_WX4_ABL = 7 and 8 exist in that form only and always launch it."""
 import argparse
 import os
 import sys
