@@ -1,6 +1,5 @@
-// rnde_bffjordc.h -- the reverse sweep of rnde_ffjordc_solve_kernel: discretise-then-optimise through every Tsit5 stage of every accepted
-// step (step sizes and times constants; the saved value EEst * dt reaches the stages through EEst), the structure of rnde_bffjordt.h with
-// the Dense chain's arithmetic.
+// rnde_bffjordc.h -- the reverse of the Dense-chain dynamics on the tile layout: FcDyn::vjp, one stage's second-order VJP as
+// rnde_ffjord_tile.h's reverse sweep calls it.
 //
 // One stage, cotangent (lz, ll, l1, l2) of F = [f; -e . eJ; sum f^2; sum eJ^2] (plain sweep: l1 = l2 = 0), notation of rnde_ffjordc.h:
 //     lf = lz + 2 l1 f,   w = -ll e + 2 l2 eJ                                   (the cotangents of f and of eJ)
@@ -11,11 +10,9 @@
 //                    W_l-bar += a_l-bar y_{l-1}',  b_l-bar += a_l-bar,  wt_l-bar += t a_l-bar,  z-bar = y_0-bar
 // phi'' is taken from the layer's output like phi' (act_d2y).
 //
-// One workgroup per tile over every accepted step, no meeting.  The stages are recomputed from the taped uprev with the forward's own
-// evaluation (fc_eval, LDS).  The 5 n + 4 per-column vectors of the second-order reverse live in the tile's global buffer (written and read
-// by the same workgroup, L2-resident), as in rnde_bffjordt.h; no private scratch.  Every product runs on the matrix cores, the weight
-// cotangents through ft_wgrad (both outer products of a layer in one pass).  Parameter cotangents go to the tile's own row of
-// pacc ([ntiles][P], plain read-modify-write by one lane per entry); rnde_ffjordt_reduce_kernel sums the tiles in order in double.
+// The 5 n + 4 per-column vectors of the second-order reverse live in the tile's global buffer (written and read by the same workgroup,
+// L2-resident), as in rnde_bffjordt.h; no private scratch.  Every product runs on the matrix cores, the weight cotangents through ft_wgrad
+// (both outer products of a layer in one pass).
 #pragma once
 #include "rnde_bffjordt.h"     // ft_wgrad, FfStepRec, rnde_ffjordt_reduce_kernel
 #include "rnde_ffjordc.h"
@@ -23,30 +20,15 @@
 namespace rnde {
 
 __host__ __device__ inline int fc_vjp_vecs(const FcGeo& G) { return 5 * G.n + 4; }
-__host__ __device__ inline size_t fc_rev_ws_floats(const FcGeo& G, bool kin = false) {
+__host__ __device__ inline size_t FcDyn::rev_ws_floats(const FcGeo& G, bool kin) {
     const int R = G.D + (kin ? 3 : 1);
     return (size_t)24 * R * 16 + (size_t)fc_vjp_vecs(G) * G.MP * 16;
 }
 
-struct FcRevParams {
-    FcGeo G;
-    const float* p;
-    const float* e;                   // D x B caller layout
-    const float* tape;                // [n_acc + 1][R][Bp]
-    const FfStepRec* rec;             // [n_acc]
-    const float* logpx_bar;           // B
-    float* ws;                        // [ntiles][fc_rev_ws_floats]
-    float* pacc;                      // [ntiles][P]
-    float* x_bar;                     // D x B caller layout (may be NULL)
-    int n_acc, B, Bp;
-    float reltol, abstol;
-    const float* reg_bar;             // kinetic sweep: 2 x B cotangents of (lambda1, lambda2), or NULL (zeros)
-};
-
 // yb[0:D] += (dF/dz)' lam and pacc += (dF/dp)' lam for the tile's 16 columns.  z: the stage input ([R][16]), kb: its cotangent lam
 // ([R][16]), yb: [R][16], V: the tile's vector slots.  Ends behind a barrier.
-template <bool KIN = false>
-__device__ __forceinline__ void fc_vjp(const FcGeo& G, const FcLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid) {
+template <bool KIN>
+__device__ __forceinline__ void FcDyn::vjp(const FcGeo& G, const FcLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid) {
     const int lane = tid & 63, wave = tid >> 6, c = lane & 15, D = G.D, n = G.n, DP = G.DP;
     const size_t FS = (size_t)G.MP * 16;
     // slots: Y_0..Y_n | v_1..v_n | m_1..m_{n-1} (slot n unused) | m_0-bar (= w) .. m_{n-1}-bar | q_1..q_n (d_l-bar .* phi_l'') | a-bar x 2 | lf
@@ -157,104 +139,6 @@ __device__ __forceinline__ void fc_vjp(const FcGeo& G, const FcLds& L, float t, 
         __syncthreads();
         float* s = ab; ab = abn; abn = s;
     }
-}
-
-template <bool KIN>
-__global__ __launch_bounds__(kFtThreads) void rnde_ffjordc_reverse_kernel(const FcRevParams Q) {
-    extern __shared__ float ft_smem[];
-    const FcGeo& G = Q.G;
-    const int tile = blockIdx.x, tid = threadIdx.x, D = G.D, R = D + (KIN ? 3 : 1), Bp = Q.Bp, col0 = tile * 16, nel = R * 16;
-    const FcLds L = fc_lds(G, ft_smem);
-    fc_load_params(G, Q.p, L.W, tid);
-    for (int idx = tid; idx < G.DP * 16; idx += kFtThreads) {
-        const int r = idx >> 4, col = col0 + (idx & 15);
-        L.E[idx] = (r < D && col < Q.B) ? Q.e[(size_t)col * D + r] : 0.f;
-        L.X[idx] = 0.f;
-    }
-    float* ws = Q.ws + (size_t)tile * fc_rev_ws_floats(G, KIN);
-    const size_t RS = (size_t)R * 16;
-    auto Ys = [&](int s) { return ws + (size_t)s * RS; };
-    auto Ks = [&](int s) { return ws + (size_t)(7 + s) * RS; };
-    auto Kb = [&](int s) { return ws + (size_t)(14 + s) * RS; };
-    float *UB = ws + 21 * RS, *UBn = ws + 22 * RS, *Yb = ws + 23 * RS, *V = ws + 24 * RS;
-    float* pacc = Q.pacc + (size_t)tile * G.P;
-    for (int q = tid; q < G.P; q += kFtThreads) pacc[q] = 0.f;
-    const size_t RB = (size_t)R * Bp;
-    for (int idx = tid; idx < nel; idx += kFtThreads) {     // logpx = sum -(log 2 pi + z^2) / 2 - l
-        const int r = idx >> 4, c = idx & 15, col = col0 + c;
-        float v = 0.f;
-        if (col < Q.B) {
-            const float g = Q.logpx_bar[col];
-            v = r < D ? -g * Q.tape[(size_t)Q.n_acc * RB + (size_t)r * Bp + col] : -g;
-            if constexpr (KIN)
-                if (r > D) v = Q.reg_bar ? Q.reg_bar[(size_t)(r - D - 1) * Q.B + col] : 0.f;
-        }
-        UB[idx] = v;
-    }
-    __syncthreads();
-    const double N = (double)R * (double)Q.B;
-    for (int n = Q.n_acc - 1; n >= 0; --n) {
-        const FfStepRec st = Q.rec[n];
-        const float t = st.t, dt = st.dt;
-        const float* U = Q.tape + (size_t)n * RB + col0;
-        // ---- recompute the stages ----
-        for (int s = 0; s < 7; ++s) {
-            for (int idx = tid; idx < nel; idx += kFtThreads) {
-                const int r = idx >> 4, c = idx & 15;
-                float acc = 0.f;
-                for (int j = 0; j < s; ++j) acc = fmaf(tsA_rt(s, j), Ks(j)[idx], acc);
-                const float y = U[(size_t)r * Bp + c] + dt * acc;
-                Ys(s)[idx] = y;
-                if (r < D) L.X[idx] = y;
-            }
-            __syncthreads();
-            fc_eval<KIN>(G, L, t + kTsC[s] * dt, Ks(s), 16, 0, 1.f, -1.f, tid);
-        }
-        for (int idx = tid; idx < nel; idx += kFtThreads) {
-            for (int s = 0; s < 7; ++s) Kb(s)[idx] = 0.f;
-            UBn[idx] = 0.f;
-            Yb[idx] = UB[idx];                                // cotangent of unew = stage-7 input
-        }
-        // ---- A: reverse of the error estimate (the saved value EEst * dt; rnde_bffjord.h) ----
-        if (st.svb != 0.f && st.eest > 0.f) {
-            const float coef = (float)(((double)st.svb * (double)dt) / (N * (double)st.eest));
-            for (int idx = tid; idx < nel; idx += kFtThreads) {
-                if (col0 + (idx & 15) >= Q.B) continue;
-                float E = 0.f;
-                for (int j = 0; j < 7; ++j) E += kTsBt[j] * Ks(j)[idx];
-                const float up = U[(size_t)(idx >> 4) * Bp + (idx & 15)], un = Ys(6)[idx];
-                const float au = fabsf(up), an = fabsf(un);
-                const bool use_new = !(au > an);
-                const float sk = Q.abstol + (use_new ? an : au) * Q.reltol;
-                const float rr = dt * E / sk, rb = coef * rr, utb = rb / sk, skb = -rb * rr / sk;
-                for (int j = 0; j < 7; ++j) Kb(j)[idx] += dt * kTsBt[j] * utb;
-                if (use_new) Yb[idx] += skb * Q.reltol * (un > 0.f ? 1.f : (un < 0.f ? -1.f : 0.f));
-                else UBn[idx] += skb * Q.reltol * (up > 0.f ? 1.f : (up < 0.f ? -1.f : 0.f));
-            }
-        }
-        __syncthreads();
-        // ---- B: the stages, last to first ----
-        for (int s = 6; s >= 0; --s) {
-            if (s != 6) {
-                for (int idx = tid; idx < nel; idx += kFtThreads) Yb[idx] = 0.f;
-                __syncthreads();
-            }
-            fc_vjp<KIN>(G, L, t + kTsC[s] * dt, Ys(s), Kb(s), Yb, V, pacc, tid);
-            for (int idx = tid; idx < nel; idx += kFtThreads) {
-                const float y = Yb[idx];
-                UBn[idx] += y;
-                for (int j = 0; j < s; ++j) Kb(j)[idx] += dt * tsA_rt(s, j) * y;
-            }
-            __syncthreads();
-        }
-        for (int idx = tid; idx < nel; idx += kFtThreads) UB[idx] = UBn[idx];
-        __syncthreads();
-    }
-    if (Q.x_bar)
-        for (int idx = tid; idx < nel; idx += kFtThreads) {
-            const int r = idx >> 4, col = col0 + (idx & 15);
-            if (r < D && col < Q.B) Q.x_bar[(size_t)col * D + r] = UB[idx];
-        }
 }
 
 }  // namespace rnde

@@ -1,14 +1,9 @@
-// rnde_bffjordt.h -- the reverse sweep of rnde_ffjordt_solve_kernel: what rnde_bffjord.h differentiates (discretise-then-optimise through every
-// Tsit5 stage of every accepted step, step sizes and times constants: track_ctrl = track_initdt = 0; the saved value EEst * dt reaches the
-// stages through EEst), with the tiled engine's geometry.
+// rnde_bffjordt.h -- the reverse of the ConcatSquash dynamics on the tile layout: FtDyn::vjp, one stage's second-order VJP as
+// rnde_ffjord_tile.h's reverse sweep calls it, and what that sweep shares with the Dense-chain dynamics (ft_wgrad, the reduce kernel).
 //
-// One workgroup per 16-column tile, every accepted step in one launch, no meeting: once the step log is fixed no column depends on another,
-// and the EEst values come from the step log.  The stage values are recomputed from the taped uprev with the forward's own evaluation
-// (rnde_ffjordt.h ft_eval, activations in LDS).  The second-order VJP of a stage needs some 27 per-column vectors; next to the resident
-// weights they do not fit in LDS at the tabular widths, so they live in a per-tile global buffer (written and read by the same workgroup,
-// L2-resident); no private scratch.  Every product, the weight cotangents included (outer products over the tile's 16 columns, k = 2 x 16),
-// runs on the matrix cores.  Parameter cotangents accumulate in the tile's own row of pacc ([ntiles][P], plain read-modify-write by one lane
-// per entry, no atomics); rnde_ffjordt_reduce_kernel sums the tiles in tile order in double.
+// The second-order VJP of a stage needs some 27 per-column vectors; next to the resident weights they do not fit in LDS at the tabular
+// widths, so they live in a per-tile global buffer (written and read by the same workgroup, L2-resident); no private scratch.  Every
+// product, the weight cotangents included (outer products over the tile's 16 columns, k = 2 x 16), runs on the matrix cores.
 //
 // Kinetic variant (KIN; the arithmetic of rnde_bffjord.h): the stage cotangent is (lz, ll, l1, l2) over R = D + 3 rows.  The cotangent of f,
 // lz + 2 l1 f, is formed in the epilogue of the layer-3 product; w = -ll e + 2 l2 eJ needs eJ = W1' v1, one more transposed product once v1
@@ -22,22 +17,7 @@ namespace rnde {
 constexpr int kFtVjpVecs = 27;
 constexpr int kFtVjpVecsKin = 28;      // + w (the cotangent of eJ)
 
-struct FtRevParams {
-    FtGeo G;
-    const float* p;
-    const float* e;                   // D x B caller layout
-    const float* tape;                // [n_acc + 1][R][Bp]
-    const FfStepRec* rec;             // [n_acc]
-    const float* logpx_bar;           // B
-    float* ws;                        // [ntiles][ft_rev_ws_floats]
-    float* pacc;                      // [ntiles][P]
-    float* x_bar;                     // D x B caller layout (may be NULL)
-    int n_acc, B, Bp;
-    float reltol, abstol;
-    const float* reg_bar;             // kinetic sweep: 2 x B cotangents of (lambda1, lambda2), or NULL (zeros)
-};
-
-__host__ __device__ inline size_t ft_rev_ws_floats(const FtGeo& G, bool kin = false) {
+__host__ __device__ inline size_t FtDyn::rev_ws_floats(const FtGeo& G, bool kin) {
     const int R = G.D + (kin ? 3 : 1), FP = G.HP > G.DP ? G.HP : G.DP;
     return (size_t)24 * R * 16 + (size_t)(kin ? kFtVjpVecsKin : kFtVjpVecs) * FP * 16;
 }
@@ -67,8 +47,8 @@ __device__ __forceinline__ void ft_wgrad(const float* A1, const float* B1, const
 // yb[0:D] += (dF/dz)' lam and pacc += (dF/dp)' lam for the tile's 16 columns, F = [f(z, t); -e . eJ], lam = (lz; ll) = kb.
 // z: the stage input ([R][16]), kb: its cotangent ([R][16]), yb: [R][16], V: the tile's vector slots.  Ends behind a barrier.
 // KIN: F = [f; -e . eJ; sum f^2; sum eJ^2], lam = (lz; ll; l1; l2).
-template <bool KIN = false>
-__device__ __forceinline__ void ft_vjp(const FtGeo& G, const FtLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid) {
+template <bool KIN>
+__device__ __forceinline__ void FtDyn::vjp(const FtGeo& G, const FtLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid) {
     const int lane = tid & 63, wave = tid >> 6, c = lane & 15, D = G.D, H = G.H, HP = G.HP, DP = G.DP;
     const int FP = HP > DP ? HP : DP;
     auto vec = [&](int k) { return V + (size_t)k * FP * 16; };
@@ -230,103 +210,6 @@ __device__ __forceinline__ void ft_vjp(const FtGeo& G, const FtLds& L, float t, 
         pv[3 * out + o] += s * ff_dsig(gs) * t;
     }
     __syncthreads();
-}
-
-template <bool KIN>
-__global__ __launch_bounds__(kFtThreads) void rnde_ffjordt_reverse_kernel(const FtRevParams Q) {
-    extern __shared__ float ft_smem[];
-    const FtGeo& G = Q.G;
-    const int tile = blockIdx.x, tid = threadIdx.x, D = G.D, R = D + (KIN ? 3 : 1), Bp = Q.Bp, col0 = tile * 16, nel = R * 16;
-    const FtLds L = ft_lds(G, ft_smem);
-    ft_load_params(G, Q.p, L.W, tid);
-    for (int idx = tid; idx < G.DP * 16; idx += kFtThreads) {
-        const int r = idx >> 4, col = col0 + (idx & 15);
-        L.E[idx] = (r < D && col < Q.B) ? Q.e[(size_t)col * D + r] : 0.f;
-        L.X[idx] = 0.f;
-    }
-    float* ws = Q.ws + (size_t)tile * ft_rev_ws_floats(G, KIN);
-    const size_t RS = (size_t)R * 16;
-    auto Ys = [&](int s) { return ws + (size_t)s * RS; };
-    auto Ks = [&](int s) { return ws + (size_t)(7 + s) * RS; };
-    auto Kb = [&](int s) { return ws + (size_t)(14 + s) * RS; };
-    float *UB = ws + 21 * RS, *UBn = ws + 22 * RS, *Yb = ws + 23 * RS, *V = ws + 24 * RS;
-    float* pacc = Q.pacc + (size_t)tile * G.P;
-    for (int q = tid; q < G.P; q += kFtThreads) pacc[q] = 0.f;
-    const size_t RB = (size_t)R * Bp;
-    for (int idx = tid; idx < nel; idx += kFtThreads) {     // logpx = sum -(log 2 pi + z^2) / 2 - l
-        const int r = idx >> 4, c = idx & 15, col = col0 + c;
-        float v = 0.f;
-        if (col < Q.B) {
-            const float g = Q.logpx_bar[col];
-            v = r < D ? -g * Q.tape[(size_t)Q.n_acc * RB + (size_t)r * Bp + col] : -g;
-            if constexpr (KIN)
-                if (r > D) v = Q.reg_bar ? Q.reg_bar[(size_t)(r - D - 1) * Q.B + col] : 0.f;
-        }
-        UB[idx] = v;
-    }
-    __syncthreads();
-    const double N = (double)R * (double)Q.B;
-    for (int n = Q.n_acc - 1; n >= 0; --n) {
-        const FfStepRec st = Q.rec[n];
-        const float t = st.t, dt = st.dt;
-        const float* U = Q.tape + (size_t)n * RB + col0;
-        // ---- recompute the stages ----
-        for (int s = 0; s < 7; ++s) {
-            for (int idx = tid; idx < nel; idx += kFtThreads) {
-                const int r = idx >> 4, c = idx & 15;
-                float acc = 0.f;
-                for (int j = 0; j < s; ++j) acc = fmaf(tsA_rt(s, j), Ks(j)[idx], acc);
-                const float y = U[(size_t)r * Bp + c] + dt * acc;
-                Ys(s)[idx] = y;
-                if (r < D) L.X[idx] = y;
-            }
-            ft_eval<KIN>(G, L, t + kTsC[s] * dt, Ks(s), 16, 0, 1.f, -1.f, nullptr, tid);
-        }
-        for (int idx = tid; idx < nel; idx += kFtThreads) {
-            for (int s = 0; s < 7; ++s) Kb(s)[idx] = 0.f;
-            UBn[idx] = 0.f;
-            Yb[idx] = UB[idx];                                // cotangent of unew = stage-7 input
-        }
-        // ---- A: reverse of the error estimate (the saved value EEst * dt; rnde_bffjord.h) ----
-        if (st.svb != 0.f && st.eest > 0.f) {
-            const float coef = (float)(((double)st.svb * (double)dt) / (N * (double)st.eest));
-            for (int idx = tid; idx < nel; idx += kFtThreads) {
-                if (col0 + (idx & 15) >= Q.B) continue;
-                float E = 0.f;
-                for (int j = 0; j < 7; ++j) E += kTsBt[j] * Ks(j)[idx];
-                const float up = U[(size_t)(idx >> 4) * Bp + (idx & 15)], un = Ys(6)[idx];
-                const float au = fabsf(up), an = fabsf(un);
-                const bool use_new = !(au > an);
-                const float sk = Q.abstol + (use_new ? an : au) * Q.reltol;
-                const float rr = dt * E / sk, rb = coef * rr, utb = rb / sk, skb = -rb * rr / sk;
-                for (int j = 0; j < 7; ++j) Kb(j)[idx] += dt * kTsBt[j] * utb;
-                if (use_new) Yb[idx] += skb * Q.reltol * (un > 0.f ? 1.f : (un < 0.f ? -1.f : 0.f));
-                else UBn[idx] += skb * Q.reltol * (up > 0.f ? 1.f : (up < 0.f ? -1.f : 0.f));
-            }
-        }
-        __syncthreads();
-        // ---- B: the stages, last to first ----
-        for (int s = 6; s >= 0; --s) {
-            if (s != 6) {
-                for (int idx = tid; idx < nel; idx += kFtThreads) Yb[idx] = 0.f;
-                __syncthreads();
-            }
-            ft_vjp<KIN>(G, L, t + kTsC[s] * dt, Ys(s), Kb(s), Yb, V, pacc, tid);
-            for (int idx = tid; idx < nel; idx += kFtThreads) {
-                const float y = Yb[idx];
-                UBn[idx] += y;
-                for (int j = 0; j < s; ++j) Kb(j)[idx] += dt * tsA_rt(s, j) * y;
-            }
-            __syncthreads();
-        }
-        for (int idx = tid; idx < nel; idx += kFtThreads) UB[idx] = UBn[idx];
-        __syncthreads();
-    }
-    if (Q.x_bar)
-        for (int idx = tid; idx < nel; idx += kFtThreads) {
-            const int r = idx >> 4, col = col0 + (idx & 15);
-            if (r < D && col < Q.B) Q.x_bar[(size_t)col * D + r] = UB[idx];
-        }
 }
 
 // p_bar[q] = sum over tiles of pacc[tile][q], in tile order, carried in double

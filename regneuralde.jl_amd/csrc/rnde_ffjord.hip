@@ -1,8 +1,9 @@
 // rnde_ffjord.hip -- C ABI of TrackedFFJORD (include/rnde.h, "TrackedFFJORD" section): create / forward / replay / backward / sample
-// over the kernels of rnde_ffjord.h (one-launch solve) and rnde_bffjord.h (one-launch reverse sweep), or, on a handle made by
-// rnde_ffjord_create_tiled, over those of rnde_ffjordt.h / rnde_bffjordt.h (the tiled engine).  The *_kinetic entries run the KIN = true
-// instantiations of the same kernels over D + 3 rows (TrackedFFJORD{false} called with regularize = true).  A handle made by
-// rnde_ffjord_create_chain (engine 2) runs the Dense-chain dynamics of rnde_ffjordc.h / rnde_bffjordc.h on the tiled layout.
+// over the kernels of rnde_ffjord.h (one-launch solve) and rnde_bffjord.h (one-launch reverse sweep), or, on a handle of the tile layout,
+// over the tile driver of rnde_ffjord_tile.h: rnde_ffjord_create_tiled (engine 1) runs it with the ConcatSquash dynamics FtDyn
+// (rnde_ffjordt.h / rnde_bffjordt.h), rnde_ffjord_create_chain (engine 2) with the Dense-chain dynamics FcDyn (rnde_ffjordc.h /
+// rnde_bffjordc.h).  The *_kinetic entries run the KIN = true instantiations of the same kernels over D + 3 rows (TrackedFFJORD{false}
+// called with regularize = true).
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -11,6 +12,7 @@
 #include "rnde_bffjord.h"
 #include "rnde_bffjordt.h"
 #include "rnde_bffjordc.h"
+#include "rnde_ffjord_tile.h"
 
 using namespace rnde;
 
@@ -45,11 +47,11 @@ struct rnde_ffjord {
     float* e_tape = nullptr;         // the library's probe of a taped forward (e_buf serves untaped calls)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float fwd_ms = -1.f, rev_ms = -1.f;
-    // the tiled engine (engine = 1): one workgroup per 16 columns, the workgroups meeting once per attempt
+    // the tile layout (engine = 1, 2): one workgroup per 16 columns, the workgroups meeting once per attempt
     int engine = 0;
     FtGeo TG{};
     int ntiles_max = 0;
-    float* qt = nullptr;             // [ntiles][HP][HP]: the exact trace's matrix, per tile
+    float* qt = nullptr;             // engine = 1: [ntiles][HP][HP], the exact trace's matrix per tile (the driver's scratch)
     InitRec* initrec_t = nullptr;    // [ntiles] (initrec = initrec_t)
     StepState* ctl_t = nullptr;      // [ntiles]
     unsigned long long* xch = nullptr;
@@ -58,7 +60,7 @@ struct rnde_ffjord {
     unsigned epoch = 0;
     int xcd_slot = 0;
     std::vector<unsigned> h_chk;     // abort word, then each tile's XCC
-    FcGeo CG{};                      // engine = 2: the Dense-chain dynamics on the tiled layout (cfg holds the shared fields, in_dims = D)
+    FcGeo CG{};                      // engine = 2: the Dense-chain dynamics on the tile layout (cfg holds the shared fields, in_dims = D)
 };
 
 #define FCHK(h, x)                                                                                  \
@@ -98,24 +100,17 @@ static const char* ff_refusal(const rnde_ffjord_config* c, bool tiled = false) {
     return nullptr;
 }
 
-// The tiled engine's buffers and kernel attributes (the config is validated).
-static rnde_status ft_create(const rnde_ffjord_config* c, rnde_ffjord** out) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= c->device) { g_ff_create_err = "no HIP device"; return RNDE_ERR_NO_DEVICE; }
-    if (hipSetDevice(c->device) != hipSuccess) { g_ff_create_err = "hipSetDevice failed"; return RNDE_ERR_NO_DEVICE; }
-    rnde_ffjord* h = new rnde_ffjord();
-    h->cfg = *c;
-    h->engine = 1;
-    h->G = ff_geo(c->in_dims, c->hidden);
-    h->TG = ft_geo(c->in_dims, c->hidden);
-    const FtGeo& G = h->TG;
-    const int D = c->in_dims, R = D + 1;
+// The buffers, kernel attributes and XCD slot of a handle of the tile layout, for the dynamics Dyn with geometry G (h->cfg is filled; on
+// failure the handle is destroyed).
+template <class Dyn>
+static rnde_status tile_create(rnde_ffjord* h, const typename Dyn::Geo& G, rnde_ffjord** out) {
+    const rnde_ffjord_config* c = &h->cfg;
+    const int D = G.D, R = D + 1;
     h->R = R;
     h->ntiles_max = (c->max_batch + 15) / 16;
     h->Bp = 16 * h->ntiles_max;
     h->T = kFtThreads;
-    h->lds_bytes = (size_t)ft_lds_floats(G) * 4;
-    if (h->lds_bytes > (size_t)kFtLdsBytes) { g_ff_create_err = "TrackedFFJORD tiled engine: a tile does not fit in LDS"; delete h; return RNDE_ERR_BAD_ARG; }
+    h->lds_bytes = (size_t)Dyn::lds_floats(G) * 4;
     auto fail = [&](hipError_t e) { g_ff_create_err = std::string("HIP: ") + hipGetErrorString(e); rnde_ffjord_destroy(h); return RNDE_ERR_HIP; };
     hipError_t e;
     const size_t RB = (size_t)R * h->Bp, MA = (size_t)c->max_attempts, NT = (size_t)h->ntiles_max;
@@ -127,9 +122,9 @@ static rnde_status ft_create(const rnde_ffjord_config* c, rnde_ffjord** out) {
     if ((e = hipMalloc(&h->e_buf, (size_t)D * h->Bp * 4)) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&h->e_tape, (size_t)D * h->Bp * 4)) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&h->replay, 2 * MA * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->rws, NT * ft_rev_ws_floats(G) * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&h->rws, NT * Dyn::rev_ws_floats(G) * 4)) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&h->pacc, NT * G.P * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->qt, NT * G.HP * G.HP * 4)) != hipSuccess) return fail(e);
+    if (Dyn::scratch_floats(G) && (e = hipMalloc(&h->qt, NT * Dyn::scratch_floats(G) * 4)) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&h->ctl, 3 * sizeof(StepState))) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&h->ctl_t, NT * sizeof(StepState))) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&h->meta, MA * sizeof(StepMeta))) != hipSuccess) return fail(e);
@@ -141,22 +136,42 @@ static rnde_status ft_create(const rnde_ffjord_config* c, rnde_ffjord** out) {
     if ((e = hipMalloc(&h->xcc, kMwMeetMax * 4)) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&h->abort_word, 8)) != hipSuccess) return fail(e);
     if ((e = hipMemset(h->abort_word, 0, 8)) != hipSuccess) return fail(e);
-    for (const void* k : {(const void*)rnde_ffjordt_solve_kernel<false>, (const void*)rnde_ffjordt_reverse_kernel<false>,
-                          (const void*)rnde_ffjordt_feval_kernel<false>, (const void*)rnde_ffjordt_solve_kernel<true>,
-                          (const void*)rnde_ffjordt_reverse_kernel<true>, (const void*)rnde_ffjordt_feval_kernel<true>})
+    for (const void* k : {(const void*)rnde_ffjord_tile_solve_kernel<Dyn, false>, (const void*)rnde_ffjord_tile_reverse_kernel<Dyn, false>,
+                          (const void*)rnde_ffjord_tile_feval_kernel<Dyn, false>, (const void*)rnde_ffjord_tile_solve_kernel<Dyn, true>,
+                          (const void*)rnde_ffjord_tile_reverse_kernel<Dyn, true>, (const void*)rnde_ffjord_tile_feval_kernel<Dyn, true>})
         if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes)) != hipSuccess) return fail(e);
     for (auto& v : h->ev) if ((e = hipEventCreate(&v)) != hipSuccess) return fail(e);
-    { static std::atomic<int> next_slot{0}; h->xcd_slot = next_slot.fetch_add(1) & 7; }
+    { static std::atomic<int> next_slot{0}; h->xcd_slot = next_slot.fetch_add(1) & 7; }      // (one counter per dynamics: each deals its handles round the XCDs)
     h->h_chk.assign(2 + kMwMeetMax, 0u);
     *out = h;
     return RNDE_OK;
+}
+
+// A handle on the selected device, or NULL with the create error set.
+static rnde_ffjord* ff_new_handle(int device, rnde_status* st) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) { g_ff_create_err = "no HIP device"; *st = RNDE_ERR_NO_DEVICE; return nullptr; }
+    if (hipSetDevice(device) != hipSuccess) { g_ff_create_err = "hipSetDevice failed"; *st = RNDE_ERR_NO_DEVICE; return nullptr; }
+    return new rnde_ffjord();
 }
 
 extern "C" rnde_status rnde_ffjord_create_tiled(const rnde_ffjord_config* c, rnde_ffjord** out) {
     if (!c || !out) { g_ff_create_err = "null argument"; return RNDE_ERR_BAD_ARG; }
     *out = nullptr;
     if (const char* why = ff_refusal(c, true)) { g_ff_create_err = why; return RNDE_ERR_BAD_ARG; }
-    return ft_create(c, out);
+    rnde_status st = RNDE_OK;
+    rnde_ffjord* h = ff_new_handle(c->device, &st);
+    if (!h) return st;
+    h->cfg = *c;
+    h->engine = 1;
+    h->G = ff_geo(c->in_dims, c->hidden);
+    h->TG = ft_geo(c->in_dims, c->hidden);
+    if ((size_t)FtDyn::lds_floats(h->TG) * 4 > (size_t)kFtLdsBytes) {
+        g_ff_create_err = "TrackedFFJORD tiled engine: a tile does not fit in LDS";
+        delete h;
+        return RNDE_ERR_BAD_ARG;
+    }
+    return tile_create<FtDyn>(h, h->TG, out);
 }
 
 extern "C" int32_t rnde_ffjord_engine(const rnde_ffjord* h) { return h ? h->engine : -1; }
@@ -201,7 +216,7 @@ static const char* fc_refusal(const rnde_ffjord_chain_config* c) {
         return "TrackedFFJORD chain dynamics: max_batch above 4096 is not served (one meeting holds kMwMeetMax = 256 resident tiles of 16 columns)";
     if (c->max_attempts > kFtMaxAttempts) return "TrackedFFJORD chain dynamics: max_attempts above 8000 is not served (meeting tags)";
     const FcGeo G = fc_geo(n, c->dims, c->act, td);
-    const size_t need = (size_t)fc_lds_floats(G) * 4;
+    const size_t need = (size_t)FcDyn::lds_floats(G) * 4;
     if (need > (size_t)kFtLdsBytes) {
         msg = "TrackedFFJORD chain dynamics: the resident weights and the activations of a tile need " + std::to_string(need) +
               " bytes of LDS, above the limit of " + std::to_string(kFtLdsBytes) + " bytes (160 KB)";
@@ -214,59 +229,20 @@ extern "C" rnde_status rnde_ffjord_create_chain(const rnde_ffjord_chain_config* 
     if (!c || !out) { g_ff_create_err = "null argument"; return RNDE_ERR_BAD_ARG; }
     *out = nullptr;
     if (const char* why = fc_refusal(c)) { g_ff_create_err = why; return RNDE_ERR_BAD_ARG; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= c->device) { g_ff_create_err = "no HIP device"; return RNDE_ERR_NO_DEVICE; }
-    if (hipSetDevice(c->device) != hipSuccess) { g_ff_create_err = "hipSetDevice failed"; return RNDE_ERR_NO_DEVICE; }
-    rnde_ffjord* h = new rnde_ffjord();
+    rnde_status st = RNDE_OK;
+    rnde_ffjord* h = ff_new_handle(c->device, &st);
+    if (!h) return st;
     h->engine = 2;
     h->CG = fc_geo(c->n_layers, c->dims, c->act, c->time_dep);
-    const FcGeo& G = h->CG;
-    const int D = G.D, R = D + 1;
+    const int D = h->CG.D;
     rnde_ffjord_config& k = h->cfg;        // the fields the shared entries read
     k = rnde_ffjord_config{};
     k.in_dims = D; k.hidden = 0; k.dynamics = RNDE_FFJORD_TRACKER_FORWARD; k.time_dep = c->time_dep; k.regularize = c->regularize;
     k.max_batch = c->max_batch; k.solver = c->solver; k.reltol = c->reltol; k.abstol = c->abstol; k.cb_save_start = c->cb_save_start;
     k.max_attempts = c->max_attempts; k.device = c->device;
     h->G = FfGeo{};
-    h->G.D = D; h->G.H = 0; h->G.P = G.P;
-    h->R = R;
-    h->ntiles_max = (c->max_batch + 15) / 16;
-    h->Bp = 16 * h->ntiles_max;
-    h->T = kFtThreads;
-    h->lds_bytes = (size_t)fc_lds_floats(G) * 4;
-    auto fail = [&](hipError_t e) { g_ff_create_err = std::string("HIP: ") + hipGetErrorString(e); rnde_ffjord_destroy(h); return RNDE_ERR_HIP; };
-    hipError_t e;
-    const size_t RB = (size_t)R * h->Bp, MA = (size_t)c->max_attempts, NT = (size_t)h->ntiles_max;
-    const size_t xb = (MA + 4) * 3 * kMwMeetMax * 8;
-    if ((e = hipMalloc(&h->ws, 10 * RB * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->tape, (MA + 1) * RB * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->norm, (8 * NT + 512) * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMemset(h->norm, 0, (8 * NT + 512) * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->e_buf, (size_t)D * h->Bp * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->e_tape, (size_t)D * h->Bp * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->replay, 2 * MA * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->rws, NT * fc_rev_ws_floats(G) * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->pacc, NT * G.P * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->ctl, 3 * sizeof(StepState))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->ctl_t, NT * sizeof(StepState))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->meta, MA * sizeof(StepMeta))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->initrec_t, NT * sizeof(InitRec))) != hipSuccess) return fail(e);
-    h->initrec = h->initrec_t;
-    if ((e = hipMalloc(&h->rec, MA * sizeof(FfStepRec))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->xch, xb)) != hipSuccess) return fail(e);
-    if ((e = hipMemset(h->xch, 0, xb)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->xcc, kMwMeetMax * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->abort_word, 8)) != hipSuccess) return fail(e);
-    if ((e = hipMemset(h->abort_word, 0, 8)) != hipSuccess) return fail(e);
-    for (const void* kf : {(const void*)rnde_ffjordc_solve_kernel<false>, (const void*)rnde_ffjordc_reverse_kernel<false>,
-                           (const void*)rnde_ffjordc_feval_kernel<false>, (const void*)rnde_ffjordc_solve_kernel<true>,
-                           (const void*)rnde_ffjordc_reverse_kernel<true>, (const void*)rnde_ffjordc_feval_kernel<true>})
-        if ((e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes)) != hipSuccess) return fail(e);
-    for (auto& v : h->ev) if ((e = hipEventCreate(&v)) != hipSuccess) return fail(e);
-    { static std::atomic<int> next_slot{0}; h->xcd_slot = next_slot.fetch_add(1) & 7; }
-    h->h_chk.assign(2 + kMwMeetMax, 0u);
-    *out = h;
-    return RNDE_OK;
+    h->G.D = D; h->G.H = 0; h->G.P = h->CG.P;
+    return tile_create<FcDyn>(h, h->CG, out);
 }
 
 extern "C" rnde_status rnde_ffjord_create(const rnde_ffjord_config* c, rnde_ffjord** out) {
@@ -342,8 +318,8 @@ static rnde_status ff_kinetic_ready(rnde_ffjord* h) {
     }
     if (h->kin_ready) return RNDE_OK;
     const size_t RBk = (size_t)Rk * h->Bp, RB = (size_t)h->R * h->Bp, MA = (size_t)h->cfg.max_attempts;
-    const size_t rws = h->engine == 2 ? (size_t)h->ntiles_max * fc_rev_ws_floats(h->CG, true)
-                       : h->engine == 1 ? (size_t)h->ntiles_max * ft_rev_ws_floats(h->TG, true)
+    const size_t rws = h->engine == 2 ? (size_t)h->ntiles_max * FcDyn::rev_ws_floats(h->CG, true)
+                       : h->engine == 1 ? (size_t)h->ntiles_max * FtDyn::rev_ws_floats(h->TG, true)
                                         : (size_t)(24 + kFfVjpVecsKin) * std::max(H, Rk) * h->Bp;
     FCHK(h, hipDeviceSynchronize());           // (rnde_ffjord_debug_feval does not wait for its launch)
     float *ws = nullptr, *tape = nullptr, *rw = nullptr;
@@ -360,6 +336,38 @@ static rnde_status ff_kinetic_ready(rnde_ffjord* h) {
     h->ws = ws; h->tape = tape; h->rws = rw;
     h->kin_ready = true;
     return RNDE_OK;
+}
+
+// The tile driver's launches for the dynamics Dyn: the shared fields come from the one-workgroup engine's parameter structs, filled once.
+template <class Dyn>
+static void tile_launch_solve(rnde_ffjord* h, const typename Dyn::Geo& G, const FfSolveParams& Q, const MwMeet& meet, bool kin, hipStream_t s) {
+    TileSolveParams<typename Dyn::Geo> T{};
+    T.F = Q.F; T.G = G; T.p = Q.p; T.x = Q.x; T.e = Q.e; T.ws = Q.ws; T.tape = Q.tape; T.logpx = Q.logpx; T.x_out = Q.x_out;
+    T.norm = Q.norm; T.initrec_t = h->initrec_t; T.ctl_t = h->ctl_t; T.scratch = Q.dir < 0 ? h->qt : nullptr;
+    T.meet = meet; T.xcc = h->xcc; T.xcd_slot = h->xcd_slot; T.dir = Q.dir; T.Bp = Q.Bp; T.ntiles = meet.ntiles; T.tbase = Q.tbase; T.reg = Q.reg;
+    const dim3 grid(meet.global ? meet.ntiles : 8 * meet.ntiles);      // one XCD: every eighth block is a tile (the others return at once)
+    if (kin) hipLaunchKernelGGL((rnde_ffjord_tile_solve_kernel<Dyn, true>), grid, dim3(kFtThreads), h->lds_bytes, s, T);
+    else hipLaunchKernelGGL((rnde_ffjord_tile_solve_kernel<Dyn, false>), grid, dim3(kFtThreads), h->lds_bytes, s, T);
+}
+
+template <class Dyn>
+static void tile_launch_reverse(rnde_ffjord* h, const typename Dyn::Geo& G, const FfRevParams& Q, bool kin, hipStream_t s) {
+    TileRevParams<typename Dyn::Geo> T{};
+    T.G = G; T.p = Q.p; T.e = Q.e; T.tape = Q.tape; T.rec = Q.rec; T.logpx_bar = Q.logpx_bar; T.ws = Q.ws; T.pacc = Q.pacc;
+    T.x_bar = Q.x_bar; T.n_acc = Q.n_acc; T.B = Q.B; T.Bp = Q.Bp; T.reltol = Q.reltol; T.abstol = Q.abstol; T.reg_bar = Q.reg_bar;
+    const int nt = (Q.B + 15) / 16;
+    if (kin) hipLaunchKernelGGL((rnde_ffjord_tile_reverse_kernel<Dyn, true>), dim3(nt), dim3(kFtThreads), h->lds_bytes, s, T);
+    else hipLaunchKernelGGL((rnde_ffjord_tile_reverse_kernel<Dyn, false>), dim3(nt), dim3(kFtThreads), h->lds_bytes, s, T);
+}
+
+template <class Dyn>
+static void tile_launch_feval(rnde_ffjord* h, const typename Dyn::Geo& G, const float* p_dev, const float* x_dev, const float* e_dev, int B, float t,
+                              int exact, bool kin, float* out_dev, hipStream_t s) {
+    const dim3 grid((B + 15) / 16);
+    if (kin) hipLaunchKernelGGL((rnde_ffjord_tile_feval_kernel<Dyn, true>), grid, dim3(kFtThreads), h->lds_bytes, s, G, p_dev, x_dev, e_dev, t, B, exact,
+                                h->rws, h->qt, out_dev);
+    else hipLaunchKernelGGL((rnde_ffjord_tile_feval_kernel<Dyn, false>), grid, dim3(kFtThreads), h->lds_bytes, s, G, p_dev, x_dev, e_dev, t, B, exact,
+                            h->rws, h->qt, out_dev);
 }
 
 // One solve: dir = +1 the forward (logpx; Hutchinson probe e), dir = -1 sampling (exact trace, tau = t1 - t).  reg_out_dev != NULL: the
@@ -394,50 +402,30 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
     Q.tape = taped ? h->tape : nullptr; Q.logpx = dir > 0 ? logpx_dev : nullptr; Q.x_out = x_out_dev; Q.norm = h->norm;
     Q.dir = dir; Q.T = h->T; Q.Bp = h->Bp; Q.tbase = t1; Q.reg = reg_out_dev;
     const int nt = (B + 15) / 16;
-    FtSolveParams TQ{};
-    if (h->engine == 1) {      // the tiled engine: every tile resident, one meeting per attempt (one XCD up to 32 tiles, agent scope above)
+    const bool tiles = h->engine >= 1;     // engines 1 and 2 share the tile layout, the meeting and its checks
+    MwMeet meet{};
+    if (tiles) {               // every tile resident, one meeting per attempt (one XCD up to 32 tiles, agent scope above)
         if (++h->epoch >= 500000u) { h->epoch = 1; FCHK(h, hipMemsetAsync(h->xch, 0, ((size_t)h->cfg.max_attempts + 4) * 3 * kMwMeetMax * 8, s)); }
-        TQ.F = P; TQ.G = h->TG; TQ.p = p_dev; TQ.x = x_dev; TQ.e = Q.e; TQ.ws = h->ws; TQ.tape = Q.tape; TQ.logpx = Q.logpx; TQ.x_out = x_out_dev;
-        TQ.norm = h->norm; TQ.initrec_t = h->initrec_t; TQ.ctl_t = h->ctl_t; TQ.qt = dir < 0 ? h->qt : nullptr;
-        TQ.meet = MwMeet{h->xch, h->abort_word, h->epoch, nt, nt > 32 ? 1 : 0};
-        TQ.xcc = h->xcc; TQ.xcd_slot = h->xcd_slot; TQ.dir = dir; TQ.Bp = h->Bp; TQ.ntiles = nt; TQ.tbase = t1;
-        TQ.reg = reg_out_dev;
+        meet = MwMeet{h->xch, h->abort_word, h->epoch, nt, nt > 32 ? 1 : 0};
     }
-    const bool tiles = h->engine >= 1;     // engines 1 and 2 share the tiled layout, the meeting and its checks
-    if (h->engine == 2) {      // the Dense-chain dynamics: the tiled engine's launch shape and meeting
-        if (++h->epoch >= 500000u) { h->epoch = 1; FCHK(h, hipMemsetAsync(h->xch, 0, ((size_t)h->cfg.max_attempts + 4) * 3 * kMwMeetMax * 8, s)); }
-        FcSolveParams CQ{};
-        CQ.F = P; CQ.G = h->CG; CQ.p = p_dev; CQ.x = x_dev; CQ.e = Q.e; CQ.ws = h->ws; CQ.tape = Q.tape; CQ.logpx = Q.logpx; CQ.x_out = x_out_dev;
-        CQ.norm = h->norm; CQ.initrec_t = h->initrec_t; CQ.ctl_t = h->ctl_t;
-        CQ.meet = MwMeet{h->xch, h->abort_word, h->epoch, nt, nt > 32 ? 1 : 0};
-        CQ.xcc = h->xcc; CQ.xcd_slot = h->xcd_slot; CQ.dir = dir; CQ.Bp = h->Bp; CQ.ntiles = nt; CQ.tbase = t1; CQ.reg = reg_out_dev;
-        TQ.meet = CQ.meet;
-        FCHK(h, hipEventRecord(h->ev[0], s));
-        const dim3 grid(CQ.meet.global ? nt : 8 * nt);
-        if (kin) hipLaunchKernelGGL(rnde_ffjordc_solve_kernel<true>, grid, dim3(kFtThreads), h->lds_bytes, s, CQ);
-        else hipLaunchKernelGGL(rnde_ffjordc_solve_kernel<false>, grid, dim3(kFtThreads), h->lds_bytes, s, CQ);
-    } else {
     FCHK(h, hipEventRecord(h->ev[0], s));
-    if (h->engine == 1) {
-        const dim3 grid(TQ.meet.global ? nt : 8 * nt);
-        if (kin) hipLaunchKernelGGL(rnde_ffjordt_solve_kernel<true>, grid, dim3(kFtThreads), h->lds_bytes, s, TQ);
-        else hipLaunchKernelGGL(rnde_ffjordt_solve_kernel<false>, grid, dim3(kFtThreads), h->lds_bytes, s, TQ);
-    } else if (kin) hipLaunchKernelGGL(rnde_ffjord_solve_kernel<true>, dim3(1), dim3(h->T), h->lds_bytes, s, Q);
+    if (h->engine == 2) tile_launch_solve<FcDyn>(h, h->CG, Q, meet, kin, s);
+    else if (h->engine == 1) tile_launch_solve<FtDyn>(h, h->TG, Q, meet, kin, s);
+    else if (kin) hipLaunchKernelGGL(rnde_ffjord_solve_kernel<true>, dim3(1), dim3(h->T), h->lds_bytes, s, Q);
     else hipLaunchKernelGGL(rnde_ffjord_solve_kernel<false>, dim3(1), dim3(h->T), h->lds_bytes, s, Q);
-    }
     FCHK(h, hipGetLastError());
     FCHK(h, hipEventRecord(h->ev[1], s));
     StepState fin;
     FCHK(h, hipMemcpyAsync(&fin, h->ctl + 2, sizeof(StepState), hipMemcpyDeviceToHost, s));
     if (tiles) {
         FCHK(h, hipMemcpyAsync(h->h_chk.data(), h->abort_word, 4, hipMemcpyDeviceToHost, s));
-        if (!TQ.meet.global) FCHK(h, hipMemcpyAsync(h->h_chk.data() + 2, h->xcc, (size_t)nt * 4, hipMemcpyDeviceToHost, s));
+        if (!meet.global) FCHK(h, hipMemcpyAsync(h->h_chk.data() + 2, h->xcc, (size_t)nt * 4, hipMemcpyDeviceToHost, s));
     }
     FCHK(h, hipStreamSynchronize(s));
     (void)hipEventElapsedTime(&h->fwd_ms, h->ev[0], h->ev[1]);
     if (tiles) {
         bool split = false;
-        for (int i = 1; i < nt && !TQ.meet.global; ++i) split |= h->h_chk[2 + i] != h->h_chk[2];
+        for (int i = 1; i < nt && !meet.global; ++i) split |= h->h_chk[2 + i] != h->h_chk[2];
         if (h->h_chk[0] != 0u || split) {      // no fall-back to other arithmetic: the call fails and says why
             FCHK(h, hipMemsetAsync(h->abort_word, 0, 8, s));
             FCHK(h, hipStreamSynchronize(s));
@@ -567,26 +555,11 @@ static rnde_status ff_backward(rnde_ffjord* h, const float* logpx_bar_dev, const
     Q.ws = h->rws; Q.pacc = h->pacc; Q.x_bar = x_bar_dev; Q.n_acc = T.n_acc; Q.B = T.B; Q.Bp = h->Bp; Q.reltol = T.reltol; Q.abstol = T.abstol;
     Q.reg_bar = reg_bar_dev;
     FCHK(h, hipEventRecord(h->ev[2], s));
-    if (h->engine == 2) {
-        FcRevParams CQ{};
-        CQ.G = h->CG; CQ.p = T.p; CQ.e = T.e; CQ.tape = h->tape; CQ.rec = h->rec; CQ.logpx_bar = logpx_bar_dev; CQ.ws = h->rws; CQ.pacc = h->pacc;
-        CQ.x_bar = x_bar_dev; CQ.n_acc = T.n_acc; CQ.B = T.B; CQ.Bp = h->Bp; CQ.reltol = T.reltol; CQ.abstol = T.abstol;
-        CQ.reg_bar = reg_bar_dev;
-        const int nt = (T.B + 15) / 16;
-        if (T.kin) hipLaunchKernelGGL(rnde_ffjordc_reverse_kernel<true>, dim3(nt), dim3(kFtThreads), h->lds_bytes, s, CQ);
-        else hipLaunchKernelGGL(rnde_ffjordc_reverse_kernel<false>, dim3(nt), dim3(kFtThreads), h->lds_bytes, s, CQ);
+    if (h->engine >= 1) {
+        if (h->engine == 2) tile_launch_reverse<FcDyn>(h, h->CG, Q, T.kin, s);
+        else tile_launch_reverse<FtDyn>(h, h->TG, Q, T.kin, s);
         FCHK(h, hipGetLastError());
-        hipLaunchKernelGGL(rnde_ffjordt_reduce_kernel, dim3((h->G.P + 255) / 256), dim3(256), 0, s, (const float*)h->pacc, h->G.P, nt, p_bar_dev);
-    } else if (h->engine == 1) {
-        FtRevParams TQ{};
-        TQ.G = h->TG; TQ.p = T.p; TQ.e = T.e; TQ.tape = h->tape; TQ.rec = h->rec; TQ.logpx_bar = logpx_bar_dev; TQ.ws = h->rws; TQ.pacc = h->pacc;
-        TQ.x_bar = x_bar_dev; TQ.n_acc = T.n_acc; TQ.B = T.B; TQ.Bp = h->Bp; TQ.reltol = T.reltol; TQ.abstol = T.abstol;
-        TQ.reg_bar = reg_bar_dev;
-        const int nt = (T.B + 15) / 16;
-        if (T.kin) hipLaunchKernelGGL(rnde_ffjordt_reverse_kernel<true>, dim3(nt), dim3(kFtThreads), h->lds_bytes, s, TQ);
-        else hipLaunchKernelGGL(rnde_ffjordt_reverse_kernel<false>, dim3(nt), dim3(kFtThreads), h->lds_bytes, s, TQ);
-        FCHK(h, hipGetLastError());
-        hipLaunchKernelGGL(rnde_ffjordt_reduce_kernel, dim3((h->G.P + 255) / 256), dim3(256), 0, s, (const float*)h->pacc, h->G.P, nt, p_bar_dev);
+        hipLaunchKernelGGL(rnde_ffjordt_reduce_kernel, dim3((h->G.P + 255) / 256), dim3(256), 0, s, (const float*)h->pacc, h->G.P, (T.B + 15) / 16, p_bar_dev);
     } else {
         if (T.kin) hipLaunchKernelGGL(rnde_ffjord_reverse_kernel<true>, dim3((T.B + 255) / 256), dim3(256), 0, s, Q);
         else hipLaunchKernelGGL(rnde_ffjord_reverse_kernel<false>, dim3((T.B + 255) / 256), dim3(256), 0, s, Q);
@@ -629,12 +602,8 @@ extern "C" rnde_status rnde_ffjord_sample(rnde_ffjord* h, const float* p_dev, co
 extern "C" rnde_status rnde_ffjord_debug_feval(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t,
                                                int32_t exact, float* out_dev, void* stream) {
     if (!h || !x_dev || !p_dev || !out_dev || B < 1 || B > h->cfg.max_batch || (!exact && !e_dev)) { if (h) h->err = "bad argument"; return RNDE_ERR_BAD_ARG; }
-    if (h->engine == 2)
-        hipLaunchKernelGGL(rnde_ffjordc_feval_kernel<false>, dim3((B + 15) / 16), dim3(kFtThreads), h->lds_bytes, (hipStream_t)stream, h->CG, p_dev, x_dev, e_dev,
-                           t, B, exact, h->rws, out_dev);
-    else if (h->engine == 1)
-        hipLaunchKernelGGL(rnde_ffjordt_feval_kernel<false>, dim3((B + 15) / 16), dim3(kFtThreads), h->lds_bytes, (hipStream_t)stream, h->TG, p_dev, x_dev, e_dev,
-                           t, B, exact, h->rws, h->qt, out_dev);
+    if (h->engine == 2) tile_launch_feval<FcDyn>(h, h->CG, p_dev, x_dev, e_dev, B, t, exact, false, out_dev, (hipStream_t)stream);
+    else if (h->engine == 1) tile_launch_feval<FtDyn>(h, h->TG, p_dev, x_dev, e_dev, B, t, exact, false, out_dev, (hipStream_t)stream);
     else
         hipLaunchKernelGGL(rnde_ffjord_feval_kernel<false>, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->G, p_dev, x_dev, e_dev, t, B, exact,
                            h->rws, out_dev);
@@ -646,12 +615,8 @@ extern "C" rnde_status rnde_ffjord_debug_feval_kinetic(rnde_ffjord* h, const flo
                                                        float* out_dev, void* stream) {
     if (!h || !x_dev || !p_dev || !e_dev || !out_dev || B < 1 || B > h->cfg.max_batch) { if (h) h->err = "bad argument"; return RNDE_ERR_BAD_ARG; }
     if (rnde_status kst = ff_kinetic_ready(h)) return kst;
-    if (h->engine == 2)
-        hipLaunchKernelGGL(rnde_ffjordc_feval_kernel<true>, dim3((B + 15) / 16), dim3(kFtThreads), h->lds_bytes, (hipStream_t)stream, h->CG, p_dev, x_dev,
-                           e_dev, t, B, 0, h->rws, out_dev);
-    else if (h->engine == 1)
-        hipLaunchKernelGGL(rnde_ffjordt_feval_kernel<true>, dim3((B + 15) / 16), dim3(kFtThreads), h->lds_bytes, (hipStream_t)stream, h->TG, p_dev, x_dev,
-                           e_dev, t, B, 0, h->rws, h->qt, out_dev);
+    if (h->engine == 2) tile_launch_feval<FcDyn>(h, h->CG, p_dev, x_dev, e_dev, B, t, 0, true, out_dev, (hipStream_t)stream);
+    else if (h->engine == 1) tile_launch_feval<FtDyn>(h, h->TG, p_dev, x_dev, e_dev, B, t, 0, true, out_dev, (hipStream_t)stream);
     else
         hipLaunchKernelGGL(rnde_ffjord_feval_kernel<true>, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->G, p_dev, x_dev, e_dev, t, B, 0,
                            h->rws, out_dev);

@@ -1,0 +1,374 @@
+// rnde_ffjord_tile.h -- the tile driver of TrackedFFJORD: everything of engines 1 and 2 that does not depend on the dynamics.  One adaptive
+// solve, one reverse sweep and one feval kernel, templated on <class Dyn, bool KIN>; the two dynamics are FtDyn (rnde_ffjordt.h /
+// rnde_bffjordt.h: ConcatSquash) and FcDyn (rnde_ffjordc.h / rnde_bffjordc.h: Dense chains).  The driver never asks which one it serves.
+//
+// Layout (rnde_ffjordt.h): one workgroup of four waves per 16 batch columns (a tile); the Runge-Kutta state is [R][Bp] in global memory
+// (R = D + 1 augmented rows, D + 3 with KIN; each tile touching its own 16 columns), the dynamics keep their parameters and activations in LDS.
+//
+// Forward solve: the whole adaptive Tsit5 solve in one launch.  Once per attempt every tile forms its partial of the error norm and the tiles
+// meet through rnde_chainmw.h's bounded mw_exchange3 (one XCD up to 32 tiles, agent scope above): partials are summed in tile order in
+// double, so every tile runs the same controller (advance_state_t over R rows) on the same bits, and a solve is bit-identical run to run.
+// A meeting that times out raises the abort word and ends the launch; the host reports it by name.
+//
+// Reverse sweep: what rnde_bffjord.h differentiates (discretise-then-optimise through every Tsit5 stage of every accepted step, step sizes
+// and times constants: track_ctrl = track_initdt = 0; the saved value EEst * dt reaches the stages through EEst).  One workgroup per tile,
+// every accepted step in one launch, no meeting: once the step log is fixed no column depends on another, and the EEst values come from the
+// step log.  The stage values are recomputed from the taped uprev with the forward's own evaluation; the per-column vectors of a stage's
+// second-order VJP live in a per-tile global buffer (Dyn::rev_ws_floats; written and read by the same workgroup, L2-resident), no private
+// scratch.  Parameter cotangents accumulate in the tile's own row of pacc ([ntiles][P], plain read-modify-write by one lane per entry, no
+// atomics); rnde_ffjordt_reduce_kernel sums the tiles in tile order in double.
+//
+// What a dynamics policy provides (a plain struct of static members):
+//   Geo, Lds                   the geometry (kernel argument: D, P, DP and whatever the dynamics need) and the LDS view (W, X, E, red, ...)
+//   lds(G, smem)               the LDS view over the dynamic shared memory
+//   load_params(G, p, W, tid)  parameters into LDS, zero-padded; every thread calls it
+//   eval<KIN>(G, L, t, kout, ks, exact, fsign, tsign, scratch, tid)
+//                              one evaluation of the augmented right-hand side for the tile's 16 columns.  pre: L.X holds the data rows of
+//                              the input ([DP][16], padded rows zero), L.E the probe (Hutchinson; zero where not valid).
+//                              out: kout[r * ks + c] = fsign * f_r (r < D), kout[D * ks + c] = tsign * tr; KIN (Hutchinson only):
+//                              kout[(D + 1) * ks + c] = sum f^2, kout[(D + 2) * ks + c] = sum eJ^2.  exact: the exact trace; scratch is
+//                              the tile's scratch_floats(G) floats of global memory (NULL where the host has none).
+//   vjp<KIN>(G, L, t, z, kb, yb, V, pacc, tid)
+//                              yb[0:D] += (dF/dz)' kb and pacc += (dF/dp)' kb; z, kb, yb: [R][16], V: the tile's vector slots
+//   lds_floats(G), rev_ws_floats(G, kin), scratch_floats(G)
+// Barriers.  The driver writes L.X (and, once, L.E) and calls eval with no barrier of its own: eval places a barrier before its first read
+// of L.X or L.E.  Parameters that eval or vjp read ahead of that barrier (FtDyn's gates) load_params makes visible itself, by ending behind
+// a barrier; a policy whose eval starts with the barrier (FcDyn) needs none there.  eval and vjp end behind a barrier, every thread of the
+// workgroup calls them.
+#pragma once
+#include "rnde_bffjord.h"      // FfStepRec
+#include "rnde_ffjordt.h"      // the tile layout's constants; MwMeet, mw_exchange3
+
+namespace rnde {
+
+template <class Geo>
+struct TileSolveParams {
+    StepParams F;                    // the controller's view (F.D = R rows; F.ctl / meta / initrec / ctl_final: tile 0's)
+    Geo G;
+    const float* p;
+    const float* x;                  // D x B caller layout
+    const float* e;                  // D x B caller layout (dir = +1), NULL (dir = -1: exact trace)
+    float* ws;                       // [10][R][Bp]: uprev, unew, (unused), k1..k7
+    float* tape;                     // [max_attempts + 1][R][Bp] or NULL
+    float* logpx;                    // B (dir = +1) or NULL
+    float* x_out;                    // D x B caller layout or NULL
+    float* norm;                     // [ntiles][8] + 512: each tile's initial-step norms (advance_state reads the third as a one-entry partial)
+    InitRec* initrec_t;              // [ntiles]: each tile's copy of the initial-step record (tile 0's is F.initrec)
+    StepState* ctl_t;                // [ntiles]: where tiles other than 0 write the state before attempt 0
+    float* scratch;                  // [ntiles][Dyn::scratch_floats] (FtDyn: the exact trace's H x H buffer) or NULL
+    MwMeet meet;
+    unsigned* xcc;                   // [ntiles] (one-XCD meeting: the host checks they agree)
+    int xcd_slot;
+    int dir, Bp, ntiles;
+    float tbase;                     // dir = -1: t1
+    float* reg;                      // kinetic solves: 2 x B (lambda1 row, then lambda2 row); NULL otherwise
+};
+
+template <class Geo>
+struct TileRevParams {
+    Geo G;
+    const float* p;
+    const float* e;                   // D x B caller layout
+    const float* tape;                // [n_acc + 1][R][Bp]
+    const FfStepRec* rec;             // [n_acc]
+    const float* logpx_bar;           // B
+    float* ws;                        // [ntiles][Dyn::rev_ws_floats]
+    float* pacc;                      // [ntiles][P]
+    float* x_bar;                     // D x B caller layout (may be NULL)
+    int n_acc, B, Bp;
+    float reltol, abstol;
+    const float* reg_bar;             // kinetic sweep: 2 x B cotangents of (lambda1, lambda2), or NULL (zeros)
+};
+
+// Publish this tile's three partials (wave 0), collect everybody's sums in tile order; false when the meeting timed out (every thread).
+__device__ __forceinline__ bool tile_meet(const MwMeet& M, float* red, int seq, float a, float b, float c, double (&out)[3], int tile, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    a = wave_sum_f(a); b = wave_sum_f(b); c = wave_sum_f(c);
+    if (lane == 0) { red[wave] = a; red[4 + wave] = b; red[8 + wave] = c; }
+    __syncthreads();
+    double* RD = (double*)(red + 64);
+    if (wave == 0) {
+        const float mine[3] = {((red[0] + red[1]) + red[2]) + red[3], ((red[4] + red[5]) + red[6]) + red[7], ((red[8] + red[9]) + red[10]) + red[11]};
+        double o[3];
+        const bool ok = mw_exchange3(M, seq, mine, o, tile, lane);
+        if (lane == 0) { RD[0] = o[0]; RD[1] = o[1]; RD[2] = o[2]; red[70] = ok ? 1.f : 0.f; }
+    }
+    __syncthreads();
+    const bool ok = red[70] != 0.f;
+    out[0] = RD[0]; out[1] = RD[1]; out[2] = RD[2];
+    __syncthreads();
+    return ok;
+}
+
+// The whole adaptive solve in one launch: forward (dir = +1, Hutchinson), replay along P.replay, sampling (dir = -1, exact trace, tau = t1 - t).
+template <class Dyn, bool KIN>
+__global__ __launch_bounds__(kFtThreads) void rnde_ffjord_tile_solve_kernel(const TileSolveParams<typename Dyn::Geo> Q) {
+    extern __shared__ float ft_smem[];
+    if (!Q.meet.global && (int)(blockIdx.x & 7) != Q.xcd_slot) return;
+    const int tile = Q.meet.global ? (int)blockIdx.x : (int)(blockIdx.x >> 3);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const typename Dyn::Geo& G = Q.G;
+    const int D = G.D, R = D + (KIN ? 3 : 1), Bp = Q.Bp, B = Q.F.B, col0 = tile * 16;
+    if (!Q.meet.global && tid == 0) Q.xcc[tile] = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 15;
+    StepParams P = Q.F;
+    P.initpart = Q.norm + 8 * tile;
+    P.initrec = Q.initrec_t + tile;
+    const bool lead = tile == 0 && tid == 0;
+    const typename Dyn::Lds L = Dyn::lds(G, ft_smem);
+    Dyn::load_params(G, Q.p, L.W, tid);
+    for (int idx = tid; idx < G.DP * 16; idx += kFtThreads) {     // (the data rows of L.X are rewritten below by the thread that zeroes them)
+        const int r = idx >> 4, col = col0 + (idx & 15);
+        L.E[idx] = (Q.dir > 0 && r < D && col < B) ? Q.e[(size_t)col * D + r] : 0.f;
+        L.X[idx] = 0.f;
+    }
+    const size_t RB = (size_t)R * Bp;
+    float* U = Q.ws + col0;
+    float* UN = Q.ws + RB + col0;
+    auto K = [&](int s) { return Q.ws + (size_t)(3 + s) * RB + col0; };
+    const int exact = Q.dir < 0 ? 1 : 0;
+    const float fsign = Q.dir > 0 ? 1.f : -1.f, tsign = Q.dir > 0 ? -1.f : 1.f;
+    float* scratch = Q.scratch ? Q.scratch + (size_t)tile * Dyn::scratch_floats(G) : nullptr;
+    auto eval = [&](float time, float* kout) {
+        Dyn::template eval<KIN>(G, L, Q.dir > 0 ? time : Q.tbase - time, kout, Bp, exact, fsign, tsign, scratch, tid);
+    };
+    const float rt = P.reltol, at = P.abstol;
+    const double N = (double)R * (double)B;
+    const int nel = R * 16;
+
+    // ---- initial state, f(u0), the initial-step rule (the arithmetic of rnde_ffjord_solve_kernel) ----
+    for (int idx = tid; idx < nel; idx += kFtThreads) {
+        const int r = idx >> 4, c = idx & 15, col = col0 + c;
+        const float v = (r < D && col < B) ? Q.x[(size_t)col * D + r] : 0.f;
+        U[(size_t)r * Bp + c] = v;
+        if (r < D) L.X[r * 16 + c] = v;
+    }
+    eval(P.t0 + 0.f, K(0));
+    float pa = 0.f, pb = 0.f;
+    for (int idx = tid; idx < nel; idx += kFtThreads) {
+        const int r = idx >> 4, c = idx & 15;
+        if (col0 + c >= B) continue;
+        const size_t ix = (size_t)r * Bp + c;
+        const float xv = U[ix], kv = K(0)[ix], sk = at + fabsf(xv) * rt;
+        const float a = xv / sk, b = kv / sk;
+        pa += a * a; pb += b * b;
+    }
+    double sm[3];
+    if (!tile_meet(Q.meet, L.red, 0, pa, pb, 0.f, sm, tile, tid)) return;
+    float dt0;
+    {
+        const float d0 = (float)sqrt(sm[0] / N), d1 = (float)sqrt(sm[1] / N), dtmax = P.t1 - P.t0;
+        int c0 = 0, cl = 0;
+        if (d0 < 1e-5f || d1 < 1e-5f) { dt0 = 1e-6f; c0 = 1; }
+        else dt0 = (d0 / d1) / 100.f;
+        if (dtmax < dt0) { dt0 = dtmax; cl = 1; }
+        if (tid == 0) { P.initrec->d0 = d0; P.initrec->d1 = d1; P.initrec->dt0 = dt0; P.initrec->dt0_const = c0; P.initrec->dt0_clamped = cl; }
+    }
+    for (int idx = tid; idx < nel; idx += kFtThreads) {
+        const int r = idx >> 4, c = idx & 15;
+        const size_t ix = (size_t)r * Bp + c;
+        if (r < D) L.X[r * 16 + c] = U[ix] + dt0 * K(0)[ix];
+    }
+    eval(P.t0 + dt0, K(1));
+    float pc = 0.f;
+    for (int idx = tid; idx < nel; idx += kFtThreads) {
+        const int r = idx >> 4, c = idx & 15;
+        if (col0 + c >= B) continue;
+        const size_t ix = (size_t)r * Bp + c;
+        const float sk = at + fabsf(U[ix]) * rt;
+        const float a = (K(1)[ix] - K(0)[ix]) / sk;
+        pc += a * a;
+    }
+    if (!tile_meet(Q.meet, L.red, 1, pc, 0.f, 0.f, sm, tile, tid)) return;
+    if (tid == 0) P.initpart[2] = (float)sm[0];       // advance_state reads the third initial norm as a one-entry partial
+    __syncthreads();
+    __threadfence_block();
+    StepState S = advance_state(P, 0, lane, tid == 0, tile == 0 ? &P.ctl[0] : Q.ctl_t + tile);
+    int n_acc = 0;
+    for (int n = 0; !S.done; ++n) {
+        const float t = S.t;
+        const float dt = (P.t1 - S.t < S.dtp) ? (P.t1 - S.t) : S.dtp;
+        for (int s = 1; s < 7; ++s) {                      // stage s + 1: input uprev + dt sum_j a_{s+1, j} k_j
+            for (int idx = tid; idx < nel; idx += kFtThreads) {
+                const int r = idx >> 4, c = idx & 15;
+                const size_t ix = (size_t)r * Bp + c;
+                float acc = 0.f;
+                for (int j = 0; j < s; ++j) acc = fmaf(tsA_rt(s, j), K(j)[ix], acc);
+                const float g = U[ix] + dt * acc;
+                if (r < D) L.X[r * 16 + c] = g;
+                if (s == 6) UN[ix] = g;
+            }
+            eval(t + kTsC[s] * dt, K(s));
+        }
+        float part = 0.f;
+        for (int idx = tid; idx < nel; idx += kFtThreads) {   // embedded error estimate, SURVEY.md B.3
+            const int r = idx >> 4, c = idx & 15;
+            if (col0 + c >= B) continue;
+            const size_t ix = (size_t)r * Bp + c;
+            float E = 0.f;
+            for (int j = 0; j < 7; ++j) E += kTsBt[j] * K(j)[ix];
+            const float ut = dt * E, sk = at + fmaxf(fabsf(U[ix]), fabsf(UN[ix])) * rt, rr = ut / sk;
+            part += rr * rr;
+        }
+        double xs[3];
+        if (!tile_meet(Q.meet, L.red, 2 + n, part, 0.f, 0.f, xs, tile, tid)) return;
+        const float none[4] = {0.f, 0.f, 0.f, 0.f};
+        const StepState Sn = advance_state_t<true>(P, n + 1, lane, lead, &P.ctl[(n + 1) & 1], none, S, xs);
+        if (Sn.n_acc > S.n_acc) {                          // accepted: tape uprev, then unew -> uprev, k7 -> k1
+            for (int idx = tid; idx < nel; idx += kFtThreads) {
+                const int r = idx >> 4, c = idx & 15;
+                const size_t ix = (size_t)r * Bp + c;
+                if (Q.tape) Q.tape[(size_t)n_acc * RB + col0 + ix] = U[ix];
+                U[ix] = UN[ix];
+                K(0)[ix] = K(6)[ix];
+            }
+            ++n_acc;
+        }
+        S = Sn;
+    }
+    if (lead) *P.ctl_final = S;
+    __syncthreads();
+    for (int idx = tid; idx < nel; idx += kFtThreads) {
+        const int r = idx >> 4, c = idx & 15;
+        const size_t ix = (size_t)r * Bp + c;
+        if (Q.tape) Q.tape[(size_t)n_acc * RB + col0 + ix] = U[ix];
+        if (r < D && col0 + c < B && Q.x_out) Q.x_out[(size_t)(col0 + c) * D + r] = U[ix];
+    }
+    if (tid < 16 && col0 + tid < B && Q.logpx) {
+        float lp = 0.f;
+        for (int r = 0; r < D; ++r) {
+            const float z = U[(size_t)r * Bp + tid];
+            lp += -(1.8378770664093453f + z * z) * 0.5f;
+        }
+        Q.logpx[col0 + tid] = lp - U[(size_t)D * Bp + tid];
+    }
+    if constexpr (KIN)
+        if (tid < 16 && col0 + tid < B) {
+            Q.reg[col0 + tid] = U[(size_t)(D + 1) * Bp + tid];
+            Q.reg[(size_t)B + col0 + tid] = U[(size_t)(D + 2) * Bp + tid];
+        }
+}
+
+// The reverse sweep of the taped solve; KIN: the stage cotangent is (lz, ll, l1, l2) over R = D + 3 rows.
+template <class Dyn, bool KIN>
+__global__ __launch_bounds__(kFtThreads) void rnde_ffjord_tile_reverse_kernel(const TileRevParams<typename Dyn::Geo> Q) {
+    extern __shared__ float ft_smem[];
+    const typename Dyn::Geo& G = Q.G;
+    const int tile = blockIdx.x, tid = threadIdx.x, D = G.D, R = D + (KIN ? 3 : 1), Bp = Q.Bp, col0 = tile * 16, nel = R * 16;
+    const typename Dyn::Lds L = Dyn::lds(G, ft_smem);
+    Dyn::load_params(G, Q.p, L.W, tid);
+    for (int idx = tid; idx < G.DP * 16; idx += kFtThreads) {
+        const int r = idx >> 4, col = col0 + (idx & 15);
+        L.E[idx] = (r < D && col < Q.B) ? Q.e[(size_t)col * D + r] : 0.f;
+        L.X[idx] = 0.f;
+    }
+    float* ws = Q.ws + (size_t)tile * Dyn::rev_ws_floats(G, KIN);
+    const size_t RS = (size_t)R * 16;
+    auto Ys = [&](int s) { return ws + (size_t)s * RS; };
+    auto Ks = [&](int s) { return ws + (size_t)(7 + s) * RS; };
+    auto Kb = [&](int s) { return ws + (size_t)(14 + s) * RS; };
+    float *UB = ws + 21 * RS, *UBn = ws + 22 * RS, *Yb = ws + 23 * RS, *V = ws + 24 * RS;
+    float* pacc = Q.pacc + (size_t)tile * G.P;
+    for (int q = tid; q < G.P; q += kFtThreads) pacc[q] = 0.f;
+    const size_t RB = (size_t)R * Bp;
+    for (int idx = tid; idx < nel; idx += kFtThreads) {     // logpx = sum -(log 2 pi + z^2) / 2 - l
+        const int r = idx >> 4, c = idx & 15, col = col0 + c;
+        float v = 0.f;
+        if (col < Q.B) {
+            const float g = Q.logpx_bar[col];
+            v = r < D ? -g * Q.tape[(size_t)Q.n_acc * RB + (size_t)r * Bp + col] : -g;
+            if constexpr (KIN)
+                if (r > D) v = Q.reg_bar ? Q.reg_bar[(size_t)(r - D - 1) * Q.B + col] : 0.f;
+        }
+        UB[idx] = v;
+    }
+    // (no barrier here: UB[idx] and L.X[idx] are next touched by the thread that wrote them, pacc and L.E behind the first eval's barriers)
+    const double N = (double)R * (double)Q.B;
+    for (int n = Q.n_acc - 1; n >= 0; --n) {
+        const FfStepRec st = Q.rec[n];
+        const float t = st.t, dt = st.dt;
+        const float* U = Q.tape + (size_t)n * RB + col0;
+        // ---- recompute the stages ----
+        for (int s = 0; s < 7; ++s) {
+            for (int idx = tid; idx < nel; idx += kFtThreads) {
+                const int r = idx >> 4, c = idx & 15;
+                float acc = 0.f;
+                for (int j = 0; j < s; ++j) acc = fmaf(tsA_rt(s, j), Ks(j)[idx], acc);
+                const float y = U[(size_t)r * Bp + c] + dt * acc;
+                Ys(s)[idx] = y;
+                if (r < D) L.X[idx] = y;
+            }
+            Dyn::template eval<KIN>(G, L, t + kTsC[s] * dt, Ks(s), 16, 0, 1.f, -1.f, nullptr, tid);
+        }
+        for (int idx = tid; idx < nel; idx += kFtThreads) {
+            for (int s = 0; s < 7; ++s) Kb(s)[idx] = 0.f;
+            UBn[idx] = 0.f;
+            Yb[idx] = UB[idx];                                // cotangent of unew = stage-7 input
+        }
+        // ---- A: reverse of the error estimate (the saved value EEst * dt; rnde_bffjord.h) ----
+        if (st.svb != 0.f && st.eest > 0.f) {
+            const float coef = (float)(((double)st.svb * (double)dt) / (N * (double)st.eest));
+            for (int idx = tid; idx < nel; idx += kFtThreads) {
+                if (col0 + (idx & 15) >= Q.B) continue;
+                float E = 0.f;
+                for (int j = 0; j < 7; ++j) E += kTsBt[j] * Ks(j)[idx];
+                const float up = U[(size_t)(idx >> 4) * Bp + (idx & 15)], un = Ys(6)[idx];
+                const float au = fabsf(up), an = fabsf(un);
+                const bool use_new = !(au > an);
+                const float sk = Q.abstol + (use_new ? an : au) * Q.reltol;
+                const float rr = dt * E / sk, rb = coef * rr, utb = rb / sk, skb = -rb * rr / sk;
+                for (int j = 0; j < 7; ++j) Kb(j)[idx] += dt * kTsBt[j] * utb;
+                if (use_new) Yb[idx] += skb * Q.reltol * (un > 0.f ? 1.f : (un < 0.f ? -1.f : 0.f));
+                else UBn[idx] += skb * Q.reltol * (up > 0.f ? 1.f : (up < 0.f ? -1.f : 0.f));
+            }
+        }
+        __syncthreads();
+        // ---- B: the stages, last to first ----
+        for (int s = 6; s >= 0; --s) {
+            if (s != 6) {
+                for (int idx = tid; idx < nel; idx += kFtThreads) Yb[idx] = 0.f;
+                __syncthreads();
+            }
+            Dyn::template vjp<KIN>(G, L, t + kTsC[s] * dt, Ys(s), Kb(s), Yb, V, pacc, tid);
+            for (int idx = tid; idx < nel; idx += kFtThreads) {
+                const float y = Yb[idx];
+                UBn[idx] += y;
+                for (int j = 0; j < s; ++j) Kb(j)[idx] += dt * tsA_rt(s, j) * y;
+            }
+            __syncthreads();
+        }
+        for (int idx = tid; idx < nel; idx += kFtThreads) UB[idx] = UBn[idx];
+        __syncthreads();
+    }
+    if (Q.x_bar)
+        for (int idx = tid; idx < nel; idx += kFtThreads) {
+            const int r = idx >> 4, col = col0 + (idx & 15);
+            if (r < D && col < Q.B) Q.x_bar[(size_t)col * D + r] = UB[idx];
+        }
+}
+
+// One evaluation of the augmented right-hand side per column (the parity instrument): out (D + 1) x B caller layout, the trace row -e . eJ
+// (exact: -tr J).  One workgroup per tile; ws: [ntiles][R][16].  KIN: (D + 3) x B, Hutchinson only.
+template <class Dyn, bool KIN>
+__global__ __launch_bounds__(kFtThreads) void rnde_ffjord_tile_feval_kernel(const typename Dyn::Geo G, const float* __restrict__ p,
+                                                                           const float* __restrict__ x, const float* __restrict__ e, float t, int B,
+                                                                           int exact, float* __restrict__ ws, float* __restrict__ scratch,
+                                                                           float* __restrict__ out) {
+    extern __shared__ float ft_smem[];
+    const int tile = blockIdx.x, tid = threadIdx.x, D = G.D, R = D + (KIN ? 3 : 1), col0 = tile * 16;
+    const typename Dyn::Lds L = Dyn::lds(G, ft_smem);
+    Dyn::load_params(G, p, L.W, tid);
+    for (int idx = tid; idx < G.DP * 16; idx += kFtThreads) {
+        const int r = idx >> 4, col = col0 + (idx & 15);
+        const bool ok = r < D && col < B;
+        L.X[idx] = ok ? x[(size_t)col * D + r] : 0.f;
+        L.E[idx] = (ok && !exact) ? e[(size_t)col * D + r] : 0.f;
+    }
+    float* k = ws + (size_t)tile * R * 16;
+    Dyn::template eval<KIN>(G, L, t, k, 16, exact, 1.f, -1.f, scratch ? scratch + (size_t)tile * Dyn::scratch_floats(G) : nullptr, tid);
+    for (int idx = tid; idx < R * 16; idx += kFtThreads) {
+        const int r = idx >> 4, col = col0 + (idx & 15);
+        if (col < B) out[(size_t)col * R + r] = k[idx];
+    }
+}
+
+}  // namespace rnde

@@ -90,7 +90,7 @@ def is_chain(model):
 
 
 def chain_lds_bytes(dims):
-    """LDS bytes of a tile of the chain kernels (rnde_ffjordc.h::fc_lds_floats): padded weights with the t column and bias vectors, the input
+    """LDS bytes of a tile of the chain kernels (rnde_ffjordc.h::FcDyn::lds_floats): padded weights with the t column and bias vectors, the input
     and the probe, every layer's output, two VJP vectors, reduction scratch."""
     pad = lambda n: (n + 15) // 16 * 16
     n = len(dims) - 1

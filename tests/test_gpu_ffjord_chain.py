@@ -205,10 +205,12 @@ def test_adaptive_controller_takes_the_fp64_decisions():
     assert nfe == 3 + 6 * len(st) and sv.saveval.numel() == int(st[:, 1].sum()) + 1
 
 
-def test_reference_tolerance_along_the_device_steps():
-    """tol 1.4e-8 over 256 columns (16 tiles): logpx against the fp64 replay along the device's own accepted steps."""
+@pytest.mark.parametrize("B", [256, 513])
+def test_reference_tolerance_along_the_device_steps(B):
+    """tol 1.4e-8 over 256 columns (16 tiles, meeting on one XCD) and over 513 (33 tiles, the last one partial: the smallest batch that meets
+    at agent scope): logpx against the fp64 replay along the device's own accepted steps."""
     c = CTRL
-    B, tol = 256, 1.4e-8
+    tol = 1.4e-8
     p, x, e, _ = CR.draw(c["dims"], c["td"], B, c["seed"], c["scale"], c["xscale"])
     ff = _layer(c["dims"], c["acts"], c["td"], B, p, tol=tol)
     with torch.no_grad():
