@@ -730,6 +730,58 @@ end
     end
 end
 
+# The exact-trace forward (an extension: the reference evaluates -tr J only inside sample()): no probe; engines :tiled and chain handles.
+# The tape remembers that it is exact, so the reverse pass is ffjord_backward.
+function ffjord_forward_exact(h::FfjordHandle, x::ROCMatrix{Float32}, p::ROCVector{Float32}, tspan; keep_tape::Bool = true)
+    B = size(x, 2)
+    logpx = similar(x, B)
+    nfe = Ref{Int64}(0); nsv = Ref{Int32}(0)
+    sv = Vector{Float32}(undef, h.cfg.max_attempts + 1)
+    GC.@preserve x p logpx begin
+        st = ccall((:rnde_ffjord_forward_exact, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float32, Float32, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int64}, Ptr{Float32}, Ref{Int32}, Int32, Ptr{Cvoid}),
+                   h.ptr, devptr(x), devptr(p), B, Float32(tspan[1]), Float32(tspan[2]), devptr(logpx), C_NULL, nfe, sv, nsv, keep_tape ? 1 : 0, _stream())
+        st == 0 || error("rnde_ffjord_forward_exact status $st: ", _fferr(h.ptr))
+    end
+    return logpx, Int(nfe[]), sv[1:nsv[]]
+end
+
+# the parity instrument: the exact solve along given (dt, accepted) pairs, flattened
+function ffjord_forward_exact_replay(h::FfjordHandle, x::ROCMatrix{Float32}, p::ROCVector{Float32}, tspan, steps::Vector{Float32}; keep_tape::Bool = true)
+    B = size(x, 2)
+    logpx = similar(x, B)
+    nfe = Ref{Int64}(0); nsv = Ref{Int32}(0)
+    sv = Vector{Float32}(undef, h.cfg.max_attempts + 1)
+    GC.@preserve x p logpx steps begin
+        st = ccall((:rnde_ffjord_forward_exact_replay, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float32, Float32, Ptr{Float32}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int64}, Ptr{Float32}, Ref{Int32}, Int32, Ptr{Cvoid}),
+                   h.ptr, devptr(x), devptr(p), B, Float32(tspan[1]), Float32(tspan[2]), steps, length(steps) ÷ 2, devptr(logpx), C_NULL, nfe, sv, nsv,
+                   keep_tape ? 1 : 0, _stream())
+        st == 0 || error("rnde_ffjord_forward_exact_replay status $st: ", _fferr(h.ptr))
+    end
+    return logpx, Int(nfe[]), sv[1:nsv[]]
+end
+
+# Tracker glue of the exact call: (logpx, saveval) -> (x-bar, p-bar), as ffjord_solve without the probe
+ffjord_solve_exact(h::FfjordHandle, x::TrackedArray, p::TrackedArray, tspan) = track(ffjord_solve_exact, h, x, p, tspan)
+ffjord_solve_exact(h::FfjordHandle, x, p::TrackedArray, tspan) = track(ffjord_solve_exact, h, x, p, tspan)
+function ffjord_solve_exact(h::FfjordHandle, x, p, tspan)       # nothing tracked: no tape
+    logpx, nfe, sv = ffjord_forward_exact(h, data(x), data(p), tspan; keep_tape = false)
+    FFJORD_NFE[h] = nfe
+    return logpx, sv
+end
+@grad function ffjord_solve_exact(h::FfjordHandle, x, p, tspan)
+    logpx, nfe, sv = ffjord_forward_exact(h, data(x), data(p), data.(tspan); keep_tape = true)
+    FFJORD_NFE[h] = nfe
+    return (logpx, sv), function (Δ)
+        lb, svb = Δ
+        lbar = lb === nothing ? fill!(similar(logpx), 0f0) : ROCArray{Float32}(data(lb))
+        svbar = svb === nothing ? Float32[] : Vector{Float32}(data(svb))
+        pbar, xbar = ffjord_backward(h, lbar, svbar, length(p), size(x, 1))
+        return (nothing, xbar, pbar, nothing)
+    end
+end
+
 # sample: z (D x n) solved from t1 back to t0 with the exact trace -> x (D x n)
 function ffjord_sample(h::FfjordHandle, p::ROCVector{Float32}, z::ROCMatrix{Float32}, tspan)
     x = similar(z)

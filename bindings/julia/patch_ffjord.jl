@@ -7,6 +7,8 @@
 # width above 64, the six activations of RNDE.act_code -- through rnde_ffjord_create_chain (one engine, whatever RNDE_FFJORD_ENGINE[] says).
 # Refused with an error that names the limit: any other model under the default forw_n_back, and widths above the engine's limit.  The {false} method's `regularize = true` (kinetic energy and Jacobian norm rows,
 # ffjord.jl:53-66) runs the library's kinetic entries: in_dims + 3 <= 64 on the one-workgroup engine, the tiled engine's limits unchanged.
+# `exact = true` (an extension: the reference has no forward exact call) solves with the exact trace -tr J instead of the Hutchinson estimate:
+# no probe, the tiled engine or a chain model only, not together with `regularize = true` on a {false} layer.
 # Both call methods are one Tracker node (RNDE.ffjord_solve): Tracker.gradient through the patched layer runs RNDE.ffjord_backward.
 using Tracker, Flux, AMDGPU
 using RegNeuralDE: TrackedFFJORD, TDChain, _convert_tspan
@@ -87,9 +89,34 @@ function _ffjord_call_kinetic(n::TrackedFFJORD{false}, x, p, e)
     return logpx, reshape(l1, 1, :), reshape(l2, 1, :), RNDE.FFJORD_NFE[H], nothing
 end
 
-(n::TrackedFFJORD{false})(x, p = n.p, e = RNDE_randn(size(x)...); regularize = false) =
-    regularize ? _ffjord_call_kinetic(n, x, p, e) : _ffjord_call(n, x, p, e)
-(n::TrackedFFJORD{true})(x, p = n.p, e = RNDE_randn(size(x)...); regularize = false) = _ffjord_call(n, x, p, e)
+# exact = true: logpx from the exact trace; the same 5-tuple, one Tracker node (RNDE.ffjord_solve_exact)
+function _ffjord_call_exact(n::TrackedFFJORD{R}, x, p, kinetic::Bool) where {R}
+    kinetic && error("RNDE: exact = true together with regularize = true on a {false} layer (kinetic energy and Jacobian norm rows) is not served: ",
+                     "the Jacobian norm row is defined on the probe")
+    (_ffjord_is_chain(n) || RNDE_FFJORD_ENGINE[] === :tiled) ||
+        error("RNDE: exact = true is served on the tiled engine only (RNDE_FFJORD_ENGINE[] = :tiled)")
+    H = _ffjord_handle(n, size(x, 2))
+    logpx, sv = RNDE.ffjord_solve_exact(H, x, p, _convert_tspan(n.tspan, p))
+    z = zeros(Float32, 1, size(x, 2))
+    return logpx, z, z, RNDE.FFJORD_NFE[H], (R ? (saveval = sv,) : nothing)
+end
+
+# (e = nothing by default so that exact = true with a probe can be told apart and refused; the probe is drawn when the call needs one)
+function (n::TrackedFFJORD{false})(x, p = n.p, e = nothing; regularize = false, exact = false)
+    if exact
+        e === nothing || error("RNDE: exact = true evaluates -tr J and takes no probe; call it without e")
+        return _ffjord_call_exact(n, x, p, regularize)
+    end
+    e = e === nothing ? RNDE_randn(size(x)...) : e
+    return regularize ? _ffjord_call_kinetic(n, x, p, e) : _ffjord_call(n, x, p, e)
+end
+function (n::TrackedFFJORD{true})(x, p = n.p, e = nothing; regularize = false, exact = false)
+    if exact
+        e === nothing || error("RNDE: exact = true evaluates -tr J and takes no probe; call it without e")
+        return _ffjord_call_exact(n, x, p, false)
+    end
+    return _ffjord_call(n, x, p, e === nothing ? RNDE_randn(size(x)...) : e)
+end
 
 function RegNeuralDE.sample(n::TrackedFFJORD, indims::Int, p = n.p; nsamples::Int = 1)
     H = _ffjord_handle(n, nsamples)

@@ -660,6 +660,26 @@ typedef struct {
 } rnde_ffjord_chain_config;
 int32_t     rnde_ffjord_chain_param_count(const rnde_ffjord_chain_config* cfg);   /* 64 for TD [2, 10, 2]; -1 for a bad shape */
 rnde_status rnde_ffjord_create_chain(const rnde_ffjord_chain_config* cfg, rnde_ffjord** out);
+/* The exact-trace forward: the state [z; l] with dl / dt = -tr J(z, t), no probe and no variance in logpx.  The function evaluated is the
+ * reference's _deterministic_ffjord over jacobian_fn (ffjord.jl:137-158: D VJPs with unit probes), which the reference runs only inside
+ * sample(), from t1 back to t0; it has no forward exact call, so these two entries are an extension and have no counterpart there.  The
+ * arguments are those of rnde_ffjord_forward / _replay without e_dev and seed; the controller, the saved values (regularize = 1 handles),
+ * rnde_ffjord_steps / _step_log / _timing and NFE (3 + 6 per attempt: right-hand-side calls, as the reference counts them) are unchanged.
+ * keep_tape != 0 marks the tape as exact: rnde_ffjord_backward then runs the exact variant of the tile driver's reverse sweep, which
+ * recomputes the stages with the exact trace and differentiates the trace row through -tr J = -sum_i e_i . (e_i J) -- D + 1 stage VJPs
+ * where the Hutchinson sweep runs one, so the reverse costs about (D + 1) times the Hutchinson one.  Deterministic, and Hutchinson calls
+ * on the same handle are unaffected.  ConcatSquash handles evaluate the trace in the closed form of rnde_ffjord_create_tiled and
+ * differentiate its unit-probe form: the same function, rounded differently.
+ * Engines 1 (rnde_ffjord_create_tiled) and 2 (rnde_ffjord_create_chain), regularize 0 or 1.  RNDE_ERR_BAD_ARG before any launch, with a
+ * message that names the reason: a handle of rnde_ffjord_create (engine 0; the message points at the tiled engine), and
+ * rnde_ffjord_backward_kinetic on an exact tape (the kinetic rows are not served with the exact trace: the Jacobian norm row is defined on
+ * the probe). */
+rnde_status rnde_ffjord_forward_exact(rnde_ffjord* h, const float* x_dev, const float* p_dev, int32_t B, float t0, float t1, float* logpx_dev,
+                                      float* z_out_dev, int64_t* nfe_out, float* saveval_host, int32_t* n_saveval_out, int32_t keep_tape,
+                                      void* stream);
+rnde_status rnde_ffjord_forward_exact_replay(rnde_ffjord* h, const float* x_dev, const float* p_dev, int32_t B, float t0, float t1,
+                                             const float* steps_host, int32_t n_steps, float* logpx_dev, float* z_out_dev, int64_t* nfe_out,
+                                             float* saveval_host, int32_t* n_saveval_out, int32_t keep_tape, void* stream);
 
 #ifdef __cplusplus
 }

@@ -200,6 +200,8 @@ def lib():
     L.rnde_ffjord_chain_param_count.restype = i32
     L.rnde_ffjord_chain_param_count.argtypes = [C.POINTER(FfjordChainConfig)]
     L.rnde_ffjord_create_chain.argtypes = [C.POINTER(FfjordChainConfig), C.POINTER(vp)]
+    L.rnde_ffjord_forward_exact.argtypes = [vp, vp, vp, i32, f, f, vp, vp, i64p, fp, i32p, i32, vp]
+    L.rnde_ffjord_forward_exact_replay.argtypes = [vp, vp, vp, i32, f, f, fp, i32, vp, vp, i64p, fp, i32p, i32, vp]
     _lib = L
     return L
 
@@ -217,7 +219,7 @@ EXPORTS = ["rnde_version", "rnde_last_error", "rnde_param_count", "rnde_node_cre
            "rnde_ffjord_forward_replay", "rnde_ffjord_steps", "rnde_ffjord_backward", "rnde_ffjord_sample", "rnde_ffjord_debug_feval",
            "rnde_ffjord_timing", "rnde_ffjord_create_tiled", "rnde_ffjord_engine", "rnde_ffjord_forward_kinetic",
            "rnde_ffjord_forward_kinetic_replay", "rnde_ffjord_backward_kinetic", "rnde_ffjord_debug_feval_kinetic", "rnde_ffjord_step_log",
-           "rnde_ffjord_chain_param_count", "rnde_ffjord_create_chain"]
+           "rnde_ffjord_chain_param_count", "rnde_ffjord_create_chain", "rnde_ffjord_forward_exact", "rnde_ffjord_forward_exact_replay"]
 
 
 def check(h, status):

@@ -3,7 +3,8 @@
 // over the tile driver of rnde_ffjord_tile.h: rnde_ffjord_create_tiled (engine 1) runs it with the ConcatSquash dynamics FtDyn
 // (rnde_ffjordt.h / rnde_bffjordt.h), rnde_ffjord_create_chain (engine 2) with the Dense-chain dynamics FcDyn (rnde_ffjordc.h /
 // rnde_bffjordc.h).  The *_kinetic entries run the KIN = true instantiations of the same kernels over D + 3 rows (TrackedFFJORD{false}
-// called with regularize = true).
+// called with regularize = true).  The *_exact entries run the plain instantiations of the tile driver with the exact trace in the forward
+// solve, on the tape and in the reverse sweep (engines 1 and 2).
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -42,6 +43,7 @@ struct rnde_ffjord {
         const float* e = nullptr;    // the probe (the caller's, or e_tape)
         const float* p = nullptr;
         bool kin = false;            // a kinetic forward: D + 3 rows per record
+        bool exact = false;          // an exact-trace forward (rnde_ffjord_forward_exact): no probe, the reverse sweep's exact variant
     } tp;
     bool kin_ready = false;          // ws / tape / rws hold D + 3 rows (grown by the first kinetic call)
     float* e_tape = nullptr;         // the library's probe of a taped forward (e_buf serves untaped calls)
@@ -340,10 +342,12 @@ static rnde_status ff_kinetic_ready(rnde_ffjord* h) {
 
 // The tile driver's launches for the dynamics Dyn: the shared fields come from the one-workgroup engine's parameter structs, filled once.
 template <class Dyn>
-static void tile_launch_solve(rnde_ffjord* h, const typename Dyn::Geo& G, const FfSolveParams& Q, const MwMeet& meet, bool kin, hipStream_t s) {
+static void tile_launch_solve(rnde_ffjord* h, const typename Dyn::Geo& G, const FfSolveParams& Q, const MwMeet& meet, bool kin, bool exact,
+                              hipStream_t s) {
     TileSolveParams<typename Dyn::Geo> T{};
     T.F = Q.F; T.G = G; T.p = Q.p; T.x = Q.x; T.e = Q.e; T.ws = Q.ws; T.tape = Q.tape; T.logpx = Q.logpx; T.x_out = Q.x_out;
-    T.norm = Q.norm; T.initrec_t = h->initrec_t; T.ctl_t = h->ctl_t; T.scratch = Q.dir < 0 ? h->qt : nullptr;
+    T.norm = Q.norm; T.initrec_t = h->initrec_t; T.ctl_t = h->ctl_t; T.exact = (Q.dir < 0 || exact) ? 1 : 0;
+    T.scratch = T.exact ? h->qt : nullptr;
     T.meet = meet; T.xcc = h->xcc; T.xcd_slot = h->xcd_slot; T.dir = Q.dir; T.Bp = Q.Bp; T.ntiles = meet.ntiles; T.tbase = Q.tbase; T.reg = Q.reg;
     const dim3 grid(meet.global ? meet.ntiles : 8 * meet.ntiles);      // one XCD: every eighth block is a tile (the others return at once)
     if (kin) hipLaunchKernelGGL((rnde_ffjord_tile_solve_kernel<Dyn, true>), grid, dim3(kFtThreads), h->lds_bytes, s, T);
@@ -351,10 +355,11 @@ static void tile_launch_solve(rnde_ffjord* h, const typename Dyn::Geo& G, const 
 }
 
 template <class Dyn>
-static void tile_launch_reverse(rnde_ffjord* h, const typename Dyn::Geo& G, const FfRevParams& Q, bool kin, hipStream_t s) {
+static void tile_launch_reverse(rnde_ffjord* h, const typename Dyn::Geo& G, const FfRevParams& Q, bool kin, bool exact, hipStream_t s) {
     TileRevParams<typename Dyn::Geo> T{};
     T.G = G; T.p = Q.p; T.e = Q.e; T.tape = Q.tape; T.rec = Q.rec; T.logpx_bar = Q.logpx_bar; T.ws = Q.ws; T.pacc = Q.pacc;
     T.x_bar = Q.x_bar; T.n_acc = Q.n_acc; T.B = Q.B; T.Bp = Q.Bp; T.reltol = Q.reltol; T.abstol = Q.abstol; T.reg_bar = Q.reg_bar;
+    T.exact = exact ? 1 : 0; T.scratch = exact ? h->qt : nullptr;
     const int nt = (Q.B + 15) / 16;
     if (kin) hipLaunchKernelGGL((rnde_ffjord_tile_reverse_kernel<Dyn, true>), dim3(nt), dim3(kFtThreads), h->lds_bytes, s, T);
     else hipLaunchKernelGGL((rnde_ffjord_tile_reverse_kernel<Dyn, false>), dim3(nt), dim3(kFtThreads), h->lds_bytes, s, T);
@@ -370,11 +375,11 @@ static void tile_launch_feval(rnde_ffjord* h, const typename Dyn::Geo& G, const 
                             h->rws, h->qt, out_dev);
 }
 
-// One solve: dir = +1 the forward (logpx; Hutchinson probe e), dir = -1 sampling (exact trace, tau = t1 - t).  reg_out_dev != NULL: the
-// kinetic forward (D + 3 rows; ff_kinetic_ready has run).
+// One solve: dir = +1 the forward (logpx; Hutchinson probe e, or exact: the exact trace and no probe), dir = -1 sampling (exact trace,
+// tau = t1 - t).  reg_out_dev != NULL: the kinetic forward (D + 3 rows; ff_kinetic_ready has run).
 static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0, float t1,
                             uint64_t seed, const float* steps_host, int32_t n_steps, float* logpx_dev, float* x_out_dev, int32_t keep_tape,
-                            hipStream_t s, float* reg_out_dev = nullptr) {
+                            hipStream_t s, float* reg_out_dev = nullptr, bool exact = false) {
     const bool kin = reg_out_dev != nullptr;
     if (!x_dev || !p_dev || B < 1 || B > h->cfg.max_batch) { h->err = "bad argument (B must be 1..max_batch)"; return RNDE_ERR_BAD_ARG; }
     if (!(t1 > t0)) { h->err = "TrackedFFJORD: tspan must satisfy t1 > t0 (sample() integrates t1 -> t0 itself)"; return RNDE_ERR_BAD_ARG; }
@@ -382,7 +387,7 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
     const bool taped = dir > 0 && keep_tape;
     if (taped) h->tp.valid = false;            // (only a taped forward replaces the tape)
     const int D = h->G.D;
-    if (dir > 0 && !e_dev) {   // the library's normal stream, drawn once per call (the reference's default argument)
+    if (dir > 0 && !exact && !e_dev) {   // the library's normal stream, drawn once per call (the reference's default argument)
         float* eb = taped ? h->e_tape : h->e_buf;
         rnde_status st = rnde_normal_fill(eb, (int64_t)D * B, seed, 0x46464A4FULL, s);
         if (st != RNDE_OK) { h->err = "rnde_normal_fill failed"; return st; }
@@ -398,7 +403,7 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
     P.tape = 1; P.max_attempts = h->cfg.max_attempts; P.reg_kind = 0; P.nsave = 0;
     P.replay = steps_host ? h->replay : nullptr; P.n_replay = steps_host ? n_steps : 0;
     P.beta1 = kBeta1; P.beta2 = kBeta2; P.rk_order = 5.f;
-    Q.G = h->G; Q.p = p_dev; Q.x = x_dev; Q.e = dir > 0 ? e_dev : nullptr; Q.ws = h->ws;
+    Q.G = h->G; Q.p = p_dev; Q.x = x_dev; Q.e = (dir > 0 && !exact) ? e_dev : nullptr; Q.ws = h->ws;
     Q.tape = taped ? h->tape : nullptr; Q.logpx = dir > 0 ? logpx_dev : nullptr; Q.x_out = x_out_dev; Q.norm = h->norm;
     Q.dir = dir; Q.T = h->T; Q.Bp = h->Bp; Q.tbase = t1; Q.reg = reg_out_dev;
     const int nt = (B + 15) / 16;
@@ -409,8 +414,8 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
         meet = MwMeet{h->xch, h->abort_word, h->epoch, nt, nt > 32 ? 1 : 0};
     }
     FCHK(h, hipEventRecord(h->ev[0], s));
-    if (h->engine == 2) tile_launch_solve<FcDyn>(h, h->CG, Q, meet, kin, s);
-    else if (h->engine == 1) tile_launch_solve<FtDyn>(h, h->TG, Q, meet, kin, s);
+    if (h->engine == 2) tile_launch_solve<FcDyn>(h, h->CG, Q, meet, kin, exact, s);
+    else if (h->engine == 1) tile_launch_solve<FtDyn>(h, h->TG, Q, meet, kin, exact, s);
     else if (kin) hipLaunchKernelGGL(rnde_ffjord_solve_kernel<true>, dim3(1), dim3(h->T), h->lds_bytes, s, Q);
     else hipLaunchKernelGGL(rnde_ffjord_solve_kernel<false>, dim3(1), dim3(h->T), h->lds_bytes, s, Q);
     FCHK(h, hipGetLastError());
@@ -449,22 +454,29 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
     if (taped) {
         rnde_ffjord::Tape& T = h->tp;
         T.meta = h->h_meta; T.n_att = h->n_att; T.n_acc = h->n_acc; T.B = B;
-        T.reltol = P.reltol; T.abstol = P.abstol; T.e = e_dev; T.p = p_dev; T.kin = kin; T.valid = true;
+        T.reltol = P.reltol; T.abstol = P.abstol; T.e = exact ? nullptr : e_dev; T.p = p_dev; T.kin = kin; T.exact = exact; T.valid = true;
     }
     return RNDE_OK;
 }
 
 static rnde_status ff_forward(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0, float t1, uint64_t seed,
                               const float* steps_host, int32_t n_steps, float* logpx_dev, float* z_out_dev, int64_t* nfe_out, float* saveval_host,
-                              int32_t* n_saveval_out, int32_t keep_tape, void* stream, bool kin = false, float* reg_out_dev = nullptr) {
+                              int32_t* n_saveval_out, int32_t keep_tape, void* stream, bool kin = false, float* reg_out_dev = nullptr,
+                              bool exact = false) {
     if (!h) return RNDE_ERR_BAD_ARG;
+    if (exact && h->engine == 0) {
+        h->err = "TrackedFFJORD exact trace: the one-workgroup engine does not serve the exact forward; create the handle with "
+                 "rnde_ffjord_create_tiled (engine = \"tiled\") or rnde_ffjord_create_chain";
+        return RNDE_ERR_BAD_ARG;
+    }
+    if (exact && kin) { h->err = "TrackedFFJORD exact trace: the kinetic energy rows are not served with it (the Jacobian norm row is defined on the probe)"; return RNDE_ERR_BAD_ARG; }
     if (!logpx_dev) { h->err = "logpx_dev is required"; return RNDE_ERR_BAD_ARG; }
     if (kin) {
         if (!reg_out_dev) { h->err = "reg_out_dev (2 x B: the kinetic energy row, then the Jacobian norm row) is required"; return RNDE_ERR_BAD_ARG; }
         if (rnde_status kst = ff_kinetic_ready(h)) return kst;
     }
     rnde_status st = ff_solve(h, +1, x_dev, p_dev, e_dev, B, t0, t1, seed, steps_host, n_steps, logpx_dev, z_out_dev, keep_tape, (hipStream_t)stream,
-                              kin ? reg_out_dev : nullptr);
+                              kin ? reg_out_dev : nullptr, exact);
     if (st != RNDE_OK) return st;
     if (nfe_out) *nfe_out = 3 + 6 * (int64_t)h->n_att;      // 2 (initial dt) + 1 (fsalfirst) + 6 per attempt, as rnde_node_forward
     int nsv = 0;
@@ -506,6 +518,21 @@ extern "C" rnde_status rnde_ffjord_forward_kinetic_replay(rnde_ffjord* h, const 
                       true, reg_out_dev);
 }
 
+extern "C" rnde_status rnde_ffjord_forward_exact(rnde_ffjord* h, const float* x_dev, const float* p_dev, int32_t B, float t0, float t1, float* logpx_dev,
+                                                 float* z_out_dev, int64_t* nfe_out, float* saveval_host, int32_t* n_saveval_out, int32_t keep_tape,
+                                                 void* stream) {
+    return ff_forward(h, x_dev, p_dev, nullptr, B, t0, t1, 0, nullptr, 0, logpx_dev, z_out_dev, nfe_out, saveval_host, n_saveval_out, keep_tape, stream,
+                      false, nullptr, true);
+}
+
+extern "C" rnde_status rnde_ffjord_forward_exact_replay(rnde_ffjord* h, const float* x_dev, const float* p_dev, int32_t B, float t0, float t1,
+                                                        const float* steps_host, int32_t n_steps, float* logpx_dev, float* z_out_dev, int64_t* nfe_out,
+                                                        float* saveval_host, int32_t* n_saveval_out, int32_t keep_tape, void* stream) {
+    if (!steps_host) { if (h) h->err = "replay: steps_host is required"; return RNDE_ERR_BAD_ARG; }
+    return ff_forward(h, x_dev, p_dev, nullptr, B, t0, t1, 0, steps_host, n_steps, logpx_dev, z_out_dev, nfe_out, saveval_host, n_saveval_out, keep_tape,
+                      stream, false, nullptr, true);
+}
+
 extern "C" rnde_status rnde_ffjord_step_log(rnde_ffjord* h, float* log_host, int32_t capacity, int32_t* n_attempts_out) {
     if (!h || !n_attempts_out) return RNDE_ERR_BAD_ARG;
     *n_attempts_out = h->n_att;
@@ -529,7 +556,8 @@ extern "C" rnde_status rnde_ffjord_steps(rnde_ffjord* h, float* steps_host, int3
     return RNDE_OK;
 }
 
-// The reverse sweep of the taped forward; a kinetic tape runs the KIN = true kernels with reg_bar_dev (NULL: zeros).
+// The reverse sweep of the taped forward; a kinetic tape runs the KIN = true kernels with reg_bar_dev (NULL: zeros), an exact tape the
+// exact variant of the tile driver's sweep.
 static rnde_status ff_backward(rnde_ffjord* h, const float* logpx_bar_dev, const float* saveval_bar_host, const float* reg_bar_dev, float* p_bar_dev,
                                float* x_bar_dev, void* stream) {
     if (!h) return RNDE_ERR_BAD_ARG;
@@ -556,8 +584,8 @@ static rnde_status ff_backward(rnde_ffjord* h, const float* logpx_bar_dev, const
     Q.reg_bar = reg_bar_dev;
     FCHK(h, hipEventRecord(h->ev[2], s));
     if (h->engine >= 1) {
-        if (h->engine == 2) tile_launch_reverse<FcDyn>(h, h->CG, Q, T.kin, s);
-        else tile_launch_reverse<FtDyn>(h, h->TG, Q, T.kin, s);
+        if (h->engine == 2) tile_launch_reverse<FcDyn>(h, h->CG, Q, T.kin, T.exact, s);
+        else tile_launch_reverse<FtDyn>(h, h->TG, Q, T.kin, T.exact, s);
         FCHK(h, hipGetLastError());
         hipLaunchKernelGGL(rnde_ffjordt_reduce_kernel, dim3((h->G.P + 255) / 256), dim3(256), 0, s, (const float*)h->pacc, h->G.P, (T.B + 15) / 16, p_bar_dev);
     } else {
@@ -581,6 +609,10 @@ extern "C" rnde_status rnde_ffjord_backward(rnde_ffjord* h, const float* logpx_b
 extern "C" rnde_status rnde_ffjord_backward_kinetic(rnde_ffjord* h, const float* logpx_bar_dev, const float* reg_bar_dev, float* p_bar_dev,
                                                     float* x_bar_dev, void* stream) {
     if (!h) return RNDE_ERR_BAD_ARG;
+    if (h->tp.valid && h->tp.exact) {
+        h->err = "backward_kinetic: the taped forward is an exact-trace one, which has no kinetic energy rows (use rnde_ffjord_backward)";
+        return RNDE_ERR_BAD_ARG;
+    }
     if (h->tp.valid && !h->tp.kin) { h->err = "backward_kinetic: the taped forward has no kinetic energy rows (use rnde_ffjord_backward)"; return RNDE_ERR_BAD_ARG; }
     return ff_backward(h, logpx_bar_dev, nullptr, reg_bar_dev, p_bar_dev, x_bar_dev, stream);
 }

@@ -47,7 +47,7 @@ struct TileSolveParams {
     Geo G;
     const float* p;
     const float* x;                  // D x B caller layout
-    const float* e;                  // D x B caller layout (dir = +1), NULL (dir = -1: exact trace)
+    const float* e;                  // D x B caller layout (Hutchinson), NULL (exact trace)
     float* ws;                       // [10][R][Bp]: uprev, unew, (unused), k1..k7
     float* tape;                     // [max_attempts + 1][R][Bp] or NULL
     float* logpx;                    // B (dir = +1) or NULL
@@ -56,6 +56,7 @@ struct TileSolveParams {
     InitRec* initrec_t;              // [ntiles]: each tile's copy of the initial-step record (tile 0's is F.initrec)
     StepState* ctl_t;                // [ntiles]: where tiles other than 0 write the state before attempt 0
     float* scratch;                  // [ntiles][Dyn::scratch_floats] (FtDyn: the exact trace's H x H buffer) or NULL
+    int exact;                       // the trace row is -tr J (sampling always; a forward solve or replay when the caller asks), not -e . eJ
     MwMeet meet;
     unsigned* xcc;                   // [ntiles] (one-XCD meeting: the host checks they agree)
     int xcd_slot;
@@ -68,7 +69,7 @@ template <class Geo>
 struct TileRevParams {
     Geo G;
     const float* p;
-    const float* e;                   // D x B caller layout
+    const float* e;                   // D x B caller layout (NULL on an exact tape)
     const float* tape;                // [n_acc + 1][R][Bp]
     const FfStepRec* rec;             // [n_acc]
     const float* logpx_bar;           // B
@@ -78,6 +79,8 @@ struct TileRevParams {
     int n_acc, B, Bp;
     float reltol, abstol;
     const float* reg_bar;             // kinetic sweep: 2 x B cotangents of (lambda1, lambda2), or NULL (zeros)
+    int exact;                        // the tape of an exact-trace forward (never with KIN)
+    float* scratch;                   // exact: [ntiles][Dyn::scratch_floats] or NULL, as the solve's
 };
 
 // Publish this tile's three partials (wave 0), collect everybody's sums in tile order; false when the meeting timed out (every thread).
@@ -100,7 +103,8 @@ __device__ __forceinline__ bool tile_meet(const MwMeet& M, float* red, int seq, 
     return ok;
 }
 
-// The whole adaptive solve in one launch: forward (dir = +1, Hutchinson), replay along P.replay, sampling (dir = -1, exact trace, tau = t1 - t).
+// The whole adaptive solve in one launch: forward (dir = +1; Hutchinson, or Q.exact: the exact trace with no probe), replay along P.replay,
+// sampling (dir = -1, exact trace, tau = t1 - t).
 template <class Dyn, bool KIN>
 __global__ __launch_bounds__(kFtThreads) void rnde_ffjord_tile_solve_kernel(const TileSolveParams<typename Dyn::Geo> Q) {
     extern __shared__ float ft_smem[];
@@ -118,14 +122,14 @@ __global__ __launch_bounds__(kFtThreads) void rnde_ffjord_tile_solve_kernel(cons
     Dyn::load_params(G, Q.p, L.W, tid);
     for (int idx = tid; idx < G.DP * 16; idx += kFtThreads) {     // (the data rows of L.X are rewritten below by the thread that zeroes them)
         const int r = idx >> 4, col = col0 + (idx & 15);
-        L.E[idx] = (Q.dir > 0 && r < D && col < B) ? Q.e[(size_t)col * D + r] : 0.f;
+        L.E[idx] = (!Q.exact && r < D && col < B) ? Q.e[(size_t)col * D + r] : 0.f;
         L.X[idx] = 0.f;
     }
     const size_t RB = (size_t)R * Bp;
     float* U = Q.ws + col0;
     float* UN = Q.ws + RB + col0;
     auto K = [&](int s) { return Q.ws + (size_t)(3 + s) * RB + col0; };
-    const int exact = Q.dir < 0 ? 1 : 0;
+    const int exact = Q.exact;
     const float fsign = Q.dir > 0 ? 1.f : -1.f, tsign = Q.dir > 0 ? -1.f : 1.f;
     float* scratch = Q.scratch ? Q.scratch + (size_t)tile * Dyn::scratch_floats(G) : nullptr;
     auto eval = [&](float time, float* kout) {
@@ -249,18 +253,23 @@ __global__ __launch_bounds__(kFtThreads) void rnde_ffjord_tile_solve_kernel(cons
 }
 
 // The reverse sweep of the taped solve; KIN: the stage cotangent is (lz, ll, l1, l2) over R = D + 3 rows.
+// Q.exact (the tape of an exact-trace forward): the stages are recomputed with the exact trace, and the trace row's cotangent goes through
+// -tr J = -sum_i e_i . (e_i J) over the unit probes.  Dyn::vjp is linear in kb, so a stage takes D + 1 calls of it: one with L.E = 0 and the
+// whole kb (the trace row is quadratic in the probe and gives nothing there), then one per unit probe with kb cut down to its trace row.
 template <class Dyn, bool KIN>
 __global__ __launch_bounds__(kFtThreads) void rnde_ffjord_tile_reverse_kernel(const TileRevParams<typename Dyn::Geo> Q) {
     extern __shared__ float ft_smem[];
     const typename Dyn::Geo& G = Q.G;
     const int tile = blockIdx.x, tid = threadIdx.x, D = G.D, R = D + (KIN ? 3 : 1), Bp = Q.Bp, col0 = tile * 16, nel = R * 16;
     const typename Dyn::Lds L = Dyn::lds(G, ft_smem);
+    const int exact = KIN ? 0 : Q.exact;
     Dyn::load_params(G, Q.p, L.W, tid);
     for (int idx = tid; idx < G.DP * 16; idx += kFtThreads) {
         const int r = idx >> 4, col = col0 + (idx & 15);
-        L.E[idx] = (r < D && col < Q.B) ? Q.e[(size_t)col * D + r] : 0.f;
+        L.E[idx] = (!exact && r < D && col < Q.B) ? Q.e[(size_t)col * D + r] : 0.f;
         L.X[idx] = 0.f;
     }
+    float* scratch = (exact && Q.scratch) ? Q.scratch + (size_t)tile * Dyn::scratch_floats(G) : nullptr;
     float* ws = Q.ws + (size_t)tile * Dyn::rev_ws_floats(G, KIN);
     const size_t RS = (size_t)R * 16;
     auto Ys = [&](int s) { return ws + (size_t)s * RS; };
@@ -297,7 +306,7 @@ __global__ __launch_bounds__(kFtThreads) void rnde_ffjord_tile_reverse_kernel(co
                 Ys(s)[idx] = y;
                 if (r < D) L.X[idx] = y;
             }
-            Dyn::template eval<KIN>(G, L, t + kTsC[s] * dt, Ks(s), 16, 0, 1.f, -1.f, nullptr, tid);
+            Dyn::template eval<KIN>(G, L, t + kTsC[s] * dt, Ks(s), 16, exact, 1.f, -1.f, scratch, tid);
         }
         for (int idx = tid; idx < nel; idx += kFtThreads) {
             for (int s = 0; s < 7; ++s) Kb(s)[idx] = 0.f;
@@ -328,7 +337,19 @@ __global__ __launch_bounds__(kFtThreads) void rnde_ffjord_tile_reverse_kernel(co
                 for (int idx = tid; idx < nel; idx += kFtThreads) Yb[idx] = 0.f;
                 __syncthreads();
             }
-            Dyn::template vjp<KIN>(G, L, t + kTsC[s] * dt, Ys(s), Kb(s), Yb, V, pacc, tid);
+            const int npass = exact ? D + 1 : 1;
+            for (int pass = 0; pass < npass; ++pass) {
+                if (exact) {          // pass 0: L.E = 0, the whole kb; pass i: the unit probe e_i, kb's trace row alone (Kb(s) is not read again)
+                    __syncthreads();
+                    for (int idx = tid; idx < G.DP * 16; idx += kFtThreads)
+                        L.E[idx] = ((idx >> 4) == pass - 1 && col0 + (idx & 15) < Q.B) ? 1.f : 0.f;
+                    if (pass == 1)
+                        for (int idx = tid; idx < D * 16; idx += kFtThreads) Kb(s)[idx] = 0.f;
+                    __syncthreads();
+                }
+                Dyn::template vjp<KIN>(G, L, t + kTsC[s] * dt, Ys(s), Kb(s), Yb, V, pacc, tid);
+            }
+            // (exact: L.E is left holding the last unit probe; harmless, neither dynamics' eval reads L.E when exact is set)
             for (int idx = tid; idx < nel; idx += kFtThreads) {
                 const float y = Yb[idx];
                 UBn[idx] += y;

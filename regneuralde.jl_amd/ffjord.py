@@ -22,6 +22,10 @@ and no layer input above 64 (the time row apart), any of the six Dense activatio
     model = TDChain(Dense(3, 10, "tanh"), Dense(11, 2))
     ffjord = TrackedFFJORD(model, [0.0, 1.0], True, False, "Tsit5", reltol=1.4e-3, abstol=1.4e-3, engine="tiled")   # p = destructure(model)
 
+Exact trace (an extension: the reference evaluates -tr J only inside sample()): ffjord(x, exact=True) solves [z; l] with dl / dt = -tr J, so
+logpx carries no probe and no variance; same 5-tuple, differentiable (the reverse sweep costs about D + 1 Hutchinson ones).  On
+engine="tiled" only, without e, and not together with the kinetic rows; loglikelihood(model, batches, exact=True) reports with it.
+
 Refused with a message that names the limit: any other dynamics, a chain model on engine="workgroup", and widths above the engine's limit.
 """
 import ctypes as C
@@ -215,6 +219,9 @@ MAX_TAPES = 4     # taped forwards that may wait for their backward at the same 
 
 
 class _Solve(torch.autograd.Function):
+    """The {false} / {true} forward and its reverse.  e = None: the exact-trace forward (rnde_ffjord_forward_exact / _replay, no probe); the tape
+    remembers that it is exact, so the reverse pass is the same call of rnde_ffjord_backward."""
+
     @staticmethod
     def forward(ctx, x, p, e, layer, t0, t1, steps, keep):
         L = _lib.lib()
@@ -227,11 +234,17 @@ class _Solve(torch.autograd.Function):
         nsv = C.c_int32()
         if keep:
             hd.busy, hd.gen = True, hd.gen + 1
-        if steps is None:
+        arr = None if steps is None else (C.c_float * len(steps))(*steps)
+        if e is None and steps is None:
+            st = L.rnde_ffjord_forward_exact(h, x.data_ptr(), p.data_ptr(), B, t0, t1, logpx.data_ptr(), None, C.byref(nfe), sv, C.byref(nsv), keep,
+                                             _stream(x.device))
+        elif e is None:
+            st = L.rnde_ffjord_forward_exact_replay(h, x.data_ptr(), p.data_ptr(), B, t0, t1, arr, len(steps) // 2, logpx.data_ptr(), None,
+                                                    C.byref(nfe), sv, C.byref(nsv), keep, _stream(x.device))
+        elif steps is None:
             st = L.rnde_ffjord_forward(h, x.data_ptr(), p.data_ptr(), e.data_ptr(), B, t0, t1, 0, logpx.data_ptr(), None, C.byref(nfe), sv, C.byref(nsv),
                                        keep, _stream(x.device))
         else:
-            arr = (C.c_float * len(steps))(*steps)
             st = L.rnde_ffjord_forward_replay(h, x.data_ptr(), p.data_ptr(), e.data_ptr(), B, t0, t1, 0, arr, len(steps) // 2, logpx.data_ptr(), None,
                                               C.byref(nfe), sv, C.byref(nsv), keep, _stream(x.device))
         layer._last = hd
@@ -325,7 +338,8 @@ class TrackedFFJORD:
     """TrackedFFJORD(model, tspan, time_dep, regularize, solver; reltol, abstol, ...) (ffjord.jl:1-51).  regularize selects the call
     method: False -> TrackedFFJORD{false} (returns logpx, 0, 0, nfe, None; called with regularize=True: logpx, lambda1, lambda2, nfe, None with
     the kinetic energy and the Jacobian norm rows, differentiable), True -> TrackedFFJORD{true} (returns logpx, 0, 0, nfe, sv with
-    sv.saveval = EEst * dt per accepted step, differentiable).  engine: "workgroup" (default) or "tiled" (see the module docstring)."""
+    sv.saveval = EEst * dt per accepted step, differentiable).  Called with exact=True (engine="tiled"; no e, no kinetic rows): the same
+    5-tuple with logpx from the exact trace -tr J instead of the Hutchinson estimate, differentiable.  engine: "workgroup" (default) or "tiled" (see the module docstring)."""
 
     def __init__(self, model, tspan, time_dep, regularize, solver="Tsit5", *, reltol=1.4e-8, abstol=1.4e-8, max_batch=1024, max_attempts=4096,
                  cb_save_start=True, device=0, dynamics=None, engine="workgroup", **kwargs):
@@ -397,8 +411,17 @@ class TrackedFFJORD:
         _lib.check(None, _lib.lib().rnde_normal_fill(out.data_ptr(), out.numel(), self._seed, 0x46464A4F, _stream(device)))
         return out
 
-    def __call__(self, x, p=None, e=None, regularize=False, steps=None):
+    def __call__(self, x, p=None, e=None, regularize=False, steps=None, exact=False):
         kinetic = bool(regularize) and not self.regularize      # ({true} never passes the keyword on: ffjord.jl:119)
+        if exact:
+            if e is not None:
+                raise ValueError("TrackedFFJORD: exact=True evaluates -tr J and takes no probe; call it without e")
+            if kinetic:
+                raise ValueError("TrackedFFJORD: exact=True together with regularize=True on a {false} layer (kinetic energy and Jacobian norm "
+                                 "rows) is not served: the Jacobian norm row is defined on the probe")
+            if self.engine != "tiled":
+                raise ValueError("TrackedFFJORD: exact=True is served on engine=\"tiled\" only (the tiled engine's solve and reverse sweep); "
+                                 f"got engine={self.engine!r}")
         if kinetic:
             check_kinetic_served(self.model, self.engine)
         p = self.p if p is None else p
@@ -407,6 +430,14 @@ class TrackedFFJORD:
         x = x.contiguous().float()
         if x.dim() != 2 or x.shape[1] != self.in_dims:
             raise ValueError(f"x must be (B, {self.in_dims})")
+        if exact:
+            p = p.contiguous()
+            if p.numel() != self.n_params:
+                raise ValueError(f"p must hold {self.n_params} parameters; got {p.numel()}")
+            keep = torch.is_grad_enabled() and (x.requires_grad or p.requires_grad)
+            logpx, saveval = _Solve.apply(x, p, None, self, self.tspan[0], self.tspan[1], steps, keep)
+            zero = torch.zeros(x.shape[0], device=x.device)
+            return logpx, zero, zero, self.last_nfe, (SavedValues(saveval) if self.regularize else None)
         if e is None:
             e = self.draw_normal(self.in_dims, x.shape[0], x.device)
         elif tuple(e.shape) != tuple(x.shape) or not e.is_cuda:
@@ -494,12 +525,12 @@ def sample(ffjord, indims, p=None, nsamples=1, z=None):
 
 
 @torch.no_grad()
-def loglikelihood(model, batches, p=None):
-    """src/metrics.jl:20-33: sum of logpx over the batches / the number of columns."""
+def loglikelihood(model, batches, p=None, exact=False):
+    """src/metrics.jl:20-33: sum of logpx over the batches / the number of columns.  exact=True: logpx from the exact trace (no probe)."""
     total, n = 0.0, 0
     for xb in batches:
         x = torch.as_tensor(xb, dtype=torch.float32).cuda(model.device)
-        total += float(model(x, p)[0].sum())
+        total += float((model(x, p, exact=True) if exact else model(x, p))[0].sum())
         n += x.shape[0]
     return total / n
 

@@ -13,7 +13,12 @@ tree, which it puts on sys.path itself.  Solve and reverse times per step come f
 loss = -mean(logpx) + LK mean(lambda1) + LJ mean(lambda2) (kinetic energy, Jacobian norm); the entry "kinetic" goes to
 profiles/ffjord_gaussian_kinetic.json.
 
+--exact-eval reports the train / test log-likelihood with the exact trace (no probe, no variance) and --exact-train also trains through it
+(ffjord(x, p, exact=True): the reverse sweep costs about D + 1 = 3 Hutchinson ones at D = 2); both run the layer on engine="tiled", and their
+entries go to profiles/ffjord_gaussian_exact.json.  The equal-work comparison stays the Hutchinson step's.
+
     python tools/train_ffjord_gaussian.py --regularize 1
+    python tools/train_ffjord_gaussian.py --regularize 1 --exact-eval --exact-train
     python tools/train_ffjord_gaussian.py --regularize 0 --kinetic 0.01 0.01
 """
 import argparse
@@ -42,11 +47,18 @@ def main():
     ap.add_argument("--reps", type=int, default=7, help="timed runs of each side of the equal-work comparison (after 2 warm-up runs)")
     ap.add_argument("--kinetic", type=float, nargs=2, default=None, metavar=("LK", "LJ"),
                     help="train with LK mean(lambda1) + LJ mean(lambda2) (kinetic energy, Jacobian norm); needs --regularize 0")
-    ap.add_argument("--out", default=None, help="default: profiles/ffjord_gaussian.json (profiles/ffjord_gaussian_kinetic.json with --kinetic)")
+    ap.add_argument("--exact-eval", action="store_true", help="train / test log-likelihood with the exact trace (engine=\"tiled\")")
+    ap.add_argument("--exact-train", action="store_true", help="train through the exact trace too (engine=\"tiled\"; not with --kinetic)")
+    ap.add_argument("--out", default=None, help="default: profiles/ffjord_gaussian.json (profiles/ffjord_gaussian_kinetic.json with --kinetic, "
+                                                "profiles/ffjord_gaussian_exact.json with --exact-eval / --exact-train)")
     a = ap.parse_args()
     if a.kinetic and a.regularize:
         ap.error("--kinetic needs --regularize 0 (the {true} method never passes regularize on)")
-    a.out = a.out or os.path.join(ROOT, "profiles", "ffjord_gaussian_kinetic.json" if a.kinetic else "ffjord_gaussian.json")
+    if a.kinetic and a.exact_train:
+        ap.error("--exact-train does not go with --kinetic (the Jacobian norm row is defined on the probe)")
+    exact_any = a.exact_eval or a.exact_train
+    a.out = a.out or os.path.join(ROOT, "profiles", "ffjord_gaussian_kinetic.json" if a.kinetic else
+                                  ("ffjord_gaussian_exact.json" if exact_any else "ffjord_gaussian.json"))
     kin = bool(a.kinetic)
     lk, lj = a.kinetic or (0.0, 0.0)
     import regneuralde_jl_amd as rn
@@ -56,8 +68,10 @@ def main():
     dev = torch.device("cuda", 0)
     tr, te = rn.load_gaussian_mixture(a.batch, nsamples=2048, ngaussians=6, seed=a.seed)
     model = rn.ffjord.MLPDynamics(2, 16, generator=torch.Generator().manual_seed(a.seed))
-    ff = rn.TrackedFFJORD(model, [0.0, 1.0], True, bool(a.regularize), "Tsit5", reltol=1.4e-8, abstol=1.4e-8, max_batch=a.batch)
+    ff = rn.TrackedFFJORD(model, [0.0, 1.0], True, bool(a.regularize), "Tsit5", reltol=1.4e-8, abstol=1.4e-8, max_batch=a.batch,
+                          **(dict(engine="tiled") if exact_any else {}))
     p = ff.p.clone().requires_grad_(True)
+    ll = lambda data: rn.loglikelihood(ff, data, p.detach(), exact=a.exact_eval)
     opt = rn.FluxADAM([p], eta=4e-2, weight_decay=1e-5)
     lam0, lam1 = 2.0e3, 1.0e3
     k = np.log(lam0 / lam1) / a.epochs
@@ -73,7 +87,7 @@ def main():
 
     rows = []
     nfe, ti = infer()
-    rows.append(dict(epoch=0, nfe=nfe, train_ll=rn.loglikelihood(ff, tr, p.detach()), test_ll=rn.loglikelihood(ff, te, p.detach()),
+    rows.append(dict(epoch=0, nfe=nfe, train_ll=ll(tr), test_ll=ll(te),
                      train_s=0.0, infer_s=ti))
     print(rows[-1], flush=True)
     step_ms, solve_ms, rev_ms, att, accd = [], [], [], [], []
@@ -84,7 +98,7 @@ def main():
             x = torch.from_numpy(xb).to(dev)
             _sync()
             t0 = time.perf_counter()
-            logpx, l1, l2, nfe, sv = ff(x, p, regularize=kin)
+            logpx, l1, l2, nfe, sv = ff(x, p, exact=True) if a.exact_train else ff(x, p, regularize=kin)
             loss = -logpx.mean() + (lam * sv.saveval.mean() if a.regularize else 0.0)
             if kin:
                 loss = loss + lk * l1.mean() + lj * l2.mean()
@@ -98,7 +112,7 @@ def main():
                 s, r, n, m = ff.timing()
                 solve_ms.append(s); rev_ms.append(r); att.append(n); accd.append(m)
         nfe, ti = infer()
-        rows.append(dict(epoch=epoch, nfe=nfe, train_ll=rn.loglikelihood(ff, tr, p.detach()), test_ll=rn.loglikelihood(ff, te, p.detach()),
+        rows.append(dict(epoch=epoch, nfe=nfe, train_ll=ll(tr), test_ll=ll(te),
                          train_s=timing, infer_s=ti, loss_last=float(loss.detach())))
         print(rows[-1], flush=True)
     samp = []
@@ -151,7 +165,7 @@ def main():
 
     dev_t = timed(device_step)
     eager_t = timed(eager_step)
-    res = dict(regularize=a.regularize, kinetic=list(a.kinetic) if kin else None, epochs=rows, sampling_time_s=min(samp), batch=a.batch,
+    res = dict(regularize=a.regularize, exact_eval=a.exact_eval, exact_train=a.exact_train, engine=ff.engine, kinetic=list(a.kinetic) if kin else None, epochs=rows, sampling_time_s=min(samp), batch=a.batch,
                train_step_ms_median=float(np.median(step_ms)), solve_launch_ms_median=float(np.median(solve_ms)),
                reverse_ms_median=float(np.median(rev_ms)), attempts_median=float(np.median(att)), accepted_median=float(np.median(accd)),
                us_per_forward_attempt=float(np.median(np.array(solve_ms) / np.array(att)) * 1e3),

@@ -15,7 +15,12 @@ gaussian experiment's MLPDynamics(2, 16), B = 1024, for the comparison with the 
 loss = -mean(logpx) + LK mean(lambda1) + LJ mean(lambda2) (kinetic energy, Jacobian norm); the entry "kinetic" goes to
 profiles/ffjord_tabular_kinetic.json.
 
+--exact-eval reports the train / test log-likelihood with the exact trace (ffjord(x, p, exact=True): no probe, no variance) on
+engine="tiled"; training stays on the Hutchinson estimate (an exact reverse sweep costs about D + 1 = 44 of them here).  The entry goes to
+profiles/ffjord_tabular_exact.json.
+
     python tools/train_ffjord_tabular.py --regularize 1 --epochs 3
+    python tools/train_ffjord_tabular.py --regularize 1 --epochs 3 --exact-eval
     python tools/train_ffjord_tabular.py --regularize 0 --kinetic 0.01 0.01 --epochs 3
 """
 import argparse
@@ -78,11 +83,16 @@ def main():
     ap.add_argument("--reps", type=int, default=7, help="timed runs of each side of the equal-work comparison (after 2 warm-up runs)")
     ap.add_argument("--kinetic", type=float, nargs=2, default=None, metavar=("LK", "LJ"),
                     help="train with LK mean(lambda1) + LJ mean(lambda2) (kinetic energy, Jacobian norm); needs --regularize 0")
-    ap.add_argument("--out", default=None, help="default: profiles/ffjord_tabular.json (profiles/ffjord_tabular_kinetic.json with --kinetic)")
+    ap.add_argument("--exact-eval", action="store_true", help="train / test log-likelihood with the exact trace (needs --engine tiled)")
+    ap.add_argument("--out", default=None, help="default: profiles/ffjord_tabular.json (profiles/ffjord_tabular_kinetic.json with --kinetic, "
+                                                "profiles/ffjord_tabular_exact.json with --exact-eval)")
     a = ap.parse_args()
     if a.kinetic and a.regularize:
         ap.error("--kinetic needs --regularize 0 (the {true} method never passes regularize on)")
-    a.out = a.out or os.path.join(ROOT, "profiles", "ffjord_tabular_kinetic.json" if a.kinetic else "ffjord_tabular.json")
+    if a.exact_eval and a.engine != "tiled":
+        ap.error("--exact-eval needs --engine tiled (the exact trace is served by the tiled engine only)")
+    a.out = a.out or os.path.join(ROOT, "profiles", "ffjord_tabular_kinetic.json" if a.kinetic else
+                                  ("ffjord_tabular_exact.json" if a.exact_eval else "ffjord_tabular.json"))
     kin = bool(a.kinetic)
     lk, lj = a.kinetic or (0.0, 0.0)
     import regneuralde_jl_amd as rn
@@ -98,6 +108,7 @@ def main():
     model = rn.ffjord.MLPDynamics(D, H, generator=torch.Generator().manual_seed(a.seed))
     ff = rn.TrackedFFJORD(model, [0.0, 1.0], True, bool(a.regularize), "Tsit5", reltol=1.4e-8, abstol=1.4e-8, max_batch=a.batch, engine=a.engine)
     p = ff.p.clone().requires_grad_(True)
+    ll = lambda data: rn.loglikelihood(ff, data, p.detach(), exact=a.exact_eval)
     opt = rn.FluxADAM([p], eta=1e-2, weight_decay=1e-5)
     lam0, lam1 = 5.0e3, 1.0e3
     k = np.log(lam0 / lam1) / a.epochs
@@ -113,7 +124,7 @@ def main():
 
     rows = []
     nfe, ti = infer()
-    rows.append(dict(epoch=0, nfe=nfe, train_ll=rn.loglikelihood(ff, tr, p.detach()), test_ll=rn.loglikelihood(ff, te, p.detach()),
+    rows.append(dict(epoch=0, nfe=nfe, train_ll=ll(tr), test_ll=ll(te),
                      train_s=0.0, infer_s=ti))
     print(rows[-1], flush=True)
     step_ms, solve_ms, rev_ms, att, accd = [], [], [], [], []
@@ -138,7 +149,7 @@ def main():
                 s, r, n, m = ff.timing()
                 solve_ms.append(s); rev_ms.append(r); att.append(n); accd.append(m)
         nfe, ti = infer()
-        rows.append(dict(epoch=epoch, nfe=nfe, train_ll=rn.loglikelihood(ff, tr, p.detach()), test_ll=rn.loglikelihood(ff, te, p.detach()),
+        rows.append(dict(epoch=epoch, nfe=nfe, train_ll=ll(tr), test_ll=ll(te),
                          train_s=timing, infer_s=ti, loss_last=float(loss.detach())))
         print(rows[-1], flush=True)
     samp = []
@@ -191,7 +202,7 @@ def main():
 
     dev_t = timed(device_step)
     eager_t = timed(eager_step)
-    res = dict(regularize=a.regularize, kinetic=list(a.kinetic) if kin else None, engine=a.engine, data=("miniboone" if a.data else "synthetic"), epochs=rows, sampling_time_s=min(samp), batch=a.batch,
+    res = dict(regularize=a.regularize, exact_eval=a.exact_eval, kinetic=list(a.kinetic) if kin else None, engine=a.engine, data=("miniboone" if a.data else "synthetic"), epochs=rows, sampling_time_s=min(samp), batch=a.batch,
                train_step_ms_median=float(np.median(step_ms)), solve_launch_ms_median=float(np.median(solve_ms)),
                reverse_ms_median=float(np.median(rev_ms)), attempts_median=float(np.median(att)), accepted_median=float(np.median(accd)),
                us_per_forward_attempt=float(np.median(np.array(solve_ms) / np.array(att)) * 1e3),
