@@ -389,7 +389,7 @@ extern "C" rnde_status rnde_node_create(const rnde_node_config* c, rnde_node** o
     ok &= dm((void**)&h->spwB, (size_t)h->sMT * h->sK2b * 64 * 16) && dm((void**)&h->spwD, (size_t)h->sHT * h->sMT * 64 * 16);
     ok &= dm((void**)&h->spwBt, (size_t)h->sMT * h->sKHb * 64 * 16) && dm((void**)&h->spwDt, (size_t)h->sHT * h->sMT * 64 * 16);
     ok &= dm((void**)&h->slab2, (size_t)2 * (h->Bpad_max / 16) * h->sR * h->sHT * 64 * 16);
-    const size_t tslab_bytes = (size_t)3 * (h->Bpad_max / 16) * h->sR * h->sHT * 64 * 16;    // three buffers of one 16-byte entry per lane and tile
+    const size_t tslab_bytes = (size_t)kSlabBufs * (h->Bpad_max / 16) * h->sR * h->sHT * 64 * 16;    // buffers of one 16-byte entry per lane and tile: three for the attempts, two for the one-launch solve's start-up
     h->tslab_bytes = tslab_bytes;
     ok &= dm((void**)&h->tslab, tslab_bytes);
     // mailbox: [0) final controller state | [512) initial-step record | [1016) abort word of the persistent kernels, [1024) their
@@ -424,8 +424,8 @@ extern "C" rnde_status rnde_node_create(const rnde_node_config* c, rnde_node** o
         h->stage_generic = (c->stage_generic != 0 || getenv("RNDE_STAGE_GENERIC") != nullptr) ? 1 : 0;
         if (const char* e6 = getenv("RNDE_STAGE_SOLVE")) h->stage_solve = atoi(e6);
     }
-    if (h->persist == 1 && h->stage_solve && c->max_attempts < 8192) {      // meeting granules of the one-launch solve: [attempt][3][256] x 8 bytes
-        const size_t xb = (size_t)(c->max_attempts + 1) * 3 * 256 * 8;
+    if (h->persist == 1 && h->stage_solve && c->max_attempts + kSolveInitRows < 8192) {      // meeting granules of the one-launch solve: [attempt | the start-up's two meetings][3][256] x 8 bytes
+        const size_t xb = (size_t)(c->max_attempts + kSolveInitRows) * 3 * 256 * 8;
         if (hipMalloc((void**)&h->sxch, xb) != hipSuccess) { g_create_err = "device allocation failed"; rnde_node_destroy(h); return RNDE_ERR_HIP; }
         hipMemset(h->sxch, 0, xb);
     }
@@ -785,6 +785,7 @@ static rnde_status forward_core(rnde_node* h, const float* x_dev, const float* p
     StageParams SQ{};
     ChainParams CQ{};
     MwParams MQ{};
+    bool stage_one_launch = false, solve_fold = false;
     if (h->engine == 3) {
         CQ = make_chain_params(h, P);
         if (h->mw) {
@@ -802,12 +803,19 @@ static rnde_status forward_core(rnde_node* h, const float* x_dev, const float* p
         if (!keep_tape) { st = stage_pack_weights(h, p_dev, s); if (st != RNDE_OK) return st; }
         SQ = make_stage_params(h, P, keep_tape ? h->pcopy : p_dev);
         if (stage_epart_reduce(h, SQ)) SQ.F.esum = (const double*)(h->errpart + 6 * (size_t)h->nwg_max + 256);      // (inside errpart's allocation, 8-byte aligned)
-        HIPCHK(h, launch_stage<SM_I1>(h, SQ, 0, 0, s));
-        HIPCHK(h, launch_stage<SM_I2>(h, SQ, 0, 0, s));
-        if ((st = couple_sum(h, P.initpart, 2LL * P.nwg, s)) != RNDE_OK) return st;            // norms of u0 and f0
-        HIPCHK(h, launch_stage<SM_I3>(h, SQ, 0, 0, s));
-        HIPCHK(h, launch_stage<SM_I4>(h, SQ, 0, 0, s));
-        if ((st = couple_sum(h, P.initpart + 2LL * P.nwg, P.nwg, s)) != RNDE_OK) return st;     // norm of f1 - f0
+        // the one-launch solve (below) runs the initial-step rule and the copy-out of the final state inside its own launch; RNDE_SOLVE_FOLD=0,
+        // read per call, keeps the four start-up launches and the finish launch around it (a redo after a time-out takes them too: persist != 1 then)
+        stage_one_launch = h->persist == 1 && h->stage_solve && h->sxch && SQ.C <= 32 && n_saveat == 0 && h->n_replay == 0 && !h->couple &&
+                           SQ.WT == 7 && SQ.HT == 7 && SQ.K2b == 7 && SQ.MT == 49 && SQ.R == 7 && h->D == 784 && h->H == 100 && !h->stage_generic;
+        if (stage_one_launch) { const char* e = getenv("RNDE_SOLVE_FOLD"); solve_fold = !(e && e[0] == '0'); }
+        if (!solve_fold) {
+            HIPCHK(h, launch_stage<SM_I1>(h, SQ, 0, 0, s));
+            HIPCHK(h, launch_stage<SM_I2>(h, SQ, 0, 0, s));
+            if ((st = couple_sum(h, P.initpart, 2LL * P.nwg, s)) != RNDE_OK) return st;            // norms of u0 and f0
+            HIPCHK(h, launch_stage<SM_I3>(h, SQ, 0, 0, s));
+            HIPCHK(h, launch_stage<SM_I4>(h, SQ, 0, 0, s));
+            if ((st = couple_sum(h, P.initpart + 2LL * P.nwg, P.nwg, s)) != RNDE_OK) return st;     // norm of f1 - f0
+        }
     }
     int launched = 0;
     int chunk = h->couple ? 16 : std::max(4, h->predicted);   // (coupled: the same launch count on every rank, whatever its history)
@@ -857,13 +865,12 @@ static rnde_status forward_core(rnde_node* h, const float* x_dev, const float* p
     }
     // ---- stage engine, headline geometry, all workgroups resident at once (<= 32 column tiles): the WHOLE adaptive solve is one launch
     // ---- (rnde_stage_solve.h: weights, uprev and k1 stay in registers across attempts, the error norm meets through agent-scope granules) ----
-    if (h->engine == 2 && h->persist == 1 && h->stage_solve && h->sxch && SQ.C <= 32 && n_saveat == 0 && h->n_replay == 0 && !h->couple &&
-        SQ.WT == 7 && SQ.HT == 7 && SQ.K2b == 7 && SQ.MT == 49 && SQ.R == 7 && h->D == 784 && h->H == 100 && !h->stage_generic) {
+    if (stage_one_launch) {
         PersistSync Y{h->tslab, h->pabort, h->pxcc, h->persist_spins};
         HIPCHK(h, slab_prepare(h, SQ.Bpad16, s));
-        if (++h->s_epoch >= 500000u) { h->s_epoch = 1; HIPCHK(h, hipMemsetAsync(h->sxch, 0, (size_t)(cap + 1) * 3 * 256 * 8, s)); }
+        if (++h->s_epoch >= 500000u) { h->s_epoch = 1; HIPCHK(h, hipMemsetAsync(h->sxch, 0, (size_t)(cap + kSolveInitRows) * 3 * 256 * 8, s)); }
         const int x3 = h->x3_fwd ? 1 : 0;      // (the weights were split by this forward's pack launch: x3_pack)
-        SolveSync Z{h->sxch, h->s_epoch, cap, h->x3B, h->x3D};
+        SolveSync Z{h->sxch, h->s_epoch, cap, h->x3B, h->x3D, solve_fold ? u_out_dev : nullptr, solve_fold ? 1 : 0};
 #ifdef RNDE_DIAG
         StageParams SD = SQ;
         if (getenv("RNDE_DIAG_SOLVE")) {      // cycle stamps of workgroup 0, every attempt (tools/diag_solve.py)
@@ -877,7 +884,7 @@ static rnde_status forward_core(rnde_node* h, const float* x_dev, const float* p
         HIPCHK(h, rnde_launch_stage_solve(&SQ, &Y, &Z, h->act2, x3, s));
 #endif
         if (h->timing) { HIPCHK(h, hipEventRecord(h->tev[1], s)); h->tev_fwd = true; }
-        hipLaunchKernelGGL(rnde_stage_finish_kernel, dim3(256), dim3(256), 0, s, SQ, -1, u_out_dev); HIPCHK(h, hipGetLastError());
+        if (!solve_fold) { hipLaunchKernelGGL(rnde_stage_finish_kernel, dim3(256), dim3(256), 0, s, SQ, -1, u_out_dev); HIPCHK(h, hipGetLastError()); }
         const int cnt = std::min(cap, std::max(64, 2 * h->predicted));      // step records copied speculatively; a longer solve fetches the rest below
         HIPCHK(h, hipMemcpyAsync(h->h_mbox, h->mbox, h->mbox_meta_off + (size_t)cnt * sizeof(StepMeta), hipMemcpyDeviceToHost, s));
         if (h->after_solve) {

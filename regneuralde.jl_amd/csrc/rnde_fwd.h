@@ -60,12 +60,16 @@ static __global__ __launch_bounds__(64) void rnde_epart_reduce_kernel(const Step
 // pre: the error partials of attempt n - 1 (first 256-entry block, this lane's four), requested by the caller ahead of this call --
 // the controller state and the partials are two cold loads that do not depend on each other
 // prev: the controller state of attempt n - 1 (P.ctl[(n - 1) & 1]), likewise loaded by the caller ahead of the call (both used when PRE and n > 0)
+// init (optional, n == 0 only): what the initial-step rule left for the first attempt's controller, held by a caller that ran the rule itself
+// (the one-launch solve's start-up, rnde_stage_solve.h) -- s2 is the sum of initpart[2] formed in sum_partials' order, d1 / dt0 the InitRec fields
+struct InitFold { double s2; float d1, dt0; int on; };      // on == 0: nothing held (as a null pointer)
 template <bool PRE>
 // sums (optional): the three cross-workgroup sums of attempt n - 1 {r^2, (k7-k6)^2, (unew-g6)^2} already formed by the caller (a kernel that
 // runs several attempts meets in memory instead of at a kernel boundary: rnde_chainmw.h MW_SOLVE) -- in the order sum_partials would
 // qold_pow (optional): powf(prev.qold, beta2) evaluated by the caller ahead of time (it does not depend on the attempt's error norm)
 __device__ __forceinline__ StepState advance_state_t(const StepParams& P, int n, int lane, bool writer, StepState* out, const float (&pre)[4],
-                                                     const StepState& prev, const double* sums = nullptr, const float* qold_pow = nullptr) {
+                                                     const StepState& prev, const double* sums = nullptr, const float* qold_pow = nullptr,
+                                                     const InitFold* init = nullptr) {
     StepState S;
     const double N = (double)P.D * (double)P.Bn;
     if (n == 0) {
@@ -75,8 +79,9 @@ __device__ __forceinline__ StepState advance_state_t(const StepParams& P, int n,
         if (P.forced) {
             S.t = P.forced_t; S.dtp = P.forced_dt;
         } else {
-            const float d1 = P.initrec->d1, dt0 = P.initrec->dt0, dtmax = P.t1 - P.t0;
-            const double s2 = sum_partials(P.initpart + 2 * P.nwg, P.nwg, lane);
+            const bool held = init && init->on;
+            const float d1 = held ? init->d1 : P.initrec->d1, dt0 = held ? init->dt0 : P.initrec->dt0, dtmax = P.t1 - P.t0;
+            const double s2 = held ? init->s2 : sum_partials(P.initpart + 2 * P.nwg, P.nwg, lane);
             const float d2 = (float)sqrt(s2 / N) / dt0;
             const float m = d1 > d2 ? d1 : d2;
             float dt1; int c1 = 0;

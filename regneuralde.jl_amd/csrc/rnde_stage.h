@@ -131,6 +131,49 @@ enum { SM_START = 0, SM_STAGE = 1, SM_LAST = 2, SM_I1 = 3, SM_I2 = 4, SM_I3 = 5,
 __device__ __forceinline__ f32x4 ld4(const float* colbase, int r0, int D, bool ok, bool vec) { return ld_tile(colbase, r0, D, ok, vec); }
 __device__ __forceinline__ void st4(float* colbase, int r0, int D, bool ok, bool vec, f32x4 v) { st_tile(colbase, r0, D, ok, vec, v); }
 
+// ---- the arithmetic of the initial-step rule, shared by rnde_stage_kernel's SM_I2 / SM_I3 / SM_I4 launches and by the start-up of
+// the one-launch solve (rnde_stage_solve.h), which runs the rule inside its own launch: 4 rows (r0 ..) of one column per call ----
+// SM_I2: partials of ||u0 / sk||^2 and ||f0 / sk||^2
+__device__ __forceinline__ void init_norm_parts_u0_f0(const StepParams& P, const f32x4& xv, const f32x4& kv, int r0, bool colok, float& part0, float& part1) {
+    if (colok) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (r0 + i < P.D) {
+                const float sk = P.abstol + fabsf(xv[i]) * P.reltol;
+                const float a = xv[i] / sk, b = kv[i] / sk;
+                part0 += a * a; part1 += b * b;
+            }
+        }
+    }
+}
+// SM_I3: dt0 from the two norm sums (s0, s1: initpart[0], initpart[1] summed in sum_partials' order); the writer thread leaves the InitRec fields
+__device__ __forceinline__ float init_dt0_rule(const StepParams& P, double s0, double s1, bool writer, float* d1_out = nullptr) {
+    const double N = (double)P.D * (double)P.Bn;
+    const float d0 = (float)sqrt(s0 / N), d1 = (float)sqrt(s1 / N), dtmax = P.t1 - P.t0;
+    float dt0;
+    int c0 = 0, cl = 0;
+    if (d0 < 1e-5f || d1 < 1e-5f) { dt0 = 1e-6f; c0 = 1; } else dt0 = (d0 / d1) / 100.f;
+    if (dtmax < dt0) { dt0 = dtmax; cl = 1; }
+    if (writer) { P.initrec->d0 = d0; P.initrec->d1 = d1; P.initrec->dt0 = dt0; P.initrec->dt0_const = c0; P.initrec->dt0_clamped = cl; }
+    if (d1_out) *d1_out = d1;
+    return dt0;
+}
+// SM_I3: the Euler step u1 = u0 + dt0 * f0
+__device__ __forceinline__ f32x4 init_euler_step(const f32x4& xv, float dt0, const f32x4& f0) { return xv + dt0 * f0; }
+// SM_I4: partial of ||(f1 - f0) / sk||^2
+__device__ __forceinline__ void init_norm_part_df(const StepParams& P, const f32x4& xv, const f32x4& f0, const f32x4& kv, int r0, bool colok, float& part0) {
+    if (colok) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (r0 + i < P.D) {
+                const float sk = P.abstol + fabsf(xv[i]) * P.reltol;
+                const float a = (kv[i] - f0[i]) / sk;
+                part0 += a * a;
+            }
+        }
+    }
+}
+
 template <int ACT2, int MODE>
 __global__ __launch_bounds__(64 * kSMaxW) void rnde_stage_kernel(const StageParams Q, const int n, const int s) {
     const StepParams& P = Q.F;
@@ -269,13 +312,8 @@ __global__ __launch_bounds__(64 * kSMaxW) void rnde_stage_kernel(const StagePara
 
     float dt0 = 0.f;
     if constexpr (MODE == SM_I3) {   // initial-step heuristic: dt0 from the norms of u0 and f0
-        const double N = (double)P.D * (double)P.Bn;
         const double s0 = sum_partials(P.initpart, P.nwg, lane), s1 = sum_partials(P.initpart + P.nwg, P.nwg, lane);
-        const float d0 = (float)sqrt(s0 / N), d1 = (float)sqrt(s1 / N), dtmax = P.t1 - P.t0;
-        int c0 = 0, cl = 0;
-        if (d0 < 1e-5f || d1 < 1e-5f) { dt0 = 1e-6f; c0 = 1; } else dt0 = (d0 / d1) / 100.f;
-        if (dtmax < dt0) { dt0 = dtmax; cl = 1; }
-        if (writer) { P.initrec->d0 = d0; P.initrec->d1 = d1; P.initrec->dt0 = dt0; P.initrec->dt0_const = c0; P.initrec->dt0_clamped = cl; }
+        dt0 = init_dt0_rule(P, s0, s1, writer);
     }
     if constexpr (MODE == SM_I4) dt0 = P.initrec->dt0;
 
@@ -415,35 +453,17 @@ __global__ __launch_bounds__(64 * kSMaxW) void rnde_stage_kernel(const StagePara
         } else if constexpr (MODE == SM_I2) {
             st4(kdst + (size_t)gcol * P.D, r0, P.D, true, vec, kv);
             const f32x4 xv = ld4(P.x + (size_t)gcol * P.D, r0, P.D, colok, P.xvec != 0);
-            if (colok) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (r0 + i < P.D) {
-                        const float sk = P.abstol + fabsf(xv[i]) * P.reltol;
-                        const float a = xv[i] / sk, b = kv[i] / sk;
-                        part0 += a * a; part1 += b * b;
-                    }
-                }
-            }
+            init_norm_parts_u0_f0(P, xv, kv, r0, colok, part0, part1);
         } else if constexpr (MODE == SM_I3) {
             const f32x4 xv = ld4(P.x + (size_t)gcol * P.D, r0, P.D, colok, P.xvec != 0);
             const f32x4 f0 = ld4(P.f0 + (size_t)gcol * P.D, r0, P.D, true, vec);
-            v = xv + dt0 * f0;
+            v = init_euler_step(xv, dt0, f0);
             st4(P.u1 + (size_t)gcol * P.D, r0, P.D, true, vec, v);
         } else if constexpr (MODE == SM_I4) {
             st4(kdst + (size_t)gcol * P.D, r0, P.D, true, vec, kv);
             const f32x4 xv = ld4(P.x + (size_t)gcol * P.D, r0, P.D, colok, P.xvec != 0);
             const f32x4 f0 = ld4(P.f0 + (size_t)gcol * P.D, r0, P.D, true, vec);
-            if (colok) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (r0 + i < P.D) {
-                        const float sk = P.abstol + fabsf(xv[i]) * P.reltol;
-                        const float a = (kv[i] - f0[i]) / sk;
-                        part0 += a * a;
-                    }
-                }
-            }
+            init_norm_part_df(P, xv, f0, kv, r0, colok, part0);
         } else if constexpr (MODE == SM_FEVAL2) {
             st4(P.dbg_out + (size_t)gcol * P.D, r0, P.D, colok, false, kv);
         }

@@ -25,7 +25,7 @@
 namespace rnde {
 
 struct PersistSync {
-    float* tslab;           // hand-off slabs [3][C][R][HT][64] f32x4 (see slab_put / slab_poll_sum)
+    float* tslab;           // hand-off slabs [3][C][R][HT][64] f32x4 (see slab_put / slab_poll_sum); two more buffers behind them: the one-launch solve's start-up (kSlabBufs, rnde_solve_sync.h)
     unsigned* abort_flag;   // [0] a hand-off timed out
     unsigned* xcc;          // [grid] XCC id of each workgroup (written every launch, checked by the host)
     int max_spins;          // bound of every polling loop (kPersistMaxSpins; RNDE_PERSIST_SPINS overrides it: the fallback test uses 0)

@@ -17,6 +17,9 @@
 // (entry index = attempt number, tag = epoch * 8192 + attempt + 1: nothing is ever reused inside a launch, nothing needs clearing).
 // All workgroups must be resident at once (<= 256, one per CU); every spin is bounded, a time-out raises the abort word the attempt
 // kernels use and the host redoes the solve launch by launch.
+// The launches that used to stand around it are inside it too (SolveSync::fold, host switch RNDE_SOLVE_FOLD): in front of the attempt loop the
+// initial-step rule -- the four SM_I* launches of rnde_stage_kernel, through the functions that kernel calls (rnde_stage.h), with hand-off buffers and
+// granule rows of its own -- and at the end the final state, stored to the caller's buffer from the registers that hold it (rnde_stage_finish_kernel's copy).
 #pragma once
 #ifndef RNDE_SOLVE_DEFER_TAPE
 #define RNDE_SOLVE_DEFER_TAPE 1
@@ -100,6 +103,50 @@ __device__ __forceinline__ StepState solve_state_get(const int* ss) {
     return S;
 }
 
+// The two Dense-layer products of a stage in their fp32-input-MFMA form (headline geometry, LDS operand images [16][116] with permuted k): used by every
+// stage of the X3 = 0 kernel and by the start-up of both (the initial-step rule is fp32-input-MFMA arithmetic in both matrix modes).
+// layer 1: this row block's partial of W1 * v for the wave's hidden tile; v goes through the image GL (one barrier inside)
+__device__ __forceinline__ f32x4 solve_f32_layer1(float* GL, const f32x4 (&wD)[7], const f32x4& v, int own_gl0, int col, int lane) {
+    constexpr int KG = 16 * 7 + 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) GL[own_gl0 + 4 * i] = v[i];
+    __syncthreads();
+    const float* gbp = GL + col * KG + 4 * (lane >> 4);
+    f32x4 bg[7];
+#pragma unroll
+    for (int kb = 0; kb < 7; ++kb) bg[kb] = *(const f32x4*)(gbp + 16 * kb);
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kb = 0; kb < 7; ++kb) {
+        acc0 = mfma16(wD[kb][0], bg[kb][0], acc0);
+        acc1 = mfma16(wD[kb][1], bg[kb][1], acc1);
+        acc0 = mfma16(wD[kb][2], bg[kb][2], acc0);
+        acc1 = mfma16(wD[kb][3], bg[kb][3], acc1);
+    }
+    return acc0 + acc1;
+}
+// layer 2: the wave's 16 rows of W2ext * [h; t; 1] from the image HL (k-steps from 104 on multiply zeros and are left out, as in the attempt kernel)
+__device__ __forceinline__ f32x4 solve_f32_layer2(const float* HL, const f32x4 (&wB)[7], int col, int lane) {
+    constexpr int KH = 16 * 7 + 4, gH = 100;
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    const float* hb = HL + col * KH + 4 * (lane >> 4);
+    f32x4 bf[7];
+#pragma unroll
+    for (int kb = 0; kb < 7; ++kb) bf[kb] = *(const f32x4*)(hb + 16 * kb);
+#pragma unroll
+    for (int kb = 0; kb < 7; ++kb) {
+        acc0 = mfma16(wB[kb][0], bf[kb][0], acc0);
+        if (16 * kb + 4 < gH + 2) acc1 = mfma16(wB[kb][1], bf[kb][1], acc1);
+        if (16 * kb + 8 < gH + 2) acc0 = mfma16(wB[kb][2], bf[kb][2], acc0);
+        if (16 * kb + 12 < gH + 2) acc1 = mfma16(wB[kb][3], bf[kb][3], acc1);
+    }
+    return acc0 + acc1;
+}
+
+// where Z.u_out lies in rnde_stage_solve_kernel's kernel-argument segment (the arguments follow each other as the members of a struct would)
+struct SolveKernelArgs { StageParams Q; PersistSync Y; SolveSync Z; };
+constexpr size_t kSolveArgUOut = offsetof(SolveKernelArgs, Z) + offsetof(SolveSync, u_out);
+
 // X3 = 1: the two Dense-layer products of every stage on the matrix cores (rnde_x3.h: exact three-way bf16 split of both operands, six
 // v_mfma_f32_16x16x32_bf16 per 32 k-values) instead of the fp32-input MFMA, which this part executes on its vector ALUs.  Everything else -- hand-off,
 // meeting, controller, tape layout, the state in registers -- is the same code.  The products are rounded differently (more accurately: rnde_x3.h), so
@@ -140,7 +187,8 @@ __global__ __launch_bounds__(64 * 7) void rnde_stage_solve_kernel(const StagePar
 
     // ---- once per solve: the state the first attempt starts from, this block's weight slice, the bias / time column of this wave's hidden tile ----
     f32x4 c_up = ld4(P.x + co, r0, gD, colok, P.xvec != 0), c_k[7];
-    c_k[0] = ld4(P.f0 + co, r0, gD, true, vec);
+    c_k[0] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (!Z.fold) c_k[0] = ld4(P.f0 + co, r0, gD, true, vec);      // (Z.fold: f0 comes out of the start-up below)
 #pragma unroll
     for (int j = 1; j < 7; ++j) c_k[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float w1t_own[4] = {0.f, 0.f, 0.f, 0.f}, b1_own[4] = {0.f, 0.f, 0.f, 0.f};
@@ -151,25 +199,18 @@ __global__ __launch_bounds__(64 * 7) void rnde_stage_solve_kernel(const StagePar
     }
     f32x4 wB[X3 ? 1 : 7], wD[X3 ? 1 : 7];
     x3u4 xB[X3 ? 4 : 1][3], xD[X3 ? 4 : 1][3];
-    if constexpr (X3) {
-        const x3u4* pB = (const x3u4*)Z.x3B + ((size_t)T * 4 * 3) * 64 + lane;
-        const x3u4* pD = (const x3u4*)Z.x3D + ((size_t)(w * gR + rb) * 4 * 3) * 64 + lane;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) { xD[s][pl] = pD[(size_t)(s * 3 + pl) * 64]; xB[s][pl] = pB[(size_t)(s * 3 + pl) * 64]; }
-        }
-        // the operand images start as zeros: k-values nobody writes (102 .. 127 of the hidden layer's, 112 .. 127 of the row block's) multiply zero weights
-        for (int i = tid; i < 2 * kX3ImageFloats; i += 64 * 7) HL[i] = 0.f;
-    } else {
+    // the fp32 fragments of this block's weight slice: the X3 = 0 kernel's operands for the whole solve; the X3 = 1 kernel needs them for the start-up
+    // only and loads its split weights behind it (the two fragment sets are never live together)
+    auto load_f32_weights = [&](f32x4 (&fB)[7], f32x4 (&fD)[7]) {
         const f32x4* pB = Q.pwB + ((size_t)T * gK2b) * 64 + lane;
         const f32x4* pD = Q.pwD + ((size_t)w * 49 + rb * gWT) * 64 + lane;
 #pragma unroll
-        for (int kb = 0; kb < 7; ++kb) wD[kb] = pD[(size_t)kb * 64];
+        for (int kb = 0; kb < 7; ++kb) fD[kb] = pD[(size_t)kb * 64];
 #pragma unroll
-        for (int kb = 0; kb < 7; ++kb) wB[kb] = pB[(size_t)kb * 64];
-        wB[6][2] = 0.f; wB[6][3] = 0.f;      // (k-steps 104.. multiply zeros and are left out, as in the attempt kernel)
-    }
+        for (int kb = 0; kb < 7; ++kb) fB[kb] = pB[(size_t)kb * 64];
+        fB[6][2] = 0.f; fB[6][3] = 0.f;      // (k-steps 104.. multiply zeros and are left out, as in the attempt kernel)
+    };
+    if constexpr (!X3) load_f32_weights(wB, wD);
 
     // loop-invariant addressing of this lane's four rows of its own hidden tile (phase A) and row tile (phase D)
     int own_kind[4];
@@ -196,26 +237,122 @@ __global__ __launch_bounds__(64 * 7) void rnde_stage_solve_kernel(const StagePar
             __syncthreads();
             const size_t tile0x = (((size_t)slab_buf(ex) * Q.C + ct) * gR + rb) * gHT;
             slab_put(Y.tslab, tile0x + w, lane, x3_tile<4>(xD, GX, lane));
-            return;
+        } else {
+            const size_t tile0 = (((size_t)slab_buf(ex) * Q.C + ct) * gR + rb) * gHT;
+            slab_put(Y.tslab, tile0 + w, lane, solve_f32_layer1(GL, wD, v, own_gl0, col, lane));
         }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) GL[own_gl0 + 4 * i] = v[i];
-        __syncthreads();
-        const size_t tile0 = (((size_t)slab_buf(ex) * Q.C + ct) * gR + rb) * gHT;
-        const float* gbp = GL + col * KG + 4 * (lane >> 4);
-        f32x4 bg[7];
-#pragma unroll
-        for (int kb = 0; kb < 7; ++kb) bg[kb] = *(const f32x4*)(gbp + 16 * kb);
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kb = 0; kb < 7; ++kb) {
-            acc0 = mfma16(wD[kb][0], bg[kb][0], acc0);
-            acc1 = mfma16(wD[kb][1], bg[kb][1], acc1);
-            acc0 = mfma16(wD[kb][2], bg[kb][2], acc0);
-            acc1 = mfma16(wD[kb][3], bg[kb][3], acc1);
-        }
-        slab_put(Y.tslab, tile0 + w, lane, acc0 + acc1);
     };
+    // phase A's arithmetic: the wave's hidden tile (rows beyond H: the time row, the bias row's 1, zeros) from the summed layer-1 partials
+    auto hidden_of = [&](const f32x4& zs, float ts) {
+        float pre[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) pre[i] = fmaf(w1t_own[i], ts, zs[i]) + b1_own[i];
+        const f32x2 t01 = tanh_fast2((f32x2){pre[0], pre[1]}), t23 = tanh_fast2((f32x2){pre[2], pre[3]});
+        f32x4 hv = {t01.x, t01.y, t23.x, t23.y};
+        if (w == 6) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) hv[i] = own_kind[i] == 0 ? hv[i] : fmaf(own_c1[i], ts, own_c0[i]);
+        }
+        return hv;
+    };
+    auto act2_of = [&](f32x4 kv) {
+        if (ACT2) {
+            const f32x2 a01 = tanh_fast2((f32x2){kv[0], kv[1]}), a23 = tanh_fast2((f32x2){kv[2], kv[3]});
+            kv = (f32x4){a01.x, a01.y, a23.x, a23.y};
+        }
+        return kv;
+    };
+
+    // ---- the start-up (Z.fold): the initial-step rule, i.e. what the launches SM_I1 .. SM_I4 of rnde_stage_kernel compute in front of a solve -- f0 = f(u0, t0),
+    // dt0 from ||u0|| and ||f0||, f1 = f(u0 + dt0 f0, t0 + dt0), ||f1 - f0|| -- through the same functions (rnde_stage.h) and the same fp32-input-MFMA products,
+    // with everything those launches leave for the reverse pass (f0, h0, u1, f1, h1, initpart, InitRec).  The two hand-offs inside a column tile use slab
+    // buffers of their own (3 and 4: the attempts cycle through 0 .. 2), emptied by their producers once every consumer is known to be through; the two
+    // cross-workgroup sums meet on the granule rows behind the attempts' (Z.n_limit, Z.n_limit + 1), formed in sum_partials' order.
+    InitFold IF{0.0, 0.f, 0.f, Z.fold};      // (wave 0) for the controller of attempt 0
+    auto startup = [&](const f32x4 (&fB)[7], const f32x4 (&fD)[7]) __attribute__((always_inline)) -> bool {
+        const f32x4 xv = c_up;
+        // f at (v, ts): layer-1 partials through start-up buffer `buf`, hidden activations to hdst; false: a hand-off gave up
+        auto feval = [&](const f32x4& v, float ts, int buf, float* hdst, f32x4& kv) __attribute__((always_inline)) -> bool {
+            const size_t tile0 = (((size_t)buf * Q.C + ct) * gR + rb) * gHT;
+            slab_put(Y.tslab, tile0 + w, lane, solve_f32_layer1(GL, fD, v, own_gl0, col, lane));
+            f32x4 zs = {0.f, 0.f, 0.f, 0.f};
+            const bool dead = !slab_poll_sum(Y, buf, Q.C, gR, gHT, ct, w, lane, zs);
+            const f32x4 hv = hidden_of(zs, ts);
+            if (own_hstore) *(f32x4*)(hdst + own_hd0) = hv;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) HL[own_hl0 + 4 * i] = hv[i];
+            if (dead && lane == 0) RED[24] = 1.f;
+            __syncthreads();
+            if (RED[24] != 0.f) return false;
+            kv = act2_of(solve_f32_layer2(HL, fB, col, lane));
+            return true;
+        };
+        // the workgroup's partial sums (summed as rnde_stage_kernel sums them) to initpart rows prow.., everybody's sums from granule row Z.n_limit + row (wave 0)
+        auto meet = [&](int nval, float p0, float p1, int prow, int row, double (&o)[3]) __attribute__((always_inline)) -> bool {
+            p0 = wave_sum_f(p0); p1 = wave_sum_f(p1);
+            if (lane == 0) { RED[w] = p0; RED[8 + w] = p1; }
+            __syncthreads();
+            if (w != 0) return true;
+            float mine[3] = {0.f, 0.f, 0.f};
+            for (int i = 0; i < gWT; ++i) { mine[0] += RED[i]; mine[1] += RED[8 + i]; }
+            if (lane == 0) { P.initpart[(size_t)prow * P.nwg + wg] = mine[0]; if (nval > 1) P.initpart[(size_t)(prow + 1) * P.nwg + wg] = mine[1]; }
+            return solve_meet(Z, Y, Z.n_limit + row, P.nwg, wg, nval, mine, o, lane);
+        };
+        const size_t tileA = (((size_t)(kSlabBufs - 2) * Q.C + ct) * gR + rb) * gHT, tileB = (((size_t)(kSlabBufs - 1) * Q.C + ct) * gR + rb) * gHT;
+        double o[3] = {0.0, 0.0, 0.0};
+        // SM_I1, SM_I2: f0, h0, the partials of ||u0|| and ||f0||
+        f32x4 f0;
+        if (!feval(xv, P.t0, kSlabBufs - 2, P.h0, f0)) return false;
+        st4(P.f0 + co, r0, gD, true, vec, f0);
+        c_k[0] = f0;
+        float p0 = 0.f, p1 = 0.f;
+        init_norm_parts_u0_f0(P, xv, f0, r0, colok, p0, p1);
+        bool ok = meet(2, p0, p1, 0, 0, o);
+        // SM_I3: dt0, the Euler step
+        if (w == 0) {
+            float d1; IF.dt0 = init_dt0_rule(P, o[0], o[1], writer, &d1); IF.d1 = d1;
+            if (lane == 0) { RED[25] = IF.dt0; if (!ok) SUMS[3] = 1.0; }
+        }
+        __syncthreads();
+        if (SUMS[3] != 0.0) return false;
+        const float dt0 = RED[25];
+        const f32x4 u1 = init_euler_step(xv, dt0, f0);
+        st4(P.u1 + co, r0, gD, true, vec, u1);
+        // SM_I4: f1, h1, the partial of ||f1 - f0||
+        f32x4 f1;
+        if (!feval(u1, P.t0 + dt0, kSlabBufs - 1, P.h1, f1)) return false;
+        slab_clear(Y.tslab, tileA + w, lane);      // (this wave's poll of the second exchange succeeded: every row block's wave w has produced it, hence consumed the first)
+        st4(P.f1 + co, r0, gD, true, vec, f1);
+        p0 = 0.f;
+        init_norm_part_df(P, xv, f0, f1, r0, colok, p0);
+        ok = meet(1, p0, 0.f, 2, 1, o);
+        if (w == 0) { IF.s2 = o[0]; if (lane == 0 && !ok) SUMS[3] = 1.0; }
+        __syncthreads();
+        if (SUMS[3] != 0.0) return false;
+        slab_clear(Y.tslab, tileB + w, lane);      // (every workgroup has come to the second meeting, hence consumed the second exchange; acknowledged before the first put of attempt 0)
+        return true;
+    };
+    if (Z.fold) {
+        if constexpr (X3) {
+            f32x4 fB[7], fD[7];
+            load_f32_weights(fB, fD);
+            if (!startup(fB, fD)) return;
+        } else {
+            if (!startup(wB, wD)) return;
+        }
+    }
+    if constexpr (X3) {
+        const x3u4* pB = (const x3u4*)Z.x3B + ((size_t)T * 4 * 3) * 64 + lane;
+        const x3u4* pD = (const x3u4*)Z.x3D + ((size_t)(w * gR + rb) * 4 * 3) * 64 + lane;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) { xD[s][pl] = pD[(size_t)(s * 3 + pl) * 64]; xB[s][pl] = pB[(size_t)(s * 3 + pl) * 64]; }
+        }
+        // the operand images start as zeros: k-values nobody writes (102 .. 127 of the hidden layer's, 112 .. 127 of the row block's) multiply zero weights
+        for (int i = tid; i < 2 * kX3ImageFloats; i += 64 * 7) HL[i] = 0.f;
+        __syncthreads();
+    }
 
 #ifdef RNDE_DIAG      // cycle stamps of workgroup 0, eight per attempt (tools/diag_solve.py)
 #define ZSTAMP(k) do { if (P.dbg_out && wg == 0 && tid == 0 && n < 120) ((unsigned long long*)P.dbg_out)[n * 8 + (k)] = clock64(); } while (0)
@@ -233,7 +370,7 @@ __global__ __launch_bounds__(64 * 7) void rnde_stage_solve_kernel(const StagePar
     StepState S{};
     if (w == 0) {
         const StepState nop{};
-        S = advance_state_t<true>(P, 0, lane, writer, &P.ctl[0], none, nop, nullptr, nullptr);
+        S = advance_state_t<true>(P, 0, lane, writer, &P.ctl[0], none, nop, nullptr, nullptr, &IF);
         if (lane == 0) solve_state_put(SS, S);
     }
     __syncthreads();
@@ -251,7 +388,14 @@ __global__ __launch_bounds__(64 * 7) void rnde_stage_solve_kernel(const StagePar
         // the stages run, the others pick it up after the meeting (the barriers in between order the LDS word); same function, same argument, same bits
         if (w == 3 && lane == 0) QP[(n + 1) & 1] = powf(S.qold, P.beta2);
         ZSTAMP(1);
-        if (S.done || n >= Z.n_limit) { if (writer) *P.ctl_final = S; return; }
+        if (S.done || n >= Z.n_limit) {
+            if (writer) *P.ctl_final = S;
+            // the final state -- x when nothing was accepted, else unew of the live record: what c_up holds after the accept hand-over -- from registers
+            // (the pointer is read from the kernel-argument segment HERE: taken from Z it stays in scalar registers across the attempt loop, which has none to spare)
+            float* const uo = *(float* volatile const*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + kSolveArgUOut);
+            if (uo) st_tile(uo + (size_t)gcol * gD, r0, gD, colok, (reinterpret_cast<size_t>(uo) & 15) == 0, c_up);
+            return;
+        }
         const float t = S.t, dt = (P.t1 - S.t < S.dtp) ? (P.t1 - S.t) : S.dtp;
         const int rec = P.tape ? n : (S.live == 0 ? 1 : 0);
         float* R = P.arena + (long long)rec * P.rec_stride;
@@ -294,15 +438,7 @@ __global__ __launch_bounds__(64 * 7) void rnde_stage_solve_kernel(const StagePar
                 if constexpr (s == 6) st4(R + L.unew() + co, r0, gD, true, vec, pend);
                 else if (P.tape) st4(R + L.g(s + 1) + co, r0, gD, true, vec, pend);
             }
-            float pre[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) pre[i] = fmaf(w1t_own[i], ts, zs[i]) + b1_own[i];
-            const f32x2 t01 = tanh_fast2((f32x2){pre[0], pre[1]}), t23 = tanh_fast2((f32x2){pre[2], pre[3]});
-            f32x4 hv = {t01.x, t01.y, t23.x, t23.y};
-            if (w == 6) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) hv[i] = own_kind[i] == 0 ? hv[i] : fmaf(own_c1[i], ts, own_c0[i]);
-            }
+            const f32x4 hv = hidden_of(zs, ts);
             if (own_hstore) *(f32x4*)(hdst + own_hd0) = hv;
             if constexpr (X3) x3_store4(HX, col, 16 * w + 4 * (lane >> 4), hv);
             else {
@@ -318,29 +454,8 @@ __global__ __launch_bounds__(64 * 7) void rnde_stage_solve_kernel(const StagePar
                 const float gave_up = RED[24];      // (requested in front of the fragments -- x3_tile's first scheduling barrier keeps it there -- and looked at behind the products)
                 kv = x3_tile<4>(xB, HX, lane);
                 if (gave_up != 0.f) { alive = false; return; }      // (X3: the flag is read with the fragments, not in front of them -- an LDS round trip per stage less on the chain; a workgroup that gives up has multiplied for nothing)
-                if (ACT2) {
-                    const f32x2 a01 = tanh_fast2((f32x2){kv[0], kv[1]}), a23 = tanh_fast2((f32x2){kv[2], kv[3]});
-                    kv = (f32x4){a01.x, a01.y, a23.x, a23.y};
-                }
-            } else {
-                f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-                const float* hb = HL + col * KH + 4 * (lane >> 4);
-                f32x4 bf[7];
-#pragma unroll
-                for (int kb = 0; kb < 7; ++kb) bf[kb] = *(const f32x4*)(hb + 16 * kb);
-#pragma unroll
-                for (int kb = 0; kb < 7; ++kb) {
-                    acc0 = mfma16(wB[kb][0], bf[kb][0], acc0);
-                    if (16 * kb + 4 < gH + 2) acc1 = mfma16(wB[kb][1], bf[kb][1], acc1);
-                    if (16 * kb + 8 < gH + 2) acc0 = mfma16(wB[kb][2], bf[kb][2], acc0);
-                    if (16 * kb + 12 < gH + 2) acc1 = mfma16(wB[kb][3], bf[kb][3], acc1);
-                }
-                kv = acc0 + acc1;
-                if (ACT2) {
-                    const f32x2 a01 = tanh_fast2((f32x2){kv[0], kv[1]}), a23 = tanh_fast2((f32x2){kv[2], kv[3]});
-                    kv = (f32x4){a01.x, a01.y, a23.x, a23.y};
-                }
-            }
+                kv = act2_of(kv);
+            } else kv = act2_of(solve_f32_layer2(HL, wB, col, lane));
             // ---- phase C ----
             if constexpr (s < 6) {
                 slab_clears_done();      // (issued two phases ago: nothing to wait for in practice) before this stage's put, see slab_put
