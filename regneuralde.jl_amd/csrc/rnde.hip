@@ -173,15 +173,11 @@ static rnde_status chain_create(const rnde_node_config* c, rnde_node** out) {
     ok &= dm((void**)&h->pcopy, (size_t)h->P * 4) && dm((void**)&h->cfrags, (size_t)(G.nfrag_f + G.nfrag_b + G.nfrag_t + 4) * 256);
     if (h->mw) ok &= dm((void**)&h->mw_tab, mw_tab_floats(h->mg) * 4);
     if (h->mw) {
-        const size_t xb = (size_t)(c->max_attempts + 4) * 3 * kMwMeetMax * 8;
-        ok &= dm((void**)&h->mw_xch, xb) && dm((void**)&h->mw_xcc, kMwMeetMax * 4) && dm((void**)&h->mw_abort, 8);
-        ok &= hipHostMalloc((void**)&h->h_mw_chk, (kMwMeetMax + 8) * 4) == hipSuccess;
+        ok &= h->mw_meet.create((size_t)c->max_attempts + 4, 3, kMwMeetMax) == hipSuccess;
         ok &= hipHostMalloc((void**)&h->h_mw_bchk, (kMwMeetMax + 8) * 4) == hipSuccess && dm((void**)&h->mw_bargs, (size_t)c->max_attempts * 16) &&
               hipHostMalloc((void**)&h->h_mw_bargs, (size_t)c->max_attempts * 16) == hipSuccess;
         if (ok) memset(h->h_mw_bchk, 0, (kMwMeetMax + 8) * 4);
-        { static std::atomic<int> next_slot{0}; h->mw_slot = next_slot.fetch_add(1) & 7; }
         if (const char* eb = getenv("RNDE_CHAIN_BSWEEP")) h->mw_bsweep = atoi(eb);
-        if (ok) { hipMemset(h->mw_xch, 0, xb); hipMemset(h->mw_abort, 0, 8); }
         const char* e = getenv("RNDE_CHAIN_SOLVE");
         if (e && e[0] == '0') h->mw_solve = 0;
     }
@@ -245,7 +241,7 @@ static hipError_t launch_mw_t(rnde_node* h, const MwParams& Q, int n, hipStream_
         if (e != hipSuccess) return e;
         attr_set.done();
     }
-    hipLaunchKernelGGL((rnde_chainmw_kernel<NR, MODE, TAB, LAT>), dim3((MODE == MW_SOLVE && !Q.xch_global) ? 8 * Q.ntiles : Q.ntiles), dim3(kMwThreads), MODE == MW_FINISH ? 0 : h->mw_lds_f, s, Q, n);
+    hipLaunchKernelGGL((rnde_chainmw_kernel<NR, MODE, TAB, LAT>), dim3(MODE == MW_SOLVE ? MeetRes::grid(Q.meet) : Q.ntiles), dim3(kMwThreads), MODE == MW_FINISH ? 0 : h->mw_lds_f, s, Q, n);
     return hipGetLastError();
 }
 template <int MODE>
@@ -424,10 +420,8 @@ extern "C" rnde_status rnde_node_create(const rnde_node_config* c, rnde_node** o
         h->stage_generic = (c->stage_generic != 0 || getenv("RNDE_STAGE_GENERIC") != nullptr) ? 1 : 0;
         if (const char* e6 = getenv("RNDE_STAGE_SOLVE")) h->stage_solve = atoi(e6);
     }
-    if (h->persist == 1 && h->stage_solve && c->max_attempts + kSolveInitRows < 8192) {      // meeting granules of the one-launch solve: [attempt | the start-up's two meetings][3][256] x 8 bytes
-        const size_t xb = (size_t)(c->max_attempts + kSolveInitRows) * 3 * 256 * 8;
-        if (hipMalloc((void**)&h->sxch, xb) != hipSuccess) { g_create_err = "device allocation failed"; rnde_node_destroy(h); return RNDE_ERR_HIP; }
-        hipMemset(h->sxch, 0, xb);
+    if (h->persist == 1 && h->stage_solve && c->max_attempts + kSolveInitRows < (int)kMeetRows) {      // meeting granules of the one-launch solve: [attempt | the start-up's two meetings][3][256] x 8 bytes
+        if (h->s_meet.create_granules((size_t)c->max_attempts + kSolveInitRows, 3, 256) != hipSuccess) { g_create_err = "device allocation failed"; rnde_node_destroy(h); return RNDE_ERR_HIP; }
     }
     // the stage kernels' Dense layers on the matrix cores (rnde_x3.h): split weight images for the headline geometry (49 row tiles, 7 x 7 (hidden tile, row
     // block) pairs) whenever the one-launch-per-attempt kernels are in use (persist == 1) -- with or without the one-launch solve
@@ -463,16 +457,13 @@ extern "C" void rnde_node_destroy(rnde_node* h) {
     if (h->replay_dev) hipFree(h->replay_dev);
     if (h->cfrags) hipFree(h->cfrags);
     if (h->mw_tab) hipFree(h->mw_tab);
-    if (h->mw_xch) hipFree(h->mw_xch);
-    if (h->mw_xcc) hipFree(h->mw_xcc);
-    if (h->mw_abort) hipFree(h->mw_abort);
-    if (h->h_mw_chk) hipHostFree(h->h_mw_chk);
+    h->mw_meet.destroy();
     if (h->h_mw_bchk) hipHostFree(h->h_mw_bchk);
     if (h->h_mw_bargs) hipHostFree(h->h_mw_bargs);
     if (h->mw_bargs) hipFree(h->mw_bargs);
     if (h->mw_slab) hipFree(h->mw_slab);
     if (h->tslab) hipFree(h->tslab);
-    if (h->sxch) hipFree(h->sxch);
+    h->s_meet.destroy();
     if (h->x3B) hipFree(h->x3B);
     if (h->x3D) hipFree(h->x3D);
     if (h->x3Bt) hipFree(h->x3Bt);
@@ -641,14 +632,12 @@ static hipError_t stage_attempt(rnde_node* h, const StageParams& Q, int n, hipSt
 bool bsweep_failed(rnde_node* h, hipStream_t s) {
     if (!h->pending_bsweep) return false;
     h->pending_bsweep = false;
-    bool bad = h->h_mw_bchk[0] != 0;
-    const int nt = h->bsweep_nt;      // the sweep's own geometry, recorded at its launch (h->B may already belong to the next forward)
-    for (int i = 1; i < nt && !h->bsweep_global && !bad; ++i) bad = h->h_mw_bchk[2 + i] != h->h_mw_bchk[2];      // (memory-side meeting: it does not depend on the placement)
-    if (!bad) return false;
+    const MeetVerdict v = meet_verdict(h->h_mw_bchk, h->bsweep_nt, h->bsweep_global);      // the sweep's own geometry, recorded at its launch (h->B may already belong to the next forward)
+    if (v == MEET_OK) return false;
     fprintf(stderr, "[rnde] chain engine: one-launch reverse sweep abandoned (%s); one launch per reversed attempt for the next %d solves\n",
-            h->h_mw_bchk[0] ? "a meeting timed out" : "workgroups pinned by block index landed on different XCDs", h->mw_retry_after);
+            v == MEET_TIMED_OUT ? "a meeting timed out" : "workgroups pinned by block index landed on different XCDs", h->mw_retry_after);
     h->mw_bsweep = -1; h->mw_clean = 0; ++h->persist_fallbacks;
-    hipMemsetAsync(h->mw_abort, 0, 8, s);
+    h->mw_meet.clear_abort(s);
     h->h_mw_bchk[0] = 0;
     return true;
 }
@@ -805,7 +794,7 @@ static rnde_status forward_core(rnde_node* h, const float* x_dev, const float* p
         if (stage_epart_reduce(h, SQ)) SQ.F.esum = (const double*)(h->errpart + 6 * (size_t)h->nwg_max + 256);      // (inside errpart's allocation, 8-byte aligned)
         // the one-launch solve (below) runs the initial-step rule and the copy-out of the final state inside its own launch; RNDE_SOLVE_FOLD=0,
         // read per call, keeps the four start-up launches and the finish launch around it (a redo after a time-out takes them too: persist != 1 then)
-        stage_one_launch = h->persist == 1 && h->stage_solve && h->sxch && SQ.C <= 32 && n_saveat == 0 && h->n_replay == 0 && !h->couple &&
+        stage_one_launch = h->persist == 1 && h->stage_solve && h->s_meet.xch && SQ.C <= 32 && n_saveat == 0 && h->n_replay == 0 && !h->couple &&
                            SQ.WT == 7 && SQ.HT == 7 && SQ.K2b == 7 && SQ.MT == 49 && SQ.R == 7 && h->D == 784 && h->H == 100 && !h->stage_generic;
         if (stage_one_launch) { const char* e = getenv("RNDE_SOLVE_FOLD"); solve_fold = !(e && e[0] == '0'); }
         if (!solve_fold) {
@@ -832,16 +821,15 @@ static rnde_status forward_core(rnde_node* h, const float* x_dev, const float* p
         const int n_limit = keep_tape ? std::min(cap, std::max(48, 2 * h->predicted)) : cap;
         if (keep_tape) { st = ensure_mw_slab(h, 2 + (long long)(h->rk_S - 1) * n_limit, P.Bpad, s); if (st != RNDE_OK) return st; MQ.slab = h->mw_slab; }
         MQ.n_limit = n_limit;
-        if (++h->mw_epoch >= 500000u) { h->mw_epoch = 1; HIPCHK(h, hipMemsetAsync(h->mw_xch, 0, (size_t)(cap + 4) * 3 * kMwMeetMax * 8, s)); }
-        const int nt = P.Bpad / 16;
-        MQ.u_out = u_out_dev; MQ.xch = h->mw_xch; MQ.xcc = h->mw_xcc; MQ.abort_word = h->mw_abort; MQ.epoch = h->mw_epoch; MQ.xch_global = nt > 32 ? 1 : 0; MQ.xcd_slot = h->mw_slot;
+        MQ.meet = h->mw_meet.begin(P.Bpad / 16, true, s);
+        HIPCHK(h, h->mw_meet.err);
+        MQ.u_out = u_out_dev; MQ.xcc = h->mw_meet.xcc; MQ.xcd_slot = h->mw_meet.slot;
         HIPCHK(h, launch_mw<MW_SOLVE>(h, MQ, 0, s));
         if (h->timing) { HIPCHK(h, hipEventRecord(h->tev[1], s)); h->tev_fwd = true; }
         HIPCHK(h, hipMemcpyAsync(h->h_ctl, h->ctl_final, sizeof(StepState), hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipMemcpyAsync(h->h_meta, h->meta, (size_t)cap * sizeof(StepMeta), hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipMemcpyAsync(h->h_init, h->initrec, sizeof(InitRec), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(h->h_mw_chk, h->mw_abort, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(h->h_mw_chk + 2, h->mw_xcc, (size_t)nt * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, h->mw_meet.queue_check(MQ.meet, s));
         if (h->after_solve) {
             HIPCHK(h, hipEventRecord(h->ev_host, s));
             const rnde_status hs = h->after_solve(s);
@@ -849,13 +837,12 @@ static rnde_status forward_core(rnde_node* h, const float* x_dev, const float* p
             HIPCHK(h, hipEventSynchronize(h->ev_host));
         } else HIPCHK(h, hipStreamSynchronize(s));
         if (bsweep_failed(h, s)) { h->err = "the one-launch reverse sweep of the previous asynchronous backward call was abandoned: the gradients of that step are invalid (one launch per reversed attempt now in use)"; return RNDE_ERR_HIP; }
-        bool bad = h->h_mw_chk[0] != 0;
-        for (int i = 1; i < nt && !MQ.xch_global && !bad; ++i) bad = h->h_mw_chk[2 + i] != h->h_mw_chk[2];
-        if (bad) {      // a meeting timed out, or the workgroups did not share an XCD: this handle goes back to one launch per attempt for the next mw_retry_after solves
+        const MeetVerdict verdict = meet_verdict(h->mw_meet.chk, MQ.meet.n, MQ.meet.global != 0);
+        if (verdict != MEET_OK) {      // a meeting timed out, or the workgroups did not share an XCD: this handle goes back to one launch per attempt for the next mw_retry_after solves
             fprintf(stderr, "[rnde] chain engine: one-launch solve abandoned (%s); one launch per attempted step for the next %d solves\n",
-                    h->h_mw_chk[0] ? "a meeting timed out" : "workgroups pinned by block index landed on different XCDs", h->mw_retry_after);
+                    verdict == MEET_TIMED_OUT ? "a meeting timed out" : "workgroups pinned by block index landed on different XCDs", h->mw_retry_after);
             h->mw_solve = -1; h->mw_clean = 0; ++h->persist_fallbacks;
-            hipMemsetAsync(h->mw_abort, 0, 8, s);
+            h->mw_meet.clear_abort(s);
             return RNDE_INTERNAL_RETRY;
         }
         if (!h->h_ctl->done && h->h_ctl->n_att >= n_limit && n_limit < cap) { h->predicted = cap; return RNDE_INTERNAL_RETRY; }
@@ -868,9 +855,10 @@ static rnde_status forward_core(rnde_node* h, const float* x_dev, const float* p
     if (stage_one_launch) {
         PersistSync Y{h->tslab, h->pabort, h->pxcc, h->persist_spins};
         HIPCHK(h, slab_prepare(h, SQ.Bpad16, s));
-        if (++h->s_epoch >= 500000u) { h->s_epoch = 1; HIPCHK(h, hipMemsetAsync(h->sxch, 0, (size_t)(cap + kSolveInitRows) * 3 * 256 * 8, s)); }
+        const Meet SM = h->s_meet.begin(SQ.F.nwg, false, s);      // (the granules and the epoch; the abort word is Y's)
+        HIPCHK(h, h->s_meet.err);
         const int x3 = h->x3_fwd ? 1 : 0;      // (the weights were split by this forward's pack launch: x3_pack)
-        SolveSync Z{h->sxch, h->s_epoch, cap, h->x3B, h->x3D, solve_fold ? u_out_dev : nullptr, solve_fold ? 1 : 0};
+        SolveSync Z{SM.xch, SM.epoch, cap, h->x3B, h->x3D, solve_fold ? u_out_dev : nullptr, solve_fold ? 1 : 0};
 #ifdef RNDE_DIAG
         StageParams SD = SQ;
         if (getenv("RNDE_DIAG_SOLVE")) {      // cycle stamps of workgroup 0, every attempt (tools/diag_solve.py)
@@ -1022,7 +1010,7 @@ static rnde_status forward_core(rnde_node* h, const float* x_dev, const float* p
         if (h->mw_solve == -1) h->mw_solve = 1;
         if (h->mw_bsweep == -1) h->mw_bsweep = 1;
         h->mw_retry_after = std::min(1024, 2 * h->mw_retry_after);
-        h->mw_slot = (h->mw_slot + 1) & 7;                                           // (and another XCD: the one it was pinned to may be the contended one)
+        h->mw_meet.slot = (h->mw_meet.slot + 1) & 7;                                           // (and another XCD: the one it was pinned to may be the contended one)
     }
     if (h->persist == -1 && h->engine == 2 && h->cfg.persist >= 0 && ++h->persist_clean >= h->persist_retry_after) {
         h->persist = 1; h->persist_retry_after = std::min(1024, 2 * h->persist_retry_after);

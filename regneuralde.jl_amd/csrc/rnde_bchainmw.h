@@ -22,9 +22,9 @@ struct BMwParams {
     long long ev_stride;
     int ntiles;
     const float* sv_t; const float* sv_ubar; int nsave;
-    // SWEEP (the whole reverse sweep in one launch): per-attempt arguments as device arrays, and the meeting of rnde_chainmw.h
+    // SWEEP (the whole reverse sweep in one launch): per-attempt arguments as device arrays, and the meeting as MW_SOLVE of rnde_chainmw.h
     const int* sv_lo; const int* sv_hi; const float* eig_c;     // [n_att], [n_att], [n_att][2]
-    unsigned long long* xch; unsigned* xcc; unsigned* abort_word; unsigned epoch; int xch_global; int xcd_slot;
+    Meet meet; unsigned* xcc; int xcd_slot;
 };
 
 // J_f^T product at a taped evaluation.  kout = f's value (element-wise), kbar its cotangent; returns gbar (element-wise) and adds
@@ -220,7 +220,7 @@ __device__ __forceinline__ void mw_fbwd_lat(const MwGeo& G, const LatWeightsT& W
 
 // SWEEP = 1: the WHOLE reverse sweep in one launch (the mirror of MW_SOLVE in rnde_chainmw.h): the loop over the attempted steps, last to first,
 // runs inside the kernel; weights and geometry are loaded once; the only thing the workgroups exchange per attempt -- their three partial
-// sums {<k, k-bar>, tau, c-weighted tau} -- goes through mw_exchange3 (the <= 32 workgroups are pinned to one XCD and meet through its L2), and
+// sums {<k, k-bar>, tau, c-weighted tau} -- goes through meet_exchange (rnde_meet.h; up to 32 workgroups are pinned to one XCD and meet through its L2), and
 // every workgroup carries the scalar chain (BState) in registers: the same double-precision arithmetic on the same sums as the
 // launch-per-attempt path, bit for bit.  n_arg = the first attempt to reverse (n_att - 1); the per-attempt arguments come from device arrays.
 template <int NR, int TAB = 0, int LAT = 0, int SWEEP = 0>
@@ -238,8 +238,8 @@ __global__ __launch_bounds__(kMwThreads) void rnde_bchainmw_kernel(const BMwPara
     float* RED = ZB + 1024;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    if constexpr (SWEEP) { if (!Q.xch_global && (int)(blockIdx.x & 7) != Q.xcd_slot) return; }      // (8 x ntiles launched: the ones that work share one XCD; xch_global: all work, see MW_SOLVE)
-    const int tile = (SWEEP && !Q.xch_global) ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    if constexpr (SWEEP) { if (!Q.meet.global && (int)(blockIdx.x & 7) != Q.xcd_slot) return; }      // (8 x ntiles launched: the ones that work share one XCD; agent scope: all work, see MW_SOLVE)
+    const int tile = (SWEEP && !Q.meet.global) ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
     if constexpr (SWEEP) { if (tid == 0) Q.xcc[tile] = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 15; }
     const int gcol = tile * 16 + (tid & 15);
     const bool colok = gcol < P.B;
@@ -516,7 +516,7 @@ __global__ __launch_bounds__(kMwThreads) void rnde_bchainmw_kernel(const BMwPara
             float mine[3] = {0.f, 0.f, 0.f};
             for (int w = 0; w < kMwWaves; ++w) { mine[0] += RED[w]; mine[1] += RED[4 + w]; mine[2] += RED[8 + w]; }
             double o[3];
-            const bool ok = mw_exchange3(MwMeet{Q.xch, Q.abort_word, Q.epoch, Q.ntiles, Q.xch_global}, n, mine, o, tile, lane);
+            const bool ok = meet_exchange<3, 3>(Q.meet, n, mine, o, tile, lane);
             if (lane == 0) { ((double*)RED2)[0] = o[0]; ((double*)RED2)[1] = o[1]; ((double*)RED2)[2] = o[2]; RED2[6] = ok ? 1.f : 0.f; }
         }
         __syncthreads();

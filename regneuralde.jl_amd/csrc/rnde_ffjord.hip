@@ -56,12 +56,7 @@ struct rnde_ffjord {
     float* qt = nullptr;             // engine = 1: [ntiles][HP][HP], the exact trace's matrix per tile (the driver's scratch)
     InitRec* initrec_t = nullptr;    // [ntiles] (initrec = initrec_t)
     StepState* ctl_t = nullptr;      // [ntiles]
-    unsigned long long* xch = nullptr;
-    unsigned* xcc = nullptr;         // [kMwMeetMax]
-    unsigned* abort_word = nullptr;
-    unsigned epoch = 0;
-    int xcd_slot = 0;
-    std::vector<unsigned> h_chk;     // abort word, then each tile's XCC
+    MeetRes meet;                    // the tiles' meeting place (rnde_meet.h)
     FcGeo CG{};                      // engine = 2: the Dense-chain dynamics on the tile layout (cfg holds the shared fields, in_dims = D)
 };
 
@@ -116,7 +111,6 @@ static rnde_status tile_create(rnde_ffjord* h, const typename Dyn::Geo& G, rnde_
     auto fail = [&](hipError_t e) { g_ff_create_err = std::string("HIP: ") + hipGetErrorString(e); rnde_ffjord_destroy(h); return RNDE_ERR_HIP; };
     hipError_t e;
     const size_t RB = (size_t)R * h->Bp, MA = (size_t)c->max_attempts, NT = (size_t)h->ntiles_max;
-    const size_t xb = (MA + 4) * 3 * kMwMeetMax * 8;
     if ((e = hipMalloc(&h->ws, 10 * RB * 4)) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&h->tape, (MA + 1) * RB * 4)) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&h->norm, (8 * NT + 512) * 4)) != hipSuccess) return fail(e);
@@ -133,18 +127,12 @@ static rnde_status tile_create(rnde_ffjord* h, const typename Dyn::Geo& G, rnde_
     if ((e = hipMalloc(&h->initrec_t, NT * sizeof(InitRec))) != hipSuccess) return fail(e);
     h->initrec = h->initrec_t;
     if ((e = hipMalloc(&h->rec, MA * sizeof(FfStepRec))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->xch, xb)) != hipSuccess) return fail(e);
-    if ((e = hipMemset(h->xch, 0, xb)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->xcc, kMwMeetMax * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->abort_word, 8)) != hipSuccess) return fail(e);
-    if ((e = hipMemset(h->abort_word, 0, 8)) != hipSuccess) return fail(e);
+    if ((e = h->meet.create(MA + 4, 3, kMwMeetMax)) != hipSuccess) return fail(e);
     for (const void* k : {(const void*)rnde_ffjord_tile_solve_kernel<Dyn, false>, (const void*)rnde_ffjord_tile_reverse_kernel<Dyn, false>,
                           (const void*)rnde_ffjord_tile_feval_kernel<Dyn, false>, (const void*)rnde_ffjord_tile_solve_kernel<Dyn, true>,
                           (const void*)rnde_ffjord_tile_reverse_kernel<Dyn, true>, (const void*)rnde_ffjord_tile_feval_kernel<Dyn, true>})
         if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes)) != hipSuccess) return fail(e);
     for (auto& v : h->ev) if ((e = hipEventCreate(&v)) != hipSuccess) return fail(e);
-    { static std::atomic<int> next_slot{0}; h->xcd_slot = next_slot.fetch_add(1) & 7; }      // (one counter per dynamics: each deals its handles round the XCDs)
-    h->h_chk.assign(2 + kMwMeetMax, 0u);
     *out = h;
     return RNDE_OK;
 }
@@ -292,9 +280,9 @@ extern "C" rnde_status rnde_ffjord_create(const rnde_ffjord_config* c, rnde_ffjo
 extern "C" void rnde_ffjord_destroy(rnde_ffjord* h) {
     if (!h) return;
     for (void* p : {(void*)h->ws, (void*)h->tape, (void*)h->norm, (void*)h->e_buf, (void*)h->e_tape, (void*)h->replay, (void*)h->rws, (void*)h->pacc,
-                    (void*)h->ctl, (void*)h->meta, (void*)h->initrec, (void*)h->rec, (void*)h->qt, (void*)h->ctl_t, (void*)h->xch, (void*)h->xcc,
-                    (void*)h->abort_word})
+                    (void*)h->ctl, (void*)h->meta, (void*)h->initrec, (void*)h->rec, (void*)h->qt, (void*)h->ctl_t})
         if (p) (void)hipFree(p);
+    h->meet.destroy();
     for (auto& v : h->ev) if (v) (void)hipEventDestroy(v);
     delete h;
 }
@@ -342,14 +330,14 @@ static rnde_status ff_kinetic_ready(rnde_ffjord* h) {
 
 // The tile driver's launches for the dynamics Dyn: the shared fields come from the one-workgroup engine's parameter structs, filled once.
 template <class Dyn>
-static void tile_launch_solve(rnde_ffjord* h, const typename Dyn::Geo& G, const FfSolveParams& Q, const MwMeet& meet, bool kin, bool exact,
+static void tile_launch_solve(rnde_ffjord* h, const typename Dyn::Geo& G, const FfSolveParams& Q, const Meet& meet, bool kin, bool exact,
                               hipStream_t s) {
     TileSolveParams<typename Dyn::Geo> T{};
     T.F = Q.F; T.G = G; T.p = Q.p; T.x = Q.x; T.e = Q.e; T.ws = Q.ws; T.tape = Q.tape; T.logpx = Q.logpx; T.x_out = Q.x_out;
     T.norm = Q.norm; T.initrec_t = h->initrec_t; T.ctl_t = h->ctl_t; T.exact = (Q.dir < 0 || exact) ? 1 : 0;
     T.scratch = T.exact ? h->qt : nullptr;
-    T.meet = meet; T.xcc = h->xcc; T.xcd_slot = h->xcd_slot; T.dir = Q.dir; T.Bp = Q.Bp; T.ntiles = meet.ntiles; T.tbase = Q.tbase; T.reg = Q.reg;
-    const dim3 grid(meet.global ? meet.ntiles : 8 * meet.ntiles);      // one XCD: every eighth block is a tile (the others return at once)
+    T.meet = meet; T.xcc = h->meet.xcc; T.xcd_slot = h->meet.slot; T.dir = Q.dir; T.Bp = Q.Bp; T.ntiles = meet.n; T.tbase = Q.tbase; T.reg = Q.reg;
+    const dim3 grid(MeetRes::grid(meet));      // one XCD: every eighth block is a tile (the others return at once)
     if (kin) hipLaunchKernelGGL((rnde_ffjord_tile_solve_kernel<Dyn, true>), grid, dim3(kFtThreads), h->lds_bytes, s, T);
     else hipLaunchKernelGGL((rnde_ffjord_tile_solve_kernel<Dyn, false>), grid, dim3(kFtThreads), h->lds_bytes, s, T);
 }
@@ -408,10 +396,10 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
     Q.dir = dir; Q.T = h->T; Q.Bp = h->Bp; Q.tbase = t1; Q.reg = reg_out_dev;
     const int nt = (B + 15) / 16;
     const bool tiles = h->engine >= 1;     // engines 1 and 2 share the tile layout, the meeting and its checks
-    MwMeet meet{};
+    Meet meet{};
     if (tiles) {               // every tile resident, one meeting per attempt (one XCD up to 32 tiles, agent scope above)
-        if (++h->epoch >= 500000u) { h->epoch = 1; FCHK(h, hipMemsetAsync(h->xch, 0, ((size_t)h->cfg.max_attempts + 4) * 3 * kMwMeetMax * 8, s)); }
-        meet = MwMeet{h->xch, h->abort_word, h->epoch, nt, nt > 32 ? 1 : 0};
+        meet = h->meet.begin(nt, true, s);
+        FCHK(h, h->meet.err);
     }
     FCHK(h, hipEventRecord(h->ev[0], s));
     if (h->engine == 2) tile_launch_solve<FcDyn>(h, h->CG, Q, meet, kin, exact, s);
@@ -422,17 +410,13 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
     FCHK(h, hipEventRecord(h->ev[1], s));
     StepState fin;
     FCHK(h, hipMemcpyAsync(&fin, h->ctl + 2, sizeof(StepState), hipMemcpyDeviceToHost, s));
-    if (tiles) {
-        FCHK(h, hipMemcpyAsync(h->h_chk.data(), h->abort_word, 4, hipMemcpyDeviceToHost, s));
-        if (!meet.global) FCHK(h, hipMemcpyAsync(h->h_chk.data() + 2, h->xcc, (size_t)nt * 4, hipMemcpyDeviceToHost, s));
-    }
+    if (tiles) FCHK(h, h->meet.queue_check(meet, s));
     FCHK(h, hipStreamSynchronize(s));
     (void)hipEventElapsedTime(&h->fwd_ms, h->ev[0], h->ev[1]);
     if (tiles) {
-        bool split = false;
-        for (int i = 1; i < nt && !meet.global; ++i) split |= h->h_chk[2 + i] != h->h_chk[2];
-        if (h->h_chk[0] != 0u || split) {      // no fall-back to other arithmetic: the call fails and says why
-            FCHK(h, hipMemsetAsync(h->abort_word, 0, 8, s));
+        const bool split = meet_split(h->meet.chk, nt, meet.global != 0);
+        if (meet_verdict(h->meet.chk, nt, meet.global != 0) != MEET_OK) {      // no fall-back to other arithmetic: the call fails and says why
+            FCHK(h, h->meet.clear_abort(s));
             FCHK(h, hipStreamSynchronize(s));
             h->n_att = h->n_acc = 0; h->h_meta.clear();
             h->err = split ? "TrackedFFJORD tiled engine: a workgroup meeting of the solve timed out (the tiles pinned to one XCD by block index "

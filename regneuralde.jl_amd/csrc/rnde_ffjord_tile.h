@@ -6,7 +6,7 @@
 // (R = D + 1 augmented rows, D + 3 with KIN; each tile touching its own 16 columns), the dynamics keep their parameters and activations in LDS.
 //
 // Forward solve: the whole adaptive Tsit5 solve in one launch.  Once per attempt every tile forms its partial of the error norm and the tiles
-// meet through rnde_chainmw.h's bounded mw_exchange3 (one XCD up to 32 tiles, agent scope above): partials are summed in tile order in
+// meet through rnde_meet.h's bounded meet_exchange (one XCD up to 32 tiles, agent scope above): partials are summed in tile order in
 // double, so every tile runs the same controller (advance_state_t over R rows) on the same bits, and a solve is bit-identical run to run.
 // A meeting that times out raises the abort word and ends the launch; the host reports it by name.
 //
@@ -37,7 +37,7 @@
 // workgroup calls them.
 #pragma once
 #include "rnde_bffjord.h"      // FfStepRec
-#include "rnde_ffjordt.h"      // the tile layout's constants; MwMeet, mw_exchange3
+#include "rnde_ffjordt.h"      // the tile layout's constants; rnde_meet.h
 
 namespace rnde {
 
@@ -57,7 +57,7 @@ struct TileSolveParams {
     StepState* ctl_t;                // [ntiles]: where tiles other than 0 write the state before attempt 0
     float* scratch;                  // [ntiles][Dyn::scratch_floats] (FtDyn: the exact trace's H x H buffer) or NULL
     int exact;                       // the trace row is -tr J (sampling always; a forward solve or replay when the caller asks), not -e . eJ
-    MwMeet meet;
+    Meet meet;                       // three rows per meeting
     unsigned* xcc;                   // [ntiles] (one-XCD meeting: the host checks they agree)
     int xcd_slot;
     int dir, Bp, ntiles;
@@ -84,7 +84,7 @@ struct TileRevParams {
 };
 
 // Publish this tile's three partials (wave 0), collect everybody's sums in tile order; false when the meeting timed out (every thread).
-__device__ __forceinline__ bool tile_meet(const MwMeet& M, float* red, int seq, float a, float b, float c, double (&out)[3], int tile, int tid) {
+__device__ __forceinline__ bool tile_meet(const Meet& M, float* red, int seq, float a, float b, float c, double (&out)[3], int tile, int tid) {
     const int lane = tid & 63, wave = tid >> 6;
     a = wave_sum_f(a); b = wave_sum_f(b); c = wave_sum_f(c);
     if (lane == 0) { red[wave] = a; red[4 + wave] = b; red[8 + wave] = c; }
@@ -93,7 +93,7 @@ __device__ __forceinline__ bool tile_meet(const MwMeet& M, float* red, int seq, 
     if (wave == 0) {
         const float mine[3] = {((red[0] + red[1]) + red[2]) + red[3], ((red[4] + red[5]) + red[6]) + red[7], ((red[8] + red[9]) + red[10]) + red[11]};
         double o[3];
-        const bool ok = mw_exchange3(M, seq, mine, o, tile, lane);
+        const bool ok = meet_exchange<3, 3>(M, seq, mine, o, tile, lane);
         if (lane == 0) { RD[0] = o[0]; RD[1] = o[1]; RD[2] = o[2]; red[70] = ok ? 1.f : 0.f; }
     }
     __syncthreads();

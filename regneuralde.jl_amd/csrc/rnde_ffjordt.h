@@ -19,7 +19,7 @@
 // trace is formed -- per-lane partials in the epilogues of the layer-3 product and of the last transposed product, then the same per-column
 // reduction.  No LDS beyond the plain kernels' (135 KB at (43, 100)), so the limits are the plain ones: in_dims <= 64, hidden <= 112.
 #pragma once
-#include "rnde_chainmw.h"     // MwMeet, mw_exchange3, kMwMeetMax, mfma16
+#include "rnde_chainmw.h"     // rnde_meet.h, kMwMeetMax, mfma16
 #include "rnde_ffjord.h"
 
 namespace rnde {
@@ -29,7 +29,7 @@ constexpr int kFtThreads = 64 * kFtWaves;
 constexpr int kFtMaxD = 64;            // the tiled engine's width limit (LDS: weights + activations of the solve within 160 KB)
 constexpr int kFtMaxH = 112;
 constexpr int kFtLdsBytes = 160 * 1024;
-constexpr int kFtMaxAttempts = 8000;   // meeting tags are epoch * 8192 + sequence + 1 (two initial meetings + one per attempt)
+constexpr int kFtMaxAttempts = 8000;   // two initial meetings + one per attempt, below kMeetRows (rnde_meet.h)
 
 struct FtGeo {
     int D, H, P, DP, HP;

@@ -620,7 +620,7 @@ static rnde_status launch_bmw_t(rnde_node* h, const BMwParams& Q, const std::vec
     rnde_status st = RNDE_OK;
     // the whole sweep as ONE launch (rnde_bchainmw.h SWEEP): every workgroup resident (<= 256 column tiles; more than 32: meeting through the
     // memory side, as the forward solve), no shared controller, more than one attempt
-    const bool sweep = h->mw_bsweep > 0 && !h->couple && Q.ntiles <= kMwMeetMax && Q.B.n_att >= 2 && h->mw_xch;
+    const bool sweep = h->mw_bsweep > 0 && !h->couple && Q.ntiles <= kMwMeetMax && Q.B.n_att >= 2 && h->mw_meet.xch;
     int* a_lo = h->h_mw_bargs; int* a_hi = a_lo + h->cfg.max_attempts; float* a_eig = (float*)(a_hi + h->cfg.max_attempts);
     for (int n = Q.B.n_att - 1; n >= 0; --n) {
         float c1 = 0.f, c2 = 0.f;   // cotangent of eigen_est for this attempt (as in bwd_run)
@@ -642,15 +642,15 @@ static rnde_status launch_bmw_t(rnde_node* h, const BMwParams& Q, const std::vec
     if (sweep) {
         const int cap = h->cfg.max_attempts;
         HIPCHK(h, hipMemcpyAsync(h->mw_bargs, h->h_mw_bargs, (size_t)cap * 16, hipMemcpyHostToDevice, s));
-        if (++h->mw_epoch >= 500000u) { h->mw_epoch = 1; HIPCHK(h, hipMemsetAsync(h->mw_xch, 0, (size_t)(cap + 4) * 3 * kMwMeetMax * 8, s)); }
         BMwParams W = Q;
+        W.meet = h->mw_meet.begin(Q.ntiles, true, s);
+        HIPCHK(h, h->mw_meet.err);
         W.sv_lo = h->mw_bargs; W.sv_hi = h->mw_bargs + cap; W.eig_c = (const float*)(h->mw_bargs + 2 * cap);
-        W.xch = h->mw_xch; W.xcc = h->mw_xcc; W.abort_word = h->mw_abort; W.epoch = h->mw_epoch; W.xch_global = Q.ntiles > 32 ? 1 : 0; W.xcd_slot = h->mw_slot;
-        hipLaunchKernelGGL((rnde_bchainmw_kernel<NR, TAB, LAT, 1>), dim3(W.xch_global ? Q.ntiles : 8 * Q.ntiles), blk, lds, s, W, Q.B.n_att - 1, h->h_meta[Q.B.n_att - 1], 0, 0, 0.f, 0.f);
+        W.xcc = h->mw_meet.xcc; W.xcd_slot = h->mw_meet.slot;
+        hipLaunchKernelGGL((rnde_bchainmw_kernel<NR, TAB, LAT, 1>), dim3(MeetRes::grid(W.meet)), blk, lds, s, W, Q.B.n_att - 1, h->h_meta[Q.B.n_att - 1], 0, 0, 0.f, 0.f);
         HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(h->h_mw_bchk, h->mw_abort, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(h->h_mw_bchk + 2, h->mw_xcc, (size_t)Q.ntiles * 4, hipMemcpyDeviceToHost, s));
-        h->pending_bsweep = true; h->bsweep_nt = Q.ntiles; h->bsweep_global = W.xch_global != 0;
+        HIPCHK(h, h->mw_meet.queue_check(W.meet, s, h->h_mw_bchk));      // (a buffer of the sweep's own: the verdict is read after a later synchronisation)
+        h->pending_bsweep = true; h->bsweep_nt = Q.ntiles; h->bsweep_global = W.meet.global != 0;
     }
     hipLaunchKernelGGL((rnde_bchainmw_init_kernel<NR, 1, LAT == 2>), grid, blk, lds, s, Q);
     if ((st = couple_sum(h, Q.B.ipart, 4LL * Q.B.F.nwg, s)) != RNDE_OK) return st;                        // dot, tau of the reversed second evaluation

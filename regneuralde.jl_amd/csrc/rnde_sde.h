@@ -13,11 +13,8 @@
 //     rejection-sampling-with-memory stacks of the noise process (RSwM3) run INSIDE the kernel, replicated per workgroup:
 //     thread 0 turns (EEst, stack metadata in LDS) into a decision block and a short list of array operations, the waves
 //     execute it on their own columns.  The stack arrays live in a slot pool in HBM, one fragment-order array per slot;
-//   * workgroups meet once per attempt, to sum the squared residuals: each publishes its partial as ONE 8-byte
-//     agent-scope atomic store {value, sequence tag} and polls the others' with agent-scope atomic loads
-//     (/opt/skills/guides/cdna_hip_programming.md section 6 Guideline 16, the 8-byte-atomics form: placement independent,
-//     no fence, no L2 write-back).  Every entry is written once per solve (index = exchange number), the tag carries the
-//     solve's epoch, every spin is bounded;
+//   * workgroups meet once per attempt, to sum the squared residuals (rnde_meet.h: two rows per exchange number, every
+//     spin bounded);
 //   * noise enters as a POOL of standard normals in the caller's layout (draw k = xi_W, xi_Z, both D x B), consumed in
 //     order: the caller may fill it from its own generator (a Julia caller: randn!) or let the library fill it
 //     (rnde_normal_fill_kernel, Philox4x32-10 + Box-Muller).
@@ -27,11 +24,11 @@
 // contracts them over columns x evaluations afterwards, as for the chain engine.
 #pragma once
 #include "rnde_bchain.h"
+#include "rnde_meet.h"
 
 namespace rnde {
 
 constexpr int kSdeMaxOps = 64;       // array operations one accept / reject can ask for (whole pops + a bridge + fresh)
-constexpr int kSdeSpinMax = 4000000; // bound of every poll (~1 s)
 
 struct SriTableau {   // lower-triangular 4x4 stage matrices (row = stage) and weights, fp32 (tableau as data)
     float A0[16], A1[16], B0[16], B1[16], alpha[4], beta1[4], beta2[4], beta3[4], beta4[4];
@@ -58,8 +55,7 @@ struct SdeParams {
     float* tape;                     // [max_acc][12][ntiles][NKD][64]: uprev dW dZ k1..4 g1..4 unew
     SdeMeta* meta;
     SdeFinal* fin;
-    unsigned long long* xch;         // [n_exchanges][2][nwg] {float value, uint tag}
-    unsigned* abort_word;
+    Meet meet;                       // [n_exchanges][2][nwg] granules; one XCD: every workgroup of the launch sits on ONE XCD (pinned by block index, verified by the host)
     float* u_out;                    // D x B, caller layout (may be NULL)
     const float* replay;             // optional: [n_replay][2] (dt, accepted)
     int n_replay;
@@ -68,15 +64,10 @@ struct SdeParams {
                                      // them, so they do not go through the meeting: a small kernel behind the solve sums them in a fixed order into meta[n].n1 / .n2
     float stab;                      // reg_kind 2: alg_stability_size (10.6 for SOSRI2)
     int D, B, ntiles, nwg, n_pool, n_slots, max_attempts, keep_tape, reg_kind;
-    unsigned epoch;
-    int xch_local;                   // 1: every workgroup of the launch sits on ONE XCD (pinned by block index, verified by the host): the meeting goes through that L2
-    unsigned* xcc;                   // [nwg] HW_REG_XCC_ID of each workgroup (xch_local: the host checks they agree)
+    unsigned* xcc;                   // [nwg] HW_REG_XCC_ID of each workgroup (one-XCD meeting: the host checks they agree)
     float t0, t1, reltol, abstol;
     float beta1, beta2, gamma, qmin, qmax, qoldinit, delta, order;
 };
-
-typedef unsigned sde_u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned long long sde_pack(float v, unsigned tag) { return ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(v); }
 
 // ---- LDS layout of the solve kernel ------------------------------------------------------------------------------------
 struct SdeOp { int type, a, b, c; float f0, f1; int draw, flags; };   // see sde_apply_ops
@@ -191,55 +182,6 @@ __device__ __forceinline__ float sde_attempt(const SdeParams& Q, const float* FR
         }
     }
     return part;
-}
-
-// ---- cross-workgroup sum of NV per-workgroup values: publish, poll, fixed-order double sum --------------------------------
-// called by wave 0 only; `mine` valid in lane 0.  Returns false on time-out / abort.
-template <int NV>
-__device__ __forceinline__ bool sde_exchange(const SdeParams& Q, int seq, const float (&mine)[NV], double (&out)[NV], int wg, int lane) {
-    const unsigned tag = Q.epoch * 8192u + (unsigned)seq + 1u;
-    unsigned long long* base = Q.xch + (size_t)seq * 2 * Q.nwg;
-    // xch_local: all participants share one L2 (same XCD), so a plain store (written through to L2) and an L1-bypassing load (sc1) are enough --
-    // the hand-off of the ODE engine's persistent kernels (rnde_stage_persist.h): ~1 us per meeting instead of ~2.5 us through memory-side atomics
-    const bool local = Q.xch_local != 0;
-    if (lane == 0) {
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            float m = mine[v];
-            if (m != m) m = __uint_as_float(0x7FC00000u);
-            if (local) base[(size_t)v * Q.nwg + wg] = sde_pack(m, tag);
-            else __hip_atomic_store(base + (size_t)v * Q.nwg + wg, sde_pack(m, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x7fffffff, 0x00020000);
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        double s = 0.0;
-        for (int b0 = 0; b0 < Q.nwg; b0 += 64) {
-            const int i = b0 + lane;
-            unsigned long long e = 0;
-            bool ok = i >= Q.nwg;
-            int spins = 0;
-            while (true) {
-                if (!ok) {
-                    if (local) {
-                        __asm__ volatile("" ::: "memory");      // (the buffer load is a plain read to the optimiser: keep it inside the spin loop)
-                        const sde_u32x2 q = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(((size_t)v * Q.nwg + i) * 8), 0, 16);   // aux 16 = sc1: misses L1
-                        e = ((unsigned long long)q.y << 32) | q.x;
-                    } else e = __hip_atomic_load(base + (size_t)v * Q.nwg + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    ok = (unsigned)(e >> 32) == tag;
-                }
-                if (__all(ok)) break;
-                if (++spins > kSdeSpinMax || ((spins & 1023) == 0 && __hip_atomic_load(Q.abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-                    if (lane == 0) __hip_atomic_store(Q.abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    return false;
-                }
-            }
-            if (i < Q.nwg) s += (double)__uint_as_float((unsigned)(e & 0xFFFFFFFFull));
-        }
-        out[v] = wave_sum_d(s);
-    }
-    return true;
 }
 
 // array element access: fragment-order slot / tape arrays of this wave's tile
@@ -456,7 +398,7 @@ __global__ __launch_bounds__(64 * kCW) void rnde_sde_solve_kernel(const SdeParam
             float mine[2] = {0.f, 0.f};
             for (int w = 0; w < kCW; ++w) { mine[0] += RED[w]; mine[1] += RED[kCW + w]; }
             double o[2];
-            const bool ok = sde_exchange<2>(Q, seq, mine, o, wg, lane);
+            const bool ok = meet_exchange<2, 2>(Q.meet, seq, mine, o, wg, lane);
             if (lane == 0) { DEC->xsum[0] = o[0]; DEC->xsum[1] = o[1]; DEC->status = ok ? 0 : 5; }
         }
         __syncthreads();
@@ -489,7 +431,7 @@ __global__ __launch_bounds__(64 * kCW) void rnde_sde_solve_kernel(const SdeParam
             float mine[1] = {0.f};
             for (int w = 0; w < kCW; ++w) mine[0] += RED[w];
             double o[1];
-            const bool ok = sde_exchange<1>(Q, seq, mine, o, wg, lane);
+            const bool ok = meet_exchange<2, 1>(Q.meet, seq, mine, o, wg, lane);
             if (lane == 0) { DEC->xsum[0] = o[0]; DEC->status = ok ? 0 : 5; }
         }
         __syncthreads();
@@ -557,10 +499,10 @@ __global__ __launch_bounds__(64 * kCW) void rnde_sde_solve_kernel(const SdeParam
             if (Q.reg_kind == 2 && lane == 0) {      // this workgroup's share of the two norms of attempt n (summed behind the solve: rnde_sde_eig_reduce_kernel)
                 float e0 = 0.f, e1 = 0.f;
                 for (int w = 0; w < kCW; ++w) { e0 += RED[2 * kCW + w]; e1 += RED[3 * kCW + w]; }
-                Q.eigpart[((size_t)n * 2) * Q.nwg + wg] = e0; Q.eigpart[((size_t)n * 2 + 1) * Q.nwg + wg] = e1;
+                Q.eigpart[((size_t)n * 2) * Q.meet.n + wg] = e0; Q.eigpart[((size_t)n * 2 + 1) * Q.meet.n + wg] = e1;      // (meet.n = nwg: the one copy this kernel reads)
             }
             double o[1];
-            const bool ok = sde_exchange<1>(Q, seq, mine, o, wg, lane);
+            const bool ok = meet_exchange<2, 1>(Q.meet, seq, mine, o, wg, lane);
             if (lane == 0) {
                 const SdeCtlView V{t, dt, qold, dtmax, dtmin, n, n_acc, next_save, cap, S1L, S1s, S2L, S2s, FREEL, STK, OPS, DEC};
                 sde_decide(Q, V, ok, o[0], N, wg);

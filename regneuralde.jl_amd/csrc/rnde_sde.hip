@@ -30,9 +30,9 @@ struct rnde_nsde {
     float* cg_ws = nullptr; size_t cg_ws_floats = 0; std::vector<float> cg_sv;
     int mw = 0;    // 1: the four-waves-per-tile solve kernel (rnde_sdemw.h) for that shape, while a tile per workgroup still fits the chip
     size_t lds_mw = 0;
-    int xch_wg = 0; // workgroups the exchange array is sized for
-    int xch_local = 1;      // the four-waves-per-tile solve pins its workgroups to one XCD while they fit it (<= 32 tiles) and meets through that L2; 0 after the placement check failed once
-    unsigned *xcc = nullptr, *h_xcc = nullptr;
+    int xch_wg = 0; // workgroups the meeting is sized for
+    int xch_local = 1;      // the four-waves-per-tile solve pins its workgroups to one XCD while they fit it and meets through that L2; 0 after the placement check failed once
+    MeetRes res;            // the meeting place (rnde_meet.h)
     int pool_pred = 0;      // library noise: draws the next solve's pool is filled with (0 = all of max_attempts + 1); grows back on demand
     int fix = 0;   // 1: the reference's own shape (drift 8 -> 16 -> 8 k-steps, one-layer diffusion): kernels with compile-time shapes
     int fix_shape = 0, mw_shape = 0;   // what fix / mw are without a pre-activation (those kernels apply none: rnde_nsde_set_pre_act)
@@ -45,14 +45,11 @@ struct rnde_nsde {
     int n_slots = 0;
     SdeMeta *meta = nullptr, *h_meta = nullptr, *acc_meta = nullptr, *h_acc_meta = nullptr;
     SdeFinal *fin = nullptr, *h_fin = nullptr;
-    unsigned long long* xch = nullptr;
-    unsigned* abort_word = nullptr;
     float* eigpart = nullptr;      // RNDE_REG_STIFF: [max_attempts][2][workgroups]
     float *svb = nullptr, *h_svb = nullptr, *slab_f = nullptr, *slab_g = nullptr, *wslab = nullptr, *wslab_r = nullptr, *ev_t = nullptr;
     size_t slab_f_floats = 0, slab_g_floats = 0, ev_t_n = 0;
     float *part = nullptr, *h_part = nullptr;
     float* sv_t_dev = nullptr; size_t sv_cap = 0; std::vector<float> saveat;   // saveat times of the last forward ({R,true} methods)
-    unsigned epoch = 0;
     size_t lds_fwd = 0, lds_bwd = 0;
     // last forward
     int B = 0, ntiles = 0, nwg = 0, n_att = 0, n_acc = 0, n_draws = 0, n_saveval = 0;
@@ -211,22 +208,19 @@ extern "C" rnde_status rnde_nsde_create(const rnde_nsde_config* c, rnde_nsde** o
     ok &= dm((void**)&h->frags_g, (size_t)(Gg.nfrag_f + Gg.nfrag_b + Gg.nfrag_t + 4) * 256);
     ok &= dm((void**)&h->slots, (size_t)h->n_slots * 2 * A * 4);
     ok &= dm((void**)&h->meta, (size_t)(c->max_attempts + 1) * sizeof(SdeMeta)) && dm((void**)&h->acc_meta, (size_t)(c->max_attempts + 1) * sizeof(SdeMeta));
-    ok &= dm((void**)&h->fin, sizeof(SdeFinal)) && dm((void**)&h->abort_word, 16);
-    ok &= dm((void**)&h->xch, (size_t)(c->max_attempts + 4) * 2 * h->xch_wg * 8);
+    ok &= dm((void**)&h->fin, sizeof(SdeFinal));
+    ok &= h->res.create((size_t)c->max_attempts + 4, 2, h->xch_wg) == hipSuccess;
     ok &= dm((void**)&h->svb, (size_t)(c->max_attempts + 1) * 4) && dm((void**)&h->replay, (size_t)(c->max_attempts + 1) * 8);
     ok &= dm((void**)&h->part, (size_t)h->nwg_max * 4);
     if (c->regularize == RNDE_REG_STIFF) ok &= dm((void**)&h->eigpart, (size_t)c->max_attempts * 2 * h->xch_wg * 4);      // per-workgroup partials of the estimate's two norms
     ok &= hipHostMalloc((void**)&h->h_meta, (size_t)(c->max_attempts + 1) * sizeof(SdeMeta)) == hipSuccess;
     ok &= hipHostMalloc((void**)&h->h_acc_meta, (size_t)(c->max_attempts + 1) * sizeof(SdeMeta)) == hipSuccess;
     ok &= hipHostMalloc((void**)&h->h_fin, sizeof(SdeFinal)) == hipSuccess;
-    ok &= dm((void**)&h->xcc, 256 * 4) && hipHostMalloc((void**)&h->h_xcc, 256 * 4) == hipSuccess;
     { const char* e = getenv("RNDE_SDE_LOCAL"); if (e && e[0] == '0') h->xch_local = 0; }
     ok &= hipHostMalloc((void**)&h->h_svb, (size_t)(c->max_attempts + 1) * 4) == hipSuccess;
     ok &= hipHostMalloc((void**)&h->h_part, (size_t)h->nwg_max * 4) == hipSuccess;
     if (!ok) { g_nsde_create_err = "device allocation failed"; rnde_nsde_destroy(h); return RNDE_ERR_HIP; }
     for (auto& e : h->tev) if (hipEventCreate(&e) != hipSuccess) { g_nsde_create_err = "hipEventCreate failed"; rnde_nsde_destroy(h); return RNDE_ERR_HIP; }
-    hipMemset(h->abort_word, 0, 16);
-    hipMemset(h->xch, 0, (size_t)(c->max_attempts + 4) * 2 * h->xch_wg * 8);
     hipMemset(h->frags_f, 0, (size_t)(Gf.nfrag_f + Gf.nfrag_b + Gf.nfrag_t + 4) * 256);
     hipMemset(h->frags_g, 0, (size_t)(Gg.nfrag_f + Gg.nfrag_b + Gg.nfrag_t + 4) * 256);
     *out = h;
@@ -235,11 +229,12 @@ extern "C" rnde_status rnde_nsde_create(const rnde_nsde_config* c, rnde_nsde** o
 
 extern "C" void rnde_nsde_destroy(rnde_nsde* h) {
     if (!h) return;
-    void* d[] = {h->eigpart, h->frags_f, h->frags_g, h->slots, h->tape, h->noise, h->replay, h->meta, h->acc_meta, h->fin, h->xch, h->abort_word, h->svb,
-                 h->slab_f, h->slab_g, h->wslab, h->wslab_r, h->ev_t, h->part, h->sv_t_dev, h->head_ws, h->cg_ws, h->xcc};
+    void* d[] = {h->eigpart, h->frags_f, h->frags_g, h->slots, h->tape, h->noise, h->replay, h->meta, h->acc_meta, h->fin, h->svb,
+                 h->slab_f, h->slab_g, h->wslab, h->wslab_r, h->ev_t, h->part, h->sv_t_dev, h->head_ws, h->cg_ws};
     for (void* p : d) if (p) (void)hipFree(p);
-    void* hd[] = {h->h_meta, h->h_acc_meta, h->h_fin, h->h_svb, h->h_part, h->h_xcc};
+    void* hd[] = {h->h_meta, h->h_acc_meta, h->h_fin, h->h_svb, h->h_part};
     for (void* p : hd) if (p) (void)hipHostFree(p);
+    h->res.destroy();
     for (hipEvent_t e : h->tev) if (e) (void)hipEventDestroy(e);
     if (h->ev_host) (void)hipEventDestroy(h->ev_host);
     delete h;
@@ -248,11 +243,11 @@ extern "C" void rnde_nsde_destroy(rnde_nsde* h) {
 static SdeParams sde_params(rnde_nsde* h, const float* x, const float* noise, int n_pool, int B, float t0, float t1, int keep_tape) {
     SdeParams Q{};
     Q.Gf = h->Gf; Q.Gg = h->Gg; Q.frags_f = h->frags_f; Q.frags_g = h->frags_g; Q.T = h->T;
-    Q.x = x; Q.noise = noise; Q.slots = h->slots; Q.tape = h->tape; Q.meta = h->meta; Q.fin = h->fin; Q.xch = h->xch; Q.abort_word = h->abort_word;
+    Q.x = x; Q.noise = noise; Q.slots = h->slots; Q.tape = h->tape; Q.meta = h->meta; Q.fin = h->fin; Q.xcc = h->res.xcc;
     Q.u_out = nullptr; Q.replay = nullptr; Q.n_replay = 0;
     Q.D = h->D; Q.B = B; Q.ntiles = (B + 15) / 16; Q.nwg = (Q.ntiles + kCW - 1) / kCW;
     Q.n_pool = n_pool; Q.n_slots = h->n_slots; Q.max_attempts = h->cfg.max_attempts; Q.keep_tape = keep_tape; Q.reg_kind = h->cfg.regularize;
-    Q.epoch = h->epoch; Q.t0 = t0; Q.t1 = t1; Q.reltol = h->cfg.reltol; Q.abstol = h->cfg.abstol;
+    Q.t0 = t0; Q.t1 = t1; Q.reltol = h->cfg.reltol; Q.abstol = h->cfg.abstol;
     Q.beta1 = h->beta1; Q.beta2 = h->beta2; Q.gamma = h->gamma; Q.qmin = h->qmin; Q.qmax = h->qmax; Q.qoldinit = h->qoldinit; Q.delta = h->delta;
     Q.order = h->order;
     Q.eigpart = h->eigpart; Q.stab = h->cfg.stability_size > 0.f ? h->cfg.stability_size : 10.6f;      // StochasticDiffEq.alg_stability_size(SOSRI2())
@@ -357,12 +352,13 @@ static rnde_status nsde_forward_impl(rnde_nsde* h, const float* x_dev, const flo
     }
     rnde_status st = sde_pack(h, p_dev, s);
     if (st != RNDE_OK) return st;
-    ++h->epoch;
-    if (h->epoch >= 500000u) {   // tags are epoch * 8192 + sequence: start over (entries are rewritten before they are read)
-        h->epoch = 1;
-        SCHK(h, hipMemsetAsync(h->xch, 0, (size_t)(h->cfg.max_attempts + 4) * 2 * h->xch_wg * 8, s));
-    }
     SdeParams Q = sde_params(h, x_dev, noise_dev, n_pool, B, t0, t1, keep_tape ? 1 : 0);
+    // one workgroup of four waves per tile, all of them resident (they meet once per attempt): 144 VGPRs and ~20 KB of LDS let a CU hold two,
+    // so the limit is 512 tiles = 8,192 columns (the reference's evaluation call with trajectories = 10 is 5,120: mnist_nsde.jl:154-155)
+    const bool mw = h->mw && ntiles <= kSmwMaxTiles;
+    if (mw) Q.nwg = ntiles;
+    Q.meet = h->res.begin(Q.nwg, mw && h->xch_local, s);      // (the one-wave kernels have no one-XCD form)
+    SCHK(h, h->res.err);
     Q.u_out = u_out_dev;
     Q.sv_t = n_saveat > 0 ? h->sv_t_dev : nullptr; Q.nsave = n_saveat; Q.sv_out = sv_out_dev;
     if (n_steps > 0) {
@@ -372,18 +368,13 @@ static rnde_status nsde_forward_impl(rnde_nsde* h, const float* x_dev, const flo
     h->tev_f = false;
     SCHK(h, hipEventRecord(h->tev[0], s));
     hipError_t e;
-    bool local_xch = false;
-    // one workgroup of four waves per tile, all of them resident (they meet once per attempt): 144 VGPRs and ~20 KB of LDS let a CU hold two,
-    // so the limit is 512 tiles = 8,192 columns (the reference's evaluation call with trajectories = 10 is 5,120: mnist_nsde.jl:154-155)
-    if (h->mw && ntiles <= kSmwMaxTiles) {
+    const bool local_xch = !Q.meet.global;
+    if (mw) {
         static DeviceOnce attr;
         if (attr.need()) { SCHK(h, hipFuncSetAttribute((const void*)rnde_sde_solve_mw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr.done(); }
-        Q.nwg = ntiles;
-        local_xch = h->xch_local && ntiles <= 32;      // one XCD has 32 CUs: one workgroup each
-        Q.xch_local = local_xch ? 1 : 0; Q.xcc = h->xcc;
-        hipLaunchKernelGGL(rnde_sde_solve_mw_kernel, dim3(local_xch ? 8 * ntiles : ntiles), dim3(kSmwThreads), h->lds_mw, s, Q);
+        hipLaunchKernelGGL(rnde_sde_solve_mw_kernel, dim3(MeetRes::grid(Q.meet)), dim3(kSmwThreads), h->lds_mw, s, Q);
         e = hipGetLastError();
-        if (local_xch && e == hipSuccess) e = hipMemcpyAsync(h->h_xcc, h->xcc, (size_t)ntiles * 4, hipMemcpyDeviceToHost, s);
+        if (local_xch && e == hipSuccess) e = h->res.queue_check(Q.meet, s, nullptr, false);      // (a time-out reaches the host in SdeFinal::status)
     } else
         e = h->fix ? launch_solve<8, 16>(h, Q, s)
                    : h->ga ? (h->NKD == 4 ? launch_solve<4, -1>(h, Q, s) : (h->NKD == 8 ? launch_solve<8, -1>(h, Q, s) : launch_solve<16, -1>(h, Q, s)))
@@ -404,9 +395,7 @@ static rnde_status nsde_forward_impl(rnde_nsde* h, const float* x_dev, const flo
         SCHK(h, hipEventSynchronize(h->ev_host));
     } else SCHK(h, hipStreamSynchronize(s));
     if (local_xch) {   // did the workgroups really share an XCD?  If not, their meeting had no coherent meeting place: redo the solve the safe way, for good
-        bool same = true;
-        for (int i = 1; i < ntiles; ++i) same = same && h->h_xcc[i] == h->h_xcc[0];
-        if (!same) {
+        if (meet_split(h->res.chk, ntiles, false)) {      // (before the solve's status is looked at: a split meeting may also have timed out)
             fprintf(stderr, "[rnde] SDE solve: workgroups pinned by block index landed on different XCDs; using the placement-independent exchange from now on\n");
             h->xch_local = 0;
             return nsde_forward_impl(h, x_dev, p_dev, B, t0, t1, lib_noise ? nullptr : noise_dev, lib_noise ? 0 : n_pool, seed, steps_host, n_steps, u_out_dev, nfe1_out, nfe2_out,
@@ -451,7 +440,7 @@ static rnde_status nsde_forward_impl(rnde_nsde* h, const float* x_dev, const flo
             }
             h->err = "noise pool or stack capacity exhausted (n_pool must cover 1 + attempts draws)"; return RNDE_ERR_BAD_ARG;
         default:
-            (void)hipMemsetAsync(h->abort_word, 0, 16, s);
+            (void)h->res.clear_abort(s);
             h->err = "a workgroup of the one-launch solve timed out waiting for the others (not all resident?)";
             return RNDE_ERR_HIP;
     }

@@ -26,11 +26,11 @@ __global__ __launch_bounds__(kSmwThreads) void rnde_sde_solve_mw_kernel(const Sd
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // xch_local: the grid is 8 x nwg and only the workgroups with blockIdx % 8 == 0 work -- under round-robin dispatch all on one XCD (each
-    // records its XCC id; the host verifies and falls back to the placement-independent exchange if the assumption ever fails)
-    if (Q.xch_local && (blockIdx.x & 7)) return;
-    const int wg = Q.xch_local ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    if (Q.xch_local && tid == 0) Q.xcc[wg] = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 15;   // HW_REG_XCC_ID
+    // one-XCD meeting: the grid is 8 x nwg and only the workgroups with blockIdx % 8 == 0 work -- under round-robin dispatch all on one XCD
+    // (each records its XCC id; the host verifies and falls back to the placement-independent exchange if the assumption ever fails)
+    if (!Q.meet.global && (blockIdx.x & 7)) return;
+    const int wg = !Q.meet.global ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    if (!Q.meet.global && tid == 0) Q.xcc[wg] = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 15;   // HW_REG_XCC_ID
     float* X0 = smem;                 // [32][16] drift input of the stage
     float* X1 = smem + 512;           // [32][16] diffusion input
     float* HD = smem + 1024;          // [64][16] hidden layer of the drift
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(kSmwThreads) void rnde_sde_solve_mw_kernel(const Sd
             float mine[2] = {0.f, 0.f};
             for (int w = 0; w < kCW; ++w) { mine[0] += RED[w]; mine[1] += RED[kCW + w]; }
             double o[2];
-            const bool ok = sde_exchange<2>(Q, seq, mine, o, wg, lane);
+            const bool ok = meet_exchange<2, 2>(Q.meet, seq, mine, o, wg, lane);
             if (lane == 0) { DEC->xsum[0] = o[0]; DEC->xsum[1] = o[1]; DEC->status = ok ? 0 : 5; }
         }
         __syncthreads();
@@ -194,7 +194,7 @@ __global__ __launch_bounds__(kSmwThreads) void rnde_sde_solve_mw_kernel(const Sd
             float mine[1] = {0.f};
             for (int w = 0; w < kCW; ++w) mine[0] += RED[w];
             double o[1];
-            const bool ok = sde_exchange<1>(Q, seq, mine, o, wg, lane);
+            const bool ok = meet_exchange<2, 1>(Q.meet, seq, mine, o, wg, lane);
             if (lane == 0) { DEC->xsum[0] = o[0]; DEC->status = ok ? 0 : 5; }
         }
         __syncthreads();
@@ -319,10 +319,10 @@ __global__ __launch_bounds__(kSmwThreads) void rnde_sde_solve_mw_kernel(const Sd
             if (Q.reg_kind == 2 && lane == 0) {      // this workgroup's share of the two norms of attempt n (summed behind the solve: rnde_sde_eig_reduce_kernel)
                 float e0 = 0.f, e1 = 0.f;
                 for (int w = 0; w < kCW; ++w) { e0 += RED[2 * kCW + w]; e1 += RED[3 * kCW + w]; }
-                Q.eigpart[((size_t)n * 2) * Q.nwg + wg] = e0; Q.eigpart[((size_t)n * 2 + 1) * Q.nwg + wg] = e1;
+                Q.eigpart[((size_t)n * 2) * Q.meet.n + wg] = e0; Q.eigpart[((size_t)n * 2 + 1) * Q.meet.n + wg] = e1;      // (meet.n = nwg: the one copy this kernel reads)
             }
             double o[1];
-            const bool ok = sde_exchange<1>(Q, seq, mine, o, wg, lane);
+            const bool ok = meet_exchange<2, 1>(Q.meet, seq, mine, o, wg, lane);
             if (lane == 0) {
                 const SdeCtlView V{t, dt, qold, dtmax, dtmin, n, n_acc, next_save, cap, S1L, S1s, S2L, S2s, FREEL, STK, OPS, DEC};
                 sde_decide(Q, V, ok, o[0], N, wg);

@@ -14,7 +14,7 @@
 //     prologue of the attempt kernel; StepMeta / StepState records are written exactly as before (the reverse pass reads them).
 // The workgroups of a column tile still hand the layer-1 partials to each other through their XCD's L2 (slab_put / slab_poll_sum);
 // the meeting crosses XCDs, which is why it uses agent-scope (sc1) stores and loads on granules every workgroup writes once per solve
-// (entry index = attempt number, tag = epoch * 8192 + attempt + 1: nothing is ever reused inside a launch, nothing needs clearing).
+// (rnde_meet.h, the form with a fixed stride of 256: entry index = attempt number, nothing is ever reused inside a launch, nothing needs clearing).
 // All workgroups must be resident at once (<= 256, one per CU); every spin is bounded, a time-out raises the abort word the attempt
 // kernels use and the host redoes the solve launch by launch.
 // The launches that used to stand around it are inside it too (SolveSync::fold, host switch RNDE_SOLVE_FOLD): in front of the attempt loop the
@@ -29,64 +29,10 @@
 #endif
 #include "rnde_stage_persist.h"
 #include "rnde_solve_sync.h"
+#include "rnde_meet.h"
 #include "rnde_x3.h"
 
 namespace rnde {
-
-typedef __attribute__((address_space(1))) unsigned long long solve_gu64;
-
-// Cross-workgroup sums of the norm partials of attempt `seq`.  Called by wave 0 of every workgroup; `mine` valid in lane 0.  The sums come
-// out as sum_partials forms them: lane l adds entries l, l + 64, l + 128, l + 192 in that order in double, then the wave reduction.
-// nval = 1 (error norm) or 3 (+ the two norms of the stiffness estimate).  false: timed out / aborted.
-__device__ __forceinline__ bool solve_meet(const SolveSync& Z, const PersistSync& Y, int seq, int nwg, int wg, int nval, const float (&mine)[3],
-                                           double (&out)[3], int lane) {
-    const unsigned tag = Z.epoch * 8192u + (unsigned)seq + 1u;
-    solve_gu64* base = (solve_gu64*)Z.xch + (size_t)seq * 3 * 256;
-    if (lane == 0) {
-#pragma unroll
-        for (int v = 0; v < 3; ++v) {
-            if (v < nval) {
-                float m = mine[v];
-                if (m != m) m = __uint_as_float(0x7FC00000u);
-                __hip_atomic_store(base + (size_t)v * 256 + wg, ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(m), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
-    out[0] = out[1] = out[2] = 0.0;
-#pragma unroll
-    for (int v = 0; v < 3; ++v) {
-        if (v >= nval) break;
-        // (one set of polling loads at a time: keeping a second set in flight -- measured in round 4 -- makes an attempt 0.3 us SLOWER; the extra
-        //  reads of the same lines on the memory side delay the stores they are waiting for; a back-off between polls, s_sleep 4 / 8 / 16, does not help
-        //  either: 23.37 / 23.46 / 23.60 us against 23.34)
-        unsigned long long e[4] = {0, 0, 0, 0};
-        bool ok[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) ok[q] = lane + 64 * q >= nwg;
-        int spins = 0;
-        while (true) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (!ok[q]) {
-                    e[q] = __hip_atomic_load(base + (size_t)v * 256 + lane + 64 * q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    ok[q] = (unsigned)(e[q] >> 32) == tag;
-                }
-            }
-            if (__all(ok[0] && ok[1] && ok[2] && ok[3])) break;
-            if (++spins > Y.max_spins || ((spins & 255) == 0 && __hip_atomic_load(Y.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-                if (lane == 0) __hip_atomic_store(Y.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                return false;
-            }
-        }
-        double s = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (lane + 64 * q < nwg) s += (double)__uint_as_float((unsigned)(e[q] & 0xFFFFFFFFull));
-        out[v] = wave_sum_d(s);
-    }
-    return true;
-}
 
 // the controller state through LDS: written by one lane, read back by every wave as scalars (twelve words)
 static_assert(sizeof(StepState) == 48, "StepState is twelve 4-byte words");
@@ -296,7 +242,7 @@ __global__ __launch_bounds__(64 * 7) void rnde_stage_solve_kernel(const StagePar
             float mine[3] = {0.f, 0.f, 0.f};
             for (int i = 0; i < gWT; ++i) { mine[0] += RED[i]; mine[1] += RED[8 + i]; }
             if (lane == 0) { P.initpart[(size_t)prow * P.nwg + wg] = mine[0]; if (nval > 1) P.initpart[(size_t)(prow + 1) * P.nwg + wg] = mine[1]; }
-            return solve_meet(Z, Y, Z.n_limit + row, P.nwg, wg, nval, mine, o, lane);
+            return meet_exchange_256(Z.xch, Z.epoch, Y.abort_flag, Y.max_spins, Z.n_limit + row, P.nwg, wg, nval, mine, o, lane);
         };
         const size_t tileA = (((size_t)(kSlabBufs - 2) * Q.C + ct) * gR + rb) * gHT, tileB = (((size_t)(kSlabBufs - 1) * Q.C + ct) * gR + rb) * gHT;
         double o[3] = {0.0, 0.0, 0.0};
@@ -522,7 +468,7 @@ __global__ __launch_bounds__(64 * 7) void rnde_stage_solve_kernel(const StagePar
             float mine[3] = {0.f, 0.f, 0.f};
             for (int i = 0; i < gWT; ++i) { mine[0] += RED[i]; if (three) { mine[1] += RED[8 + i]; mine[2] += RED[16 + i]; } }
             double o[3];
-            const bool ok = solve_meet(Z, Y, n, P.nwg, wg, P.reg_kind >= 2 ? 3 : 1, mine, o, lane);
+            const bool ok = meet_exchange_256(Z.xch, Z.epoch, Y.abort_flag, Y.max_spins, n, P.nwg, wg, P.reg_kind >= 2 ? 3 : 1, mine, o, lane);
             ZSTAMP(5); ZARRIVE(1);
             // the state before attempt n + 1, from the sums just formed (qold^beta2 of the state this attempt started from: wave 3 left it in QP while
             // the stages ran; the barrier in front of the meeting ordered it)

@@ -1,4 +1,4 @@
-// micro-benchmark: the cross-XCD MEETING of the one-launch solve (csrc/rnde_stage_solve.h `solve_meet`): 224 workgroups, one per CU, each contributes one
+// micro-benchmark: the cross-XCD MEETING of the one-launch solve (csrc/rnde_meet.h `meet_exchange_256`): 224 workgroups, one per CU, each contributes one
 // float per round; every workgroup needs the sum of all of them (in a FIXED order) before it goes on.  The product's form (FLAT) measured 2.2-3.0 us from the
 // LAST arrival to the way out (profiles/r05_attempt_stamps.txt) -- slower than a kernel boundary.  Which form is faster?
 //   FLAT        every workgroup publishes an 8-byte {value, tag} granule (agent-scope store) and polls ALL granules (agent-scope loads): 224 pollers x 14 lines
