@@ -66,15 +66,22 @@ mutable struct Handle
     ptr::Ptr{Cvoid}
     cfg::NodeConfig
     last_nfe::Int
-    function Handle(cfg::NodeConfig)
+    # tiled = true: rnde_node_create_tiled (include/rnde.h) -- Dense chains wider than 64 whose padded weights fit LDS (tiled_lds_bytes(cfg) <=
+    # 160 KB).  Its reverse pass treats step sizes and times as constants: the config must carry track_ctrl = track_initdt = 0
+    # (config_for(...; track = false)), the library refuses anything else by name.
+    function Handle(cfg::NodeConfig; tiled::Bool = false)
         out = Ref{Ptr{Cvoid}}(C_NULL)
-        st = ccall((:rnde_node_create, LIB), Cint, (Ref{NodeConfig}, Ref{Ptr{Cvoid}}), cfg, out)
-        st == 0 || error("rnde_node_create: ", unsafe_string(ccall((:rnde_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
+        st = tiled ? ccall((:rnde_node_create_tiled, LIB), Cint, (Ref{NodeConfig}, Ref{Ptr{Cvoid}}), cfg, out) :
+                     ccall((:rnde_node_create, LIB), Cint, (Ref{NodeConfig}, Ref{Ptr{Cvoid}}), cfg, out)
+        st == 0 || error(tiled ? "rnde_node_create_tiled: " : "rnde_node_create: ", unsafe_string(ccall((:rnde_last_error, LIB), Cstring, (Ptr{Cvoid},), C_NULL)))
         h = new(out[], cfg, 0)
         finalizer(h -> ccall((:rnde_node_destroy, LIB), Cvoid, (Ptr{Cvoid},), h.ptr), h)
         return h
     end
 end
+
+# LDS bytes of a tile of the tiled engine for this config (no device needed; -1: a malformed shape); the limit is 160 * 1024
+tiled_lds_bytes(cfg::NodeConfig) = ccall((:rnde_node_tiled_lds_bytes, LIB), Int64, (Ref{NodeConfig},), cfg)
 
 check(h::Handle, st) = st == 0 ||
     error("rnde status $st: ", unsafe_string(ccall((:rnde_last_error, LIB), Cstring, (Ptr{Cvoid},), h.ptr)))
@@ -133,10 +140,11 @@ end
 
 # Flux.Dense chain (MLPDynamics / TDChain) -> config.  `p` from Flux.destructure is accepted as is.
 function config_for(dims::Vector{Int}, acts::Vector{Int}; time_dep, max_batch, reltol, abstol, regularize,
-                    max_attempts = 160, device = 0, pre_act = false)
+                    max_attempts = 160, device = 0, pre_act = false, track = true)
     d = ntuple(i -> Int32(i <= length(dims) ? dims[i] : 0), 9)
     a = ntuple(i -> Int32(i <= length(acts) ? acts[i] : 0), 8)
-    NodeConfig(length(acts), d, a, time_dep, pre_act, max_batch, 0, reltol, abstol, regularize, 1, 1, 1, max_attempts, device, 0, 0, 0, 0)
+    tr = track ? 1 : 0      # track_ctrl, track_initdt (false: step sizes and times are constants of the reverse pass; what the tiled engine serves)
+    NodeConfig(length(acts), d, a, time_dep, pre_act, max_batch, 0, reltol, abstol, regularize, 1, tr, tr, max_attempts, device, 0, 0, 0, 0)
 end
 
 """

@@ -114,6 +114,30 @@ int32_t     rnde_param_count(const rnde_node_config* cfg);
 rnde_status rnde_node_create(const rnde_node_config* cfg, rnde_node** out);
 void        rnde_node_destroy(rnde_node* h);
 
+/* The tiled engine (opt-in; rnde_node_create never selects it): the same layer for Dense chains WIDER than the chain engine's 64, on the tile
+ * layout of TrackedFFJORD's chain dynamics -- one workgroup of four waves per 16 batch columns, the padded weights resident in LDS, the whole
+ * adaptive Tsit5 solve in one launch (the tiles meet once per attempt), the reverse sweep in one launch with no meeting.
+ * Serves: 1..8 Dense layers, Chain or TDChain (time_dep), the six rnde_act activations in any layer, dims[0] == dims[n_layers], pre_act =
+ *   RNDE_PRE_NONE, col_tile = 0, Tsit5, regularize RNDE_REG_NONE or RNDE_REG_ERR (cb_save_start honoured), max_batch <= 4096 (256 resident
+ *   tiles), max_attempts <= 8000.
+ * Widths are limited by BYTES, not rows: rnde_node_tiled_lds_bytes(cfg) -- padded weights (in_p x (out_p + 1) floats per layer, plus the t
+ *   column and the bias), the input tile, every layer's output and two VJP vectors ([rows_p][16] each), 128 floats of scratch -- must not
+ *   exceed 163840 (160 KB); the solve and the reverse sweep share the layout.  [2,128,128,2] needs 120512 bytes, [64,192,64] 146944 (served);
+ *   [64,256,64] needs 192768 and is refused with that count in the message.  The state may have more than 64 rows where the bytes allow.
+ *   rnde_node_tiled_lds_bytes needs no device; -1 for a malformed shape.
+ * CONSTANT STEP SIZES IN THE REVERSE: rnde_node_backward on this engine differentiates the recorded Runge-Kutta program with step sizes and
+ *   times as constants (the cotangent of a saved value EEst * dt reaches the stages through EEst) and returns tspan_bar = (0, 0).  That is
+ *   track_ctrl = track_initdt = 0, and rnde_node_create_tiled REFUSES a config with either flag set: nobody gets the constant-step gradient
+ *   without asking for it.  (Differentiating the controller on this layout takes one meeting per reversed step: not built.)
+ * Calls served on such a handle: rnde_node_forward, _forward_replay, _backward, _release_tape, _steps, _timing (solve, reverse sweep, tile
+ *   reduction; always recorded), _last_attempts, rnde_debug_feval, rnde_node_forward_host / _backward_host, rnde_node_destroy.
+ * Refused with RNDE_ERR_BAD_ARG and a message naming the entry: rnde_node_forward_saveat / _everystep, rnde_debug_attempt, rnde_bench_*,
+ *   rnde_node_set_coupling, rnde_node_set_matrix_mode(h, 1), rnde_node_classifier_grad, rnde_node_backward_async; a tape pool
+ *   (rnde_tapes_create) holds rnde_node_create instances only.  A meeting of the solve that times out is RNDE_ERR_HIP with a message that
+ *   says so; nothing falls back to other arithmetic. */
+rnde_status rnde_node_create_tiled(const rnde_node_config* cfg, rnde_node** out);
+int64_t     rnde_node_tiled_lds_bytes(const rnde_node_config* cfg);
+
 /* Forward solve on [t0,t1].  u_out_dev: D x B.  saveval_host (may be NULL when regularize==0):
  * room for max_attempts+1 floats.  keep_tape != 0 records what rnde_node_backward needs.
  * nfe_out = sol.destats.nf (neural_ode.jl:72,:142).  Synchronises `stream` before returning. */

@@ -74,6 +74,9 @@ def lib():
     L.rnde_node_create.argtypes = [C.POINTER(NodeConfig), C.POINTER(vp)]
     L.rnde_node_destroy.argtypes = [vp]
     L.rnde_node_destroy.restype = None
+    L.rnde_node_create_tiled.argtypes = [C.POINTER(NodeConfig), C.POINTER(vp)]
+    L.rnde_node_tiled_lds_bytes.argtypes = [C.POINTER(NodeConfig)]
+    L.rnde_node_tiled_lds_bytes.restype = C.c_int64
     L.rnde_node_forward.argtypes = [vp, vp, vp, i32, f, f, vp, i64p, fp, i32p, i32, vp]
     L.rnde_node_forward_saveat.argtypes = [vp, vp, vp, i32, f, f, fp, i32, vp, i64p, fp, i32p, i32, vp]
     L.rnde_node_forward_everystep.argtypes = [vp, vp, vp, i32, f, f, i32, vp, i32, fp, i32p, i64p, fp, i32p, i32, vp]
@@ -219,7 +222,8 @@ EXPORTS = ["rnde_version", "rnde_last_error", "rnde_param_count", "rnde_node_cre
            "rnde_ffjord_forward_replay", "rnde_ffjord_steps", "rnde_ffjord_backward", "rnde_ffjord_sample", "rnde_ffjord_debug_feval",
            "rnde_ffjord_timing", "rnde_ffjord_create_tiled", "rnde_ffjord_engine", "rnde_ffjord_forward_kinetic",
            "rnde_ffjord_forward_kinetic_replay", "rnde_ffjord_backward_kinetic", "rnde_ffjord_debug_feval_kinetic", "rnde_ffjord_step_log",
-           "rnde_ffjord_chain_param_count", "rnde_ffjord_create_chain", "rnde_ffjord_forward_exact", "rnde_ffjord_forward_exact_replay"]
+           "rnde_ffjord_chain_param_count", "rnde_ffjord_create_chain", "rnde_ffjord_forward_exact", "rnde_ffjord_forward_exact_replay",
+           "rnde_node_create_tiled", "rnde_node_tiled_lds_bytes"]
 
 
 def check(h, status):

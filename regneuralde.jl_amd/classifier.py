@@ -58,6 +58,9 @@ def fused_loss_and_grad(model, x, y, lam=1.0e2, regularize=True, tspan=None, syn
     import ctypes as C
     from . import _lib
     node = model.node
+    if getattr(node, "engine", None) == "tiled":
+        raise ValueError('fused_loss_and_grad: a TrackedNeuralODE(engine="tiled") layer is not served (rnde_node_classifier_grad and '
+                         "rnde_node_backward_async run on the stage engine); call the layer and use autograd, or build it with the default engine")
     L = _lib.lib()
     from .node import _check_f32
     for name, t in (("x", x), ("y", y), ("p2", model.p2), ("p3", model.p3)):

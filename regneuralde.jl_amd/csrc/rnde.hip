@@ -3,6 +3,7 @@
 #include "rnde_node.h"
 
 static thread_local std::string g_create_err;   // last create error of the calling thread (rnde_last_error(NULL)); no process-wide mutable state
+void rnde_set_create_error(const std::string& msg) { g_create_err = msg; }
 extern "C" const char* rnde_version(void) { return "rnde 0.1.0 (gfx950)"; }
 extern "C" const char* rnde_last_error(const rnde_node* h) { return h ? h->err.c_str() : g_create_err.c_str(); }
 
@@ -55,7 +56,7 @@ static bool chain_geo(const rnde_node_config* c, ChainGeo& G) {
 }
 static rnde_status chain_create(const rnde_node_config* c, rnde_node** out) {
     ChainGeo G;
-    if (!chain_geo(c, G)) { g_create_err = "unsupported dynamics: beyond the 2-layer time-dependent form the kernels cover Dense chains of width <= 64"; return RNDE_ERR_BAD_ARG; }
+    if (!chain_geo(c, G)) { g_create_err = "unsupported dynamics: beyond the 2-layer time-dependent form the kernels cover Dense chains of width <= 64 (rnde_node_create_tiled / engine = \"tiled\" serves wider Dense chains whose weights fit LDS, with track_ctrl = track_initdt = 0; a tape pool, rnde_tapes_create, holds rnde_node_create instances only)"; return RNDE_ERR_BAD_ARG; }
     // LDS: fragment tables rounded up to whole 1 KiB DMA units, then 64 floats of reduction scratch
     size_t lds_f = ((size_t)((G.nfrag_f + G.nfrag_b + 3) / 4) * 256 + 64) * 4, lds_b = ((size_t)((G.nfrag_f + G.nfrag_b + G.nfrag_t + 3) / 4) * 256 + 64) * 4;
     if (lds_b > 160 * 1024) { g_create_err = "chain too large: its weight fragments must fit the 160 KB LDS of a CU"; return RNDE_ERR_BAD_ARG; }
@@ -440,6 +441,7 @@ extern "C" rnde_status rnde_node_create(const rnde_node_config* c, rnde_node** o
 
 extern "C" void rnde_node_destroy(rnde_node* h) {
     if (!h) return;
+    node_tiled_destroy(h);
     void* d[] = {h->f0, h->h0, h->u1, h->f1, h->h1, h->arena, h->xcopy, h->pcopy, h->spwB, h->spwD, h->spwBt, h->spwDt, h->slab2,
                  h->ctl, h->ctl_final, h->meta, h->initrec, h->errpart, h->initpart};
     if (h->mbox || h->h_mbox) {   // these alias the mailbox
@@ -495,6 +497,7 @@ rnde_status couple_sum(rnde_node* h, float* partials, long long count, hipStream
 }
 extern "C" rnde_status rnde_node_set_coupling(rnde_node* h, rnde_comm* c, int32_t global_batch) {
     if (!h) return RNDE_ERR_BAD_ARG;
+    RNDE_TILED_REFUSE(h, "rnde_node_set_coupling is not served (one controller over several shards: the stage engine and the chain engine's multi-wave kernels, rnde_node_create)");
     if (!c) { h->couple = nullptr; h->couple_batch = 0; h->couple_world = 1; return RNDE_OK; }
     const int world = rnde_comm_world(c);
     if (h->engine != 2 && !(h->engine == 3 && h->mw)) { h->err = "coupled controller: the stage engine (MNIST form, col_tile 0 or 16) and the chain engine's multi-wave kernels only"; return RNDE_ERR_BAD_ARG; }
@@ -679,6 +682,7 @@ static bool persist_failed(rnde_node* h, int grid, int C, int R, hipStream_t s) 
 rnde_status forward_impl(rnde_node* h, const float* x_dev, const float* p_dev, int32_t B, float t0, float t1,
                                 float* u_out_dev, const float* saveat_host, int32_t n_saveat, float* sv_out_dev,
                                 int64_t* nfe_out, float* saveval_host, int32_t* n_saveval_out, int32_t keep_tape, void* stream) {
+    if (h && h->engine == 4) return node_tiled_forward(h, x_dev, p_dev, B, t0, t1, u_out_dev, saveat_host, n_saveat, sv_out_dev, nfe_out, saveval_host, n_saveval_out, keep_tape, stream);
     // a solve may ask to be redone for two independent reasons (the record slab has to grow; a one-launch kernel gave up and the handle fell back):
     // both can happen back to back, each at most once per cause -- anything beyond that is an error, not a status the caller should ever see
     rnde_status st = RNDE_INTERNAL_RETRY;
@@ -1061,6 +1065,7 @@ extern "C" rnde_status rnde_node_forward_everystep(rnde_node* h, const float* x_
                                                    float* sol_out_dev, int32_t capacity, float* t_host_out, int32_t* n_out, int64_t* nfe_out,
                                                    float* saveval_host, int32_t* n_saveval_out, int32_t keep_tape, void* stream) {
     if (!h || !n_out || !sol_out_dev || capacity < 1) return RNDE_ERR_BAD_ARG;
+    RNDE_TILED_REFUSE(h, "rnde_node_forward_everystep is not served (the end state only; save_everystep runs on the engines of rnde_node_create)");
     rnde_status st = forward_impl(h, x_dev, p_dev, B, t0, t1, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, stream);
     if (st != RNDE_OK) return st;
     std::vector<float> times;
@@ -1106,6 +1111,7 @@ extern "C" rnde_status rnde_node_set_timing(rnde_node* h, int32_t on) {
     return RNDE_OK;
 }
 extern "C" rnde_status rnde_node_timing(rnde_node* h, float* fwd_attempts_ms, float* rev_sweep_ms, float* rev_rest_ms) {
+    if (h && h->engine == 4) return node_tiled_timing(h, fwd_attempts_ms, rev_sweep_ms, rev_rest_ms);      // (its events are always recorded: the solve, the reverse sweep, the tile reduction)
     if (!h || !h->timing) return RNDE_ERR_BAD_ARG;
     float a = -1.f, b = -1.f, c = -1.f;
     if (h->tev_fwd) { HIPCHK(h, hipEventSynchronize(h->tev[1])); HIPCHK(h, hipEventElapsedTime(&a, h->tev[0], h->tev[1])); }
@@ -1125,6 +1131,7 @@ extern "C" int32_t rnde_node_one_launch_solves(const rnde_node* h) { return h ? 
 extern "C" rnde_status rnde_node_set_matrix_mode(rnde_node* h, int32_t mode) {
     if (!h) return RNDE_ERR_BAD_ARG;
     if (mode != RNDE_MATRIX_F32 && mode != RNDE_MATRIX_BF16X3) { h->err = "matrix mode: 0 (fp32-input MFMA) or 1 (bf16x3 on the matrix cores)"; return RNDE_ERR_BAD_ARG; }
+    if (mode == RNDE_MATRIX_BF16X3) RNDE_TILED_REFUSE(h, "rnde_node_set_matrix_mode(h, 1) is not served (its layer products are the fp32-input MFMA, mode 0; bf16x3 serves the MNIST form on the stage engine)");
     h->x3 = (mode == RNDE_MATRIX_BF16X3 && h->x3B && h->x3D) ? 1 : 0;
     return RNDE_OK;
 }
@@ -1159,6 +1166,7 @@ extern "C" rnde_status rnde_node_forward_host(rnde_node* h, const float* x, cons
 extern "C" rnde_status rnde_debug_feval(rnde_node* h, const float* u_dev, const float* p_dev, int32_t B, float t,
                                         float* out_dev, void* stream) {
     if (!h || B < 1 || B > h->cfg.max_batch) return RNDE_ERR_BAD_ARG;
+    if (h->engine == 4) return node_tiled_feval(h, u_dev, p_dev, B, t, out_dev, stream);
     hipStream_t s = (hipStream_t)stream;
     StepParams P = make_params(h, u_dev, B, 0.f, 1.f, 0);
     P.forced = 1; P.forced_t = t; P.dbg_out = out_dev;
@@ -1187,6 +1195,7 @@ extern "C" rnde_status rnde_debug_attempt(rnde_node* h, const float* uprev_dev, 
                                           int32_t B, float t, float dt, float* k_out_dev, float* unew_out_dev,
                                           float* eest_out, void* stream) {
     if (!h || B < 1 || B > h->cfg.max_batch) return RNDE_ERR_BAD_ARG;
+    RNDE_TILED_REFUSE(h, "rnde_debug_attempt is not served (its solve is one launch with no single-attempt entry; rnde_node_forward_replay runs a given attempt sequence)");
     hipStream_t s = (hipStream_t)stream;
     h->have_tape = false;
     StepParams P = make_params(h, uprev_dev, B, 0.f, 1.f, 0);
@@ -1249,6 +1258,7 @@ extern "C" rnde_status rnde_bench_attempt_cold_tape(rnde_node* h, const float* x
 static rnde_status bench_attempt_impl(rnde_node* h, const float* x_dev, const float* p_dev, int32_t B, int32_t iters, int32_t taped,
                                       float* mean_us_out, void* stream) {
     if (!h || B < 1 || B > h->cfg.max_batch || iters < 1) return RNDE_ERR_BAD_ARG;
+    RNDE_TILED_REFUSE(h, "rnde_bench_attempt* are not served (there is no per-attempt launch to time; rnde_node_timing reports the one-launch solve and the reverse sweep)");
     hipStream_t s = (hipStream_t)stream;
     h->have_tape = false;
     if (taped > 1) { const rnde_status sa = ensure_arena(h, std::min<long long>(taped, h->cfg.max_attempts)); if (sa != RNDE_OK) return sa; }

@@ -38,6 +38,7 @@
 #pragma once
 #include "rnde_bffjord.h"      // FfStepRec
 #include "rnde_ffjordt.h"      // the tile layout's constants; rnde_meet.h
+#include "rnde_tile_meet.h"    // tile_meet
 
 namespace rnde {
 
@@ -82,26 +83,6 @@ struct TileRevParams {
     int exact;                        // the tape of an exact-trace forward (never with KIN)
     float* scratch;                   // exact: [ntiles][Dyn::scratch_floats] or NULL, as the solve's
 };
-
-// Publish this tile's three partials (wave 0), collect everybody's sums in tile order; false when the meeting timed out (every thread).
-__device__ __forceinline__ bool tile_meet(const Meet& M, float* red, int seq, float a, float b, float c, double (&out)[3], int tile, int tid) {
-    const int lane = tid & 63, wave = tid >> 6;
-    a = wave_sum_f(a); b = wave_sum_f(b); c = wave_sum_f(c);
-    if (lane == 0) { red[wave] = a; red[4 + wave] = b; red[8 + wave] = c; }
-    __syncthreads();
-    double* RD = (double*)(red + 64);
-    if (wave == 0) {
-        const float mine[3] = {((red[0] + red[1]) + red[2]) + red[3], ((red[4] + red[5]) + red[6]) + red[7], ((red[8] + red[9]) + red[10]) + red[11]};
-        double o[3];
-        const bool ok = meet_exchange<3, 3>(M, seq, mine, o, tile, lane);
-        if (lane == 0) { RD[0] = o[0]; RD[1] = o[1]; RD[2] = o[2]; red[70] = ok ? 1.f : 0.f; }
-    }
-    __syncthreads();
-    const bool ok = red[70] != 0.f;
-    out[0] = RD[0]; out[1] = RD[1]; out[2] = RD[2];
-    __syncthreads();
-    return ok;
-}
 
 // The whole adaptive solve in one launch: forward (dir = +1; Hutchinson, or Q.exact: the exact trace with no probe), replay along P.replay,
 // sampling (dir = -1, exact trace, tau = t1 - t).

@@ -51,7 +51,8 @@ struct rnde_node {
     int D = 0, H = 0, P = 0, BT = 8, act2 = 1;
     int Bpad_max = 0, nwg_max = 0;
     // stage engine (rnde_stage.h)
-    int engine = 1;                       // 1 column-owner, 2 stage kernels, 3 chain engine (rnde_chain.h)
+    int engine = 1;                       // 1 column-owner, 2 stage kernels, 3 chain engine (rnde_chain.h), 4 tiled engine (rnde_node_tile.h)
+    struct rnde_node_tiled* tiled = nullptr;   // engine 4: everything of that engine (rnde_node_tile.hip); the fields below it uses are cfg, D, P, h_meta, n_att, B, have_tape, err
     ChainGeo cg{}; float* cfrags = nullptr; int NKD = 0, chain_alt = 0;
     int chain_ga = 0;             // a layer's activation is other than identity / tanh: the kernel variants that serve every rnde_act (ALT / LAT = 2)
     size_t chain_lds_f = 0, chain_lds_b = 0;
@@ -126,6 +127,25 @@ struct rnde_node {
             (h)->err = std::string(#call) + ": " + hipGetErrorString(e__);                           \
             return RNDE_ERR_HIP;                                                                     \
         }                                                                                            \
+    } while (0)
+
+// ---- rnde_node_tile.hip: the tiled engine (engine 4) behind the public entries of rnde.hip / rnde_reverse.hip ----
+void rnde_set_create_error(const std::string& msg);      // (rnde.hip: what rnde_last_error(NULL) returns on this thread)
+void node_tiled_destroy(rnde_node* h);
+rnde_status node_tiled_forward(rnde_node* h, const float* x_dev, const float* p_dev, int32_t B, float t0, float t1, float* u_out_dev,
+                               const float* saveat_host, int32_t n_saveat, float* sv_out_dev, int64_t* nfe_out, float* saveval_host,
+                               int32_t* n_saveval_out, int32_t keep_tape, void* stream);
+rnde_status node_tiled_backward(rnde_node* h, const float* u_bar_dev, const float* saveval_bar_host, float* x_bar_dev, float* p_bar_dev,
+                                float* tspan_bar_host, void* stream);
+rnde_status node_tiled_feval(rnde_node* h, const float* u_dev, const float* p_dev, int32_t B, float t, float* out_dev, void* stream);
+rnde_status node_tiled_timing(rnde_node* h, float* fwd_ms, float* rev_sweep_ms, float* rev_rest_ms);
+// an entry the tiled engine does not serve: the message names the entry and the alternative
+#define RNDE_TILED_REFUSE(h, what)                                                                                                       \
+    do {                                                                                                                                 \
+        if ((h) && (h)->engine == 4) {                                                                                                   \
+            (h)->err = std::string("TrackedNeuralODE tiled engine: ") + what;                                                            \
+            return RNDE_ERR_BAD_ARG;                                                                                                     \
+        }                                                                                                                                \
     } while (0)
 
 static const rnde_status RNDE_INTERNAL_RETRY = static_cast<rnde_status>(100);

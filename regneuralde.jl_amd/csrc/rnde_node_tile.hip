@@ -1,0 +1,279 @@
+// rnde_node_tile.hip -- C ABI of the tiled engine of TrackedNeuralODE (include/rnde.h: rnde_node_create_tiled, engine 4): an rnde_node
+// whose solve, reverse sweep and feval are the kernels of rnde_node_tile.h / rnde_bnode_tile.h.  The public rnde_node_* entries (rnde.hip,
+// rnde_reverse.hip) hand a handle of this engine to the node_tiled_* functions below, or refuse it by name.
+#include "rnde_node.h"
+#include "rnde_bnode_tile.h"
+
+struct rnde_node_tiled {
+    FcGeo G{};
+    int Bp = 0, ntiles_max = 0;
+    size_t lds_bytes = 0;
+    float *ws = nullptr, *tape = nullptr, *norm = nullptr, *replay = nullptr, *rws = nullptr, *pacc = nullptr, *pcopy = nullptr;
+    StepState* ctl = nullptr;        // [3]: the two live states, then the final one
+    StepState* ctl_t = nullptr;      // [ntiles]
+    StepMeta* meta = nullptr;        // [max_attempts]
+    InitRec* initrec_t = nullptr;    // [ntiles]
+    NtStepRec* rec = nullptr;        // [max_attempts]
+    MeetRes meet;
+    // the taped forward, kept apart from the last solve (an untaped probe between a taped forward and its backward leaves it alone)
+    std::vector<StepMeta> tp_meta;
+    int tp_n_att = 0, tp_n_acc = 0, tp_B = 0;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool ev_fwd = false, ev_bwd = false;
+};
+
+
+static FcGeo nt_geo(const rnde_node_config* c) { return fc_geo(c->n_layers, c->dims, c->act, c->time_dep); }
+static bool nt_shape_ok(const rnde_node_config* c) {
+    if (!c || c->n_layers < 1 || c->n_layers > RNDE_MAX_LAYERS) return false;
+    for (int l = 0; l <= c->n_layers; ++l) if (c->dims[l] < 1 || c->dims[l] > 65536) return false;
+    return true;
+}
+
+extern "C" int64_t rnde_node_tiled_lds_bytes(const rnde_node_config* c) {
+    if (!nt_shape_ok(c)) return -1;
+    int64_t w = 0, y = 0, mp = 0;      // (in 64 bits: a shape far beyond the limit must not wrap into it)
+    auto pad = [](int64_t n) { return (n + 15) / 16 * 16; };
+    for (int l = 0; l <= c->n_layers; ++l) mp = std::max(mp, pad(c->dims[l]));
+    for (int l = 0; l < c->n_layers; ++l) { w += pad(c->dims[l]) * (pad(c->dims[l + 1]) + 1) + 2 * pad(c->dims[l + 1]); y += pad(c->dims[l + 1]) * 16; }
+    return 4 * ((w + 3) / 4 * 4 + pad(c->dims[0]) * 16 + y + 2 * mp * 16 + 128);
+}
+
+// What the tiled engine serves; a message that names the limit or the alternative otherwise (no device needed).
+static const char* nt_refusal(const rnde_node_config* c) {
+    static thread_local std::string msg;
+    if (c->n_layers < 1 || c->n_layers > RNDE_MAX_LAYERS) return "TrackedNeuralODE tiled engine: n_layers must be 1..RNDE_MAX_LAYERS (8 Dense layers)";
+    const int n = c->n_layers;
+    for (int l = 0; l <= n; ++l) if (c->dims[l] < 1) return "TrackedNeuralODE tiled engine: every width must be at least 1";
+    if (c->dims[0] != c->dims[n]) return "TrackedNeuralODE tiled engine: dims[0] must equal dims[n_layers] (the dynamics map the state to its own rate)";
+    for (int l = 0; l < n; ++l)
+        if (c->act[l] < RNDE_ACT_IDENTITY || c->act[l] > RNDE_ACT_ELU)
+            return "TrackedNeuralODE tiled engine: an activation code outside rnde_act (identity, tanh, relu, sigmoid, softplus, elu) is not served";
+    if (c->solver != RNDE_SOLVER_TSIT5) return "TrackedNeuralODE tiled engine: only Tsit5 is served (DP5 / DOP853 run on the chain engine, rnde_node_create, widths <= 64)";
+    if (c->regularize >= RNDE_REG_STIFF && c->regularize <= RNDE_REG_STIFF_DT)
+        return "TrackedNeuralODE tiled engine: the stiffness callbacks (RNDE_REG_STIFF, RNDE_REG_ERR_STIFF, RNDE_REG_STIFF_DT) are not served; "
+               "regularize is RNDE_REG_NONE or RNDE_REG_ERR (EEst * dt per accepted step)";
+    if (c->regularize != RNDE_REG_NONE && c->regularize != RNDE_REG_ERR) return "TrackedNeuralODE tiled engine: regularize: unknown value";
+    if (c->pre_act != RNDE_PRE_NONE) return "TrackedNeuralODE tiled engine: pre_act must be RNDE_PRE_NONE (a leading tanh or cube runs on the chain engine, rnde_node_create)";
+    if (c->col_tile != 0) return "TrackedNeuralODE tiled engine: col_tile must be 0 (the engine has one layout: four waves per 16 columns)";
+    if (c->track_ctrl != 0 || c->track_initdt != 0)
+        return "TrackedNeuralODE tiled engine: track_ctrl = 1 and track_initdt = 1 are not served: the reverse sweep treats step sizes and times as "
+               "constants (set track_ctrl = 0 and track_initdt = 0; rnde_node_create differentiates the controller and the initial step)";
+    if (c->max_batch < 1 || c->max_attempts < 1 || !(c->reltol > 0.f) || !(c->abstol > 0.f)) return "TrackedNeuralODE tiled engine: bad max_batch / max_attempts / tolerances";
+    if (c->max_batch > 16 * kMwMeetMax)
+        return "TrackedNeuralODE tiled engine: max_batch above 4096 is not served (one meeting holds kMwMeetMax = 256 resident tiles of 16 columns)";
+    if (c->max_attempts > kFtMaxAttempts) return "TrackedNeuralODE tiled engine: max_attempts above 8000 is not served (meeting tags)";
+    const int64_t need = rnde_node_tiled_lds_bytes(c);
+    if (need < 0 || need > (int64_t)kFtLdsBytes) {
+        msg = "TrackedNeuralODE tiled engine: the resident weights and the activations of a tile need " + std::to_string((long long)need) +
+              " bytes of LDS, above the limit of " + std::to_string(kFtLdsBytes) + " bytes (160 KB; solve and reverse sweep use the same layout)";
+        return msg.c_str();
+    }
+    return nullptr;
+}
+
+void node_tiled_destroy(rnde_node* h) {
+    rnde_node_tiled* T = h->tiled;
+    if (!T) return;
+    for (void* p : {(void*)T->ws, (void*)T->tape, (void*)T->norm, (void*)T->replay, (void*)T->rws, (void*)T->pacc, (void*)T->pcopy, (void*)T->ctl,
+                    (void*)T->ctl_t, (void*)T->meta, (void*)T->initrec_t, (void*)T->rec})
+        if (p) (void)hipFree(p);
+    T->meet.destroy();
+    for (auto& v : T->ev) if (v) (void)hipEventDestroy(v);
+    delete T;
+    h->tiled = nullptr;
+}
+
+extern "C" rnde_status rnde_node_create_tiled(const rnde_node_config* c, rnde_node** out) {
+    if (!c || !out) { rnde_set_create_error("null argument"); return RNDE_ERR_BAD_ARG; }
+    *out = nullptr;
+    if (const char* why = nt_refusal(c)) { rnde_set_create_error(why); return RNDE_ERR_BAD_ARG; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= c->device) { rnde_set_create_error("no HIP device"); return RNDE_ERR_NO_DEVICE; }
+    if (hipSetDevice(c->device) != hipSuccess) { rnde_set_create_error("hipSetDevice failed"); return RNDE_ERR_NO_DEVICE; }
+    rnde_node* h = new rnde_node();
+    rnde_node_tiled* T = new rnde_node_tiled();
+    h->tiled = T;
+    h->cfg = *c; h->engine = 4;
+    T->G = nt_geo(c);
+    h->D = c->dims[0]; h->H = 0; h->P = T->G.P; h->BT = 16;
+    T->ntiles_max = (c->max_batch + 15) / 16;
+    T->Bp = 16 * T->ntiles_max;
+    h->Bpad_max = T->Bp; h->nwg_max = T->ntiles_max;
+    T->lds_bytes = (size_t)NtDyn::lds_floats(T->G) * 4;
+    if ((int64_t)T->lds_bytes != rnde_node_tiled_lds_bytes(c)) { rnde_set_create_error("internal: LDS byte counts disagree"); rnde_node_destroy(h); return RNDE_ERR_BAD_ARG; }
+    auto fail = [&](hipError_t e) { rnde_set_create_error(std::string("HIP: ") + hipGetErrorString(e)); rnde_node_destroy(h); return RNDE_ERR_HIP; };
+    hipError_t e;
+    const int D = h->D;
+    const size_t RB = (size_t)D * T->Bp, MA = (size_t)c->max_attempts, NT = (size_t)T->ntiles_max;
+    if ((e = hipMalloc(&T->ws, 10 * RB * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&T->tape, (MA + 1) * RB * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&T->norm, (8 * NT + 512) * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMemset(T->norm, 0, (8 * NT + 512) * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&T->replay, 2 * MA * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&T->rws, NT * NtDyn::rev_ws_floats(T->G) * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&T->pacc, NT * T->G.P * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&T->pcopy, (size_t)T->G.P * 4)) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&T->ctl, 3 * sizeof(StepState))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&T->ctl_t, NT * sizeof(StepState))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&T->meta, MA * sizeof(StepMeta))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&T->initrec_t, NT * sizeof(InitRec))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&T->rec, MA * sizeof(NtStepRec))) != hipSuccess) return fail(e);
+    if ((e = hipHostMalloc((void**)&h->h_meta, MA * sizeof(StepMeta))) != hipSuccess) return fail(e);
+    if ((e = T->meet.create(MA + 4, 3, kMwMeetMax)) != hipSuccess) return fail(e);
+    for (const void* k : {(const void*)rnde_node_tile_solve_kernel, (const void*)rnde_node_tile_reverse_kernel, (const void*)rnde_node_tile_feval_kernel})
+        if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)T->lds_bytes)) != hipSuccess) return fail(e);
+    if (T->ntiles_max > kMeetXcdCus) {      // the agent-scope meeting: every tile of the largest batch must be resident at once
+        int per_cu = 0;
+        hipDeviceProp_t prop;
+        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rnde_node_tile_solve_kernel, kFtThreads, T->lds_bytes)) != hipSuccess) return fail(e);
+        if ((e = hipGetDeviceProperties(&prop, c->device)) != hipSuccess) return fail(e);
+        if ((long long)per_cu * prop.multiProcessorCount < T->ntiles_max) {
+            rnde_set_create_error("TrackedNeuralODE tiled engine: max_batch needs " + std::to_string(T->ntiles_max) + " resident tiles for the meeting, the device holds " +
+                              std::to_string((long long)per_cu * prop.multiProcessorCount) + " workgroups of this LDS footprint");
+            rnde_node_destroy(h);
+            return RNDE_ERR_BAD_ARG;
+        }
+    }
+    for (auto& v : T->ev) if ((e = hipEventCreate(&v)) != hipSuccess) return fail(e);
+    *out = h;
+    return RNDE_OK;
+}
+
+rnde_status node_tiled_forward(rnde_node* h, const float* x_dev, const float* p_dev, int32_t B, float t0, float t1, float* u_out_dev,
+                               const float* saveat_host, int32_t n_saveat, float* sv_out_dev, int64_t* nfe_out, float* saveval_host,
+                               int32_t* n_saveval_out, int32_t keep_tape, void* stream) {
+    rnde_node_tiled* T = h->tiled;
+    hipStream_t s = (hipStream_t)stream;
+    if (saveat_host || n_saveat > 0 || sv_out_dev) {
+        h->err = "TrackedNeuralODE tiled engine: rnde_node_forward_saveat is not served (the end state only; saveat runs on the engines of rnde_node_create)";
+        return RNDE_ERR_BAD_ARG;
+    }
+    if (!x_dev || !p_dev || B < 1 || B > h->cfg.max_batch) { h->err = "bad argument (B must be 1..max_batch)"; return RNDE_ERR_BAD_ARG; }
+    if (!(t1 > t0)) { h->err = "bad B or tspan"; return RNDE_ERR_BAD_ARG; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const float* steps_host = h->replay_host;
+    const int n_steps = h->n_replay;
+    const bool taped = keep_tape != 0;
+    if (taped) {
+        h->have_tape = false;
+        HIPCHK(h, hipMemcpyAsync(T->pcopy, p_dev, (size_t)h->P * 4, hipMemcpyDeviceToDevice, s));      // (the tape keeps no caller pointer)
+    }
+    if (steps_host) HIPCHK(h, hipMemcpyAsync(T->replay, steps_host, (size_t)2 * n_steps * 4, hipMemcpyHostToDevice, s));
+    NodeTileSolveParams Q{};
+    StepParams& P = Q.F;
+    P.x = x_dev; P.D = h->D; P.B = B; P.Bn = B; P.Bpad = T->Bp; P.nwg = 1;
+    P.ctl = T->ctl; P.ctl_final = T->ctl + 2; P.meta = T->meta; P.initrec = T->initrec_t; P.initpart = T->norm;
+    P.reltol = h->cfg.reltol; P.abstol = h->cfg.abstol; P.t0 = t0; P.t1 = t1;
+    P.tape = 1; P.max_attempts = h->cfg.max_attempts; P.reg_kind = 0; P.nsave = 0;
+    P.replay = steps_host ? T->replay : nullptr; P.n_replay = steps_host ? n_steps : 0;
+    P.beta1 = kBeta1; P.beta2 = kBeta2; P.rk_order = 5.f;
+    const int nt = (B + 15) / 16;
+    const Meet meet = T->meet.begin(nt, true, s);      // every tile resident, one meeting per attempt (one XCD up to 32 tiles, agent scope above)
+    HIPCHK(h, T->meet.err);
+    Q.G = T->G; Q.p = p_dev; Q.x = x_dev; Q.ws = T->ws; Q.tape = taped ? T->tape : nullptr; Q.u_out = u_out_dev; Q.norm = T->norm;
+    Q.initrec_t = T->initrec_t; Q.ctl_t = T->ctl_t; Q.meet = meet; Q.xcc = T->meet.xcc; Q.xcd_slot = T->meet.slot; Q.Bp = T->Bp;
+    HIPCHK(h, hipEventRecord(T->ev[0], s));
+    hipLaunchKernelGGL(rnde_node_tile_solve_kernel, dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(T->ev[1], s));
+    T->ev_fwd = true;
+    StepState fin;
+    HIPCHK(h, hipMemcpyAsync(&fin, T->ctl + 2, sizeof(StepState), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, T->meet.queue_check(meet, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    const bool split = meet_split(T->meet.chk, nt, meet.global != 0);
+    if (meet_verdict(T->meet.chk, nt, meet.global != 0) != MEET_OK) {      // no fall-back to other arithmetic: the call fails and says why
+        HIPCHK(h, T->meet.clear_abort(s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        h->n_att = 0;
+        h->err = split ? "TrackedNeuralODE tiled engine: a workgroup meeting of the solve timed out (the tiles pinned to one XCD by block index landed on "
+                         "different XCDs); the solve was abandoned"
+                       : "TrackedNeuralODE tiled engine: a workgroup meeting of the solve timed out (not every tile was resident); the solve was abandoned";
+        return RNDE_ERR_HIP;
+    }
+    h->n_att = fin.n_att; h->B = B; h->Bpad = T->Bp; h->t0 = t0; h->t1 = t1;
+    if (fin.n_att) HIPCHK(h, hipMemcpy(h->h_meta, T->meta, (size_t)fin.n_att * sizeof(StepMeta), hipMemcpyDeviceToHost));
+    switch (fin.status) {
+        case 0: break;
+        case 2: h->err = "max_attempts reached"; return RNDE_ERR_MAX_ATTEMPTS;
+        case 3: h->err = "dt underflow"; return RNDE_ERR_DT_UNDERFLOW;
+        default: h->err = "non-finite error estimate or dt"; return RNDE_ERR_NONFINITE;
+    }
+    if (nfe_out) *nfe_out = 3 + 6 * (int64_t)fin.n_att;      // 2 (initial dt) + 1 (fsalfirst) + 6 per attempt
+    int nsv = 0;
+    if (h->cfg.regularize == RNDE_REG_ERR) {       // SavingCallback(EEst * dt): 0 at init when it fires there, then one per accepted step
+        if (h->cfg.cb_save_start) { if (saveval_host) saveval_host[nsv] = 0.f; ++nsv; }
+        for (int i = 0; i < fin.n_att; ++i)
+            if (h->h_meta[i].flags & F_ACCEPT) { if (saveval_host) saveval_host[nsv] = h->h_meta[i].eest * h->h_meta[i].dt; ++nsv; }
+    }
+    h->n_saveval = nsv;
+    if (n_saveval_out) *n_saveval_out = nsv;
+    if (taped) {
+        T->tp_meta.assign(h->h_meta, h->h_meta + fin.n_att);
+        T->tp_n_att = fin.n_att; T->tp_n_acc = fin.n_acc; T->tp_B = B;
+        h->have_tape = true;
+    }
+    return RNDE_OK;
+}
+
+rnde_status node_tiled_backward(rnde_node* h, const float* u_bar_dev, const float* saveval_bar_host, float* x_bar_dev, float* p_bar_dev,
+                                float* tspan_bar_host, void* stream) {
+    rnde_node_tiled* T = h->tiled;
+    if (!u_bar_dev || !p_bar_dev) { h->err = "u_bar_dev and p_bar_dev are required"; return RNDE_ERR_BAD_ARG; }
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const bool reg = h->cfg.regularize == RNDE_REG_ERR;
+    std::vector<NtStepRec> rec;
+    rec.reserve(T->tp_n_acc);
+    int k = (reg && h->cfg.cb_save_start) ? 1 : 0;       // (the value saved at init is a constant)
+    for (int i = 0; i < T->tp_n_att; ++i) {
+        const StepMeta& m = T->tp_meta[i];
+        if (!(m.flags & F_ACCEPT)) continue;
+        NtStepRec r{m.t, m.dt, m.eest, 0.f};
+        if (reg && saveval_bar_host) r.svb = saveval_bar_host[k];
+        ++k;
+        rec.push_back(r);
+    }
+    if ((int)rec.size() != T->tp_n_acc) { h->err = "internal: accepted-step count mismatch"; return RNDE_ERR_BAD_ARG; }
+    if (!rec.empty()) HIPCHK(h, hipMemcpyAsync(T->rec, rec.data(), rec.size() * sizeof(NtStepRec), hipMemcpyHostToDevice, s));
+    NodeTileRevParams Q{};
+    Q.G = T->G; Q.p = T->pcopy; Q.tape = T->tape; Q.rec = T->rec; Q.u_bar = u_bar_dev; Q.ws = T->rws; Q.pacc = T->pacc; Q.x_bar = x_bar_dev;
+    Q.n_acc = T->tp_n_acc; Q.B = T->tp_B; Q.Bp = T->Bp; Q.reltol = h->cfg.reltol; Q.abstol = h->cfg.abstol;
+    const int nt = (T->tp_B + 15) / 16;
+    HIPCHK(h, hipEventRecord(T->ev[2], s));
+    hipLaunchKernelGGL(rnde_node_tile_reverse_kernel, dim3(nt), dim3(kFtThreads), T->lds_bytes, s, Q);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(T->ev[3], s));
+    hipLaunchKernelGGL(rnde_node_tile_reduce_kernel, dim3((h->P + 255) / 256), dim3(256), 0, s, (const float*)T->pacc, h->P, nt, p_bar_dev);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(T->ev[4], s));
+    T->ev_bwd = true;
+    HIPCHK(h, hipStreamSynchronize(s));      // (rec is a host vector: the copy must have left it)
+    if (tspan_bar_host) { tspan_bar_host[0] = 0.f; tspan_bar_host[1] = 0.f; }      // step sizes and times are constants of this sweep
+    return RNDE_OK;
+}
+
+rnde_status node_tiled_feval(rnde_node* h, const float* u_dev, const float* p_dev, int32_t B, float t, float* out_dev, void* stream) {
+    rnde_node_tiled* T = h->tiled;
+    if (!u_dev || !p_dev || !out_dev) { h->err = "bad argument"; return RNDE_ERR_BAD_ARG; }
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(rnde_node_tile_feval_kernel, dim3((B + 15) / 16), dim3(kFtThreads), T->lds_bytes, s, T->G, p_dev, u_dev, t, B, T->rws, out_dev);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(s));
+    return RNDE_OK;
+}
+
+rnde_status node_tiled_timing(rnde_node* h, float* fwd_ms, float* rev_sweep_ms, float* rev_rest_ms) {
+    rnde_node_tiled* T = h->tiled;
+    float a = -1.f, b = -1.f, c = -1.f;
+    if (T->ev_fwd) { HIPCHK(h, hipEventSynchronize(T->ev[1])); HIPCHK(h, hipEventElapsedTime(&a, T->ev[0], T->ev[1])); }
+    if (T->ev_bwd) {
+        HIPCHK(h, hipEventSynchronize(T->ev[4]));
+        HIPCHK(h, hipEventElapsedTime(&b, T->ev[2], T->ev[3])); HIPCHK(h, hipEventElapsedTime(&c, T->ev[3], T->ev[4]));
+    }
+    if (fwd_ms) *fwd_ms = a;
+    if (rev_sweep_ms) *rev_sweep_ms = b;
+    if (rev_rest_ms) *rev_rest_ms = c;
+    return RNDE_OK;
+}

@@ -12,6 +12,7 @@ static rnde_status bwd_run(rnde_node* h, const float* u_bar_dev, const float* sa
 extern "C" rnde_status rnde_node_backward_async(rnde_node* h, const float* u_bar_dev, const float* saveval_bar_host, float* x_bar_dev,
                                                 float* p_bar_dev, float* tspan_bar_dev, void* stream) {
     if (!h) return RNDE_ERR_BAD_ARG;
+    RNDE_TILED_REFUSE(h, "rnde_node_backward_async is not served (rnde_node_backward runs its reverse sweep and waits for it)");
     if (!h->have_tape) { h->err = "no recorded forward"; return RNDE_ERR_NO_TAPE; }
     if (h->engine == 3) return chain_bwd_run(h, u_bar_dev, saveval_bar_host, x_bar_dev, p_bar_dev, nullptr, (hipStream_t)stream, false, tspan_bar_dev);
     return bwd_run(h, u_bar_dev, saveval_bar_host, x_bar_dev, p_bar_dev, nullptr, (hipStream_t)stream, false, tspan_bar_dev);
@@ -21,6 +22,7 @@ extern "C" rnde_status rnde_node_backward(rnde_node* h, const float* u_bar_dev, 
                                           float* x_bar_dev, float* p_bar_dev, float* tspan_bar_host, void* stream) {
     if (!h) return RNDE_ERR_BAD_ARG;
     if (!h->have_tape) { h->err = "no recorded forward"; return RNDE_ERR_NO_TAPE; }
+    if (h->engine == 4) return node_tiled_backward(h, u_bar_dev, saveval_bar_host, x_bar_dev, p_bar_dev, tspan_bar_host, stream);
     if (h->engine == 3) return chain_bwd_run(h, u_bar_dev, saveval_bar_host, x_bar_dev, p_bar_dev, tspan_bar_host, (hipStream_t)stream);
     return bwd_run(h, u_bar_dev, saveval_bar_host, x_bar_dev, p_bar_dev, tspan_bar_host, (hipStream_t)stream);
 }
@@ -519,6 +521,7 @@ extern "C" rnde_status rnde_node_classifier_grad(rnde_node* h, const float* x_de
                                                  float* ce_out_dev, float* reg_out_host, int64_t* nfe_out, rnde_comm* comm,
                                                  void* stream) {
     if (!h || !x_dev || !p2_dev || !p3_dev || !y_dev || !p2_bar_dev || !p3_bar_dev || !ce_out_dev) return RNDE_ERR_BAD_ARG;
+    RNDE_TILED_REFUSE(h, "rnde_node_classifier_grad is not served (the fused training step runs on the stage engine: two-layer dynamics, rnde_node_create with col_tile 0)");
     if (h->engine != 2) { h->err = "rnde_node_classifier_grad: two-layer dynamics on the stage engine (col_tile 0)"; return RNDE_ERR_BAD_ARG; }
     if (B < 1 || B > h->cfg.max_batch) { h->err = "bad B or tspan"; return RNDE_ERR_BAD_ARG; }
     HIPCHK(h, hipSetDevice(h->cfg.device));

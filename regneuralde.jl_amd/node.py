@@ -15,6 +15,10 @@ computes the value inside its kernels -- or that callback's name ('error_est' / 
 Differences from the Julia layer that are inherent to the host language:
 `save_everystep=True` (a result whose length is data dependent; no reference call site uses it): `rnde_node_forward_everystep`, the state
 after every accepted step (and the initial one with save_start=True), (B, n, D) with n known after the call.
+
+`engine="tiled"` (opt-in; `rnde_node_create_tiled`) serves Dense chains wider than 64 whose padded weights fit LDS (`tiled_lds_bytes(dims)` <=
+160 KB): end state only, Tsit5, EEst*dt or no callback.  Its gradient treats step sizes and times as constants, so the layer must be built with
+`track_ctrl=False, track_initdt=False`; `check_tiled_served` raises a ValueError that names the limit for everything else it does not serve.
 """
 import ctypes as C
 
@@ -74,10 +78,57 @@ class SavedValues:
         self.saveval = saveval
 
 
+ENGINES = (None, "tiled")      # None: rnde_node_create's own routing (stage engine / chain engine); "tiled": rnde_node_create_tiled
+TILED_LDS_BYTES = 160 * 1024
+TILED_MAX_BATCH, TILED_MAX_ATTEMPTS = 4096, 8000
+
+
+def tiled_lds_bytes(dims):
+    """LDS bytes of a tile of the tiled engine (rnde_node_tiled_lds_bytes; rnde_node_tile.h::NtDyn::lds_floats): padded weights with the t column
+    and bias vectors, the input, every layer's output, two VJP vectors, reduction scratch.  The solve and the reverse sweep share the layout."""
+    pad = lambda n: (n + 15) // 16 * 16
+    n = len(dims) - 1
+    w = sum(pad(dims[l]) * (pad(dims[l + 1]) + 1) + 2 * pad(dims[l + 1]) for l in range(n))
+    mp = max(pad(d) for d in dims)
+    return 4 * ((w + 3) // 4 * 4 + pad(dims[0]) * 16 + sum(pad(dims[l + 1]) * 16 for l in range(n)) + 2 * mp * 16 + 128)
+
+
+def check_tiled_served(layer):
+    """ValueError naming the limit or the alternative for what engine="tiled" does not serve (include/rnde.h: rnde_node_create_tiled)."""
+    if layer.track_ctrl is not False or layer.track_initdt is not False:
+        raise ValueError('TrackedNeuralODE(engine="tiled"): the reverse sweep of the tiled engine treats step sizes and times as constants; pass '
+                         "track_ctrl=False and track_initdt=False to ask for that gradient (the defaults, True, differentiate the controller and the "
+                         "initial step, which only the default engines do)")
+    if layer.solver != "Tsit5":
+        raise ValueError(f'TrackedNeuralODE(engine="tiled"): solver must be "Tsit5"; got {layer.solver!r} (AutoTsit5, DP5 and DOP853 run on the default engines)')
+    if "saveat" in layer.kwargs or layer.kwargs.get("save_everystep", False):
+        raise ValueError('TrackedNeuralODE(engine="tiled"): saveat= and save_everystep=True are not served (the end state only); use the default engine')
+    if getattr(layer.model, "pre_act", False):
+        raise ValueError('TrackedNeuralODE(engine="tiled"): a leading element-wise map (pre_act) is not served; use the default engine')
+    if layer.col_tile != 0:
+        raise ValueError('TrackedNeuralODE(engine="tiled"): col_tile must be 0')
+    if layer.matrix_mode not in (None, 0):
+        raise ValueError('TrackedNeuralODE(engine="tiled"): matrix_mode 1 (bf16x3) is not served; its layer products are the fp32-input MFMA')
+    dims = layer.model.dims()
+    if not 1 <= len(dims) - 1 <= _lib.MAX_LAYERS:
+        raise ValueError(f'TrackedNeuralODE(engine="tiled"): 1..{_lib.MAX_LAYERS} Dense layers; got {len(dims) - 1}')
+    if dims[0] != dims[-1]:
+        raise ValueError('TrackedNeuralODE(engine="tiled"): the chain must map the state to its own width (dims[0] == dims[-1])')
+    if layer.max_batch > TILED_MAX_BATCH:
+        raise ValueError(f'TrackedNeuralODE(engine="tiled"): max_batch above {TILED_MAX_BATCH} is not served (256 resident tiles of 16 columns meet)')
+    if layer.max_attempts > TILED_MAX_ATTEMPTS:
+        raise ValueError(f'TrackedNeuralODE(engine="tiled"): max_attempts above {TILED_MAX_ATTEMPTS} is not served (meeting tags)')
+    need = tiled_lds_bytes(dims)
+    if need > TILED_LDS_BYTES:
+        raise ValueError(f'TrackedNeuralODE(engine="tiled"): the resident weights and the activations of a tile need {need} bytes of LDS, above the '
+                         f"limit of {TILED_LDS_BYTES} bytes")
+
+
 class _Handle:
-    def __init__(self, cfg):
+    def __init__(self, cfg, engine=None):
         self.ptr = C.c_void_p()
-        st = _lib.lib().rnde_node_create(C.byref(cfg), C.byref(self.ptr))
+        create = _lib.lib().rnde_node_create_tiled if engine == "tiled" else _lib.lib().rnde_node_create
+        st = create(C.byref(cfg), C.byref(self.ptr))
         _lib.check(None, st)
         self.busy = False
 
@@ -190,7 +241,10 @@ class TrackedNeuralODE:
     """Mirror of reference src/models/neural_ode.jl:1-33 (struct + constructor) and :48-180 (call methods)."""
 
     def __init__(self, model, tspan, time_dep, regularize, solver="Tsit5", *, max_batch=512, max_attempts=128,
-                 cb_save_start=True, track_ctrl=True, track_initdt=True, col_tile=0, matrix_mode=None, **kwargs):
+                 cb_save_start=True, track_ctrl=True, track_initdt=True, col_tile=0, matrix_mode=None, engine=None, **kwargs):
+        if engine not in ENGINES:
+            raise ValueError(f"engine must be one of {ENGINES}; got {engine!r}")
+        self.engine = engine
         if solver not in ("Tsit5", "AutoTsit5", "DP5", "DOP853"):
             raise ValueError("solver: the reference's call sites use Tsit5() / AutoTsit5(Tsit5()) only; DP5 (a second 7-stage pair) and DOP853 "
                              "(a 13-stage table) run on the tableau-as-data kernels (Dense chains of width <= 64)")
@@ -213,6 +267,8 @@ class TrackedNeuralODE:
         # (bf16x3 on the matrix cores where the kernels serve the shape, RNDE_X3 overrides), 0 = fp32-input MFMA, 1 = bf16x3
         self.matrix_mode = matrix_mode
         self.P = self.p.numel()
+        if engine == "tiled":      # (opt-in: Dense chains wider than 64 on the tile layout; refusals need no device)
+            check_tiled_served(self)
         self._handles = {}
         self._coupling = None
         self.last_nfe = None
@@ -252,7 +308,7 @@ class TrackedNeuralODE:
         if len(hs) >= MAX_HANDLES_PER_KEY:
             raise RuntimeError(f"{len(hs)} taped forwards of this layer are pending without a backward pass; each owns a tape of "
                                "max_attempts records.  Run them under torch.no_grad() (NFE probes), call backward, or drop the graphs")
-        h = _Handle(self._config(x.device.index or 0, self._func))
+        h = _Handle(self._config(x.device.index or 0, self._func), self.engine)
         if self.matrix_mode is not None:
             _lib.check(h.ptr, _lib.lib().rnde_node_set_matrix_mode(h.ptr, int(self.matrix_mode)))
         if self._coupling is not None:
@@ -264,6 +320,8 @@ class TrackedNeuralODE:
         """SURVEY 8e mode 2 (include/rnde.h: rnde_node_set_coupling): ONE step-size controller for all shards of a minibatch split by
         columns over `world` layers.  `comm`: an rnde_comm* (ctypes void pointer: `GradientAllReducer.comm` across processes,
         rnde_comm_create_local_group inside one); None switches back to independent controllers.  Every rank must make the same calls."""
+        if self.engine == "tiled":
+            raise ValueError('TrackedNeuralODE(engine="tiled"): set_coupling is not served (one controller over several shards runs on the default engines)')
         self._coupling = None if comm is None else (comm, int(global_batch))
         for hs in self._handles.values():
             for h in hs:
@@ -300,6 +358,8 @@ class TrackedNeuralODE:
             raise ValueError("func must be a callback (u, t, integrator) -> value or one of None/'error_est', 'stiff_est', "
                              "'error_stiff_est' (the three callbacks of experiments/mnist_node.jl:62-103), 'stiff_est_dt' (test/test_node.jl:75)")
         effective_reg(_FUNCS[func], self.solver == "AutoTsit5")      # names and closures alike: a callback that reads eigen_est needs the composite solver
+        if self.engine == "tiled" and _FUNCS[func] > 1:
+            raise ValueError('TrackedNeuralODE(engine="tiled"): the stiffness callbacks are not served; func is None / "error_est" (EEst * dt)')
         return func
 
     # -- call operator ------------------------------------------------------------------------
