@@ -608,6 +608,14 @@ function ffjord_chain_config(dims::Vector{Int}, acts::Vector{Int}; time_dep, reg
 end
 ffjord_chain_param_count(cfg::FfjordChainConfig) = Int(ccall((:rnde_ffjord_chain_param_count, LIB), Int32, (Ref{FfjordChainConfig},), cfg))
 ffjord_engine(h) = Int(ccall((:rnde_ffjord_engine, LIB), Int32, (Ptr{Cvoid},), h.ptr))     # 0: one workgroup, 1: tiled, 2: chain dynamics
+# the tracked-controller reverse sweep (engines 1 and 2, regularize = 1 handles, no tape held): ffjord_backward then differentiates the PI
+# controller as well (track_ctrl = 1, track_initdt = 0); the tape remembers the setting of its forward
+function ffjord_set_track_ctrl(h, on::Bool)
+    st = ccall((:rnde_ffjord_set_track_ctrl, LIB), Cint, (Ptr{Cvoid}, Int32), h.ptr, Int32(on))
+    st == 0 || error("rnde_ffjord_set_track_ctrl status $st: ", _fferr(h.ptr))
+    return on
+end
+ffjord_track_ctrl(h) = Int(ccall((:rnde_ffjord_track_ctrl, LIB), Int32, (Ptr{Cvoid},), h.ptr)) == 1
 ffjord_param_count(cfg::FfjordConfig) = Int(ccall((:rnde_ffjord_param_count, LIB), Int32, (Ref{FfjordConfig},), cfg))
 _fferr(p) = unsafe_string(ccall((:rnde_ffjord_last_error, LIB), Cstring, (Ptr{Cvoid},), p))
 

@@ -704,6 +704,20 @@ rnde_status rnde_ffjord_forward_exact(rnde_ffjord* h, const float* x_dev, const 
 rnde_status rnde_ffjord_forward_exact_replay(rnde_ffjord* h, const float* x_dev, const float* p_dev, int32_t B, float t0, float t1,
                                              const float* steps_host, int32_t n_steps, float* logpx_dev, float* z_out_dev, int64_t* nfe_out,
                                              float* saveval_host, int32_t* n_saveval_out, int32_t keep_tape, void* stream);
+/* The tracked-controller reverse sweep (opt-in; the default, 0, is the constant-step sweep above, bit for bit).  The reference's Tracker tape
+ * runs through the solver's scalar arithmetic, so the saved value EEst * dt of TrackedFFJORD{true} depends on the parameters through dt as
+ * well as through EEst; with on = 1, rnde_ffjord_backward differentiates the PI controller too (track_ctrl = 1, track_initdt = 0 in
+ * rnde_node_config's terms: the initial step stays a constant, and no tspan cotangent is returned).  The sweep then walks every attempt,
+ * rejected ones included, and the tiles meet once per attempt for the three sums of the dt cotangent (bounded, placed as the solve's
+ * meetings; a meeting that times out fails the backward call with RNDE_ERR_HIP and a message naming it, nothing falls back).
+ * Deterministic.  The tape remembers the setting of its forward, Hutchinson and exact-trace tapes alike; a tracked replay tape is
+ * differentiated as if the controller had produced the sequence (the convention of rnde_node_forward_replay).
+ * RNDE_ERR_BAD_ARG with a message that names the reason: a handle of rnde_ffjord_create (engine 0; the message points at the tiled engine);
+ * a regularize = 0 handle (without a saved value the two sweeps agree to O(tol): 2e-10 to 2e-6 relative against the fp64 oracle; this keeps
+ * the kinetic tapes out as well); a handle that holds a tape; max_batch above what the device keeps resident on the tracked kernel's
+ * footprint (checked when tracking is first switched on). */
+rnde_status rnde_ffjord_set_track_ctrl(rnde_ffjord* h, int32_t on);
+int32_t     rnde_ffjord_track_ctrl(const rnde_ffjord* h);      /* the setting; -1 for NULL */
 
 #ifdef __cplusplus
 }

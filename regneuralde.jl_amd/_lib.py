@@ -205,6 +205,9 @@ def lib():
     L.rnde_ffjord_create_chain.argtypes = [C.POINTER(FfjordChainConfig), C.POINTER(vp)]
     L.rnde_ffjord_forward_exact.argtypes = [vp, vp, vp, i32, f, f, vp, vp, i64p, fp, i32p, i32, vp]
     L.rnde_ffjord_forward_exact_replay.argtypes = [vp, vp, vp, i32, f, f, fp, i32, vp, vp, i64p, fp, i32p, i32, vp]
+    L.rnde_ffjord_set_track_ctrl.argtypes = [vp, i32]
+    L.rnde_ffjord_track_ctrl.restype = i32
+    L.rnde_ffjord_track_ctrl.argtypes = [vp]
     _lib = L
     return L
 
@@ -223,6 +226,7 @@ EXPORTS = ["rnde_version", "rnde_last_error", "rnde_param_count", "rnde_node_cre
            "rnde_ffjord_timing", "rnde_ffjord_create_tiled", "rnde_ffjord_engine", "rnde_ffjord_forward_kinetic",
            "rnde_ffjord_forward_kinetic_replay", "rnde_ffjord_backward_kinetic", "rnde_ffjord_debug_feval_kinetic", "rnde_ffjord_step_log",
            "rnde_ffjord_chain_param_count", "rnde_ffjord_create_chain", "rnde_ffjord_forward_exact", "rnde_ffjord_forward_exact_replay",
+           "rnde_ffjord_set_track_ctrl", "rnde_ffjord_track_ctrl",
            "rnde_node_create_tiled", "rnde_node_tiled_lds_bytes"]
 
 

@@ -27,8 +27,10 @@ __host__ __device__ inline size_t FcDyn::rev_ws_floats(const FcGeo& G, bool kin)
 
 // yb[0:D] += (dF/dz)' lam and pacc += (dF/dp)' lam for the tile's 16 columns.  z: the stage input ([R][16]), kb: its cotangent lam
 // ([R][16]), yb: [R][16], V: the tile's vector slots.  Ends behind a barrier.
+// Returns this thread's share of <dF/dt, lam> summed over the tile's columns (the tracked sweep's time cotangent): a_l = W_l y + wt_l t + b_l,
+// so it is sum_l <wt_l, a_l-bar summed over the columns>, first- and second-order parts alike; zero for a plain Chain.
 template <bool KIN>
-__device__ __forceinline__ void FcDyn::vjp(const FcGeo& G, const FcLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid) {
+__device__ __forceinline__ float FcDyn::vjp(const FcGeo& G, const FcLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid) {
     const int lane = tid & 63, wave = tid >> 6, c = lane & 15, D = G.D, n = G.n, DP = G.DP;
     const size_t FS = (size_t)G.MP * 16;
     // slots: Y_0..Y_n | v_1..v_n | m_1..m_{n-1} (slot n unused) | m_0-bar (= w) .. m_{n-1}-bar | q_1..q_n (d_l-bar .* phi_l'') | a-bar x 2 | lf
@@ -111,6 +113,7 @@ __device__ __forceinline__ void FcDyn::vjp(const FcGeo& G, const FcLds& L, float
     }
     // the primal walk: a_n-bar = lf .* d_n + q_n, then layer by layer down to z-bar
     float *ab = AB0, *abn = AB1;
+    float tsum = 0.f;
     for (int idx = tid; idx < G.outp[n - 1] * 16; idx += kFtThreads) ab[idx] = fmaf(LF[idx], act_dy(G.act[n - 1], Ys(n)[idx]), Qs(n)[idx]);
     __syncthreads();
     for (int l = n; l >= 1; --l) {
@@ -120,7 +123,7 @@ __device__ __forceinline__ void FcDyn::vjp(const FcGeo& G, const FcLds& L, float
         for (int o = tid; o < out; o += kFtThreads) {
             float s = 0.f;
             for (int k = 0; k < 16; ++k) s += ab[o * 16 + k];
-            if (G.td) pl[in * out + o] += t * s;
+            if (G.td) { pl[in * out + o] += t * s; tsum = fmaf(L.W[G.voff[l - 1] + o], s, tsum); }
             pl[(in + G.td) * out + o] += s;
         }
         if (l > 1) {
@@ -139,6 +142,7 @@ __device__ __forceinline__ void FcDyn::vjp(const FcGeo& G, const FcLds& L, float
         __syncthreads();
         float* s = ab; ab = abn; abn = s;
     }
+    return tsum;
 }
 
 }  // namespace rnde

@@ -47,8 +47,10 @@ __device__ __forceinline__ void ft_wgrad(const float* A1, const float* B1, const
 // yb[0:D] += (dF/dz)' lam and pacc += (dF/dp)' lam for the tile's 16 columns, F = [f(z, t); -e . eJ], lam = (lz; ll) = kb.
 // z: the stage input ([R][16]), kb: its cotangent ([R][16]), yb: [R][16], V: the tile's vector slots.  Ends behind a barrier.
 // KIN: F = [f; -e . eJ; sum f^2; sum eJ^2], lam = (lz; ll; l1; l2).
+// Returns this thread's share of <dF/dt, lam> summed over the tile's columns (the tracked sweep's time cotangent): h = p sig(gw t) + bw t + bb,
+// so wherever t X goes to gw-bar, gw X goes to the sum (formed ahead of the product with t: t = 0 occurs), and <bw, bb-bar> with it.
 template <bool KIN>
-__device__ __forceinline__ void FtDyn::vjp(const FtGeo& G, const FtLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid) {
+__device__ __forceinline__ float FtDyn::vjp(const FtGeo& G, const FtLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid) {
     const int lane = tid & 63, wave = tid >> 6, c = lane & 15, D = G.D, H = G.H, HP = G.HP, DP = G.DP;
     const int FP = HP > DP ? HP : DP;
     auto vec = [&](int k) { return V + (size_t)k * FP * 16; };
@@ -196,6 +198,7 @@ __device__ __forceinline__ void FtDyn::vjp(const FtGeo& G, const FtLds& L, float
     ft_wgrad(KIN ? V1 : CV1, KIN ? WV : L.E, Pb1, ZP, G.outp[0], G.inp[0], G.out[0], G.in[0], pacc + G.off[0], wave, lane);
     ft_wgrad(V2, Mb1, Pb2, X1, G.outp[1], G.inp[1], G.out[1], G.in[1], pacc + G.off[1], wave, lane);
     ft_wgrad(V3, Mb2, Pb3, X2, G.outp[2], G.inp[2], G.out[2], G.in[2], pacc + G.off[2], wave, lane);
+    float tsum = 0.f;
     for (int q = tid; q < 2 * H + D; q += kFtThreads) {
         const int l = q < H ? 0 : (q < 2 * H ? 1 : 2), o = q - (l == 0 ? 0 : (l == 1 ? H : 2 * H));
         const float *pb = l == 0 ? Pb1 : (l == 1 ? Pb2 : Pb3), *beta = l == 0 ? Hb1 : (l == 1 ? Hb2 : LZ), *sb = l == 0 ? SB1 : (l == 1 ? SB2 : SB3);
@@ -208,8 +211,10 @@ __device__ __forceinline__ void FtDyn::vjp(const FtGeo& G, const FtLds& L, float
         pv[out + o] += b * t;
         pv[2 * out + o] += b;
         pv[3 * out + o] += s * ff_dsig(gs) * t;
+        tsum = fmaf(ft_vec(G, L.W, l, 3)[o], s * ff_dsig(gs), fmaf(ft_vec(G, L.W, l, 1)[o], b, tsum));
     }
     __syncthreads();
+    return tsum;
 }
 
 // p_bar[q] = sum over tiles of pacc[tile][q], in tile order, carried in double

@@ -44,6 +44,7 @@ struct rnde_ffjord {
         const float* p = nullptr;
         bool kin = false;            // a kinetic forward: D + 3 rows per record
         bool exact = false;          // an exact-trace forward (rnde_ffjord_forward_exact): no probe, the reverse sweep's exact variant
+        bool trk = false;            // the handle's track_ctrl setting at the forward: backward runs the tracked sweep
     } tp;
     bool kin_ready = false;          // ws / tape / rws hold D + 3 rows (grown by the first kinetic call)
     float* e_tape = nullptr;         // the library's probe of a taped forward (e_buf serves untaped calls)
@@ -58,6 +59,8 @@ struct rnde_ffjord {
     StepState* ctl_t = nullptr;      // [ntiles]
     MeetRes meet;                    // the tiles' meeting place (rnde_meet.h)
     FcGeo CG{};                      // engine = 2: the Dense-chain dynamics on the tile layout (cfg holds the shared fields, in_dims = D)
+    bool track_ctrl = false;         // rnde_ffjord_set_track_ctrl: taped forwards are reversed with the controller differentiated
+    FfAttRec* att = nullptr;         // [max_attempts]: the tracked sweep's attempt records (allocated when tracking is first switched on)
 };
 
 #define FCHK(h, x)                                                                                  \
@@ -130,7 +133,8 @@ static rnde_status tile_create(rnde_ffjord* h, const typename Dyn::Geo& G, rnde_
     if ((e = h->meet.create(MA + 4, 3, kMwMeetMax)) != hipSuccess) return fail(e);
     for (const void* k : {(const void*)rnde_ffjord_tile_solve_kernel<Dyn, false>, (const void*)rnde_ffjord_tile_reverse_kernel<Dyn, false>,
                           (const void*)rnde_ffjord_tile_feval_kernel<Dyn, false>, (const void*)rnde_ffjord_tile_solve_kernel<Dyn, true>,
-                          (const void*)rnde_ffjord_tile_reverse_kernel<Dyn, true>, (const void*)rnde_ffjord_tile_feval_kernel<Dyn, true>})
+                          (const void*)rnde_ffjord_tile_reverse_kernel<Dyn, true>, (const void*)rnde_ffjord_tile_feval_kernel<Dyn, true>,
+                          (const void*)rnde_ffjord_tile_reverse_kernel<Dyn, false, true>})
         if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes)) != hipSuccess) return fail(e);
     for (auto& v : h->ev) if ((e = hipEventCreate(&v)) != hipSuccess) return fail(e);
     *out = h;
@@ -165,6 +169,51 @@ extern "C" rnde_status rnde_ffjord_create_tiled(const rnde_ffjord_config* c, rnd
 }
 
 extern "C" int32_t rnde_ffjord_engine(const rnde_ffjord* h) { return h ? h->engine : -1; }
+
+// ---- the tracked-controller reverse sweep (engines 1 and 2, regularize = 1) ----
+// Its meeting needs every tile of the largest batch resident at once, on the tracked kernel's own footprint.
+template <class Dyn>
+static rnde_status trk_residency(rnde_ffjord* h) {
+    int per_cu = 0;
+    hipDeviceProp_t prop;
+    FCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rnde_ffjord_tile_reverse_kernel<Dyn, false, true>, kFtThreads, h->lds_bytes));
+    FCHK(h, hipGetDeviceProperties(&prop, h->cfg.device));
+    const long long room = h->ntiles_max > kMeetXcdCus ? (long long)per_cu * prop.multiProcessorCount : (per_cu > 0 ? kMeetXcdCus : 0);
+    if (room < h->ntiles_max) {
+        h->err = "TrackedFFJORD track_ctrl: max_batch needs " + std::to_string(h->ntiles_max) + " resident tiles for the reverse sweep's meeting, the device holds " +
+                 std::to_string(room) + " workgroups of the tracked sweep's footprint";
+        return RNDE_ERR_BAD_ARG;
+    }
+    return RNDE_OK;
+}
+
+extern "C" rnde_status rnde_ffjord_set_track_ctrl(rnde_ffjord* h, int32_t on) {
+    if (!h) return RNDE_ERR_BAD_ARG;
+    if (on != 0 && on != 1) { h->err = "TrackedFFJORD track_ctrl: the setting is 0 (step sizes and times are constants of the reverse sweep) or 1"; return RNDE_ERR_BAD_ARG; }
+    if (h->engine == 0) {
+        h->err = "TrackedFFJORD track_ctrl: the one-workgroup engine does not differentiate the step controller; create the handle with "
+                 "rnde_ffjord_create_tiled (engine = \"tiled\") or rnde_ffjord_create_chain";
+        return RNDE_ERR_BAD_ARG;
+    }
+    if (!h->cfg.regularize) {
+        h->err = "TrackedFFJORD track_ctrl: a regularize = 0 handle has no saved value EEst * dt, and without one the tracked and the constant-step "
+                 "sweep agree to O(tol) (2e-10 to 2e-6 relative, measured with the fp64 oracle); track_ctrl needs regularize = 1";
+        return RNDE_ERR_BAD_ARG;
+    }
+    if (h->tp.valid) {
+        h->err = "TrackedFFJORD track_ctrl: the handle holds a tape (a taped forward waiting for its backward); the tape remembers the setting of its "
+                 "forward, change it before the forward";
+        return RNDE_ERR_BAD_ARG;
+    }
+    if (on && !h->att) {
+        if (rnde_status st = h->engine == 2 ? trk_residency<FcDyn>(h) : trk_residency<FtDyn>(h)) return st;
+        FCHK(h, hipMalloc(&h->att, (size_t)h->cfg.max_attempts * sizeof(FfAttRec)));
+    }
+    h->track_ctrl = on != 0;
+    return RNDE_OK;
+}
+
+extern "C" int32_t rnde_ffjord_track_ctrl(const rnde_ffjord* h) { return h ? (h->track_ctrl ? 1 : 0) : -1; }
 
 // ---- the Dense-chain dynamics (rnde_ffjord_create_chain) ----
 static bool fc_shape_ok(const rnde_ffjord_chain_config* c) {
@@ -280,7 +329,7 @@ extern "C" rnde_status rnde_ffjord_create(const rnde_ffjord_config* c, rnde_ffjo
 extern "C" void rnde_ffjord_destroy(rnde_ffjord* h) {
     if (!h) return;
     for (void* p : {(void*)h->ws, (void*)h->tape, (void*)h->norm, (void*)h->e_buf, (void*)h->e_tape, (void*)h->replay, (void*)h->rws, (void*)h->pacc,
-                    (void*)h->ctl, (void*)h->meta, (void*)h->initrec, (void*)h->rec, (void*)h->qt, (void*)h->ctl_t})
+                    (void*)h->ctl, (void*)h->meta, (void*)h->initrec, (void*)h->rec, (void*)h->qt, (void*)h->ctl_t, (void*)h->att})
         if (p) (void)hipFree(p);
     h->meet.destroy();
     for (auto& v : h->ev) if (v) (void)hipEventDestroy(v);
@@ -342,13 +391,20 @@ static void tile_launch_solve(rnde_ffjord* h, const typename Dyn::Geo& G, const 
     else hipLaunchKernelGGL((rnde_ffjord_tile_solve_kernel<Dyn, false>), grid, dim3(kFtThreads), h->lds_bytes, s, T);
 }
 
+// meet != NULL: the tracked sweep (Q.rec is unused; n_att attempt records in h->att), placed as the solve is.
 template <class Dyn>
-static void tile_launch_reverse(rnde_ffjord* h, const typename Dyn::Geo& G, const FfRevParams& Q, bool kin, bool exact, hipStream_t s) {
+static void tile_launch_reverse(rnde_ffjord* h, const typename Dyn::Geo& G, const FfRevParams& Q, bool kin, bool exact, hipStream_t s,
+                                const Meet* meet = nullptr, int n_att = 0) {
     TileRevParams<typename Dyn::Geo> T{};
     T.G = G; T.p = Q.p; T.e = Q.e; T.tape = Q.tape; T.rec = Q.rec; T.logpx_bar = Q.logpx_bar; T.ws = Q.ws; T.pacc = Q.pacc;
     T.x_bar = Q.x_bar; T.n_acc = Q.n_acc; T.B = Q.B; T.Bp = Q.Bp; T.reltol = Q.reltol; T.abstol = Q.abstol; T.reg_bar = Q.reg_bar;
     T.exact = exact ? 1 : 0; T.scratch = exact ? h->qt : nullptr;
     const int nt = (Q.B + 15) / 16;
+    if (meet) {
+        T.att = h->att; T.n_att = n_att; T.meet = *meet; T.xcc = h->meet.xcc; T.xcd_slot = h->meet.slot;
+        hipLaunchKernelGGL((rnde_ffjord_tile_reverse_kernel<Dyn, false, true>), dim3(MeetRes::grid(*meet)), dim3(kFtThreads), h->lds_bytes, s, T);
+        return;
+    }
     if (kin) hipLaunchKernelGGL((rnde_ffjord_tile_reverse_kernel<Dyn, true>), dim3(nt), dim3(kFtThreads), h->lds_bytes, s, T);
     else hipLaunchKernelGGL((rnde_ffjord_tile_reverse_kernel<Dyn, false>), dim3(nt), dim3(kFtThreads), h->lds_bytes, s, T);
 }
@@ -438,7 +494,7 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
     if (taped) {
         rnde_ffjord::Tape& T = h->tp;
         T.meta = h->h_meta; T.n_att = h->n_att; T.n_acc = h->n_acc; T.B = B;
-        T.reltol = P.reltol; T.abstol = P.abstol; T.e = exact ? nullptr : e_dev; T.p = p_dev; T.kin = kin; T.exact = exact; T.valid = true;
+        T.reltol = P.reltol; T.abstol = P.abstol; T.e = exact ? nullptr : e_dev; T.p = p_dev; T.kin = kin; T.exact = exact; T.trk = h->track_ctrl; T.valid = true;
     }
     return RNDE_OK;
 }
@@ -562,14 +618,32 @@ static rnde_status ff_backward(rnde_ffjord* h, const float* logpx_bar_dev, const
     }
     if ((int)rec.size() != T.n_acc) { h->err = "internal: accepted-step count mismatch"; return RNDE_ERR_BAD_ARG; }
     if (!rec.empty()) FCHK(h, hipMemcpyAsync(h->rec, rec.data(), rec.size() * sizeof(FfStepRec), hipMemcpyHostToDevice, s));
+    const bool trk = T.trk && h->engine >= 1 && !T.kin;
+    std::vector<FfAttRec> att;
+    Meet meet{};
+    const int nt = (T.B + 15) / 16;
+    if (trk) {      // one record per attempt; a rejected attempt reads the tape record of the accepted attempt behind it
+        att.reserve(T.n_att);
+        int acc = 0;
+        for (int i = 0; i < T.n_att; ++i) {
+            const StepMeta& m = T.meta[i];
+            const bool a = (m.flags & F_ACCEPT) != 0;
+            att.push_back(ff_att_rec(m, a ? rec[acc].svb : 0.f, acc));
+            if (a) ++acc;
+        }
+        while (!att.empty() && !(att.back().flags & F_ACCEPT)) att.pop_back();      // (attempts behind the last accepted one reach nothing)
+        if (!att.empty()) FCHK(h, hipMemcpyAsync(h->att, att.data(), att.size() * sizeof(FfAttRec), hipMemcpyHostToDevice, s));
+        meet = h->meet.begin(nt, true, s);
+        FCHK(h, h->meet.err);
+    }
     FfRevParams Q{};
     Q.G = h->G; Q.p = T.p; Q.e = T.e; Q.tape = h->tape; Q.rec = h->rec; Q.logpx_bar = logpx_bar_dev;
     Q.ws = h->rws; Q.pacc = h->pacc; Q.x_bar = x_bar_dev; Q.n_acc = T.n_acc; Q.B = T.B; Q.Bp = h->Bp; Q.reltol = T.reltol; Q.abstol = T.abstol;
     Q.reg_bar = reg_bar_dev;
     FCHK(h, hipEventRecord(h->ev[2], s));
     if (h->engine >= 1) {
-        if (h->engine == 2) tile_launch_reverse<FcDyn>(h, h->CG, Q, T.kin, T.exact, s);
-        else tile_launch_reverse<FtDyn>(h, h->TG, Q, T.kin, T.exact, s);
+        if (h->engine == 2) tile_launch_reverse<FcDyn>(h, h->CG, Q, T.kin, T.exact, s, trk ? &meet : nullptr, (int)att.size());
+        else tile_launch_reverse<FtDyn>(h, h->TG, Q, T.kin, T.exact, s, trk ? &meet : nullptr, (int)att.size());
         FCHK(h, hipGetLastError());
         hipLaunchKernelGGL(rnde_ffjordt_reduce_kernel, dim3((h->G.P + 255) / 256), dim3(256), 0, s, (const float*)h->pacc, h->G.P, (T.B + 15) / 16, p_bar_dev);
     } else {
@@ -580,8 +654,22 @@ static rnde_status ff_backward(rnde_ffjord* h, const float* logpx_bar_dev, const
     }
     FCHK(h, hipGetLastError());
     FCHK(h, hipEventRecord(h->ev[3], s));
+    if (trk) FCHK(h, h->meet.queue_check(meet, s));
     FCHK(h, hipEventSynchronize(h->ev[3]));
     (void)hipEventElapsedTime(&h->rev_ms, h->ev[2], h->ev[3]);
+    if (trk) {
+        FCHK(h, hipStreamSynchronize(s));
+        const bool split = meet_split(h->meet.chk, nt, meet.global != 0);
+        if (meet_verdict(h->meet.chk, nt, meet.global != 0) != MEET_OK) {      // no fall-back to the constant-step sweep: the call fails and says why
+            FCHK(h, h->meet.clear_abort(s));
+            FCHK(h, hipStreamSynchronize(s));
+            h->err = split ? "TrackedFFJORD track_ctrl: a workgroup meeting of the tracked reverse sweep timed out (the tiles pinned to one XCD by block "
+                             "index landed on different XCDs); the sweep was abandoned, p_bar and x_bar are not valid"
+                           : "TrackedFFJORD track_ctrl: a workgroup meeting of the tracked reverse sweep timed out (not every tile was resident); the "
+                             "sweep was abandoned, p_bar and x_bar are not valid";
+            return RNDE_ERR_HIP;
+        }
+    }
     return RNDE_OK;
 }
 

@@ -18,6 +18,13 @@
 // scratch.  Parameter cotangents accumulate in the tile's own row of pacc ([ntiles][P], plain read-modify-write by one lane per entry, no
 // atomics); rnde_ffjordt_reduce_kernel sums the tiles in tile order in double.
 //
+// Tracked reverse sweep (TRK, rnde_ffjord_set_track_ctrl): the PI controller is differentiated as well (track_ctrl = 1, track_initdt = 0;
+// the chain engine's scalar reverse, rnde_bchain.h).  The sweep walks ATTEMPTS, last to first; every tile carries the cotangents of
+// (t, the proposed dt, qold) in double registers and computes them identically.  A rejected attempt recomputes its stages from the uprev
+// it shares with the accepted attempt behind it, has no unew cotangent and ADDS to the running uprev cotangent.  The cotangent of dt needs
+// three sums over the whole batch (sum <k_j, k_j-bar>, sum tau_s, sum c_s tau_s with tau_s = <dF/dt at stage s, k_s-bar>): one tile_meet
+// per attempt, in tile order in double, under the solve's launch placement (one XCD up to 32 tiles, agent scope above).
+//
 // What a dynamics policy provides (a plain struct of static members):
 //   Geo, Lds                   the geometry (kernel argument: D, P, DP and whatever the dynamics need) and the LDS view (W, X, E, red, ...)
 //   lds(G, smem)               the LDS view over the dynamic shared memory
@@ -29,7 +36,8 @@
 //                              kout[(D + 1) * ks + c] = sum f^2, kout[(D + 2) * ks + c] = sum eJ^2.  exact: the exact trace; scratch is
 //                              the tile's scratch_floats(G) floats of global memory (NULL where the host has none).
 //   vjp<KIN>(G, L, t, z, kb, yb, V, pacc, tid)
-//                              yb[0:D] += (dF/dz)' kb and pacc += (dF/dp)' kb; z, kb, yb: [R][16], V: the tile's vector slots
+//                              yb[0:D] += (dF/dz)' kb and pacc += (dF/dp)' kb; z, kb, yb: [R][16], V: the tile's vector slots.  Returns the
+//                              calling thread's share of <dF/dt, kb> over the tile's columns (the tracked sweep sums the shares)
 //   lds_floats(G), rev_ws_floats(G, kin), scratch_floats(G)
 // Barriers.  The driver writes L.X (and, once, L.E) and calls eval with no barrier of its own: eval places a barrier before its first read
 // of L.X or L.E.  Parameters that eval or vjp read ahead of that barrier (FtDyn's gates) load_params makes visible itself, by ending behind
@@ -66,6 +74,43 @@ struct TileSolveParams {
     float* reg;                      // kinetic solves: 2 x B (lambda1 row, then lambda2 row); NULL otherwise
 };
 
+// One attempt of the tracked sweep, in forward order: (t, dt, EEst) and the flags of the step log, the tape record that holds the attempt's
+// uprev, and the scalar reverse of the controller branch the forward took (rnde_bchain.h's prologue with track_ctrl = 1, t0-bar and t1-bar
+// dropped).  That reverse is linear in the running cotangents (t-bar, dtp-bar, qold-bar) behind the attempt, with coefficients that depend
+// on the step log alone, so the host forms them once, in double (ff_att_rec):
+//     EEst-bar  = e0 + e_dtp dtp-bar + e_q qold-bar                 (e0 = svb dt: the saved value EEst * dt)
+//     dt-bar    = d0 + d_t t-bar + d_dtp dtp-bar + (the three sums)   (d0 = svb EEst; d_t = 1 on an accepted attempt: t' = t + dt)
+//     qold-bar' = c_dtp dtp-bar + c_q qold-bar                        (in front of the attempt)
+struct FfAttRec {
+    float t, dt, eest;
+    int flags, rec, pad;
+    double e0, e_dtp, e_q, d0, d_t, d_dtp, c_dtp, c_q;
+};
+// Accepted: dtp' = dt / q, q = clip(q11 / qold^beta2 / gamma), qold' = max(EEst, qoldinit).  Rejected: dtp' = dt / rej_m, rej_m =
+// min(1 / qmin, q11 / gamma).  F_QCLAMP, F_DTMAXCLAMP and F_EZERO cut the path, F_REJQ11 selects it; q11 = EEst^beta1.
+inline FfAttRec ff_att_rec(const StepMeta& m, float svb, int rec) {
+    FfAttRec a{};
+    a.t = m.t; a.dt = m.dt; a.eest = m.eest; a.flags = m.flags; a.rec = rec;
+    const double dt = m.dt;
+    double qb = 0.0, q11b = 0.0;         // per unit of dtp-bar
+    if (m.flags & F_ACCEPT) {
+        a.e0 = (double)svb * dt; a.d0 = (double)svb * (double)m.eest;
+        a.d_t = 1.0;
+        if (!(m.flags & F_DTMAXCLAMP)) { a.d_dtp = 1.0 / (double)m.q; qb = -dt / ((double)m.q * (double)m.q); }
+        if (m.eest > kQoldInit) a.e_q = 1.0;
+    } else {
+        a.d_dtp = 1.0 / (double)m.rej_m;
+        if (m.flags & F_REJQ11) q11b = -dt / ((double)m.rej_m * (double)m.rej_m) / (double)kGamma;
+        a.c_q = 1.0;
+    }
+    if (!(m.flags & F_QCLAMP) && !(m.flags & F_EZERO)) {
+        q11b += qb / (pow((double)m.qold_in, (double)kBeta2) * (double)kGamma);
+        a.c_dtp = -(double)kBeta2 * qb * (double)m.q / (double)m.qold_in;
+    }
+    if (!(m.flags & F_EZERO) && m.eest > 0.f) a.e_dtp = q11b * (double)kBeta1 * (double)m.q11 / (double)m.eest;
+    return a;
+}
+
 template <class Geo>
 struct TileRevParams {
     Geo G;
@@ -82,6 +127,12 @@ struct TileRevParams {
     const float* reg_bar;             // kinetic sweep: 2 x B cotangents of (lambda1, lambda2), or NULL (zeros)
     int exact;                        // the tape of an exact-trace forward (never with KIN)
     float* scratch;                   // exact: [ntiles][Dyn::scratch_floats] or NULL, as the solve's
+    // the tracked sweep (TRK) alone
+    const FfAttRec* att;              // [n_att]
+    int n_att;
+    Meet meet;                        // three rows per meeting, one meeting per attempt
+    unsigned* xcc;                    // [ntiles] (one-XCD meeting: the host checks they agree)
+    int xcd_slot;
 };
 
 // The whole adaptive solve in one launch: forward (dir = +1; Hutchinson, or Q.exact: the exact trace with no probe), replay along P.replay,
@@ -237,11 +288,17 @@ __global__ __launch_bounds__(kFtThreads) void rnde_ffjord_tile_solve_kernel(cons
 // Q.exact (the tape of an exact-trace forward): the stages are recomputed with the exact trace, and the trace row's cotangent goes through
 // -tr J = -sum_i e_i . (e_i J) over the unit probes.  Dyn::vjp is linear in kb, so a stage takes D + 1 calls of it: one with L.E = 0 and the
 // whole kb (the trace row is quadratic in the probe and gives nothing there), then one per unit probe with kb cut down to its trace row.
-template <class Dyn, bool KIN>
+// TRK: the tracked sweep (the header); launched as the solve is (MeetRes::grid), one loop iteration per attempt.
+template <class Dyn, bool KIN, bool TRK = false>
 __global__ __launch_bounds__(kFtThreads) void rnde_ffjord_tile_reverse_kernel(const TileRevParams<typename Dyn::Geo> Q) {
     extern __shared__ float ft_smem[];
     const typename Dyn::Geo& G = Q.G;
-    const int tile = blockIdx.x, tid = threadIdx.x, D = G.D, R = D + (KIN ? 3 : 1), Bp = Q.Bp, col0 = tile * 16, nel = R * 16;
+    if constexpr (TRK)
+        if (!Q.meet.global && (int)(blockIdx.x & 7) != Q.xcd_slot) return;
+    const int tile = (TRK && !Q.meet.global) ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    if constexpr (TRK)
+        if (!Q.meet.global && threadIdx.x == 0) Q.xcc[tile] = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 15;
+    const int tid = threadIdx.x, D = G.D, R = D + (KIN ? 3 : 1), Bp = Q.Bp, col0 = tile * 16, nel = R * 16;
     const typename Dyn::Lds L = Dyn::lds(G, ft_smem);
     const int exact = KIN ? 0 : Q.exact;
     Dyn::load_params(G, Q.p, L.W, tid);
@@ -273,10 +330,15 @@ __global__ __launch_bounds__(kFtThreads) void rnde_ffjord_tile_reverse_kernel(co
     }
     // (no barrier here: UB[idx] and L.X[idx] are next touched by the thread that wrote them, pacc and L.E behind the first eval's barriers)
     const double N = (double)R * (double)Q.B;
-    for (int n = Q.n_acc - 1; n >= 0; --n) {
-        const FfStepRec st = Q.rec[n];
+    double tb = 0.0, dtpb = 0.0, qoldb = 0.0;      // TRK: the cotangents of (t, the proposed dt, qold) behind attempt n
+    for (int n = (TRK ? Q.n_att : Q.n_acc) - 1; n >= 0; --n) {
+        FfStepRec st;
+        int flags = F_ACCEPT, urec = n;
+        if constexpr (TRK) { const FfAttRec& a = Q.att[n]; st.t = a.t; st.dt = a.dt; st.eest = a.eest; st.svb = 0.f; flags = a.flags; urec = a.rec; }
+        else st = Q.rec[n];
         const float t = st.t, dt = st.dt;
-        const float* U = Q.tape + (size_t)n * RB + col0;
+        const bool accepted = (flags & F_ACCEPT) != 0;
+        const float* U = Q.tape + (size_t)urec * RB + col0;
         // ---- recompute the stages ----
         for (int s = 0; s < 7; ++s) {
             for (int idx = tid; idx < nel; idx += kFtThreads) {
@@ -292,11 +354,19 @@ __global__ __launch_bounds__(kFtThreads) void rnde_ffjord_tile_reverse_kernel(co
         for (int idx = tid; idx < nel; idx += kFtThreads) {
             for (int s = 0; s < 7; ++s) Kb(s)[idx] = 0.f;
             UBn[idx] = 0.f;
-            Yb[idx] = UB[idx];                                // cotangent of unew = stage-7 input
+            Yb[idx] = accepted ? UB[idx] : 0.f;               // cotangent of unew = stage-7 input (a rejected attempt has none)
         }
-        // ---- A: reverse of the error estimate (the saved value EEst * dt; rnde_bffjord.h) ----
-        if (st.svb != 0.f && st.eest > 0.f) {
-            const float coef = (float)(((double)st.svb * (double)dt) / (N * (double)st.eest));
+        // ---- TRK: the scalar reverse of the controller (FfAttRec) ----
+        double eb = 0.0, dtb_pre = 0.0, qoldb_in = 0.0;
+        if constexpr (TRK) {
+            const FfAttRec& a = Q.att[n];
+            eb = a.e0 + a.e_dtp * dtpb + a.e_q * qoldb;
+            dtb_pre = a.d0 + a.d_t * tb + a.d_dtp * dtpb;
+            qoldb_in = a.c_dtp * dtpb + a.c_q * qoldb;
+        }
+        // ---- A: reverse of the error estimate (the saved value EEst * dt; rnde_bffjord.h.  TRK: every attempt, with the coefficient eb) ----
+        if (TRK ? (eb != 0.0 && st.eest > 0.f) : (st.svb != 0.f && st.eest > 0.f)) {
+            const float coef = TRK ? (float)(eb / (N * (double)st.eest)) : (float)(((double)st.svb * (double)dt) / (N * (double)st.eest));
             for (int idx = tid; idx < nel; idx += kFtThreads) {
                 if (col0 + (idx & 15) >= Q.B) continue;
                 float E = 0.f;
@@ -312,6 +382,7 @@ __global__ __launch_bounds__(kFtThreads) void rnde_ffjord_tile_reverse_kernel(co
             }
         }
         __syncthreads();
+        float pS = 0.f, ptau = 0.f, pctau = 0.f;              // TRK: this thread's shares of the three sums of the dt cotangent
         // ---- B: the stages, last to first ----
         for (int s = 6; s >= 0; --s) {
             if (s != 6) {
@@ -319,6 +390,8 @@ __global__ __launch_bounds__(kFtThreads) void rnde_ffjord_tile_reverse_kernel(co
                 __syncthreads();
             }
             const int npass = exact ? D + 1 : 1;
+            if constexpr (TRK)        // <k_s, k_s-bar>: k_s-bar is complete here (an exact sweep's pass 1 cuts it down)
+                for (int idx = tid; idx < nel; idx += kFtThreads) pS = fmaf(Ks(s)[idx], Kb(s)[idx], pS);
             for (int pass = 0; pass < npass; ++pass) {
                 if (exact) {          // pass 0: L.E = 0, the whole kb; pass i: the unit probe e_i, kb's trace row alone (Kb(s) is not read again)
                     __syncthreads();
@@ -328,7 +401,8 @@ __global__ __launch_bounds__(kFtThreads) void rnde_ffjord_tile_reverse_kernel(co
                         for (int idx = tid; idx < D * 16; idx += kFtThreads) Kb(s)[idx] = 0.f;
                     __syncthreads();
                 }
-                Dyn::template vjp<KIN>(G, L, t + kTsC[s] * dt, Ys(s), Kb(s), Yb, V, pacc, tid);
+                const float ts = Dyn::template vjp<KIN>(G, L, t + kTsC[s] * dt, Ys(s), Kb(s), Yb, V, pacc, tid);
+                if constexpr (TRK) { ptau += ts; pctau = fmaf(kTsC[s], ts, pctau); }
             }
             // (exact: L.E is left holding the last unit probe; harmless, neither dynamics' eval reads L.E when exact is set)
             for (int idx = tid; idx < nel; idx += kFtThreads) {
@@ -338,8 +412,16 @@ __global__ __launch_bounds__(kFtThreads) void rnde_ffjord_tile_reverse_kernel(co
             }
             __syncthreads();
         }
-        for (int idx = tid; idx < nel; idx += kFtThreads) UB[idx] = UBn[idx];
+        for (int idx = tid; idx < nel; idx += kFtThreads) UB[idx] = accepted ? UBn[idx] : UB[idx] + UBn[idx];
         __syncthreads();
+        if constexpr (TRK) {          // the meeting, then the scalar tail (finish_attempt_scalars_sums, rnde_bwd.h): dt = min(dtp, t1 - t), t' = t + dt
+            double xs[3];
+            if (!tile_meet(Q.meet, L.red, n, pS, ptau, pctau, xs, tile, tid)) return;
+            const double dtb = dtb_pre + xs[0] / (double)dt + xs[2];
+            tb += xs[1];
+            if (flags & F_CLAMP) { tb -= dtb; dtpb = 0.0; } else dtpb = dtb;
+            qoldb = qoldb_in;
+        }
     }
     if (Q.x_bar)
         for (int idx = tid; idx < nel; idx += kFtThreads) {

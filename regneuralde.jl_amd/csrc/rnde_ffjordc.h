@@ -93,7 +93,7 @@ struct FcDyn {
     template <bool KIN>
     __device__ static void eval(const FcGeo& G, const FcLds& L, float t, float* kout, int ks, int exact, float fsign, float tsign, float* scratch, int tid);
     template <bool KIN>
-    __device__ static void vjp(const FcGeo& G, const FcLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid);      // (rnde_bffjordc.h)
+    __device__ static float vjp(const FcGeo& G, const FcLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid);      // (rnde_bffjordc.h)
 };
 
 // y_l = phi_l(W_l y_{l-1} + wt_l t + b_l) for every layer: X -> Y.  last(o, c, y): called for the rows o < D of the last layer.

@@ -103,7 +103,7 @@ struct FtDyn {
     template <bool KIN>
     __device__ static void eval(const FtGeo& G, const FtLds& L, float t, float* kout, int ks, int exact, float fsign, float tsign, float* QT, int tid);
     template <bool KIN>
-    __device__ static void vjp(const FtGeo& G, const FtLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid);      // (rnde_bffjordt.h)
+    __device__ static float vjp(const FtGeo& G, const FtLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid);      // (rnde_bffjordt.h)
 };
 __device__ __forceinline__ const float* ft_vec(const FtGeo& G, const float* W, int l, int k) { return W + G.voff[l] + k * G.outp[l]; }
 

@@ -26,6 +26,10 @@ Exact trace (an extension: the reference evaluates -tr J only inside sample()): 
 logpx carries no probe and no variance; same 5-tuple, differentiable (the reverse sweep costs about D + 1 Hutchinson ones).  On
 engine="tiled" only, without e, and not together with the kinetic rows; loglikelihood(model, batches, exact=True) reports with it.
 
+Tracked step controller (track_ctrl=True; engine="tiled" and regularize=True): the reverse pass differentiates the PI controller as well, as
+the reference's Tracker tape does (track_ctrl = 1, track_initdt = 0 of TrackedNeuralODE), so the gradient of the regulariser sum(EEst * dt)
+sees dt's dependence on the parameters.  The default (False) treats step sizes and times as constants.
+
 Refused with a message that names the limit: any other dynamics, a chain model on engine="workgroup", and widths above the engine's limit.
 """
 import ctypes as C
@@ -154,6 +158,17 @@ def check_served(model, regularize_kinetic=False, engine="workgroup"):
         raise ValueError("TrackedFFJORD{false} with regularize = true (kinetic energy and Jacobian norm rows) is not served")
 
 
+def check_track_ctrl_served(engine, regularize):
+    """ValueError naming the reason track_ctrl=True is not served (rnde_ffjord_set_track_ctrl's refusals, before a device is needed)."""
+    if engine != "tiled":
+        raise ValueError("TrackedFFJORD track_ctrl: the one-workgroup engine does not differentiate the step controller; "
+                         f"track_ctrl=True needs engine=\"tiled\" (got engine={engine!r})")
+    if not regularize:
+        raise ValueError("TrackedFFJORD track_ctrl: a regularize = false layer has no saved value EEst * dt, and without one the tracked and the "
+                         "constant-step sweep agree to O(tol) (2e-10 to 2e-6 relative, measured with the fp64 oracle); track_ctrl=True needs "
+                         "regularize=True")
+
+
 def check_kinetic_served(model, engine="workgroup"):
     """ValueError naming the limit for the {false} method's regularize = true rows (kinetic energy, Jacobian norm) on `engine`: the limits
     of check_served with two more state rows."""
@@ -179,7 +194,7 @@ class _Handle:
     """One rnde_ffjord handle.  A handle holds ONE tape: `gen` counts the taped forwards run on it, `busy` is set while a taped forward
     waits for its backward (or for its graph to be dropped)."""
 
-    def __init__(self, cfg, engine="workgroup"):
+    def __init__(self, cfg, engine="workgroup", track_ctrl=False):
         self.h = C.c_void_p()
         if isinstance(cfg, _lib.FfjordChainConfig):
             create = _lib.lib().rnde_ffjord_create_chain
@@ -187,6 +202,8 @@ class _Handle:
             create = _lib.lib().rnde_ffjord_create_tiled if engine == "tiled" else _lib.lib().rnde_ffjord_create
         _lib.check_ffjord(None, create(C.byref(cfg), C.byref(self.h)))
         self.gen, self.busy = 0, False
+        if track_ctrl:
+            _lib.check_ffjord(self.h, _lib.lib().rnde_ffjord_set_track_ctrl(self.h, 1))
 
     def __del__(self):
         try:
@@ -339,10 +356,11 @@ class TrackedFFJORD:
     method: False -> TrackedFFJORD{false} (returns logpx, 0, 0, nfe, None; called with regularize=True: logpx, lambda1, lambda2, nfe, None with
     the kinetic energy and the Jacobian norm rows, differentiable), True -> TrackedFFJORD{true} (returns logpx, 0, 0, nfe, sv with
     sv.saveval = EEst * dt per accepted step, differentiable).  Called with exact=True (engine="tiled"; no e, no kinetic rows): the same
-    5-tuple with logpx from the exact trace -tr J instead of the Hutchinson estimate, differentiable.  engine: "workgroup" (default) or "tiled" (see the module docstring)."""
+    5-tuple with logpx from the exact trace -tr J instead of the Hutchinson estimate, differentiable.  engine: "workgroup" (default) or "tiled" (see the module docstring).
+    track_ctrl=True (engine="tiled", regularize=True): the reverse pass differentiates the step controller too (every handle of the layer)."""
 
     def __init__(self, model, tspan, time_dep, regularize, solver="Tsit5", *, reltol=1.4e-8, abstol=1.4e-8, max_batch=1024, max_attempts=4096,
-                 cb_save_start=True, device=0, dynamics=None, engine="workgroup", **kwargs):
+                 cb_save_start=True, device=0, dynamics=None, engine="workgroup", track_ctrl=False, **kwargs):
         if dynamics is not None and dynamics != "forw_n_back":
             raise ValueError("TrackedFFJORD: only dynamics = forw_n_back of the ConcatSquash MLPDynamics is served")
         self.chain = is_chain(model)
@@ -358,6 +376,9 @@ class TrackedFFJORD:
         if engine == "tiled" and int(max_batch) > TILED_MAX_BATCH:
             raise ValueError(f"TrackedFFJORD tiled engine: max_batch above {TILED_MAX_BATCH} is not served (one meeting holds 256 resident tiles)")
         self.engine = engine
+        if track_ctrl:
+            check_track_ctrl_served(engine, bool(regularize))
+        self.track_ctrl = bool(track_ctrl)
         if solver != "Tsit5":
             raise ValueError("TrackedFFJORD: only Tsit5 is served")
         self.model, self.tspan, self.time_dep, self.regularize = model, (float(tspan[0]), float(tspan[1])), bool(time_dep), bool(regularize)
@@ -391,7 +412,7 @@ class TrackedFFJORD:
 
     def _handle(self):
         if self._h is None:
-            self._h = _Handle(self.config(), self.engine)
+            self._h = _Handle(self.config(), self.engine, self.track_ctrl)
         return self._h
 
     def _taped_handle(self):
@@ -401,7 +422,7 @@ class TrackedFFJORD:
         if len(self._pool) >= MAX_TAPES:
             raise RuntimeError(f"TrackedFFJORD: {MAX_TAPES} taped forwards are waiting for their backward pass; run backward (or drop the graphs) "
                                "before taping more")
-        self._pool.append(_Handle(self.config(), self.engine))
+        self._pool.append(_Handle(self.config(), self.engine, self.track_ctrl))
         return self._pool[-1]
 
     def draw_normal(self, rows, cols, device):

@@ -49,16 +49,23 @@ def main():
                     help="train with LK mean(lambda1) + LJ mean(lambda2) (kinetic energy, Jacobian norm); needs --regularize 0")
     ap.add_argument("--exact-eval", action="store_true", help="train / test log-likelihood with the exact trace (engine=\"tiled\")")
     ap.add_argument("--exact-train", action="store_true", help="train through the exact trace too (engine=\"tiled\"; not with --kinetic)")
+    ap.add_argument("--track-ctrl", action="store_true",
+                    help="differentiate the step controller in the reverse pass (engine=\"tiled\", needs --regularize 1; the equal-work comparison's "
+                         "eager restatement keeps its constant steps)")
     ap.add_argument("--out", default=None, help="default: profiles/ffjord_gaussian.json (profiles/ffjord_gaussian_kinetic.json with --kinetic, "
-                                                "profiles/ffjord_gaussian_exact.json with --exact-eval / --exact-train)")
+                                                "profiles/ffjord_gaussian_exact.json with --exact-eval / --exact-train, "
+                                                "profiles/ffjord_gaussian_track.json with --track-ctrl)")
     a = ap.parse_args()
     if a.kinetic and a.regularize:
         ap.error("--kinetic needs --regularize 0 (the {true} method never passes regularize on)")
     if a.kinetic and a.exact_train:
         ap.error("--exact-train does not go with --kinetic (the Jacobian norm row is defined on the probe)")
+    if a.track_ctrl and not a.regularize:
+        ap.error("--track-ctrl needs --regularize 1 (without a saved value the tracked and the constant-step sweep agree to O(tol))")
     exact_any = a.exact_eval or a.exact_train
     a.out = a.out or os.path.join(ROOT, "profiles", "ffjord_gaussian_kinetic.json" if a.kinetic else
-                                  ("ffjord_gaussian_exact.json" if exact_any else "ffjord_gaussian.json"))
+                                  ("ffjord_gaussian_track.json" if a.track_ctrl else
+                                   ("ffjord_gaussian_exact.json" if exact_any else "ffjord_gaussian.json")))
     kin = bool(a.kinetic)
     lk, lj = a.kinetic or (0.0, 0.0)
     import regneuralde_jl_amd as rn
@@ -69,7 +76,7 @@ def main():
     tr, te = rn.load_gaussian_mixture(a.batch, nsamples=2048, ngaussians=6, seed=a.seed)
     model = rn.ffjord.MLPDynamics(2, 16, generator=torch.Generator().manual_seed(a.seed))
     ff = rn.TrackedFFJORD(model, [0.0, 1.0], True, bool(a.regularize), "Tsit5", reltol=1.4e-8, abstol=1.4e-8, max_batch=a.batch,
-                          **(dict(engine="tiled") if exact_any else {}))
+                          **(dict(engine="tiled") if exact_any or a.track_ctrl else {}), track_ctrl=a.track_ctrl)
     p = ff.p.clone().requires_grad_(True)
     ll = lambda data: rn.loglikelihood(ff, data, p.detach(), exact=a.exact_eval)
     opt = rn.FluxADAM([p], eta=4e-2, weight_decay=1e-5)
@@ -165,7 +172,7 @@ def main():
 
     dev_t = timed(device_step)
     eager_t = timed(eager_step)
-    res = dict(regularize=a.regularize, exact_eval=a.exact_eval, exact_train=a.exact_train, engine=ff.engine, kinetic=list(a.kinetic) if kin else None, epochs=rows, sampling_time_s=min(samp), batch=a.batch,
+    res = dict(regularize=a.regularize, track_ctrl=a.track_ctrl, exact_eval=a.exact_eval, exact_train=a.exact_train, engine=ff.engine, kinetic=list(a.kinetic) if kin else None, epochs=rows, sampling_time_s=min(samp), batch=a.batch,
                train_step_ms_median=float(np.median(step_ms)), solve_launch_ms_median=float(np.median(solve_ms)),
                reverse_ms_median=float(np.median(rev_ms)), attempts_median=float(np.median(att)), accepted_median=float(np.median(accd)),
                us_per_forward_attempt=float(np.median(np.array(solve_ms) / np.array(att)) * 1e3),

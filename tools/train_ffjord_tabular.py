@@ -84,15 +84,21 @@ def main():
     ap.add_argument("--kinetic", type=float, nargs=2, default=None, metavar=("LK", "LJ"),
                     help="train with LK mean(lambda1) + LJ mean(lambda2) (kinetic energy, Jacobian norm); needs --regularize 0")
     ap.add_argument("--exact-eval", action="store_true", help="train / test log-likelihood with the exact trace (needs --engine tiled)")
+    ap.add_argument("--track-ctrl", action="store_true",
+                    help="differentiate the step controller in the reverse pass (needs --engine tiled and --regularize 1)")
     ap.add_argument("--out", default=None, help="default: profiles/ffjord_tabular.json (profiles/ffjord_tabular_kinetic.json with --kinetic, "
-                                                "profiles/ffjord_tabular_exact.json with --exact-eval)")
+                                                "profiles/ffjord_tabular_exact.json with --exact-eval, profiles/ffjord_tabular_track.json with "
+                                                "--track-ctrl)")
     a = ap.parse_args()
     if a.kinetic and a.regularize:
         ap.error("--kinetic needs --regularize 0 (the {true} method never passes regularize on)")
     if a.exact_eval and a.engine != "tiled":
         ap.error("--exact-eval needs --engine tiled (the exact trace is served by the tiled engine only)")
+    if a.track_ctrl and (a.engine != "tiled" or not a.regularize):
+        ap.error("--track-ctrl needs --engine tiled and --regularize 1 (without a saved value the tracked and the constant-step sweep agree to O(tol))")
     a.out = a.out or os.path.join(ROOT, "profiles", "ffjord_tabular_kinetic.json" if a.kinetic else
-                                  ("ffjord_tabular_exact.json" if a.exact_eval else "ffjord_tabular.json"))
+                                  ("ffjord_tabular_track.json" if a.track_ctrl else
+                                   ("ffjord_tabular_exact.json" if a.exact_eval else "ffjord_tabular.json")))
     kin = bool(a.kinetic)
     lk, lj = a.kinetic or (0.0, 0.0)
     import regneuralde_jl_amd as rn
@@ -106,7 +112,8 @@ def main():
     else:
         tr, te = synthetic(a.batch, D, a.seed)
     model = rn.ffjord.MLPDynamics(D, H, generator=torch.Generator().manual_seed(a.seed))
-    ff = rn.TrackedFFJORD(model, [0.0, 1.0], True, bool(a.regularize), "Tsit5", reltol=1.4e-8, abstol=1.4e-8, max_batch=a.batch, engine=a.engine)
+    ff = rn.TrackedFFJORD(model, [0.0, 1.0], True, bool(a.regularize), "Tsit5", reltol=1.4e-8, abstol=1.4e-8, max_batch=a.batch, engine=a.engine,
+                          track_ctrl=a.track_ctrl)
     p = ff.p.clone().requires_grad_(True)
     ll = lambda data: rn.loglikelihood(ff, data, p.detach(), exact=a.exact_eval)
     opt = rn.FluxADAM([p], eta=1e-2, weight_decay=1e-5)
@@ -202,7 +209,7 @@ def main():
 
     dev_t = timed(device_step)
     eager_t = timed(eager_step)
-    res = dict(regularize=a.regularize, exact_eval=a.exact_eval, kinetic=list(a.kinetic) if kin else None, engine=a.engine, data=("miniboone" if a.data else "synthetic"), epochs=rows, sampling_time_s=min(samp), batch=a.batch,
+    res = dict(regularize=a.regularize, track_ctrl=a.track_ctrl, exact_eval=a.exact_eval, kinetic=list(a.kinetic) if kin else None, engine=a.engine, data=("miniboone" if a.data else "synthetic"), epochs=rows, sampling_time_s=min(samp), batch=a.batch,
                train_step_ms_median=float(np.median(step_ms)), solve_launch_ms_median=float(np.median(solve_ms)),
                reverse_ms_median=float(np.median(rev_ms)), attempts_median=float(np.median(att)), accepted_median=float(np.median(accd)),
                us_per_forward_attempt=float(np.median(np.array(solve_ms) / np.array(att)) * 1e3),
