@@ -67,8 +67,8 @@ mutable struct Handle
     cfg::NodeConfig
     last_nfe::Int
     # tiled = true: rnde_node_create_tiled (include/rnde.h) -- Dense chains wider than 64 whose padded weights fit LDS (tiled_lds_bytes(cfg) <=
-    # 160 KB).  Its reverse pass treats step sizes and times as constants: the config must carry track_ctrl = track_initdt = 0
-    # (config_for(...; track = false)), the library refuses anything else by name.
+    # 160 KB).  By default its reverse pass treats step sizes and times as constants: the config must carry track_ctrl = track_initdt = 0
+    # (config_for(...; track = false)), the library refuses anything else by name; set_tracking(h, true, true) then asks for the tracked sweep.
     function Handle(cfg::NodeConfig; tiled::Bool = false)
         out = Ref{Ptr{Cvoid}}(C_NULL)
         st = tiled ? ccall((:rnde_node_create_tiled, LIB), Cint, (Ref{NodeConfig}, Ref{Ptr{Cvoid}}), cfg, out) :
@@ -78,6 +78,29 @@ mutable struct Handle
         finalizer(h -> ccall((:rnde_node_destroy, LIB), Cvoid, (Ptr{Cvoid},), h.ptr), h)
         return h
     end
+end
+
+# Which reverse sweep the taped forwards of a TILED handle get (include/rnde.h: rnde_node_set_tracking): (false, false) the default, step sizes
+# and times constants; (true, false) the step-size controller differentiated; (true, true) the initial step as well -- the reference's gradient.
+# Set after creation (the create config keeps track_ctrl = track_initdt = 0) and while the handle holds no tape.
+function set_tracking(h::Handle, track_ctrl::Bool, track_initdt::Bool = false)
+    st = ccall((:rnde_node_set_tracking, LIB), Cint, (Ptr{Cvoid}, Int32, Int32), h.ptr, Int32(track_ctrl), Int32(track_initdt))
+    st == 0 || error("rnde_node_set_tracking status $st: ", unsafe_string(ccall((:rnde_last_error, LIB), Cstring, (Ptr{Cvoid},), h.ptr)))
+    return h
+end
+function tracking(h::Handle)
+    c = Ref{Int32}(0); i = Ref{Int32}(0)
+    st = ccall((:rnde_node_tracking, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}), h.ptr, c, i)
+    st == 0 || error("rnde_node_tracking status $st")
+    return c[] != 0, i[] != 0
+end
+# (t, dt, dtp_in, EEst, accepted, q) of every attempt of the last solve, 6 x n (rnde_node_attempts_ext)
+function attempts_ext(h::Handle)
+    n = Ref{Int32}(0)
+    out = Matrix{Float32}(undef, 6, h.cfg.max_attempts)
+    st = ccall((:rnde_node_attempts_ext, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Int32, Ref{Int32}), h.ptr, out, Int32(h.cfg.max_attempts), n)
+    st == 0 || error("rnde_node_attempts_ext status $st: ", unsafe_string(ccall((:rnde_last_error, LIB), Cstring, (Ptr{Cvoid},), h.ptr)))
+    return out[:, 1:n[]]
 end
 
 # LDS bytes of a tile of the tiled engine for this config (no device needed; -1: a malformed shape); the limit is 160 * 1024

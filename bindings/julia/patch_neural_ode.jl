@@ -18,8 +18,11 @@ using RegNeuralDE: TrackedNeuralODE, TDChain, _convert_tspan
 
 const RNDE_ODE_HANDLES = IdDict{Any,Dict{Tuple{Int,Int},RNDE.Handle}}()
 # :default -- rnde_node_create's own routing; :tiled -- rnde_node_create_tiled (Dense chains wider than 64 whose weights fit LDS; end state only,
-# Tsit5, EEst * dt or no callback).  OPT-IN, because its gradient differs: step sizes and times are constants of its reverse pass.
+# Tsit5, EEst * dt or no callback).  OPT-IN.  By default step sizes and times are constants of its reverse pass; RNDE_ODE_TILED_TRACKING[] =
+# (true, true) makes every tiled handle created from then on differentiate the controller and the initial step (RNDE.set_tracking), which is the
+# reference's gradient; (true, false) the controller alone.
 const RNDE_ODE_ENGINE = Ref(:default)
+const RNDE_ODE_TILED_TRACKING = Ref((false, false))
 const TSIT5_STABILITY_SIZE = 3.5068      # OrdinaryDiffEq.alg_stability_size(Tsit5()), the constant mnist_node.jl:73,:86 divides by
 
 # Dense sizes / activations of the dynamics (TDChain or Chain of Dense layers; a leading `x -> tanh.(x)` is latent_ode.jl:114's pre-activation).
@@ -58,8 +61,10 @@ function rnde_handle(n::TrackedNeuralODE, B::Int, code::Int)
     get!(tab, (B, code)) do
         dims, acts, td, pre = _dense_layout(n.model)
         tiled = RNDE_ODE_ENGINE[] === :tiled
-        RNDE.Handle(RNDE.config_for(dims, acts; time_dep = td, pre_act = pre, max_batch = B, reltol = Float32(get(n.kwargs, :reltol, 1f-3)),
-                                    abstol = Float32(get(n.kwargs, :abstol, 1f-6)), regularize = code, track = !tiled); tiled = tiled)
+        h = RNDE.Handle(RNDE.config_for(dims, acts; time_dep = td, pre_act = pre, max_batch = B, reltol = Float32(get(n.kwargs, :reltol, 1f-3)),
+                                        abstol = Float32(get(n.kwargs, :abstol, 1f-6)), regularize = code, track = !tiled); tiled = tiled)
+        tiled && RNDE_ODE_TILED_TRACKING[][1] && RNDE.set_tracking(h, RNDE_ODE_TILED_TRACKING[]...)
+        h
     end
 end
 

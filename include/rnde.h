@@ -125,18 +125,34 @@ void        rnde_node_destroy(rnde_node* h);
  *   exceed 163840 (160 KB); the solve and the reverse sweep share the layout.  [2,128,128,2] needs 120512 bytes, [64,192,64] 146944 (served);
  *   [64,256,64] needs 192768 and is refused with that count in the message.  The state may have more than 64 rows where the bytes allow.
  *   rnde_node_tiled_lds_bytes needs no device; -1 for a malformed shape.
- * CONSTANT STEP SIZES IN THE REVERSE: rnde_node_backward on this engine differentiates the recorded Runge-Kutta program with step sizes and
- *   times as constants (the cotangent of a saved value EEst * dt reaches the stages through EEst) and returns tspan_bar = (0, 0).  That is
- *   track_ctrl = track_initdt = 0, and rnde_node_create_tiled REFUSES a config with either flag set: nobody gets the constant-step gradient
- *   without asking for it.  (Differentiating the controller on this layout takes one meeting per reversed step: not built.)
- * Calls served on such a handle: rnde_node_forward, _forward_replay, _backward, _release_tape, _steps, _timing (solve, reverse sweep, tile
- *   reduction; always recorded), _last_attempts, rnde_debug_feval, rnde_node_forward_host / _backward_host, rnde_node_destroy.
+ * CONSTANT STEP SIZES IN THE REVERSE BY DEFAULT: rnde_node_backward on this engine differentiates the recorded Runge-Kutta program with step
+ *   sizes and times as constants (the cotangent of a saved value EEst * dt reaches the stages through EEst) and returns tspan_bar = (0, 0).
+ *   That is track_ctrl = track_initdt = 0, and rnde_node_create_tiled REFUSES a config with either flag set: nobody gets the constant-step
+ *   gradient without asking for it.  rnde_node_set_tracking (below) switches the handle to the tracked sweep AFTER creation: the PI
+ *   controller, the clamps and (track_initdt) the initial-step rule are differentiated too, one meeting of the tiles per reversed attempt,
+ *   and tspan_bar is the real cotangent.  With regularize = RNDE_REG_ERR the constant-step gradient of sum EEst * dt is 40-94 % away from
+ *   the tracked one.
+ * Calls served on such a handle: rnde_node_forward, _forward_replay, _backward, _release_tape, _steps, _attempts_ext, _set_tracking,
+ *   _tracking, _timing (solve, reverse sweep, tile reduction; always recorded), _last_attempts, rnde_debug_feval, rnde_node_forward_host / _backward_host, rnde_node_destroy.
  * Refused with RNDE_ERR_BAD_ARG and a message naming the entry: rnde_node_forward_saveat / _everystep, rnde_debug_attempt, rnde_bench_*,
  *   rnde_node_set_coupling, rnde_node_set_matrix_mode(h, 1), rnde_node_classifier_grad, rnde_node_backward_async; a tape pool
- *   (rnde_tapes_create) holds rnde_node_create instances only.  A meeting of the solve that times out is RNDE_ERR_HIP with a message that
- *   says so; nothing falls back to other arithmetic. */
+ *   (rnde_tapes_create) holds rnde_node_create instances only.  A meeting of the solve or of the tracked reverse sweep that times out is
+ *   RNDE_ERR_HIP with a message that says which; nothing falls back to other arithmetic. */
 rnde_status rnde_node_create_tiled(const rnde_node_config* cfg, rnde_node** out);
 int64_t     rnde_node_tiled_lds_bytes(const rnde_node_config* cfg);
+
+/* Which reverse sweep the taped forwards of a TILED handle get, set after creation (any regularize).  (0, 0): the default, step sizes and
+ * times constants, bit for bit the sweep of a handle that was never switched.  (1, 0): the step-size controller and the clamps to t1 are
+ * differentiated, the first proposed step is a constant.  (1, 1): the initial-step rule as well -- the reference's gradient (its Tracker
+ * tapes the solver's scalar arithmetic).  The tape remembers the setting of its forward; rnde_node_backward runs the sweep the tape asks
+ * for and tspan_bar_host receives (t0-bar, t1-bar) from a tracked tape, (0, 0) otherwise.  A tracked replay tape is differentiated as if
+ * the controller had produced the sequence.  Refused with RNDE_ERR_BAD_ARG and a message, before any launch: (0, 1) (with the controller
+ * a constant the first step reaches nothing), values other than 0 / 1, a handle of rnde_node_create (those engines take cfg.track_ctrl /
+ * cfg.track_initdt), a handle that holds a tape, and -- when tracking is first switched on with max_batch above 512 -- a device that does
+ * not hold max_batch / 16 workgroups of the tracked sweep at once.  rnde_node_tracking reads the setting back (a handle of
+ * rnde_node_create: its config's flags). */
+rnde_status rnde_node_set_tracking(rnde_node* h, int32_t track_ctrl, int32_t track_initdt);
+rnde_status rnde_node_tracking(const rnde_node* h, int32_t* ctrl_out, int32_t* initdt_out);
 
 /* Forward solve on [t0,t1].  u_out_dev: D x B.  saveval_host (may be NULL when regularize==0):
  * room for max_attempts+1 floats.  keep_tape != 0 records what rnde_node_backward needs.
@@ -204,6 +220,10 @@ rnde_status rnde_node_backward_host(rnde_node* h, const float* u_bar, const floa
 
 /* Per-attempt log of the last forward: 4 floats per attempt (t, dt, EEst, accepted). */
 rnde_status rnde_node_steps(rnde_node* h, float* steps_host, int32_t capacity, int32_t* n_attempts_out);
+/* The same log with the controller's side of it: 6 floats per attempt (t, dt, dtp_in, EEst, accepted, q) -- dtp_in the step the controller
+ * proposed (dt = min(dtp_in, t1 - t)), q its step-size factor.  Every engine.  out_host NULL: the count only; capacity below the attempt
+ * count: RNDE_ERR_BAD_ARG.  (dtp_in, accepted) replays the solve through rnde_node_forward_replay with the same clamp to t1.) */
+rnde_status rnde_node_attempts_ext(rnde_node* h, float* out_host, int32_t capacity, int32_t* n_attempts_out);
 
 /* Kernel-level entry points used by the parity tests and by bench.py's roofline leg.
  * rnde_debug_attempt: ONE Tsit5 attempt (6 f evaluations + error estimate) from a given

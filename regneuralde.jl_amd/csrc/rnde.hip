@@ -1104,6 +1104,20 @@ extern "C" rnde_status rnde_node_steps(rnde_node* h, float* steps_host, int32_t 
     return RNDE_OK;
 }
 
+extern "C" rnde_status rnde_node_attempts_ext(rnde_node* h, float* out_host, int32_t capacity, int32_t* n_out) {
+    if (!h || !n_out) return RNDE_ERR_BAD_ARG;
+    *n_out = h->n_att;
+    if (out_host) {
+        if (capacity < h->n_att) { h->err = "rnde_node_attempts_ext: capacity below the attempt count"; return RNDE_ERR_BAD_ARG; }
+        for (int i = 0; i < h->n_att; ++i) {
+            const StepMeta& m = h->h_meta[i];
+            float* o = out_host + 6 * (size_t)i;
+            o[0] = m.t; o[1] = m.dt; o[2] = m.dtp_in; o[3] = m.eest; o[4] = (m.flags & F_ACCEPT) ? 1.f : 0.f; o[5] = m.q;
+        }
+    }
+    return RNDE_OK;
+}
+
 extern "C" rnde_status rnde_node_set_timing(rnde_node* h, int32_t on) {
     if (!h) return RNDE_ERR_BAD_ARG;
     if (on && !h->tev[0]) for (auto& e : h->tev) HIPCHK(h, hipEventCreate(&e));

@@ -47,6 +47,7 @@
 #include "rnde_bffjord.h"      // FfStepRec
 #include "rnde_ffjordt.h"      // the tile layout's constants; rnde_meet.h
 #include "rnde_tile_meet.h"    // tile_meet
+#include "rnde_track_rec.h"    // FfAttRec, ff_att_rec
 
 namespace rnde {
 
@@ -74,42 +75,7 @@ struct TileSolveParams {
     float* reg;                      // kinetic solves: 2 x B (lambda1 row, then lambda2 row); NULL otherwise
 };
 
-// One attempt of the tracked sweep, in forward order: (t, dt, EEst) and the flags of the step log, the tape record that holds the attempt's
-// uprev, and the scalar reverse of the controller branch the forward took (rnde_bchain.h's prologue with track_ctrl = 1, t0-bar and t1-bar
-// dropped).  That reverse is linear in the running cotangents (t-bar, dtp-bar, qold-bar) behind the attempt, with coefficients that depend
-// on the step log alone, so the host forms them once, in double (ff_att_rec):
-//     EEst-bar  = e0 + e_dtp dtp-bar + e_q qold-bar                 (e0 = svb dt: the saved value EEst * dt)
-//     dt-bar    = d0 + d_t t-bar + d_dtp dtp-bar + (the three sums)   (d0 = svb EEst; d_t = 1 on an accepted attempt: t' = t + dt)
-//     qold-bar' = c_dtp dtp-bar + c_q qold-bar                        (in front of the attempt)
-struct FfAttRec {
-    float t, dt, eest;
-    int flags, rec, pad;
-    double e0, e_dtp, e_q, d0, d_t, d_dtp, c_dtp, c_q;
-};
-// Accepted: dtp' = dt / q, q = clip(q11 / qold^beta2 / gamma), qold' = max(EEst, qoldinit).  Rejected: dtp' = dt / rej_m, rej_m =
-// min(1 / qmin, q11 / gamma).  F_QCLAMP, F_DTMAXCLAMP and F_EZERO cut the path, F_REJQ11 selects it; q11 = EEst^beta1.
-inline FfAttRec ff_att_rec(const StepMeta& m, float svb, int rec) {
-    FfAttRec a{};
-    a.t = m.t; a.dt = m.dt; a.eest = m.eest; a.flags = m.flags; a.rec = rec;
-    const double dt = m.dt;
-    double qb = 0.0, q11b = 0.0;         // per unit of dtp-bar
-    if (m.flags & F_ACCEPT) {
-        a.e0 = (double)svb * dt; a.d0 = (double)svb * (double)m.eest;
-        a.d_t = 1.0;
-        if (!(m.flags & F_DTMAXCLAMP)) { a.d_dtp = 1.0 / (double)m.q; qb = -dt / ((double)m.q * (double)m.q); }
-        if (m.eest > kQoldInit) a.e_q = 1.0;
-    } else {
-        a.d_dtp = 1.0 / (double)m.rej_m;
-        if (m.flags & F_REJQ11) q11b = -dt / ((double)m.rej_m * (double)m.rej_m) / (double)kGamma;
-        a.c_q = 1.0;
-    }
-    if (!(m.flags & F_QCLAMP) && !(m.flags & F_EZERO)) {
-        q11b += qb / (pow((double)m.qold_in, (double)kBeta2) * (double)kGamma);
-        a.c_dtp = -(double)kBeta2 * qb * (double)m.q / (double)m.qold_in;
-    }
-    if (!(m.flags & F_EZERO) && m.eest > 0.f) a.e_dtp = q11b * (double)kBeta1 * (double)m.q11 / (double)m.eest;
-    return a;
-}
+// (FfAttRec / ff_att_rec, one attempt of the tracked sweep and the scalar reverse of its controller branch: rnde_track_rec.h)
 
 template <class Geo>
 struct TileRevParams {

@@ -20,6 +20,7 @@
 #pragma once
 #include "rnde_tile_meet.h"        // tile_meet; rnde_ffjordt.h, rnde_meet.h
 #include "rnde_ffjordc.h"          // FcGeo, fc_geo, FcDyn::load_params, fc_chain
+#include "rnde_track_rec.h"        // FfAttRec; the initial-step rule's scalar reverse
 
 namespace rnde {
 
@@ -82,6 +83,15 @@ struct NodeTileRevParams {
     float* x_bar;                     // D x B caller layout (may be NULL)
     int n_acc, B, Bp;
     float reltol, abstol;
+    // the tracked sweep (rnde_node_tile_reverse_kernel<true>) alone
+    const FfAttRec* att;              // [n_att]
+    int n_att, track_initdt;
+    InitRec init;                     // the taped solve's initial-step record
+    float t0;
+    double* tspan_out;                // [2]: (t0-bar, t1-bar), written by tile 0
+    Meet meet;                        // three rows per meeting: one per attempt, then two for the initial step
+    unsigned* xcc;                    // [ntiles] (one-XCD meeting: the host checks they agree)
+    int xcd_slot;
 };
 
 // The whole adaptive solve in one launch (also the replay along F.replay).

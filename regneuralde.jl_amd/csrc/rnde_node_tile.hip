@@ -1,6 +1,7 @@
 // rnde_node_tile.hip -- C ABI of the tiled engine of TrackedNeuralODE (include/rnde.h: rnde_node_create_tiled, engine 4): an rnde_node
-// whose solve, reverse sweep and feval are the kernels of rnde_node_tile.h / rnde_bnode_tile.h.  The public rnde_node_* entries (rnde.hip,
-// rnde_reverse.hip) hand a handle of this engine to the node_tiled_* functions below, or refuse it by name.
+// whose solve, reverse sweeps (constant-step and tracked: rnde_node_set_tracking) and feval are the kernels of rnde_node_tile.h /
+// rnde_bnode_tile.h.  The public rnde_node_* entries (rnde.hip, rnde_reverse.hip) hand a handle of this engine to the node_tiled_* functions
+// below, or refuse it by name.
 #include "rnde_node.h"
 #include "rnde_bnode_tile.h"
 
@@ -14,10 +15,20 @@ struct rnde_node_tiled {
     StepMeta* meta = nullptr;        // [max_attempts]
     InitRec* initrec_t = nullptr;    // [ntiles]
     NtStepRec* rec = nullptr;        // [max_attempts]
+    // rnde_node_set_tracking: taped forwards are reversed with the controller (and the initial step) differentiated
+    bool track_ctrl = false, track_initdt = false;
+    FfAttRec* att = nullptr;         // [max_attempts]: the tracked sweep's attempt records (allocated when tracking is first switched on)
+    double* tsb = nullptr;           // [2]: the tracked sweep's (t0-bar, t1-bar)
+    double* h_tsb = nullptr;         // pinned [2]: where the host reads them (an asynchronous copy must not land in a dead stack frame)
+    std::vector<NtStepRec> h_rec;    // the accepted steps' records of the last reverse sweep (likewise)
+    std::vector<FfAttRec> h_att;     // the attempt records of the last tracked sweep (the source of an asynchronous copy: it outlives the call)
     MeetRes meet;
     // the taped forward, kept apart from the last solve (an untaped probe between a taped forward and its backward leaves it alone)
     std::vector<StepMeta> tp_meta;
     int tp_n_att = 0, tp_n_acc = 0, tp_B = 0;
+    bool tp_track_ctrl = false, tp_track_initdt = false;      // the tape remembers the setting of its forward
+    InitRec tp_init{};
+    float tp_t0 = 0.f;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     bool ev_fwd = false, ev_bwd = false;
 };
@@ -57,8 +68,9 @@ static const char* nt_refusal(const rnde_node_config* c) {
     if (c->pre_act != RNDE_PRE_NONE) return "TrackedNeuralODE tiled engine: pre_act must be RNDE_PRE_NONE (a leading tanh or cube runs on the chain engine, rnde_node_create)";
     if (c->col_tile != 0) return "TrackedNeuralODE tiled engine: col_tile must be 0 (the engine has one layout: four waves per 16 columns)";
     if (c->track_ctrl != 0 || c->track_initdt != 0)
-        return "TrackedNeuralODE tiled engine: track_ctrl = 1 and track_initdt = 1 are not served: the reverse sweep treats step sizes and times as "
-               "constants (set track_ctrl = 0 and track_initdt = 0; rnde_node_create differentiates the controller and the initial step)";
+        return "TrackedNeuralODE tiled engine: track_ctrl = 1 and track_initdt = 1 are not served in the create config: a fresh handle's reverse sweep "
+               "treats step sizes and times as constants (set track_ctrl = 0 and track_initdt = 0; rnde_node_set_tracking then switches the handle to "
+               "the sweep that differentiates the controller and the initial step, as rnde_node_create's engines do)";
     if (c->max_batch < 1 || c->max_attempts < 1 || !(c->reltol > 0.f) || !(c->abstol > 0.f)) return "TrackedNeuralODE tiled engine: bad max_batch / max_attempts / tolerances";
     if (c->max_batch > 16 * kMwMeetMax)
         return "TrackedNeuralODE tiled engine: max_batch above 4096 is not served (one meeting holds kMwMeetMax = 256 resident tiles of 16 columns)";
@@ -76,9 +88,10 @@ void node_tiled_destroy(rnde_node* h) {
     rnde_node_tiled* T = h->tiled;
     if (!T) return;
     for (void* p : {(void*)T->ws, (void*)T->tape, (void*)T->norm, (void*)T->replay, (void*)T->rws, (void*)T->pacc, (void*)T->pcopy, (void*)T->ctl,
-                    (void*)T->ctl_t, (void*)T->meta, (void*)T->initrec_t, (void*)T->rec})
+                    (void*)T->ctl_t, (void*)T->meta, (void*)T->initrec_t, (void*)T->rec, (void*)T->att, (void*)T->tsb})
         if (p) (void)hipFree(p);
     T->meet.destroy();
+    if (T->h_tsb) (void)hipHostFree(T->h_tsb);
     for (auto& v : T->ev) if (v) (void)hipEventDestroy(v);
     delete T;
     h->tiled = nullptr;
@@ -121,7 +134,7 @@ extern "C" rnde_status rnde_node_create_tiled(const rnde_node_config* c, rnde_no
     if ((e = hipMalloc(&T->rec, MA * sizeof(NtStepRec))) != hipSuccess) return fail(e);
     if ((e = hipHostMalloc((void**)&h->h_meta, MA * sizeof(StepMeta))) != hipSuccess) return fail(e);
     if ((e = T->meet.create(MA + 4, 3, kMwMeetMax)) != hipSuccess) return fail(e);
-    for (const void* k : {(const void*)rnde_node_tile_solve_kernel, (const void*)rnde_node_tile_reverse_kernel, (const void*)rnde_node_tile_feval_kernel})
+    for (const void* k : {(const void*)rnde_node_tile_solve_kernel, (const void*)rnde_node_tile_reverse_kernel<false>, (const void*)rnde_node_tile_feval_kernel})
         if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)T->lds_bytes)) != hipSuccess) return fail(e);
     if (T->ntiles_max > kMeetXcdCus) {      // the agent-scope meeting: every tile of the largest batch must be resident at once
         int per_cu = 0;
@@ -212,8 +225,116 @@ rnde_status node_tiled_forward(rnde_node* h, const float* x_dev, const float* p_
     if (taped) {
         T->tp_meta.assign(h->h_meta, h->h_meta + fin.n_att);
         T->tp_n_att = fin.n_att; T->tp_n_acc = fin.n_acc; T->tp_B = B;
+        T->tp_track_ctrl = T->track_ctrl; T->tp_track_initdt = T->track_initdt; T->tp_t0 = t0;
+        if (T->track_initdt) HIPCHK(h, hipMemcpy(&T->tp_init, T->initrec_t, sizeof(InitRec), hipMemcpyDeviceToHost));      // (every tile's record is tile 0's)
         h->have_tape = true;
     }
+    return RNDE_OK;
+}
+
+// The tracked sweep of a tape whose forward ran under rnde_node_set_tracking(h, 1, *): launched as the solve is, one meeting per attempt
+// (and two for the initial step); rec: the accepted steps with their saved values' cotangents.
+static rnde_status node_tiled_backward_tracked(rnde_node* h, const std::vector<NtStepRec>& rec, const float* u_bar_dev, float* x_bar_dev, float* p_bar_dev,
+                                               float* tspan_bar_host, hipStream_t s) {
+    rnde_node_tiled* T = h->tiled;
+    std::vector<FfAttRec>& att = T->h_att;      // one record per attempt; a rejected attempt reads the tape record of the accepted attempt behind it
+    att.clear();
+    att.reserve(T->tp_n_att);
+    int acc = 0;
+    for (int i = 0; i < T->tp_n_att; ++i) {
+        const StepMeta& m = T->tp_meta[i];
+        const bool a = (m.flags & F_ACCEPT) != 0;
+        att.push_back(ff_att_rec(m, a ? rec[acc].svb : 0.f, acc));
+        if (a) ++acc;
+    }
+    while (!att.empty() && !(att.back().flags & F_ACCEPT)) att.pop_back();      // (attempts behind the last accepted one reach nothing)
+    if (!att.empty()) HIPCHK(h, hipMemcpyAsync(T->att, att.data(), att.size() * sizeof(FfAttRec), hipMemcpyHostToDevice, s));
+    const int nt = (T->tp_B + 15) / 16;
+    const Meet meet = T->meet.begin(nt, true, s);      // a new epoch re-arms the rows the solve used
+    HIPCHK(h, T->meet.err);
+    NodeTileRevParams Q{};
+    Q.G = T->G; Q.p = T->pcopy; Q.tape = T->tape; Q.rec = T->rec; Q.u_bar = u_bar_dev; Q.ws = T->rws; Q.pacc = T->pacc; Q.x_bar = x_bar_dev;
+    Q.n_acc = T->tp_n_acc; Q.B = T->tp_B; Q.Bp = T->Bp; Q.reltol = h->cfg.reltol; Q.abstol = h->cfg.abstol;
+    Q.att = T->att; Q.n_att = (int)att.size(); Q.track_initdt = T->tp_track_initdt ? 1 : 0; Q.init = T->tp_init; Q.t0 = T->tp_t0; Q.tspan_out = T->tsb;
+    Q.meet = meet; Q.xcc = T->meet.xcc; Q.xcd_slot = T->meet.slot;
+    HIPCHK(h, hipEventRecord(T->ev[2], s));
+    hipLaunchKernelGGL(rnde_node_tile_reverse_kernel<true>, dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(T->ev[3], s));
+    hipLaunchKernelGGL(rnde_node_tile_reduce_kernel, dim3((h->P + 255) / 256), dim3(256), 0, s, (const float*)T->pacc, h->P, nt, p_bar_dev);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(T->ev[4], s));
+    T->ev_bwd = true;
+    double* tsb = T->h_tsb;
+    HIPCHK(h, hipMemcpyAsync(tsb, T->tsb, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, T->meet.queue_check(meet, s));
+    HIPCHK(h, hipStreamSynchronize(s));      // (att and tsb are members: a copy still in flight on an error return above touches live memory)
+    const bool split = meet_split(T->meet.chk, nt, meet.global != 0);
+    if (meet_verdict(T->meet.chk, nt, meet.global != 0) != MEET_OK) {      // no fall-back to the constant-step sweep: the call fails and says why
+        HIPCHK(h, T->meet.clear_abort(s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        h->err = split ? "TrackedNeuralODE tiled engine: a workgroup meeting of the tracked reverse sweep timed out (the tiles pinned to one XCD by block "
+                         "index landed on different XCDs); the sweep was abandoned, x_bar, p_bar and tspan_bar are not valid"
+                       : "TrackedNeuralODE tiled engine: a workgroup meeting of the tracked reverse sweep timed out (not every tile was resident); the "
+                         "sweep was abandoned, x_bar, p_bar and tspan_bar are not valid";
+        return RNDE_ERR_HIP;
+    }
+    if (tspan_bar_host) { tspan_bar_host[0] = (float)tsb[0]; tspan_bar_host[1] = (float)tsb[1]; }
+    return RNDE_OK;
+}
+
+// ---- rnde_node_set_tracking: which reverse sweep the taped forwards of a tiled handle get ----
+extern "C" rnde_status rnde_node_set_tracking(rnde_node* h, int32_t track_ctrl, int32_t track_initdt) {
+    if (!h) return RNDE_ERR_BAD_ARG;
+    if (h->engine != 4) {
+        h->err = "rnde_node_set_tracking: served on handles of rnde_node_create_tiled; the engines of rnde_node_create take cfg.track_ctrl / cfg.track_initdt "
+                 "at creation";
+        return RNDE_ERR_BAD_ARG;
+    }
+    rnde_node_tiled* T = h->tiled;
+    if ((track_ctrl != 0 && track_ctrl != 1) || (track_initdt != 0 && track_initdt != 1)) {
+        h->err = "TrackedNeuralODE tiled engine: rnde_node_set_tracking: track_ctrl and track_initdt are 0 or 1";
+        return RNDE_ERR_BAD_ARG;
+    }
+    if (!track_ctrl && track_initdt) {
+        h->err = "TrackedNeuralODE tiled engine: rnde_node_set_tracking: track_ctrl = 0 with track_initdt = 1 is not served: with the controller a constant "
+                 "the proposed step of attempt 0 reaches nothing, so it repairs nothing (the settings are (0, 0), (1, 0) and (1, 1))";
+        return RNDE_ERR_BAD_ARG;
+    }
+    if (h->have_tape) {
+        h->err = "TrackedNeuralODE tiled engine: rnde_node_set_tracking: the handle holds a tape (a taped forward waiting for its backward); the tape "
+                 "remembers the setting of its forward, change it before the forward or after rnde_node_release_tape";
+        return RNDE_ERR_BAD_ARG;
+    }
+    if (track_ctrl && !T->att) {
+        HIPCHK(h, hipSetDevice(h->cfg.device));
+        HIPCHK(h, hipFuncSetAttribute((const void*)rnde_node_tile_reverse_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)T->lds_bytes));
+        if (T->ntiles_max > kMeetXcdCus) {      // the agent-scope meeting: every tile of the largest batch resident at once, on the tracked kernel's own footprint
+            int per_cu = 0;
+            hipDeviceProp_t prop;
+            HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rnde_node_tile_reverse_kernel<true>, kFtThreads, T->lds_bytes));
+            HIPCHK(h, hipGetDeviceProperties(&prop, h->cfg.device));
+            if ((long long)per_cu * prop.multiProcessorCount < T->ntiles_max) {
+                h->err = "TrackedNeuralODE tiled engine: rnde_node_set_tracking: max_batch needs " + std::to_string(T->ntiles_max) +
+                         " resident tiles for the tracked reverse sweep's meeting, the device holds " +
+                         std::to_string((long long)per_cu * prop.multiProcessorCount) + " workgroups of the tracked sweep's footprint";
+                return RNDE_ERR_BAD_ARG;
+            }
+        }
+        // (att last: it is what marks the switch-on as done, so a call that failed half way is simply made again)
+        if (!T->tsb) HIPCHK(h, hipMalloc(&T->tsb, 2 * sizeof(double)));
+        if (!T->h_tsb) HIPCHK(h, hipHostMalloc((void**)&T->h_tsb, 2 * sizeof(double)));
+        HIPCHK(h, hipMalloc(&T->att, (size_t)h->cfg.max_attempts * sizeof(FfAttRec)));
+    }
+    T->track_ctrl = track_ctrl != 0; T->track_initdt = track_initdt != 0;
+    return RNDE_OK;
+}
+
+extern "C" rnde_status rnde_node_tracking(const rnde_node* h, int32_t* ctrl_out, int32_t* initdt_out) {
+    if (!h) return RNDE_ERR_BAD_ARG;
+    // (a handle of rnde_node_create: its config's flags, fixed at creation)
+    if (ctrl_out) *ctrl_out = h->engine == 4 ? (h->tiled->track_ctrl ? 1 : 0) : h->cfg.track_ctrl;
+    if (initdt_out) *initdt_out = h->engine == 4 ? (h->tiled->track_initdt ? 1 : 0) : h->cfg.track_initdt;
     return RNDE_OK;
 }
 
@@ -224,7 +345,8 @@ rnde_status node_tiled_backward(rnde_node* h, const float* u_bar_dev, const floa
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const bool reg = h->cfg.regularize == RNDE_REG_ERR;
-    std::vector<NtStepRec> rec;
+    std::vector<NtStepRec>& rec = T->h_rec;      // (a member: the source of an asynchronous copy outlives an error return)
+    rec.clear();
     rec.reserve(T->tp_n_acc);
     int k = (reg && h->cfg.cb_save_start) ? 1 : 0;       // (the value saved at init is a constant)
     for (int i = 0; i < T->tp_n_att; ++i) {
@@ -237,12 +359,13 @@ rnde_status node_tiled_backward(rnde_node* h, const float* u_bar_dev, const floa
     }
     if ((int)rec.size() != T->tp_n_acc) { h->err = "internal: accepted-step count mismatch"; return RNDE_ERR_BAD_ARG; }
     if (!rec.empty()) HIPCHK(h, hipMemcpyAsync(T->rec, rec.data(), rec.size() * sizeof(NtStepRec), hipMemcpyHostToDevice, s));
+    if (T->tp_track_ctrl) return node_tiled_backward_tracked(h, rec, u_bar_dev, x_bar_dev, p_bar_dev, tspan_bar_host, s);
     NodeTileRevParams Q{};
     Q.G = T->G; Q.p = T->pcopy; Q.tape = T->tape; Q.rec = T->rec; Q.u_bar = u_bar_dev; Q.ws = T->rws; Q.pacc = T->pacc; Q.x_bar = x_bar_dev;
     Q.n_acc = T->tp_n_acc; Q.B = T->tp_B; Q.Bp = T->Bp; Q.reltol = h->cfg.reltol; Q.abstol = h->cfg.abstol;
     const int nt = (T->tp_B + 15) / 16;
     HIPCHK(h, hipEventRecord(T->ev[2], s));
-    hipLaunchKernelGGL(rnde_node_tile_reverse_kernel, dim3(nt), dim3(kFtThreads), T->lds_bytes, s, Q);
+    hipLaunchKernelGGL(rnde_node_tile_reverse_kernel<false>, dim3(nt), dim3(kFtThreads), T->lds_bytes, s, Q);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(T->ev[3], s));
     hipLaunchKernelGGL(rnde_node_tile_reduce_kernel, dim3((h->P + 255) / 256), dim3(256), 0, s, (const float*)T->pacc, h->P, nt, p_bar_dev);

@@ -17,8 +17,11 @@ Differences from the Julia layer that are inherent to the host language:
 after every accepted step (and the initial one with save_start=True), (B, n, D) with n known after the call.
 
 `engine="tiled"` (opt-in; `rnde_node_create_tiled`) serves Dense chains wider than 64 whose padded weights fit LDS (`tiled_lds_bytes(dims)` <=
-160 KB): end state only, Tsit5, EEst*dt or no callback.  Its gradient treats step sizes and times as constants, so the layer must be built with
-`track_ctrl=False, track_initdt=False`; `check_tiled_served` raises a ValueError that names the limit for everything else it does not serve.
+160 KB): end state only, Tsit5, EEst*dt or no callback.  By default its gradient treats step sizes and times as constants, and the layer must be
+built with `track_ctrl=False, track_initdt=False` (they describe the create config); `set_tracking(True, True)` or the constructor keyword
+`tiled_tracking=(True, True)` then switches its handles to the tracked reverse sweep (`rnde_node_set_tracking`): the controller and the initial
+step are differentiated and `last_tspan_bar` carries the real cotangent.  `check_tiled_served` raises a ValueError that names the limit for
+everything else the engine does not serve.
 """
 import ctypes as C
 
@@ -131,6 +134,7 @@ class _Handle:
         st = create(C.byref(cfg), C.byref(self.ptr))
         _lib.check(None, st)
         self.busy = False
+        self.tracking = (False, False)      # engine="tiled": the pair this handle runs under (rnde_node_set_tracking)
 
     def __del__(self):
         try:
@@ -241,7 +245,8 @@ class TrackedNeuralODE:
     """Mirror of reference src/models/neural_ode.jl:1-33 (struct + constructor) and :48-180 (call methods)."""
 
     def __init__(self, model, tspan, time_dep, regularize, solver="Tsit5", *, max_batch=512, max_attempts=128,
-                 cb_save_start=True, track_ctrl=True, track_initdt=True, col_tile=0, matrix_mode=None, engine=None, **kwargs):
+                 cb_save_start=True, track_ctrl=True, track_initdt=True, col_tile=0, matrix_mode=None, engine=None, tiled_tracking=(False, False),
+                 **kwargs):
         if engine not in ENGINES:
             raise ValueError(f"engine must be one of {ENGINES}; got {engine!r}")
         self.engine = engine
@@ -271,6 +276,9 @@ class TrackedNeuralODE:
             check_tiled_served(self)
         self._handles = {}
         self._coupling = None
+        self.tiled_tracking = (False, False)
+        if tuple(tiled_tracking) != (False, False):
+            self.set_tracking(*tiled_tracking)
         self.last_nfe = None
         self.last_times = None                            # save_everystep: the times of the states the last call returned
         self.last_tspan_bar = None
@@ -304,6 +312,7 @@ class TrackedNeuralODE:
         hs = self._handles.setdefault(key, [])
         for h in hs:
             if not h.busy:
+                self._apply_tracking(h)      # (a handle that was pending while set_tracking ran takes the layer's pair when it is next handed out)
                 return h
         if len(hs) >= MAX_HANDLES_PER_KEY:
             raise RuntimeError(f"{len(hs)} taped forwards of this layer are pending without a backward pass; each owns a tape of "
@@ -313,6 +322,7 @@ class TrackedNeuralODE:
             _lib.check(h.ptr, _lib.lib().rnde_node_set_matrix_mode(h.ptr, int(self.matrix_mode)))
         if self._coupling is not None:
             _lib.check(h.ptr, _lib.lib().rnde_node_set_coupling(h.ptr, self._coupling[0], self._coupling[1]))
+        self._apply_tracking(h)
         hs.append(h)
         return h
 
@@ -326,6 +336,36 @@ class TrackedNeuralODE:
         for hs in self._handles.values():
             for h in hs:
                 _lib.check(h.ptr, _lib.lib().rnde_node_set_coupling(h.ptr, comm, int(global_batch) if comm is not None else 0))
+
+    def set_tracking(self, track_ctrl, track_initdt=False):
+        """Which reverse sweep the taped forwards of an engine="tiled" layer get (include/rnde.h: rnde_node_set_tracking): (False, False) the
+        default, step sizes and times constants; (True, False) the step-size controller differentiated; (True, True) the initial step as well
+        -- the reference's gradient.  Applies at once to every handle that is not pending (the tape of a finished backward is released for it),
+        to a pending one -- a taped forward waiting for its backward keeps the setting it ran under -- when it is next handed out, and to every
+        handle created later."""
+        if self.engine != "tiled":
+            raise ValueError('TrackedNeuralODE.set_tracking: served with engine="tiled" only; the default engines take track_ctrl / track_initdt '
+                             "in the constructor")
+        ctrl, initdt = bool(track_ctrl), bool(track_initdt)
+        if initdt and not ctrl:
+            raise ValueError("TrackedNeuralODE.set_tracking: track_ctrl=False with track_initdt=True is not served: with the controller a constant "
+                             "the first proposed step reaches nothing (the settings are (False, False), (True, False) and (True, True))")
+        self.tiled_tracking = (ctrl, initdt)
+        for hs in self._handles.values():
+            for h in hs:
+                if not h.busy:
+                    self._apply_tracking(h)
+
+    def _apply_tracking(self, h):
+        """Bring a handle that is not pending to the layer's pair.  A handle whose backward has run still holds its tape on the library's side
+        (rnde_node_backward may be called again on it), and the library refuses to switch a handle that holds one: nothing of this layer waits
+        for that tape any more, so it is released first."""
+        if h.tracking == self.tiled_tracking:
+            return
+        L = _lib.lib()
+        _lib.check(h.ptr, L.rnde_node_release_tape(h.ptr))
+        _lib.check(h.ptr, L.rnde_node_set_tracking(h.ptr, int(self.tiled_tracking[0]), int(self.tiled_tracking[1])))
+        h.tracking = self.tiled_tracking
 
     @staticmethod
     def _saveat_times(saveat, ts):
