@@ -94,6 +94,21 @@ function tracking(h::Handle)
     st == 0 || error("rnde_node_tracking status $st")
     return c[] != 0, i[] != 0
 end
+# Saved points on a TILED handle (include/rnde.h: rnde_node_tiled_reserve_saveat): room for up to max_saveat save times per call switches
+# rnde_node_forward_saveat / _everystep on; 0 releases, and the handle refuses them again.  While the handle holds no tape.
+function reserve_saveat(h::Handle, max_saveat::Integer)
+    st = ccall((:rnde_node_tiled_reserve_saveat, LIB), Cint, (Ptr{Cvoid}, Int32), h.ptr, Int32(max_saveat))
+    st == 0 || error("rnde_node_tiled_reserve_saveat status $st: ", unsafe_string(ccall((:rnde_last_error, LIB), Cstring, (Ptr{Cvoid},), h.ptr)))
+    return h
+end
+# 0: a tiled handle without a capacity; -1: a handle of rnde_node_create
+saveat_capacity(h::Handle) = Int(ccall((:rnde_node_tiled_saveat_capacity, LIB), Int32, (Ptr{Cvoid},), h.ptr))
+# the next forward_saveat on this handle runs along `steps` (2 x n: proposed size, accepted != 0): rnde_debug_arm_replay, a parity instrument
+function arm_replay(h::Handle, steps::Matrix{Float32})
+    st = ccall((:rnde_debug_arm_replay, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Int32), h.ptr, steps, Int32(size(steps, 2)))
+    st == 0 || error("rnde_debug_arm_replay status $st")
+    return h
+end
 # (t, dt, dtp_in, EEst, accepted, q) of every attempt of the last solve, 6 x n (rnde_node_attempts_ext)
 function attempts_ext(h::Handle)
     n = Ref{Int32}(0)

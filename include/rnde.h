@@ -133,8 +133,11 @@ void        rnde_node_destroy(rnde_node* h);
  *   and tspan_bar is the real cotangent.  With regularize = RNDE_REG_ERR the constant-step gradient of sum EEst * dt is 40-94 % away from
  *   the tracked one.
  * Calls served on such a handle: rnde_node_forward, _forward_replay, _backward, _release_tape, _steps, _attempts_ext, _set_tracking,
- *   _tracking, _timing (solve, reverse sweep, tile reduction; always recorded), _last_attempts, rnde_debug_feval, rnde_node_forward_host / _backward_host, rnde_node_destroy.
- * Refused with RNDE_ERR_BAD_ARG and a message naming the entry: rnde_node_forward_saveat / _everystep, rnde_debug_attempt, rnde_bench_*,
+ *   _tracking, _timing (solve, reverse sweep, tile reduction; always recorded), _last_attempts, rnde_debug_feval, rnde_node_forward_host / _backward_host, rnde_node_destroy,
+ *   rnde_node_tiled_reserve_saveat / _saveat_capacity; and, once a saveat capacity is reserved (below), rnde_node_forward_saveat /
+ *   _everystep with the D x n x B backward that follows them, and rnde_debug_arm_replay.
+ * Refused with RNDE_ERR_BAD_ARG and a message naming the entry: rnde_node_forward_saveat / _everystep on a handle without a saveat capacity
+ *   (every fresh handle), rnde_debug_attempt, rnde_bench_*,
  *   rnde_node_set_coupling, rnde_node_set_matrix_mode(h, 1), rnde_node_classifier_grad, rnde_node_backward_async; a tape pool
  *   (rnde_tapes_create) holds rnde_node_create instances only.  A meeting of the solve or of the tracked reverse sweep that times out is
  *   RNDE_ERR_HIP with a message that says which; nothing falls back to other arithmetic. */
@@ -153,6 +156,23 @@ int64_t     rnde_node_tiled_lds_bytes(const rnde_node_config* cfg);
  * rnde_node_create: its config's flags). */
 rnde_status rnde_node_set_tracking(rnde_node* h, int32_t track_ctrl, int32_t track_initdt);
 rnde_status rnde_node_tracking(const rnde_node* h, int32_t* ctrl_out, int32_t* initdt_out);
+
+/* Saved points on a TILED handle, switched on after creation by a capacity: room for up to max_saveat save times per call (the device copy
+ * of the times, the tape's own copy, one range of save indices per attempt for the reverse sweep).  On a handle with a capacity
+ * rnde_node_forward_saveat is served as described below -- times increasing inside [t0, t1], a first time equal to t0 yields x, output
+ * D x n_saveat x B -- by the one-launch solve: behind the controller of an accepted attempt every tile writes the states of that step's
+ * save times (unew itself at the step's end, the Tsit5 dense output inside it); the times never enter the controller, so the attempts are
+ * the end-state solve's bit for bit.  rnde_node_forward_everystep runs through it twice (its own description); rnde_node_backward after a
+ * taped saving forward takes u_bar_dev D x n x B and runs the sweep the tape's tracking setting asks for: (0, 0) with step sizes and times
+ * constants and tspan_bar = (0, 0), tracked with the cotangents of theta = (ts - t) / dt in the attempt's sums and the real tspan_bar.
+ * n_saveat (or the step ends of _everystep) above the capacity: RNDE_ERR_BAD_ARG naming both numbers.  End-state calls on the handle are
+ * the kernels and the bits of a handle that never reserved.  max_saveat = 0 releases: the handle refuses saving calls again exactly as a
+ * fresh one.  Refused by name with RNDE_ERR_BAD_ARG, before any launch: a handle of rnde_node_create (its engines need no reservation), a
+ * handle that holds a tape, max_saveat < 0 or above cfg.max_attempts + 1, and -- max_batch above 512 -- a device that does not hold
+ * max_batch / 16 workgroups of the saving kernels at once.  rnde_node_tiled_saveat_capacity: the capacity, 0 for a tiled handle without
+ * one, -1 for NULL or a handle of rnde_node_create. */
+rnde_status rnde_node_tiled_reserve_saveat(rnde_node* h, int32_t max_saveat);
+int32_t     rnde_node_tiled_saveat_capacity(const rnde_node* h);
 
 /* Forward solve on [t0,t1].  u_out_dev: D x B.  saveval_host (may be NULL when regularize==0):
  * room for max_attempts+1 floats.  keep_tape != 0 records what rnde_node_backward needs.
@@ -192,6 +212,12 @@ rnde_status rnde_node_forward_replay(rnde_node* h, const float* x_dev, const flo
                                      float t0, float t1, const float* steps_host, int32_t n_steps,
                                      float* u_out_dev, int64_t* nfe_out, float* saveval_host,
                                      int32_t* n_saveval_out, int32_t keep_tape, void* stream);
+
+/* Parity instrument for saved points: the NEXT rnde_node_forward_saveat on this handle runs along the given sequence of attempts (steps_host:
+ * n_steps pairs as for rnde_node_forward_replay, copied), then the handle is back to its controller; n_steps = 0 disarms.  Every engine: the
+ * solves read the handle's replay state whether they save or not, and rnde_node_forward_replay, which sets it for its own call only, has no
+ * saving form.  Not a reference entry point. */
+rnde_status rnde_debug_arm_replay(rnde_node* h, const float* steps_host, int32_t n_steps);
 
 /* Reverse pass of the last recorded forward.  u_bar_dev: D x B cotangent of u_out;
  * saveval_bar_host: one cotangent per saveval element (NULL = zeros).

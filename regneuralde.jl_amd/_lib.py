@@ -91,6 +91,10 @@ def lib():
     L.rnde_node_attempts_ext.argtypes = [vp, fp, i32, i32p]
     L.rnde_node_set_tracking.argtypes = [vp, i32, i32]
     L.rnde_node_tracking.argtypes = [vp, i32p, i32p]
+    L.rnde_node_tiled_reserve_saveat.argtypes = [vp, i32]
+    L.rnde_node_tiled_saveat_capacity.argtypes = [vp]
+    L.rnde_node_tiled_saveat_capacity.restype = i32
+    L.rnde_debug_arm_replay.argtypes = [vp, fp, i32]
     L.rnde_debug_feval.argtypes = [vp, vp, vp, i32, f, vp, vp]
     L.rnde_debug_attempt.argtypes = [vp, vp, vp, vp, i32, f, f, vp, vp, fp, vp]
     L.rnde_bench_attempt.argtypes = [vp, vp, vp, i32, i32, fp, vp]
@@ -230,7 +234,8 @@ EXPORTS = ["rnde_version", "rnde_last_error", "rnde_param_count", "rnde_node_cre
            "rnde_ffjord_forward_kinetic_replay", "rnde_ffjord_backward_kinetic", "rnde_ffjord_debug_feval_kinetic", "rnde_ffjord_step_log",
            "rnde_ffjord_chain_param_count", "rnde_ffjord_create_chain", "rnde_ffjord_forward_exact", "rnde_ffjord_forward_exact_replay",
            "rnde_ffjord_set_track_ctrl", "rnde_ffjord_track_ctrl",
-           "rnde_node_create_tiled", "rnde_node_tiled_lds_bytes", "rnde_node_set_tracking", "rnde_node_tracking", "rnde_node_attempts_ext"]
+           "rnde_node_create_tiled", "rnde_node_tiled_lds_bytes", "rnde_node_set_tracking", "rnde_node_tracking", "rnde_node_attempts_ext",
+           "rnde_node_tiled_reserve_saveat", "rnde_node_tiled_saveat_capacity", "rnde_debug_arm_replay"]
 
 
 def check(h, status):

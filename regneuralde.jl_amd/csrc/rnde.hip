@@ -715,7 +715,20 @@ extern "C" rnde_status rnde_node_forward_saveat(rnde_node* h, const float* x_dev
                                                 int64_t* nfe_out, float* saveval_host, int32_t* n_saveval_out,
                                                 int32_t keep_tape, void* stream) {
     if (!h || !saveat_host || n_saveat < 1 || !u_saved_dev) return RNDE_ERR_BAD_ARG;
-    return forward_impl(h, x_dev, p_dev, B, t0, t1, nullptr, saveat_host, n_saveat, u_saved_dev, nfe_out, saveval_host, n_saveval_out, keep_tape, stream);
+    // every engine's solve reads the replay state of the handle, a saving solve included; rnde_node_forward_replay sets it for its own call and
+    // clears it, so no saving call ever meets it -- except the one behind rnde_debug_arm_replay (the parity instrument for saved points)
+    const bool armed = !h->replay_armed.empty();
+    if (armed) { h->replay_host = h->replay_armed.data(); h->n_replay = (int)(h->replay_armed.size() / 2); }
+    const rnde_status st = forward_impl(h, x_dev, p_dev, B, t0, t1, nullptr, saveat_host, n_saveat, u_saved_dev, nfe_out, saveval_host, n_saveval_out, keep_tape, stream);
+    if (armed) { h->replay_host = nullptr; h->n_replay = 0; h->replay_armed.clear(); }
+    return st;
+}
+
+extern "C" rnde_status rnde_debug_arm_replay(rnde_node* h, const float* steps_host, int32_t n_steps) {
+    if (!h || n_steps < 0 || (n_steps > 0 && !steps_host)) return RNDE_ERR_BAD_ARG;
+    if (n_steps > h->cfg.max_attempts) { h->err = "replay: more steps than max_attempts"; return RNDE_ERR_BAD_ARG; }
+    h->replay_armed.assign(steps_host, steps_host + 2 * (size_t)n_steps);
+    return RNDE_OK;
 }
 
 static rnde_status forward_core(rnde_node* h, const float* x_dev, const float* p_dev, int32_t B, float t0, float t1,
@@ -1065,7 +1078,8 @@ extern "C" rnde_status rnde_node_forward_everystep(rnde_node* h, const float* x_
                                                    float* sol_out_dev, int32_t capacity, float* t_host_out, int32_t* n_out, int64_t* nfe_out,
                                                    float* saveval_host, int32_t* n_saveval_out, int32_t keep_tape, void* stream) {
     if (!h || !n_out || !sol_out_dev || capacity < 1) return RNDE_ERR_BAD_ARG;
-    RNDE_TILED_REFUSE(h, "rnde_node_forward_everystep is not served (the end state only; save_everystep runs on the engines of rnde_node_create)");
+    if (rnde_node_tiled_saveat_capacity(h) == 0)      // (a tiled handle without a saveat capacity: rnde_node_tiled_reserve_saveat switches saving on)
+        RNDE_TILED_REFUSE(h, "rnde_node_forward_everystep is not served (the end state only; save_everystep runs on the engines of rnde_node_create)");
     rnde_status st = forward_impl(h, x_dev, p_dev, B, t0, t1, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, stream);
     if (st != RNDE_OK) return st;
     std::vector<float> times;

@@ -108,7 +108,13 @@ __device__ __forceinline__ float nt_vjp(const FcGeo& G, const NtLds& L, float t,
 }
 
 // TRK: the tracked sweep (the header); launched as the solve is (MeetRes::grid), one loop iteration per attempt, then the initial step.
-template <bool TRK = false>
+// SAVE: a saving tape.  The only outputs are the saved points: the running uprev cotangent starts at zero, and behind the seeds of an
+// accepted attempt the cotangent of each of its save indices (Q.rng, formed on the host by save_plan) enters -- at the step's end into the
+// unew cotangent, inside the step into the uprev cotangent and, times dt b_j(theta), into every stage cotangent (the reverse of the dense
+// output, rnde_bchain.h).  TRK adds the theta terms to the attempt's sums: -<u_s-bar, sum_j b_j'(theta) k_j> to the t sum and theta times it
+// to the dt sum (theta = (ts - t) / dt); the dt b_j part of the dt cotangent is in sum <k_j, k_j-bar> already.  The meeting carries them:
+// no meeting is added.  The cotangent of index 0 under save_start goes straight to x-bar.
+template <bool TRK = false, bool SAVE = false>
 __global__ __launch_bounds__(kFtThreads) void rnde_node_tile_reverse_kernel(const NodeTileRevParams Q) {
     extern __shared__ float nt_smem[];
     const FcGeo& G = Q.G;
@@ -132,7 +138,7 @@ __global__ __launch_bounds__(kFtThreads) void rnde_node_tile_reverse_kernel(cons
     const size_t RB = (size_t)D * Bp;
     for (int idx = tid; idx < nel; idx += kFtThreads) {
         const int r = idx >> 4, col = col0 + (idx & 15);
-        UB[idx] = col < Q.B ? Q.u_bar[(size_t)col * D + r] : 0.f;
+        UB[idx] = (!SAVE && col < Q.B) ? Q.u_bar[(size_t)col * D + r] : 0.f;
     }
     __syncthreads();      // pacc and L.X are next touched by other threads (the entries' owner lanes, the stage loop)
     const double N = (double)D * (double)Q.B;
@@ -163,6 +169,33 @@ __global__ __launch_bounds__(kFtThreads) void rnde_node_tile_reverse_kernel(cons
             UBn[idx] = 0.f;
             Yb[idx] = accepted ? UB[idx] : 0.f;               // cotangent of unew = stage-7 input (a rejected attempt has none)
         }
+        float pS = 0.f, ptau = 0.f, pctau = 0.f;              // TRK: this thread's shares of the three sums of the dt cotangent
+        if constexpr (SAVE) {         // ---- the saved points of this step (every array below is touched by its entry's owner thread alone) ----
+            const SaveRange rg = Q.rng[n];
+            for (int si = rg.lo; si < rg.hi; ++si) {
+                const float ts = Q.sv_t[si], th = (ts - t) / dt;
+                const bool at_end = ts == t + dt;
+                float bw[7], dbw[7];
+                dense_weights(th, bw);
+                if constexpr (TRK) dense_weights_deriv(th, dbw);
+                for (int idx = tid; idx < nel; idx += kFtThreads) {
+                    const int r = idx >> 4, col = col0 + (idx & 15);
+                    if (col >= Q.B) continue;
+                    const float ub = Q.u_bar[((size_t)col * Q.nsave + si) * D + r];
+                    if (at_end) { Yb[idx] += ub; continue; }
+                    UBn[idx] += ub;
+#pragma unroll
+                    for (int j = 0; j < 7; ++j) Kb(j)[idx] += dt * bw[j] * ub;      // (unrolled: bw, dbw stay in registers)
+                    if constexpr (TRK) {
+                        float dacc = dbw[0] * Ks(0)[idx];
+#pragma unroll
+                        for (int j = 1; j < 7; ++j) dacc += dbw[j] * Ks(j)[idx];
+                        const float v = -ub * dacc;
+                        ptau += v; pctau = fmaf(th, v, pctau);
+                    }
+                }
+            }
+        }
         // ---- TRK: the scalar reverse of the controller (FfAttRec); dtp' = t1 - t0 under F_DTMAXCLAMP ----
         double eb = 0.0, dtb_pre = 0.0, qoldb_in = 0.0;
         if constexpr (TRK) {
@@ -189,7 +222,6 @@ __global__ __launch_bounds__(kFtThreads) void rnde_node_tile_reverse_kernel(cons
             }
         }
         __syncthreads();
-        float pS = 0.f, ptau = 0.f, pctau = 0.f;              // TRK: this thread's shares of the three sums of the dt cotangent
         // ---- B: the stages, last to first ----
         for (int s = 6; s >= 0; --s) {
             if (s != 6) {
@@ -285,7 +317,11 @@ __global__ __launch_bounds__(kFtThreads) void rnde_node_tile_reverse_kernel(cons
     if (Q.x_bar)
         for (int idx = tid; idx < nel; idx += kFtThreads) {
             const int r = idx >> 4, col = col0 + (idx & 15);
-            if (col < Q.B) Q.x_bar[(size_t)col * D + r] = UB[idx];
+            if (col >= Q.B) continue;
+            float v = UB[idx];
+            if constexpr (SAVE)
+                if (Q.save_t0) v += Q.u_bar[((size_t)col * Q.nsave) * D + r];
+            Q.x_bar[(size_t)col * D + r] = v;
         }
 }
 

@@ -79,6 +79,7 @@ struct rnde_node {
     float* cg_ws = nullptr; size_t cg_ws_floats = 0; std::vector<float> cg_sv;
     float* sv_t_dev = nullptr; size_t sv_cap = 0; std::vector<float> saveat;   // saveat times of the last forward
     float* replay_dev = nullptr; size_t replay_cap = 0; const float* replay_host = nullptr; int n_replay = 0;   // rnde_node_forward_replay (set for one forward)
+    std::vector<float> replay_armed;   // rnde_debug_arm_replay: the sequence the next rnde_node_forward_saveat runs along (then cleared)
     // persistent attempt kernel (rnde_stage_persist.h): 1 = in use, 0 = off (RNDE_PERSIST=0), -1 = disabled after a failure
     int wgrad_side_pct = 30, stage_generic = 0;
     int persist_clean = 0, persist_retry_after = 8, persist_fallbacks = 0;   // non-sticky fallback: clean multi-launch solves since the last failure, when to try again   // fixed at creation (config fields; RNDE_* environment overrides are read once, there)

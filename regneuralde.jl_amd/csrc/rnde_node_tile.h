@@ -21,6 +21,7 @@
 #include "rnde_tile_meet.h"        // tile_meet; rnde_ffjordt.h, rnde_meet.h
 #include "rnde_ffjordc.h"          // FcGeo, fc_geo, FcDyn::load_params, fc_chain
 #include "rnde_track_rec.h"        // FfAttRec; the initial-step rule's scalar reverse
+#include "rnde_save_plan.h"        // SaveRange
 
 namespace rnde {
 
@@ -92,9 +93,19 @@ struct NodeTileRevParams {
     Meet meet;                        // three rows per meeting: one per attempt, then two for the initial step
     unsigned* xcc;                    // [ntiles] (one-XCD meeting: the host checks they agree)
     int xcd_slot;
+    // a saving tape (rnde_node_tile_reverse_kernel<*, true>) alone: u_bar is then D x nsave x B, the cotangents of the saved states
+    const float* sv_t;                // [nsave]: the tape's own copy of the save times
+    const SaveRange* rng;             // the save indices of record n of the sweep's walk: [n_att] by attempt (tracked), [n_acc] by accepted step
+    int nsave, save_t0;               // save_t0: index 0 is the start (sv_t[0] == t0), its cotangent goes straight to x_bar
 };
 
 // The whole adaptive solve in one launch (also the replay along F.replay).
+// SAVE (a handle with a saveat capacity, F.nsave > 0): behind the controller of an accepted attempt every tile writes u(ts) for the save
+// indices [S.next_save, Sn.next_save) of the step -- unew itself at the step's end, uprev + dt sum_j b_j(theta) k_j inside it (the Tsit5
+// dense output, dense_weights; the arithmetic of chain_dense_points) -- into F.sv_out (D x nsave x B, caller layout).  Every tile holds
+// the same controller bits, so the range is uniform: no meeting and no barrier beyond the loop's.  The save times never enter the
+// controller: a saving solve takes the end-state solve's attempts bit for bit.  Without SAVE the kernel is the end-state solve unchanged.
+template <bool SAVE = false>
 __global__ __launch_bounds__(kFtThreads) void rnde_node_tile_solve_kernel(const NodeTileSolveParams Q) {
     extern __shared__ float nt_smem[];
     if (!Q.meet.global && (int)(blockIdx.x & 7) != Q.xcd_slot) return;
@@ -166,6 +177,13 @@ __global__ __launch_bounds__(kFtThreads) void rnde_node_tile_solve_kernel(const 
     __threadfence_block();
     StepState S = advance_state(P, 0, lane, tid == 0, tile == 0 ? &P.ctl[0] : Q.ctl_t + tile);
     int n_acc = 0;
+    if constexpr (SAVE) {
+        if (S.next_save > 0)                                   // save_start: sv_t[0] == t0, index 0 is x itself
+            for (int idx = tid; idx < nel; idx += kFtThreads) {
+                const int r = idx >> 4, c = idx & 15;
+                if (col0 + c < B) P.sv_out[((size_t)(col0 + c) * P.nsave) * D + r] = U[(size_t)r * Bp + c];
+            }
+    }
     for (int n = 0; !S.done; ++n) {
         const float t = S.t;
         const float dt = (P.t1 - S.t < S.dtp) ? (P.t1 - S.t) : S.dtp;
@@ -195,6 +213,27 @@ __global__ __launch_bounds__(kFtThreads) void rnde_node_tile_solve_kernel(const 
         if (!tile_meet(Q.meet, L.red, 2 + n, part, 0.f, 0.f, xs, tile, tid)) return;
         const float none[4] = {0.f, 0.f, 0.f, 0.f};
         const StepState Sn = advance_state_t<true>(P, n + 1, lane, lead, &P.ctl[(n + 1) & 1], none, S, xs);
+        if constexpr (SAVE) {
+            for (int si = S.next_save; si < Sn.next_save; ++si) {      // (a rejected attempt leaves next_save alone: an empty range)
+                const float ts = P.sv_t[si];
+                const bool at_end = ts == Sn.t;
+                float bw[7];
+                dense_weights((ts - t) / dt, bw);
+                for (int idx = tid; idx < nel; idx += kFtThreads) {
+                    const int r = idx >> 4, c = idx & 15;
+                    if (col0 + c >= B) continue;
+                    const size_t ix = (size_t)r * Bp + c;
+                    float o = UN[ix];
+                    if (!at_end) {
+                        float acc = bw[0] * K(0)[ix];
+#pragma unroll
+                        for (int j = 1; j < 7; ++j) acc += bw[j] * K(j)[ix];      // (unrolled: bw stays in registers)
+                        o = U[ix] + dt * acc;
+                    }
+                    P.sv_out[((size_t)(col0 + c) * P.nsave + si) * D + r] = o;
+                }
+            }
+        }
         if (Sn.n_acc > S.n_acc) {                          // accepted: tape uprev, then unew -> uprev, k7 -> k1
             for (int idx = tid; idx < nel; idx += kFtThreads) {
                 const int r = idx >> 4, c = idx & 15;

@@ -2,6 +2,8 @@
 // whose solve, reverse sweeps (constant-step and tracked: rnde_node_set_tracking) and feval are the kernels of rnde_node_tile.h /
 // rnde_bnode_tile.h.  The public rnde_node_* entries (rnde.hip, rnde_reverse.hip) hand a handle of this engine to the node_tiled_* functions
 // below, or refuse it by name.
+// Saved points (rnde_node_forward_saveat / _everystep, the D x n x B backward) are served on a handle with a saveat capacity
+// (rnde_node_tiled_reserve_saveat) by the SAVE instantiations of the same kernels; a handle without one refuses them as before.
 #include "rnde_node.h"
 #include "rnde_bnode_tile.h"
 
@@ -31,6 +33,13 @@ struct rnde_node_tiled {
     float tp_t0 = 0.f;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     bool ev_fwd = false, ev_bwd = false;
+    // rnde_node_tiled_reserve_saveat: room for up to sv_cap save times per call (0: saving calls are refused, as on a fresh handle)
+    int sv_cap = 0;
+    float* sv_t = nullptr;           // [sv_cap]: the save times of the running solve
+    float* tp_sv_t = nullptr;        // [sv_cap]: the tape's own copy (an untaped saving probe between a taped forward and its backward leaves it alone)
+    SaveRange* sv_rng = nullptr;     // [max_attempts]: the save indices of each record the reverse sweep walks (save_plan, formed on the host)
+    std::vector<float> h_sv, tp_saveat;      // the running solve's times (the source of an asynchronous copy); the taped forward's (empty: an end-state tape)
+    std::vector<SaveRange> h_rng;            // (likewise a copy's source)
 };
 
 
@@ -88,7 +97,8 @@ void node_tiled_destroy(rnde_node* h) {
     rnde_node_tiled* T = h->tiled;
     if (!T) return;
     for (void* p : {(void*)T->ws, (void*)T->tape, (void*)T->norm, (void*)T->replay, (void*)T->rws, (void*)T->pacc, (void*)T->pcopy, (void*)T->ctl,
-                    (void*)T->ctl_t, (void*)T->meta, (void*)T->initrec_t, (void*)T->rec, (void*)T->att, (void*)T->tsb})
+                    (void*)T->ctl_t, (void*)T->meta, (void*)T->initrec_t, (void*)T->rec, (void*)T->att, (void*)T->tsb, (void*)T->sv_t, (void*)T->tp_sv_t,
+                    (void*)T->sv_rng})
         if (p) (void)hipFree(p);
     T->meet.destroy();
     if (T->h_tsb) (void)hipHostFree(T->h_tsb);
@@ -134,12 +144,12 @@ extern "C" rnde_status rnde_node_create_tiled(const rnde_node_config* c, rnde_no
     if ((e = hipMalloc(&T->rec, MA * sizeof(NtStepRec))) != hipSuccess) return fail(e);
     if ((e = hipHostMalloc((void**)&h->h_meta, MA * sizeof(StepMeta))) != hipSuccess) return fail(e);
     if ((e = T->meet.create(MA + 4, 3, kMwMeetMax)) != hipSuccess) return fail(e);
-    for (const void* k : {(const void*)rnde_node_tile_solve_kernel, (const void*)rnde_node_tile_reverse_kernel<false>, (const void*)rnde_node_tile_feval_kernel})
+    for (const void* k : {(const void*)rnde_node_tile_solve_kernel<false>, (const void*)rnde_node_tile_reverse_kernel<false>, (const void*)rnde_node_tile_feval_kernel})
         if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)T->lds_bytes)) != hipSuccess) return fail(e);
     if (T->ntiles_max > kMeetXcdCus) {      // the agent-scope meeting: every tile of the largest batch must be resident at once
         int per_cu = 0;
         hipDeviceProp_t prop;
-        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rnde_node_tile_solve_kernel, kFtThreads, T->lds_bytes)) != hipSuccess) return fail(e);
+        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rnde_node_tile_solve_kernel<false>, kFtThreads, T->lds_bytes)) != hipSuccess) return fail(e);
         if ((e = hipGetDeviceProperties(&prop, c->device)) != hipSuccess) return fail(e);
         if ((long long)per_cu * prop.multiProcessorCount < T->ntiles_max) {
             rnde_set_create_error("TrackedNeuralODE tiled engine: max_batch needs " + std::to_string(T->ntiles_max) + " resident tiles for the meeting, the device holds " +
@@ -158,12 +168,25 @@ rnde_status node_tiled_forward(rnde_node* h, const float* x_dev, const float* p_
                                int32_t* n_saveval_out, int32_t keep_tape, void* stream) {
     rnde_node_tiled* T = h->tiled;
     hipStream_t s = (hipStream_t)stream;
-    if (saveat_host || n_saveat > 0 || sv_out_dev) {
+    const bool saving = saveat_host || n_saveat > 0 || sv_out_dev;
+    if (saving && T->sv_cap == 0) {      // (a handle without a saveat capacity: rnde_node_tiled_reserve_saveat switches saving on)
         h->err = "TrackedNeuralODE tiled engine: rnde_node_forward_saveat is not served (the end state only; saveat runs on the engines of rnde_node_create)";
         return RNDE_ERR_BAD_ARG;
     }
     if (!x_dev || !p_dev || B < 1 || B > h->cfg.max_batch) { h->err = "bad argument (B must be 1..max_batch)"; return RNDE_ERR_BAD_ARG; }
     if (!(t1 > t0)) { h->err = "bad B or tspan"; return RNDE_ERR_BAD_ARG; }
+    if (saving) {
+        if (!saveat_host || n_saveat < 1 || !sv_out_dev) { h->err = "TrackedNeuralODE tiled engine: rnde_node_forward_saveat: saveat_host, n_saveat >= 1 and u_saved_dev are required"; return RNDE_ERR_BAD_ARG; }
+        if (n_saveat > T->sv_cap) {
+            h->err = "TrackedNeuralODE tiled engine: rnde_node_forward_saveat: n_saveat = " + std::to_string(n_saveat) + " is above the handle's saveat capacity of " +
+                     std::to_string(T->sv_cap) + " (rnde_node_tiled_reserve_saveat)";
+            return RNDE_ERR_BAD_ARG;
+        }
+        for (int i = 0; i < n_saveat; ++i)
+            if (!(saveat_host[i] >= t0 && saveat_host[i] <= t1) || (i > 0 && !(saveat_host[i] > saveat_host[i - 1]))) {
+                h->err = "saveat must be increasing and inside [t0, t1]"; return RNDE_ERR_BAD_ARG;
+            }
+    }
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const float* steps_host = h->replay_host;
     const int n_steps = h->n_replay;
@@ -173,12 +196,18 @@ rnde_status node_tiled_forward(rnde_node* h, const float* x_dev, const float* p_
         HIPCHK(h, hipMemcpyAsync(T->pcopy, p_dev, (size_t)h->P * 4, hipMemcpyDeviceToDevice, s));      // (the tape keeps no caller pointer)
     }
     if (steps_host) HIPCHK(h, hipMemcpyAsync(T->replay, steps_host, (size_t)2 * n_steps * 4, hipMemcpyHostToDevice, s));
+    if (saving) {
+        T->h_sv.assign(saveat_host, saveat_host + n_saveat);
+        HIPCHK(h, hipMemcpyAsync(T->sv_t, T->h_sv.data(), (size_t)n_saveat * 4, hipMemcpyHostToDevice, s));
+        if (taped) HIPCHK(h, hipMemcpyAsync(T->tp_sv_t, T->h_sv.data(), (size_t)n_saveat * 4, hipMemcpyHostToDevice, s));
+    }
     NodeTileSolveParams Q{};
     StepParams& P = Q.F;
     P.x = x_dev; P.D = h->D; P.B = B; P.Bn = B; P.Bpad = T->Bp; P.nwg = 1;
     P.ctl = T->ctl; P.ctl_final = T->ctl + 2; P.meta = T->meta; P.initrec = T->initrec_t; P.initpart = T->norm;
     P.reltol = h->cfg.reltol; P.abstol = h->cfg.abstol; P.t0 = t0; P.t1 = t1;
     P.tape = 1; P.max_attempts = h->cfg.max_attempts; P.reg_kind = 0; P.nsave = 0;
+    if (saving) { P.sv_t = T->sv_t; P.nsave = n_saveat; P.sv_out = sv_out_dev; }
     P.replay = steps_host ? T->replay : nullptr; P.n_replay = steps_host ? n_steps : 0;
     P.beta1 = kBeta1; P.beta2 = kBeta2; P.rk_order = 5.f;
     const int nt = (B + 15) / 16;
@@ -187,7 +216,8 @@ rnde_status node_tiled_forward(rnde_node* h, const float* x_dev, const float* p_
     Q.G = T->G; Q.p = p_dev; Q.x = x_dev; Q.ws = T->ws; Q.tape = taped ? T->tape : nullptr; Q.u_out = u_out_dev; Q.norm = T->norm;
     Q.initrec_t = T->initrec_t; Q.ctl_t = T->ctl_t; Q.meet = meet; Q.xcc = T->meet.xcc; Q.xcd_slot = T->meet.slot; Q.Bp = T->Bp;
     HIPCHK(h, hipEventRecord(T->ev[0], s));
-    hipLaunchKernelGGL(rnde_node_tile_solve_kernel, dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
+    if (saving) hipLaunchKernelGGL(rnde_node_tile_solve_kernel<true>, dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
+    else hipLaunchKernelGGL(rnde_node_tile_solve_kernel<false>, dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(T->ev[1], s));
     T->ev_fwd = true;
@@ -226,6 +256,7 @@ rnde_status node_tiled_forward(rnde_node* h, const float* x_dev, const float* p_
         T->tp_meta.assign(h->h_meta, h->h_meta + fin.n_att);
         T->tp_n_att = fin.n_att; T->tp_n_acc = fin.n_acc; T->tp_B = B;
         T->tp_track_ctrl = T->track_ctrl; T->tp_track_initdt = T->track_initdt; T->tp_t0 = t0;
+        if (saving) T->tp_saveat = T->h_sv; else T->tp_saveat.clear();
         if (T->track_initdt) HIPCHK(h, hipMemcpy(&T->tp_init, T->initrec_t, sizeof(InitRec), hipMemcpyDeviceToHost));      // (every tile's record is tile 0's)
         h->have_tape = true;
     }
@@ -249,6 +280,12 @@ static rnde_status node_tiled_backward_tracked(rnde_node* h, const std::vector<N
     }
     while (!att.empty() && !(att.back().flags & F_ACCEPT)) att.pop_back();      // (attempts behind the last accepted one reach nothing)
     if (!att.empty()) HIPCHK(h, hipMemcpyAsync(T->att, att.data(), att.size() * sizeof(FfAttRec), hipMemcpyHostToDevice, s));
+    const bool saving = !T->tp_saveat.empty();
+    if (saving) {                               // one range per attempt (the trimmed ones covered nothing)
+        T->h_rng.resize(T->tp_n_att + 1);
+        save_plan(T->tp_saveat.data(), (int)T->tp_saveat.size(), T->tp_t0, T->tp_meta.data(), T->tp_n_att, F_ACCEPT, T->h_rng.data());
+        if (!att.empty()) HIPCHK(h, hipMemcpyAsync(T->sv_rng, T->h_rng.data(), att.size() * sizeof(SaveRange), hipMemcpyHostToDevice, s));
+    }
     const int nt = (T->tp_B + 15) / 16;
     const Meet meet = T->meet.begin(nt, true, s);      // a new epoch re-arms the rows the solve used
     HIPCHK(h, T->meet.err);
@@ -257,8 +294,10 @@ static rnde_status node_tiled_backward_tracked(rnde_node* h, const std::vector<N
     Q.n_acc = T->tp_n_acc; Q.B = T->tp_B; Q.Bp = T->Bp; Q.reltol = h->cfg.reltol; Q.abstol = h->cfg.abstol;
     Q.att = T->att; Q.n_att = (int)att.size(); Q.track_initdt = T->tp_track_initdt ? 1 : 0; Q.init = T->tp_init; Q.t0 = T->tp_t0; Q.tspan_out = T->tsb;
     Q.meet = meet; Q.xcc = T->meet.xcc; Q.xcd_slot = T->meet.slot;
+    if (saving) { Q.sv_t = T->tp_sv_t; Q.rng = T->sv_rng; Q.nsave = (int)T->tp_saveat.size(); Q.save_t0 = T->tp_saveat[0] == T->tp_t0 ? 1 : 0; }
     HIPCHK(h, hipEventRecord(T->ev[2], s));
-    hipLaunchKernelGGL(rnde_node_tile_reverse_kernel<true>, dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
+    if (saving) hipLaunchKernelGGL((rnde_node_tile_reverse_kernel<true, true>), dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
+    else hipLaunchKernelGGL((rnde_node_tile_reverse_kernel<true, false>), dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(T->ev[3], s));
     hipLaunchKernelGGL(rnde_node_tile_reduce_kernel, dim3((h->P + 255) / 256), dim3(256), 0, s, (const float*)T->pacc, h->P, nt, p_bar_dev);
@@ -308,7 +347,7 @@ extern "C" rnde_status rnde_node_set_tracking(rnde_node* h, int32_t track_ctrl, 
     }
     if (track_ctrl && !T->att) {
         HIPCHK(h, hipSetDevice(h->cfg.device));
-        HIPCHK(h, hipFuncSetAttribute((const void*)rnde_node_tile_reverse_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)T->lds_bytes));
+        HIPCHK(h, hipFuncSetAttribute((const void*)rnde_node_tile_reverse_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)T->lds_bytes));
         if (T->ntiles_max > kMeetXcdCus) {      // the agent-scope meeting: every tile of the largest batch resident at once, on the tracked kernel's own footprint
             int per_cu = 0;
             hipDeviceProp_t prop;
@@ -338,6 +377,56 @@ extern "C" rnde_status rnde_node_tracking(const rnde_node* h, int32_t* ctrl_out,
     return RNDE_OK;
 }
 
+// ---- rnde_node_tiled_reserve_saveat: the per-handle switch of the saving calls (a capacity, which the engine needs anyway) ----
+extern "C" int32_t rnde_node_tiled_saveat_capacity(const rnde_node* h) { return (h && h->engine == 4 && h->tiled) ? h->tiled->sv_cap : -1; }
+
+extern "C" rnde_status rnde_node_tiled_reserve_saveat(rnde_node* h, int32_t max_saveat) {
+    if (!h) return RNDE_ERR_BAD_ARG;
+    if (h->engine != 4) {
+        h->err = "rnde_node_tiled_reserve_saveat: served on handles of rnde_node_create_tiled; the engines of rnde_node_create serve "
+                 "rnde_node_forward_saveat / _everystep without a reservation";
+        return RNDE_ERR_BAD_ARG;
+    }
+    rnde_node_tiled* T = h->tiled;
+    if (h->have_tape) {
+        h->err = "TrackedNeuralODE tiled engine: rnde_node_tiled_reserve_saveat: the handle holds a tape (a taped forward waiting for its backward, which "
+                 "may own save times); reserve before the forward or after rnde_node_release_tape";
+        return RNDE_ERR_BAD_ARG;
+    }
+    if (max_saveat < 0 || max_saveat > h->cfg.max_attempts + 1) {
+        h->err = "TrackedNeuralODE tiled engine: rnde_node_tiled_reserve_saveat: max_saveat = " + std::to_string(max_saveat) + " is outside 0.." +
+                 std::to_string(h->cfg.max_attempts + 1) + " (max_attempts + 1: what save_everystep with save_start can need)";
+        return RNDE_ERR_BAD_ARG;
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    T->sv_cap = 0;                              // (set last: a call that failed half way leaves a handle that refuses, and is simply made again)
+    T->tp_saveat.clear();
+    for (void** p : {(void**)&T->sv_t, (void**)&T->tp_sv_t, (void**)&T->sv_rng}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    if (max_saveat == 0) return RNDE_OK;
+    const void* kernels[3] = {(const void*)rnde_node_tile_solve_kernel<true>, (const void*)rnde_node_tile_reverse_kernel<false, true>,
+                              (const void*)rnde_node_tile_reverse_kernel<true, true>};
+    for (const void* k : kernels) HIPCHK(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)T->lds_bytes));
+    if (T->ntiles_max > kMeetXcdCus) {          // the agent-scope meeting: every tile of the largest batch resident at once, on the saving kernels' own footprint
+        hipDeviceProp_t prop;
+        HIPCHK(h, hipGetDeviceProperties(&prop, h->cfg.device));
+        int per_cu = 0, k0 = 0, k2 = 0;
+        HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&k0, rnde_node_tile_solve_kernel<true>, kFtThreads, T->lds_bytes));
+        HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&k2, rnde_node_tile_reverse_kernel<true, true>, kFtThreads, T->lds_bytes));
+        per_cu = std::min(k0, k2);
+        if ((long long)per_cu * prop.multiProcessorCount < T->ntiles_max) {
+            h->err = "TrackedNeuralODE tiled engine: rnde_node_tiled_reserve_saveat: max_batch needs " + std::to_string(T->ntiles_max) +
+                     " resident tiles for the meeting of the saving solve and sweep, the device holds " +
+                     std::to_string((long long)per_cu * prop.multiProcessorCount) + " workgroups of their footprint";
+            return RNDE_ERR_BAD_ARG;
+        }
+    }
+    HIPCHK(h, hipMalloc(&T->sv_t, (size_t)max_saveat * 4));
+    HIPCHK(h, hipMalloc(&T->tp_sv_t, (size_t)max_saveat * 4));
+    HIPCHK(h, hipMalloc(&T->sv_rng, (size_t)h->cfg.max_attempts * sizeof(SaveRange)));
+    T->sv_cap = max_saveat;
+    return RNDE_OK;
+}
+
 rnde_status node_tiled_backward(rnde_node* h, const float* u_bar_dev, const float* saveval_bar_host, float* x_bar_dev, float* p_bar_dev,
                                 float* tspan_bar_host, void* stream) {
     rnde_node_tiled* T = h->tiled;
@@ -364,8 +453,18 @@ rnde_status node_tiled_backward(rnde_node* h, const float* u_bar_dev, const floa
     Q.G = T->G; Q.p = T->pcopy; Q.tape = T->tape; Q.rec = T->rec; Q.u_bar = u_bar_dev; Q.ws = T->rws; Q.pacc = T->pacc; Q.x_bar = x_bar_dev;
     Q.n_acc = T->tp_n_acc; Q.B = T->tp_B; Q.Bp = T->Bp; Q.reltol = h->cfg.reltol; Q.abstol = h->cfg.abstol;
     const int nt = (T->tp_B + 15) / 16;
+    const bool saving = !T->tp_saveat.empty();
+    if (saving) {                               // one range per accepted step, in the order of rec
+        std::vector<SaveRange> by_att(T->tp_n_att + 1);
+        save_plan(T->tp_saveat.data(), (int)T->tp_saveat.size(), T->tp_t0, T->tp_meta.data(), T->tp_n_att, F_ACCEPT, by_att.data());
+        T->h_rng.clear();
+        for (int i = 0; i < T->tp_n_att; ++i) if (T->tp_meta[i].flags & F_ACCEPT) T->h_rng.push_back(by_att[i]);
+        if (!T->h_rng.empty()) HIPCHK(h, hipMemcpyAsync(T->sv_rng, T->h_rng.data(), T->h_rng.size() * sizeof(SaveRange), hipMemcpyHostToDevice, s));
+        Q.sv_t = T->tp_sv_t; Q.rng = T->sv_rng; Q.nsave = (int)T->tp_saveat.size(); Q.save_t0 = T->tp_saveat[0] == T->tp_t0 ? 1 : 0;
+    }
     HIPCHK(h, hipEventRecord(T->ev[2], s));
-    hipLaunchKernelGGL(rnde_node_tile_reverse_kernel<false>, dim3(nt), dim3(kFtThreads), T->lds_bytes, s, Q);
+    if (saving) hipLaunchKernelGGL((rnde_node_tile_reverse_kernel<false, true>), dim3(nt), dim3(kFtThreads), T->lds_bytes, s, Q);
+    else hipLaunchKernelGGL((rnde_node_tile_reverse_kernel<false, false>), dim3(nt), dim3(kFtThreads), T->lds_bytes, s, Q);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(T->ev[3], s));
     hipLaunchKernelGGL(rnde_node_tile_reduce_kernel, dim3((h->P + 255) / 256), dim3(256), 0, s, (const float*)T->pacc, h->P, nt, p_bar_dev);

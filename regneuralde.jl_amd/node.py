@@ -17,7 +17,8 @@ Differences from the Julia layer that are inherent to the host language:
 after every accepted step (and the initial one with save_start=True), (B, n, D) with n known after the call.
 
 `engine="tiled"` (opt-in; `rnde_node_create_tiled`) serves Dense chains wider than 64 whose padded weights fit LDS (`tiled_lds_bytes(dims)` <=
-160 KB): end state only, Tsit5, EEst*dt or no callback.  By default its gradient treats step sizes and times as constants, and the layer must be
+160 KB): Tsit5, EEst*dt or no callback; the end state, and with `tiled_max_saveat=n` (the capacity every handle of the layer reserves,
+`rnde_node_tiled_reserve_saveat`) also `saveat=` of up to n times and `save_everystep=True`.  By default its gradient treats step sizes and times as constants, and the layer must be
 built with `track_ctrl=False, track_initdt=False` (they describe the create config); `set_tracking(True, True)` or the constructor keyword
 `tiled_tracking=(True, True)` then switches its handles to the tracked reverse sweep (`rnde_node_set_tracking`): the controller and the initial
 step are differentiated and `last_tspan_bar` carries the real cotangent.  `check_tiled_served` raises a ValueError that names the limit for
@@ -104,7 +105,7 @@ def check_tiled_served(layer):
                          "initial step, which only the default engines do)")
     if layer.solver != "Tsit5":
         raise ValueError(f'TrackedNeuralODE(engine="tiled"): solver must be "Tsit5"; got {layer.solver!r} (AutoTsit5, DP5 and DOP853 run on the default engines)')
-    if "saveat" in layer.kwargs or layer.kwargs.get("save_everystep", False):
+    if ("saveat" in layer.kwargs or layer.kwargs.get("save_everystep", False)) and layer.tiled_max_saveat is None:
         raise ValueError('TrackedNeuralODE(engine="tiled"): saveat= and save_everystep=True are not served (the end state only); use the default engine')
     if getattr(layer.model, "pre_act", False):
         raise ValueError('TrackedNeuralODE(engine="tiled"): a leading element-wise map (pre_act) is not served; use the default engine')
@@ -246,10 +247,21 @@ class TrackedNeuralODE:
 
     def __init__(self, model, tspan, time_dep, regularize, solver="Tsit5", *, max_batch=512, max_attempts=128,
                  cb_save_start=True, track_ctrl=True, track_initdt=True, col_tile=0, matrix_mode=None, engine=None, tiled_tracking=(False, False),
-                 **kwargs):
+                 tiled_max_saveat=None, **kwargs):
         if engine not in ENGINES:
             raise ValueError(f"engine must be one of {ENGINES}; got {engine!r}")
         self.engine = engine
+        # engine="tiled": the saveat capacity every handle of the layer reserves (rnde_node_tiled_reserve_saveat); None: saving calls are refused
+        if tiled_max_saveat is not None:
+            if engine != "tiled":
+                raise ValueError('TrackedNeuralODE: tiled_max_saveat is served with engine="tiled" only; the default engines take saveat= and '
+                                 "save_everystep=True without a reservation")
+            if isinstance(tiled_max_saveat, bool) or not isinstance(tiled_max_saveat, int) or tiled_max_saveat < 1:
+                raise ValueError(f'TrackedNeuralODE(engine="tiled"): tiled_max_saveat must be an integer >= 1 or None; got {tiled_max_saveat!r}')
+            if tiled_max_saveat > int(max_attempts) + 1:
+                raise ValueError(f'TrackedNeuralODE(engine="tiled"): tiled_max_saveat = {tiled_max_saveat} is above max_attempts + 1 = '
+                                 f"{int(max_attempts) + 1} (what save_everystep with save_start can need)")
+        self.tiled_max_saveat = tiled_max_saveat
         if solver not in ("Tsit5", "AutoTsit5", "DP5", "DOP853"):
             raise ValueError("solver: the reference's call sites use Tsit5() / AutoTsit5(Tsit5()) only; DP5 (a second 7-stage pair) and DOP853 "
                              "(a 13-stage table) run on the tableau-as-data kernels (Dense chains of width <= 64)")
@@ -322,6 +334,8 @@ class TrackedNeuralODE:
             _lib.check(h.ptr, _lib.lib().rnde_node_set_matrix_mode(h.ptr, int(self.matrix_mode)))
         if self._coupling is not None:
             _lib.check(h.ptr, _lib.lib().rnde_node_set_coupling(h.ptr, self._coupling[0], self._coupling[1]))
+        if self.tiled_max_saveat is not None:      # (a fresh handle holds no tape)
+            _lib.check(h.ptr, _lib.lib().rnde_node_tiled_reserve_saveat(h.ptr, int(self.tiled_max_saveat)))
         self._apply_tracking(h)
         hs.append(h)
         return h
@@ -427,6 +441,9 @@ class TrackedNeuralODE:
             times = "everystep"
         elif self.return_multiple:      # update_saveat! (neural_ode.jl:35-46): a per-call override, the stored one otherwise
             times = self._saveat_times(self.kwargs["saveat"] if saveat is None else saveat, ts)
+            if self.engine == "tiled" and len(times) > self.tiled_max_saveat:      # (before any launch; the library refuses it too)
+                raise ValueError(f'TrackedNeuralODE(engine="tiled"): {len(times)} save times are above the layer\'s tiled_max_saveat = '
+                                 f"{self.tiled_max_saveat}")
         u, saveval = _Solve.apply(x2, p.contiguous(), self, ts[0], ts[1], keep, times)
         sv = SavedValues(saveval) if self.regularize else None
         return u, self.last_nfe, sv
