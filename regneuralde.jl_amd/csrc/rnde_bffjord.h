@@ -18,13 +18,12 @@
 // the same.  Two more per-column vectors (lz + 2 l1 f, and w) and one more D x H product (eJ) per stage.
 #pragma once
 #include "rnde_ffjord.h"
+#include "rnde_track_rec.h"    // FfStepRec
 
 namespace rnde {
 
 constexpr int kFfVjpVecs = 22;        // per-column vectors of one reverse evaluation (rows: max(H, D))
 constexpr int kFfVjpVecsKin = 24;     // the kinetic sweep: + lz + 2 l1 f, + w
-
-struct FfStepRec { float t, dt, eest, svb; };     // one accepted step, in forward order; svb = cotangent of its saved value EEst * dt
 
 struct FfRevParams {
     FfGeo G;

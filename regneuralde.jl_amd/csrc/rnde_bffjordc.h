@@ -1,5 +1,5 @@
 // rnde_bffjordc.h -- the reverse of the Dense-chain dynamics on the tile layout: FcDyn::vjp, one stage's second-order VJP as
-// rnde_ffjord_tile.h's reverse sweep calls it.
+// rnde_tile_driver.h's reverse sweep calls it.
 //
 // One stage, cotangent (lz, ll, l1, l2) of F = [f; -e . eJ; sum f^2; sum eJ^2] (plain sweep: l1 = l2 = 0), notation of rnde_ffjordc.h:
 //     lf = lz + 2 l1 f,   w = -ll e + 2 l2 eJ                                   (the cotangents of f and of eJ)
@@ -14,7 +14,7 @@
 // L2-resident), as in rnde_bffjordt.h; no private scratch.  Every product runs on the matrix cores, the weight cotangents through ft_wgrad
 // (both outer products of a layer in one pass).
 #pragma once
-#include "rnde_bffjordt.h"     // ft_wgrad, FfStepRec, rnde_ffjordt_reduce_kernel
+#include "rnde_bffjordt.h"     // ft_wgrad
 #include "rnde_ffjordc.h"
 
 namespace rnde {
@@ -30,7 +30,7 @@ __host__ __device__ inline size_t FcDyn::rev_ws_floats(const FcGeo& G, bool kin)
 // Returns this thread's share of <dF/dt, lam> summed over the tile's columns (the tracked sweep's time cotangent): a_l = W_l y + wt_l t + b_l,
 // so it is sum_l <wt_l, a_l-bar summed over the columns>, first- and second-order parts alike; zero for a plain Chain.
 template <bool KIN>
-__device__ __forceinline__ float FcDyn::vjp(const FcGeo& G, const FcLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid) {
+__device__ __forceinline__ float FcDyn::vjp(const FcGeo& G, const FcLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid, float*) {
     const int lane = tid & 63, wave = tid >> 6, c = lane & 15, D = G.D, n = G.n, DP = G.DP;
     const size_t FS = (size_t)G.MP * 16;
     // slots: Y_0..Y_n | v_1..v_n | m_1..m_{n-1} (slot n unused) | m_0-bar (= w) .. m_{n-1}-bar | q_1..q_n (d_l-bar .* phi_l'') | a-bar x 2 | lf

@@ -1,5 +1,5 @@
 // rnde_bffjordt.h -- the reverse of the ConcatSquash dynamics on the tile layout: FtDyn::vjp, one stage's second-order VJP as
-// rnde_ffjord_tile.h's reverse sweep calls it, and what that sweep shares with the Dense-chain dynamics (ft_wgrad, the reduce kernel).
+// rnde_tile_driver.h's reverse sweep calls it, and what it shares with the Dense-chain dynamics (ft_wgrad).
 //
 // The second-order VJP of a stage needs some 27 per-column vectors; next to the resident weights they do not fit in LDS at the tabular
 // widths, so they live in a per-tile global buffer (written and read by the same workgroup, L2-resident); no private scratch.  Every
@@ -9,7 +9,7 @@
 // lz + 2 l1 f, is formed in the epilogue of the layer-3 product; w = -ll e + 2 l2 eJ needs eJ = W1' v1, one more transposed product once v1
 // is known, and W1 w replaces c (W1 e).  Both are two more vector slots of the per-tile global buffer: no LDS beyond the plain kernel's.
 #pragma once
-#include "rnde_bffjord.h"      // FfStepRec, ff_dsig
+#include "rnde_bffjord.h"      // ff_dsig
 #include "rnde_ffjordt.h"
 
 namespace rnde {
@@ -50,7 +50,7 @@ __device__ __forceinline__ void ft_wgrad(const float* A1, const float* B1, const
 // Returns this thread's share of <dF/dt, lam> summed over the tile's columns (the tracked sweep's time cotangent): h = p sig(gw t) + bw t + bb,
 // so wherever t X goes to gw-bar, gw X goes to the sum (formed ahead of the product with t: t = 0 occurs), and <bw, bb-bar> with it.
 template <bool KIN>
-__device__ __forceinline__ float FtDyn::vjp(const FtGeo& G, const FtLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid) {
+__device__ __forceinline__ float FtDyn::vjp(const FtGeo& G, const FtLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid, float*) {
     const int lane = tid & 63, wave = tid >> 6, c = lane & 15, D = G.D, H = G.H, HP = G.HP, DP = G.DP;
     const int FP = HP > DP ? HP : DP;
     auto vec = [&](int k) { return V + (size_t)k * FP * 16; };
@@ -215,15 +215,6 @@ __device__ __forceinline__ float FtDyn::vjp(const FtGeo& G, const FtLds& L, floa
     }
     __syncthreads();
     return tsum;
-}
-
-// p_bar[q] = sum over tiles of pacc[tile][q], in tile order, carried in double
-__global__ __launch_bounds__(256) void rnde_ffjordt_reduce_kernel(const float* __restrict__ pacc, int P, int ntiles, float* __restrict__ p_bar) {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= P) return;
-    double s = 0.0;
-    for (int t = 0; t < ntiles; ++t) s += (double)pacc[(size_t)t * P + q];
-    p_bar[q] = (float)s;
 }
 
 }  // namespace rnde

@@ -1,6 +1,6 @@
 // rnde_ffjord.hip -- C ABI of TrackedFFJORD (include/rnde.h, "TrackedFFJORD" section): create / forward / replay / backward / sample
 // over the kernels of rnde_ffjord.h (one-launch solve) and rnde_bffjord.h (one-launch reverse sweep), or, on a handle of the tile layout,
-// over the tile driver of rnde_ffjord_tile.h: rnde_ffjord_create_tiled (engine 1) runs it with the ConcatSquash dynamics FtDyn
+// over the tile driver of rnde_tile_driver.h: rnde_ffjord_create_tiled (engine 1) runs it with the ConcatSquash dynamics FtDyn
 // (rnde_ffjordt.h / rnde_bffjordt.h), rnde_ffjord_create_chain (engine 2) with the Dense-chain dynamics FcDyn (rnde_ffjordc.h /
 // rnde_bffjordc.h).  The *_kinetic entries run the KIN = true instantiations of the same kernels over D + 3 rows (TrackedFFJORD{false}
 // called with regularize = true).  The *_exact entries run the plain instantiations of the tile driver with the exact trace in the forward
@@ -13,7 +13,8 @@
 #include "rnde_bffjord.h"
 #include "rnde_bffjordt.h"
 #include "rnde_bffjordc.h"
-#include "rnde_ffjord_tile.h"
+#include "rnde_tile_driver.h"
+#include "rnde_tile_host.h"
 
 using namespace rnde;
 
@@ -131,10 +132,10 @@ static rnde_status tile_create(rnde_ffjord* h, const typename Dyn::Geo& G, rnde_
     h->initrec = h->initrec_t;
     if ((e = hipMalloc(&h->rec, MA * sizeof(FfStepRec))) != hipSuccess) return fail(e);
     if ((e = h->meet.create(MA + 4, 3, kMwMeetMax)) != hipSuccess) return fail(e);
-    for (const void* k : {(const void*)rnde_ffjord_tile_solve_kernel<Dyn, false>, (const void*)rnde_ffjord_tile_reverse_kernel<Dyn, false>,
-                          (const void*)rnde_ffjord_tile_feval_kernel<Dyn, false>, (const void*)rnde_ffjord_tile_solve_kernel<Dyn, true>,
-                          (const void*)rnde_ffjord_tile_reverse_kernel<Dyn, true>, (const void*)rnde_ffjord_tile_feval_kernel<Dyn, true>,
-                          (const void*)rnde_ffjord_tile_reverse_kernel<Dyn, false, true>})
+    for (const void* k : {(const void*)rnde_tile_solve_kernel<Dyn, false>, (const void*)rnde_tile_reverse_kernel<Dyn, false>,
+                          (const void*)rnde_tile_feval_kernel<Dyn, false>, (const void*)rnde_tile_solve_kernel<Dyn, true>,
+                          (const void*)rnde_tile_reverse_kernel<Dyn, true>, (const void*)rnde_tile_feval_kernel<Dyn, true>,
+                          (const void*)rnde_tile_reverse_kernel<Dyn, false, true>})
         if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes)) != hipSuccess) return fail(e);
     for (auto& v : h->ev) if ((e = hipEventCreate(&v)) != hipSuccess) return fail(e);
     *out = h;
@@ -174,16 +175,11 @@ extern "C" int32_t rnde_ffjord_engine(const rnde_ffjord* h) { return h ? h->engi
 // Its meeting needs every tile of the largest batch resident at once, on the tracked kernel's own footprint.
 template <class Dyn>
 static rnde_status trk_residency(rnde_ffjord* h) {
-    int per_cu = 0;
-    hipDeviceProp_t prop;
-    FCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rnde_ffjord_tile_reverse_kernel<Dyn, false, true>, kFtThreads, h->lds_bytes));
-    FCHK(h, hipGetDeviceProperties(&prop, h->cfg.device));
-    const long long room = h->ntiles_max > kMeetXcdCus ? (long long)per_cu * prop.multiProcessorCount : (per_cu > 0 ? kMeetXcdCus : 0);
-    if (room < h->ntiles_max) {
-        h->err = "TrackedFFJORD track_ctrl: max_batch needs " + std::to_string(h->ntiles_max) + " resident tiles for the reverse sweep's meeting, the device holds " +
-                 std::to_string(room) + " workgroups of the tracked sweep's footprint";
-        return RNDE_ERR_BAD_ARG;
-    }
+    hipError_t e;
+    const std::string why = tile_residency_refusal({(const void*)rnde_tile_reverse_kernel<Dyn, false, true>}, kFtThreads, h->lds_bytes, h->ntiles_max,
+                                                   h->cfg.device, "TrackedFFJORD track_ctrl: ", "the reverse sweep's meeting", "the tracked sweep's footprint", &e);
+    FCHK(h, e);
+    if (!why.empty()) { h->err = why; return RNDE_ERR_BAD_ARG; }
     return RNDE_OK;
 }
 
@@ -387,8 +383,8 @@ static void tile_launch_solve(rnde_ffjord* h, const typename Dyn::Geo& G, const 
     T.scratch = T.exact ? h->qt : nullptr;
     T.meet = meet; T.xcc = h->meet.xcc; T.xcd_slot = h->meet.slot; T.dir = Q.dir; T.Bp = Q.Bp; T.ntiles = meet.n; T.tbase = Q.tbase; T.reg = Q.reg;
     const dim3 grid(MeetRes::grid(meet));      // one XCD: every eighth block is a tile (the others return at once)
-    if (kin) hipLaunchKernelGGL((rnde_ffjord_tile_solve_kernel<Dyn, true>), grid, dim3(kFtThreads), h->lds_bytes, s, T);
-    else hipLaunchKernelGGL((rnde_ffjord_tile_solve_kernel<Dyn, false>), grid, dim3(kFtThreads), h->lds_bytes, s, T);
+    if (kin) hipLaunchKernelGGL((rnde_tile_solve_kernel<Dyn, true>), grid, dim3(kFtThreads), h->lds_bytes, s, T);
+    else hipLaunchKernelGGL((rnde_tile_solve_kernel<Dyn, false>), grid, dim3(kFtThreads), h->lds_bytes, s, T);
 }
 
 // meet != NULL: the tracked sweep (Q.rec is unused; n_att attempt records in h->att), placed as the solve is.
@@ -396,26 +392,26 @@ template <class Dyn>
 static void tile_launch_reverse(rnde_ffjord* h, const typename Dyn::Geo& G, const FfRevParams& Q, bool kin, bool exact, hipStream_t s,
                                 const Meet* meet = nullptr, int n_att = 0) {
     TileRevParams<typename Dyn::Geo> T{};
-    T.G = G; T.p = Q.p; T.e = Q.e; T.tape = Q.tape; T.rec = Q.rec; T.logpx_bar = Q.logpx_bar; T.ws = Q.ws; T.pacc = Q.pacc;
+    T.G = G; T.p = Q.p; T.e = Q.e; T.tape = Q.tape; T.rec = Q.rec; T.out_bar = Q.logpx_bar; T.ws = Q.ws; T.pacc = Q.pacc;
     T.x_bar = Q.x_bar; T.n_acc = Q.n_acc; T.B = Q.B; T.Bp = Q.Bp; T.reltol = Q.reltol; T.abstol = Q.abstol; T.reg_bar = Q.reg_bar;
     T.exact = exact ? 1 : 0; T.scratch = exact ? h->qt : nullptr;
     const int nt = (Q.B + 15) / 16;
     if (meet) {
         T.att = h->att; T.n_att = n_att; T.meet = *meet; T.xcc = h->meet.xcc; T.xcd_slot = h->meet.slot;
-        hipLaunchKernelGGL((rnde_ffjord_tile_reverse_kernel<Dyn, false, true>), dim3(MeetRes::grid(*meet)), dim3(kFtThreads), h->lds_bytes, s, T);
+        hipLaunchKernelGGL((rnde_tile_reverse_kernel<Dyn, false, true>), dim3(MeetRes::grid(*meet)), dim3(kFtThreads), h->lds_bytes, s, T);
         return;
     }
-    if (kin) hipLaunchKernelGGL((rnde_ffjord_tile_reverse_kernel<Dyn, true>), dim3(nt), dim3(kFtThreads), h->lds_bytes, s, T);
-    else hipLaunchKernelGGL((rnde_ffjord_tile_reverse_kernel<Dyn, false>), dim3(nt), dim3(kFtThreads), h->lds_bytes, s, T);
+    if (kin) hipLaunchKernelGGL((rnde_tile_reverse_kernel<Dyn, true>), dim3(nt), dim3(kFtThreads), h->lds_bytes, s, T);
+    else hipLaunchKernelGGL((rnde_tile_reverse_kernel<Dyn, false>), dim3(nt), dim3(kFtThreads), h->lds_bytes, s, T);
 }
 
 template <class Dyn>
 static void tile_launch_feval(rnde_ffjord* h, const typename Dyn::Geo& G, const float* p_dev, const float* x_dev, const float* e_dev, int B, float t,
                               int exact, bool kin, float* out_dev, hipStream_t s) {
     const dim3 grid((B + 15) / 16);
-    if (kin) hipLaunchKernelGGL((rnde_ffjord_tile_feval_kernel<Dyn, true>), grid, dim3(kFtThreads), h->lds_bytes, s, G, p_dev, x_dev, e_dev, t, B, exact,
+    if (kin) hipLaunchKernelGGL((rnde_tile_feval_kernel<Dyn, true>), grid, dim3(kFtThreads), h->lds_bytes, s, G, p_dev, x_dev, e_dev, t, B, exact,
                                 h->rws, h->qt, out_dev);
-    else hipLaunchKernelGGL((rnde_ffjord_tile_feval_kernel<Dyn, false>), grid, dim3(kFtThreads), h->lds_bytes, s, G, p_dev, x_dev, e_dev, t, B, exact,
+    else hipLaunchKernelGGL((rnde_tile_feval_kernel<Dyn, false>), grid, dim3(kFtThreads), h->lds_bytes, s, G, p_dev, x_dev, e_dev, t, B, exact,
                             h->rws, h->qt, out_dev);
 }
 
@@ -470,17 +466,10 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
     FCHK(h, hipStreamSynchronize(s));
     (void)hipEventElapsedTime(&h->fwd_ms, h->ev[0], h->ev[1]);
     if (tiles) {
-        const bool split = meet_split(h->meet.chk, nt, meet.global != 0);
-        if (meet_verdict(h->meet.chk, nt, meet.global != 0) != MEET_OK) {      // no fall-back to other arithmetic: the call fails and says why
-            FCHK(h, h->meet.clear_abort(s));
-            FCHK(h, hipStreamSynchronize(s));
-            h->n_att = h->n_acc = 0; h->h_meta.clear();
-            h->err = split ? "TrackedFFJORD tiled engine: a workgroup meeting of the solve timed out (the tiles pinned to one XCD by block index "
-                             "landed on different XCDs); the solve was abandoned"
-                           : "TrackedFFJORD tiled engine: a workgroup meeting of the solve timed out (not every tile was resident); the solve was "
-                             "abandoned";
-            return RNDE_ERR_HIP;
-        }
+        hipError_t me;
+        const std::string why = tile_meet_refusal(h->meet, meet, nt, s, "TrackedFFJORD tiled engine: ", "the solve", "the solve was abandoned", &me);
+        FCHK(h, me);
+        if (!why.empty()) { h->n_att = h->n_acc = 0; h->h_meta.clear(); h->err = why; return RNDE_ERR_HIP; }
     }
     h->n_att = fin.n_att; h->n_acc = fin.n_acc; h->B = B;
     h->h_meta.resize(fin.n_att);
@@ -606,32 +595,15 @@ static rnde_status ff_backward(rnde_ffjord* h, const float* logpx_bar_dev, const
     if (!logpx_bar_dev || !p_bar_dev) { h->err = "logpx_bar_dev and p_bar_dev are required"; return RNDE_ERR_BAD_ARG; }
     hipStream_t s = (hipStream_t)stream;
     std::vector<FfStepRec> rec;
-    rec.reserve(T.n_acc);
-    int k = (h->cfg.regularize && h->cfg.cb_save_start) ? 1 : 0;       // (the value saved at init is a constant)
-    for (int i = 0; i < T.n_att; ++i) {
-        const StepMeta& m = T.meta[i];
-        if (!(m.flags & F_ACCEPT)) continue;
-        FfStepRec r{m.t, m.dt, m.eest, 0.f};
-        if (h->cfg.regularize && saveval_bar_host) r.svb = saveval_bar_host[k];
-        ++k;
-        rec.push_back(r);
-    }
+    tile_step_recs(T.meta.data(), T.n_att, h->cfg.regularize ? saveval_bar_host : nullptr, h->cfg.regularize && h->cfg.cb_save_start, rec);
     if ((int)rec.size() != T.n_acc) { h->err = "internal: accepted-step count mismatch"; return RNDE_ERR_BAD_ARG; }
     if (!rec.empty()) FCHK(h, hipMemcpyAsync(h->rec, rec.data(), rec.size() * sizeof(FfStepRec), hipMemcpyHostToDevice, s));
     const bool trk = T.trk && h->engine >= 1 && !T.kin;
     std::vector<FfAttRec> att;
     Meet meet{};
     const int nt = (T.B + 15) / 16;
-    if (trk) {      // one record per attempt; a rejected attempt reads the tape record of the accepted attempt behind it
-        att.reserve(T.n_att);
-        int acc = 0;
-        for (int i = 0; i < T.n_att; ++i) {
-            const StepMeta& m = T.meta[i];
-            const bool a = (m.flags & F_ACCEPT) != 0;
-            att.push_back(ff_att_rec(m, a ? rec[acc].svb : 0.f, acc));
-            if (a) ++acc;
-        }
-        while (!att.empty() && !(att.back().flags & F_ACCEPT)) att.pop_back();      // (attempts behind the last accepted one reach nothing)
+    if (trk) {
+        tile_att_recs(T.meta.data(), T.n_att, rec, att);
         if (!att.empty()) FCHK(h, hipMemcpyAsync(h->att, att.data(), att.size() * sizeof(FfAttRec), hipMemcpyHostToDevice, s));
         meet = h->meet.begin(nt, true, s);
         FCHK(h, h->meet.err);
@@ -645,7 +617,7 @@ static rnde_status ff_backward(rnde_ffjord* h, const float* logpx_bar_dev, const
         if (h->engine == 2) tile_launch_reverse<FcDyn>(h, h->CG, Q, T.kin, T.exact, s, trk ? &meet : nullptr, (int)att.size());
         else tile_launch_reverse<FtDyn>(h, h->TG, Q, T.kin, T.exact, s, trk ? &meet : nullptr, (int)att.size());
         FCHK(h, hipGetLastError());
-        hipLaunchKernelGGL(rnde_ffjordt_reduce_kernel, dim3((h->G.P + 255) / 256), dim3(256), 0, s, (const float*)h->pacc, h->G.P, (T.B + 15) / 16, p_bar_dev);
+        hipLaunchKernelGGL(rnde_tile_reduce_kernel, dim3((h->G.P + 255) / 256), dim3(256), 0, s, (const float*)h->pacc, h->G.P, (T.B + 15) / 16, p_bar_dev);
     } else {
         if (T.kin) hipLaunchKernelGGL(rnde_ffjord_reverse_kernel<true>, dim3((T.B + 255) / 256), dim3(256), 0, s, Q);
         else hipLaunchKernelGGL(rnde_ffjord_reverse_kernel<false>, dim3((T.B + 255) / 256), dim3(256), 0, s, Q);
@@ -659,16 +631,11 @@ static rnde_status ff_backward(rnde_ffjord* h, const float* logpx_bar_dev, const
     (void)hipEventElapsedTime(&h->rev_ms, h->ev[2], h->ev[3]);
     if (trk) {
         FCHK(h, hipStreamSynchronize(s));
-        const bool split = meet_split(h->meet.chk, nt, meet.global != 0);
-        if (meet_verdict(h->meet.chk, nt, meet.global != 0) != MEET_OK) {      // no fall-back to the constant-step sweep: the call fails and says why
-            FCHK(h, h->meet.clear_abort(s));
-            FCHK(h, hipStreamSynchronize(s));
-            h->err = split ? "TrackedFFJORD track_ctrl: a workgroup meeting of the tracked reverse sweep timed out (the tiles pinned to one XCD by block "
-                             "index landed on different XCDs); the sweep was abandoned, p_bar and x_bar are not valid"
-                           : "TrackedFFJORD track_ctrl: a workgroup meeting of the tracked reverse sweep timed out (not every tile was resident); the "
-                             "sweep was abandoned, p_bar and x_bar are not valid";
-            return RNDE_ERR_HIP;
-        }
+        hipError_t me;
+        const std::string why = tile_meet_refusal(h->meet, meet, nt, s, "TrackedFFJORD track_ctrl: ", "the tracked reverse sweep",
+                                                  "the sweep was abandoned, p_bar and x_bar are not valid", &me);
+        FCHK(h, me);
+        if (!why.empty()) { h->err = why; return RNDE_ERR_HIP; }
     }
     return RNDE_OK;
 }

@@ -1,6 +1,6 @@
 // rnde_ffjordc.h -- TrackedFFJORD's default dynamics (ffjord.jl:21-27: Tracker.forward(z -> m(z, t), z) and back(e)) for a chain of Dense
 // layers, plain (Chain) or time dependent (TDChain: t appended to every layer's input), on the tile layout of rnde_ffjordt.h
-// (FcDyn; rnde_ffjord_create_chain, engine 2).  The solve, the reverse sweep and the feval kernel are rnde_ffjord_tile.h's.
+// (FcDyn; rnde_ffjord_create_chain, engine 2).  The solve, the reverse sweep and the feval kernel are rnde_tile_driver.h's.
 //
 // Dynamics, y_0 = z:   a_l = W_l y_{l-1} + wt_l t + b_l,   y_l = phi_l(a_l),   f = y_n,   d_l = phi_l' taken from y_l (act_dy)
 //     v_n = d_n .* e,   m_l = W_{l+1}' v_{l+1} (the z columns only),   v_l = d_l .* m_l,   eJ = W_1' v_1,   F = [f; -e . eJ]
@@ -54,10 +54,12 @@ struct FcLds {
     float* red;                        // 128 floats (the meeting keeps doubles at red + 64)
 };
 
-// The Dense-chain dynamics as the tile driver sees them (the policy's contract: rnde_ffjord_tile.h).
+// The Dense-chain dynamics as the tile driver sees them (the policy's contract: rnde_tile_driver.h).
 struct FcDyn {
     using Geo = FcGeo;
     using Lds = FcLds;
+    static constexpr int kAug = 1;                                                       // [z; l]: the log-density row
+    static constexpr bool kProbe = true, kDensity = true, kSpan = false, kVjpKdot = false;
     // LDS floats of the solve / feval / reverse kernels: parameters, X, E, every layer's output, two VJP vectors, reduction scratch
     __host__ __device__ static int lds_floats(const FcGeo& G) { return ft_align4(G.wfloats) + 2 * G.DP * 16 + G.yfloats + 2 * G.MP * 16 + 128; }
     __host__ __device__ static size_t scratch_floats(const FcGeo&) { return 0; }                          // (the exact trace needs none)
@@ -93,7 +95,7 @@ struct FcDyn {
     template <bool KIN>
     __device__ static void eval(const FcGeo& G, const FcLds& L, float t, float* kout, int ks, int exact, float fsign, float tsign, float* scratch, int tid);
     template <bool KIN>
-    __device__ static float vjp(const FcGeo& G, const FcLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid);      // (rnde_bffjordc.h)
+    __device__ static float vjp(const FcGeo& G, const FcLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid, float* kdot);      // (rnde_bffjordc.h)
 };
 
 // y_l = phi_l(W_l y_{l-1} + wt_l t + b_l) for every layer: X -> Y.  last(o, c, y): called for the rows o < D of the last layer.

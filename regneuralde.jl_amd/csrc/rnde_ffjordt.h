@@ -1,6 +1,6 @@
 // rnde_ffjordt.h -- the tile layout of TrackedFFJORD and its ConcatSquash dynamics (FtDyn; rnde_ffjord_create_tiled, engine 1): the dynamics
 // of rnde_ffjord.h at widths the one-workgroup engine does not serve (the tabular experiment's 43 -> 100), with the layer products on the
-// matrix cores.  The solve, the reverse sweep and the feval kernel that run these dynamics are rnde_ffjord_tile.h's; what is shared with the
+// matrix cores.  The solve, the reverse sweep and the feval kernel that run these dynamics are rnde_tile_driver.h's; what is shared with the
 // Dense-chain dynamics (rnde_ffjordc.h) is here: the kFt* constants, ft_pad16, ft_align4, ft_fwd, ft_tr, ft_colsum.
 //
 // Geometry (rnde_chainmw.h's layout): one workgroup of four waves per 16 batch columns (a tile).  The padded parameters stay resident in LDS,
@@ -65,10 +65,12 @@ struct FtLds {
     float* red;                        // 64 floats (+ 64 for the meeting)
 };
 
-// The ConcatSquash dynamics as the tile driver sees them (the policy's contract: rnde_ffjord_tile.h).
+// The ConcatSquash dynamics as the tile driver sees them (the policy's contract: rnde_tile_driver.h).
 struct FtDyn {
     using Geo = FtGeo;
     using Lds = FtLds;
+    static constexpr int kAug = 1;                                                       // [z; l]: the log-density row
+    static constexpr bool kProbe = true, kDensity = true, kSpan = false, kVjpKdot = false;
     // LDS floats of the solve / feval / reverse kernels: parameters, gates, six activation buffers, reduction scratch
     __host__ __device__ static int lds_floats(const FtGeo& G) { return ft_align4(G.wfloats) + ft_align4(ft_gt_floats(G)) + (2 * G.DP + 4 * G.HP) * 16 + 128; }
     __host__ __device__ static size_t scratch_floats(const FtGeo& G) { return (size_t)G.HP * G.HP; }      // QT of the exact trace
@@ -103,7 +105,7 @@ struct FtDyn {
     template <bool KIN>
     __device__ static void eval(const FtGeo& G, const FtLds& L, float t, float* kout, int ks, int exact, float fsign, float tsign, float* QT, int tid);
     template <bool KIN>
-    __device__ static float vjp(const FtGeo& G, const FtLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid);      // (rnde_bffjordt.h)
+    __device__ static float vjp(const FtGeo& G, const FtLds& L, float t, const float* z, const float* kb, float* yb, float* V, float* pacc, int tid, float* kdot);      // (rnde_bffjordt.h)
 };
 __device__ __forceinline__ const float* ft_vec(const FtGeo& G, const float* W, int l, int k) { return W + G.voff[l] + k * G.outp[l]; }
 

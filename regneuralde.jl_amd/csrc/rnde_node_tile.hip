@@ -1,11 +1,15 @@
 // rnde_node_tile.hip -- C ABI of the tiled engine of TrackedNeuralODE (include/rnde.h: rnde_node_create_tiled, engine 4): an rnde_node
-// whose solve, reverse sweeps (constant-step and tracked: rnde_node_set_tracking) and feval are the kernels of rnde_node_tile.h /
-// rnde_bnode_tile.h.  The public rnde_node_* entries (rnde.hip, rnde_reverse.hip) hand a handle of this engine to the node_tiled_* functions
+// whose solve, reverse sweeps (constant-step and tracked: rnde_node_set_tracking) and feval are the tile driver's kernels
+// (rnde_tile_driver.h) over the dynamics NtDyn (rnde_node_tile.h).  The public rnde_node_* entries (rnde.hip, rnde_reverse.hip) hand a handle of this engine to the node_tiled_* functions
 // below, or refuse it by name.
 // Saved points (rnde_node_forward_saveat / _everystep, the D x n x B backward) are served on a handle with a saveat capacity
 // (rnde_node_tiled_reserve_saveat) by the SAVE instantiations of the same kernels; a handle without one refuses them as before.
 #include "rnde_node.h"
-#include "rnde_bnode_tile.h"
+#include "rnde_node_tile.h"
+#include "rnde_tile_driver.h"
+#include "rnde_tile_host.h"
+
+static const char kNtPrefix[] = "TrackedNeuralODE tiled engine: ";
 
 struct rnde_node_tiled {
     FcGeo G{};
@@ -16,13 +20,13 @@ struct rnde_node_tiled {
     StepState* ctl_t = nullptr;      // [ntiles]
     StepMeta* meta = nullptr;        // [max_attempts]
     InitRec* initrec_t = nullptr;    // [ntiles]
-    NtStepRec* rec = nullptr;        // [max_attempts]
+    FfStepRec* rec = nullptr;        // [max_attempts]
     // rnde_node_set_tracking: taped forwards are reversed with the controller (and the initial step) differentiated
     bool track_ctrl = false, track_initdt = false;
     FfAttRec* att = nullptr;         // [max_attempts]: the tracked sweep's attempt records (allocated when tracking is first switched on)
     double* tsb = nullptr;           // [2]: the tracked sweep's (t0-bar, t1-bar)
     double* h_tsb = nullptr;         // pinned [2]: where the host reads them (an asynchronous copy must not land in a dead stack frame)
-    std::vector<NtStepRec> h_rec;    // the accepted steps' records of the last reverse sweep (likewise)
+    std::vector<FfStepRec> h_rec;    // the accepted steps' records of the last reverse sweep (likewise)
     std::vector<FfAttRec> h_att;     // the attempt records of the last tracked sweep (the source of an asynchronous copy: it outlives the call)
     MeetRes meet;
     // the taped forward, kept apart from the last solve (an untaped probe between a taped forward and its backward leaves it alone)
@@ -141,22 +145,16 @@ extern "C" rnde_status rnde_node_create_tiled(const rnde_node_config* c, rnde_no
     if ((e = hipMalloc(&T->ctl_t, NT * sizeof(StepState))) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&T->meta, MA * sizeof(StepMeta))) != hipSuccess) return fail(e);
     if ((e = hipMalloc(&T->initrec_t, NT * sizeof(InitRec))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&T->rec, MA * sizeof(NtStepRec))) != hipSuccess) return fail(e);
+    if ((e = hipMalloc(&T->rec, MA * sizeof(FfStepRec))) != hipSuccess) return fail(e);
     if ((e = hipHostMalloc((void**)&h->h_meta, MA * sizeof(StepMeta))) != hipSuccess) return fail(e);
     if ((e = T->meet.create(MA + 4, 3, kMwMeetMax)) != hipSuccess) return fail(e);
-    for (const void* k : {(const void*)rnde_node_tile_solve_kernel<false>, (const void*)rnde_node_tile_reverse_kernel<false>, (const void*)rnde_node_tile_feval_kernel})
+    const void* solve = (const void*)rnde_tile_solve_kernel<NtDyn, false, false>;
+    for (const void* k : {solve, (const void*)rnde_tile_reverse_kernel<NtDyn, false, false, false>, (const void*)rnde_tile_feval_kernel<NtDyn, false>})
         if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)T->lds_bytes)) != hipSuccess) return fail(e);
     if (T->ntiles_max > kMeetXcdCus) {      // the agent-scope meeting: every tile of the largest batch must be resident at once
-        int per_cu = 0;
-        hipDeviceProp_t prop;
-        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rnde_node_tile_solve_kernel<false>, kFtThreads, T->lds_bytes)) != hipSuccess) return fail(e);
-        if ((e = hipGetDeviceProperties(&prop, c->device)) != hipSuccess) return fail(e);
-        if ((long long)per_cu * prop.multiProcessorCount < T->ntiles_max) {
-            rnde_set_create_error("TrackedNeuralODE tiled engine: max_batch needs " + std::to_string(T->ntiles_max) + " resident tiles for the meeting, the device holds " +
-                              std::to_string((long long)per_cu * prop.multiProcessorCount) + " workgroups of this LDS footprint");
-            rnde_node_destroy(h);
-            return RNDE_ERR_BAD_ARG;
-        }
+        const std::string why = tile_residency_refusal({solve}, kFtThreads, T->lds_bytes, T->ntiles_max, c->device, kNtPrefix, "the meeting", "this LDS footprint", &e);
+        if (e != hipSuccess) return fail(e);
+        if (!why.empty()) { rnde_set_create_error(why); rnde_node_destroy(h); return RNDE_ERR_BAD_ARG; }
     }
     for (auto& v : T->ev) if ((e = hipEventCreate(&v)) != hipSuccess) return fail(e);
     *out = h;
@@ -201,7 +199,7 @@ rnde_status node_tiled_forward(rnde_node* h, const float* x_dev, const float* p_
         HIPCHK(h, hipMemcpyAsync(T->sv_t, T->h_sv.data(), (size_t)n_saveat * 4, hipMemcpyHostToDevice, s));
         if (taped) HIPCHK(h, hipMemcpyAsync(T->tp_sv_t, T->h_sv.data(), (size_t)n_saveat * 4, hipMemcpyHostToDevice, s));
     }
-    NodeTileSolveParams Q{};
+    TileSolveParams<FcGeo> Q{};
     StepParams& P = Q.F;
     P.x = x_dev; P.D = h->D; P.B = B; P.Bn = B; P.Bpad = T->Bp; P.nwg = 1;
     P.ctl = T->ctl; P.ctl_final = T->ctl + 2; P.meta = T->meta; P.initrec = T->initrec_t; P.initpart = T->norm;
@@ -213,11 +211,11 @@ rnde_status node_tiled_forward(rnde_node* h, const float* x_dev, const float* p_
     const int nt = (B + 15) / 16;
     const Meet meet = T->meet.begin(nt, true, s);      // every tile resident, one meeting per attempt (one XCD up to 32 tiles, agent scope above)
     HIPCHK(h, T->meet.err);
-    Q.G = T->G; Q.p = p_dev; Q.x = x_dev; Q.ws = T->ws; Q.tape = taped ? T->tape : nullptr; Q.u_out = u_out_dev; Q.norm = T->norm;
-    Q.initrec_t = T->initrec_t; Q.ctl_t = T->ctl_t; Q.meet = meet; Q.xcc = T->meet.xcc; Q.xcd_slot = T->meet.slot; Q.Bp = T->Bp;
+    Q.G = T->G; Q.p = p_dev; Q.x = x_dev; Q.ws = T->ws; Q.tape = taped ? T->tape : nullptr; Q.x_out = u_out_dev; Q.norm = T->norm;
+    Q.initrec_t = T->initrec_t; Q.ctl_t = T->ctl_t; Q.meet = meet; Q.xcc = T->meet.xcc; Q.xcd_slot = T->meet.slot; Q.dir = 1; Q.Bp = T->Bp; Q.ntiles = nt;
     HIPCHK(h, hipEventRecord(T->ev[0], s));
-    if (saving) hipLaunchKernelGGL(rnde_node_tile_solve_kernel<true>, dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
-    else hipLaunchKernelGGL(rnde_node_tile_solve_kernel<false>, dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
+    if (saving) hipLaunchKernelGGL((rnde_tile_solve_kernel<NtDyn, false, true>), dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
+    else hipLaunchKernelGGL((rnde_tile_solve_kernel<NtDyn, false, false>), dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(T->ev[1], s));
     T->ev_fwd = true;
@@ -225,16 +223,10 @@ rnde_status node_tiled_forward(rnde_node* h, const float* x_dev, const float* p_
     HIPCHK(h, hipMemcpyAsync(&fin, T->ctl + 2, sizeof(StepState), hipMemcpyDeviceToHost, s));
     HIPCHK(h, T->meet.queue_check(meet, s));
     HIPCHK(h, hipStreamSynchronize(s));
-    const bool split = meet_split(T->meet.chk, nt, meet.global != 0);
-    if (meet_verdict(T->meet.chk, nt, meet.global != 0) != MEET_OK) {      // no fall-back to other arithmetic: the call fails and says why
-        HIPCHK(h, T->meet.clear_abort(s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        h->n_att = 0;
-        h->err = split ? "TrackedNeuralODE tiled engine: a workgroup meeting of the solve timed out (the tiles pinned to one XCD by block index landed on "
-                         "different XCDs); the solve was abandoned"
-                       : "TrackedNeuralODE tiled engine: a workgroup meeting of the solve timed out (not every tile was resident); the solve was abandoned";
-        return RNDE_ERR_HIP;
-    }
+    hipError_t me;
+    const std::string why = tile_meet_refusal(T->meet, meet, nt, s, kNtPrefix, "the solve", "the solve was abandoned", &me);
+    HIPCHK(h, me);
+    if (!why.empty()) { h->n_att = 0; h->err = why; return RNDE_ERR_HIP; }
     h->n_att = fin.n_att; h->B = B; h->Bpad = T->Bp; h->t0 = t0; h->t1 = t1;
     if (fin.n_att) HIPCHK(h, hipMemcpy(h->h_meta, T->meta, (size_t)fin.n_att * sizeof(StepMeta), hipMemcpyDeviceToHost));
     switch (fin.status) {
@@ -265,20 +257,11 @@ rnde_status node_tiled_forward(rnde_node* h, const float* x_dev, const float* p_
 
 // The tracked sweep of a tape whose forward ran under rnde_node_set_tracking(h, 1, *): launched as the solve is, one meeting per attempt
 // (and two for the initial step); rec: the accepted steps with their saved values' cotangents.
-static rnde_status node_tiled_backward_tracked(rnde_node* h, const std::vector<NtStepRec>& rec, const float* u_bar_dev, float* x_bar_dev, float* p_bar_dev,
-                                               float* tspan_bar_host, hipStream_t s) {
+static rnde_status node_tiled_backward_tracked(rnde_node* h, const std::vector<FfStepRec>& rec, TileRevParams<FcGeo> Q, float* p_bar_dev, float* tspan_bar_host,
+                                               hipStream_t s) {
     rnde_node_tiled* T = h->tiled;
-    std::vector<FfAttRec>& att = T->h_att;      // one record per attempt; a rejected attempt reads the tape record of the accepted attempt behind it
-    att.clear();
-    att.reserve(T->tp_n_att);
-    int acc = 0;
-    for (int i = 0; i < T->tp_n_att; ++i) {
-        const StepMeta& m = T->tp_meta[i];
-        const bool a = (m.flags & F_ACCEPT) != 0;
-        att.push_back(ff_att_rec(m, a ? rec[acc].svb : 0.f, acc));
-        if (a) ++acc;
-    }
-    while (!att.empty() && !(att.back().flags & F_ACCEPT)) att.pop_back();      // (attempts behind the last accepted one reach nothing)
+    std::vector<FfAttRec>& att = T->h_att;
+    tile_att_recs(T->tp_meta.data(), T->tp_n_att, rec, att);
     if (!att.empty()) HIPCHK(h, hipMemcpyAsync(T->att, att.data(), att.size() * sizeof(FfAttRec), hipMemcpyHostToDevice, s));
     const bool saving = !T->tp_saveat.empty();
     if (saving) {                               // one range per attempt (the trimmed ones covered nothing)
@@ -289,18 +272,14 @@ static rnde_status node_tiled_backward_tracked(rnde_node* h, const std::vector<N
     const int nt = (T->tp_B + 15) / 16;
     const Meet meet = T->meet.begin(nt, true, s);      // a new epoch re-arms the rows the solve used
     HIPCHK(h, T->meet.err);
-    NodeTileRevParams Q{};
-    Q.G = T->G; Q.p = T->pcopy; Q.tape = T->tape; Q.rec = T->rec; Q.u_bar = u_bar_dev; Q.ws = T->rws; Q.pacc = T->pacc; Q.x_bar = x_bar_dev;
-    Q.n_acc = T->tp_n_acc; Q.B = T->tp_B; Q.Bp = T->Bp; Q.reltol = h->cfg.reltol; Q.abstol = h->cfg.abstol;
     Q.att = T->att; Q.n_att = (int)att.size(); Q.track_initdt = T->tp_track_initdt ? 1 : 0; Q.init = T->tp_init; Q.t0 = T->tp_t0; Q.tspan_out = T->tsb;
     Q.meet = meet; Q.xcc = T->meet.xcc; Q.xcd_slot = T->meet.slot;
-    if (saving) { Q.sv_t = T->tp_sv_t; Q.rng = T->sv_rng; Q.nsave = (int)T->tp_saveat.size(); Q.save_t0 = T->tp_saveat[0] == T->tp_t0 ? 1 : 0; }
     HIPCHK(h, hipEventRecord(T->ev[2], s));
-    if (saving) hipLaunchKernelGGL((rnde_node_tile_reverse_kernel<true, true>), dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
-    else hipLaunchKernelGGL((rnde_node_tile_reverse_kernel<true, false>), dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
+    if (saving) hipLaunchKernelGGL((rnde_tile_reverse_kernel<NtDyn, false, true, true>), dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
+    else hipLaunchKernelGGL((rnde_tile_reverse_kernel<NtDyn, false, true, false>), dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(T->ev[3], s));
-    hipLaunchKernelGGL(rnde_node_tile_reduce_kernel, dim3((h->P + 255) / 256), dim3(256), 0, s, (const float*)T->pacc, h->P, nt, p_bar_dev);
+    hipLaunchKernelGGL(rnde_tile_reduce_kernel, dim3((h->P + 255) / 256), dim3(256), 0, s, (const float*)T->pacc, h->P, nt, p_bar_dev);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(T->ev[4], s));
     T->ev_bwd = true;
@@ -308,16 +287,11 @@ static rnde_status node_tiled_backward_tracked(rnde_node* h, const std::vector<N
     HIPCHK(h, hipMemcpyAsync(tsb, T->tsb, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(h, T->meet.queue_check(meet, s));
     HIPCHK(h, hipStreamSynchronize(s));      // (att and tsb are members: a copy still in flight on an error return above touches live memory)
-    const bool split = meet_split(T->meet.chk, nt, meet.global != 0);
-    if (meet_verdict(T->meet.chk, nt, meet.global != 0) != MEET_OK) {      // no fall-back to the constant-step sweep: the call fails and says why
-        HIPCHK(h, T->meet.clear_abort(s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        h->err = split ? "TrackedNeuralODE tiled engine: a workgroup meeting of the tracked reverse sweep timed out (the tiles pinned to one XCD by block "
-                         "index landed on different XCDs); the sweep was abandoned, x_bar, p_bar and tspan_bar are not valid"
-                       : "TrackedNeuralODE tiled engine: a workgroup meeting of the tracked reverse sweep timed out (not every tile was resident); the "
-                         "sweep was abandoned, x_bar, p_bar and tspan_bar are not valid";
-        return RNDE_ERR_HIP;
-    }
+    hipError_t me;
+    const std::string why = tile_meet_refusal(T->meet, meet, nt, s, kNtPrefix, "the tracked reverse sweep",
+                                              "the sweep was abandoned, x_bar, p_bar and tspan_bar are not valid", &me);
+    HIPCHK(h, me);
+    if (!why.empty()) { h->err = why; return RNDE_ERR_HIP; }
     if (tspan_bar_host) { tspan_bar_host[0] = (float)tsb[0]; tspan_bar_host[1] = (float)tsb[1]; }
     return RNDE_OK;
 }
@@ -347,18 +321,15 @@ extern "C" rnde_status rnde_node_set_tracking(rnde_node* h, int32_t track_ctrl, 
     }
     if (track_ctrl && !T->att) {
         HIPCHK(h, hipSetDevice(h->cfg.device));
-        HIPCHK(h, hipFuncSetAttribute((const void*)rnde_node_tile_reverse_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)T->lds_bytes));
+        const void* sweep = (const void*)rnde_tile_reverse_kernel<NtDyn, false, true, false>;
+        HIPCHK(h, hipFuncSetAttribute(sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)T->lds_bytes));
         if (T->ntiles_max > kMeetXcdCus) {      // the agent-scope meeting: every tile of the largest batch resident at once, on the tracked kernel's own footprint
-            int per_cu = 0;
-            hipDeviceProp_t prop;
-            HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rnde_node_tile_reverse_kernel<true>, kFtThreads, T->lds_bytes));
-            HIPCHK(h, hipGetDeviceProperties(&prop, h->cfg.device));
-            if ((long long)per_cu * prop.multiProcessorCount < T->ntiles_max) {
-                h->err = "TrackedNeuralODE tiled engine: rnde_node_set_tracking: max_batch needs " + std::to_string(T->ntiles_max) +
-                         " resident tiles for the tracked reverse sweep's meeting, the device holds " +
-                         std::to_string((long long)per_cu * prop.multiProcessorCount) + " workgroups of the tracked sweep's footprint";
-                return RNDE_ERR_BAD_ARG;
-            }
+            hipError_t e;
+            const std::string why = tile_residency_refusal({sweep}, kFtThreads, T->lds_bytes, T->ntiles_max, h->cfg.device,
+                                                           "TrackedNeuralODE tiled engine: rnde_node_set_tracking: ", "the tracked reverse sweep's meeting",
+                                                           "the tracked sweep's footprint", &e);
+            HIPCHK(h, e);
+            if (!why.empty()) { h->err = why; return RNDE_ERR_BAD_ARG; }
         }
         // (att last: it is what marks the switch-on as done, so a call that failed half way is simply made again)
         if (!T->tsb) HIPCHK(h, hipMalloc(&T->tsb, 2 * sizeof(double)));
@@ -403,22 +374,16 @@ extern "C" rnde_status rnde_node_tiled_reserve_saveat(rnde_node* h, int32_t max_
     T->tp_saveat.clear();
     for (void** p : {(void**)&T->sv_t, (void**)&T->tp_sv_t, (void**)&T->sv_rng}) { if (*p) (void)hipFree(*p); *p = nullptr; }
     if (max_saveat == 0) return RNDE_OK;
-    const void* kernels[3] = {(const void*)rnde_node_tile_solve_kernel<true>, (const void*)rnde_node_tile_reverse_kernel<false, true>,
-                              (const void*)rnde_node_tile_reverse_kernel<true, true>};
-    for (const void* k : kernels) HIPCHK(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)T->lds_bytes));
+    const void *solve = (const void*)rnde_tile_solve_kernel<NtDyn, false, true>, *sweep = (const void*)rnde_tile_reverse_kernel<NtDyn, false, true, true>;
+    for (const void* k : {solve, (const void*)rnde_tile_reverse_kernel<NtDyn, false, false, true>, sweep})
+        HIPCHK(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)T->lds_bytes));
     if (T->ntiles_max > kMeetXcdCus) {          // the agent-scope meeting: every tile of the largest batch resident at once, on the saving kernels' own footprint
-        hipDeviceProp_t prop;
-        HIPCHK(h, hipGetDeviceProperties(&prop, h->cfg.device));
-        int per_cu = 0, k0 = 0, k2 = 0;
-        HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&k0, rnde_node_tile_solve_kernel<true>, kFtThreads, T->lds_bytes));
-        HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&k2, rnde_node_tile_reverse_kernel<true, true>, kFtThreads, T->lds_bytes));
-        per_cu = std::min(k0, k2);
-        if ((long long)per_cu * prop.multiProcessorCount < T->ntiles_max) {
-            h->err = "TrackedNeuralODE tiled engine: rnde_node_tiled_reserve_saveat: max_batch needs " + std::to_string(T->ntiles_max) +
-                     " resident tiles for the meeting of the saving solve and sweep, the device holds " +
-                     std::to_string((long long)per_cu * prop.multiProcessorCount) + " workgroups of their footprint";
-            return RNDE_ERR_BAD_ARG;
-        }
+        hipError_t e;
+        const std::string why = tile_residency_refusal({solve, sweep}, kFtThreads, T->lds_bytes, T->ntiles_max, h->cfg.device,
+                                                       "TrackedNeuralODE tiled engine: rnde_node_tiled_reserve_saveat: ",
+                                                       "the meeting of the saving solve and sweep", "their footprint", &e);
+        HIPCHK(h, e);
+        if (!why.empty()) { h->err = why; return RNDE_ERR_BAD_ARG; }
     }
     HIPCHK(h, hipMalloc(&T->sv_t, (size_t)max_saveat * 4));
     HIPCHK(h, hipMalloc(&T->tp_sv_t, (size_t)max_saveat * 4));
@@ -434,40 +399,30 @@ rnde_status node_tiled_backward(rnde_node* h, const float* u_bar_dev, const floa
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const bool reg = h->cfg.regularize == RNDE_REG_ERR;
-    std::vector<NtStepRec>& rec = T->h_rec;      // (a member: the source of an asynchronous copy outlives an error return)
-    rec.clear();
-    rec.reserve(T->tp_n_acc);
-    int k = (reg && h->cfg.cb_save_start) ? 1 : 0;       // (the value saved at init is a constant)
-    for (int i = 0; i < T->tp_n_att; ++i) {
-        const StepMeta& m = T->tp_meta[i];
-        if (!(m.flags & F_ACCEPT)) continue;
-        NtStepRec r{m.t, m.dt, m.eest, 0.f};
-        if (reg && saveval_bar_host) r.svb = saveval_bar_host[k];
-        ++k;
-        rec.push_back(r);
-    }
+    std::vector<FfStepRec>& rec = T->h_rec;      // (a member: the source of an asynchronous copy outlives an error return)
+    tile_step_recs(T->tp_meta.data(), T->tp_n_att, reg ? saveval_bar_host : nullptr, reg && h->cfg.cb_save_start, rec);
     if ((int)rec.size() != T->tp_n_acc) { h->err = "internal: accepted-step count mismatch"; return RNDE_ERR_BAD_ARG; }
-    if (!rec.empty()) HIPCHK(h, hipMemcpyAsync(T->rec, rec.data(), rec.size() * sizeof(NtStepRec), hipMemcpyHostToDevice, s));
-    if (T->tp_track_ctrl) return node_tiled_backward_tracked(h, rec, u_bar_dev, x_bar_dev, p_bar_dev, tspan_bar_host, s);
-    NodeTileRevParams Q{};
-    Q.G = T->G; Q.p = T->pcopy; Q.tape = T->tape; Q.rec = T->rec; Q.u_bar = u_bar_dev; Q.ws = T->rws; Q.pacc = T->pacc; Q.x_bar = x_bar_dev;
+    if (!rec.empty()) HIPCHK(h, hipMemcpyAsync(T->rec, rec.data(), rec.size() * sizeof(FfStepRec), hipMemcpyHostToDevice, s));
+    TileRevParams<FcGeo> Q{};
+    Q.G = T->G; Q.p = T->pcopy; Q.tape = T->tape; Q.rec = T->rec; Q.out_bar = u_bar_dev; Q.ws = T->rws; Q.pacc = T->pacc; Q.x_bar = x_bar_dev;
     Q.n_acc = T->tp_n_acc; Q.B = T->tp_B; Q.Bp = T->Bp; Q.reltol = h->cfg.reltol; Q.abstol = h->cfg.abstol;
-    const int nt = (T->tp_B + 15) / 16;
     const bool saving = !T->tp_saveat.empty();
+    if (saving) { Q.sv_t = T->tp_sv_t; Q.rng = T->sv_rng; Q.nsave = (int)T->tp_saveat.size(); Q.save_t0 = T->tp_saveat[0] == T->tp_t0 ? 1 : 0; }
+    if (T->tp_track_ctrl) return node_tiled_backward_tracked(h, rec, Q, p_bar_dev, tspan_bar_host, s);
+    const int nt = (T->tp_B + 15) / 16;
     if (saving) {                               // one range per accepted step, in the order of rec
         std::vector<SaveRange> by_att(T->tp_n_att + 1);
         save_plan(T->tp_saveat.data(), (int)T->tp_saveat.size(), T->tp_t0, T->tp_meta.data(), T->tp_n_att, F_ACCEPT, by_att.data());
         T->h_rng.clear();
         for (int i = 0; i < T->tp_n_att; ++i) if (T->tp_meta[i].flags & F_ACCEPT) T->h_rng.push_back(by_att[i]);
         if (!T->h_rng.empty()) HIPCHK(h, hipMemcpyAsync(T->sv_rng, T->h_rng.data(), T->h_rng.size() * sizeof(SaveRange), hipMemcpyHostToDevice, s));
-        Q.sv_t = T->tp_sv_t; Q.rng = T->sv_rng; Q.nsave = (int)T->tp_saveat.size(); Q.save_t0 = T->tp_saveat[0] == T->tp_t0 ? 1 : 0;
     }
     HIPCHK(h, hipEventRecord(T->ev[2], s));
-    if (saving) hipLaunchKernelGGL((rnde_node_tile_reverse_kernel<false, true>), dim3(nt), dim3(kFtThreads), T->lds_bytes, s, Q);
-    else hipLaunchKernelGGL((rnde_node_tile_reverse_kernel<false, false>), dim3(nt), dim3(kFtThreads), T->lds_bytes, s, Q);
+    if (saving) hipLaunchKernelGGL((rnde_tile_reverse_kernel<NtDyn, false, false, true>), dim3(nt), dim3(kFtThreads), T->lds_bytes, s, Q);
+    else hipLaunchKernelGGL((rnde_tile_reverse_kernel<NtDyn, false, false, false>), dim3(nt), dim3(kFtThreads), T->lds_bytes, s, Q);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(T->ev[3], s));
-    hipLaunchKernelGGL(rnde_node_tile_reduce_kernel, dim3((h->P + 255) / 256), dim3(256), 0, s, (const float*)T->pacc, h->P, nt, p_bar_dev);
+    hipLaunchKernelGGL(rnde_tile_reduce_kernel, dim3((h->P + 255) / 256), dim3(256), 0, s, (const float*)T->pacc, h->P, nt, p_bar_dev);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(T->ev[4], s));
     T->ev_bwd = true;
@@ -480,7 +435,8 @@ rnde_status node_tiled_feval(rnde_node* h, const float* u_dev, const float* p_de
     rnde_node_tiled* T = h->tiled;
     if (!u_dev || !p_dev || !out_dev) { h->err = "bad argument"; return RNDE_ERR_BAD_ARG; }
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(rnde_node_tile_feval_kernel, dim3((B + 15) / 16), dim3(kFtThreads), T->lds_bytes, s, T->G, p_dev, u_dev, t, B, T->rws, out_dev);
+    hipLaunchKernelGGL((rnde_tile_feval_kernel<NtDyn, false>), dim3((B + 15) / 16), dim3(kFtThreads), T->lds_bytes, s, T->G, p_dev, u_dev, (const float*)nullptr, t, B, 0,
+                       T->rws, (float*)nullptr, out_dev);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(s));
     return RNDE_OK;

@@ -1,12 +1,14 @@
 // rnde_track_rec.h -- the scalar reverse of the step-size controller and of the initial-step rule as the tracked sweeps on the tile layout use
-// it (rnde_ffjord_tile.h: rnde_ffjord_tile_reverse_kernel<Dyn, KIN, true>; rnde_bnode_tile.h: rnde_node_tile_reverse_kernel<true>).  No
-// kernel lives here: both translation units of the tile layout include it, and a stand-alone host program checks it against finite
-// differences (tests/track_host/track_host_check.cpp).
+// it (rnde_tile_driver.h: rnde_tile_reverse_kernel<Dyn, KIN, true>), beside the records of a sweep's walk.  No kernel lives here: both
+// translation units of the tile layout include it, and a stand-alone host program checks it against finite differences
+// (tests/track_host/track_host_check.cpp).
 #pragma once
 #include "rnde_device.h"       // StepMeta, InitRec, the controller's constants and flags
 #include <cmath>
 
 namespace rnde {
+
+struct FfStepRec { float t, dt, eest, svb; };     // one accepted step, in forward order; svb = cotangent of its saved value EEst * dt
 
 // One attempt of the tracked sweep, in forward order: (t, dt, EEst) and the flags of the step log, the tape record that holds the attempt's
 // uprev, and the scalar reverse of the controller branch the forward took (rnde_bchain.h's prologue with track_ctrl = 1, t0-bar and t1-bar

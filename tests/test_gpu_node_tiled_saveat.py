@@ -1,5 +1,5 @@
-"""Saved points on the tiled TrackedNeuralODE engine (rnde_node_tiled_reserve_saveat; rnde_node_tile_solve_kernel<true>,
-rnde_node_tile_reverse_kernel<*, true>): rnde_node_forward_saveat / _everystep and the D x n x B backward behind them, against the fp64 CPU
+"""Saved points on the tiled TrackedNeuralODE engine (rnde_node_tiled_reserve_saveat; rnde_tile_solve_kernel<NtDyn, false, true>,
+rnde_tile_reverse_kernel<NtDyn, false, *, true>): rnde_node_forward_saveat / _everystep and the D x n x B backward behind them, against the fp64 CPU
 oracle.  Shapes, inputs and helpers are those of tests/test_gpu_node_tiled.py and tests/test_gpu_node_tiled_track.py (imported); reltol =
 abstol = 1e-5.  Every case fails without the feature: the reserve symbol does not exist.
 

@@ -1,4 +1,4 @@
-"""The tracked reverse sweep of the tiled TrackedNeuralODE engine (rnde_node_set_tracking; rnde_node_tile_reverse_kernel<true>): the step-size
+"""The tracked reverse sweep of the tiled TrackedNeuralODE engine (rnde_node_set_tracking; rnde_tile_reverse_kernel<NtDyn, false, true>): the step-size
 controller, the clamps to t1 and the initial-step rule differentiated, against the fp64 CPU oracle with the same flags.
 
 Cases: the adaptive inputs of tests/test_gpu_node_tiled.py (imported) -- pad_td ([3,7,3] TD, B = 37: three tiles, a partial last one, padding

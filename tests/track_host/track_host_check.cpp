@@ -1,7 +1,9 @@
 // The scalar reverses of csrc/rnde_track_rec.h, checked by a program of its own (tests/test_node_tiled_track_host.py compiles and runs it; no
 // GPU is touched): init_rev_phase1 / init_rev_phase2 against central finite differences of the initial-step rule, and ff_att_rec's eight
-// coefficients against finite differences of the PI controller, both forward rules written here in double beside them.  Prints one line per
-// failed check; exit status 0 when there is none.
+// coefficients against finite differences of the PI controller, both forward rules written here in double beside them; and the two record
+// builders of csrc/rnde_tile_host.h (the accepted steps and the attempts a reverse sweep walks) on written-down step logs, against records
+// written out by hand.  Prints one line per failed check; exit status 0 when there is none.
+#include "rnde_tile_host.h"
 #include "rnde_track_rec.h"
 
 #include <algorithm>
@@ -22,7 +24,7 @@ static bool close_to(const char* what, const char* name, double got, double want
     return ok;
 }
 
-// ---- the initial-step rule (rnde_node_tile_solve_kernel and advance_state_t, n == 0) over its scalars ----
+// ---- the initial-step rule (rnde_tile_solve_kernel and advance_state_t, n == 0) over its scalars ----
 // n2 = rms((f1 - f0) / sk) depends on dt0 through u1 = x + dt0 f0 and through the time t0 + dt0: modelled as n2 = n2b + kd dt0 + kt (t0 + dt0),
 // so that the two sums of phase 1's VJP are dot = kd n2-bar and tau = kt n2-bar.
 struct InitIn { double d0, d1, n2b, kd, kt, t0, t1; };
@@ -129,6 +131,63 @@ static void check_ctl(const char* what, const CtlIn& in, bool accept, double dtm
     close_to(what, "d0", a.d0, accept ? (double)svb * in.eest : 0.0, 1e-12);
 }
 
+// ---- the record builders (tile_step_recs, tile_att_recs) on written-down step logs; every number is a dyadic fraction, so == is exact ----
+static StepMeta log_entry(float t, float dt, float eest, int flags) {
+    StepMeta m{};
+    m.t = t; m.dt = dt; m.dtp_in = dt; m.eest = eest; m.q11 = 1.f; m.q = 1.f; m.qold_in = 1.f; m.rej_m = 2.f; m.flags = flags;
+    return m;
+}
+struct StepWant { float t, dt, eest, svb; };
+struct AttWant { float t, dt, eest; int flags, rec; double e0, d0; };
+template <int NS, int NA>
+static void check_records(const char* what, const std::vector<StepMeta>& log, const float* bar, bool skip_first, const StepWant (&sw)[NS], const AttWant (&aw)[NA]) {
+    std::vector<FfStepRec> rec{FfStepRec{9.f, 9.f, 9.f, 9.f}};      // (the builders clear what they are given)
+    std::vector<FfAttRec> att(7);
+    tile_step_recs(log.data(), (int)log.size(), bar, skip_first, rec);
+    tile_att_recs(log.data(), (int)log.size(), rec, att);
+    if (rec.size() != (size_t)NS || att.size() != (size_t)NA) { std::printf("FAILED %s: %zu step and %zu attempt records\n", what, rec.size(), att.size()); ++failures; return; }
+    for (int i = 0; i < NS; ++i)
+        if (!(rec[i].t == sw[i].t && rec[i].dt == sw[i].dt && rec[i].eest == sw[i].eest && rec[i].svb == sw[i].svb)) { std::printf("FAILED %s: step record %d\n", what, i); ++failures; }
+    for (int i = 0; i < NA; ++i) {
+        const FfAttRec& a = att[i];
+        const FfAttRec c = ff_att_rec(log[i], 0.f, 0);        // (the controller's coefficients do not depend on svb: checked above)
+        if (!(a.t == aw[i].t && a.dt == aw[i].dt && a.eest == aw[i].eest && a.flags == aw[i].flags && a.rec == aw[i].rec && a.e0 == aw[i].e0 && a.d0 == aw[i].d0 &&
+              a.e_dtp == c.e_dtp && a.e_q == c.e_q && a.d_t == c.d_t && a.d_dtp == c.d_dtp && a.c_dtp == c.c_dtp && a.c_q == c.c_q)) {
+            std::printf("FAILED %s: attempt record %d\n", what, i); ++failures;
+        }
+    }
+}
+static void check_builders() {
+    const int A = F_ACCEPT, J = F_REJQ11;
+    // a rejected first attempt, a rejection between accepted steps, the last step clamped to t1
+    const std::vector<StepMeta> first{log_entry(0.f, 0.5f, 2.5f, J), log_entry(0.f, 0.25f, 0.5f, A), log_entry(0.25f, 0.25f, 0.25f, A), log_entry(0.5f, 1.f, 3.f, 0),
+                                      log_entry(0.5f, 0.5f, 0.125f, A | F_CLAMP)};
+    const float bar_on[4] = {9.f, 0.5f, 0.25f, 0.75f}, bar_off[3] = {0.5f, 0.25f, 0.75f};
+    const StepWant sw[3] = {{0.f, 0.25f, 0.5f, 0.5f}, {0.25f, 0.25f, 0.25f, 0.25f}, {0.5f, 0.5f, 0.125f, 0.75f}};
+    const AttWant aw[5] = {{0.f, 0.5f, 2.5f, J, 0, 0.0, 0.0}, {0.f, 0.25f, 0.5f, A, 0, 0.125, 0.25}, {0.25f, 0.25f, 0.25f, A, 1, 0.0625, 0.0625},
+                           {0.5f, 1.f, 3.f, 0, 2, 0.0, 0.0}, {0.5f, 0.5f, 0.125f, A | F_CLAMP, 2, 0.375, 0.09375}};
+    check_records("rejected first attempt, cb_save_start on", first, bar_on, true, sw, aw);
+    check_records("rejected first attempt, cb_save_start off", first, bar_off, false, sw, aw);
+    const StepWant sw0[3] = {{0.f, 0.25f, 0.5f, 0.f}, {0.25f, 0.25f, 0.25f, 0.f}, {0.5f, 0.5f, 0.125f, 0.f}};
+    const AttWant aw0[5] = {{0.f, 0.5f, 2.5f, J, 0, 0.0, 0.0}, {0.f, 0.25f, 0.5f, A, 0, 0.0, 0.0}, {0.25f, 0.25f, 0.25f, A, 1, 0.0, 0.0}, {0.5f, 1.f, 3.f, 0, 2, 0.0, 0.0},
+                            {0.5f, 0.5f, 0.125f, A | F_CLAMP, 2, 0.0, 0.0}};
+    check_records("null saveval_bar", first, nullptr, false, sw0, aw0);
+    check_records("null saveval_bar, cb_save_start on", first, nullptr, true, sw0, aw0);
+    // rejected attempts behind the last accepted one (a solve that ran into max_attempts): trimmed from the attempt records
+    const std::vector<StepMeta> tail{log_entry(0.f, 0.25f, 0.5f, A), log_entry(0.25f, 0.5f, 0.25f, A), log_entry(0.75f, 0.5f, 4.f, J), log_entry(0.75f, 0.25f, 2.f, J)};
+    const StepWant tw[2] = {{0.f, 0.25f, 0.5f, 0.25f}, {0.25f, 0.5f, 0.25f, 0.75f}};
+    const AttWant ta[2] = {{0.f, 0.25f, 0.5f, A, 0, 0.0625, 0.125}, {0.25f, 0.5f, 0.25f, A, 1, 0.375, 0.1875}};
+    check_records("rejections behind the last accepted step", tail, bar_on + 2, false, tw, ta);
+    check_records("rejections behind the last accepted step, cb_save_start on", tail, bar_on + 1, true, tw, ta);
+    // a log with no accepted step: no record of either kind
+    std::vector<FfStepRec> rec;
+    std::vector<FfAttRec> att;
+    const std::vector<StepMeta> none{log_entry(0.f, 0.5f, 2.5f, J)};
+    tile_step_recs(none.data(), 1, nullptr, false, rec);
+    tile_att_recs(none.data(), 1, rec, att);
+    CHECK(rec.empty() && att.empty());
+}
+
 int main() {
     // ---- the initial step: every branch of the rule ----
     //                                   d0    d1   n2b    kd     kt    t0   t1     sel c1 mx c0 cl
@@ -150,6 +209,7 @@ int main() {
     check_ctl("accepted, F_QCLAMP", CtlIn{1e-12, 0.05, 0.2, 1e-4}, true, 1.0, F_ACCEPT | F_QCLAMP);
     check_ctl("rejected, F_QCLAMP", CtlIn{1e6, 0.05, 0.2, 1e-4}, false, 1.0, F_QCLAMP);
     check_ctl("accepted, F_DTMAXCLAMP", CtlIn{2e-4, 0.5, 0.2, 0.2}, true, 1.0, F_ACCEPT | F_DTMAXCLAMP);
+    check_builders();
     if (failures) { std::printf("%d check(s) failed\n", failures); return 1; }
     std::printf("track host checks passed\n");
     return 0;
