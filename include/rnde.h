@@ -108,6 +108,13 @@ typedef struct rnde_node rnde_node;
 typedef struct rnde_comm rnde_comm;   /* gradient collective, see rnde_comm_* below */
 
 const char* rnde_version(void);
+/* Debugging aid.  With the environment variable RNDE_POISON set (read per allocation), every device allocation of the library -- of every
+ * engine and layer below, create-time and grown while a handle runs -- is filled with 0xFF bytes (NaN as float), so that a read of memory
+ * nothing wrote shows up as NaN instead of depending on what the allocator hands back.  The two readers return how many allocations and
+ * how many bytes were filled since the library was loaded (0 while the variable was never set): a test that creates a handle under the
+ * variable checks that they grew. */
+int64_t     rnde_debug_poison_allocs(void);
+int64_t     rnde_debug_poison_bytes(void);
 const char* rnde_last_error(const rnde_node* h); /* h may be NULL: last create error */
 int32_t     rnde_param_count(const rnde_node_config* cfg);
 

@@ -67,6 +67,11 @@ def lib():
     L = C.CDLL(path)
     vp, f, i32, i64p, fp, i32p = C.c_void_p, C.c_float, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_int32)
     L.rnde_version.restype = C.c_char_p
+    if hasattr(L, "rnde_debug_poison_allocs"):      # (an older build loaded through RNDE_LIB for an A/B run has no such readers)
+        L.rnde_debug_poison_allocs.restype = C.c_int64
+        L.rnde_debug_poison_allocs.argtypes = []
+        L.rnde_debug_poison_bytes.restype = C.c_int64
+        L.rnde_debug_poison_bytes.argtypes = []
     L.rnde_last_error.restype = C.c_char_p
     L.rnde_last_error.argtypes = [vp]
     L.rnde_param_count.restype = i32
@@ -219,7 +224,7 @@ def lib():
     return L
 
 
-EXPORTS = ["rnde_version", "rnde_last_error", "rnde_param_count", "rnde_node_create", "rnde_node_destroy",
+EXPORTS = ["rnde_version", "rnde_debug_poison_allocs", "rnde_debug_poison_bytes", "rnde_last_error", "rnde_param_count", "rnde_node_create", "rnde_node_destroy",
            "rnde_node_forward", "rnde_node_forward_saveat", "rnde_node_forward_everystep", "rnde_node_forward_replay", "rnde_node_backward", "rnde_node_backward_async", "rnde_node_release_tape", "rnde_node_forward_host",
            "rnde_node_backward_host", "rnde_node_steps", "rnde_debug_feval", "rnde_debug_attempt",
            "rnde_bench_attempt", "rnde_bench_attempt_taped", "rnde_bench_attempt_cold_tape", "rnde_node_set_timing", "rnde_node_timing", "rnde_node_last_attempts", "rnde_node_fallback_count",

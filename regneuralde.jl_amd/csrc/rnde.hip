@@ -5,6 +5,8 @@
 static thread_local std::string g_create_err;   // last create error of the calling thread (rnde_last_error(NULL)); no process-wide mutable state
 void rnde_set_create_error(const std::string& msg) { g_create_err = msg; }
 extern "C" const char* rnde_version(void) { return "rnde 0.1.0 (gfx950)"; }
+extern "C" int64_t rnde_debug_poison_allocs(void) { return (int64_t)rnde_g_poison_allocs.load(); }      // rnde_alloc.h
+extern "C" int64_t rnde_debug_poison_bytes(void) { return (int64_t)rnde_g_poison_bytes.load(); }
 extern "C" const char* rnde_last_error(const rnde_node* h) { return h ? h->err.c_str() : g_create_err.c_str(); }
 
 extern "C" int32_t rnde_param_count(const rnde_node_config* c) {

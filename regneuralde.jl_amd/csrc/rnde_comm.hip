@@ -10,6 +10,7 @@
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
+#include "rnde_alloc.h"      // every hipMalloc below: the RNDE_POISON wrapper
 
 #include <algorithm>
 #include <atomic>

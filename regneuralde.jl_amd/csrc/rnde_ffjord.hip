@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/rnde.h"
+#include "rnde_alloc.h"          // first among the project headers: every hipMalloc behind it goes through the RNDE_POISON wrapper
 #include "rnde_bffjord.h"
 #include "rnde_bffjordt.h"
 #include "rnde_bffjordc.h"

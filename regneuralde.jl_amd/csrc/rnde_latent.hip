@@ -1,6 +1,7 @@
 // rnde_latent.hip -- C ABI of the latent-ODE caller of the hot path (include/rnde.h: rnde_latent_*) over the kernels of rnde_latent.h.
 // No torch, no oracle, no CPU fallback.
 #include "../../include/rnde.h"
+#include "rnde_alloc.h"       // first among the project headers: every hipMalloc behind it goes through the RNDE_POISON wrapper
 #include "rnde_latent.h"
 #include "rnde_device.h"      // DeviceOnce
 

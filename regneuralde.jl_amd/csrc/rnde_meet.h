@@ -162,7 +162,10 @@ struct MeetRes {
     unsigned epoch = 0; int slot = 0; size_t bytes = 0;      // bytes of xch: max_rows sequence numbers x rows_per_seq x max_wg granules
     hipError_t err = hipSuccess;     // of the last begin
 
-    // xch and the epoch alone (the stage solve: the rest is PersistSync's).  (Neither create goes through rnde_node.h's RNDE_POISON wrapper.)
+    // xch and the epoch alone (the stage solve: the rest is PersistSync's).  Neither create goes through the RNDE_POISON wrapper of
+    // rnde_alloc.h, on purpose (the parenthesised name): these words are protocol state, a tag or an abort word that reads as anything but
+    // "not yet" ends or hangs a meeting.  Both zero EVERYTHING they allocate -- the granules, the XCC ids (the host compares the first n of
+    // them behind a one-XCD launch; a workgroup writes its own before anything else), the abort word and the pinned check words.
     hipError_t create_granules(size_t max_rows, int rows_per_seq, int max_wg) {
         bytes = max_rows * rows_per_seq * max_wg * 8;
         const hipError_t e = (hipMalloc)((void**)&xch, bytes);
@@ -175,6 +178,7 @@ struct MeetRes {
         if (e == hipSuccess) e = (hipMalloc)((void**)&xcc, (size_t)max_wg * 4);
         if (e == hipSuccess) e = (hipMalloc)((void**)&abort_word, 16);
         if (e == hipSuccess) e = hipHostMalloc((void**)&chk, (size_t)(max_wg + 2) * 4);
+        if (e == hipSuccess) e = hipMemset(xcc, 0, (size_t)max_wg * 4);
         if (e == hipSuccess) e = hipMemset(abort_word, 0, 16);
         if (e == hipSuccess) for (int i = 0; i < max_wg + 2; ++i) chk[i] = 0u;
         return e;

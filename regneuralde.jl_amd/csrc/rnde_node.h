@@ -3,6 +3,10 @@
 // classifier head and the optimiser steps).  Not an interface: include/rnde.h is.
 #pragma once
 #include "../../include/rnde.h"
+// The device allocations of the translation units that include this header (rnde.hip, rnde_reverse.hip, rnde_node_tile.hip) go through
+// rnde_alloc.h's wrapper (RNDE_POISON), first among the project headers; the other allocating units (rnde_ffjord.hip, rnde_sde.hip,
+// rnde_latent.hip, rnde_comm.hip) include that header themselves.  MeetRes::create (rnde_meet.h) stays outside it on purpose.
+#include "rnde_alloc.h"
 #include "rnde_fwd.h"
 #include "rnde_bwd.h"
 #include "rnde_stage.h"
@@ -30,16 +34,6 @@
 #include <string>
 #include <vector>
 
-// Every device allocation of the library goes through here.  RNDE_POISON=1 fills fresh memory with 0xFF bytes (NaN as float): a
-// read of something that was never written then shows up as NaN in the results instead of depending on what the allocator hands
-// back (a debugging aid; tests/test_gpu_edge.py runs a solve under it).
-static hipError_t rnde_malloc(void** p, size_t bytes) {
-    const hipError_t e = (hipMalloc)(p, bytes);
-    const bool poison = getenv("RNDE_POISON") != nullptr;       // (read per allocation: allocations are rare)
-    if (e == hipSuccess && poison && bytes) (void)hipMemset(*p, 0xFF, bytes);
-    return e;
-}
-#define hipMalloc(p, n) rnde_malloc((void**)(p), (n))
 
 // rnde_stage_solve.hip (its own translation unit, parameter blocks by address: the same struct definitions on both sides)
 extern "C" hipError_t rnde_launch_stage_solve(const void* stage_params, const void* persist_sync, const void* solve_sync, int act2, int x3, hipStream_t s);

@@ -4,6 +4,7 @@
 // The kernel headers define (non-template) kernels in namespace rnde; rnde.hip includes them too.  This translation unit
 // gets its own copy under another namespace name so that the two objects link into one library.
 #define rnde rnde_sde_tu
+#include "rnde_alloc.h"      // first among the project headers: every hipMalloc behind it goes through the RNDE_POISON wrapper
 #include "rnde_sde.h"
 #include "rnde_sdemw.h"
 #include "rnde_head.h"

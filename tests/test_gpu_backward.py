@@ -227,11 +227,15 @@ def test_retired_column_owner_tiles_are_refused():
 
 @pytest.mark.parametrize("kind,B,tol,scale,saveat,reg", [("test_node", 5, 1e-3, 3.0, np.linspace(0, 1, 7), 1), ("small", 12, 1e-3, 4.0, np.array([0.1, 0.5, 0.9]), 1),
                                                           ("mnist", 19, 1e-3, 3.0, np.linspace(0, 1, 13), 1), ("small", 33, 1e-4, 4.0, np.array([0.0, 0.25, 1.0]), 0),
-                                                          ("small", 7, 1e-3, 4.0, np.array([0.31, 0.32, 0.33, 0.34]), 3)])
+                                                          ("small", 7, 1e-3, 4.0, np.array([0.31, 0.32, 0.33, 0.34]), 3),
+                                                          ("mnist", 19, 1e-3, 3.0, np.linspace(0, 1, 13), 2), ("mnist", 19, 1e-3, 3.0, np.linspace(0, 1, 13), 3)])
 def test_saveat_reverse_matches_oracle(kind, B, tol, scale, saveat, reg):
     """Reverse pass of the {R,true} call methods (neural_ode.jl:79-108,:146-180): the cotangent is the D x T x B array
     Tracker hands back for diffeqsol_to_3dtrackedarray (src/utils.jl:17-19); dense-output points carry their theta
-    dependence on t and dt."""
+    dependence on t and dt.
+    The two MNIST cases with a stiffness callback (reg 2, 3) run, under the default matrix mode, the bf16x3 reverse attempt kernel's saveat +
+    stiffness instantiation (SV = 3), the one at the 256-VGPR limit.  They keep the siblings' bounds: the fp32 CPU oracle is 2.2e-5 / 3.0e-5 /
+    5.1e-5 (reg 2) and 2.9e-6 / 3.9e-6 / 2.8e-5 (reg 3) from the fp64 one on x-bar / p-bar / tspan-bar there, far inside 2e-3."""
     from tests.util import Node, Oracle, rel_err
     from tests.test_gpu_forward import _setup, _cfg
     arch, p, x = _setup(kind, B, 5, scale)
@@ -246,6 +250,7 @@ def test_saveat_reverse_matches_oracle(kind, B, tol, scale, saveat, reg):
     got = n.forward_saveat(x, p, sa, keep_tape=True)
     assert got["nfe"] == ref["nfe"] and len(got["saveval"]) == len(ref["saveval"])
     gx, gp, gt = n.backward(ubar, svbar)
+    print(f"saveat reverse {kind} B={B} reg={reg}: x-bar {rel_err(gx, rx):.2e} p-bar {rel_err(gp, rp):.2e} tspan-bar {np.abs(gt - rt).max() / max(1.0, np.abs(rt).max()):.2e}")
     assert rel_err(gx, rx) < 2e-3
     assert rel_err(gp, rp) < 2e-3
     assert np.abs(gt - rt).max() <= 2e-3 * max(1.0, np.abs(rt).max())
