@@ -115,6 +115,10 @@ const char* rnde_version(void);
  * variable checks that they grew. */
 int64_t     rnde_debug_poison_allocs(void);
 int64_t     rnde_debug_poison_bytes(void);
+/* How many device allocations of the library are live, and their bytes (every engine and layer below, whatever RNDE_POISON says; pinned host
+ * memory is not counted).  A handle that is created, run and destroyed leaves both where they were. */
+int64_t     rnde_debug_live_allocs(void);
+int64_t     rnde_debug_live_bytes(void);
 const char* rnde_last_error(const rnde_node* h); /* h may be NULL: last create error */
 int32_t     rnde_param_count(const rnde_node_config* cfg);
 

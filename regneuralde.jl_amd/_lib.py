@@ -72,6 +72,11 @@ def lib():
         L.rnde_debug_poison_allocs.argtypes = []
         L.rnde_debug_poison_bytes.restype = C.c_int64
         L.rnde_debug_poison_bytes.argtypes = []
+    if hasattr(L, "rnde_debug_live_allocs"):
+        L.rnde_debug_live_allocs.restype = C.c_int64
+        L.rnde_debug_live_allocs.argtypes = []
+        L.rnde_debug_live_bytes.restype = C.c_int64
+        L.rnde_debug_live_bytes.argtypes = []
     L.rnde_last_error.restype = C.c_char_p
     L.rnde_last_error.argtypes = [vp]
     L.rnde_param_count.restype = i32
@@ -224,7 +229,7 @@ def lib():
     return L
 
 
-EXPORTS = ["rnde_version", "rnde_debug_poison_allocs", "rnde_debug_poison_bytes", "rnde_last_error", "rnde_param_count", "rnde_node_create", "rnde_node_destroy",
+EXPORTS = ["rnde_version", "rnde_debug_poison_allocs", "rnde_debug_poison_bytes", "rnde_debug_live_allocs", "rnde_debug_live_bytes", "rnde_last_error", "rnde_param_count", "rnde_node_create", "rnde_node_destroy",
            "rnde_node_forward", "rnde_node_forward_saveat", "rnde_node_forward_everystep", "rnde_node_forward_replay", "rnde_node_backward", "rnde_node_backward_async", "rnde_node_release_tape", "rnde_node_forward_host",
            "rnde_node_backward_host", "rnde_node_steps", "rnde_debug_feval", "rnde_debug_attempt",
            "rnde_bench_attempt", "rnde_bench_attempt_taped", "rnde_bench_attempt_cold_tape", "rnde_node_set_timing", "rnde_node_timing", "rnde_node_last_attempts", "rnde_node_fallback_count",

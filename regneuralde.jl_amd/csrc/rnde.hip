@@ -7,6 +7,8 @@ void rnde_set_create_error(const std::string& msg) { g_create_err = msg; }
 extern "C" const char* rnde_version(void) { return "rnde 0.1.0 (gfx950)"; }
 extern "C" int64_t rnde_debug_poison_allocs(void) { return (int64_t)rnde_g_poison_allocs.load(); }      // rnde_alloc.h
 extern "C" int64_t rnde_debug_poison_bytes(void) { return (int64_t)rnde_g_poison_bytes.load(); }
+extern "C" int64_t rnde_debug_live_allocs(void) { return (int64_t)rnde_g_live_allocs.load(); }
+extern "C" int64_t rnde_debug_live_bytes(void) { return (int64_t)rnde_g_live_bytes.load(); }
 extern "C" const char* rnde_last_error(const rnde_node* h) { return h ? h->err.c_str() : g_create_err.c_str(); }
 
 extern "C" int32_t rnde_param_count(const rnde_node_config* c) {
@@ -65,7 +67,8 @@ static rnde_status chain_create(const rnde_node_config* c, rnde_node** out) {
     if (c->regularize < RNDE_REG_NONE || c->regularize > RNDE_REG_STIFF_DT) { g_create_err = "regularize: unknown value"; return RNDE_ERR_BAD_ARG; }
     if (c->col_tile != 0 && c->col_tile != 64 && c->col_tile != 65) { g_create_err = "col_tile: this network runs on the chain engine (0 = auto, 64 = one wave per column tile, 65 = four waves per column tile)"; return RNDE_ERR_BAD_ARG; }
     if (c->max_batch < 1 || c->max_attempts < 1) { g_create_err = "max_batch / max_attempts"; return RNDE_ERR_BAD_ARG; }
-    rnde_node* h = new rnde_node();
+    std::unique_ptr<rnde_node, void (*)(rnde_node*)> hold(new rnde_node(), rnde_node_destroy);      // (until the last step has succeeded)
+    rnde_node* h = hold.get();
     h->cfg = *c; h->engine = 3; h->cg = G;
     h->D = c->dims[0]; h->H = 0; h->P = rnde_param_count(c); h->BT = 16;
     h->NKD = G.nksD <= 4 ? 4 : (G.nksD <= 8 ? 8 : 16);
@@ -100,7 +103,7 @@ static rnde_status chain_create(const rnde_node_config* c, rnde_node** out) {
         const bool fits = h->mw_lds_f <= 160 * 1024 && h->mw_lds_b <= 160 * 1024;
         const char* e = getenv("RNDE_CHAIN_MW");
         h->mw = (fits && c->col_tile != 64 && !(e && e[0] == '0')) ? 1 : 0;
-        if (c->col_tile == 65 && !fits) { g_create_err = "col_tile 65: the multi-wave kernels need the padded weight fragments in 160 KB of LDS"; delete h; return RNDE_ERR_BAD_ARG; }
+        if (c->col_tile == 65 && !fits) { g_create_err = "col_tile 65: the multi-wave kernels need the padded weight fragments in 160 KB of LDS"; return RNDE_ERR_BAD_ARG; }
         if (h->mw) h->nwg_max = ntiles;
         {   // experiments/latent_ode.jl:113-124 exactly: eight time-independent layers of widths 20 <-> 50
             bool lat = plain_acts && h->mw && c->n_layers == kLatLayers && !c->time_dep && h->NKD == 8;
@@ -108,12 +111,12 @@ static rnde_status chain_create(const rnde_node_config* c, rnde_node** out) {
             const char* e = getenv("RNDE_CHAIN_LAT");
             h->mw_lat = (lat && !(e && e[0] == '0')) ? 1 : 0;
         }
-        if ((c->solver == RNDE_SOLVER_DP5 || c->solver == RNDE_SOLVER_DOP853) && !h->mw) { g_create_err = "DP5 / DOP853 need the multi-wave kernels (weights must fit LDS)"; delete h; return RNDE_ERR_BAD_ARG; }
+        if ((c->solver == RNDE_SOLVER_DP5 || c->solver == RNDE_SOLVER_DOP853) && !h->mw) { g_create_err = "DP5 / DOP853 need the multi-wave kernels (weights must fit LDS)"; return RNDE_ERR_BAD_ARG; }
         h->rk_tab = (h->mw && (c->solver == RNDE_SOLVER_DP5 || getenv("RNDE_CHAIN_TAB") != nullptr)) ? 1 : 0;
         if (c->solver == RNDE_SOLVER_DOP853) {
             // an S-stage pair as a table (csrc/rk_tables.h): the kernels take stage count, tape layout and evaluation counts from it.  Neither a
             // dense output nor the stiffness estimate (k_S - k_{S-1} is not an eigenvalue estimate for an arbitrary pair) exist for it.
-            if (c->regularize >= 2) { g_create_err = "DOP853: callbacks none / error_est only (no stiffness estimate for a table pair)"; delete h; return RNDE_ERR_BAD_ARG; }
+            if (c->regularize >= 2) { g_create_err = "DOP853: callbacks none / error_est only (no stiffness estimate for a table pair)"; return RNDE_ERR_BAD_ARG; }
             h->rk_tab = 2; h->mw_lat = 0; h->rk_S = kDop853S; h->rk_order = kDop853Order;
             RkTab& T = h->rk;
             T = RkTab{};
@@ -167,36 +170,36 @@ static rnde_status chain_create(const rnde_node_config* c, rnde_node** out) {
         }
     }
     h->chain_lds_f = lds_f; h->chain_lds_b = lds_b;
-    if (hipSetDevice(c->device) != hipSuccess) { g_create_err = "hipSetDevice failed"; delete h; return RNDE_ERR_HIP; }
+    if (hipSetDevice(c->device) != hipSuccess) { g_create_err = "hipSetDevice failed"; return RNDE_ERR_HIP; }
     const size_t Ac = (size_t)ntiles * h->NKD * 64;   // fragment-order arrays are padded to NKD k-steps
     h->rec_stride = ChainRec{(long long)Ac, h->rk_S}.total();
-    auto dm = [&](void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess; };
+    auto dm = [](auto& buf, size_t n) { return buf.alloc(n) == hipSuccess; };      // (n elements)
     bool ok = true;
-    ok &= dm((void**)&h->f0, Ac * 4) && dm((void**)&h->u1, Ac * 4) && dm((void**)&h->f1, Ac * 4) && dm((void**)&h->xcopy, (size_t)h->D * h->Bpad_max * 4);
-    ok &= dm((void**)&h->pcopy, (size_t)h->P * 4) && dm((void**)&h->cfrags, (size_t)(G.nfrag_f + G.nfrag_b + G.nfrag_t + 4) * 256);
-    if (h->mw) ok &= dm((void**)&h->mw_tab, mw_tab_floats(h->mg) * 4);
+    ok &= dm(h->f0, Ac) && dm(h->u1, Ac) && dm(h->f1, Ac) && dm(h->xcopy, (size_t)h->D * h->Bpad_max);
+    ok &= dm(h->pcopy, (size_t)h->P) && dm(h->cfrags, (size_t)(G.nfrag_f + G.nfrag_b + G.nfrag_t + 4) * 64);
+    if (h->mw) ok &= dm(h->mw_tab, mw_tab_floats(h->mg));
     if (h->mw) {
         ok &= h->mw_meet.create((size_t)c->max_attempts + 4, 3, kMwMeetMax) == hipSuccess;
-        ok &= hipHostMalloc((void**)&h->h_mw_bchk, (kMwMeetMax + 8) * 4) == hipSuccess && dm((void**)&h->mw_bargs, (size_t)c->max_attempts * 16) &&
-              hipHostMalloc((void**)&h->h_mw_bargs, (size_t)c->max_attempts * 16) == hipSuccess;
+        ok &= dm(h->h_mw_bchk, kMwMeetMax + 8) && dm(h->mw_bargs, (size_t)c->max_attempts * 4) && dm(h->h_mw_bargs, (size_t)c->max_attempts * 4);
         if (ok) memset(h->h_mw_bchk, 0, (kMwMeetMax + 8) * 4);
         if (const char* eb = getenv("RNDE_CHAIN_BSWEEP")) h->mw_bsweep = atoi(eb);
         const char* e = getenv("RNDE_CHAIN_SOLVE");
         if (e && e[0] == '0') h->mw_solve = 0;
     }
-    ok &= dm((void**)&h->ctl, 2 * sizeof(StepState)) && dm((void**)&h->ctl_final, sizeof(StepState));
-    ok &= dm((void**)&h->meta, (size_t)(c->max_attempts + 1) * sizeof(StepMeta)) && dm((void**)&h->initrec, sizeof(InitRec));
-    ok &= dm((void**)&h->errpart, (size_t)(6 * h->nwg_max + 256 + 16) * 4) && dm((void**)&h->initpart, (size_t)(3 * h->nwg_max + 256) * 4);   // (+256: sum_partials reads whole 256-entry blocks; +16: the [2][4] doubles of rnde_epart_reduce_kernel)
-    h->arena_recs = 2;
-    ok &= dm((void**)&h->arena, (size_t)h->arena_recs * h->rec_stride * 4);
-    ok &= hipHostMalloc((void**)&h->h_ctl, sizeof(StepState)) == hipSuccess;
-    ok &= hipHostMalloc((void**)&h->h_meta, (size_t)(c->max_attempts + 1) * sizeof(StepMeta)) == hipSuccess;
-    ok &= hipHostMalloc((void**)&h->h_init, sizeof(InitRec)) == hipSuccess;
-    ok &= hipHostMalloc((void**)&h->h_scal, 64 * sizeof(float)) == hipSuccess;
-    if (!ok) { g_create_err = "device allocation failed"; rnde_node_destroy(h); return RNDE_ERR_HIP; }
+    ok &= dm(h->ctl, 2) && dm(h->own_ctl_final, 1);
+    ok &= dm(h->own_meta, (size_t)(c->max_attempts + 1)) && dm(h->own_initrec, 1);
+    ok &= dm(h->errpart, (size_t)(6 * h->nwg_max + 256 + 16)) && dm(h->initpart, (size_t)(3 * h->nwg_max + 256));   // (+256: sum_partials reads whole 256-entry blocks; +16: the [2][4] doubles of rnde_epart_reduce_kernel)
+    ok &= dm(h->arena, (size_t)2 * h->rec_stride);
+    ok &= dm(h->own_h_ctl, 1);
+    ok &= dm(h->own_h_meta, (size_t)(c->max_attempts + 1));
+    ok &= dm(h->own_h_init, 1);
+    ok &= dm(h->h_scal, 64);
+    if (!ok) { g_create_err = "device allocation failed"; return RNDE_ERR_HIP; }
+    h->ctl_final = h->own_ctl_final; h->meta = h->own_meta; h->initrec = h->own_initrec;
+    h->h_ctl = h->own_h_ctl; h->h_meta = h->own_h_meta; h->h_init = h->own_h_init;
     hipMemset(h->initrec, 0, sizeof(InitRec));
     h->predicted = 12;
-    *out = h;
+    *out = hold.release();
     return RNDE_OK;
 }
 ChainParams make_chain_params(rnde_node* h, const StepParams& P) {
@@ -296,19 +299,15 @@ static rnde_status ensure_mw_slab(rnde_node* h, long long evals, int Bpad, hipSt
         const size_t full_bytes = (size_t)full * per_eval * 4;
         if (full > want && cap_mb > 0 && full_bytes <= (size_t)cap_mb << 20 && hipMemGetInfo(&fr, &tot) == hipSuccess && full_bytes <= fr / 8) want = full;
     }
-    float* nb = nullptr;
+    DevBuf<float> nb;
     HIPCHK(h, hipStreamSynchronize(s));
-    if (hipMalloc((void**)&nb, (size_t)want * per_eval * 4) != hipSuccess) {      // the eager size did not fit after all (fragmentation, a neighbour): what the call needs, no more
+    if (nb.alloc((size_t)want * per_eval) != hipSuccess) {      // the eager size did not fit after all (fragmentation, a neighbour): what the call needs, no more
         (void)hipGetLastError();
-        nb = nullptr;
         want = evals;
-        HIPCHK(h, hipMalloc((void**)&nb, (size_t)want * per_eval * 4));
+        HIPCHK(h, nb.alloc((size_t)want * per_eval));
     }
-    if (h->mw_slab) {
-        HIPCHK(h, hipMemcpy(nb, h->mw_slab, (size_t)h->mw_slab_evals * per_eval * 4, hipMemcpyDeviceToDevice));
-        hipFree(h->mw_slab);
-    }
-    h->mw_slab = nb; h->mw_slab_evals = want;
+    if (h->mw_slab) HIPCHK(h, hipMemcpy(nb, h->mw_slab, (size_t)h->mw_slab_evals * per_eval * 4, hipMemcpyDeviceToDevice));
+    h->mw_slab.swap(nb); h->mw_slab_evals = want;      // (nb goes with what the slab held)
     return RNDE_OK;
 }
 
@@ -354,17 +353,18 @@ extern "C" rnde_status rnde_node_create(const rnde_node_config* c, rnde_node** o
     }
     if (c->col_tile == 64 || c->col_tile == 65 || !mnist_form) return chain_create(c, out);   // small-width chains (latent_ode.jl:113-124): rnde_chain.h
     if (c->regularize < RNDE_REG_NONE || c->regularize > RNDE_REG_STIFF_DT) { g_create_err = "regularize: unknown value"; return RNDE_ERR_BAD_ARG; }
-    rnde_node* h = new rnde_node();
+    std::unique_ptr<rnde_node, void (*)(rnde_node*)> hold(new rnde_node(), rnde_node_destroy);      // (until the last step has succeeded)
+    rnde_node* h = hold.get();
     h->cfg = *c;
     h->D = c->dims[0]; h->H = c->dims[1]; h->P = rnde_param_count(c); h->act2 = c->act[1];
     h->BT = 8;   // (column granularity of the batch padding the tape's copy of x is zero-filled to)
     if (c->col_tile != 0 && c->col_tile != 16) {
         g_create_err = "col_tile must be 0 (auto) or 16 (stage engine) for the two-layer TDChain form; 64 / 65 select the chain engine.  (The round-1 column-owner "
                        "engine, col_tile 4 / 8, was retired in round 4: 126 us per attempted step against 24; its sources are kept under tools/experiments/column_owner/.)";
-        delete h; return RNDE_ERR_BAD_ARG;
+        return RNDE_ERR_BAD_ARG;
     }
     if (h->H + 2 > 128 || h->D < 1 || h->H < 1 || (h->D + 15) / 16 > 64 || c->max_batch < 1 || c->max_attempts < 1) {
-        g_create_err = "shape outside the kernel limits (H <= 126, D <= 1024)"; delete h; return RNDE_ERR_BAD_ARG;
+        g_create_err = "shape outside the kernel limits (H <= 126, D <= 1024)"; return RNDE_ERR_BAD_ARG;
     }
     h->Bpad_max = ((c->max_batch + 15) / 16) * 16;
     // stage engine geometry: WT row tiles (waves) per block chosen to minimise padding, preferring more waves
@@ -376,41 +376,40 @@ extern "C" rnde_status rnde_node_create(const rnde_node_config* c, rnde_node** o
     h->engine = 2;
     h->nwg_max = std::max(h->Bpad_max / h->BT, h->sR * (h->Bpad_max / 16));
     h->stage_lds = sizeof(float) * ((size_t)16 * (16 * std::max(h->sK2b, h->sHT) + 4) + (size_t)16 * (16 * std::max(h->sWT, h->sKHb) + 4) + 64);
-    if (hipSetDevice(c->device) != hipSuccess) { g_create_err = "hipSetDevice failed"; delete h; return RNDE_ERR_HIP; }
+    if (hipSetDevice(c->device) != hipSuccess) { g_create_err = "hipSetDevice failed"; return RNDE_ERR_HIP; }
     const size_t A = (size_t)h->D * h->Bpad_max, HB = (size_t)h->H * h->Bpad_max;
     RecLayout L{(long long)A, (long long)HB};
     h->rec_stride = L.total();
-    auto dm = [&](void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess; };
+    auto dm = [](auto& buf, size_t n) { return buf.alloc(n) == hipSuccess; };      // (n elements)
     bool ok = true;
-    ok &= dm((void**)&h->f0, A * 4) && dm((void**)&h->u1, A * 4) && dm((void**)&h->f1, A * 4) && dm((void**)&h->xcopy, A * 4);
-    ok &= dm((void**)&h->h0, HB * 4) && dm((void**)&h->h1, HB * 4);
-    ok &= dm((void**)&h->pcopy, (size_t)h->P * 4);
-    ok &= dm((void**)&h->spwB, (size_t)h->sMT * h->sK2b * 64 * 16) && dm((void**)&h->spwD, (size_t)h->sHT * h->sMT * 64 * 16);
-    ok &= dm((void**)&h->spwBt, (size_t)h->sMT * h->sKHb * 64 * 16) && dm((void**)&h->spwDt, (size_t)h->sHT * h->sMT * 64 * 16);
-    ok &= dm((void**)&h->slab2, (size_t)2 * (h->Bpad_max / 16) * h->sR * h->sHT * 64 * 16);
+    ok &= dm(h->f0, A) && dm(h->u1, A) && dm(h->f1, A) && dm(h->xcopy, A);
+    ok &= dm(h->h0, HB) && dm(h->h1, HB);
+    ok &= dm(h->pcopy, (size_t)h->P);
+    ok &= dm(h->spwB, (size_t)h->sMT * h->sK2b * 64) && dm(h->spwD, (size_t)h->sHT * h->sMT * 64);
+    ok &= dm(h->spwBt, (size_t)h->sMT * h->sKHb * 64) && dm(h->spwDt, (size_t)h->sHT * h->sMT * 64);
+    ok &= dm(h->slab2, (size_t)2 * (h->Bpad_max / 16) * h->sR * h->sHT * 64 * 4);
     const size_t tslab_bytes = (size_t)kSlabBufs * (h->Bpad_max / 16) * h->sR * h->sHT * 64 * 16;    // buffers of one 16-byte entry per lane and tile: three for the attempts, two for the one-launch solve's start-up
     h->tslab_bytes = tslab_bytes;
-    ok &= dm((void**)&h->tslab, tslab_bytes);
+    ok &= dm(h->tslab, tslab_bytes / 4);
     // mailbox: [0) final controller state | [512) initial-step record | [1016) abort word of the persistent kernels, [1024) their
     // XCC ids | [meta_off) step metadata -- read by the host with ONE copy per chunk (was five)
     static_assert(sizeof(StepState) <= 512 && sizeof(InitRec) <= 504, "mailbox layout");
     h->mbox_meta_off = (1024 + (size_t)h->nwg_max * 4 + 255) / 256 * 256;
     const size_t mbox_bytes = h->mbox_meta_off + (size_t)(c->max_attempts + 1) * sizeof(StepMeta);
-    ok &= dm((void**)&h->mbox, mbox_bytes) && hipHostMalloc((void**)&h->h_mbox, mbox_bytes) == hipSuccess;
+    ok &= dm(h->mbox, mbox_bytes) && dm(h->h_mbox, mbox_bytes);
     if (ok) {
         hipMemset(h->mbox, 0, mbox_bytes);
-        h->ctl_final = (StepState*)h->mbox; h->initrec = (InitRec*)(h->mbox + 512);
+        h->ctl_final = (StepState*)h->mbox.get(); h->initrec = (InitRec*)(h->mbox + 512);
         h->pabort = (unsigned*)(h->mbox + 1016); h->pxcc = (unsigned*)(h->mbox + 1024); h->meta = (StepMeta*)(h->mbox + h->mbox_meta_off);
-        h->h_ctl = (StepState*)h->h_mbox; h->h_init = (InitRec*)(h->h_mbox + 512);
+        h->h_ctl = (StepState*)h->h_mbox.get(); h->h_init = (InitRec*)(h->h_mbox + 512);
         h->h_pchk = (unsigned*)(h->h_mbox + 1016); h->h_meta = (StepMeta*)(h->h_mbox + h->mbox_meta_off);
     }
-    ok &= dm((void**)&h->ctl, 2 * sizeof(StepState));
-    ok &= dm((void**)&h->errpart, (size_t)(6 * h->nwg_max + 256 + 16) * 4) && dm((void**)&h->initpart, (size_t)(3 * h->nwg_max + 256) * 4);   // (+256: sum_partials reads whole 256-entry blocks; +16: the [2][4] doubles of rnde_epart_reduce_kernel)
+    ok &= dm(h->ctl, 2);
+    ok &= dm(h->errpart, (size_t)(6 * h->nwg_max + 256 + 16)) && dm(h->initpart, (size_t)(3 * h->nwg_max + 256));   // (+256: sum_partials reads whole 256-entry blocks; +16: the [2][4] doubles of rnde_epart_reduce_kernel)
     // scratch records: 2 (no-tape ring); grown to max_attempts on the first taped forward
-    h->arena_recs = 2;
-    ok &= dm((void**)&h->arena, (size_t)h->arena_recs * h->rec_stride * 4);
-    ok &= hipHostMalloc((void**)&h->h_scal, 64 * sizeof(float)) == hipSuccess;
-    if (!ok) { g_create_err = "device allocation failed"; rnde_node_destroy(h); return RNDE_ERR_HIP; }
+    ok &= dm(h->arena, (size_t)2 * h->rec_stride);
+    ok &= dm(h->h_scal, 64);
+    if (!ok) { g_create_err = "device allocation failed"; return RNDE_ERR_HIP; }
     hipMemset(h->tslab, 0xFF, tslab_bytes); hipMemset(h->pabort, 0, 8); hipMemset(h->pxcc, 0, (size_t)h->nwg_max * 4);
     {   // tuning knobs: config fields, each with a create-time environment override for A/B tooling (never read per solve)
         const char* e = getenv("RNDE_PERSIST");
@@ -424,7 +423,7 @@ extern "C" rnde_status rnde_node_create(const rnde_node_config* c, rnde_node** o
         if (const char* e6 = getenv("RNDE_STAGE_SOLVE")) h->stage_solve = atoi(e6);
     }
     if (h->persist == 1 && h->stage_solve && c->max_attempts + kSolveInitRows < (int)kMeetRows) {      // meeting granules of the one-launch solve: [attempt | the start-up's two meetings][3][256] x 8 bytes
-        if (h->s_meet.create_granules((size_t)c->max_attempts + kSolveInitRows, 3, 256) != hipSuccess) { g_create_err = "device allocation failed"; rnde_node_destroy(h); return RNDE_ERR_HIP; }
+        if (h->s_meet.create_granules((size_t)c->max_attempts + kSolveInitRows, 3, 256) != hipSuccess) { g_create_err = "device allocation failed"; return RNDE_ERR_HIP; }
     }
     // the stage kernels' Dense layers on the matrix cores (rnde_x3.h): split weight images for the headline geometry (49 row tiles, 7 x 7 (hidden tile, row
     // block) pairs) whenever the one-launch-per-attempt kernels are in use (persist == 1) -- with or without the one-launch solve
@@ -433,59 +432,18 @@ extern "C" rnde_status rnde_node_create(const rnde_node_config* c, rnde_node** o
         if (const char* e7 = getenv("RNDE_X3")) h->x3 = atoi(e7) != 0;
         if (h->sMT == 49 && h->sHT == 7 && h->sR == 7 && h->sWT == 7 && h->D == 784 && h->H == 100 && !h->stage_generic) {
             const size_t img = (size_t)49 * 4 * 3 * 64 * 16;
-            if (hipMalloc(&h->x3B, img) != hipSuccess || hipMalloc(&h->x3D, img) != hipSuccess || hipMalloc(&h->x3Bt, img) != hipSuccess || hipMalloc(&h->x3Dt, img) != hipSuccess) { g_create_err = "device allocation failed"; rnde_node_destroy(h); return RNDE_ERR_HIP; }
+            if (!(dm(h->x3B, img) && dm(h->x3D, img) && dm(h->x3Bt, img) && dm(h->x3Dt, img))) { g_create_err = "device allocation failed"; return RNDE_ERR_HIP; }
         } else h->x3 = 0;
     }
     h->predicted = 12;
-    *out = h;
+    *out = hold.release();
     return RNDE_OK;
 }
 
 extern "C" void rnde_node_destroy(rnde_node* h) {
     if (!h) return;
     node_tiled_destroy(h);
-    void* d[] = {h->f0, h->h0, h->u1, h->f1, h->h1, h->arena, h->xcopy, h->pcopy, h->spwB, h->spwD, h->spwBt, h->spwDt, h->slab2,
-                 h->ctl, h->ctl_final, h->meta, h->initrec, h->errpart, h->initpart};
-    if (h->mbox || h->h_mbox) {   // these alias the mailbox
-        for (void*& p : d) if (p == h->ctl_final || p == h->meta || p == h->initrec) p = nullptr;
-        h->pabort = h->pxcc = nullptr; h->h_pchk = nullptr; h->h_ctl = nullptr; h->h_meta = nullptr; h->h_init = nullptr;
-        if (h->mbox) hipFree(h->mbox);
-        if (h->h_mbox) hipHostFree(h->h_mbox);
-    }
-    for (void* p : d) if (p) hipFree(p);
-    bwd_free(h->bw);
-    if (h->head_ws) hipFree(h->head_ws);
-    if (h->cg_ws) hipFree(h->cg_ws);
-    if (h->ev_host) hipEventDestroy(h->ev_host);
-    if (h->sv_t_dev) hipFree(h->sv_t_dev);
-    if (h->replay_dev) hipFree(h->replay_dev);
-    if (h->cfrags) hipFree(h->cfrags);
-    if (h->mw_tab) hipFree(h->mw_tab);
-    h->mw_meet.destroy();
-    if (h->h_mw_bchk) hipHostFree(h->h_mw_bchk);
-    if (h->h_mw_bargs) hipHostFree(h->h_mw_bargs);
-    if (h->mw_bargs) hipFree(h->mw_bargs);
-    if (h->mw_slab) hipFree(h->mw_slab);
-    if (h->tslab) hipFree(h->tslab);
-    h->s_meet.destroy();
-    if (h->x3B) hipFree(h->x3B);
-    if (h->x3D) hipFree(h->x3D);
-    if (h->x3Bt) hipFree(h->x3Bt);
-    if (h->x3Dt) hipFree(h->x3Dt);
-    if (h->pabort) hipFree(h->pabort);
-    if (h->pxcc) hipFree(h->pxcc);
-    if (h->h_pchk) hipHostFree(h->h_pchk);
-    if (h->cslab) hipFree(h->cslab);
-    if (h->ev_t) hipFree(h->ev_t);
-    if (h->h_ev_t) hipHostFree(h->h_ev_t);
-    for (hipEvent_t e : h->wevents) hipEventDestroy(e);
-    for (hipEvent_t e : h->tev) if (e) hipEventDestroy(e);
-    if (h->wstream) hipStreamDestroy(h->wstream);
-    if (h->h_ctl) hipHostFree(h->h_ctl);
-    if (h->h_meta) hipHostFree(h->h_meta);
-    if (h->h_init) hipHostFree(h->h_init);
-    if (h->h_scal) hipHostFree(h->h_scal);
-    delete h;
+    delete h;      // (every buffer, event and stream is an owner: rnde_node.h)
 }
 
 // ---- SURVEY 8e mode 2: one controller for all shards (include/rnde.h: rnde_node_set_coupling).  Every launch that leaves per-workgroup
@@ -509,11 +467,7 @@ extern "C" rnde_status rnde_node_set_coupling(rnde_node* h, rnde_comm* c, int32_
 }
 
 static rnde_status ensure_arena(rnde_node* h, long long recs) {
-    if (h->arena_recs >= recs) return RNDE_OK;
-    if (h->arena) hipFree(h->arena);
-    h->arena = nullptr; h->arena_recs = 0;
-    HIPCHK(h, hipMalloc((void**)&h->arena, (size_t)recs * h->rec_stride * 4));
-    h->arena_recs = recs;
+    HIPCHK(h, h->arena.reserve((size_t)recs * h->rec_stride));
     return RNDE_OK;
 }
 
@@ -744,12 +698,7 @@ static rnde_status forward_core(rnde_node* h, const float* x_dev, const float* p
             if (!(saveat_host[i] >= t0 && saveat_host[i] <= t1) || (i > 0 && !(saveat_host[i] > saveat_host[i - 1]))) {
                 h->err = "saveat must be increasing and inside [t0, t1]"; return RNDE_ERR_BAD_ARG;
             }
-        if ((size_t)n_saveat > h->sv_cap) {
-            if (h->sv_t_dev) hipFree(h->sv_t_dev);
-            h->sv_t_dev = nullptr; h->sv_cap = 0;
-            HIPCHK(h, hipMalloc((void**)&h->sv_t_dev, (size_t)n_saveat * 4));
-            h->sv_cap = n_saveat;
-        }
+        HIPCHK(h, h->sv_t_dev.reserve((size_t)n_saveat));
         h->saveat.assign(saveat_host, saveat_host + n_saveat);
         HIPCHK(h, hipMemcpyAsync(h->sv_t_dev, h->saveat.data(), (size_t)n_saveat * 4, hipMemcpyHostToDevice, s));
     } else h->saveat.clear();
@@ -776,12 +725,7 @@ static rnde_status forward_core(rnde_node* h, const float* x_dev, const float* p
     StepParams P = make_params(h, x_dev, B, t0, t1, keep_tape ? 1 : 0);
     P.sv_t = n_saveat > 0 ? h->sv_t_dev : nullptr; P.nsave = n_saveat; P.sv_out = sv_out_dev;
     if (h->n_replay > 0) {
-        if ((size_t)h->n_replay > h->replay_cap) {
-            if (h->replay_dev) hipFree(h->replay_dev);
-            h->replay_dev = nullptr; h->replay_cap = 0;
-            HIPCHK(h, hipMalloc((void**)&h->replay_dev, (size_t)h->n_replay * 8));
-            h->replay_cap = h->n_replay;
-        }
+        HIPCHK(h, h->replay_dev.reserve((size_t)h->n_replay * 2));
         HIPCHK(h, hipMemcpyAsync(h->replay_dev, h->replay_host, (size_t)h->n_replay * 8, hipMemcpyHostToDevice, s));
         P.replay = h->replay_dev; P.n_replay = h->n_replay;
     }
@@ -881,8 +825,8 @@ static rnde_status forward_core(rnde_node* h, const float* x_dev, const float* p
 #ifdef RNDE_DIAG
         StageParams SD = SQ;
         if (getenv("RNDE_DIAG_SOLVE")) {      // cycle stamps of workgroup 0, every attempt (tools/diag_solve.py)
-            if (h->diag_buf) hipFree(h->diag_buf);
-            hipMalloc((void**)&h->diag_buf, 16384);
+            h->diag_buf.reset();
+            (void)h->diag_buf.alloc(4096);
             hipMemsetAsync(h->diag_buf, 0, 16384, s);
             SD.F.dbg_out = h->diag_buf;
         }
@@ -960,7 +904,7 @@ static rnde_status forward_core(rnde_node* h, const float* x_dev, const float* p
 #ifdef RNDE_DIAG
                 static const int diag_n = getenv("RNDE_DIAG_FWD") ? atoi(getenv("RNDE_DIAG_FWD")) : -1;   // cycle stamps of THIS attempt of a real solve
                 if (launched == diag_n) {
-                    if (!h->diag_buf) hipMalloc((void**)&h->diag_buf, 8192);
+                    (void)h->diag_buf.reserve(2048);
                     hipMemsetAsync(h->diag_buf, 0, 8192, s);
                     StageParams SD = SQ; SD.F.dbg_out = h->diag_buf;
                     HIPCHK(h, stage_attempt(h, SD, launched, s));
@@ -1136,7 +1080,7 @@ extern "C" rnde_status rnde_node_attempts_ext(rnde_node* h, float* out_host, int
 
 extern "C" rnde_status rnde_node_set_timing(rnde_node* h, int32_t on) {
     if (!h) return RNDE_ERR_BAD_ARG;
-    if (on && !h->tev[0]) for (auto& e : h->tev) HIPCHK(h, hipEventCreate(&e));
+    if (on) for (auto& e : h->tev) HIPCHK(h, e.create());
     h->timing = on ? 1 : 0; h->tev_fwd = h->tev_bwd = false;
     return RNDE_OK;
 }
@@ -1182,13 +1126,12 @@ extern "C" rnde_status rnde_node_forward_host(rnde_node* h, const float* x, cons
                                               float* u_out, int64_t* nfe_out, float* saveval, int32_t* n_saveval_out,
                                               int32_t keep_tape) {
     if (!h) return RNDE_ERR_BAD_ARG;
-    float *xd = nullptr, *pd = nullptr, *ud = nullptr;
+    DevBuf<float> xd, pd, ud;
     const size_t nb = (size_t)h->D * B * 4;
-    HIPCHK(h, hipMalloc((void**)&xd, nb)); HIPCHK(h, hipMalloc((void**)&ud, nb)); HIPCHK(h, hipMalloc((void**)&pd, (size_t)h->P * 4));
+    HIPCHK(h, xd.alloc(nb / 4)); HIPCHK(h, ud.alloc(nb / 4)); HIPCHK(h, pd.alloc((size_t)h->P));
     HIPCHK(h, hipMemcpy(xd, x, nb, hipMemcpyHostToDevice)); HIPCHK(h, hipMemcpy(pd, p, (size_t)h->P * 4, hipMemcpyHostToDevice));
     rnde_status st = rnde_node_forward(h, xd, pd, B, t0, t1, ud, nfe_out, saveval, n_saveval_out, keep_tape, nullptr);
     if (st == RNDE_OK || st == RNDE_ERR_MAX_ATTEMPTS) hipMemcpy(u_out, ud, nb, hipMemcpyDeviceToHost);
-    hipFree(xd); hipFree(pd); hipFree(ud);
     return st;
 }
 
@@ -1316,13 +1259,13 @@ static rnde_status bench_attempt_impl(rnde_node* h, const float* x_dev, const fl
         HIPCHK(h, launch_stage<SM_I2>(h, SQ, 0, 0, s));   // k1 = f(x, 0) into f0
         for (int i = 0; i < 3; ++i) HIPCHK(h, stage_attempt(h, SQ, 0, s));
     }
-    hipEvent_t e0, e1;
-    HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
+    Event e0, e1;
+    HIPCHK(h, e0.create()); HIPCHK(h, e1.create());
     HIPCHK(h, hipEventRecord(e0, s));
     const auto host_t0 = std::chrono::steady_clock::now();
     // taped > 1 (stage engine): every attempt writes ANOTHER record of the arena, `taped` of them in turn -- what a solve does (31 records
     // of 21.7 MB at B = 512: the tape leaves the chip); taped == 1 rewrites record 0, which then lives in the Infinity Cache
-    const int cyc = (taped > 1 && h->engine == 2) ? (int)std::min<long long>(taped, h->arena_recs) : 1;
+    const int cyc = (taped > 1 && h->engine == 2) ? (int)std::min<long long>(taped, (long long)h->arena.cap() / h->rec_stride) : 1;
     for (int i = 0; i < iters; ++i) {
         if (h->engine == 3 && h->mw) HIPCHK(h, launch_mw<MW_STEP>(h, MQ, 0, s));
         else if (h->engine == 3) HIPCHK(h, launch_chain<CM_STEP>(h, CQ, 0, nullptr, s));
@@ -1334,30 +1277,29 @@ static rnde_status bench_attempt_impl(rnde_node* h, const float* x_dev, const fl
     HIPCHK(h, hipEventSynchronize(e1));
     float ms = 0.f;
     HIPCHK(h, hipEventElapsedTime(&ms, e0, e1));
-    hipEventDestroy(e0); hipEventDestroy(e1);
     if (mean_us_out) *mean_us_out = ms * 1000.f / iters;
 #ifdef RNDE_DIAG
     {   // phase stamps of the LAST f evaluation of one launch (workgroup 0), in shader cycles relative to stamp 0 of wave 0
-        unsigned long long* d = nullptr; unsigned long long hst[512] = {0};
-        hipMalloc((void**)&d, sizeof(hst)); hipMemset(d, 0, sizeof(hst));
-        P.dbg_out = (float*)d;
+        DevBuf<unsigned long long> d; unsigned long long hst[512] = {0};
+        (void)d.alloc(512); hipMemset(d, 0, sizeof(hst));
+        P.dbg_out = (float*)d.get();
         if (h->engine == 3 && h->mw) {
-            MQ.F.dbg_out = (float*)d; launch_mw<MW_STEP>(h, MQ, 0, s); hipStreamSynchronize(s); hipMemcpy(hst, d, sizeof(hst), hipMemcpyDeviceToHost);
+            MQ.F.dbg_out = (float*)d.get(); launch_mw<MW_STEP>(h, MQ, 0, s); hipStreamSynchronize(s); hipMemcpy(hst, d, sizeof(hst), hipMemcpyDeviceToHost);
             fprintf(stderr, "mw chain stamps (cycles): LDS fill %lld, controller %lld, state load %lld |", (long long)(hst[1]-hst[0]), (long long)(hst[2]-hst[1]), (long long)(hst[3]-hst[2]));
             for (int i = 4; i <= 9; ++i) fprintf(stderr, " eval%d %lld", i - 3, (long long)(hst[i]-hst[i-1]));
             fprintf(stderr, " | tail %lld total %lld\n  first eval: input->L0 %lld", (long long)(hst[10]-hst[9]), (long long)(hst[10]-hst[0]), (long long)(hst[16]-hst[3]));
             for (int l = 0; l < h->mg.n_layers; ++l) fprintf(stderr, " L%d %lld", l, (long long)(hst[17+l]-hst[16+l]));
             fprintf(stderr, "\n");
-            hipFree(d); return RNDE_OK; }
-        if (h->engine == 3) { CQ.F.dbg_out = (float*)d; launch_chain<CM_STEP>(h, CQ, 0, nullptr, s); hipStreamSynchronize(s); hipMemcpy(hst, d, sizeof(hst), hipMemcpyDeviceToHost);
+            return RNDE_OK; }
+        if (h->engine == 3) { CQ.F.dbg_out = (float*)d.get(); launch_chain<CM_STEP>(h, CQ, 0, nullptr, s); hipStreamSynchronize(s); hipMemcpy(hst, d, sizeof(hst), hipMemcpyDeviceToHost);
             fprintf(stderr, "chain stamps (cycles): fill %lld ctl %lld loads %lld |", (long long)(hst[1]-hst[0]), (long long)(hst[2]-hst[1]), (long long)(hst[3]-hst[2]));
             for (int i = 4; i <= 9; ++i) fprintf(stderr, " st%d %lld", i - 3, (long long)(hst[i]-hst[i-1]));
             fprintf(stderr, " | tail %lld total %lld\n", (long long)(hst[10]-hst[9]), (long long)(hst[10]-hst[0]));
             for (int l = 0; l < h->cg.n_layers; ++l) fprintf(stderr, "  layer %d: bias %lld mm %lld act %lld (gap to next %lld)\n", l, (long long)(hst[17+4*l]-hst[16+4*l]), (long long)(hst[18+4*l]-hst[17+4*l]), (long long)(hst[19+4*l]-hst[18+4*l]), l + 1 < h->cg.n_layers ? (long long)(hst[20+4*l]-hst[19+4*l]) : 0LL);
-            hipFree(d); return RNDE_OK; }
+            return RNDE_OK; }
         if (h->engine == 2 && h->persist == 1) {
-            SQ.F.dbg_out = (float*)d; stage_attempt(h, SQ, 0, s); hipStreamSynchronize(s);
-            hipMemcpy(hst, d, sizeof(hst), hipMemcpyDeviceToHost); hipFree(d);
+            SQ.F.dbg_out = (float*)d.get(); stage_attempt(h, SQ, 0, s); hipStreamSynchronize(s);
+            hipMemcpy(hst, d, sizeof(hst), hipMemcpyDeviceToHost);
             fprintf(stderr, "persistent attempt (workgroup 0 thread 0, cycles): prologue(weights) %lld ctl %lld startC %lld startD %lld\n", 0LL, (long long)(hst[1]-hst[0]), (long long)(hst[2]-hst[1]), (long long)(hst[3]-hst[2]));
             for (int st = 1; st <= 6; ++st) { const unsigned long long* q = hst + 4 + 5 * (st - 1); const unsigned long long prev = st == 1 ? hst[3] : hst[8 + 5 * (st - 2)];
                 if (st < 6) fprintf(stderr, "  stage %d: poll %lld A %lld B %lld C %lld D+put %lld\n", st, (long long)(q[0]-prev), (long long)(q[1]-q[0]), (long long)(q[2]-q[1]), (long long)(q[3]-q[2]), (long long)(q[4]-q[3]));
@@ -1367,9 +1309,9 @@ static rnde_status bench_attempt_impl(rnde_node* h, const float* x_dev, const fl
                 fprintf(stderr, "  stage %d wave %d: %6lld | %6lld %6lld | %6lld | %6lld | %6lld | %6lld\n", st, w, (long long)q[0]-z, (long long)q[1]-z, (long long)q[2]-z, (long long)q[3]-z, (long long)q[4]-z, (long long)q[5]-z, (long long)q[6]-z); }
             return RNDE_OK;
         }
-        SQ.F.dbg_out = (float*)d; stage_attempt(h, SQ, 0, s);
+        SQ.F.dbg_out = (float*)d.get(); stage_attempt(h, SQ, 0, s);
         hipStreamSynchronize(s);
-        hipMemcpy(hst, d, sizeof(hst), hipMemcpyDeviceToHost); hipFree(d);
+        hipMemcpy(hst, d, sizeof(hst), hipMemcpyDeviceToHost);
         fprintf(stderr, "stamps (cycles since wave0 stamp0); column-owner: start sync1 gemm1 sync2 reduce sync3 gemm2 tanh | stage: start scalars A sync B C sync D\n");
         for (int w = 0; w < 8; ++w) { fprintf(stderr, "wave %d:", w); for (int i = 0; i < 8; ++i) fprintf(stderr, " %7lld", (long long)(hst[w * 8 + i] - hst[0])); fprintf(stderr, "\n"); }
     }

@@ -49,27 +49,23 @@ struct BwdParams {
     const double* bsum;                // [2][4] or NULL: the three sums over bpart[parity] already formed by rnde_bpart_reduce_kernel (large batches, round 5)
 };
 
-struct BwdBuffers {
-    float *U = nullptr, *K1 = nullptr, *UB1 = nullptr, *zi2 = nullptr, *zi1 = nullptr, *svb_att = nullptr;
-    BState* bstate = nullptr;
-    IBState* ibstate = nullptr;
-    float *bpart = nullptr, *ipart = nullptr, *tspan_out = nullptr;
-    EvalDesc *ev1 = nullptr, *ev2 = nullptr;
-    float *slab = nullptr, *slab_r = nullptr;   // per-chunk partials; second-level partials of the two-pass reduction
-    size_t slab_floats = 0;
-    float *UTB = nullptr, *UNB = nullptr, *UPB0 = nullptr, *GB = nullptr;   // stage engine scratch
-    EvalDesc *h_ev1 = nullptr, *h_ev2 = nullptr;  // pinned
-    float* h_svb = nullptr;
+struct BwdBuffers {      // (owners, rnde_alloc.h; the three views are marked)
+    DevBuf<float> U, K1, UB1, zi2, zi1, svb_att;
+    DevBuf<unsigned char> bstate_mem;           // [2] BState (stage engine: and the [2][4] sums of rnde_bpart_reduce_kernel behind them)
+    BState* bstate = nullptr;                   // view: bstate_mem
+    DevBuf<IBState> ibstate;
+    DevBuf<float> bpart, ipart, tspan_out;
+    DevBuf<unsigned char> ev1_mem;              // [ev1 | ev2 | svb] back to back: sent in one copy
+    PinBuf<unsigned char> h_ev1_mem;
+    EvalDesc *ev1 = nullptr, *h_ev1 = nullptr;  // views: ev1_mem, h_ev1_mem
+    DevBuf<EvalDesc> ev2;
+    DevBuf<float> slab, slab_r;   // per-chunk partials; second-level partials of the two-pass reduction
+    size_t slab_floats = 0;       // per layer (slab holds two layers)
+    DevBuf<float> UTB, UNB, UPB0, GB;   // stage engine scratch
+    PinBuf<EvalDesc> h_ev2;
+    PinBuf<float> h_svb;
     bool ready = false;
 };
-inline void bwd_free(BwdBuffers& b) {
-    void* d[] = {b.U, b.K1, b.UB1, b.zi2, b.zi1, b.svb_att, b.bstate, b.ibstate, b.bpart, b.ipart, b.tspan_out, b.ev1, b.ev2, b.slab, b.slab_r, b.UTB, b.UNB, b.UPB0, b.GB};
-    for (void* p : d) if (p) (void)hipFree(p);
-    if (b.h_ev1) (void)hipHostFree(b.h_ev1);
-    if (b.h_ev2) (void)hipHostFree(b.h_ev2);
-    if (b.h_svb) (void)hipHostFree(b.h_svb);
-    b = BwdBuffers{};
-}
 
 __device__ __forceinline__ float sgnf(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
 

@@ -6,6 +6,7 @@
 // called with regularize = true).  The *_exact entries run the plain instantiations of the tile driver with the exact trace in the forward
 // solve, on the tape and in the reverse sweep (engines 1 and 2).
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -27,12 +28,16 @@ struct rnde_ffjord {
     std::string err;
     int Bp = 0, T = 0, R = 0;
     size_t lds_bytes = 0;
-    float *ws = nullptr, *tape = nullptr, *norm = nullptr, *e_buf = nullptr, *replay = nullptr;
-    float *rws = nullptr, *pacc = nullptr;
-    StepState* ctl = nullptr;        // [3]: the two live states, then the final one
-    StepMeta* meta = nullptr;        // [max_attempts]
-    InitRec* initrec = nullptr;
-    FfStepRec* rec = nullptr;        // [max_attempts]
+    Event ev[4];                     // (ahead of the buffers: members go in reverse order, the buffers first)
+    // (every allocated member is an owner, rnde_alloc.h; initrec is the one view)
+    DevBuf<float> ws, tape, norm, e_buf, replay;
+    DevBuf<float> rws, pacc;
+    DevBuf<StepState> ctl;           // [3]: the two live states, then the final one
+    PinBuf<StepState> h_fin;         // pinned: the final state of the running solve (an asynchronous copy must not land in a dead stack frame)
+    DevBuf<StepMeta> meta;           // [max_attempts]
+    InitRec* initrec = nullptr;      // view: own_initrec (engine 0) or initrec_t
+    DevBuf<InitRec> own_initrec;
+    DevBuf<FfStepRec> rec;           // [max_attempts]
     std::vector<StepMeta> h_meta;    // step log of the last solve (rnde_ffjord_steps / _timing)
     int n_att = 0, n_acc = 0, B = 0;
     // the taped forward, kept apart from the last solve: an untaped call (an inference probe, sample) between a taped forward and its
@@ -49,20 +54,19 @@ struct rnde_ffjord {
         bool trk = false;            // the handle's track_ctrl setting at the forward: backward runs the tracked sweep
     } tp;
     bool kin_ready = false;          // ws / tape / rws hold D + 3 rows (grown by the first kinetic call)
-    float* e_tape = nullptr;         // the library's probe of a taped forward (e_buf serves untaped calls)
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    DevBuf<float> e_tape;            // the library's probe of a taped forward (e_buf serves untaped calls)
     float fwd_ms = -1.f, rev_ms = -1.f;
     // the tile layout (engine = 1, 2): one workgroup per 16 columns, the workgroups meeting once per attempt
     int engine = 0;
     FtGeo TG{};
     int ntiles_max = 0;
-    float* qt = nullptr;             // engine = 1: [ntiles][HP][HP], the exact trace's matrix per tile (the driver's scratch)
-    InitRec* initrec_t = nullptr;    // [ntiles] (initrec = initrec_t)
-    StepState* ctl_t = nullptr;      // [ntiles]
+    DevBuf<float> qt;                // engine = 1: [ntiles][HP][HP], the exact trace's matrix per tile (the driver's scratch)
+    DevBuf<InitRec> initrec_t;       // [ntiles] (initrec = initrec_t)
+    DevBuf<StepState> ctl_t;         // [ntiles]
     MeetRes meet;                    // the tiles' meeting place (rnde_meet.h)
     FcGeo CG{};                      // engine = 2: the Dense-chain dynamics on the tile layout (cfg holds the shared fields, in_dims = D)
     bool track_ctrl = false;         // rnde_ffjord_set_track_ctrl: taped forwards are reversed with the controller differentiated
-    FfAttRec* att = nullptr;         // [max_attempts]: the tracked sweep's attempt records (allocated when tracking is first switched on)
+    DevBuf<FfAttRec> att;            // [max_attempts]: the tracked sweep's attempt records (allocated when tracking is first switched on)
 };
 
 #define FCHK(h, x)                                                                                  \
@@ -102,10 +106,12 @@ static const char* ff_refusal(const rnde_ffjord_config* c, bool tiled = false) {
     return nullptr;
 }
 
-// The buffers, kernel attributes and XCD slot of a handle of the tile layout, for the dynamics Dyn with geometry G (h->cfg is filled; on
-// failure the handle is destroyed).
+using FfHold = std::unique_ptr<rnde_ffjord, void (*)(rnde_ffjord*)>;      // a handle under construction: destroyed unless the last step releases it
+
+// The buffers, kernel attributes and XCD slot of a handle of the tile layout, for the dynamics Dyn with geometry G (h->cfg is filled).
 template <class Dyn>
-static rnde_status tile_create(rnde_ffjord* h, const typename Dyn::Geo& G, rnde_ffjord** out) {
+static rnde_status tile_create(FfHold hold, const typename Dyn::Geo& G, rnde_ffjord** out) {
+    rnde_ffjord* h = hold.get();
     const rnde_ffjord_config* c = &h->cfg;
     const int D = G.D, R = D + 1;
     h->R = R;
@@ -113,42 +119,44 @@ static rnde_status tile_create(rnde_ffjord* h, const typename Dyn::Geo& G, rnde_
     h->Bp = 16 * h->ntiles_max;
     h->T = kFtThreads;
     h->lds_bytes = (size_t)Dyn::lds_floats(G) * 4;
-    auto fail = [&](hipError_t e) { g_ff_create_err = std::string("HIP: ") + hipGetErrorString(e); rnde_ffjord_destroy(h); return RNDE_ERR_HIP; };
+    auto fail = [&](hipError_t e) { g_ff_create_err = std::string("HIP: ") + hipGetErrorString(e); return RNDE_ERR_HIP; };
     hipError_t e;
     const size_t RB = (size_t)R * h->Bp, MA = (size_t)c->max_attempts, NT = (size_t)h->ntiles_max;
-    if ((e = hipMalloc(&h->ws, 10 * RB * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->tape, (MA + 1) * RB * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->norm, (8 * NT + 512) * 4)) != hipSuccess) return fail(e);
+    if ((e = h->ws.alloc(10 * RB)) != hipSuccess) return fail(e);
+    if ((e = h->tape.alloc((MA + 1) * RB)) != hipSuccess) return fail(e);
+    if ((e = h->norm.alloc((8 * NT + 512))) != hipSuccess) return fail(e);
     if ((e = hipMemset(h->norm, 0, (8 * NT + 512) * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->e_buf, (size_t)D * h->Bp * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->e_tape, (size_t)D * h->Bp * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->replay, 2 * MA * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->rws, NT * Dyn::rev_ws_floats(G) * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->pacc, NT * G.P * 4)) != hipSuccess) return fail(e);
-    if (Dyn::scratch_floats(G) && (e = hipMalloc(&h->qt, NT * Dyn::scratch_floats(G) * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->ctl, 3 * sizeof(StepState))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->ctl_t, NT * sizeof(StepState))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->meta, MA * sizeof(StepMeta))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->initrec_t, NT * sizeof(InitRec))) != hipSuccess) return fail(e);
+    if ((e = h->e_buf.alloc((size_t)D * h->Bp)) != hipSuccess) return fail(e);
+    if ((e = h->e_tape.alloc((size_t)D * h->Bp)) != hipSuccess) return fail(e);
+    if ((e = h->replay.alloc(2 * MA)) != hipSuccess) return fail(e);
+    if ((e = h->rws.alloc(NT * Dyn::rev_ws_floats(G))) != hipSuccess) return fail(e);
+    if ((e = h->pacc.alloc(NT * G.P)) != hipSuccess) return fail(e);
+    if (Dyn::scratch_floats(G) && (e = h->qt.alloc(NT * Dyn::scratch_floats(G))) != hipSuccess) return fail(e);
+    if ((e = h->ctl.alloc(3)) != hipSuccess) return fail(e);
+    if ((e = h->ctl_t.alloc(NT)) != hipSuccess) return fail(e);
+    if ((e = h->meta.alloc(MA)) != hipSuccess) return fail(e);
+    if ((e = h->initrec_t.alloc(NT)) != hipSuccess) return fail(e);
     h->initrec = h->initrec_t;
-    if ((e = hipMalloc(&h->rec, MA * sizeof(FfStepRec))) != hipSuccess) return fail(e);
+    if ((e = h->rec.alloc(MA)) != hipSuccess) return fail(e);
     if ((e = h->meet.create(MA + 4, 3, kMwMeetMax)) != hipSuccess) return fail(e);
     for (const void* k : {(const void*)rnde_tile_solve_kernel<Dyn, false>, (const void*)rnde_tile_reverse_kernel<Dyn, false>,
                           (const void*)rnde_tile_feval_kernel<Dyn, false>, (const void*)rnde_tile_solve_kernel<Dyn, true>,
                           (const void*)rnde_tile_reverse_kernel<Dyn, true>, (const void*)rnde_tile_feval_kernel<Dyn, true>,
                           (const void*)rnde_tile_reverse_kernel<Dyn, false, true>})
         if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes)) != hipSuccess) return fail(e);
-    for (auto& v : h->ev) if ((e = hipEventCreate(&v)) != hipSuccess) return fail(e);
-    *out = h;
+    for (auto& v : h->ev) if ((e = v.create()) != hipSuccess) return fail(e);
+    if ((e = h->h_fin.alloc(1)) != hipSuccess) return fail(e);
+    *out = hold.release();
     return RNDE_OK;
 }
 
 // A handle on the selected device, or NULL with the create error set.
-static rnde_ffjord* ff_new_handle(int device, rnde_status* st) {
+static FfHold ff_new_handle(int device, rnde_status* st) {
+    FfHold none(nullptr, rnde_ffjord_destroy);
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) { g_ff_create_err = "no HIP device"; *st = RNDE_ERR_NO_DEVICE; return nullptr; }
-    if (hipSetDevice(device) != hipSuccess) { g_ff_create_err = "hipSetDevice failed"; *st = RNDE_ERR_NO_DEVICE; return nullptr; }
-    return new rnde_ffjord();
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) { g_ff_create_err = "no HIP device"; *st = RNDE_ERR_NO_DEVICE; return none; }
+    if (hipSetDevice(device) != hipSuccess) { g_ff_create_err = "hipSetDevice failed"; *st = RNDE_ERR_NO_DEVICE; return none; }
+    return FfHold(new rnde_ffjord(), rnde_ffjord_destroy);
 }
 
 extern "C" rnde_status rnde_ffjord_create_tiled(const rnde_ffjord_config* c, rnde_ffjord** out) {
@@ -156,7 +164,7 @@ extern "C" rnde_status rnde_ffjord_create_tiled(const rnde_ffjord_config* c, rnd
     *out = nullptr;
     if (const char* why = ff_refusal(c, true)) { g_ff_create_err = why; return RNDE_ERR_BAD_ARG; }
     rnde_status st = RNDE_OK;
-    rnde_ffjord* h = ff_new_handle(c->device, &st);
+    FfHold h = ff_new_handle(c->device, &st);
     if (!h) return st;
     h->cfg = *c;
     h->engine = 1;
@@ -164,10 +172,10 @@ extern "C" rnde_status rnde_ffjord_create_tiled(const rnde_ffjord_config* c, rnd
     h->TG = ft_geo(c->in_dims, c->hidden);
     if ((size_t)FtDyn::lds_floats(h->TG) * 4 > (size_t)kFtLdsBytes) {
         g_ff_create_err = "TrackedFFJORD tiled engine: a tile does not fit in LDS";
-        delete h;
         return RNDE_ERR_BAD_ARG;
     }
-    return tile_create<FtDyn>(h, h->TG, out);
+    const FtGeo G = h->TG;
+    return tile_create<FtDyn>(std::move(h), G, out);
 }
 
 extern "C" int32_t rnde_ffjord_engine(const rnde_ffjord* h) { return h ? h->engine : -1; }
@@ -204,7 +212,7 @@ extern "C" rnde_status rnde_ffjord_set_track_ctrl(rnde_ffjord* h, int32_t on) {
     }
     if (on && !h->att) {
         if (rnde_status st = h->engine == 2 ? trk_residency<FcDyn>(h) : trk_residency<FtDyn>(h)) return st;
-        FCHK(h, hipMalloc(&h->att, (size_t)h->cfg.max_attempts * sizeof(FfAttRec)));
+        FCHK(h, h->att.alloc((size_t)h->cfg.max_attempts));
     }
     h->track_ctrl = on != 0;
     return RNDE_OK;
@@ -266,7 +274,7 @@ extern "C" rnde_status rnde_ffjord_create_chain(const rnde_ffjord_chain_config* 
     *out = nullptr;
     if (const char* why = fc_refusal(c)) { g_ff_create_err = why; return RNDE_ERR_BAD_ARG; }
     rnde_status st = RNDE_OK;
-    rnde_ffjord* h = ff_new_handle(c->device, &st);
+    FfHold h = ff_new_handle(c->device, &st);
     if (!h) return st;
     h->engine = 2;
     h->CG = fc_geo(c->n_layers, c->dims, c->act, c->time_dep);
@@ -278,7 +286,8 @@ extern "C" rnde_status rnde_ffjord_create_chain(const rnde_ffjord_chain_config* 
     k.max_attempts = c->max_attempts; k.device = c->device;
     h->G = FfGeo{};
     h->G.D = D; h->G.H = 0; h->G.P = h->CG.P;
-    return tile_create<FcDyn>(h, h->CG, out);
+    const FcGeo G = h->CG;
+    return tile_create<FcDyn>(std::move(h), G, out);
 }
 
 extern "C" rnde_status rnde_ffjord_create(const rnde_ffjord_config* c, rnde_ffjord** out) {
@@ -288,7 +297,8 @@ extern "C" rnde_status rnde_ffjord_create(const rnde_ffjord_config* c, rnde_ffjo
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= c->device) { g_ff_create_err = "no HIP device"; return RNDE_ERR_NO_DEVICE; }
     if (hipSetDevice(c->device) != hipSuccess) { g_ff_create_err = "hipSetDevice failed"; return RNDE_ERR_NO_DEVICE; }
-    rnde_ffjord* h = new rnde_ffjord();
+    FfHold hold(new rnde_ffjord(), rnde_ffjord_destroy);
+    rnde_ffjord* h = hold.get();
     h->cfg = *c;
     h->G = ff_geo(c->in_dims, c->hidden);
     const int D = c->in_dims, R = D + 1, HS = std::max(c->hidden, D), HR = std::max(c->hidden, R);
@@ -299,39 +309,33 @@ extern "C" rnde_status rnde_ffjord_create(const rnde_ffjord_config* c, rnde_ffjo
         const size_t bytes = ((size_t)h->G.P + 32 + (size_t)3 * HS * T) * 4;
         if (bytes <= 160 * 1024 && (T <= h->Bp || T == 64)) { h->T = T; h->lds_bytes = bytes; break; }
     }
-    auto fail = [&](hipError_t e) { g_ff_create_err = std::string("HIP: ") + hipGetErrorString(e); rnde_ffjord_destroy(h); return RNDE_ERR_HIP; };
+    auto fail = [&](hipError_t e) { g_ff_create_err = std::string("HIP: ") + hipGetErrorString(e); return RNDE_ERR_HIP; };
     hipError_t e;
-    if (!h->T) { g_ff_create_err = "TrackedFFJORD: parameters and per-column vectors do not fit in LDS"; delete h; return RNDE_ERR_BAD_ARG; }
+    if (!h->T) { g_ff_create_err = "TrackedFFJORD: parameters and per-column vectors do not fit in LDS"; return RNDE_ERR_BAD_ARG; }
     const size_t RB = (size_t)R * h->Bp, MA = (size_t)c->max_attempts;
-    if ((e = hipMalloc(&h->ws, 10 * RB * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->tape, (MA + 1) * RB * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->norm, 512 * 4)) != hipSuccess) return fail(e);
+    if ((e = h->ws.alloc(10 * RB)) != hipSuccess) return fail(e);
+    if ((e = h->tape.alloc((MA + 1) * RB)) != hipSuccess) return fail(e);
+    if ((e = h->norm.alloc(512)) != hipSuccess) return fail(e);
     if ((e = hipMemset(h->norm, 0, 512 * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->e_buf, (size_t)D * h->Bp * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->e_tape, (size_t)D * h->Bp * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->replay, 2 * MA * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->rws, (size_t)(24 + kFfVjpVecs) * HR * h->Bp * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->pacc, (size_t)h->G.P * h->Bp * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->ctl, 3 * sizeof(StepState))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->meta, MA * sizeof(StepMeta))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->initrec, sizeof(InitRec))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&h->rec, MA * sizeof(FfStepRec))) != hipSuccess) return fail(e);
+    if ((e = h->e_buf.alloc((size_t)D * h->Bp)) != hipSuccess) return fail(e);
+    if ((e = h->e_tape.alloc((size_t)D * h->Bp)) != hipSuccess) return fail(e);
+    if ((e = h->replay.alloc(2 * MA)) != hipSuccess) return fail(e);
+    if ((e = h->rws.alloc((size_t)(24 + kFfVjpVecs) * HR * h->Bp)) != hipSuccess) return fail(e);
+    if ((e = h->pacc.alloc((size_t)h->G.P * h->Bp)) != hipSuccess) return fail(e);
+    if ((e = h->ctl.alloc(3)) != hipSuccess) return fail(e);
+    if ((e = h->meta.alloc(MA)) != hipSuccess) return fail(e);
+    if ((e = h->own_initrec.alloc(1)) != hipSuccess) return fail(e);
+    h->initrec = h->own_initrec;
+    if ((e = h->rec.alloc(MA)) != hipSuccess) return fail(e);
     for (const void* k : {(const void*)rnde_ffjord_solve_kernel<false>, (const void*)rnde_ffjord_solve_kernel<true>})
         if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes)) != hipSuccess) return fail(e);
-    for (auto& v : h->ev) if ((e = hipEventCreate(&v)) != hipSuccess) return fail(e);
-    *out = h;
+    for (auto& v : h->ev) if ((e = v.create()) != hipSuccess) return fail(e);
+    if ((e = h->h_fin.alloc(1)) != hipSuccess) return fail(e);
+    *out = hold.release();
     return RNDE_OK;
 }
 
-extern "C" void rnde_ffjord_destroy(rnde_ffjord* h) {
-    if (!h) return;
-    for (void* p : {(void*)h->ws, (void*)h->tape, (void*)h->norm, (void*)h->e_buf, (void*)h->e_tape, (void*)h->replay, (void*)h->rws, (void*)h->pacc,
-                    (void*)h->ctl, (void*)h->meta, (void*)h->initrec, (void*)h->rec, (void*)h->qt, (void*)h->ctl_t, (void*)h->att})
-        if (p) (void)hipFree(p);
-    h->meet.destroy();
-    for (auto& v : h->ev) if (v) (void)hipEventDestroy(v);
-    delete h;
-}
+extern "C" void rnde_ffjord_destroy(rnde_ffjord* h) { delete h; }      // (every buffer and event is an owner)
 
 // The first kinetic call of a handle: the limits, then state, tape and reverse workspace for D + 3 rows.  Plain calls go on using the
 // same buffers with their own D + 1 row layout; a plain tape waiting for its backward is carried over.
@@ -358,18 +362,16 @@ static rnde_status ff_kinetic_ready(rnde_ffjord* h) {
                        : h->engine == 1 ? (size_t)h->ntiles_max * FtDyn::rev_ws_floats(h->TG, true)
                                         : (size_t)(24 + kFfVjpVecsKin) * std::max(H, Rk) * h->Bp;
     FCHK(h, hipDeviceSynchronize());           // (rnde_ffjord_debug_feval does not wait for its launch)
-    float *ws = nullptr, *tape = nullptr, *rw = nullptr;
-    hipError_t e = hipMalloc(&ws, 10 * RBk * 4);
-    if (e == hipSuccess) e = hipMalloc(&tape, (MA + 1) * RBk * 4);
-    if (e == hipSuccess) e = hipMalloc(&rw, rws * 4);
+    DevBuf<float> ws, tape, rw;      // (the handle keeps what it has unless all three are there)
+    hipError_t e = ws.alloc(10 * RBk);
+    if (e == hipSuccess) e = tape.alloc((MA + 1) * RBk);
+    if (e == hipSuccess) e = rw.alloc(rws);
     if (e == hipSuccess && h->tp.valid) e = hipMemcpy(tape, h->tape, ((size_t)h->tp.n_acc + 1) * RB * 4, hipMemcpyDeviceToDevice);
     if (e != hipSuccess) {
-        for (float* q : {ws, tape, rw}) if (q) (void)hipFree(q);
         h->err = std::string("TrackedFFJORD kinetic energy rows: HIP: ") + hipGetErrorString(e);
         return RNDE_ERR_HIP;
     }
-    (void)hipFree(h->ws); (void)hipFree(h->tape); (void)hipFree(h->rws);
-    h->ws = ws; h->tape = tape; h->rws = rw;
+    h->ws.swap(ws); h->tape.swap(tape); h->rws.swap(rw);      // (the old three go with the locals)
     h->kin_ready = true;
     return RNDE_OK;
 }
@@ -461,8 +463,8 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
     else hipLaunchKernelGGL(rnde_ffjord_solve_kernel<false>, dim3(1), dim3(h->T), h->lds_bytes, s, Q);
     FCHK(h, hipGetLastError());
     FCHK(h, hipEventRecord(h->ev[1], s));
-    StepState fin;
-    FCHK(h, hipMemcpyAsync(&fin, h->ctl + 2, sizeof(StepState), hipMemcpyDeviceToHost, s));
+    const StepState& fin = *h->h_fin;
+    FCHK(h, hipMemcpyAsync(h->h_fin, h->ctl + 2, sizeof(StepState), hipMemcpyDeviceToHost, s));
     if (tiles) FCHK(h, h->meet.queue_check(meet, s));
     FCHK(h, hipStreamSynchronize(s));
     (void)hipEventElapsedTime(&h->fwd_ms, h->ev[0], h->ev[1]);

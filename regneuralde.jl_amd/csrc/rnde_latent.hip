@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <string>
 
 constexpr int kFusedSegs = 16;             // segments of the first reduction level over those partials
@@ -16,12 +17,13 @@ using namespace rnde_lat;
 
 struct rnde_latent {
     rnde_latent_config cfg{};
-    float *act = nullptr, *del = nullptr, *y = nullptr, *yb = nullptr, *h1 = nullptr, *out = nullptr, *d1 = nullptr, *d2 = nullptr;
-    float *kl = nullptr, *ll = nullptr, *gD = nullptr, *eps = nullptr;
-    float *raw = nullptr, *raw2 = nullptr, *raw_side = nullptr, *raw2_side = nullptr;      // accumulator images of the fused weight-gradient passes (main stream: up to 144 tiles; side stream: 28)
+    Stream side; Event ev_fork, ev_join;      // rec_to_gen's weight gradients run beside the reverse GRU (32 workgroups); ahead of the buffers: members go in reverse order
+    // (every allocated member is an owner, rnde_alloc.h; the handle holds no view)
+    DevBuf<float> act, del, y, yb, h1, out, d1, d2;
+    DevBuf<float> kl, ll, gD, eps;
+    DevBuf<float> raw, raw2, raw_side, raw2_side;      // accumulator images of the fused weight-gradient passes (main stream: up to 144 tiles; side stream: 28)
     int B = 0, T = 0;
     bool encoded = false;
-    hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;      // rec_to_gen's weight gradients run beside the reverse GRU (32 workgroups)
     std::string err;
 };
 static thread_local std::string g_latent_err;
@@ -45,29 +47,25 @@ extern "C" rnde_status rnde_latent_create(const rnde_latent_config* c, rnde_late
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= c->device) { g_latent_err = "no HIP device"; return RNDE_ERR_NO_DEVICE; }
     if (c->max_batch < 1 || c->max_T < 1 || c->max_T > 64) { g_latent_err = "max_batch >= 1, 1 <= max_T <= 64 (one thread per save time in the likelihood kernel)"; return RNDE_ERR_BAD_ARG; }
     if (hipSetDevice(c->device) != hipSuccess) { g_latent_err = "hipSetDevice failed"; return RNDE_ERR_HIP; }
-    rnde_latent* h = new rnde_latent();
+    std::unique_ptr<rnde_latent, void (*)(rnde_latent*)> hold(new rnde_latent(), rnde_latent_destroy);      // (until the last step has succeeded)
+    rnde_latent* h = hold.get();
     h->cfg = *c;
     const size_t S = (size_t)c->max_batch * c->max_T, B = c->max_batch;
-    bool ok = hipMalloc((void**)&h->act, S * kActLd * 4) == hipSuccess && hipMalloc((void**)&h->del, S * kDelLd * 4) == hipSuccess &&
-              hipMalloc((void**)&h->y, B * 2 * kL * 4) == hipSuccess && hipMalloc((void**)&h->yb, B * 2 * kL * 4) == hipSuccess &&
-              hipMalloc((void**)&h->h1, B * kRec * 4) == hipSuccess && hipMalloc((void**)&h->out, B * 2 * kLat * 4) == hipSuccess &&
-              hipMalloc((void**)&h->d1, B * kRec * 4) == hipSuccess && hipMalloc((void**)&h->d2, B * 2 * kLat * 4) == hipSuccess &&
-              hipMalloc((void**)&h->kl, B * 4) == hipSuccess && hipMalloc((void**)&h->ll, B * 4) == hipSuccess &&
-              hipMalloc((void**)&h->gD, S * 40 * 4) == hipSuccess && hipMalloc((void**)&h->eps, B * kLat * 4) == hipSuccess;
-    ok = ok && hipMalloc((void**)&h->raw, (size_t)kFusedWgradGroups * kFwWaves * kFwTilesPerWave * 256 * 4) == hipSuccess && hipMalloc((void**)&h->raw2, (size_t)kFusedSegs * kFwWaves * kFwTilesPerWave * 256 * 4) == hipSuccess &&
-         hipMalloc((void**)&h->raw_side, (size_t)kFusedWgradGroups * 32 * 256 * 4) == hipSuccess && hipMalloc((void**)&h->raw2_side, (size_t)kFusedSegs * 32 * 256 * 4) == hipSuccess;
-    ok = ok && hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) == hipSuccess;
-    if (!ok) { g_latent_err = "device allocation failed"; rnde_latent_destroy(h); return RNDE_ERR_HIP; }
-    *out = h;
+    auto dm = [](DevBuf<float>& buf, size_t n) { return buf.alloc(n) == hipSuccess; };      // (n floats)
+    bool ok = dm(h->act, S * kActLd) && dm(h->del, S * kDelLd) && dm(h->y, B * 2 * kL) && dm(h->yb, B * 2 * kL) && dm(h->h1, B * kRec) &&
+              dm(h->out, B * 2 * kLat) && dm(h->d1, B * kRec) && dm(h->d2, B * 2 * kLat) && dm(h->kl, B) && dm(h->ll, B) && dm(h->gD, S * 40) &&
+              dm(h->eps, B * kLat);
+    ok = ok && dm(h->raw, (size_t)kFusedWgradGroups * kFwWaves * kFwTilesPerWave * 256) && dm(h->raw2, (size_t)kFusedSegs * kFwWaves * kFwTilesPerWave * 256) &&
+         dm(h->raw_side, (size_t)kFusedWgradGroups * 32 * 256) && dm(h->raw2_side, (size_t)kFusedSegs * 32 * 256);
+    ok = ok && hipStreamCreateWithFlags(&h->side.s, hipStreamNonBlocking) == hipSuccess && h->ev_fork.create(hipEventDisableTiming) == hipSuccess &&
+         h->ev_join.create(hipEventDisableTiming) == hipSuccess;
+    if (!ok) { g_latent_err = "device allocation failed"; return RNDE_ERR_HIP; }
+    *out = hold.release();
     return RNDE_OK;
 }
 extern "C" void rnde_latent_destroy(rnde_latent* h) {
     if (!h) return;
-    if (h->side) { (void)hipStreamSynchronize(h->side); (void)hipStreamDestroy(h->side); }
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    for (float* p : {h->act, h->del, h->y, h->yb, h->h1, h->out, h->d1, h->d2, h->kl, h->ll, h->gD, h->eps, h->raw, h->raw2, h->raw_side, h->raw2_side}) if (p) (void)hipFree(p);
+    if (h->side) (void)hipStreamSynchronize(h->side);      // (what runs there reads the buffers)
     delete h;
 }
 

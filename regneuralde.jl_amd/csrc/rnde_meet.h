@@ -9,6 +9,7 @@
 // participants share one L2: 8 x n workgroups are launched, every eighth works and records its XCC id, and the host checks behind the launch
 // that the ids agree (meet_verdict) -- a solve whose workgroups were split is thrown away.
 #pragma once
+#include "rnde_alloc.h"
 #include "rnde_device.h"
 
 namespace rnde {
@@ -157,40 +158,36 @@ inline bool meet_next_epoch(unsigned& epoch) { if (++epoch < kMeetEpochs) return
 
 // A handle's meeting place; slot: the XCD its one-XCD launches work on (blockIdx % 8 == slot; handles take turns: two streams, two XCDs).
 struct MeetRes {
-    unsigned long long* xch = nullptr; unsigned* xcc = nullptr; unsigned* abort_word = nullptr;
-    unsigned* chk = nullptr;         // pinned: [2 + max_wg]
-    unsigned epoch = 0; int slot = 0; size_t bytes = 0;      // bytes of xch: max_rows sequence numbers x rows_per_seq x max_wg granules
+    // (owners, rnde_alloc.h: counted, and released with the handle that holds the MeetRes)
+    Buf<unsigned long long, DevPlain> xch;      // max_rows sequence numbers x rows_per_seq x max_wg granules
+    Buf<unsigned, DevPlain> xcc, abort_word;
+    PinBuf<unsigned> chk;            // pinned: [2 + max_wg]
+    unsigned epoch = 0; int slot = 0;
     hipError_t err = hipSuccess;     // of the last begin
 
-    // xch and the epoch alone (the stage solve: the rest is PersistSync's).  Neither create goes through the RNDE_POISON wrapper of
-    // rnde_alloc.h, on purpose (the parenthesised name): these words are protocol state, a tag or an abort word that reads as anything but
+    // xch and the epoch alone (the stage solve: the rest is PersistSync's).  Neither create goes through the RNDE_POISON fill of
+    // rnde_alloc.h, on purpose (the DevPlain policy): these words are protocol state, a tag or an abort word that reads as anything but
     // "not yet" ends or hangs a meeting.  Both zero EVERYTHING they allocate -- the granules, the XCC ids (the host compares the first n of
     // them behind a one-XCD launch; a workgroup writes its own before anything else), the abort word and the pinned check words.
     hipError_t create_granules(size_t max_rows, int rows_per_seq, int max_wg) {
-        bytes = max_rows * rows_per_seq * max_wg * 8;
-        const hipError_t e = (hipMalloc)((void**)&xch, bytes);
-        return e == hipSuccess ? hipMemset(xch, 0, bytes) : e;
+        const hipError_t e = xch.alloc(max_rows * rows_per_seq * max_wg);
+        return e == hipSuccess ? hipMemset(xch, 0, xch.cap() * 8) : e;
     }
     hipError_t create(size_t max_rows, int rows_per_seq, int max_wg) {
         static std::atomic<int> next_slot{0};
         slot = next_slot.fetch_add(1) & 7;
         hipError_t e = create_granules(max_rows, rows_per_seq, max_wg);
-        if (e == hipSuccess) e = (hipMalloc)((void**)&xcc, (size_t)max_wg * 4);
-        if (e == hipSuccess) e = (hipMalloc)((void**)&abort_word, 16);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&chk, (size_t)(max_wg + 2) * 4);
+        if (e == hipSuccess) e = xcc.alloc((size_t)max_wg);
+        if (e == hipSuccess) e = abort_word.alloc(4);
+        if (e == hipSuccess) e = chk.alloc((size_t)max_wg + 2);
         if (e == hipSuccess) e = hipMemset(xcc, 0, (size_t)max_wg * 4);
         if (e == hipSuccess) e = hipMemset(abort_word, 0, 16);
         if (e == hipSuccess) for (int i = 0; i < max_wg + 2; ++i) chk[i] = 0u;
         return e;
     }
-    void destroy() {
-        for (void* p : {(void*)xch, (void*)xcc, (void*)abort_word}) if (p) (void)hipFree(p);
-        if (chk) (void)hipHostFree(chk);
-        xch = nullptr; xcc = nullptr; abort_word = nullptr; chk = nullptr;
-    }
     // The parameter block of the next launch's meetings of n workgroups; allow_local: the one-XCD form while they fit one.
     Meet begin(int n, bool allow_local, hipStream_t s) {
-        err = meet_next_epoch(epoch) ? hipMemsetAsync(xch, 0, bytes, s) : hipSuccess;
+        err = meet_next_epoch(epoch) ? hipMemsetAsync(xch, 0, xch.cap() * 8, s) : hipSuccess;
         return Meet{xch, abort_word, epoch, n, (allow_local && n <= kMeetXcdCus) ? 0 : 1};
     }
     static int grid(const Meet& m) { return m.global ? m.n : 8 * m.n; }      // one XCD: every eighth workgroup works

@@ -5,7 +5,8 @@
 #include "../../include/rnde.h"
 // The device allocations of the translation units that include this header (rnde.hip, rnde_reverse.hip, rnde_node_tile.hip) go through
 // rnde_alloc.h's wrapper (RNDE_POISON), first among the project headers; the other allocating units (rnde_ffjord.hip, rnde_sde.hip,
-// rnde_latent.hip, rnde_comm.hip) include that header themselves.  MeetRes::create (rnde_meet.h) stays outside it on purpose.
+// rnde_latent.hip, rnde_comm.hip) include that header themselves.  MeetRes::create (rnde_meet.h) stays outside the fill on purpose (it is
+// counted like the rest).  The same header has the owning types the handle's members are made of.
 #include "rnde_alloc.h"
 #include "rnde_fwd.h"
 #include "rnde_bwd.h"
@@ -31,6 +32,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -45,9 +47,16 @@ struct rnde_node {
     int D = 0, H = 0, P = 0, BT = 8, act2 = 1;
     int Bpad_max = 0, nwg_max = 0;
     // stage engine (rnde_stage.h)
+    // Owners (rnde_alloc.h): every allocated member is a DevBuf / PinBuf / Event / Stream and goes with the handle; a member that points into
+    // another allocation is a raw pointer marked "view", and nothing is freed through it.  The stream and the events come first: members go
+    // in reverse order, the buffers before them.
+    Stream wstream;                       // (experimental overlap path of the weight-gradient GEMMs)
+    Event wevents[66];
+    Event tev[5];                         // rnde_node_set_timing: around the attempt loop of the forward, the reverse sweep and the rest of the reverse pass
+    Event ev_host;                        // rnde_node_classifier_grad: what the forward's host wait uses
     int engine = 1;                       // 1 column-owner, 2 stage kernels, 3 chain engine (rnde_chain.h), 4 tiled engine (rnde_node_tile.h)
     struct rnde_node_tiled* tiled = nullptr;   // engine 4: everything of that engine (rnde_node_tile.hip); the fields below it uses are cfg, D, P, h_meta, n_att, B, have_tape, err
-    ChainGeo cg{}; float* cfrags = nullptr; int NKD = 0, chain_alt = 0;
+    ChainGeo cg{}; DevBuf<float> cfrags; int NKD = 0, chain_alt = 0;
     int chain_ga = 0;             // a layer's activation is other than identity / tanh: the kernel variants that serve every rnde_act (ALT / LAT = 2)
     size_t chain_lds_f = 0, chain_lds_b = 0;
     // multi-wave kernels of the chain engine (rnde_chainmw.h): 4 waves per 16 columns, activations taped in the slab by the forward
@@ -56,62 +65,62 @@ struct rnde_node {
     // chain engine, multi-wave kernels: the whole adaptive solve as ONE launch (rnde_chainmw.h MW_SOLVE) while the tiles fit one XCD (<= 32)
     int mw_clean = 0, mw_retry_after = 8;   // non-sticky fallback of those kernels, as persist_clean / persist_retry_after of the stage engine
     int mw_solve = 1; MeetRes mw_meet;   // the meeting place of both one-launch kernels (rnde_meet.h); its XCD slot moves on after a failure
-    int mw_bsweep = 1; int* mw_bargs = nullptr; int* h_mw_bargs = nullptr; unsigned* h_mw_bchk = nullptr; bool pending_bsweep = false; int bsweep_nt = 0; bool bsweep_global = false;   // (the pending sweep's OWN check words, tile count and meeting kind: a later forward may overwrite h->B and the meeting's own check buffer before the verdict is read)
+    int mw_bsweep = 1; DevBuf<int> mw_bargs; PinBuf<int> h_mw_bargs; PinBuf<unsigned> h_mw_bchk; bool pending_bsweep = false; int bsweep_nt = 0; bool bsweep_global = false;   // (the pending sweep's OWN check words, tile count and meeting kind: a later forward may overwrite h->B and the meeting's own check buffer before the verdict is read)
       // the reverse sweep as one launch (rnde_bchainmw.h SWEEP): per-attempt arguments [sv_lo | sv_hi | eig_c], check words
     int rk_S = 7, rk_order = 5;   // stages of the pair in first-same-as-last form (evaluations per attempted step = rk_S - 1), controller order
     int mw_lat = 0;               // the reference's latent-ODE shape (20 <-> 50, 8 layers): forward kernels with register-stationary weights
-    int mw = 0; MwGeo mg{}; float* mw_tab = nullptr; float* mw_slab = nullptr; long long mw_slab_evals = 0; size_t mw_lds_f = 0, mw_lds_b = 0;
-    float* cslab = nullptr; size_t cslab_floats = 0; float* ev_t = nullptr; float* h_ev_t = nullptr;   // chain reverse: (H, Z) dump, evaluation times
+    int mw = 0; MwGeo mg{}; DevBuf<float> mw_tab; DevBuf<float> mw_slab; long long mw_slab_evals = 0; size_t mw_lds_f = 0, mw_lds_b = 0;
+    DevBuf<float> cslab; DevBuf<float> ev_t; PinBuf<float> h_ev_t;   // chain reverse: (H, Z) dump, evaluation times
     int sMT = 0, sWT = 0, sR = 0, sHT = 0, sK2b = 0, sKHb = 0;
-    f32x4 *spwB = nullptr, *spwD = nullptr, *spwBt = nullptr, *spwDt = nullptr;
-    float* slab2 = nullptr;
+    DevBuf<f32x4> spwB, spwD, spwBt, spwDt;
+    DevBuf<float> slab2;
     size_t stage_lds = 0;
-    float* head_ws = nullptr; size_t head_ws_floats = 0;   // fused classifier head scratch
+    DevBuf<float> head_ws;   // fused classifier head scratch
     // rnde_node_classifier_grad: work the forward enqueues BEHIND the copy its host wait needs (so it runs while the host wakes up),
-    // the event that wait uses, the caller-independent buffers of the fused step, and "the reverse sweep's weight packs are already queued"
-    std::function<rnde_status(hipStream_t)> after_solve; hipEvent_t ev_host = nullptr; bool rev_packed = false;
-    float* cg_ws = nullptr; size_t cg_ws_floats = 0; std::vector<float> cg_sv;
-    float* sv_t_dev = nullptr; size_t sv_cap = 0; std::vector<float> saveat;   // saveat times of the last forward
-    float* replay_dev = nullptr; size_t replay_cap = 0; const float* replay_host = nullptr; int n_replay = 0;   // rnde_node_forward_replay (set for one forward)
+    // (the event that wait uses: ev_host above), the caller-independent buffers of the fused step, and "the reverse sweep's weight packs are already queued"
+    std::function<rnde_status(hipStream_t)> after_solve; bool rev_packed = false;
+    DevBuf<float> cg_ws; std::vector<float> cg_sv;
+    DevBuf<float> sv_t_dev; std::vector<float> saveat;   // saveat times of the last forward
+    DevBuf<float> replay_dev; const float* replay_host = nullptr; int n_replay = 0;   // rnde_node_forward_replay (set for one forward)
     std::vector<float> replay_armed;   // rnde_debug_arm_replay: the sequence the next rnde_node_forward_saveat runs along (then cleared)
     // persistent attempt kernel (rnde_stage_persist.h): 1 = in use, 0 = off (RNDE_PERSIST=0), -1 = disabled after a failure
     int wgrad_side_pct = 30, stage_generic = 0;
     int persist_clean = 0, persist_retry_after = 8, persist_fallbacks = 0;   // non-sticky fallback: clean multi-launch solves since the last failure, when to try again   // fixed at creation (config fields; RNDE_* environment overrides are read once, there)
     int persist2 = -1;   // two column tiles per workgroup in the forward attempt kernel: -1 automatic (by tile count), 0 never, 1 whenever possible (RNDE_PERSIST2, read at creation)
-    int persist = 0, persist_spins = kPersistMaxSpins; int tslab_Bpad = -1; size_t tslab_bytes = 0; float* tslab = nullptr; unsigned *pabort = nullptr, *pxcc = nullptr; unsigned* h_pchk = nullptr;
+    int persist = 0, persist_spins = kPersistMaxSpins; int tslab_Bpad = -1; size_t tslab_bytes = 0; DevBuf<float> tslab; unsigned *pabort = nullptr, *pxcc = nullptr; unsigned* h_pchk = nullptr;   // pabort, pxcc: views into mbox; h_pchk: view into h_mbox
     // the whole forward solve as one launch (rnde_stage_solve.h): 1 = use it where it applies, 0 = off (RNDE_STAGE_SOLVE=0 at creation); meeting granules and the epoch of their tags
     // (the abort word and the XCC ids of that kernel are PersistSync's)
     int stage_solve = 1; MeetRes s_meet; int one_launch_solves = 0;
     // the one-launch solve's Dense layers on the matrix cores (rnde_x3.h): 1 = on (RNDE_X3 at creation / rnde_node_set_matrix_mode), split weight images, "packed for the current p"
-    int x3 = 0; void *x3B = nullptr, *x3D = nullptr, *x3Bt = nullptr, *x3Dt = nullptr; bool x3_packed = false, x3_fwd = false;      // x3_fwd: this forward's stage kernels run with x3 (weights split by its pack launch); x3_packed: the last forward ran the x3 solve, the four images hold ITS parameters (the reverse pass may use the transposed pair)
-    hipStream_t wstream = nullptr;        // (experimental overlap path of the weight-gradient GEMMs)
-    std::vector<hipEvent_t> wevents;
+    int x3 = 0; DevBuf<unsigned char> x3B, x3D, x3Bt, x3Dt; bool x3_packed = false, x3_fwd = false;      // x3_fwd: this forward's stage kernels run with x3 (weights split by its pack launch); x3_packed: the last forward ran the x3 solve, the four images hold ITS parameters (the reverse pass may use the transposed pair)
     // device
-    float *f0 = nullptr, *h0 = nullptr, *u1 = nullptr, *f1 = nullptr, *h1 = nullptr, *arena = nullptr;
-    float* xcopy = nullptr;  // private copy of x (the tape must not alias caller memory)
-    long long arena_recs = 0, rec_stride = 0;
-    float* pcopy = nullptr;
-    StepState *ctl = nullptr, *ctl_final = nullptr;
-    unsigned char *mbox = nullptr, *h_mbox = nullptr; size_t mbox_meta_off = 0;   // stage engine: everything the host reads per chunk, contiguous (one copy)
+    DevBuf<float> f0, h0, u1, f1, h1, arena;      // arena: arena.cap() / rec_stride records
+    DevBuf<float> xcopy;     // private copy of x (the tape must not alias caller memory)
+    long long rec_stride = 0;
+    DevBuf<float> pcopy;
+    DevBuf<StepState> ctl;
+    DevBuf<unsigned char> mbox; PinBuf<unsigned char> h_mbox; size_t mbox_meta_off = 0;   // stage engine: everything the host reads per chunk, contiguous (one copy)
+    // Views.  Stage engine: into mbox / h_mbox.  Chain and tiled engines: onto the own_* allocations below, which no other code names.
+    StepState* ctl_final = nullptr;
     StepMeta* meta = nullptr;
     InitRec* initrec = nullptr;
-    float *errpart = nullptr, *initpart = nullptr;
-    BwdBuffers bw{};
-    // pinned host
     StepState* h_ctl = nullptr;
     StepMeta* h_meta = nullptr;
     InitRec* h_init = nullptr;
-    float* h_scal = nullptr;
+    DevBuf<StepState> own_ctl_final; DevBuf<StepMeta> own_meta; DevBuf<InitRec> own_initrec;
+    PinBuf<StepState> own_h_ctl; PinBuf<StepMeta> own_h_meta; PinBuf<InitRec> own_h_init;
+    DevBuf<float> errpart, initpart;
+    BwdBuffers bw;
+    PinBuf<float> h_scal;    // pinned host
     // last forward
     int B = 0, Bpad = 0, nwg = 0, n_att = 0, predicted = 0;
     float t0 = 0, t1 = 0;
     bool have_tape = false;
     bool pending_bwd = false;
-    float* diag_buf = nullptr;   // (RNDE_DIAG builds) cycle stamps   // an asynchronous reverse pass whose health words have not been looked at yet
+    DevBuf<float> diag_buf;   // (RNDE_DIAG builds) cycle stamps   // an asynchronous reverse pass whose health words have not been looked at yet
     std::vector<int> sv_index;  // per attempt: index into saveval or -1
     int n_saveval = 0;
-    // rnde_node_set_timing: HIP events around the attempt loop of the forward, the reverse sweep and the rest of the reverse pass
-    int timing = 0; hipEvent_t tev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool tev_fwd = false, tev_bwd = false;
+    int timing = 0; bool tev_fwd = false, tev_bwd = false;
     std::string err;
 };
 

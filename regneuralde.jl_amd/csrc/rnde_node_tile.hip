@@ -15,17 +15,20 @@ struct rnde_node_tiled {
     FcGeo G{};
     int Bp = 0, ntiles_max = 0;
     size_t lds_bytes = 0;
-    float *ws = nullptr, *tape = nullptr, *norm = nullptr, *replay = nullptr, *rws = nullptr, *pacc = nullptr, *pcopy = nullptr;
-    StepState* ctl = nullptr;        // [3]: the two live states, then the final one
-    StepState* ctl_t = nullptr;      // [ntiles]
-    StepMeta* meta = nullptr;        // [max_attempts]
-    InitRec* initrec_t = nullptr;    // [ntiles]
-    FfStepRec* rec = nullptr;        // [max_attempts]
+    Event ev[5];                     // (ahead of the buffers: members go in reverse order, the buffers and the meeting place first)
+    // (every pointer member is an owner, rnde_alloc.h; h->h_meta, where the host reads the step log, is an owner of the rnde_node)
+    DevBuf<float> ws, tape, norm, replay, rws, pacc, pcopy;
+    DevBuf<StepState> ctl;           // [3]: the two live states, then the final one
+    DevBuf<StepState> ctl_t;         // [ntiles]
+    DevBuf<StepMeta> meta;           // [max_attempts]
+    DevBuf<InitRec> initrec_t;       // [ntiles]
+    DevBuf<FfStepRec> rec;           // [max_attempts]
+    PinBuf<StepState> h_fin;         // pinned: the final controller state of the running solve (an asynchronous copy must not land in a dead stack frame)
     // rnde_node_set_tracking: taped forwards are reversed with the controller (and the initial step) differentiated
     bool track_ctrl = false, track_initdt = false;
-    FfAttRec* att = nullptr;         // [max_attempts]: the tracked sweep's attempt records (allocated when tracking is first switched on)
-    double* tsb = nullptr;           // [2]: the tracked sweep's (t0-bar, t1-bar)
-    double* h_tsb = nullptr;         // pinned [2]: where the host reads them (an asynchronous copy must not land in a dead stack frame)
+    DevBuf<FfAttRec> att;            // [max_attempts]: the tracked sweep's attempt records (allocated when tracking is first switched on)
+    DevBuf<double> tsb;              // [2]: the tracked sweep's (t0-bar, t1-bar)
+    PinBuf<double> h_tsb;            // pinned [2]: where the host reads them (likewise)
     std::vector<FfStepRec> h_rec;    // the accepted steps' records of the last reverse sweep (likewise)
     std::vector<FfAttRec> h_att;     // the attempt records of the last tracked sweep (the source of an asynchronous copy: it outlives the call)
     MeetRes meet;
@@ -35,13 +38,12 @@ struct rnde_node_tiled {
     bool tp_track_ctrl = false, tp_track_initdt = false;      // the tape remembers the setting of its forward
     InitRec tp_init{};
     float tp_t0 = 0.f;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     bool ev_fwd = false, ev_bwd = false;
     // rnde_node_tiled_reserve_saveat: room for up to sv_cap save times per call (0: saving calls are refused, as on a fresh handle)
     int sv_cap = 0;
-    float* sv_t = nullptr;           // [sv_cap]: the save times of the running solve
-    float* tp_sv_t = nullptr;        // [sv_cap]: the tape's own copy (an untaped saving probe between a taped forward and its backward leaves it alone)
-    SaveRange* sv_rng = nullptr;     // [max_attempts]: the save indices of each record the reverse sweep walks (save_plan, formed on the host)
+    DevBuf<float> sv_t;              // [sv_cap]: the save times of the running solve
+    DevBuf<float> tp_sv_t;           // [sv_cap]: the tape's own copy (an untaped saving probe between a taped forward and its backward leaves it alone)
+    DevBuf<SaveRange> sv_rng;        // [max_attempts]: the save indices of each record the reverse sweep walks (save_plan, formed on the host)
     std::vector<float> h_sv, tp_saveat;      // the running solve's times (the source of an asynchronous copy); the taped forward's (empty: an end-state tape)
     std::vector<SaveRange> h_rng;            // (likewise a copy's source)
 };
@@ -98,16 +100,7 @@ static const char* nt_refusal(const rnde_node_config* c) {
 }
 
 void node_tiled_destroy(rnde_node* h) {
-    rnde_node_tiled* T = h->tiled;
-    if (!T) return;
-    for (void* p : {(void*)T->ws, (void*)T->tape, (void*)T->norm, (void*)T->replay, (void*)T->rws, (void*)T->pacc, (void*)T->pcopy, (void*)T->ctl,
-                    (void*)T->ctl_t, (void*)T->meta, (void*)T->initrec_t, (void*)T->rec, (void*)T->att, (void*)T->tsb, (void*)T->sv_t, (void*)T->tp_sv_t,
-                    (void*)T->sv_rng})
-        if (p) (void)hipFree(p);
-    T->meet.destroy();
-    if (T->h_tsb) (void)hipHostFree(T->h_tsb);
-    for (auto& v : T->ev) if (v) (void)hipEventDestroy(v);
-    delete T;
+    delete h->tiled;
     h->tiled = nullptr;
 }
 
@@ -118,7 +111,8 @@ extern "C" rnde_status rnde_node_create_tiled(const rnde_node_config* c, rnde_no
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= c->device) { rnde_set_create_error("no HIP device"); return RNDE_ERR_NO_DEVICE; }
     if (hipSetDevice(c->device) != hipSuccess) { rnde_set_create_error("hipSetDevice failed"); return RNDE_ERR_NO_DEVICE; }
-    rnde_node* h = new rnde_node();
+    std::unique_ptr<rnde_node, void (*)(rnde_node*)> hold(new rnde_node(), rnde_node_destroy);
+    rnde_node* h = hold.get();
     rnde_node_tiled* T = new rnde_node_tiled();
     h->tiled = T;
     h->cfg = *c; h->engine = 4;
@@ -128,25 +122,27 @@ extern "C" rnde_status rnde_node_create_tiled(const rnde_node_config* c, rnde_no
     T->Bp = 16 * T->ntiles_max;
     h->Bpad_max = T->Bp; h->nwg_max = T->ntiles_max;
     T->lds_bytes = (size_t)NtDyn::lds_floats(T->G) * 4;
-    if ((int64_t)T->lds_bytes != rnde_node_tiled_lds_bytes(c)) { rnde_set_create_error("internal: LDS byte counts disagree"); rnde_node_destroy(h); return RNDE_ERR_BAD_ARG; }
-    auto fail = [&](hipError_t e) { rnde_set_create_error(std::string("HIP: ") + hipGetErrorString(e)); rnde_node_destroy(h); return RNDE_ERR_HIP; };
+    if ((int64_t)T->lds_bytes != rnde_node_tiled_lds_bytes(c)) { rnde_set_create_error("internal: LDS byte counts disagree"); return RNDE_ERR_BAD_ARG; }
+    auto fail = [&](hipError_t e) { rnde_set_create_error(std::string("HIP: ") + hipGetErrorString(e)); return RNDE_ERR_HIP; };
     hipError_t e;
     const int D = h->D;
     const size_t RB = (size_t)D * T->Bp, MA = (size_t)c->max_attempts, NT = (size_t)T->ntiles_max;
-    if ((e = hipMalloc(&T->ws, 10 * RB * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&T->tape, (MA + 1) * RB * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&T->norm, (8 * NT + 512) * 4)) != hipSuccess) return fail(e);
+    if ((e = T->ws.alloc(10 * RB)) != hipSuccess) return fail(e);
+    if ((e = T->tape.alloc((MA + 1) * RB)) != hipSuccess) return fail(e);
+    if ((e = T->norm.alloc(8 * NT + 512)) != hipSuccess) return fail(e);
     if ((e = hipMemset(T->norm, 0, (8 * NT + 512) * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&T->replay, 2 * MA * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&T->rws, NT * NtDyn::rev_ws_floats(T->G) * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&T->pacc, NT * T->G.P * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&T->pcopy, (size_t)T->G.P * 4)) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&T->ctl, 3 * sizeof(StepState))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&T->ctl_t, NT * sizeof(StepState))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&T->meta, MA * sizeof(StepMeta))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&T->initrec_t, NT * sizeof(InitRec))) != hipSuccess) return fail(e);
-    if ((e = hipMalloc(&T->rec, MA * sizeof(FfStepRec))) != hipSuccess) return fail(e);
-    if ((e = hipHostMalloc((void**)&h->h_meta, MA * sizeof(StepMeta))) != hipSuccess) return fail(e);
+    if ((e = T->replay.alloc(2 * MA)) != hipSuccess) return fail(e);
+    if ((e = T->rws.alloc(NT * NtDyn::rev_ws_floats(T->G))) != hipSuccess) return fail(e);
+    if ((e = T->pacc.alloc(NT * T->G.P)) != hipSuccess) return fail(e);
+    if ((e = T->pcopy.alloc((size_t)T->G.P)) != hipSuccess) return fail(e);
+    if ((e = T->ctl.alloc(3)) != hipSuccess) return fail(e);
+    if ((e = T->ctl_t.alloc(NT)) != hipSuccess) return fail(e);
+    if ((e = T->meta.alloc(MA)) != hipSuccess) return fail(e);
+    if ((e = T->initrec_t.alloc(NT)) != hipSuccess) return fail(e);
+    if ((e = T->rec.alloc(MA)) != hipSuccess) return fail(e);
+    if ((e = h->own_h_meta.alloc(MA)) != hipSuccess) return fail(e);
+    h->h_meta = h->own_h_meta;
+    if ((e = T->h_fin.alloc(1)) != hipSuccess) return fail(e);
     if ((e = T->meet.create(MA + 4, 3, kMwMeetMax)) != hipSuccess) return fail(e);
     const void* solve = (const void*)rnde_tile_solve_kernel<NtDyn, false, false>;
     for (const void* k : {solve, (const void*)rnde_tile_reverse_kernel<NtDyn, false, false, false>, (const void*)rnde_tile_feval_kernel<NtDyn, false>})
@@ -154,10 +150,10 @@ extern "C" rnde_status rnde_node_create_tiled(const rnde_node_config* c, rnde_no
     if (T->ntiles_max > kMeetXcdCus) {      // the agent-scope meeting: every tile of the largest batch must be resident at once
         const std::string why = tile_residency_refusal({solve}, kFtThreads, T->lds_bytes, T->ntiles_max, c->device, kNtPrefix, "the meeting", "this LDS footprint", &e);
         if (e != hipSuccess) return fail(e);
-        if (!why.empty()) { rnde_set_create_error(why); rnde_node_destroy(h); return RNDE_ERR_BAD_ARG; }
+        if (!why.empty()) { rnde_set_create_error(why); return RNDE_ERR_BAD_ARG; }
     }
-    for (auto& v : T->ev) if ((e = hipEventCreate(&v)) != hipSuccess) return fail(e);
-    *out = h;
+    for (auto& v : T->ev) if ((e = v.create()) != hipSuccess) return fail(e);
+    *out = hold.release();
     return RNDE_OK;
 }
 
@@ -219,8 +215,8 @@ rnde_status node_tiled_forward(rnde_node* h, const float* x_dev, const float* p_
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(T->ev[1], s));
     T->ev_fwd = true;
-    StepState fin;
-    HIPCHK(h, hipMemcpyAsync(&fin, T->ctl + 2, sizeof(StepState), hipMemcpyDeviceToHost, s));
+    const StepState& fin = *T->h_fin;
+    HIPCHK(h, hipMemcpyAsync(T->h_fin, T->ctl + 2, sizeof(StepState), hipMemcpyDeviceToHost, s));
     HIPCHK(h, T->meet.queue_check(meet, s));
     HIPCHK(h, hipStreamSynchronize(s));
     hipError_t me;
@@ -332,9 +328,9 @@ extern "C" rnde_status rnde_node_set_tracking(rnde_node* h, int32_t track_ctrl, 
             if (!why.empty()) { h->err = why; return RNDE_ERR_BAD_ARG; }
         }
         // (att last: it is what marks the switch-on as done, so a call that failed half way is simply made again)
-        if (!T->tsb) HIPCHK(h, hipMalloc(&T->tsb, 2 * sizeof(double)));
-        if (!T->h_tsb) HIPCHK(h, hipHostMalloc((void**)&T->h_tsb, 2 * sizeof(double)));
-        HIPCHK(h, hipMalloc(&T->att, (size_t)h->cfg.max_attempts * sizeof(FfAttRec)));
+        HIPCHK(h, T->tsb.reserve(2));
+        HIPCHK(h, T->h_tsb.reserve(2));
+        HIPCHK(h, T->att.alloc((size_t)h->cfg.max_attempts));
     }
     T->track_ctrl = track_ctrl != 0; T->track_initdt = track_initdt != 0;
     return RNDE_OK;
@@ -372,7 +368,7 @@ extern "C" rnde_status rnde_node_tiled_reserve_saveat(rnde_node* h, int32_t max_
     HIPCHK(h, hipSetDevice(h->cfg.device));
     T->sv_cap = 0;                              // (set last: a call that failed half way leaves a handle that refuses, and is simply made again)
     T->tp_saveat.clear();
-    for (void** p : {(void**)&T->sv_t, (void**)&T->tp_sv_t, (void**)&T->sv_rng}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    T->sv_t.reset(); T->tp_sv_t.reset(); T->sv_rng.reset();
     if (max_saveat == 0) return RNDE_OK;
     const void *solve = (const void*)rnde_tile_solve_kernel<NtDyn, false, true>, *sweep = (const void*)rnde_tile_reverse_kernel<NtDyn, false, true, true>;
     for (const void* k : {solve, (const void*)rnde_tile_reverse_kernel<NtDyn, false, false, true>, sweep})
@@ -385,9 +381,9 @@ extern "C" rnde_status rnde_node_tiled_reserve_saveat(rnde_node* h, int32_t max_
         HIPCHK(h, e);
         if (!why.empty()) { h->err = why; return RNDE_ERR_BAD_ARG; }
     }
-    HIPCHK(h, hipMalloc(&T->sv_t, (size_t)max_saveat * 4));
-    HIPCHK(h, hipMalloc(&T->tp_sv_t, (size_t)max_saveat * 4));
-    HIPCHK(h, hipMalloc(&T->sv_rng, (size_t)h->cfg.max_attempts * sizeof(SaveRange)));
+    HIPCHK(h, T->sv_t.reserve((size_t)max_saveat));
+    HIPCHK(h, T->tp_sv_t.reserve((size_t)max_saveat));
+    HIPCHK(h, T->sv_rng.reserve((size_t)h->cfg.max_attempts));
     T->sv_cap = max_saveat;
     return RNDE_OK;
 }

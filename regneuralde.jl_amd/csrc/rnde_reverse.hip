@@ -29,13 +29,12 @@ extern "C" rnde_status rnde_node_backward(rnde_node* h, const float* u_bar_dev, 
 extern "C" rnde_status rnde_node_backward_host(rnde_node* h, const float* u_bar, const float* saveval_bar, float* x_bar,
                                                float* p_bar, float* tspan_bar) {
     if (!h) return RNDE_ERR_BAD_ARG;
-    float *ub = nullptr, *xb = nullptr, *pb = nullptr;
+    DevBuf<float> ub, xb, pb;
     const size_t nb = (size_t)h->D * h->B * 4;
-    HIPCHK(h, hipMalloc((void**)&ub, nb)); HIPCHK(h, hipMalloc((void**)&xb, nb)); HIPCHK(h, hipMalloc((void**)&pb, (size_t)h->P * 4));
+    HIPCHK(h, ub.alloc(nb / 4)); HIPCHK(h, xb.alloc(nb / 4)); HIPCHK(h, pb.alloc((size_t)h->P));
     HIPCHK(h, hipMemcpy(ub, u_bar, nb, hipMemcpyHostToDevice));
     rnde_status st = rnde_node_backward(h, ub, saveval_bar, xb, pb, tspan_bar, nullptr);
     if (st == RNDE_OK) { hipMemcpy(x_bar, xb, nb, hipMemcpyDeviceToHost); hipMemcpy(p_bar, pb, (size_t)h->P * 4, hipMemcpyDeviceToHost); }
-    hipFree(ub); hipFree(xb); hipFree(pb);
     return st;
 }
 
@@ -45,32 +44,32 @@ static rnde_status bwd_prepare(rnde_node* h) {
     if (b.ready) return RNDE_OK;
     const size_t A = (size_t)h->D * h->Bpad_max, HB = (size_t)h->H * h->Bpad_max;
     const int cap = h->cfg.max_attempts;
-    HIPCHK(h, hipMalloc((void**)&b.U, A * 4)); HIPCHK(h, hipMalloc((void**)&b.K1, A * 4)); HIPCHK(h, hipMalloc((void**)&b.UB1, A * 4));
-    HIPCHK(h, hipMalloc((void**)&b.zi2, 2 * A * 4)); HIPCHK(h, hipMalloc((void**)&b.zi1, 2 * HB * 4));
-    HIPCHK(h, hipMalloc((void**)&b.svb_att, (size_t)cap * 4));
-    HIPCHK(h, hipMalloc((void**)&b.bstate, 2 * sizeof(BState) + 64)); HIPCHK(h, hipMalloc((void**)&b.ibstate, 2 * sizeof(IBState)));      // (+ 64 bytes: the [2][4] sums of rnde_bpart_reduce_kernel)
-    HIPCHK(h, hipMalloc((void**)&b.bpart, (size_t)(2 * h->nwg_max + 256) * 4 * 4)); HIPCHK(h, hipMalloc((void**)&b.ipart, (size_t)2 * h->nwg_max * 4 * 4));   // (+256 entries: finish_attempt_scalars reads whole 256-entry blocks)
-    HIPCHK(h, hipMalloc((void**)&b.tspan_out, 2 * 4));
+    // (reserve: a call that failed half way is simply made again)
+    HIPCHK(h, b.U.reserve(A)); HIPCHK(h, b.K1.reserve(A)); HIPCHK(h, b.UB1.reserve(A));
+    HIPCHK(h, b.zi2.reserve(2 * A)); HIPCHK(h, b.zi1.reserve(2 * HB));
+    HIPCHK(h, b.svb_att.reserve((size_t)cap));
+    HIPCHK(h, b.bstate_mem.reserve(2 * sizeof(BState) + 64)); b.bstate = (BState*)b.bstate_mem.get(); HIPCHK(h, b.ibstate.reserve(2));      // (+ 64 bytes: the [2][4] sums of rnde_bpart_reduce_kernel)
+    HIPCHK(h, b.bpart.reserve((size_t)(2 * h->nwg_max + 256) * 4)); HIPCHK(h, b.ipart.reserve((size_t)2 * h->nwg_max * 4));   // (+256 entries: finish_attempt_scalars reads whole 256-entry blocks)
+    HIPCHK(h, b.tspan_out.reserve(2));
     const size_t nev = (size_t)6 * cap + 2;
     // (ev1 / h_ev1 are sized for [ev1 | ev2 | svb] back to back: bwd_run lays the three out contiguously and sends them in ONE copy)
     const size_t desc_blob = 2 * nev * sizeof(EvalDesc) + (size_t)cap * 4 + 64;
-    HIPCHK(h, hipMalloc((void**)&b.ev1, desc_blob)); HIPCHK(h, hipMalloc((void**)&b.ev2, nev * sizeof(EvalDesc)));
-    HIPCHK(h, hipHostMalloc((void**)&b.h_ev1, desc_blob)); HIPCHK(h, hipHostMalloc((void**)&b.h_ev2, nev * sizeof(EvalDesc)));
-    HIPCHK(h, hipHostMalloc((void**)&b.h_svb, (size_t)cap * 4));
+    HIPCHK(h, b.ev1_mem.reserve(desc_blob)); b.ev1 = (EvalDesc*)b.ev1_mem.get(); HIPCHK(h, b.ev2.reserve(nev));
+    HIPCHK(h, b.h_ev1_mem.reserve(desc_blob)); b.h_ev1 = (EvalDesc*)b.h_ev1_mem.get(); HIPCHK(h, b.h_ev2.reserve(nev));
+    HIPCHK(h, b.h_svb.reserve((size_t)cap));
     const size_t seg = std::max((size_t)h->H * (h->D + 2), (size_t)h->D * (h->H + 2));
     b.slab_floats = seg * 256;              // per layer; two layers back to back
-    HIPCHK(h, hipMalloc((void**)&b.slab, 2 * b.slab_floats * 4));
-    HIPCHK(h, hipMalloc((void**)&b.slab_r, 2 * 16 * seg * 4));      // second-level partials, one region per layer
+    HIPCHK(h, b.slab.reserve(2 * b.slab_floats));
+    HIPCHK(h, b.slab_r.reserve(2 * 16 * seg));      // second-level partials, one region per layer
     if (!h->wstream) {
         int prio_least = 0, prio_greatest = 0;
         (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-        HIPCHK(h, hipStreamCreateWithPriority(&h->wstream, hipStreamNonBlocking, prio_least));   // never ahead of the sweep
-        h->wevents.resize(66);
-        for (auto& e : h->wevents) HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        HIPCHK(h, hipStreamCreateWithPriority(&h->wstream.s, hipStreamNonBlocking, prio_least));   // never ahead of the sweep
+        for (auto& e : h->wevents) HIPCHK(h, e.create(hipEventDisableTiming));
     }
     if (h->engine == 2) {
-        HIPCHK(h, hipMalloc((void**)&b.UTB, A * 4)); HIPCHK(h, hipMalloc((void**)&b.UNB, A * 4)); HIPCHK(h, hipMalloc((void**)&b.UPB0, A * 4));
-        HIPCHK(h, hipMalloc((void**)&b.GB, 15 * A * 4));   // gbar_1..6, EXK, EXG (stiffness extras), W_1..7 (saveat)
+        HIPCHK(h, b.UTB.reserve(A)); HIPCHK(h, b.UNB.reserve(A)); HIPCHK(h, b.UPB0.reserve(A));
+        HIPCHK(h, b.GB.reserve(15 * A));   // gbar_1..6, EXK, EXG (stiffness extras), W_1..7 (saveat)
     }
     b.ready = true;
     return RNDE_OK;
@@ -233,7 +232,7 @@ static rnde_status bwd_run(rnde_node* h, const float* u_bar_dev, const float* sa
     Q.bpart_n = Q.F.nwg;
     Q.tspan_scale = h->couple ? 1.f / (float)h->couple_world : 1.f;
 #ifdef RNDE_DIAG
-    if (getenv("RNDE_DIAG_BWD")) { if (!h->diag_buf) hipMalloc((void**)&h->diag_buf, 8192); hipMemset(h->diag_buf, 0, 512); Q.F.dbg_out = h->diag_buf; }
+    if (getenv("RNDE_DIAG_BWD")) { (void)h->diag_buf.reserve(2048); hipMemset(h->diag_buf, 0, 512); Q.F.dbg_out = h->diag_buf; }
 #endif
     Q.sv_T = (int)h->saveat.size();
     Q.sv_ubar0 = (!h->saveat.empty() && h->saveat[0] == h->t0) ? u_bar_dev : nullptr;
@@ -479,12 +478,7 @@ static rnde_status bwd_run(rnde_node* h, const float* u_bar_dev, const float* sa
 // ---- fused classifier head ------------------------------------------------------
 static rnde_status head_reserve(rnde_node* h, int32_t B, int32_t n_classes) {
     const size_t need = (size_t)B * n_classes + B + (size_t)kHeadChunks * n_classes * h->D;
-    if (h->head_ws_floats < need) {
-        if (h->head_ws) hipFree(h->head_ws);
-        h->head_ws = nullptr; h->head_ws_floats = 0;
-        HIPCHK(h, hipMalloc((void**)&h->head_ws, need * 4));
-        h->head_ws_floats = need;
-    }
+    HIPCHK(h, h->head_ws.reserve(need));
     return RNDE_OK;
 }
 extern "C" rnde_status rnde_classifier_head(rnde_node* h, const float* u_dev, const float* p3_dev, const float* y_dev,
@@ -526,13 +520,8 @@ extern "C" rnde_status rnde_node_classifier_grad(rnde_node* h, const float* x_de
     if (B < 1 || B > h->cfg.max_batch) { h->err = "bad B or tspan"; return RNDE_ERR_BAD_ARG; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t A = (size_t)h->D * B;
-    if (h->cg_ws_floats < 3 * A) {
-        if (h->cg_ws) hipFree(h->cg_ws);
-        h->cg_ws = nullptr; h->cg_ws_floats = 0;
-        HIPCHK(h, hipMalloc((void**)&h->cg_ws, 3 * A * 4));
-        h->cg_ws_floats = 3 * A;
-    }
-    if (!h->ev_host) HIPCHK(h, hipEventCreateWithFlags(&h->ev_host, hipEventDisableTiming));
+    HIPCHK(h, h->cg_ws.reserve(3 * A));
+    HIPCHK(h, h->ev_host.create(hipEventDisableTiming));
     if (n_classes < 1 || n_classes > kHeadMaxC) return RNDE_ERR_BAD_ARG;
     rnde_status st = head_reserve(h, B, n_classes);   // (the hook below runs between an event record and the host's wait on it: it only enqueues)
     if (st != RNDE_OK) return st;
@@ -672,14 +661,14 @@ static rnde_status chain_mw_bwd_run(rnde_node* h, const float* u_bar_dev, const 
     const int E = h->rk_S - 1;      // evaluations per attempted step (6; S - 1 for an S-stage table)
     if (!b.ready) {
         const size_t Ac = (size_t)ntiles_max * h->NKD * 64;
-        HIPCHK(h, hipMalloc((void**)&b.U, Ac * 4)); HIPCHK(h, hipMalloc((void**)&b.K1, Ac * 4)); HIPCHK(h, hipMalloc((void**)&b.UB1, Ac * 4));
-        HIPCHK(h, hipMalloc((void**)&b.svb_att, (size_t)cap * 4));
-        HIPCHK(h, hipMalloc((void**)&b.bstate, 2 * sizeof(BState))); HIPCHK(h, hipMalloc((void**)&b.ibstate, 2 * sizeof(IBState)));
-        HIPCHK(h, hipMalloc((void**)&b.bpart, (size_t)(2 * h->nwg_max + 256) * 4 * 4)); HIPCHK(h, hipMalloc((void**)&b.ipart, (size_t)2 * h->nwg_max * 4 * 4));   // (+256 entries: finish_attempt_scalars reads whole 256-entry blocks)
-        HIPCHK(h, hipMalloc((void**)&b.tspan_out, 2 * 4));
-        HIPCHK(h, hipHostMalloc((void**)&b.h_svb, (size_t)cap * 4));
-        HIPCHK(h, hipMalloc((void**)&b.slab, (size_t)96 * h->P * 4)); HIPCHK(h, hipMalloc((void**)&b.slab_r, (size_t)16 * h->P * 4));
-        HIPCHK(h, hipMalloc((void**)&h->ev_t, ((size_t)E * cap + 2) * 4)); HIPCHK(h, hipHostMalloc((void**)&h->h_ev_t, ((size_t)E * cap + 2) * 4));
+        HIPCHK(h, b.U.reserve(Ac)); HIPCHK(h, b.K1.reserve(Ac)); HIPCHK(h, b.UB1.reserve(Ac));
+        HIPCHK(h, b.svb_att.reserve((size_t)cap));
+        HIPCHK(h, b.bstate_mem.reserve(2 * sizeof(BState))); b.bstate = (BState*)b.bstate_mem.get(); HIPCHK(h, b.ibstate.reserve(2));
+        HIPCHK(h, b.bpart.reserve((size_t)(2 * h->nwg_max + 256) * 4)); HIPCHK(h, b.ipart.reserve((size_t)2 * h->nwg_max * 4));   // (+256 entries: finish_attempt_scalars reads whole 256-entry blocks)
+        HIPCHK(h, b.tspan_out.reserve(2));
+        HIPCHK(h, b.h_svb.reserve((size_t)cap));
+        HIPCHK(h, b.slab.reserve((size_t)96 * h->P)); HIPCHK(h, b.slab_r.reserve((size_t)16 * h->P));
+        HIPCHK(h, h->ev_t.reserve((size_t)E * cap + 2)); HIPCHK(h, h->h_ev_t.reserve((size_t)E * cap + 2));
         b.ready = true;
     }
     const int n_att = h->n_att, n_evals = E * n_att + 2;
@@ -771,14 +760,14 @@ static rnde_status chain_bwd_run(rnde_node* h, const float* u_bar_dev, const flo
     const int cap = h->cfg.max_attempts, ntiles_max = h->Bpad_max / 16;
     if (!b.ready) {
         const size_t Ac = (size_t)ntiles_max * h->NKD * 64;
-        HIPCHK(h, hipMalloc((void**)&b.U, Ac * 4)); HIPCHK(h, hipMalloc((void**)&b.K1, Ac * 4)); HIPCHK(h, hipMalloc((void**)&b.UB1, Ac * 4));
-        HIPCHK(h, hipMalloc((void**)&b.svb_att, (size_t)cap * 4));
-        HIPCHK(h, hipMalloc((void**)&b.bstate, 2 * sizeof(BState))); HIPCHK(h, hipMalloc((void**)&b.ibstate, 2 * sizeof(IBState)));
-        HIPCHK(h, hipMalloc((void**)&b.bpart, (size_t)(2 * h->nwg_max + 256) * 4 * 4)); HIPCHK(h, hipMalloc((void**)&b.ipart, (size_t)2 * h->nwg_max * 4 * 4));   // (+256 entries: finish_attempt_scalars reads whole 256-entry blocks)
-        HIPCHK(h, hipMalloc((void**)&b.tspan_out, 2 * 4));
-        HIPCHK(h, hipHostMalloc((void**)&b.h_svb, (size_t)cap * 4));
-        HIPCHK(h, hipMalloc((void**)&b.slab, (size_t)96 * h->P * 4)); HIPCHK(h, hipMalloc((void**)&b.slab_r, (size_t)16 * h->P * 4));
-        HIPCHK(h, hipMalloc((void**)&h->ev_t, ((size_t)6 * cap + 2) * 4)); HIPCHK(h, hipHostMalloc((void**)&h->h_ev_t, ((size_t)6 * cap + 2) * 4));
+        HIPCHK(h, b.U.reserve(Ac)); HIPCHK(h, b.K1.reserve(Ac)); HIPCHK(h, b.UB1.reserve(Ac));
+        HIPCHK(h, b.svb_att.reserve((size_t)cap));
+        HIPCHK(h, b.bstate_mem.reserve(2 * sizeof(BState))); b.bstate = (BState*)b.bstate_mem.get(); HIPCHK(h, b.ibstate.reserve(2));
+        HIPCHK(h, b.bpart.reserve((size_t)(2 * h->nwg_max + 256) * 4)); HIPCHK(h, b.ipart.reserve((size_t)2 * h->nwg_max * 4));   // (+256 entries: finish_attempt_scalars reads whole 256-entry blocks)
+        HIPCHK(h, b.tspan_out.reserve(2));
+        HIPCHK(h, b.h_svb.reserve((size_t)cap));
+        HIPCHK(h, b.slab.reserve((size_t)96 * h->P)); HIPCHK(h, b.slab_r.reserve((size_t)16 * h->P));
+        HIPCHK(h, h->ev_t.reserve((size_t)6 * cap + 2)); HIPCHK(h, h->h_ev_t.reserve((size_t)6 * cap + 2));
         b.ready = true;
     }
     const int n_att = h->n_att, n_evals = 6 * n_att + 2;
@@ -803,13 +792,8 @@ static rnde_status chain_bwd_run(rnde_node* h, const float* u_bar_dev, const flo
     Q.RS = row; Q.ev_stride = (long long)Q.ntiles * row * 64;
     Q.sv_t = h->saveat.empty() ? nullptr : h->sv_t_dev; Q.sv_ubar = u_bar_dev; Q.nsave = (int)h->saveat.size();
     const size_t need = (size_t)n_evals * Q.ev_stride;
-    if (h->cslab_floats < need) {
-        if (h->cslab) hipFree(h->cslab);
-        h->cslab = nullptr; h->cslab_floats = 0;
-        const size_t grow = need + need / 2;        // (head room: a step count that creeps up while a model trains must not free + allocate every step)
-        if (hipMalloc((void**)&h->cslab, grow * 4) == hipSuccess) h->cslab_floats = grow;
-        else { HIPCHK(h, hipMalloc((void**)&h->cslab, need * 4)); h->cslab_floats = need; }
-    }
+    if (h->cslab.cap() < need && h->cslab.reserve(need + need / 2) != hipSuccess)      // (head room: a step count that creeps up while a model trains must not free + allocate every step)
+        HIPCHK(h, h->cslab.reserve(need));
     Q.slab = h->cslab;
     // evaluation times (time column of TDChain layers) and the save indices each accepted attempt covers
     std::vector<int> sv_lo(std::max(1, n_att), 0), sv_hi(std::max(1, n_att), 0);

@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -24,11 +25,13 @@ using namespace rnde;
 struct rnde_nsde {
     rnde_nsde_config cfg{};
     int D = 0, Pf = 0, Pg = 0, P = 0, NKD = 8, Bpad_max = 0, ntiles_max = 0, nwg_max = 0;
-    float* head_ws = nullptr; size_t head_ws_floats = 0;   // rnde_nsde_classifier_head
+    Event tev[4], ev_host;      // around the solve kernel / the reverse sweep kernel; the fused step's host wait (ahead of the buffers: members go in reverse order)
+    // (every allocated member is an owner, rnde_alloc.h; the handle holds no view)
+    DevBuf<float> head_ws;   // rnde_nsde_classifier_head
     // rnde_nsde_classifier_grad: work the forward enqueues behind the copies its host wait needs (it runs while the host wakes up), the
-    // event that wait uses, and the buffers of the fused step
-    std::function<rnde_status(hipStream_t)> after_solve; hipEvent_t ev_host = nullptr;
-    float* cg_ws = nullptr; size_t cg_ws_floats = 0; std::vector<float> cg_sv;
+    // event that wait uses (ev_host), and the buffers of the fused step
+    std::function<rnde_status(hipStream_t)> after_solve;
+    DevBuf<float> cg_ws; std::vector<float> cg_sv;
     int mw = 0;    // 1: the four-waves-per-tile solve kernel (rnde_sdemw.h) for that shape, while a tile per workgroup still fits the chip
     size_t lds_mw = 0;
     int xch_wg = 0; // workgroups the meeting is sized for
@@ -41,22 +44,20 @@ struct rnde_nsde {
     ChainGeo Gf{}, Gg{};
     SriTableau T{};
     float order = 1.5f, beta1 = 0, beta2 = 0, gamma = 0, qmin = 0, qmax = 0, qoldinit = 0, delta = 0;
-    float *frags_f = nullptr, *frags_g = nullptr, *slots = nullptr, *tape = nullptr, *noise = nullptr, *replay = nullptr;
-    size_t noise_floats = 0, tape_floats = 0;
+    DevBuf<float> frags_f, frags_g, slots, tape, noise, replay;
     int n_slots = 0;
-    SdeMeta *meta = nullptr, *h_meta = nullptr, *acc_meta = nullptr, *h_acc_meta = nullptr;
-    SdeFinal *fin = nullptr, *h_fin = nullptr;
-    float* eigpart = nullptr;      // RNDE_REG_STIFF: [max_attempts][2][workgroups]
-    float *svb = nullptr, *h_svb = nullptr, *slab_f = nullptr, *slab_g = nullptr, *wslab = nullptr, *wslab_r = nullptr, *ev_t = nullptr;
-    size_t slab_f_floats = 0, slab_g_floats = 0, ev_t_n = 0;
-    float *part = nullptr, *h_part = nullptr;
-    float* sv_t_dev = nullptr; size_t sv_cap = 0; std::vector<float> saveat;   // saveat times of the last forward ({R,true} methods)
+    DevBuf<SdeMeta> meta, acc_meta; PinBuf<SdeMeta> h_meta, h_acc_meta;
+    DevBuf<SdeFinal> fin; PinBuf<SdeFinal> h_fin;
+    DevBuf<float> eigpart;         // RNDE_REG_STIFF: [max_attempts][2][workgroups]
+    DevBuf<float> svb, slab_f, slab_g, wslab, wslab_r, ev_t; PinBuf<float> h_svb;
+    DevBuf<float> part; PinBuf<float> h_part;
+    DevBuf<float> sv_t_dev; std::vector<float> saveat;   // saveat times of the last forward ({R,true} methods)
     size_t lds_fwd = 0, lds_bwd = 0;
     // last forward
     int B = 0, ntiles = 0, nwg = 0, n_att = 0, n_acc = 0, n_draws = 0, n_saveval = 0;
     float t0 = 0.f;
     bool have_tape = false;
-    hipEvent_t tev[4] = {nullptr, nullptr, nullptr, nullptr}; bool tev_f = false, tev_b = false;   // around the solve kernel / the reverse sweep kernel
+    bool tev_f = false, tev_b = false;
     std::vector<int> sv_index;   // per accepted step: index into saveval
     std::string err;
 };
@@ -166,7 +167,8 @@ extern "C" rnde_status rnde_nsde_create(const rnde_nsde_config* c, rnde_nsde** o
         g_nsde_create_err = "RNDE_REG_STIFF (the stiffness estimate of the SRI step) is defined for RNDE_SDE_SOSRI2 only"; return RNDE_ERR_BAD_ARG;
     }
     if (!(c->stability_size >= 0.f)) { g_nsde_create_err = "stability_size must be >= 0 (0 = 10.6)"; return RNDE_ERR_BAD_ARG; }
-    rnde_nsde* h = new rnde_nsde();
+    std::unique_ptr<rnde_nsde, void (*)(rnde_nsde*)> hold(new rnde_nsde(), rnde_nsde_destroy);      // (until the last step has succeeded)
+    rnde_nsde* h = hold.get();
     h->cfg = *c; h->D = D; h->Gf = Gf; h->Gg = Gg;
     h->Pf = chain_params(c->drift_layers, c->drift_dims); h->Pg = chain_params(c->diff_layers, c->diff_dims); h->P = h->Pf + h->Pg;
     h->NKD = D <= 16 ? 4 : (D <= 32 ? 8 : 16);
@@ -191,7 +193,7 @@ extern "C" rnde_status rnde_nsde_create(const rnde_nsde_config* c, rnde_nsde** o
     h->Bpad_max = ((c->max_batch + 15) / 16) * 16;
     h->ntiles_max = h->Bpad_max / 16;
     h->nwg_max = (h->ntiles_max + kCW - 1) / kCW;
-    if (h->nwg_max > 256) { g_nsde_create_err = "max_batch: at most 16384 columns (every workgroup of the one-launch solve must be resident)"; delete h; return RNDE_ERR_BAD_ARG; }
+    if (h->nwg_max > 256) { g_nsde_create_err = "max_batch: at most 16384 columns (every workgroup of the one-launch solve must be resident)"; return RNDE_ERR_BAD_ARG; }
     const int cap = 2 * c->max_attempts + 8;
     const size_t uf = (size_t)((Gf.nfrag_f + Gf.nfrag_b + 3) / 4), ug = (size_t)((Gg.nfrag_f + Gg.nfrag_b + 3) / 4);
     h->lds_fwd = (uf + ug) * 1024 + (size_t)(56 + kSdeMaxOps * 8 + 5 * cap) * 4 + 64;
@@ -199,47 +201,36 @@ extern "C" rnde_status rnde_nsde_create(const rnde_nsde_config* c, rnde_nsde** o
     h->xch_wg = h->mw ? std::max(h->nwg_max, std::min(h->ntiles_max, kSmwMaxTiles)) : h->nwg_max;
     const size_t ufb = (size_t)((Gf.nfrag_f + Gf.nfrag_b + Gf.nfrag_t + 3) / 4), ugb = (size_t)((Gg.nfrag_f + Gg.nfrag_b + Gg.nfrag_t + 3) / 4);
     h->lds_bwd = (ufb + ugb) * 1024 + 64;
-    if (h->lds_fwd > 160 * 1024 || h->lds_bwd > 160 * 1024) { g_nsde_create_err = "networks too large: the weight fragments of both chains must fit the 160 KB LDS of a CU"; delete h; return RNDE_ERR_BAD_ARG; }
-    if (hipSetDevice(c->device) != hipSuccess) { g_nsde_create_err = "hipSetDevice failed"; delete h; return RNDE_ERR_HIP; }
+    if (h->lds_fwd > 160 * 1024 || h->lds_bwd > 160 * 1024) { g_nsde_create_err = "networks too large: the weight fragments of both chains must fit the 160 KB LDS of a CU"; return RNDE_ERR_BAD_ARG; }
+    if (hipSetDevice(c->device) != hipSuccess) { g_nsde_create_err = "hipSetDevice failed"; return RNDE_ERR_HIP; }
     const size_t A = (size_t)h->ntiles_max * h->NKD * 64;
     h->n_slots = cap;
-    auto dm = [&](void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess; };
+    auto dm = [](auto& buf, size_t n) { return buf.alloc(n) == hipSuccess; };      // (n elements)
     bool ok = true;
-    ok &= dm((void**)&h->frags_f, (size_t)(Gf.nfrag_f + Gf.nfrag_b + Gf.nfrag_t + 4) * 256);
-    ok &= dm((void**)&h->frags_g, (size_t)(Gg.nfrag_f + Gg.nfrag_b + Gg.nfrag_t + 4) * 256);
-    ok &= dm((void**)&h->slots, (size_t)h->n_slots * 2 * A * 4);
-    ok &= dm((void**)&h->meta, (size_t)(c->max_attempts + 1) * sizeof(SdeMeta)) && dm((void**)&h->acc_meta, (size_t)(c->max_attempts + 1) * sizeof(SdeMeta));
-    ok &= dm((void**)&h->fin, sizeof(SdeFinal));
+    ok &= dm(h->frags_f, (size_t)(Gf.nfrag_f + Gf.nfrag_b + Gf.nfrag_t + 4) * 64);
+    ok &= dm(h->frags_g, (size_t)(Gg.nfrag_f + Gg.nfrag_b + Gg.nfrag_t + 4) * 64);
+    ok &= dm(h->slots, (size_t)h->n_slots * 2 * A);
+    ok &= dm(h->meta, (size_t)(c->max_attempts + 1)) && dm(h->acc_meta, (size_t)(c->max_attempts + 1));
+    ok &= dm(h->fin, 1);
     ok &= h->res.create((size_t)c->max_attempts + 4, 2, h->xch_wg) == hipSuccess;
-    ok &= dm((void**)&h->svb, (size_t)(c->max_attempts + 1) * 4) && dm((void**)&h->replay, (size_t)(c->max_attempts + 1) * 8);
-    ok &= dm((void**)&h->part, (size_t)h->nwg_max * 4);
-    if (c->regularize == RNDE_REG_STIFF) ok &= dm((void**)&h->eigpart, (size_t)c->max_attempts * 2 * h->xch_wg * 4);      // per-workgroup partials of the estimate's two norms
-    ok &= hipHostMalloc((void**)&h->h_meta, (size_t)(c->max_attempts + 1) * sizeof(SdeMeta)) == hipSuccess;
-    ok &= hipHostMalloc((void**)&h->h_acc_meta, (size_t)(c->max_attempts + 1) * sizeof(SdeMeta)) == hipSuccess;
-    ok &= hipHostMalloc((void**)&h->h_fin, sizeof(SdeFinal)) == hipSuccess;
+    ok &= dm(h->svb, (size_t)(c->max_attempts + 1)) && dm(h->replay, (size_t)(c->max_attempts + 1) * 2);
+    ok &= dm(h->part, (size_t)h->nwg_max);
+    if (c->regularize == RNDE_REG_STIFF) ok &= dm(h->eigpart, (size_t)c->max_attempts * 2 * h->xch_wg);      // per-workgroup partials of the estimate's two norms
+    ok &= dm(h->h_meta, (size_t)(c->max_attempts + 1));
+    ok &= dm(h->h_acc_meta, (size_t)(c->max_attempts + 1));
+    ok &= dm(h->h_fin, 1);
     { const char* e = getenv("RNDE_SDE_LOCAL"); if (e && e[0] == '0') h->xch_local = 0; }
-    ok &= hipHostMalloc((void**)&h->h_svb, (size_t)(c->max_attempts + 1) * 4) == hipSuccess;
-    ok &= hipHostMalloc((void**)&h->h_part, (size_t)h->nwg_max * 4) == hipSuccess;
-    if (!ok) { g_nsde_create_err = "device allocation failed"; rnde_nsde_destroy(h); return RNDE_ERR_HIP; }
-    for (auto& e : h->tev) if (hipEventCreate(&e) != hipSuccess) { g_nsde_create_err = "hipEventCreate failed"; rnde_nsde_destroy(h); return RNDE_ERR_HIP; }
+    ok &= dm(h->h_svb, (size_t)(c->max_attempts + 1));
+    ok &= dm(h->h_part, (size_t)h->nwg_max);
+    if (!ok) { g_nsde_create_err = "device allocation failed"; return RNDE_ERR_HIP; }
+    for (auto& e : h->tev) if (e.create() != hipSuccess) { g_nsde_create_err = "hipEventCreate failed"; return RNDE_ERR_HIP; }
     hipMemset(h->frags_f, 0, (size_t)(Gf.nfrag_f + Gf.nfrag_b + Gf.nfrag_t + 4) * 256);
     hipMemset(h->frags_g, 0, (size_t)(Gg.nfrag_f + Gg.nfrag_b + Gg.nfrag_t + 4) * 256);
-    *out = h;
+    *out = hold.release();
     return RNDE_OK;
 }
 
-extern "C" void rnde_nsde_destroy(rnde_nsde* h) {
-    if (!h) return;
-    void* d[] = {h->eigpart, h->frags_f, h->frags_g, h->slots, h->tape, h->noise, h->replay, h->meta, h->acc_meta, h->fin, h->svb,
-                 h->slab_f, h->slab_g, h->wslab, h->wslab_r, h->ev_t, h->part, h->sv_t_dev, h->head_ws, h->cg_ws};
-    for (void* p : d) if (p) (void)hipFree(p);
-    void* hd[] = {h->h_meta, h->h_acc_meta, h->h_fin, h->h_svb, h->h_part};
-    for (void* p : hd) if (p) (void)hipHostFree(p);
-    h->res.destroy();
-    for (hipEvent_t e : h->tev) if (e) (void)hipEventDestroy(e);
-    if (h->ev_host) (void)hipEventDestroy(h->ev_host);
-    delete h;
-}
+extern "C" void rnde_nsde_destroy(rnde_nsde* h) { delete h; }      // (every buffer and event is an owner)
 
 static SdeParams sde_params(rnde_nsde* h, const float* x, const float* noise, int n_pool, int B, float t0, float t1, int keep_tape) {
     SdeParams Q{};
@@ -308,12 +299,7 @@ static rnde_status nsde_forward_impl(rnde_nsde* h, const float* x_dev, const flo
             if (!(saveat_host[i] >= t0 && saveat_host[i] <= t1) || (i > 0 && !(saveat_host[i] > saveat_host[i - 1]))) {
                 h->err = "saveat must be increasing and inside [t0, t1]"; return RNDE_ERR_BAD_ARG;
             }
-        if ((size_t)n_saveat > h->sv_cap) {
-            if (h->sv_t_dev) (void)hipFree(h->sv_t_dev);
-            h->sv_t_dev = nullptr; h->sv_cap = 0;
-            SCHK(h, hipMalloc((void**)&h->sv_t_dev, (size_t)n_saveat * 4));
-            h->sv_cap = n_saveat;
-        }
+        SCHK(h, h->sv_t_dev.reserve((size_t)n_saveat));
         h->saveat.assign(saveat_host, saveat_host + n_saveat);
         SCHK(h, hipMemcpyAsync(h->sv_t_dev, h->saveat.data(), (size_t)n_saveat * 4, hipMemcpyHostToDevice, s));
     } else h->saveat.clear();
@@ -326,12 +312,7 @@ static rnde_status nsde_forward_impl(rnde_nsde* h, const float* x_dev, const flo
     const size_t A = (size_t)ntiles * h->NKD * 64;
     if (keep_tape) {
         const size_t need = (size_t)h->cfg.max_attempts * 12 * A;
-        if (h->tape_floats < need) {
-            if (h->tape) (void)hipFree(h->tape);
-            h->tape = nullptr; h->tape_floats = 0;
-            SCHK(h, hipMalloc((void**)&h->tape, need * 4));
-            h->tape_floats = need;
-        }
+        SCHK(h, h->tape.reserve(need));
     }
     bool lib_noise = false;
     if (!noise_dev) {   // the library's own stream: one pool per solve from (seed, epoch-independent: the seed alone names the path)
@@ -341,12 +322,7 @@ static rnde_status nsde_forward_impl(rnde_nsde* h, const float* x_dev, const flo
         lib_noise = true;
         n_pool = (h->pool_pred > 0 && n_steps == 0) ? std::min(h->pool_pred, h->cfg.max_attempts + 1) : h->cfg.max_attempts + 1;
         const size_t need = (size_t)n_pool * 2 * h->D * B;
-        if (h->noise_floats < need) {
-            if (h->noise) (void)hipFree(h->noise);
-            h->noise = nullptr; h->noise_floats = 0;
-            SCHK(h, hipMalloc((void**)&h->noise, need * 4));
-            h->noise_floats = need;
-        }
+        SCHK(h, h->noise.reserve(need));
         hipLaunchKernelGGL(rnde_normal_fill_kernel, dim3((unsigned)std::min<size_t>((need / 4 + 255) / 256, 4096)), dim3(256), 0, s, h->noise, (long long)need, (unsigned long long)seed, 0ull);
         SCHK(h, hipGetLastError());
         noise_dev = h->noise;
@@ -561,29 +537,18 @@ static rnde_status nsde_backward_impl(rnde_nsde* h, const float* u_bar_dev, cons
     // model trains, the step count creeps up by one or two per training step, and a hipFree + hipMalloc per step stalled the GPU for
     // ~0.4 ms of a 1.6 ms step (the free waits for the device).
     const size_t n_evals_cap = 4 * ((size_t)std::max(1, n_acc) * 3 / 2 + 16);
-    auto ensure = [&](float*& p, size_t& have, size_t need, size_t grow_to) -> bool {
-        if (have >= need) return true;
-        if (p) (void)hipFree(p);
-        p = nullptr; have = 0;
-        if (hipMalloc((void**)&p, grow_to * 4) != hipSuccess) {
-            if (hipMalloc((void**)&p, need * 4) != hipSuccess) return false;   // (no room for the head room: exactly what is needed)
-            grow_to = need;
-        }
-        have = grow_to;
-        return true;
+    auto ensure = [](DevBuf<float>& b, size_t need, size_t grow_to) {      // (no room for the head room: exactly what is needed)
+        return b.cap() >= need || b.reserve(grow_to) == hipSuccess || b.reserve(need) == hipSuccess;
     };
-    if (!ensure(h->slab_f, h->slab_f_floats, (size_t)n_evals * Bq.Cf.ev_stride, n_evals_cap * Bq.Cf.ev_stride) ||
-        !ensure(h->slab_g, h->slab_g_floats, (size_t)n_evals * Bq.Cg.ev_stride, n_evals_cap * Bq.Cg.ev_stride)) {
+    if (!ensure(h->slab_f, (size_t)n_evals * Bq.Cf.ev_stride, n_evals_cap * Bq.Cf.ev_stride) ||
+        !ensure(h->slab_g, (size_t)n_evals * Bq.Cg.ev_stride, n_evals_cap * Bq.Cg.ev_stride)) {
         h->err = "slab allocation failed"; return RNDE_ERR_HIP;
     }
-    if (h->ev_t_n < (size_t)n_evals) {
-        if (h->ev_t) (void)hipFree(h->ev_t);
-        h->ev_t = nullptr; h->ev_t_n = 0;
-        SCHK(h, hipMalloc((void**)&h->ev_t, n_evals_cap * 4));
+    if (h->ev_t.cap() < (size_t)n_evals) {
+        SCHK(h, h->ev_t.reserve(n_evals_cap));
         SCHK(h, hipMemsetAsync(h->ev_t, 0, n_evals_cap * 4, s));
-        h->ev_t_n = n_evals_cap;
     }
-    if (!h->wslab) { SCHK(h, hipMalloc((void**)&h->wslab, (size_t)96 * h->P * 4)); SCHK(h, hipMalloc((void**)&h->wslab_r, (size_t)16 * h->P * 4)); }
+    SCHK(h, h->wslab.reserve((size_t)96 * h->P)); SCHK(h, h->wslab_r.reserve((size_t)16 * h->P));
     Bq.Cf.slab = h->slab_f; Bq.Cg.slab = h->slab_g;
     if (n_acc == 0) {   // nothing was integrated: identity (never with saveat: t1 > t0 guarantees a step)
         if (Bq.nsave) { h->err = "reverse pass of a saveat solve without accepted steps"; return RNDE_ERR_NO_TAPE; }
@@ -641,12 +606,7 @@ extern "C" rnde_status rnde_nsde_backward_async(rnde_nsde* h, const float* u_bar
 // as rnde_classifier_head for the ODE classifier; reference src/models/supervised_classification.jl:96-97 + experiments/mnist_nsde.jl loss)
 static rnde_status nsde_head_reserve(rnde_nsde* h, int32_t B, int32_t n_classes) {
     const size_t need = (size_t)B * n_classes + B + (size_t)kHeadChunks * n_classes * h->D;
-    if (h->head_ws_floats < need) {
-        if (h->head_ws) (void)hipFree(h->head_ws);
-        h->head_ws = nullptr; h->head_ws_floats = 0;
-        SCHK(h, hipMalloc((void**)&h->head_ws, need * 4));
-        h->head_ws_floats = need;
-    }
+    SCHK(h, h->head_ws.reserve(need));
     return RNDE_OK;
 }
 extern "C" rnde_status rnde_nsde_classifier_head(rnde_nsde* h, const float* u_dev, const float* p3_dev, const float* y_dev, int32_t B, int32_t n_classes,
@@ -678,13 +638,8 @@ extern "C" rnde_status rnde_nsde_classifier_grad(rnde_nsde* h, const float* x_de
     if (B < 1 || B > h->cfg.max_batch || n_classes < 1 || n_classes > kHeadMaxC) return RNDE_ERR_BAD_ARG;
     SCHK(h, hipSetDevice(h->cfg.device));
     const size_t A = (size_t)h->D * B;
-    if (h->cg_ws_floats < 2 * A) {
-        if (h->cg_ws) (void)hipFree(h->cg_ws);
-        h->cg_ws = nullptr; h->cg_ws_floats = 0;
-        SCHK(h, hipMalloc((void**)&h->cg_ws, 2 * A * 4));
-        h->cg_ws_floats = 2 * A;
-    }
-    if (!h->ev_host) SCHK(h, hipEventCreateWithFlags(&h->ev_host, hipEventDisableTiming));
+    SCHK(h, h->cg_ws.reserve(2 * A));
+    SCHK(h, h->ev_host.create(hipEventDisableTiming));
     rnde_status st = nsde_head_reserve(h, B, n_classes);   // (the hook runs between an event record and the host's wait on it: it only enqueues)
     if (st != RNDE_OK) return st;
     float* u = h->cg_ws; float* ubar = h->cg_ws + A;
@@ -750,13 +705,8 @@ extern "C" rnde_status rnde_nsde_moment_grad(rnde_nsde* h, const float* x_dev, c
     SCHK(h, hipSetDevice(h->cfg.device));
     const size_t A = (size_t)h->D * n_saveat * B, X = (size_t)h->D * B;
     const size_t need = 2 * A + (x_bar_dev ? 0 : X);
-    if (h->cg_ws_floats < need) {
-        if (h->cg_ws) (void)hipFree(h->cg_ws);
-        h->cg_ws = nullptr; h->cg_ws_floats = 0;
-        SCHK(h, hipMalloc((void**)&h->cg_ws, need * 4));
-        h->cg_ws_floats = need;
-    }
-    if (!h->ev_host) SCHK(h, hipEventCreateWithFlags(&h->ev_host, hipEventDisableTiming));
+    SCHK(h, h->cg_ws.reserve(need));
+    SCHK(h, h->ev_host.create(hipEventDisableTiming));
     float* u = h->cg_ws; float* ubar = h->cg_ws + A;
     float* xbar = x_bar_dev ? x_bar_dev : h->cg_ws + 2 * A;
     h->cg_sv.resize((size_t)h->cfg.max_attempts + 1);
