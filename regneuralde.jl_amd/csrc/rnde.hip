@@ -221,16 +221,7 @@ static hipError_t launch_chain_t(rnde_node* h, const ChainParams& Q, int n, floa
 }
 template <int MODE>
 static hipError_t launch_chain(rnde_node* h, const ChainParams& Q, int n, float* u_out, hipStream_t s) {
-    if (h->chain_ga) switch (h->NKD) {     // (any served activation: the ALT = 2 kernels)
-        case 4: return launch_chain_t<4, MODE, 2>(h, Q, n, u_out, s);
-        case 8: return launch_chain_t<8, MODE, 2>(h, Q, n, u_out, s);
-        default: return launch_chain_t<16, MODE, 2>(h, Q, n, u_out, s);
-    }
-    switch (h->NKD) {
-        case 4: return launch_chain_t<4, MODE>(h, Q, n, u_out, s);
-        case 8: return h->chain_alt ? launch_chain_t<8, MODE, 1>(h, Q, n, u_out, s) : launch_chain_t<8, MODE>(h, Q, n, u_out, s);
-        default: return launch_chain_t<16, MODE>(h, Q, n, u_out, s);
-    }
+    return chain_variant(h, [&](auto nkd, auto alt) { return launch_chain_t<nkd(), MODE, alt()>(h, Q, n, u_out, s); });
 }
 MwParams make_mw_params(rnde_node* h, const StepParams& P) {
     MwParams Q{};
@@ -252,34 +243,7 @@ static hipError_t launch_mw_t(rnde_node* h, const MwParams& Q, int n, hipStream_
 }
 template <int MODE>
 static hipError_t launch_mw(rnde_node* h, const MwParams& Q, int n, hipStream_t s) {
-    if (h->chain_ga) {     // any served activation: the LAT = 2 kernels
-        const int tab = h->rk_tab;
-        switch (h->NKD) {
-            case 4: return tab == 2 ? launch_mw_t<1, MODE, 2, 2>(h, Q, n, s) : (tab ? launch_mw_t<1, MODE, 1, 2>(h, Q, n, s) : launch_mw_t<1, MODE, 0, 2>(h, Q, n, s));
-            case 8: return tab == 2 ? launch_mw_t<2, MODE, 2, 2>(h, Q, n, s) : (tab ? launch_mw_t<2, MODE, 1, 2>(h, Q, n, s) : launch_mw_t<2, MODE, 0, 2>(h, Q, n, s));
-            default: return tab == 2 ? launch_mw_t<4, MODE, 2, 2>(h, Q, n, s) : (tab ? launch_mw_t<4, MODE, 1, 2>(h, Q, n, s) : launch_mw_t<4, MODE, 0, 2>(h, Q, n, s));
-        }
-    }
-    if (h->rk_tab == 2) {      // S-stage table
-        switch (h->NKD) {
-            case 4: return launch_mw_t<1, MODE, 2>(h, Q, n, s);
-            case 8: return launch_mw_t<2, MODE, 2>(h, Q, n, s);
-            default: return launch_mw_t<4, MODE, 2>(h, Q, n, s);
-        }
-    }
-    if (h->mw_lat) return h->rk_tab ? launch_mw_t<2, MODE, 1, 1>(h, Q, n, s) : launch_mw_t<2, MODE, 0, 1>(h, Q, n, s);   // latent-ODE shape: weights register stationary
-    if (h->rk_tab) {
-        switch (h->NKD) {
-            case 4: return launch_mw_t<1, MODE, 1>(h, Q, n, s);
-            case 8: return launch_mw_t<2, MODE, 1>(h, Q, n, s);
-            default: return launch_mw_t<4, MODE, 1>(h, Q, n, s);
-        }
-    }
-    switch (h->NKD) {
-        case 4: return launch_mw_t<1, MODE, 0>(h, Q, n, s);
-        case 8: return launch_mw_t<2, MODE, 0>(h, Q, n, s);
-        default: return launch_mw_t<4, MODE, 0>(h, Q, n, s);
-    }
+    return mw_variant(h, [&](auto nr, auto tab, auto lat) { return launch_mw_t<nr(), MODE, tab(), lat()>(h, Q, n, s); });
 }
 // the forward tapes every layer input of every evaluation into the slab: make room for `evals` evaluations (growing keeps what is there)
 static rnde_status ensure_mw_slab(rnde_node* h, long long evals, int Bpad, hipStream_t s) {

@@ -490,6 +490,19 @@ static __global__ void rnde_wgrad_reduce(const float* __restrict__ slab, int n_c
         o[i] = s;
     }
 }
+// `chunks` partials of `len` floats in `slab` -> out.  Above 16 chunks in two passes: 16 chunk groups in parallel into slab_r (16 * len floats),
+// then their partial sums (fixed order => deterministic).
+static inline hipError_t launch_wgrad_reduce(const float* slab, int chunks, long long len, float* slab_r, float* out, hipStream_t s) {
+    const int grid = (int)((len + 255) / 256 < 2048 ? (len + 255) / 256 : 2048);
+    if (chunks <= 16) {
+        hipLaunchKernelGGL(rnde_wgrad_reduce, dim3(grid, 1), dim3(256), 0, s, slab, chunks, chunks, len, out);
+    } else {
+        const int per_group = (chunks + 15) / 16, groups = (chunks + per_group - 1) / per_group;
+        hipLaunchKernelGGL(rnde_wgrad_reduce, dim3(grid, groups), dim3(256), 0, s, slab, chunks, per_group, len, slab_r);
+        hipLaunchKernelGGL(rnde_wgrad_reduce, dim3(grid, 1), dim3(256), 0, s, (const float*)slab_r, groups, groups, len, out);
+    }
+    return hipGetLastError();
+}
 
 // the same for the two layers of the stage engine in ONE launch per pass (blockIdx.z = layer): four launches of ~9 us were two too many
 struct ReduceJob { const float* slab; float* out; long long len; int n_chunks, per_group; };

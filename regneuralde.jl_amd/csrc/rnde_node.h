@@ -23,6 +23,7 @@
 #include "rnde_bchain.h"
 #include "rnde_chainmw.h"
 #include "rnde_bchainmw.h"
+#include "rnde_rev_plan.h"
 
 #include <chrono>
 #include <algorithm>
@@ -34,6 +35,7 @@
 #include <functional>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 
@@ -54,7 +56,7 @@ struct rnde_node {
     Event wevents[66];
     Event tev[5];                         // rnde_node_set_timing: around the attempt loop of the forward, the reverse sweep and the rest of the reverse pass
     Event ev_host;                        // rnde_node_classifier_grad: what the forward's host wait uses
-    int engine = 1;                       // 1 column-owner, 2 stage kernels, 3 chain engine (rnde_chain.h), 4 tiled engine (rnde_node_tile.h)
+    int engine = 0;                       // set at creation: 2 stage kernels, 3 chain engine (rnde_chain.h), 4 tiled engine (rnde_node_tile.h)
     struct rnde_node_tiled* tiled = nullptr;   // engine 4: everything of that engine (rnde_node_tile.hip); the fields below it uses are cfg, D, P, h_meta, n_att, B, have_tape, err
     ChainGeo cg{}; DevBuf<float> cfrags; int NKD = 0, chain_alt = 0;
     int chain_ga = 0;             // a layer's activation is other than identity / tanh: the kernel variants that serve every rnde_act (ALT / LAT = 2)
@@ -151,6 +153,41 @@ rnde_status node_tiled_timing(rnde_node* h, float* fwd_ms, float* rev_sweep_ms, 
             return RNDE_ERR_BAD_ARG;                                                                                                     \
         }                                                                                                                                \
     } while (0)
+
+// ---- handle -> kernel instantiation, stated once per kernel family: the forward (rnde.hip) and the reverse (rnde_reverse.hip) of one handle launch
+// the same variant.  f is a generic lambda; it receives the template arguments as std::integral_constant values and is instantiated for the
+// combinations listed here and no other.
+template <int V> using IC = std::integral_constant<int, V>;
+// one-wave chain kernels (rnde_chain.h, rnde_bchain.h): f(NKD, ALT); ALT 2 serves every rnde_act, ALT 1 is the compile-time latent-ODE shape
+template <class F>
+static auto chain_variant(const rnde_node* h, F&& f) {
+    if (h->chain_ga) switch (h->NKD) {
+        case 4: return f(IC<4>{}, IC<2>{});
+        case 8: return f(IC<8>{}, IC<2>{});
+        default: return f(IC<16>{}, IC<2>{});
+    }
+    switch (h->NKD) {
+        case 4: return f(IC<4>{}, IC<0>{});
+        case 8: return h->chain_alt ? f(IC<8>{}, IC<1>{}) : f(IC<8>{}, IC<0>{});
+        default: return f(IC<16>{}, IC<0>{});
+    }
+}
+// multi-wave chain kernels (rnde_chainmw.h, rnde_bchainmw.h): f(NR, TAB, LAT); TAB 0 constant-folded Tsit5, 1 a 7-stage table, 2 an S-stage table;
+// LAT 2 serves every rnde_act, LAT 1 is the latent-ODE shape with register-stationary weights (NR 2, 7-stage pairs only)
+template <class F>
+static auto mw_variant(const rnde_node* h, F&& f) {
+    auto by_nr = [&](auto tab, auto lat) {
+        switch (h->NKD) {
+            case 4: return f(IC<1>{}, tab, lat);
+            case 8: return f(IC<2>{}, tab, lat);
+            default: return f(IC<4>{}, tab, lat);
+        }
+    };
+    auto by_tab = [&](auto lat) { return h->rk_tab == 2 ? by_nr(IC<2>{}, lat) : (h->rk_tab ? by_nr(IC<1>{}, lat) : by_nr(IC<0>{}, lat)); };
+    if (h->chain_ga) return by_tab(IC<2>{});
+    if (h->rk_tab != 2 && h->mw_lat) return h->rk_tab ? f(IC<2>{}, IC<1>{}, IC<1>{}) : f(IC<2>{}, IC<0>{}, IC<1>{});
+    return by_tab(IC<0>{});
+}
 
 static const rnde_status RNDE_INTERNAL_RETRY = static_cast<rnde_status>(100);
 // ---- rnde.hip, used by rnde_reverse.hip ----

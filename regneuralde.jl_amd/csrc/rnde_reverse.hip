@@ -67,10 +67,8 @@ static rnde_status bwd_prepare(rnde_node* h) {
         HIPCHK(h, hipStreamCreateWithPriority(&h->wstream.s, hipStreamNonBlocking, prio_least));   // never ahead of the sweep
         for (auto& e : h->wevents) HIPCHK(h, e.create(hipEventDisableTiming));
     }
-    if (h->engine == 2) {
-        HIPCHK(h, b.UTB.reserve(A)); HIPCHK(h, b.UNB.reserve(A)); HIPCHK(h, b.UPB0.reserve(A));
-        HIPCHK(h, b.GB.reserve(15 * A));   // gbar_1..6, EXK, EXG (stiffness extras), W_1..7 (saveat)
-    }
+    HIPCHK(h, b.UTB.reserve(A)); HIPCHK(h, b.UNB.reserve(A)); HIPCHK(h, b.UPB0.reserve(A));
+    HIPCHK(h, b.GB.reserve(15 * A));   // gbar_1..6, EXK, EXG (stiffness extras), W_1..7 (saveat)
     b.ready = true;
     return RNDE_OK;
 }
@@ -81,6 +79,8 @@ static bool wgrad3_ok(int M, int Nx) {
     return getenv("RNDE_WGRAD_LEGACY") == nullptr && getenv("RNDE_WGRAD_V2") == nullptr && M % 4 == 0 && Nx % 4 == 0 && wide > 656 &&
            wide <= 800 && narrow <= 112;
 }
+// The instantiations of one kernel template share a signature: each launch below picks its kernel as a function pointer from a small table.
+using WgradKern = decltype(&rnde_wgrad3_kernel<true>);      // (rnde_wgrad_kernel, rnde_wgrad2_kernel, rnde_wgrad3_kernel, rnde_wgrad3x_kernel)
 // `max_chunks` > 0 caps the number of chunks (two workgroups each) of the 16x16x4 kernel: 16 for the launches that run
 // underneath the sweep on the CUs it leaves idle, see bwd_run
 static rnde_status launch_wgrad_part(rnde_node* h, const EvalDesc* ev, int n_evals, int per_chunk, int M, int Nx, int Bpad,
@@ -114,12 +114,13 @@ static rnde_status launch_wgrad_part(rnde_node* h, const EvalDesc* ev, int n_eva
             const int spc4 = (total_steps + sc4 - 1) / sc4;
             sc4 = (total_steps + spc4 - 1) / spc4;
             if ((size_t)(*chunk_cursor + sc4) * (size_t)len > h->bw.slab_floats) { h->err = "weight-gradient slab overflow"; return RNDE_ERR_BAD_ARG; }
+            static constexpr decltype(&rnde_wgrad4x_kernel<true, 0>) kern4[2][2] = {{rnde_wgrad4x_kernel<false, 0>, rnde_wgrad4x_kernel<false, 1>},
+                                                                                    {rnde_wgrad4x_kernel<true, 0>, rnde_wgrad4x_kernel<true, 1>}};      // [tall][FEED]
+            static constexpr size_t lds4[2] = {kWx4LdsBytes, kWx4fLdsBytes};                                                                       // [FEED]
             static DeviceOnce attr4;
             if (attr4.need()) {
-                HIPCHK(h, hipFuncSetAttribute((const void*)rnde_wgrad4x_kernel<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWx4LdsBytes));
-                HIPCHK(h, hipFuncSetAttribute((const void*)rnde_wgrad4x_kernel<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWx4LdsBytes));
-                HIPCHK(h, hipFuncSetAttribute((const void*)rnde_wgrad4x_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWx4fLdsBytes));
-                HIPCHK(h, hipFuncSetAttribute((const void*)rnde_wgrad4x_kernel<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWx4fLdsBytes));
+                for (int t = 0; t < 2; ++t)
+                    for (int f = 0; f < 2; ++f) HIPCHK(h, hipFuncSetAttribute((const void*)kern4[t][f], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4[f]));
                 attr4.done();
             }
             const dim3 g4(32 * ((sc4 + 7) / 8));
@@ -131,37 +132,22 @@ static rnde_status launch_wgrad_part(rnde_node* h, const EvalDesc* ev, int n_eva
             const char* ef = getenv("RNDE_X3_WGRAD_FEED");
             const bool q0 = getenv("RNDE_X3_WGRAD_Q0") != nullptr || (ef ? ef[0] == '0' : kWx4DefaultFeed == 0);
 #endif
-            if (q0) {
-                if (tall) hipLaunchKernelGGL((rnde_wgrad4x_kernel<true, 0>), g4, dim3(448), kWx4LdsBytes, s, ev, n_evals, spc4, sc4, M, Nx, Bpad, dst);
-                else hipLaunchKernelGGL((rnde_wgrad4x_kernel<false, 0>), g4, dim3(448), kWx4LdsBytes, s, ev, n_evals, spc4, sc4, M, Nx, Bpad, dst);
-            } else if (tall) hipLaunchKernelGGL((rnde_wgrad4x_kernel<true, 1>), g4, dim3(448), kWx4fLdsBytes, s, ev, n_evals, spc4, sc4, M, Nx, Bpad, dst);
-            else hipLaunchKernelGGL((rnde_wgrad4x_kernel<false, 1>), g4, dim3(448), kWx4fLdsBytes, s, ev, n_evals, spc4, sc4, M, Nx, Bpad, dst);
+            const int feed = q0 ? 0 : 1;
+            hipLaunchKernelGGL(kern4[tall][feed], g4, dim3(448), lds4[feed], s, ev, n_evals, spc4, sc4, M, Nx, Bpad, dst);
             HIPCHK(h, hipGetLastError());
             *chunk_cursor += sc4;
             return RNDE_OK;
         }
-        if (h->x3_packed && !x3_off) {
-            static DeviceOnce attrx;
-            if (attrx.need()) {
-                HIPCHK(h, hipFuncSetAttribute((const void*)rnde_wgrad3x_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWxLdsBytes));
-                HIPCHK(h, hipFuncSetAttribute((const void*)rnde_wgrad3x_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWxLdsBytes));
-                attrx.done();
-            }
-            if (tall) hipLaunchKernelGGL((rnde_wgrad3x_kernel<true>), dim3(2, sc), dim3(448), kWxLdsBytes, s, ev, n_evals, steps_per_chunk, M, Nx, Bpad, dst);
-            else hipLaunchKernelGGL((rnde_wgrad3x_kernel<false>), dim3(2, sc), dim3(448), kWxLdsBytes, s, ev, n_evals, steps_per_chunk, M, Nx, Bpad, dst);
-            HIPCHK(h, hipGetLastError());
-            *chunk_cursor += sc;
-            return RNDE_OK;
+        // the 16x16x4 kernel proper, bf16x3 (rnde_wgradx.h) or fp32 inputs (rnde_bwd.h): [x3][tall]
+        static constexpr WgradKern kern3[2][2] = {{rnde_wgrad3_kernel<false>, rnde_wgrad3_kernel<true>}, {rnde_wgrad3x_kernel<false>, rnde_wgrad3x_kernel<true>}};
+        static constexpr size_t lds3[2] = {(size_t)2 * 32 * (464 + 144) * sizeof(float) /* two buffers */, kWxLdsBytes};
+        static DeviceOnce attr3[2];
+        const int x3 = (h->x3_packed && !x3_off) ? 1 : 0;
+        if (attr3[x3].need()) {
+            for (int t = 0; t < 2; ++t) HIPCHK(h, hipFuncSetAttribute((const void*)kern3[x3][t], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3[x3]));
+            attr3[x3].done();
         }
-        const size_t lds = (size_t)2 * 32 * (464 + 144) * sizeof(float);   // two buffers
-        static DeviceOnce attr;
-        if (attr.need()) {
-            HIPCHK(h, hipFuncSetAttribute((const void*)rnde_wgrad3_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            HIPCHK(h, hipFuncSetAttribute((const void*)rnde_wgrad3_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr.done();
-        }
-        if (tall) hipLaunchKernelGGL((rnde_wgrad3_kernel<true>), dim3(2, sc), dim3(448), lds, s, ev, n_evals, steps_per_chunk, M, Nx, Bpad, dst);
-        else hipLaunchKernelGGL((rnde_wgrad3_kernel<false>), dim3(2, sc), dim3(448), lds, s, ev, n_evals, steps_per_chunk, M, Nx, Bpad, dst);
+        hipLaunchKernelGGL(kern3[x3][tall], dim3(2, sc), dim3(448), lds3[x3], s, ev, n_evals, steps_per_chunk, M, Nx, Bpad, dst);
         HIPCHK(h, hipGetLastError());
         *chunk_cursor += sc;
         return RNDE_OK;
@@ -176,8 +162,8 @@ static rnde_status launch_wgrad_part(rnde_node* h, const EvalDesc* ev, int n_eva
         const int steps_per_chunk = (total_steps + sc - 1) / sc;
         sc = (total_steps + steps_per_chunk - 1) / steps_per_chunk;
         if ((size_t)(*chunk_cursor + sc) * (size_t)len > h->bw.slab_floats) { h->err = "weight-gradient slab overflow"; return RNDE_ERR_BAD_ARG; }
-        if (tall) hipLaunchKernelGGL((rnde_wgrad2_kernel<true>), dim3(pblocks, sc), dim3(256), 0, s, ev, n_evals, steps_per_chunk, M, Nx, Bpad, dst);
-        else hipLaunchKernelGGL((rnde_wgrad2_kernel<false>), dim3(pblocks, sc), dim3(256), 0, s, ev, n_evals, steps_per_chunk, M, Nx, Bpad, dst);
+        static constexpr WgradKern kern2[2] = {rnde_wgrad2_kernel<false>, rnde_wgrad2_kernel<true>};      // [tall]
+        hipLaunchKernelGGL(kern2[tall], dim3(pblocks, sc), dim3(256), 0, s, ev, n_evals, steps_per_chunk, M, Nx, Bpad, dst);
         HIPCHK(h, hipGetLastError());
         *chunk_cursor += sc;
         return RNDE_OK;
@@ -185,27 +171,41 @@ static rnde_status launch_wgrad_part(rnde_node* h, const EvalDesc* ev, int n_eva
         // (this check used to sit in front of ALL paths with the direct kernels' chunk count -- up to 240 -- and refused solves of more than ~65
         //  attempts on the 16x16x4 path, which needs 127 chunks behind the sweep: "slab overflow" in a training run whose step count had grown)
         if ((size_t)(*chunk_cursor + chunks) * (size_t)len > h->bw.slab_floats) { h->err = "weight-gradient slab overflow"; return RNDE_ERR_BAD_ARG; }
-        if (tall) hipLaunchKernelGGL((rnde_wgrad_kernel<2, 4>), dim3(blocks, chunks), dim3(64), 0, s, ev, n_evals, per_chunk, M, Nx, Bpad, dst);
-        else hipLaunchKernelGGL((rnde_wgrad_kernel<4, 2>), dim3(blocks, chunks), dim3(64), 0, s, ev, n_evals, per_chunk, M, Nx, Bpad, dst);
+        static constexpr WgradKern kern[2] = {rnde_wgrad_kernel<4, 2>, rnde_wgrad_kernel<2, 4>};      // [tall]: <MB, NB>
+        hipLaunchKernelGGL(kern[tall], dim3(blocks, chunks), dim3(64), 0, s, ev, n_evals, per_chunk, M, Nx, Bpad, dst);
     }
     HIPCHK(h, hipGetLastError());
     *chunk_cursor += chunks;
     return RNDE_OK;
 }
-static rnde_status launch_wgrad_reduce(rnde_node* h, const float* slab, int chunks, int M, int Nx, float* out, hipStream_t s) {
-    const long long len = (long long)M * (Nx + 2);
-    const int grid = (int)std::min<long long>((len + 255) / 256, 2048);
-    if (chunks <= 16) {
-        hipLaunchKernelGGL(rnde_wgrad_reduce, dim3(grid, 1), dim3(256), 0, s, slab, chunks, chunks, len, out);
-    } else {   // two passes: 16 chunk groups in parallel, then their 16 partial sums (fixed order => deterministic)
-        const int per_group = (chunks + 15) / 16, groups = (chunks + per_group - 1) / per_group;
-        hipLaunchKernelGGL(rnde_wgrad_reduce, dim3(grid, groups), dim3(256), 0, s, slab, chunks, per_group, len, h->bw.slab_r);
-        hipLaunchKernelGGL(rnde_wgrad_reduce, dim3(grid, 1), dim3(256), 0, s, (const float*)h->bw.slab_r, groups, groups, len, out);
-    }
-    HIPCHK(h, hipGetLastError());
-    return RNDE_OK;
-}
 
+// ---- what the three engines' run functions share ------------------------------------------------------------------------------------
+// the saved-value cotangent per attempt into h_svb (coupled controller: every rank passes the cotangent of its own loss; the shared scalars then
+// carry `world` times the single-device cotangent, like everything else -- see rnde_node_set_coupling)
+static void gather_saveval_bar(rnde_node* h, const float* saveval_bar_host) {
+    gather_svb(h->sv_index.data(), h->n_att, h->couple ? (float)h->couple_world : 1.f, saveval_bar_host, h->bw.h_svb);
+}
+// which saveat indices each attempt of the recorded solve covers (all empty without saveat)
+static std::vector<SaveRange> save_ranges(const rnde_node* h) {
+    std::vector<SaveRange> rng((size_t)std::max(1, h->n_att), SaveRange{0, 0});
+    save_plan(h->saveat.data(), (int)h->saveat.size(), h->t0, h->h_meta, h->n_att, F_ACCEPT, rng.data());
+    return rng;
+}
+// the parameter block every reverse kernel starts from (the stage engine replaces svb_att by its place in the one host-to-device copy)
+static BwdParams fill_bwd_params(rnde_node* h, const float* u_bar_dev, float* x_bar_dev) {
+    const BwdBuffers& b = h->bw;
+    BwdParams Q{};
+    Q.F = make_params(h, h->xcopy, h->B, h->t0, h->t1, 1);
+    Q.U = b.U; Q.K1 = b.K1; Q.UB1 = b.UB1; Q.zi2 = b.zi2; Q.zi1 = b.zi1; Q.svb_att = b.svb_att;
+    Q.bstate = b.bstate; Q.ibstate = b.ibstate; Q.bpart = b.bpart; Q.ipart = b.ipart;
+    Q.ubar = u_bar_dev; Q.xbar = x_bar_dev; Q.tspan_out = b.tspan_out;
+    Q.n_att = h->n_att; Q.track_ctrl = h->cfg.track_ctrl; Q.track_initdt = h->cfg.track_initdt; Q.reg_kind = h->cfg.regularize;
+    Q.bpart_n = Q.F.nwg;
+    Q.tspan_scale = h->couple ? 1.f / (float)h->couple_world : 1.f;
+    Q.sv_T = (int)h->saveat.size();
+    Q.sv_ubar0 = (!h->saveat.empty() && h->saveat[0] == h->t0) ? u_bar_dev : nullptr;
+    return Q;
+}
 static rnde_status bwd_run(rnde_node* h, const float* u_bar_dev, const float* saveval_bar_host, float* x_bar_dev,
                            float* p_bar_dev, float* tspan_bar_host, hipStream_t s, bool sync, float* tspan_bar_dev) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -213,30 +213,17 @@ static rnde_status bwd_run(rnde_node* h, const float* u_bar_dev, const float* sa
     if (st != RNDE_OK) return st;
     BwdBuffers& b = h->bw;
     int n_att = h->n_att;
-    // (coupled controller: every rank passes the cotangent of its own loss; the shared scalars then carry `world` times the
-    //  single-device cotangent, like everything else -- see rnde_node_set_coupling)
-    const float svb_scale = h->couple ? (float)h->couple_world : 1.f;
-    for (int i = 0; i < n_att; ++i)
-        b.h_svb[i] = (saveval_bar_host && h->sv_index[i] >= 0) ? svb_scale * saveval_bar_host[h->sv_index[i]] : 0.f;
+    gather_saveval_bar(h, saveval_bar_host);
     // one host-to-device copy for everything the reverse pass reads from the host: [ev1 (ne) | ev2 (ne) | svb (n_att)], ne = 2 + 6 n_att
     const int ne_all = 2 + 6 * n_att;
     EvalDesc* const h_ev1 = b.h_ev1; EvalDesc* const h_ev2 = b.h_ev1 + ne_all; float* const h_svb_blob = (float*)(b.h_ev1 + 2 * (size_t)ne_all);
     EvalDesc* const d_ev1 = b.ev1;   EvalDesc* const d_ev2 = b.ev1 + ne_all;   float* const d_svb = (float*)(b.ev1 + 2 * (size_t)ne_all);
     memcpy(h_svb_blob, b.h_svb, (size_t)n_att * 4);
-    BwdParams Q{};
-    Q.F = make_params(h, h->xcopy, h->B, h->t0, h->t1, 1);
-    Q.U = b.U; Q.K1 = b.K1; Q.UB1 = b.UB1; Q.zi2 = b.zi2; Q.zi1 = b.zi1; Q.svb_att = d_svb;
-    Q.bstate = b.bstate; Q.ibstate = b.ibstate; Q.bpart = b.bpart; Q.ipart = b.ipart;
-    Q.ubar = u_bar_dev; Q.xbar = x_bar_dev; Q.tspan_out = b.tspan_out;
-    Q.n_att = n_att; Q.track_ctrl = h->cfg.track_ctrl; Q.track_initdt = h->cfg.track_initdt; Q.reg_kind = h->cfg.regularize;
-    Q.bpart_n = Q.F.nwg;
-    Q.tspan_scale = h->couple ? 1.f / (float)h->couple_world : 1.f;
+    BwdParams Q = fill_bwd_params(h, u_bar_dev, x_bar_dev);
+    Q.svb_att = d_svb;
 #ifdef RNDE_DIAG
     if (getenv("RNDE_DIAG_BWD")) { (void)h->diag_buf.reserve(2048); hipMemset(h->diag_buf, 0, 512); Q.F.dbg_out = h->diag_buf; }
 #endif
-    Q.sv_T = (int)h->saveat.size();
-    Q.sv_ubar0 = (!h->saveat.empty() && h->saveat[0] == h->t0) ? u_bar_dev : nullptr;
-    if (!h->saveat.empty() && h->engine != 2) { h->err = "saveat reverse pass runs on the stage engine only"; return RNDE_ERR_BAD_ARG; }
     // ---- evaluation descriptors for the parameter-gradient GEMMs (all pointers are known before the sweep) ----
     const long long A = (long long)h->D * Q.F.Bpad, HB = (long long)h->H * Q.F.Bpad;
     RecLayout L{A, HB};
@@ -270,7 +257,7 @@ static rnde_status bwd_run(rnde_node* h, const float* u_bar_dev, const float* sa
     // unrestricted grids was a net loss (the GEMM waves took CUs the sweep's workgroups needed: 6.4 -> 8.4..9.8 ms per step).
     const int side_pct = h->wgrad_side_pct;
     const int sweep_cus = 8 * h->sR * ((Q.F.Bpad / 16 + 7) / 8);
-    const bool side = h->engine == 2 && h->persist == 1 && side_pct > 0 && n_att >= 8 && sweep_cus <= 224 &&
+    const bool side = h->persist == 1 && side_pct > 0 && n_att >= 8 && sweep_cus <= 224 &&
                       wgrad3_ok(h->H, h->D) && wgrad3_ok(h->D, h->H);
     const int side_att = side ? std::min(n_att, n_att * side_pct / 100) : 0;      // attempts [n_att - side_att, n_att)
     const int group = std::max(4, (side_att + 5) / 6);                             // <= 6 side launches per layer (slab space: 16 chunks each)
@@ -292,8 +279,8 @@ static rnde_status bwd_run(rnde_node* h, const float* u_bar_dev, const float* sa
     hipError_t e;
     h->tev_bwd = false;
     if (h->timing) HIPCHK(h, hipEventRecord(h->tev[2], s));
-    if (h->engine == 2) {
-        // stage engine sweep: one persistent launch per reversed attempt (fallback: 7 launches); then the (column-owner) kernels for the initialisation part
+    {
+        // the sweep: one persistent launch per reversed attempt (fallback: 7 launches); then the kernels for the initialisation part
         if (!h->rev_packed) {
             HIPCHK(h, stage_pack(h, h->pcopy, h->spwBt, 2, h->sMT, h->sKHb, s));
             HIPCHK(h, stage_pack(h, h->pcopy, h->spwDt, 3, h->sHT, h->sMT, s));
@@ -311,73 +298,55 @@ static rnde_status bwd_run(rnde_node* h, const float* u_bar_dev, const float* sa
         const bool pre_reduce = h->persist == 1 && Q.bpart_n >= 896 && !getenv("RNDE_NO_BPART_REDUCE");
         if (pre_reduce) BQ.B.bsum = bsum;
         const dim3 grid(BQ.R * BQ.C), blk(64 * BQ.WT);
-        // saveat: which save indices each accepted attempt covers (same float comparisons as the forward controller)
-        std::vector<int> sv_lo(n_att, 0), sv_hi(n_att, 0);
-        if (!h->saveat.empty()) {
-            int ns = (h->saveat[0] == h->t0) ? 1 : 0;
-            for (int n = 0; n < n_att; ++n) {
-                sv_lo[n] = ns;
-                if (h->h_meta[n].flags & F_ACCEPT) {
-                    const float tnew = h->h_meta[n].t + h->h_meta[n].dt;
-                    while (ns < (int)h->saveat.size() && h->saveat[ns] <= tnew) ++ns;
-                }
-                sv_hi[n] = ns;
-            }
-        }
-        // cotangent coefficients of eigen_est for an attempt (host-known: saveval cotangent, callback form, recorded norms)
-        auto eig_coefs = [&](int n, float& c1, float& c2) {
-            c1 = 0.f; c2 = 0.f;
-            const StepMeta& mm = h->h_meta[n];
-            const bool eg_ok = !(mm.eigen == 0.f || mm.eigen != mm.eigen);
-            double eigb = 0.0;
-            if (h->cfg.regularize == RNDE_REG_STIFF && eg_ok) eigb = (double)b.h_svb[n] * (mm.eigen > 0 ? 1.0 : -1.0) / 3.5068;
-            if (h->cfg.regularize == RNDE_REG_ERR_STIFF && eg_ok) eigb = 0.1 * (double)b.h_svb[n] / 3.5068;
-            if (h->cfg.regularize == RNDE_REG_STIFF_DT && eg_ok) eigb = (double)b.h_svb[n] * ((double)mm.eigen * (double)mm.dt > 0 ? 1.0 : -1.0) * (double)mm.dt;      // |eigen_est * dt| (test/test_node.jl:75)
-            if (eigb != 0.0 && mm.n1 > 0.f && mm.n2 > 0.f) {
-                c1 = (float)(eigb / ((double)mm.n2 * (double)mm.n1));
-                c2 = (float)(-eigb * ((double)mm.n1 / (double)mm.n2) / ((double)mm.n2 * (double)mm.n2));
-            }
-        };
+        const std::vector<SaveRange> rng = save_ranges(h);
+        const int a2 = h->act2 ? 1 : 0;
+        // the instantiations of each kernel template share a signature: the kernel is a function pointer from a table, one launch statement per family
+        using BAttemptKern = decltype(&rnde_bstage_attempt_kernel<0, 0>);
+        static constexpr BAttemptKern kAttempt[2][2] = {{rnde_bstage_attempt_kernel<0, 0>, rnde_bstage_attempt_kernel<0, 1>},
+                                                        {rnde_bstage_attempt_kernel<1, 0>, rnde_bstage_attempt_kernel<1, 1>}};      // [ACT2][FIX]
+        static constexpr BAttemptKern kAttemptX3[2][4] = {      // [ACT2][EX]: the fixed geometry in matrix mode 1
+            {rnde_bstage_attempt_kernel<0, 1, 1, 0>, rnde_bstage_attempt_kernel<0, 1, 1, 1>, rnde_bstage_attempt_kernel<0, 1, 1, 2>, rnde_bstage_attempt_kernel<0, 1, 1, 3>},
+            {rnde_bstage_attempt_kernel<1, 1, 1, 0>, rnde_bstage_attempt_kernel<1, 1, 1, 1>, rnde_bstage_attempt_kernel<1, 1, 1, 2>, rnde_bstage_attempt_kernel<1, 1, 1, 3>}};
+        static constexpr decltype(&rnde_bstage_kernel<0, BM_START>) kStage[2][2] = {{rnde_bstage_kernel<0, BM_START>, rnde_bstage_kernel<0, BM_STAGE>},
+                                                                                   {rnde_bstage_kernel<1, BM_START>, rnde_bstage_kernel<1, BM_STAGE>}};      // [ACT2][MODE]
+        static constexpr decltype(&rnde_binit_stage_kernel<0, 0>) kInit[2][4] = {      // [ACT2][STEP]
+            {rnde_binit_stage_kernel<0, 0>, rnde_binit_stage_kernel<0, 1>, rnde_binit_stage_kernel<0, 2>, rnde_binit_stage_kernel<0, 3>},
+            {rnde_binit_stage_kernel<1, 0>, rnde_binit_stage_kernel<1, 1>, rnde_binit_stage_kernel<1, 2>, rnde_binit_stage_kernel<1, 3>}};
         for (int n = n_att - 1; n >= 0; --n) {
-            float c1 = 0.f, c2 = 0.f;
-            eig_coefs(n, c1, c2);
+            float c1 = 0.f, c2 = 0.f;      // cotangent coefficients of eigen_est (host-known: saveval cotangent, callback form, recorded norms)
+            eig_cotangent(h->cfg.regularize, b.h_svb[n], h->h_meta[n], &c1, &c2);
             const double qo = pow((double)h->h_meta[n].qold_in, (double)kBeta2);   // for the scalar adjoint chain of the attempt
             if (h->persist == 1) {   // the attempt's 7 reverse launches as one (rnde_bstage_persist.h)
                 PersistSync Y{h->tslab, h->pabort, h->pxcc, h->persist_spins};
                 HIPCHK(h, slab_prepare(h, Q.F.Bpad, s));
                 const dim3 pgrid(8 * BQ.R * ((BQ.C + 7) / 8));
                 const bool fix = BQ.WT == 7 && BQ.HT == 7 && BQ.KHb == 7 && BQ.MT == 49 && BQ.R == 7 && h->D == 784 && h->H == 100 && !h->stage_generic;
+                BAttemptKern kern = kAttempt[a2][fix];
+                size_t lds = h->stage_lds;
                 if (fix) {
                     // (+ the START-staged tape operands of the six stages, rnde_bstage_persist.h: 6 x 7 waves x 2 arrays x 1 KiB)
-                    const size_t flds = h->stage_lds + (size_t)(RNDE_BSTAGE_HDMA ? 1 : 0) * 6 * 7 * 2 * 1024;
+                    lds = h->stage_lds + (size_t)(RNDE_BSTAGE_HDMA ? 1 : 0) * 6 * 7 * 2 * 1024;
                     static DeviceOnce attr;
                     if (attr.need()) {
-                        HIPCHK(h, hipFuncSetAttribute((const void*)rnde_bstage_attempt_kernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                        HIPCHK(h, hipFuncSetAttribute((const void*)rnde_bstage_attempt_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                        for (int a = 0; a < 2; ++a) HIPCHK(h, hipFuncSetAttribute((const void*)kAttempt[a][1], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
                         attr.done();
                     }
                     // matrix mode 1 (rnde_x3.h): the forward ran the x3 solve and split the transposed weights too; the x3 form serves every callback of the
                     // experiments (the eigen_est cotangents fit since the partial sums became scalars: 198 VGPRs), and saveat in an instantiation of its own (256)
                     const bool x3 = h->x3_packed && h->x3Bt && h->x3Dt && !getenv("RNDE_X3_REV_OFF");
                     if (x3) {
-                        const size_t xlds = sizeof(float) * ((size_t)2 * kX3ImageFloats + 64) + (size_t)(RNDE_BSTAGE_HDMA ? 1 : 0) * 6 * 7 * 2 * 1024;
+                        lds = sizeof(float) * ((size_t)2 * kX3ImageFloats + 64) + (size_t)(RNDE_BSTAGE_HDMA ? 1 : 0) * 6 * 7 * 2 * 1024;
                         static DeviceOnce attr3;
                         if (attr3.need()) {
-#define RNDE_X3_ATTR(A, E) HIPCHK(h, hipFuncSetAttribute((const void*)rnde_bstage_attempt_kernel<A, 1, 1, E>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                            RNDE_X3_ATTR(1, 0) RNDE_X3_ATTR(1, 1) RNDE_X3_ATTR(1, 2) RNDE_X3_ATTR(1, 3) RNDE_X3_ATTR(0, 0) RNDE_X3_ATTR(0, 1) RNDE_X3_ATTR(0, 2) RNDE_X3_ATTR(0, 3)
-#undef RNDE_X3_ATTR
+                            for (int a = 0; a < 2; ++a)
+                                for (int e = 0; e < 4; ++e) HIPCHK(h, hipFuncSetAttribute((const void*)kAttemptX3[a][e], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
                             attr3.done();
                         }
                         // the instantiation by what this reverse pass needs: saveat cotangents (bit 0), eigen_est cotangents (bit 1: the three stiffness callbacks)
-                        const int ex = (h->saveat.empty() ? 0 : 1) | (h->cfg.regularize >= RNDE_REG_STIFF ? 2 : 0);
-#define RNDE_X3_LAUNCH(A, E) hipLaunchKernelGGL((rnde_bstage_attempt_kernel<A, 1, 1, E>), pgrid, blk, xlds, s, BQ, n, h->h_meta[n], c1, c2, sv_lo[n], sv_hi[n], Y, qo, b.h_svb[n])
-                        if (h->act2) { if (ex == 0) RNDE_X3_LAUNCH(1, 0); else if (ex == 1) RNDE_X3_LAUNCH(1, 1); else if (ex == 2) RNDE_X3_LAUNCH(1, 2); else RNDE_X3_LAUNCH(1, 3); }
-                        else { if (ex == 0) RNDE_X3_LAUNCH(0, 0); else if (ex == 1) RNDE_X3_LAUNCH(0, 1); else if (ex == 2) RNDE_X3_LAUNCH(0, 2); else RNDE_X3_LAUNCH(0, 3); }
-#undef RNDE_X3_LAUNCH
-                    } else if (h->act2) hipLaunchKernelGGL((rnde_bstage_attempt_kernel<1, 1>), pgrid, blk, flds, s, BQ, n, h->h_meta[n], c1, c2, sv_lo[n], sv_hi[n], Y, qo, b.h_svb[n]);
-                    else hipLaunchKernelGGL((rnde_bstage_attempt_kernel<0, 1>), pgrid, blk, flds, s, BQ, n, h->h_meta[n], c1, c2, sv_lo[n], sv_hi[n], Y, qo, b.h_svb[n]);
-                } else if (h->act2) hipLaunchKernelGGL((rnde_bstage_attempt_kernel<1, 0>), pgrid, blk, h->stage_lds, s, BQ, n, h->h_meta[n], c1, c2, sv_lo[n], sv_hi[n], Y, qo, b.h_svb[n]);
-                else hipLaunchKernelGGL((rnde_bstage_attempt_kernel<0, 0>), pgrid, blk, h->stage_lds, s, BQ, n, h->h_meta[n], c1, c2, sv_lo[n], sv_hi[n], Y, qo, b.h_svb[n]);
+                        kern = kAttemptX3[a2][(h->saveat.empty() ? 0 : 1) | (h->cfg.regularize >= RNDE_REG_STIFF ? 2 : 0)];
+                    }
+                }
+                hipLaunchKernelGGL(kern, pgrid, blk, lds, s, BQ, n, h->h_meta[n], c1, c2, rng[n].lo, rng[n].hi, Y, qo, b.h_svb[n]);
                 if ((st = couple_sum(h, b.bpart + (size_t)(n & 1) * Q.bpart_n * 4, 4LL * Q.bpart_n, s)) != RNDE_OK) return st;
                 if (pre_reduce && n > 0) hipLaunchKernelGGL(rnde_bpart_reduce_kernel, dim3(1), dim3(64), 0, s, Q, n, bsum);      // (attempt 0's partials go to the reverse of the initial-step rule, which sums them itself)
                 if (n >= n_att - side_att && (hi_att - n >= group || n == n_att - side_att)) {   // attempts [n, hi_att) are final
@@ -387,32 +356,17 @@ static rnde_status bwd_run(rnde_node* h, const float* u_bar_dev, const float* sa
                 }
                 continue;
             }
-            if (h->act2) hipLaunchKernelGGL((rnde_bstage_kernel<1, BM_START>), grid, blk, h->stage_lds, s, BQ, n, 0, h->h_meta[n], c1, c2, sv_lo[n], sv_hi[n], qo);
-            else hipLaunchKernelGGL((rnde_bstage_kernel<0, BM_START>), grid, blk, h->stage_lds, s, BQ, n, 0, h->h_meta[n], c1, c2, sv_lo[n], sv_hi[n], qo);
-            for (int j = 6; j >= 1; --j) {
-                if (h->act2) hipLaunchKernelGGL((rnde_bstage_kernel<1, BM_STAGE>), grid, blk, h->stage_lds, s, BQ, n, j, h->h_meta[n], c1, c2, sv_lo[n], sv_hi[n], qo);
-                else hipLaunchKernelGGL((rnde_bstage_kernel<0, BM_STAGE>), grid, blk, h->stage_lds, s, BQ, n, j, h->h_meta[n], c1, c2, sv_lo[n], sv_hi[n], qo);
-            }
+            hipLaunchKernelGGL(kStage[a2][BM_START], grid, blk, h->stage_lds, s, BQ, n, 0, h->h_meta[n], c1, c2, rng[n].lo, rng[n].hi, qo);
+            for (int j = 6; j >= 1; --j) hipLaunchKernelGGL(kStage[a2][BM_STAGE], grid, blk, h->stage_lds, s, BQ, n, j, h->h_meta[n], c1, c2, rng[n].lo, rng[n].hi, qo);
             if ((st = couple_sum(h, b.bpart + (size_t)(n & 1) * Q.bpart_n * 4, 4LL * Q.bpart_n, s)) != RNDE_OK) return st;
         }
         HIPCHK(h, hipGetLastError());
         {   // reverse of the initial-step rule: four stage-engine launches (rnde_binit_stage.h)
-            if (h->act2) {
-                hipLaunchKernelGGL((rnde_binit_stage_kernel<1, 0>), grid, blk, h->stage_lds, s, BQ);
-                hipLaunchKernelGGL((rnde_binit_stage_kernel<1, 1>), grid, blk, h->stage_lds, s, BQ);
-            } else {
-                hipLaunchKernelGGL((rnde_binit_stage_kernel<0, 0>), grid, blk, h->stage_lds, s, BQ);
-                hipLaunchKernelGGL((rnde_binit_stage_kernel<0, 1>), grid, blk, h->stage_lds, s, BQ);
+            for (int step = 0; step < 4; ++step) {
+                hipLaunchKernelGGL(kInit[a2][step], grid, blk, h->stage_lds, s, BQ);
+                // (coupled controller) after step 1: dot, tau of the reversed second evaluation; after step 3: tau of the first
+                if ((step & 1) && (st = couple_sum(h, Q.ipart + (step / 2) * 4LL * Q.F.nwg, 4LL * Q.F.nwg, s)) != RNDE_OK) return st;
             }
-            if ((st = couple_sum(h, Q.ipart, 4LL * Q.F.nwg, s)) != RNDE_OK) return st;                       // (coupled controller: dot, tau of the reversed second evaluation)
-            if (h->act2) {
-                hipLaunchKernelGGL((rnde_binit_stage_kernel<1, 2>), grid, blk, h->stage_lds, s, BQ);
-                hipLaunchKernelGGL((rnde_binit_stage_kernel<1, 3>), grid, blk, h->stage_lds, s, BQ);
-            } else {
-                hipLaunchKernelGGL((rnde_binit_stage_kernel<0, 2>), grid, blk, h->stage_lds, s, BQ);
-                hipLaunchKernelGGL((rnde_binit_stage_kernel<0, 3>), grid, blk, h->stage_lds, s, BQ);
-            }
-            if ((st = couple_sum(h, Q.ipart + 4LL * Q.F.nwg, 4LL * Q.F.nwg, s)) != RNDE_OK) return st;      // tau of the first
             hipLaunchKernelGGL(rnde_bfin_kernel, dim3(1), dim3(64), 0, s, Q);
             HIPCHK(h, hipGetLastError());
         }
@@ -438,14 +392,12 @@ static rnde_status bwd_run(rnde_node* h, const float* u_bar_dev, const float* sa
         hipLaunchKernelGGL(rnde_wgrad_reduce_pair, dim3(grid, 1, 2), dim3(256), 0, s, Bp);
         HIPCHK(h, hipGetLastError());
     } else {
-        st = launch_wgrad_reduce(h, slab1, cur1, h->H, h->D, p_bar_dev, s);                                    // [W1; b1]
-        if (st != RNDE_OK) return st;
-        st = launch_wgrad_reduce(h, slab2w, cur2, h->D, h->H, p_bar_dev + (size_t)h->H * (h->D + 2), s);      // [W2; b2]
-        if (st != RNDE_OK) return st;
+        HIPCHK(h, launch_wgrad_reduce(slab1, cur1, (long long)h->H * (h->D + 2), b.slab_r, p_bar_dev, s));                                       // [W1; b1]
+        HIPCHK(h, launch_wgrad_reduce(slab2w, cur2, (long long)h->D * (h->H + 2), b.slab_r, p_bar_dev + (size_t)h->H * (h->D + 2), s));      // [W2; b2]
     }
     if (h->timing) { HIPCHK(h, hipEventRecord(h->tev[4], s)); h->tev_bwd = true; }
 #ifdef RNDE_DIAG
-    if (h->engine == 2 && h->persist == 1 && getenv("RNDE_DIAG_BWD")) {
+    if (h->persist == 1 && getenv("RNDE_DIAG_BWD")) {
         unsigned long long hst[64] = {0};
         hipStreamSynchronize(s);
         hipMemcpy(hst, h->diag_buf, sizeof(hst), hipMemcpyDeviceToHost);
@@ -459,16 +411,16 @@ static rnde_status bwd_run(rnde_node* h, const float* u_bar_dev, const float* sa
     if (!sync) {   // rnde_node_backward_async: no host round trip; the health words are looked at by the next synchronising call
         if (tspan_bar_dev) HIPCHK(h, hipMemcpyAsync(tspan_bar_dev, b.tspan_out, 8, hipMemcpyDeviceToDevice, s));
         h->have_tape = false;
-        h->pending_bwd = (h->engine == 2 && h->persist == 1);
+        h->pending_bwd = h->persist == 1;
         return RNDE_OK;
     }
     HIPCHK(h, hipMemcpyAsync(h->h_scal, b.tspan_out, 8, hipMemcpyDeviceToHost, s));
-    if (h->engine == 2) persist_check_enqueue(h, h->sR * (Q.F.Bpad / 16), s);
+    persist_check_enqueue(h, h->sR * (Q.F.Bpad / 16), s);
     HIPCHK(h, hipStreamSynchronize(s));
     if (h->couple && rnde_comm_health(h->couple) != RNDE_OK) { h->err = std::string("coupled controller: ") + rnde_comm_last_error(h->couple); return RNDE_ERR_HIP; }
     if (tspan_bar_host) { tspan_bar_host[0] = h->h_scal[0]; tspan_bar_host[1] = h->h_scal[1]; }
     h->have_tape = false;  // z2bar overwrote k_s in place: the tape is consumed
-    if (h->engine == 2 && persist_check_result(h, Q.F.Bpad / 16, h->sR, s)) {
+    if (persist_check_result(h, Q.F.Bpad / 16, h->sR, s)) {
         h->err = "persistent reverse kernel abandoned its hand-off (tape consumed): rerun forward + backward, the multi-launch kernels are now in use";
         return RNDE_ERR_HIP;
     }
@@ -561,8 +513,7 @@ extern "C" rnde_status rnde_node_classifier_grad(rnde_node* h, const float* x_de
 
 // ---- chain engine reverse pass ----------------------------------------------------------------------------
 template <int NKD, int ALT = 0>
-static hipError_t launch_bchain_t(rnde_node* h, const BChainParams& Q, const std::vector<int>& sv_lo, const std::vector<int>& sv_hi, hipStream_t s) {
-    const BwdBuffers& b = h->bw;
+static hipError_t launch_bchain_t(rnde_node* h, const BChainParams& Q, const SaveRange* rng, hipStream_t s) {
     const size_t lds = h->chain_lds_b;
     static DeviceOnce attr_set;
     if (attr_set.need()) {
@@ -574,18 +525,10 @@ static hipError_t launch_bchain_t(rnde_node* h, const BChainParams& Q, const std
     }
     const dim3 grid(Q.B.F.nwg), blk(64 * kCW);
     for (int n = Q.B.n_att - 1; n >= 0; --n) {
-        float c1 = 0.f, c2 = 0.f;   // cotangent of eigen_est for this attempt (as in bwd_run)
+        float c1 = 0.f, c2 = 0.f;   // cotangent of eigen_est for this attempt
         const StepMeta& mm = h->h_meta[n];
-        const bool eg_ok = !(mm.eigen == 0.f || mm.eigen != mm.eigen);
-        double eigb = 0.0;
-        if (h->cfg.regularize == RNDE_REG_STIFF && eg_ok) eigb = (double)b.h_svb[n] * (mm.eigen > 0 ? 1.0 : -1.0) / 3.5068;
-        if (h->cfg.regularize == RNDE_REG_ERR_STIFF && eg_ok) eigb = 0.1 * (double)b.h_svb[n] / 3.5068;
-        if (h->cfg.regularize == RNDE_REG_STIFF_DT && eg_ok) eigb = (double)b.h_svb[n] * ((double)mm.eigen * (double)mm.dt > 0 ? 1.0 : -1.0) * (double)mm.dt;      // |eigen_est * dt| (test/test_node.jl:75)
-        if (eigb != 0.0 && mm.n1 > 0.f && mm.n2 > 0.f) {
-            c1 = (float)(eigb / ((double)mm.n2 * (double)mm.n1));
-            c2 = (float)(-eigb * ((double)mm.n1 / (double)mm.n2) / ((double)mm.n2 * (double)mm.n2));
-        }
-        hipLaunchKernelGGL((rnde_bchain_kernel<NKD, ALT>), grid, blk, lds, s, Q, n, mm, sv_lo[n], sv_hi[n], c1, c2);
+        eig_cotangent(h->cfg.regularize, h->bw.h_svb[n], mm, &c1, &c2);
+        hipLaunchKernelGGL((rnde_bchain_kernel<NKD, ALT>), grid, blk, lds, s, Q, n, mm, rng[n].lo, rng[n].hi, c1, c2);
     }
     hipLaunchKernelGGL((rnde_bchain_init_kernel<NKD, 1, ALT>), grid, blk, lds, s, Q);
     hipLaunchKernelGGL((rnde_bchain_init_kernel<NKD, 2, ALT>), grid, blk, lds, s, Q);
@@ -596,7 +539,7 @@ static hipError_t launch_bchain_t(rnde_node* h, const BChainParams& Q, const std
 
 // ---- chain engine, multi-wave kernels: reverse pass (rnde_bchainmw.h) ------------------------------------------------------
 template <int NR, int TAB, int LAT = 0>
-static rnde_status launch_bmw_t(rnde_node* h, const BMwParams& Q, const std::vector<int>& sv_lo, const std::vector<int>& sv_hi, hipStream_t s) {
+static rnde_status launch_bmw_t(rnde_node* h, const BMwParams& Q, const SaveRange* rng, hipStream_t s) {
     const BwdBuffers& b = h->bw;
     const size_t lds = h->mw_lds_b;
     static DeviceOnce attr_set;
@@ -615,19 +558,11 @@ static rnde_status launch_bmw_t(rnde_node* h, const BMwParams& Q, const std::vec
     const bool sweep = h->mw_bsweep > 0 && !h->couple && Q.ntiles <= kMwMeetMax && Q.B.n_att >= 2 && h->mw_meet.xch;
     int* a_lo = h->h_mw_bargs; int* a_hi = a_lo + h->cfg.max_attempts; float* a_eig = (float*)(a_hi + h->cfg.max_attempts);
     for (int n = Q.B.n_att - 1; n >= 0; --n) {
-        float c1 = 0.f, c2 = 0.f;   // cotangent of eigen_est for this attempt (as in bwd_run)
+        float c1 = 0.f, c2 = 0.f;   // cotangent of eigen_est for this attempt
         const StepMeta& mm = h->h_meta[n];
-        const bool eg_ok = !(mm.eigen == 0.f || mm.eigen != mm.eigen);
-        double eigb = 0.0;
-        if (h->cfg.regularize == RNDE_REG_STIFF && eg_ok) eigb = (double)b.h_svb[n] * (mm.eigen > 0 ? 1.0 : -1.0) / 3.5068;
-        if (h->cfg.regularize == RNDE_REG_ERR_STIFF && eg_ok) eigb = 0.1 * (double)b.h_svb[n] / 3.5068;
-        if (h->cfg.regularize == RNDE_REG_STIFF_DT && eg_ok) eigb = (double)b.h_svb[n] * ((double)mm.eigen * (double)mm.dt > 0 ? 1.0 : -1.0) * (double)mm.dt;      // |eigen_est * dt| (test/test_node.jl:75)
-        if (eigb != 0.0 && mm.n1 > 0.f && mm.n2 > 0.f) {
-            c1 = (float)(eigb / ((double)mm.n2 * (double)mm.n1));
-            c2 = (float)(-eigb * ((double)mm.n1 / (double)mm.n2) / ((double)mm.n2 * (double)mm.n2));
-        }
-        if (sweep) { a_lo[n] = sv_lo[n]; a_hi[n] = sv_hi[n]; a_eig[2 * n] = c1; a_eig[2 * n + 1] = c2; continue; }
-        hipLaunchKernelGGL((rnde_bchainmw_kernel<NR, TAB, LAT>), grid, blk, lds, s, Q, n, mm, sv_lo[n], sv_hi[n], c1, c2);
+        eig_cotangent(h->cfg.regularize, b.h_svb[n], mm, &c1, &c2);
+        if (sweep) { a_lo[n] = rng[n].lo; a_hi[n] = rng[n].hi; a_eig[2 * n] = c1; a_eig[2 * n + 1] = c2; continue; }
+        hipLaunchKernelGGL((rnde_bchainmw_kernel<NR, TAB, LAT>), grid, blk, lds, s, Q, n, mm, rng[n].lo, rng[n].hi, c1, c2);
         // (coupled controller, SURVEY 8e mode 2: the S, tau, c-tau partials of attempt n summed over the ranks before attempt n - 1 reads them)
         if ((st = couple_sum(h, b.bpart + (size_t)(n & 1) * Q.B.bpart_n * 4, 4LL * Q.B.bpart_n, s)) != RNDE_OK) return st;
     }
@@ -653,91 +588,46 @@ static rnde_status launch_bmw_t(rnde_node* h, const BMwParams& Q, const std::vec
     return RNDE_OK;
 }
 
-static rnde_status chain_mw_bwd_run(rnde_node* h, const float* u_bar_dev, const float* saveval_bar_host, float* x_bar_dev,
-                                    float* p_bar_dev, float* tspan_bar_host, hipStream_t s, bool sync, float* tspan_bar_dev) {
+// ---- what the two chain run functions share ----------------------------------------------------------------------------------------------
+static const float kTsit5C[7] = {tsC(0), tsC(1), tsC(2), tsC(3), tsC(4), tsC(5), tsC(6)};      // nodes of the constant-folded pair, as RkTab::c holds a table's
+
+// the buffers of a chain handle's reverse pass, allocated once; E: evaluations per attempted step (6; S - 1 for an S-stage table)
+static rnde_status chain_bwd_prepare(rnde_node* h, int E) {
     BwdBuffers& b = h->bw;
-    const ChainGeo& G = h->cg;
+    if (b.ready) return RNDE_OK;
     const int cap = h->cfg.max_attempts, ntiles_max = h->Bpad_max / 16;
-    const int E = h->rk_S - 1;      // evaluations per attempted step (6; S - 1 for an S-stage table)
-    if (!b.ready) {
-        const size_t Ac = (size_t)ntiles_max * h->NKD * 64;
-        HIPCHK(h, b.U.reserve(Ac)); HIPCHK(h, b.K1.reserve(Ac)); HIPCHK(h, b.UB1.reserve(Ac));
-        HIPCHK(h, b.svb_att.reserve((size_t)cap));
-        HIPCHK(h, b.bstate_mem.reserve(2 * sizeof(BState))); b.bstate = (BState*)b.bstate_mem.get(); HIPCHK(h, b.ibstate.reserve(2));
-        HIPCHK(h, b.bpart.reserve((size_t)(2 * h->nwg_max + 256) * 4)); HIPCHK(h, b.ipart.reserve((size_t)2 * h->nwg_max * 4));   // (+256 entries: finish_attempt_scalars reads whole 256-entry blocks)
-        HIPCHK(h, b.tspan_out.reserve(2));
-        HIPCHK(h, b.h_svb.reserve((size_t)cap));
-        HIPCHK(h, b.slab.reserve((size_t)96 * h->P)); HIPCHK(h, b.slab_r.reserve((size_t)16 * h->P));
-        HIPCHK(h, h->ev_t.reserve((size_t)E * cap + 2)); HIPCHK(h, h->h_ev_t.reserve((size_t)E * cap + 2));
-        b.ready = true;
-    }
-    const int n_att = h->n_att, n_evals = E * n_att + 2;
-    if (!h->mw_slab || h->mw_slab_evals < n_evals) { h->err = "activation slab missing: the forward was not taped on the multi-wave kernels"; return RNDE_ERR_NO_TAPE; }
-    // (coupled controller: every rank passes the cotangent of its own loss; the shared scalars carry `world` times it -- as in bwd_run)
-    const float svb_scale = h->couple ? (float)h->couple_world : 1.f;
-    for (int i = 0; i < n_att; ++i)
-        b.h_svb[i] = (saveval_bar_host && h->sv_index[i] >= 0) ? svb_scale * saveval_bar_host[h->sv_index[i]] : 0.f;
-    HIPCHK(h, hipMemcpyAsync(b.svb_att, b.h_svb, (size_t)std::max(1, n_att) * 4, hipMemcpyHostToDevice, s));
-    BMwParams Q{};
-    Q.B.F = make_params(h, h->xcopy, h->B, h->t0, h->t1, 1);
-    Q.B.U = b.U; Q.B.K1 = b.K1; Q.B.UB1 = b.UB1; Q.B.svb_att = b.svb_att;
-    Q.B.bstate = b.bstate; Q.B.ibstate = b.ibstate; Q.B.bpart = b.bpart; Q.B.ipart = b.ipart;
-    Q.B.ubar = u_bar_dev; Q.B.xbar = x_bar_dev; Q.B.tspan_out = b.tspan_out;
-    Q.B.n_att = n_att; Q.B.track_ctrl = h->cfg.track_ctrl; Q.B.track_initdt = h->cfg.track_initdt; Q.B.reg_kind = h->cfg.regularize;
-    Q.B.bpart_n = Q.B.F.nwg;
-    Q.B.tspan_scale = h->couple ? 1.f / (float)h->couple_world : 1.f;
-    Q.B.sv_T = (int)h->saveat.size();
-    Q.B.sv_ubar0 = (!h->saveat.empty() && h->saveat[0] == h->t0) ? u_bar_dev : nullptr;
-    Q.G = h->mg; Q.rk = h->rk; Q.tab = h->mw_tab; Q.ntiles = Q.B.F.Bpad / 16;
-    Q.slab = h->mw_slab; Q.ev_stride = (long long)Q.ntiles * h->mg.RS * 64;
-    Q.sv_t = h->saveat.empty() ? nullptr : h->sv_t_dev; Q.sv_ubar = u_bar_dev; Q.nsave = (int)h->saveat.size();
-    // evaluation times in slab order (0: f(u0,t0), 1: f(u1,t0+dt0), 2 + 6n + (s-1): stage s of attempt n), save indices per accepted attempt
-    std::vector<int> sv_lo(std::max(1, n_att), 0), sv_hi(std::max(1, n_att), 0);
-    {
-        int ns = (!h->saveat.empty() && h->saveat[0] == h->t0) ? 1 : 0;
-        h->h_ev_t[0] = h->t0; h->h_ev_t[1] = h->t0 + h->h_init->dt0;
-        for (int n = 0; n < n_att; ++n) {
-            const StepMeta& m = h->h_meta[n];
-            for (int sidx = 2; sidx <= h->rk_S; ++sidx) h->h_ev_t[2 + E * n + sidx - 2] = m.t + (h->rk_tab ? h->rk.c[sidx - 1] : tsC(sidx - 1)) * m.dt;
-            sv_lo[n] = ns;
-            if (m.flags & F_ACCEPT) {
-                const float tnew = m.t + m.dt;
-                while (ns < (int)h->saveat.size() && h->saveat[ns] <= tnew) ++ns;
-            }
-            sv_hi[n] = ns;
-        }
-    }
-    HIPCHK(h, hipMemcpyAsync(h->ev_t, h->h_ev_t, (size_t)n_evals * 4, hipMemcpyHostToDevice, s));
-    rnde_status e;
-    if (h->chain_ga) {     // (any served activation: the LAT = 2 kernels)
-        if (h->rk_tab == 2) e = h->NKD == 4 ? launch_bmw_t<1, 2, 2>(h, Q, sv_lo, sv_hi, s) : (h->NKD == 8 ? launch_bmw_t<2, 2, 2>(h, Q, sv_lo, sv_hi, s) : launch_bmw_t<4, 2, 2>(h, Q, sv_lo, sv_hi, s));
-        else if (h->rk_tab) e = h->NKD == 4 ? launch_bmw_t<1, 1, 2>(h, Q, sv_lo, sv_hi, s) : (h->NKD == 8 ? launch_bmw_t<2, 1, 2>(h, Q, sv_lo, sv_hi, s) : launch_bmw_t<4, 1, 2>(h, Q, sv_lo, sv_hi, s));
-        else e = h->NKD == 4 ? launch_bmw_t<1, 0, 2>(h, Q, sv_lo, sv_hi, s) : (h->NKD == 8 ? launch_bmw_t<2, 0, 2>(h, Q, sv_lo, sv_hi, s) : launch_bmw_t<4, 0, 2>(h, Q, sv_lo, sv_hi, s));
-    } else if (h->rk_tab == 2) e = h->NKD == 4 ? launch_bmw_t<1, 2>(h, Q, sv_lo, sv_hi, s) : (h->NKD == 8 ? launch_bmw_t<2, 2>(h, Q, sv_lo, sv_hi, s) : launch_bmw_t<4, 2>(h, Q, sv_lo, sv_hi, s));
-    else if (h->mw_lat) e = h->rk_tab ? launch_bmw_t<2, 1, 1>(h, Q, sv_lo, sv_hi, s) : launch_bmw_t<2, 0, 1>(h, Q, sv_lo, sv_hi, s);   // latent-ODE shape: transposed weights register stationary
-    else if (h->rk_tab) e = h->NKD == 4 ? launch_bmw_t<1, 1>(h, Q, sv_lo, sv_hi, s) : (h->NKD == 8 ? launch_bmw_t<2, 1>(h, Q, sv_lo, sv_hi, s) : launch_bmw_t<4, 1>(h, Q, sv_lo, sv_hi, s));
-    else e = h->NKD == 4 ? launch_bmw_t<1, 0>(h, Q, sv_lo, sv_hi, s) : (h->NKD == 8 ? launch_bmw_t<2, 0>(h, Q, sv_lo, sv_hi, s) : launch_bmw_t<4, 0>(h, Q, sv_lo, sv_hi, s));
-    if (e != RNDE_OK) return e;
-    // parameter gradients of all layers over all evaluations: the one-wave engine's kernel on the same slab format
-    BChainParams W{};
-    W.G = G; W.ntiles = Q.ntiles; W.slab = h->mw_slab; W.ev_stride = Q.ev_stride; W.RS = h->mg.RS;
-    for (int l = 0; l <= G.n_layers; ++l) { W.hrow[l] = h->mg.hrow[l]; if (l < G.n_layers) W.zrow[l] = h->mg.zrow[l]; }
-    const int n_units = n_evals * Q.ntiles;
+    const size_t Ac = (size_t)ntiles_max * h->NKD * 64;
+    HIPCHK(h, b.U.reserve(Ac)); HIPCHK(h, b.K1.reserve(Ac)); HIPCHK(h, b.UB1.reserve(Ac));
+    HIPCHK(h, b.svb_att.reserve((size_t)cap));
+    HIPCHK(h, b.bstate_mem.reserve(2 * sizeof(BState))); b.bstate = (BState*)b.bstate_mem.get(); HIPCHK(h, b.ibstate.reserve(2));
+    HIPCHK(h, b.bpart.reserve((size_t)(2 * h->nwg_max + 256) * 4)); HIPCHK(h, b.ipart.reserve((size_t)2 * h->nwg_max * 4));   // (+256 entries: finish_attempt_scalars reads whole 256-entry blocks)
+    HIPCHK(h, b.tspan_out.reserve(2));
+    HIPCHK(h, b.h_svb.reserve((size_t)cap));
+    HIPCHK(h, b.slab.reserve((size_t)96 * h->P)); HIPCHK(h, b.slab_r.reserve((size_t)16 * h->P));
+    HIPCHK(h, h->ev_t.reserve((size_t)E * cap + 2)); HIPCHK(h, h->h_ev_t.reserve((size_t)E * cap + 2));
+    b.ready = true;
+    return RNDE_OK;
+}
+// what a chain sweep reads from the host, sent ahead of it: the saved-value cotangent per attempt and the evaluation times (rnde_rev_plan.h)
+static rnde_status chain_bwd_inputs(rnde_node* h, const float* saveval_bar_host, int E, const float* nodes, bool init_first, hipStream_t s) {
+    BwdBuffers& b = h->bw;
+    gather_saveval_bar(h, saveval_bar_host);
+    HIPCHK(h, hipMemcpyAsync(b.svb_att, b.h_svb, (size_t)std::max(1, h->n_att) * 4, hipMemcpyHostToDevice, s));
+    eval_times(h->h_meta, h->n_att, E, nodes, h->t0, h->h_init->dt0, init_first, h->h_ev_t);
+    HIPCHK(h, hipMemcpyAsync(h->ev_t, h->h_ev_t, (size_t)(E * h->n_att + 2) * 4, hipMemcpyHostToDevice, s));
+    return RNDE_OK;
+}
+// behind the sweep: the parameter gradients of all layers over all evaluations (W: the slab as rnde_chain_wgrad_kernel reads it) and their
+// fixed-order reduction; then tspan-bar to the device (async) or, behind a synchronisation, to the host.  The tape is consumed either way.
+static rnde_status chain_bwd_finish(rnde_node* h, const BChainParams& W, int n_evals, float* p_bar_dev, float* tspan_bar_host, hipStream_t s, bool sync,
+                                    float* tspan_bar_dev) {
+    BwdBuffers& b = h->bw;
+    const int n_units = n_evals * W.ntiles;
     const int chunks = std::max(1, std::min(96, n_units / 8));
     const int per_chunk = (n_units + chunks - 1) / chunks;
-    hipLaunchKernelGGL(rnde_chain_wgrad_kernel, dim3(G.n_layers, chunks), dim3(64 * kCW), 0, s, W, (const float*)h->ev_t, n_units, per_chunk, b.slab, h->P);
+    hipLaunchKernelGGL(rnde_chain_wgrad_kernel, dim3(W.G.n_layers, chunks), dim3(64 * kCW), 0, s, W, (const float*)h->ev_t, n_units, per_chunk, b.slab, h->P);
     HIPCHK(h, hipGetLastError());
-    {
-        const long long len = h->P;
-        const int grid = (int)std::min<long long>((len + 255) / 256, 2048);
-        if (chunks <= 16) hipLaunchKernelGGL(rnde_wgrad_reduce, dim3(grid, 1), dim3(256), 0, s, (const float*)b.slab, chunks, chunks, len, p_bar_dev);
-        else {
-            const int per_group = (chunks + 15) / 16, groups = (chunks + per_group - 1) / per_group;
-            hipLaunchKernelGGL(rnde_wgrad_reduce, dim3(grid, groups), dim3(256), 0, s, (const float*)b.slab, chunks, per_group, len, b.slab_r);
-            hipLaunchKernelGGL(rnde_wgrad_reduce, dim3(grid, 1), dim3(256), 0, s, (const float*)b.slab_r, groups, groups, len, p_bar_dev);
-        }
-        HIPCHK(h, hipGetLastError());
-    }
+    HIPCHK(h, launch_wgrad_reduce(b.slab, chunks, h->P, b.slab_r, p_bar_dev, s));
     h->have_tape = false;
     if (!sync) {
         if (tspan_bar_dev) HIPCHK(h, hipMemcpyAsync(tspan_bar_dev, b.tspan_out, 8, hipMemcpyDeviceToDevice, s));
@@ -745,45 +635,51 @@ static rnde_status chain_mw_bwd_run(rnde_node* h, const float* u_bar_dev, const 
     }
     HIPCHK(h, hipMemcpyAsync(h->h_scal, b.tspan_out, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
-    if (bsweep_failed(h, s))     // nothing the sweep reads was consumed: the same reverse pass again, one launch per attempt
-        return chain_mw_bwd_run(h, u_bar_dev, saveval_bar_host, x_bar_dev, p_bar_dev, tspan_bar_host, s, sync, tspan_bar_dev);
     if (tspan_bar_host) { tspan_bar_host[0] = h->h_scal[0]; tspan_bar_host[1] = h->h_scal[1]; }
     return RNDE_OK;
+}
+
+static rnde_status chain_mw_bwd_run(rnde_node* h, const float* u_bar_dev, const float* saveval_bar_host, float* x_bar_dev,
+                                    float* p_bar_dev, float* tspan_bar_host, hipStream_t s, bool sync, float* tspan_bar_dev) {
+    const ChainGeo& G = h->cg;
+    const int E = h->rk_S - 1;      // evaluations per attempted step (6; S - 1 for an S-stage table)
+    rnde_status st = chain_bwd_prepare(h, E);
+    if (st != RNDE_OK) return st;
+    const int n_evals = E * h->n_att + 2;
+    if (!h->mw_slab || h->mw_slab_evals < n_evals) { h->err = "activation slab missing: the forward was not taped on the multi-wave kernels"; return RNDE_ERR_NO_TAPE; }
+    // evaluation times in slab order: 0: f(u0,t0), 1: f(u1,t0+dt0), 2 + E n + (s-2): stage s of attempt n
+    if ((st = chain_bwd_inputs(h, saveval_bar_host, E, h->rk_tab ? h->rk.c : kTsit5C, true, s)) != RNDE_OK) return st;
+    BMwParams Q{};
+    Q.B = fill_bwd_params(h, u_bar_dev, x_bar_dev);
+    Q.G = h->mg; Q.rk = h->rk; Q.tab = h->mw_tab; Q.ntiles = Q.B.F.Bpad / 16;
+    Q.slab = h->mw_slab; Q.ev_stride = (long long)Q.ntiles * h->mg.RS * 64;
+    Q.sv_t = h->saveat.empty() ? nullptr : h->sv_t_dev; Q.sv_ubar = u_bar_dev; Q.nsave = (int)h->saveat.size();
+    const std::vector<SaveRange> rng = save_ranges(h);
+    st = mw_variant(h, [&](auto nr, auto tab, auto lat) { return launch_bmw_t<nr(), tab(), lat()>(h, Q, rng.data(), s); });
+    if (st != RNDE_OK) return st;
+    // parameter gradients of all layers over all evaluations: the one-wave engine's kernel on the same slab format
+    BChainParams W{};
+    W.G = G; W.ntiles = Q.ntiles; W.slab = h->mw_slab; W.ev_stride = Q.ev_stride; W.RS = h->mg.RS;
+    for (int l = 0; l <= G.n_layers; ++l) { W.hrow[l] = h->mg.hrow[l]; if (l < G.n_layers) W.zrow[l] = h->mg.zrow[l]; }
+    st = chain_bwd_finish(h, W, n_evals, p_bar_dev, tspan_bar_host, s, sync, tspan_bar_dev);
+    if (st == RNDE_OK && sync && bsweep_failed(h, s))     // nothing the sweep reads was consumed: the same reverse pass again, one launch per attempt
+        return chain_mw_bwd_run(h, u_bar_dev, saveval_bar_host, x_bar_dev, p_bar_dev, tspan_bar_host, s, sync, tspan_bar_dev);
+    return st;
 }
 
 static rnde_status chain_bwd_run(rnde_node* h, const float* u_bar_dev, const float* saveval_bar_host, float* x_bar_dev,
                                  float* p_bar_dev, float* tspan_bar_host, hipStream_t s, bool sync, float* tspan_bar_dev) {
     if (h->mw) { HIPCHK(h, hipSetDevice(h->cfg.device)); return chain_mw_bwd_run(h, u_bar_dev, saveval_bar_host, x_bar_dev, p_bar_dev, tspan_bar_host, s, sync, tspan_bar_dev); }
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    BwdBuffers& b = h->bw;
     const ChainGeo& G = h->cg;
-    const int cap = h->cfg.max_attempts, ntiles_max = h->Bpad_max / 16;
-    if (!b.ready) {
-        const size_t Ac = (size_t)ntiles_max * h->NKD * 64;
-        HIPCHK(h, b.U.reserve(Ac)); HIPCHK(h, b.K1.reserve(Ac)); HIPCHK(h, b.UB1.reserve(Ac));
-        HIPCHK(h, b.svb_att.reserve((size_t)cap));
-        HIPCHK(h, b.bstate_mem.reserve(2 * sizeof(BState))); b.bstate = (BState*)b.bstate_mem.get(); HIPCHK(h, b.ibstate.reserve(2));
-        HIPCHK(h, b.bpart.reserve((size_t)(2 * h->nwg_max + 256) * 4)); HIPCHK(h, b.ipart.reserve((size_t)2 * h->nwg_max * 4));   // (+256 entries: finish_attempt_scalars reads whole 256-entry blocks)
-        HIPCHK(h, b.tspan_out.reserve(2));
-        HIPCHK(h, b.h_svb.reserve((size_t)cap));
-        HIPCHK(h, b.slab.reserve((size_t)96 * h->P)); HIPCHK(h, b.slab_r.reserve((size_t)16 * h->P));
-        HIPCHK(h, h->ev_t.reserve((size_t)6 * cap + 2)); HIPCHK(h, h->h_ev_t.reserve((size_t)6 * cap + 2));
-        b.ready = true;
-    }
-    const int n_att = h->n_att, n_evals = 6 * n_att + 2;
-    for (int i = 0; i < n_att; ++i)
-        b.h_svb[i] = (saveval_bar_host && h->sv_index[i] >= 0) ? saveval_bar_host[h->sv_index[i]] : 0.f;
-    HIPCHK(h, hipMemcpyAsync(b.svb_att, b.h_svb, (size_t)std::max(1, n_att) * 4, hipMemcpyHostToDevice, s));
+    const int E = 6;      // evaluations per attempted step
+    rnde_status st = chain_bwd_prepare(h, E);
+    if (st != RNDE_OK) return st;
+    const int n_evals = E * h->n_att + 2;
+    // evaluation times in slab order: E n + (s-2): stage s of attempt n; then f(u0,t0), f(u1,t0+dt0)
+    if ((st = chain_bwd_inputs(h, saveval_bar_host, E, kTsit5C, false, s)) != RNDE_OK) return st;
     BChainParams Q{};
-    Q.B.F = make_params(h, h->xcopy, h->B, h->t0, h->t1, 1);
-    Q.B.U = b.U; Q.B.K1 = b.K1; Q.B.UB1 = b.UB1; Q.B.svb_att = b.svb_att;
-    Q.B.bstate = b.bstate; Q.B.ibstate = b.ibstate; Q.B.bpart = b.bpart; Q.B.ipart = b.ipart;
-    Q.B.ubar = u_bar_dev; Q.B.xbar = x_bar_dev; Q.B.tspan_out = b.tspan_out;
-    Q.B.n_att = n_att; Q.B.track_ctrl = h->cfg.track_ctrl; Q.B.track_initdt = h->cfg.track_initdt; Q.B.reg_kind = h->cfg.regularize;
-    Q.B.bpart_n = Q.B.F.nwg;
-    Q.B.tspan_scale = h->couple ? 1.f / (float)h->couple_world : 1.f;
-    Q.B.sv_T = (int)h->saveat.size();
-    Q.B.sv_ubar0 = (!h->saveat.empty() && h->saveat[0] == h->t0) ? u_bar_dev : nullptr;
+    Q.B = fill_bwd_params(h, u_bar_dev, x_bar_dev);
     Q.G = G; Q.frags = h->cfrags; Q.ntiles = Q.B.F.Bpad / 16;
     int row = 0;
     auto pad4 = [](int k) { return 4 * ((k + 3) / 4); };
@@ -795,60 +691,10 @@ static rnde_status chain_bwd_run(rnde_node* h, const float* u_bar_dev, const flo
     if (h->cslab.cap() < need && h->cslab.reserve(need + need / 2) != hipSuccess)      // (head room: a step count that creeps up while a model trains must not free + allocate every step)
         HIPCHK(h, h->cslab.reserve(need));
     Q.slab = h->cslab;
-    // evaluation times (time column of TDChain layers) and the save indices each accepted attempt covers
-    std::vector<int> sv_lo(std::max(1, n_att), 0), sv_hi(std::max(1, n_att), 0);
-    {
-        int ns = (!h->saveat.empty() && h->saveat[0] == h->t0) ? 1 : 0;
-        for (int n = 0; n < n_att; ++n) {
-            const StepMeta& m = h->h_meta[n];
-            for (int sidx = 2; sidx <= 7; ++sidx) h->h_ev_t[6 * n + sidx - 2] = m.t + tsC(sidx - 1) * m.dt;
-            sv_lo[n] = ns;
-            if (m.flags & F_ACCEPT) {
-                const float tnew = m.t + m.dt;
-                while (ns < (int)h->saveat.size() && h->saveat[ns] <= tnew) ++ns;
-            }
-            sv_hi[n] = ns;
-        }
-        h->h_ev_t[6 * n_att] = h->t0; h->h_ev_t[6 * n_att + 1] = h->t0 + h->h_init->dt0;
-    }
-    HIPCHK(h, hipMemcpyAsync(h->ev_t, h->h_ev_t, (size_t)n_evals * 4, hipMemcpyHostToDevice, s));
-    hipError_t e;
-    if (h->chain_ga) switch (h->NKD) {     // (any served activation: the ALT = 2 kernels)
-        case 4: e = launch_bchain_t<4, 2>(h, Q, sv_lo, sv_hi, s); break;
-        case 8: e = launch_bchain_t<8, 2>(h, Q, sv_lo, sv_hi, s); break;
-        default: e = launch_bchain_t<16, 2>(h, Q, sv_lo, sv_hi, s); break;
-    } else switch (h->NKD) {
-        case 4: e = launch_bchain_t<4>(h, Q, sv_lo, sv_hi, s); break;
-        case 8: e = h->chain_alt ? launch_bchain_t<8, 1>(h, Q, sv_lo, sv_hi, s) : launch_bchain_t<8>(h, Q, sv_lo, sv_hi, s); break;
-        default: e = launch_bchain_t<16>(h, Q, sv_lo, sv_hi, s); break;
-    }
+    const std::vector<SaveRange> rng = save_ranges(h);
+    const hipError_t e = chain_variant(h, [&](auto nkd, auto alt) { return launch_bchain_t<nkd(), alt()>(h, Q, rng.data(), s); });
     HIPCHK(h, e);
-    // parameter gradients of all layers over all evaluations
-    const int n_units = n_evals * Q.ntiles;
-    const int chunks = std::max(1, std::min(96, n_units / 8));
-    const int per_chunk = (n_units + chunks - 1) / chunks;
-    hipLaunchKernelGGL(rnde_chain_wgrad_kernel, dim3(G.n_layers, chunks), dim3(64 * kCW), 0, s, Q, (const float*)h->ev_t, n_units, per_chunk, b.slab, h->P);
-    HIPCHK(h, hipGetLastError());
-    {
-        const long long len = h->P;
-        const int grid = (int)std::min<long long>((len + 255) / 256, 2048);
-        if (chunks <= 16) hipLaunchKernelGGL(rnde_wgrad_reduce, dim3(grid, 1), dim3(256), 0, s, (const float*)b.slab, chunks, chunks, len, p_bar_dev);
-        else {
-            const int per_group = (chunks + 15) / 16, groups = (chunks + per_group - 1) / per_group;
-            hipLaunchKernelGGL(rnde_wgrad_reduce, dim3(grid, groups), dim3(256), 0, s, (const float*)b.slab, chunks, per_group, len, b.slab_r);
-            hipLaunchKernelGGL(rnde_wgrad_reduce, dim3(grid, 1), dim3(256), 0, s, (const float*)b.slab_r, groups, groups, len, p_bar_dev);
-        }
-        HIPCHK(h, hipGetLastError());
-    }
-    h->have_tape = false;
-    if (!sync) {
-        if (tspan_bar_dev) HIPCHK(h, hipMemcpyAsync(tspan_bar_dev, b.tspan_out, 8, hipMemcpyDeviceToDevice, s));
-        return RNDE_OK;
-    }
-    HIPCHK(h, hipMemcpyAsync(h->h_scal, b.tspan_out, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    if (tspan_bar_host) { tspan_bar_host[0] = h->h_scal[0]; tspan_bar_host[1] = h->h_scal[1]; }
-    return RNDE_OK;
+    return chain_bwd_finish(h, Q, n_evals, p_bar_dev, tspan_bar_host, s, sync, tspan_bar_dev);
 }
 
 extern "C" rnde_status rnde_adam_step(float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t len, int64_t t, float eta, float beta1,

@@ -578,17 +578,7 @@ static rnde_status nsde_backward_impl(rnde_nsde* h, const float* u_bar_dev, cons
     hipLaunchKernelGGL(rnde_chain_wgrad_kernel, dim3(h->Gf.n_layers, chunks), dim3(64 * kCW), 0, s, Bq.Cf, (const float*)h->ev_t, n_units, per_chunk, h->wslab, h->P);
     hipLaunchKernelGGL(rnde_chain_wgrad_kernel, dim3(h->Gg.n_layers, chunks), dim3(64 * kCW), 0, s, Bq.Cg, (const float*)h->ev_t, n_units, per_chunk, h->wslab + h->Pf, h->P);
     SCHK(h, hipGetLastError());
-    {
-        const long long len = h->P;
-        const int grid = (int)std::min<long long>((len + 255) / 256, 2048);
-        if (chunks <= 16) hipLaunchKernelGGL(rnde_wgrad_reduce, dim3(grid, 1), dim3(256), 0, s, (const float*)h->wslab, chunks, chunks, len, p_bar_dev);
-        else {
-            const int per_group = (chunks + 15) / 16, groups = (chunks + per_group - 1) / per_group;
-            hipLaunchKernelGGL(rnde_wgrad_reduce, dim3(grid, groups), dim3(256), 0, s, (const float*)h->wslab, chunks, per_group, len, h->wslab_r);
-            hipLaunchKernelGGL(rnde_wgrad_reduce, dim3(grid, 1), dim3(256), 0, s, (const float*)h->wslab_r, groups, groups, len, p_bar_dev);
-        }
-        SCHK(h, hipGetLastError());
-    }
+    SCHK(h, launch_wgrad_reduce(h->wslab, chunks, h->P, h->wslab_r, p_bar_dev, s));
     if (sync) SCHK(h, hipStreamSynchronize(s));     // (nothing is read back: the synchronising form only makes "returned" mean "finished")
     h->have_tape = false;
     return RNDE_OK;

@@ -66,7 +66,7 @@
 #include "rnde_ffjordt.h"      // the tile layout's constants; rnde_meet.h
 #include "rnde_tile_meet.h"    // tile_meet, tile_place
 #include "rnde_track_rec.h"    // FfStepRec, FfAttRec, the initial-step rule's scalar reverse
-#include "rnde_save_plan.h"    // SaveRange
+#include "rnde_rev_plan.h"    // SaveRange
 
 namespace rnde {
 
