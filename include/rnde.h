@@ -301,6 +301,11 @@ int32_t     rnde_node_launches_per_attempt(const rnde_node* h);
  * rnde_stage_solve_kernel for the MNIST form at <= 512 columns, MW_SOLVE for the Dense-chain and SDE engines) -- the launch that replaces
  * the body of `solve(prob, Tsit5(); ...)`, reference src/models/neural_ode.jl:131-137.  bench.py's roofline bookkeeping and the tests. */
 int32_t     rnde_node_one_launch_solves(const rnde_node* h);
+/* How many launches of this handle took one of the folded forms around the two sweeps, in the order of their switches: counts[0]
+ * RNDE_REDUCE_FOLD (the weight-gradient reduction's two passes as one launch), [1] RNDE_WGRAD_PAIR (both layers' weight-gradient launches behind the
+ * sweep as one), [2] RNDE_X3_PACK_FOLD (the x3 weight split inside the pack launch), [3] RNDE_BINIT_PAIR (launches of rnde_binit_pair_kernel: two per
+ * reverse pass).  For the tests, which must know that the form they compare actually ran. */
+void        rnde_node_tail_folds(const rnde_node* h, int64_t counts[4]);
 /* Which arithmetic unit forms the Dense-layer products of the stage engine -- the f(u, p, t) evaluations inside `solve(prob, Tsit5(); ...)`, reference
  * src/models/neural_ode.jl:131-137 with the dynamics of experiments/mnist_node.jl:41-54, their transposes in the reverse pass and the parameter-gradient GEMMs:
  *   RNDE_MATRIX_F32   (0) the fp32-input MFMA v_mfma_f32_16x16x4_f32 -- on gfx950 an instruction of the VECTOR ALUs (64 FLOP/clk/SIMD, no overlap with

@@ -485,12 +485,22 @@ rnde_status stage_pack_all(rnde_node* h, const float* p_dev, hipStream_t s, cons
     };
     add_copy(h->pcopy, nullptr, (long long)h->P);
     if (x_src) add_copy(h->xcopy, x_src, x_floats);           // the tape's copy of x rides along (was a launch of its own)
+    // matrix mode 1 in effect (x3_pack's condition) and RNDE_X3_PACK_FOLD=1 (read per call; off by default): the split weights ride along too,
+    // transposed pair included, instead of rnde_x3_pack_kernel behind this launch -- byte for byte the same images
+    const bool x3_in = h->x3 && h->x3B && h->x3D && h->persist == 1 && !h->stage_generic && tail_switch("RNDE_X3_PACK_FOLD", false);
+    if (x3_in) {
+        const bool rev = h->x3Bt && h->x3Dt;
+        J.x3 = X3PackDst{{(x3u4*)h->x3B.get(), (x3u4*)h->x3D.get(), rev ? (x3u4*)h->x3Bt.get() : nullptr, rev ? (x3u4*)h->x3Dt.get() : nullptr}};
+        J.MT = h->sMT; J.WT = h->sWT; J.R = h->sR; J.HT = h->sHT;
+        add(nullptr, x3_pack_count(J.x3, J.MT, J.R, J.HT), 4, 0, 0);
+    }
     long long most = 0;
     for (int i = 0; i < n; ++i) most = std::max(most, J.j[i].total);
     const int grid = (int)std::min<long long>((most + 255) / 256, 256);
     hipLaunchKernelGGL(rnde_pack_all_kernel, dim3(grid, n), dim3(256), 0, s, p_dev, J, h->D, h->H);
     HIPCHK(h, hipGetLastError());
     h->rev_packed = true;
+    if (x3_in) { h->x3_fwd = true; h->x3_packed = true; ++h->tail_folds[2]; return RNDE_OK; }      // (what x3_pack records behind its launch)
     return x3_pack(h, p_dev, true, s);
 }
 // The hand-off slabs must read "empty" wherever the persistent kernels have not written in the current tile indexing: at
@@ -1066,6 +1076,7 @@ extern "C" int32_t rnde_node_last_attempts(const rnde_node* h) { return h ? h->n
 extern "C" int32_t rnde_node_fallback_count(const rnde_node* h) { return h ? h->persist_fallbacks : 0; }
 
 extern "C" int32_t rnde_node_one_launch_solves(const rnde_node* h) { return h ? h->one_launch_solves : 0; }
+extern "C" void rnde_node_tail_folds(const rnde_node* h, int64_t counts[4]) { for (int i = 0; i < 4; ++i) counts[i] = h ? (int64_t)h->tail_folds[i] : 0; }
 extern "C" rnde_status rnde_node_set_matrix_mode(rnde_node* h, int32_t mode) {
     if (!h) return RNDE_ERR_BAD_ARG;
     if (mode != RNDE_MATRIX_F32 && mode != RNDE_MATRIX_BF16X3) { h->err = "matrix mode: 0 (fp32-input MFMA) or 1 (bf16x3 on the matrix cores)"; return RNDE_ERR_BAD_ARG; }

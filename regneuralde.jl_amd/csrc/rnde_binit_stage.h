@@ -7,43 +7,81 @@
 // in place of the two column-owner launches (rnde_binit_kernel, 2 x ~32 us on 64 workgroups that stream the weights through L2 and triple that
 // the moment anything else streams beside them).  Same arithmetic per element (rnde_bwd.h: rnde_binit_kernel / f_bwd); the sums over workgroups
 // run over the stage engine's R x C partials instead of the column owner's B / 8 -- a different association of the same terms.
+//
+// STEP 0 -> STEP 1 and STEP 2 -> STEP 3 are separated by nothing but the hand-off of the hbar partials between the R row blocks of a column tile; the sums over
+// ALL workgroups (ipart, and with it the coupled controller's all-reduce) sit behind STEP 1 and behind STEP 3.  rnde_binit_pair_kernel<ACT2, PHASE> runs a pair as
+// one launch, the way rnde_bstage_attempt_kernel runs an attempt's seven: the same grid and (rb, ct) decoding (a column tile's row blocks on one XCD), the partials
+// through the hand-off slabs of rnde_stage_persist.h (slab_put / slab_poll_sum, bounded spins, the abort word), the weights of both phases and the state arrays
+// requested once.  The two steps of a pair are the bodies below (binit_phase_d, binit_phase_ab), which the four stand-alone launches run too: the same
+// instructions on the same values, the partials summed over r = 0 .. R - 1 from zero in both forms, so the same bits.
+//   Which slab buffers (the attempt kernels' invariant, rnde_stage_persist.h: a launch finds buffers 1 and 2 empty and buffer 0 holding some launch's last
+// exchange, which whoever exchanges first empties before buffer 0 is used again): phase 1 exchanges through buffer 1 and every workgroup empties ITS entries of
+// buffer 0 (their readers finished launches ago); phase 2 exchanges through buffer 0 -- emptied a kernel boundary earlier -- and every workgroup empties its
+// entries of buffer 1 (phase 1's exchange: consumed a kernel boundary earlier).  Behind phase 2 buffers 1 and 2 are empty and buffer 0 holds the last exchange:
+// the state every launch starts from.  No wait on a clear anywhere: each is followed by a kernel boundary before the buffer is written again.
 #pragma once
 #include "rnde_bstage.h"
+#include "rnde_stage_persist.h"      // PersistSync, slab_put, slab_poll_sum, slab_clear
 
 namespace rnde {
 
-template <int ACT2, int STEP>
-__global__ __launch_bounds__(64 * kSMaxW) void rnde_binit_stage_kernel(const BStageParams Q) {
+// what a workgroup (row block rb, column tile ct; wg = rb * C + ct in both launch forms) and its lanes are to the two bodies
+struct BinitGeo {
+    int tid, lane, w, rb, ct, wg, col, gcol, T, r0, KZ, KG;
+    bool colok, vec, writer, tile_ok;
+    long long A, HB;
+    size_t co;
+    float *ZL, *GL, *RED;
+};
+__device__ __forceinline__ BinitGeo binit_geo(const BStageParams& Q, float* smem, int rb, int ct) {
+    const StepParams& P = Q.B.F;
+    BinitGeo g;
+    g.KZ = 16 * Q.KHb + 4; g.KG = 16 * Q.WT + 4;
+    g.ZL = smem;                        // [16][KZ]  z1bar (K = hidden), permuted k
+    g.GL = g.ZL + kSCB * g.KZ;          // [16][KG]  this block's rows of z2bar, permuted k
+    g.RED = g.GL + kSCB * g.KG;         // [32]
+    g.tid = threadIdx.x; g.lane = g.tid & 63;
+    g.w = __builtin_amdgcn_readfirstlane(g.tid >> 6);
+    g.rb = rb; g.ct = ct; g.wg = rb * Q.C + ct;
+    g.col = g.lane & 15; g.gcol = ct * kSCB + g.col;
+    g.colok = g.gcol < P.B;
+    g.vec = (P.D & 3) == 0;
+    g.writer = (g.wg == 0 && g.tid == 0);
+    g.T = rb * Q.WT + g.w;
+    g.r0 = 16 * g.T + 4 * (g.lane >> 4);
+    g.tile_ok = g.T < Q.MT;
+    g.A = (long long)P.D * P.Bpad; g.HB = (long long)P.H * P.Bpad;
+    g.co = (size_t)g.gcol * P.D;
+    return g;
+}
+// the slab buffer a paired phase exchanges through, and the one whose entries it empties (header above)
+__device__ __forceinline__ constexpr int binit_pair_buf(int phase) { return phase == 1 ? 1 : 0; }
+__device__ __forceinline__ constexpr int binit_pair_clear(int phase) { return phase == 1 ? 0 : 1; }
+
+// A fragments of phases A + B (W1x^T rows of this wave's row tile): requested by the stand-alone STEP 1 / 3 at their start, by a pair in front of its phase D
+__device__ __forceinline__ void binit_load_wB(const BStageParams& Q, const BinitGeo& g, f32x4 (&wB)[kSMaxHT]) {
+#pragma unroll
+    for (int kb = 0; kb < kSMaxHT; ++kb)
+        if (kb < Q.KHb && g.tile_ok) wB[kb] = Q.pwBt[((size_t)g.T * Q.KHb + kb) * 64 + g.lane];
+}
+
+// ---- STEP 0 (kPhase 1) / STEP 2 (kPhase 2): the phase's scalars, z2bar, phase D.  PAIR: the hbar partials go to the hand-off slab (slab_put) instead of Q.slab.
+// f0v_out: the lane's rows of f0, which phases A + B of kPhase 1 need again.
+template <int ACT2, int kPhase, bool PAIR>
+__device__ __forceinline__ void binit_phase_d(const BStageParams& Q, const PersistSync& Y, const BinitGeo& g, f32x4& f0v_out) {
 #pragma clang fp contract(off)
     const BwdParams& Bq = Q.B;
     const StepParams& P = Bq.F;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int KZ = 16 * Q.KHb + 4, KG = 16 * Q.WT + 4;
-    float* ZL = smem;                    // [16][KZ]  z1bar (K = hidden), permuted k
-    float* GL = ZL + kSCB * KZ;          // [16][KG]  this block's rows of z2bar, permuted k
-    float* RED = GL + kSCB * KG;         // [32]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int rb = blockIdx.x / Q.C, ct = blockIdx.x - rb * Q.C;
-    const int wg = blockIdx.x;
-    const int col = lane & 15, gcol = ct * kSCB + col;
-    const bool colok = gcol < P.B;
-    const bool vec = (P.D & 3) == 0;
-    const bool writer = (blockIdx.x == 0 && tid == 0);
-    const int T = rb * Q.WT + w;
-    const int r0 = 16 * T + 4 * (lane >> 4);
-    const bool tile_ok = T < Q.MT;
-    const long long A = (long long)P.D * P.Bpad, HB = (long long)P.H * P.Bpad;
-    const size_t co = (size_t)gcol * P.D;
+    const int lane = g.lane, w = g.w, rb = g.rb, ct = g.ct, col = g.col, gcol = g.gcol, r0 = g.r0, KG = g.KG;
+    const bool colok = g.colok, vec = g.vec, writer = g.writer, tile_ok = g.tile_ok;
+    const long long A = g.A;
+    const size_t co = g.co;
+    float* GL = g.GL;
     const double N = (double)P.D * (double)P.Bn;
     const InitRec ir = *P.initrec;
     const float dt0 = ir.dt0;
-    constexpr bool kD = (STEP == 0 || STEP == 2);      // the launches that end in phase D
-    constexpr int kPhase = STEP < 2 ? 1 : 2;
-    constexpr int par = STEP < 2 ? 0 : 1;              // slab parity of the phase
-
-    float dot = 0.f, tau = 0.f;
-    if constexpr (kD) {
+    constexpr int par = kPhase == 1 ? 0 : 1;              // slab parity of the phase
+    {
         f32x4 wD[kSMaxW];
 #pragma unroll
         for (int kb = 0; kb < kSMaxW; ++kb)
@@ -59,6 +97,7 @@ __global__ __launch_bounds__(64 * kSMaxW) void rnde_binit_stage_kernel(const BSt
                 K1v = ld4(Bq.K1 + co, r0, P.D, true, vec);
             }
         }
+        f0v_out = f0v;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};                 // z2bar of this lane's four rows
         if constexpr (kPhase == 1) {
             // ---- scalars of phase 1 (rnde_binit_kernel, PHASE == 1), identical in every wave ----
@@ -119,11 +158,12 @@ __global__ __launch_bounds__(64 * kSMaxW) void rnde_binit_stage_kernel(const BSt
                 st_tile(Bq.xbar + co, r0, P.D, colok, false, u0b);      // the direct part of x-bar; STEP 3 adds the part through f0
             }
         }
-        // ---- phase D: hbar partial (and layer-2 time row) of this row block -> slab[par] ----
+        // ---- phase D: hbar partial (and layer-2 time row) of this row block -> slab[par] (PAIR: -> the hand-off slab) ----
 #pragma unroll
         for (int i = 0; i < 4; ++i) GL[col * KG + kperm(16 * w + 4 * (lane >> 4) + i)] = tile_ok ? v[i] : 0.f;
         __syncthreads();
         f32x4* sl = (f32x4*)Q.slab + ((((size_t)par * Q.C + ct) * Q.R + rb) * Q.HT) * 64;
+        const size_t tile0 = (((size_t)binit_pair_buf(kPhase) * Q.C + ct) * Q.R + rb) * Q.HT;
         const float* gbp = GL + col * KG + 4 * (lane >> 4);
         f32x4 bg[kSMaxW];
 #pragma unroll
@@ -139,7 +179,8 @@ __global__ __launch_bounds__(64 * kSMaxW) void rnde_binit_stage_kernel(const BSt
                     acc1 = mfma16(wD[kb][3], bg[kb][3], acc1);
                 }
             }
-            sl[(size_t)w * 64 + lane] = acc0 + acc1;
+            if constexpr (PAIR) slab_put(Y.tslab, tile0 + w, lane, acc0 + acc1);
+            else sl[(size_t)w * 64 + lane] = acc0 + acc1;
         }
         for (int ht = w + Q.WT; ht < Q.HT; ht += Q.WT) {
             f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -153,24 +194,41 @@ __global__ __launch_bounds__(64 * kSMaxW) void rnde_binit_stage_kernel(const BSt
                     acc1 = mfma16(a[3], bg[kb][3], acc1);
                 }
             }
-            sl[(size_t)ht * 64 + lane] = acc0 + acc1;
+            if constexpr (PAIR) slab_put(Y.tslab, tile0 + ht, lane, acc0 + acc1);
+            else sl[(size_t)ht * 64 + lane] = acc0 + acc1;
         }
-        return;
-    } else {
-        // ---- phases A + B of the evaluation (f1 at (u1, t0 + dt0): hidden activations h1; f0 at (u0, t0): h0) ----
-        f32x4 wB[kSMaxHT];
-#pragma unroll
-        for (int kb = 0; kb < kSMaxHT; ++kb)
-            if (kb < Q.KHb && tile_ok) wB[kb] = Q.pwBt[((size_t)T * Q.KHb + kb) * 64 + lane];
+    }
+}
+
+// ---- STEP 1 (kPhase 1) / STEP 3 (kPhase 2): phases A + B of the evaluation (f1 at (u1, t0 + dt0): hidden activations h1; f0 at (u0, t0): h0) and the
+// workgroup's partial sums.  PAIR: the sum over the row blocks' partials is the poll of the hand-off (slab_poll_sum: from zero, r = 0 .. R - 1, as the loop over
+// Q.slab), and the workgroup empties its entries of the other buffer (header above).  A hand-off that times out raises the abort word and leaves zeros: the
+// workgroup finishes (nothing waits behind this poll) and the host, which looks at that word behind every reverse pass, refuses the result.
+template <int ACT2, int kPhase, bool PAIR>
+__device__ __forceinline__ void binit_phase_ab(const BStageParams& Q, const PersistSync& Y, const BinitGeo& g, const f32x4 (&wB)[kSMaxHT], const f32x4& f0v) {
+#pragma clang fp contract(off)
+    const BwdParams& Bq = Q.B;
+    const StepParams& P = Bq.F;
+    const int tid = g.tid, lane = g.lane, w = g.w, rb = g.rb, ct = g.ct, wg = g.wg, col = g.col, gcol = g.gcol, r0 = g.r0, KZ = g.KZ;
+    const bool colok = g.colok, vec = g.vec, tile_ok = g.tile_ok;
+    const long long HB = g.HB;
+    const size_t co = g.co;
+    float* ZL = g.ZL; float* RED = g.RED;
+    constexpr int par = kPhase == 1 ? 0 : 1;
+    float dot = 0.f, tau = 0.f;
+    {
         const float* hsrc = kPhase == 1 ? P.h1 : P.h0;
         float* z1dst = kPhase == 1 ? Bq.zi1 + HB : Bq.zi1;
         const float* W1t = Q.p + (size_t)P.H * P.D;
         const f32x4* sl = (const f32x4*)Q.slab + (((size_t)par * Q.C + ct) * Q.R) * Q.HT * 64;
-        f32x4 f0v = {0.f, 0.f, 0.f, 0.f};
-        if (kPhase == 1 && tile_ok) f0v = ld4(P.f0 + co, r0, P.D, true, vec);
+        const size_t tclr0 = (((size_t)binit_pair_clear(kPhase) * Q.C + ct) * Q.R + rb) * Q.HT;
         for (int ht = w; ht < Q.HT; ht += Q.WT) {
             f32x4 z = {0.f, 0.f, 0.f, 0.f};
-            for (int r = 0; r < Q.R; ++r) z += sl[((size_t)r * Q.HT + ht) * 64 + lane];
+            if constexpr (PAIR) {
+                if (slab_poll_sum(Y, binit_pair_buf(kPhase), Q.C, Q.R, Q.HT, ct, ht, lane, z)) slab_clear(Y.tslab, tclr0 + ht, lane);
+            } else {
+                for (int r = 0; r < Q.R; ++r) z += sl[((size_t)r * Q.HT + ht) * 64 + lane];
+            }
             const int h0 = 16 * ht + 4 * (lane >> 4);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -233,6 +291,41 @@ __global__ __launch_bounds__(64 * kSMaxW) void rnde_binit_stage_kernel(const BSt
             else { float* o = Bq.ipart + ((size_t)P.nwg + wg) * 4; o[0] = ta; o[1] = 0.f; o[2] = 0.f; o[3] = 0.f; }
         }
     }
+}
+
+// the four stand-alone launches (the fallback of the pairs, RNDE_PERSIST=0, RNDE_BINIT_PAIR=0): workgroup blockIdx.x = rb * C + ct
+template <int ACT2, int STEP>
+__global__ __launch_bounds__(64 * kSMaxW) void rnde_binit_stage_kernel(const BStageParams Q) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int rb = blockIdx.x / Q.C, ct = blockIdx.x - rb * Q.C;
+    const BinitGeo g = binit_geo(Q, smem, rb, ct);
+    constexpr int kPhase = STEP < 2 ? 1 : 2;
+    const PersistSync none{};
+    f32x4 f0v = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (STEP == 0 || STEP == 2) {      // the launches that end in phase D
+        binit_phase_d<ACT2, kPhase, false>(Q, none, g, f0v);
+    } else {
+        const StepParams& P = Q.B.F;
+        f32x4 wB[kSMaxHT];
+        binit_load_wB(Q, g, wB);
+        if (kPhase == 1 && g.tile_ok) f0v = ld4(P.f0 + g.co, g.r0, P.D, true, g.vec);
+        binit_phase_ab<ACT2, kPhase, false>(Q, none, g, wB, f0v);
+    }
+}
+
+// STEP 0 + STEP 1 (PHASE 1) or STEP 2 + STEP 3 (PHASE 2) as one launch: grid 8 * R * ceil(C / 8), the attempt kernel's (rb, ct) decoding (rnde_stage_persist.h)
+template <int ACT2, int PHASE>
+__global__ __launch_bounds__(64 * kSMaxW) void rnde_binit_pair_kernel(const BStageParams Q, const PersistSync Y) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int rb = (blockIdx.x >> 3) % Q.R, ct = 8 * ((blockIdx.x >> 3) / Q.R) + (blockIdx.x & 7);
+    if (ct >= Q.C) return;
+    const BinitGeo g = binit_geo(Q, smem, rb, ct);
+    if (g.tid == 0) Y.xcc[g.wg] = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 15;      // (as the attempt kernels: the host checks that a column tile sits on one XCD)
+    f32x4 wB[kSMaxHT];
+    binit_load_wB(Q, g, wB);      // both phases' weights are in flight before the first of them is multiplied
+    f32x4 f0v;
+    binit_phase_d<ACT2, PHASE, true>(Q, Y, g, f0v);
+    binit_phase_ab<ACT2, PHASE, true>(Q, Y, g, wB, f0v);
 }
 
 }  // namespace rnde

@@ -526,5 +526,41 @@ static __global__ void rnde_wgrad_reduce_pair(const ReducePair R) {
         o[i] = s;
     }
 }
+// Both passes of the pair above in ONE launch (bwd_run; host switch RNDE_REDUCE_FOLD, read per call).  A thread owns an element and keeps the (at most 16) group
+// sums of the first pass in registers: group g adds its chunks g * per_group, g * per_group + 1, ... front to back into s[g] (what the eight-wide loop does: it only
+// requests eight values before the first of its strictly sequential additions), then the total is 0.f + s[0], + s[1], ... as the second pass formed it.  The same
+// additions in the same order, so the same bits -- without the round trip of the group sums through slab_r (16 * len floats written and read per layer) and
+// without the boundary between the passes.  The groups are independent chains, so a thread walks them side by side, two chunks of every group (32 loads) requested
+// before the first addition: one group after the other would leave a thread with per_group <= 8 loads in flight where the first pass had sixteen times the threads.
+// A chunk past a group's end is read as chunk 0 and added as 0.f (s + 0.f is s: s is never -0.f, it starts at +0.f).  blockIdx.z = layer.
+static __global__ void rnde_wgrad_reduce_fold_pair(const ReducePair R) {
+    const ReduceJob J = R.j[blockIdx.z];
+    const int pg = J.per_group, groups = (J.n_chunks + pg - 1) / pg;      // host: groups <= 16
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < J.len; i += (long long)gridDim.x * blockDim.x) {
+        float s[16];
+#pragma unroll
+        for (int g = 0; g < 16; ++g) s[g] = 0.f;
+        for (int k = 0; k < pg; k += 2) {
+            float v[2][16];
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int g = 0; g < 16; ++g) {
+                    const int c = g * pg + k + u;
+                    const bool ok = k + u < pg && c < J.n_chunks;
+                    const float x = __builtin_nontemporal_load(J.slab + (size_t)(ok ? c : 0) * J.len + i);
+                    v[u][g] = ok ? x : 0.f;
+                }
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int g = 0; g < 16; ++g) s[g] += v[u][g];
+        }
+        float total = 0.f;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) total = g < groups ? total + s[g] : total;
+        J.out[i] = total;
+    }
+}
 
 }  // namespace rnde

@@ -92,6 +92,7 @@ struct rnde_node {
     int persist = 0, persist_spins = kPersistMaxSpins; int tslab_Bpad = -1; size_t tslab_bytes = 0; DevBuf<float> tslab; unsigned *pabort = nullptr, *pxcc = nullptr; unsigned* h_pchk = nullptr;   // pabort, pxcc: views into mbox; h_pchk: view into h_mbox
     // the whole forward solve as one launch (rnde_stage_solve.h): 1 = use it where it applies, 0 = off (RNDE_STAGE_SOLVE=0 at creation); meeting granules and the epoch of their tags
     // (the abort word and the XCC ids of that kernel are PersistSync's)
+    long long tail_folds[4] = {0, 0, 0, 0};      // launches that took a folded form (rnde_node_tail_folds: reduce fold, weight-gradient pair, x3 pack fold, binit pairs)
     int stage_solve = 1; MeetRes s_meet; int one_launch_solves = 0;
     // the one-launch solve's Dense layers on the matrix cores (rnde_x3.h): 1 = on (RNDE_X3 at creation / rnde_node_set_matrix_mode), split weight images, "packed for the current p"
     int x3 = 0; DevBuf<unsigned char> x3B, x3D, x3Bt, x3Dt; bool x3_packed = false, x3_fwd = false;      // x3_fwd: this forward's stage kernels run with x3 (weights split by its pack launch); x3_packed: the last forward ran the x3 solve, the four images hold ITS parameters (the reverse pass may use the transposed pair)
@@ -190,6 +191,12 @@ static auto mw_variant(const rnde_node* h, F&& f) {
 }
 
 static const rnde_status RNDE_INTERNAL_RETRY = static_cast<rnde_status>(100);
+// The launches around the two sweeps that are folded into a neighbour, one host switch each, read per call like RNDE_SOLVE_FOLD (tests and A/B
+// runs flip them inside one process; 0 = off, anything else = on): RNDE_REDUCE_FOLD (the two passes of the weight-gradient reduction as one launch),
+// RNDE_WGRAD_PAIR (both layers' full-width weight-gradient launches as one), RNDE_BINIT_PAIR (the reverse of the initial-step rule as two paired launches)
+// -- on unless set to 0 -- and RNDE_X3_PACK_FOLD (the x3 weight split inside the pack launch), off unless set: its own A/B did not separate from the
+// run-to-run spread.  Every one of them leaves the results bit for bit what they were.
+static inline bool tail_switch(const char* name, bool by_default = true) { const char* e = getenv(name); return e ? e[0] != '0' : by_default; }
 // ---- rnde.hip, used by rnde_reverse.hip ----
 StepParams make_params(rnde_node* h, const float* x, int B, float t0, float t1, int tape);
 MwParams make_mw_params(rnde_node* h, const StepParams& P);

@@ -79,6 +79,34 @@ static bool wgrad3_ok(int M, int Nx) {
     return getenv("RNDE_WGRAD_LEGACY") == nullptr && getenv("RNDE_WGRAD_V2") == nullptr && M % 4 == 0 && Nx % 4 == 0 && wide > 656 &&
            wide <= 800 && narrow <= 112;
 }
+// Does the quarter form of the bf16x3 weight-gradient kernel (rnde_wgrad4x_kernel) serve this launch, and with which chunks (steps per chunk, number of chunks)
+// and operand feed?  One place for launch_wgrad_part and launch_wgrad_pair: the chunks fix the summation order.
+struct Wx4Plan { bool ok; int spc4, sc4, feed; };
+static Wx4Plan wgrad4_plan(const rnde_node* h, int n_evals, int M, int Nx, int Bpad, int max_chunks) {
+    Wx4Plan q{false, 0, 0, 0};
+    if (n_evals <= 0 || !wgrad3_ok(M, Nx)) return q;
+    const bool tall = M >= Nx;
+    const int total_steps = n_evals * ((Bpad + 31) / 32);
+    // matrix mode 1 in effect for this step (the forward ran the x3 solve): the GEMMs on the matrix cores too (rnde_wgradx.h; RNDE_X3_WGRAD_OFF=1: A/B)
+    const bool x3_off = getenv("RNDE_X3_WGRAD_OFF") != nullptr;            // (read per call: A/B runs and tests switch inside one process)
+    const bool x3_half = getenv("RNDE_X3_WGRAD_HALF") != nullptr;         // (A/B: the single-buffered half form)
+    const int TT4 = ((tall ? M : Nx + 2) + 15) / 16;
+    if (!(h->x3_packed && !x3_off && !x3_half && TT4 >= 28 && TT4 <= 52)) return q;
+    static const int target4 = getenv("RNDE_WGRAD4_CHUNKS") ? atoi(getenv("RNDE_WGRAD4_CHUNKS")) : 64;
+    int sc4 = std::max(1, std::min({max_chunks > 0 ? max_chunks / 2 : target4, total_steps, 256}));
+    const int spc4 = (total_steps + sc4 - 1) / sc4;
+    sc4 = (total_steps + spc4 - 1) / spc4;
+#if RNDE_WX4_ABL == 7 || RNDE_WX4_ABL == 8      // (these two timing ablations exist in the first form only: such a build always launches it)
+    const bool q0 = true;
+#else
+    // which operand feed (rnde_wgradx.h; same chunks, same bits), read per call for A/B runs and tests: RNDE_X3_WGRAD_Q0=1 the quarter form as first built
+    // (FEED 0), RNDE_X3_WGRAD_FEED=1 the coalesced, unrepeated feed (FEED 1); neither set: kWx4DefaultFeed
+    const char* ef = getenv("RNDE_X3_WGRAD_FEED");
+    const bool q0 = getenv("RNDE_X3_WGRAD_Q0") != nullptr || (ef ? ef[0] == '0' : kWx4DefaultFeed == 0);
+#endif
+    q.ok = true; q.spc4 = spc4; q.sc4 = sc4; q.feed = q0 ? 0 : 1;
+    return q;
+}
 // The instantiations of one kernel template share a signature: each launch below picks its kernel as a function pointer from a small table.
 using WgradKern = decltype(&rnde_wgrad3_kernel<true>);      // (rnde_wgrad_kernel, rnde_wgrad2_kernel, rnde_wgrad3_kernel, rnde_wgrad3x_kernel)
 // `max_chunks` > 0 caps the number of chunks (two workgroups each) of the 16x16x4 kernel: 16 for the launches that run
@@ -105,14 +133,10 @@ static rnde_status launch_wgrad_part(rnde_node* h, const EvalDesc* ev, int n_eva
         if ((size_t)(*chunk_cursor + sc) * (size_t)len > h->bw.slab_floats) { h->err = "weight-gradient slab overflow"; return RNDE_ERR_BAD_ARG; }
         // matrix mode 1 in effect for this step (the forward ran the x3 solve): the GEMMs on the matrix cores too (rnde_wgradx.h; RNDE_X3_WGRAD_OFF=1: A/B)
         const bool x3_off = getenv("RNDE_X3_WGRAD_OFF") != nullptr;            // (read per call: A/B runs and tests switch inside one process)
-        const bool x3_half = getenv("RNDE_X3_WGRAD_HALF") != nullptr;         // (A/B: the single-buffered half form)
-        const int TT4 = ((tall ? M : Nx + 2) + 15) / 16;
-        if (h->x3_packed && !x3_off && !x3_half && TT4 >= 28 && TT4 <= 52) {
+        const Wx4Plan q4 = wgrad4_plan(h, n_evals, M, Nx, Bpad, max_chunks);
+        if (q4.ok) {
             // quarter form (rnde_wgrad4x_kernel): four workgroups per chunk, two LDS images; the launches underneath the sweep stay at 32 workgroups (8 chunks)
-            static const int target4 = getenv("RNDE_WGRAD4_CHUNKS") ? atoi(getenv("RNDE_WGRAD4_CHUNKS")) : 64;
-            int sc4 = std::max(1, std::min({max_chunks > 0 ? max_chunks / 2 : target4, total_steps, 256}));
-            const int spc4 = (total_steps + sc4 - 1) / sc4;
-            sc4 = (total_steps + spc4 - 1) / spc4;
+            const int sc4 = q4.sc4, spc4 = q4.spc4, feed = q4.feed;
             if ((size_t)(*chunk_cursor + sc4) * (size_t)len > h->bw.slab_floats) { h->err = "weight-gradient slab overflow"; return RNDE_ERR_BAD_ARG; }
             static constexpr decltype(&rnde_wgrad4x_kernel<true, 0>) kern4[2][2] = {{rnde_wgrad4x_kernel<false, 0>, rnde_wgrad4x_kernel<false, 1>},
                                                                                     {rnde_wgrad4x_kernel<true, 0>, rnde_wgrad4x_kernel<true, 1>}};      // [tall][FEED]
@@ -124,15 +148,6 @@ static rnde_status launch_wgrad_part(rnde_node* h, const EvalDesc* ev, int n_eva
                 attr4.done();
             }
             const dim3 g4(32 * ((sc4 + 7) / 8));
-#if RNDE_WX4_ABL == 7 || RNDE_WX4_ABL == 8      // (these two timing ablations exist in the first form only: such a build always launches it)
-            const bool q0 = true;
-#else
-            // which operand feed (rnde_wgradx.h; same chunks, same bits), read per call for A/B runs and tests: RNDE_X3_WGRAD_Q0=1 the quarter form as first built
-            // (FEED 0), RNDE_X3_WGRAD_FEED=1 the coalesced, unrepeated feed (FEED 1); neither set: kWx4DefaultFeed
-            const char* ef = getenv("RNDE_X3_WGRAD_FEED");
-            const bool q0 = getenv("RNDE_X3_WGRAD_Q0") != nullptr || (ef ? ef[0] == '0' : kWx4DefaultFeed == 0);
-#endif
-            const int feed = q0 ? 0 : 1;
             hipLaunchKernelGGL(kern4[tall][feed], g4, dim3(448), lds4[feed], s, ev, n_evals, spc4, sc4, M, Nx, Bpad, dst);
             HIPCHK(h, hipGetLastError());
             *chunk_cursor += sc4;
@@ -176,6 +191,37 @@ static rnde_status launch_wgrad_part(rnde_node* h, const EvalDesc* ev, int n_eva
     }
     HIPCHK(h, hipGetLastError());
     *chunk_cursor += chunks;
+    return RNDE_OK;
+}
+// The full-width launches behind the sweep, layer 1 then layer 2, over the same evaluations.  Where both are the quarter form with FEED 1 they go out as ONE launch
+// (rnde_wgrad4x_pair_kernel: the two grids back to back; host switch RNDE_WGRAD_PAIR, read per call): each layer's chunk table, steps per chunk, number of chunks,
+// chunk-to-XCD map (a layer's grid is a multiple of 32 workgroups, so the second layer's linear ids keep their id % 8) and slab positions are those of the two
+// launches, which serve every other case.
+static rnde_status launch_wgrad_pair(rnde_node* h, const EvalDesc* ev1, const EvalDesc* ev2, int n_evals, int per_chunk, int Bpad, float* slab1, int* cur1,
+                                     float* slab2, int* cur2, hipStream_t s) {
+    const int H = h->H, D = h->D;
+    const Wx4Plan q1 = wgrad4_plan(h, n_evals, H, D, Bpad, 0), q2 = wgrad4_plan(h, n_evals, D, H, Bpad, 0);
+    const long long len1 = (long long)H * (D + 2), len2 = (long long)D * (H + 2);
+    // (launch_wgrad_part checks the slab against the 16x16x4 kernel's chunk count in front of the quarter form's own: a call it would refuse is left to it)
+    const int most = std::max({q1.sc4, q2.sc4, std::min({128, n_evals * ((Bpad + 31) / 32), 256})});
+    const bool fits = (size_t)(*cur1 + most) * (size_t)len1 <= h->bw.slab_floats && (size_t)(*cur2 + most) * (size_t)len2 <= h->bw.slab_floats;
+    static const bool chunks_env = getenv("RNDE_WGRAD3_CHUNKS") != nullptr;      // (an A/B run that moves that count: the two launches, which read it)
+    if (!(q1.ok && q2.ok && q1.feed == 1 && q2.feed == 1 && fits && !chunks_env && tail_switch("RNDE_WGRAD_PAIR"))) {
+        rnde_status r = launch_wgrad_part(h, ev1, n_evals, per_chunk, H, D, Bpad, slab1, cur1, s);
+        if (r != RNDE_OK) return r;
+        return launch_wgrad_part(h, ev2, n_evals, per_chunk, D, H, Bpad, slab2, cur2, s);
+    }
+    static DeviceOnce attrp;
+    if (attrp.need()) {
+        HIPCHK(h, hipFuncSetAttribute((const void*)rnde_wgrad4x_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWx4fLdsBytes));
+        attrp.done();
+    }
+    const Wx4Job j1{ev1, n_evals, q1.spc4, q1.sc4, H, D, slab1 + (size_t)(*cur1) * len1};
+    const Wx4Job j2{ev2, n_evals, q2.spc4, q2.sc4, D, H, slab2 + (size_t)(*cur2) * len2};
+    const int g1 = 32 * ((q1.sc4 + 7) / 8), g2 = 32 * ((q2.sc4 + 7) / 8);
+    hipLaunchKernelGGL(rnde_wgrad4x_pair_kernel, dim3(g1 + g2), dim3(448), kWx4fLdsBytes, s, j1, j2, g1, Bpad);
+    HIPCHK(h, hipGetLastError());
+    *cur1 += q1.sc4; *cur2 += q2.sc4; ++h->tail_folds[1];
     return RNDE_OK;
 }
 
@@ -270,7 +316,7 @@ static rnde_status bwd_run(rnde_node* h, const float* u_bar_dev, const float* sa
             HIPCHK(h, hipEventRecord(ev, s));
             HIPCHK(h, hipStreamWaitEvent(h->wstream, ev, 0));
             ws = h->wstream; used_side = true;
-        }
+        } else return launch_wgrad_pair(h, d_ev1 + lo, d_ev2 + lo, hi - lo, per_chunk, h->B, slab1, &cur1, slab2w, &cur2, s);      // (behind the sweep: both layers in one launch where the quarter form serves them)
         rnde_status r = launch_wgrad_part(h, d_ev1 + lo, hi - lo, per_chunk, h->H, h->D, h->B, slab1, &cur1, ws, on_side ? 16 : 0);
         if (r != RNDE_OK) return r;
         return launch_wgrad_part(h, d_ev2 + lo, hi - lo, per_chunk, h->D, h->H, h->B, slab2w, &cur2, ws, on_side ? 16 : 0);
@@ -361,8 +407,25 @@ static rnde_status bwd_run(rnde_node* h, const float* u_bar_dev, const float* sa
             if ((st = couple_sum(h, b.bpart + (size_t)(n & 1) * Q.bpart_n * 4, 4LL * Q.bpart_n, s)) != RNDE_OK) return st;
         }
         HIPCHK(h, hipGetLastError());
-        {   // reverse of the initial-step rule: four stage-engine launches (rnde_binit_stage.h)
-            for (int step = 0; step < 4; ++step) {
+        {   // reverse of the initial-step rule (rnde_binit_stage.h): four stage-engine steps, each pair of them -- STEP 0 + 1, STEP 2 + 3: nothing but a hand-off
+            // inside the column tile between them -- as one launch on the persistent grid while the persistent kernels are in use (a hand-off that gives up is
+            // found by persist_check_* behind this pass, as for the attempt kernel: the handle then falls back to the four launches); RNDE_BINIT_PAIR=0, read per
+            // call: the four launches.  The sums over all workgroups (ipart; the coupled controller's all-reduce) stay between the pairs.
+            const bool pairs = h->persist == 1 && tail_switch("RNDE_BINIT_PAIR");
+            if (pairs) {
+                static constexpr decltype(&rnde_binit_pair_kernel<0, 1>) kPair[2][2] = {{rnde_binit_pair_kernel<0, 1>, rnde_binit_pair_kernel<0, 2>},
+                                                                                      {rnde_binit_pair_kernel<1, 1>, rnde_binit_pair_kernel<1, 2>}};      // [ACT2][PHASE - 1]
+                PersistSync Y{h->tslab, h->pabort, h->pxcc, h->persist_spins};
+                HIPCHK(h, slab_prepare(h, Q.F.Bpad, s));
+                const dim3 pgrid(8 * BQ.R * ((BQ.C + 7) / 8));
+                for (int ph = 0; ph < 2; ++ph) {
+                    hipLaunchKernelGGL(kPair[a2][ph], pgrid, blk, h->stage_lds, s, BQ, Y);
+                    ++h->tail_folds[3];
+                    // (coupled controller) after phase 1: dot, tau of the reversed second evaluation; after phase 2: tau of the first
+                    if ((st = couple_sum(h, Q.ipart + ph * 4LL * Q.F.nwg, 4LL * Q.F.nwg, s)) != RNDE_OK) return st;
+                }
+            }
+            for (int step = 0; step < 4 && !pairs; ++step) {
                 hipLaunchKernelGGL(kInit[a2][step], grid, blk, h->stage_lds, s, BQ);
                 // (coupled controller) after step 1: dot, tau of the reversed second evaluation; after step 3: tau of the first
                 if ((step & 1) && (st = couple_sum(h, Q.ipart + (step / 2) * 4LL * Q.F.nwg, 4LL * Q.F.nwg, s)) != RNDE_OK) return st;
@@ -386,10 +449,16 @@ static rnde_status bwd_run(rnde_node* h, const float* u_bar_dev, const float* sa
         float* r1 = b.slab_r; float* r2 = b.slab_r + 16 * seg_r;
         const int pg1 = (cur1 + 15) / 16, g1 = (cur1 + pg1 - 1) / pg1, pg2 = (cur2 + 15) / 16, g2 = (cur2 + pg2 - 1) / pg2;
         const int grid = (int)std::min<long long>((std::max(len1, len2) + 255) / 256, 2048);
-        ReducePair A{{{slab1, r1, len1, cur1, pg1}, {slab2w, r2, len2, cur2, pg2}}};
-        hipLaunchKernelGGL(rnde_wgrad_reduce_pair, dim3(grid, std::max(g1, g2), 2), dim3(256), 0, s, A);
-        ReducePair Bp{{{r1, p_bar_dev, len1, g1, g1}, {r2, p_bar_dev + (size_t)h->H * (h->D + 2), len2, g2, g2}}};
-        hipLaunchKernelGGL(rnde_wgrad_reduce_pair, dim3(grid, 1, 2), dim3(256), 0, s, Bp);
+        if (tail_switch("RNDE_REDUCE_FOLD")) {      // the two passes as one launch, the group sums in registers (rnde_wgrad_reduce_fold_pair: same sums, same order)
+            ReducePair F{{{slab1, p_bar_dev, len1, cur1, pg1}, {slab2w, p_bar_dev + (size_t)h->H * (h->D + 2), len2, cur2, pg2}}};
+            hipLaunchKernelGGL(rnde_wgrad_reduce_fold_pair, dim3(grid, 1, 2), dim3(256), 0, s, F);
+            ++h->tail_folds[0];
+        } else {
+            ReducePair A{{{slab1, r1, len1, cur1, pg1}, {slab2w, r2, len2, cur2, pg2}}};
+            hipLaunchKernelGGL(rnde_wgrad_reduce_pair, dim3(grid, std::max(g1, g2), 2), dim3(256), 0, s, A);
+            ReducePair Bp{{{r1, p_bar_dev, len1, g1, g1}, {r2, p_bar_dev + (size_t)h->H * (h->D + 2), len2, g2, g2}}};
+            hipLaunchKernelGGL(rnde_wgrad_reduce_pair, dim3(grid, 1, 2), dim3(256), 0, s, Bp);
+        }
         HIPCHK(h, hipGetLastError());
     } else {
         HIPCHK(h, launch_wgrad_reduce(slab1, cur1, (long long)h->H * (h->D + 2), b.slab_r, p_bar_dev, s));                                       // [W1; b1]

@@ -16,6 +16,7 @@
 // column-owner engine (rnde_fwd.h).
 #pragma once
 #include "rnde_fwd.h"
+#include "rnde_x3.h"      // x3_pack_elem (rnde_pack_all_kernel)
 
 namespace rnde {
 
@@ -88,13 +89,16 @@ static __global__ void rnde_stage_pack_kernel(const float* __restrict__ p, f32x4
 
 // Everything a taped solve derives from the parameter vector, in ONE launch (was six pack launches and a copy, ~5 us each, in front
 // of every training step): blockIdx.y selects the job -- a stage-engine pack (kind 0), a column-owner pack for the kernels of the
-// initial-step rule (kind 1), or the tape's own copy of p (kind 2).
+// initial-step rule (kind 1), or the tape's own copy of p (kind 2).  Matrix mode 1: the split of the weights into three bf16 planes as well (kind 4, rnde_x3.h:
+// the fragments of rnde_x3_pack_kernel through the same x3_pack_elem, so the images are byte for byte that launch's; one job, its destinations and tile geometry in
+// `x3` / `MT, WT, R, HT` of the block, total = x3_pack_count).
 struct PackJob { void* dst; const float* src; long long total; int kind, which, kdim, pad; };   // src: kind 2 only (NULL = the parameter vector)
-struct PackJobs { PackJob j[8]; };
+struct PackJobs { PackJob j[8]; X3PackDst x3; int MT, WT, R, HT; };
 static __global__ void rnde_pack_all_kernel(const float* __restrict__ p, const PackJobs J, int D, int H) {
     const PackJob job = J.j[blockIdx.y];
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < job.total; i += (long long)gridDim.x * blockDim.x) {
         if (job.kind == 0) ((f32x4*)job.dst)[i] = stage_pack_elem(p, job.which, D, H, job.kdim, i);
+        else if (job.kind == 4) x3_pack_elem(p, J.x3, D, H, J.MT, J.WT, J.R, J.HT, i);
         else if (job.kind == 2) ((float*)job.dst)[i] = (job.src ? job.src : p)[i];
         else ((f32x4*)job.dst)[i] = ((const f32x4*)(job.src ? job.src : p))[i];      // kind 3: 16-byte copy (total counts float4s)
     }

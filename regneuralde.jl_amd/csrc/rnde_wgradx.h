@@ -199,15 +199,17 @@ constexpr int kWx4fImageShorts = 3 * kWx4fPlane;
 constexpr size_t kWx4fLdsBytes = (size_t)2 * kWx4fImageShorts * 2;   // 125,952 bytes: two images
 constexpr int kWx4DefaultFeed = 1;      // bit-identical (tests/test_gpu_wgrad_feed.py) and 11 % faster per launch (profiles/wgrad_feed_probe.csv)
 
+// (the kernel's body as a function of the workgroup's linear id `lin` within its layer's grid: rnde_wgrad4x_kernel runs it with blockIdx.x, rnde_wgrad4x_pair_kernel
+//  with the id inside whichever of its two grids the workgroup belongs to -- the same instructions either way)
 template <bool TALL_IS_Z, int FEED>
-__global__ __launch_bounds__(448) void rnde_wgrad4x_kernel(const EvalDesc* __restrict__ evals, int n_evals, int per_chunk, int n_chunks, int M, int Nx, int Bpad,
-                                                           float* __restrict__ slab) {
+__device__ __forceinline__ void wgrad4x_body(const int lin, const EvalDesc* __restrict__ evals, int n_evals, int per_chunk, int n_chunks, int M, int Nx, int Bpad,
+                                             float* __restrict__ slab) {
     constexpr int KC = 32;
     extern __shared__ __attribute__((aligned(16))) unsigned short wxs[];
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int mrow = lane & 15, kk = lane >> 4;
     // linear id -> XCD (round-robin dispatch: id % 8), then chunk-major inside the XCD: the four parts of a chunk are neighbours on one XCD
-    const int lin = blockIdx.x, xcd = lin & 7, within = lin >> 3;
+    const int xcd = lin & 7, within = lin >> 3;
     const int chunk = (within >> 2) * 8 + xcd, part = within & 3;
     if (chunk >= n_chunks) return;
     const int TR = TALL_IS_Z ? M : Nx + 2, SR = TALL_IS_Z ? Nx + 2 : M;          // rows of the wide / narrow operand, synthetic {t, 1} rows included
@@ -410,6 +412,20 @@ __global__ __launch_bounds__(448) void rnde_wgrad4x_kernel(const EvalDesc* __res
             }
         }
     }
+}
+template <bool TALL_IS_Z, int FEED>
+__global__ __launch_bounds__(448) void rnde_wgrad4x_kernel(const EvalDesc* __restrict__ evals, int n_evals, int per_chunk, int n_chunks, int M, int Nx, int Bpad,
+                                                           float* __restrict__ slab) {
+    wgrad4x_body<TALL_IS_Z, FEED>(blockIdx.x, evals, n_evals, per_chunk, n_chunks, M, Nx, Bpad, slab);
+}
+// Both layers' full-width launches behind the sweep as ONE launch (FEED 1): the grid is layer 1's (grid1 workgroups, a multiple of 32) followed by layer 2's; which
+// layer a workgroup serves is workgroup-uniform, and it then runs that layer's body with its id inside that layer's grid -- chunk, part and XCD (id % 8) as in a launch
+// of the layer's own.  One boundary less, each behind ~20 MB of freshly written partials, and layer 2's workgroups start on the CUs layer 1's last ones leave idle.
+struct Wx4Job { const EvalDesc* evals; int n_evals, per_chunk, n_chunks, M, Nx; float* slab; };
+static __global__ __launch_bounds__(448) void rnde_wgrad4x_pair_kernel(const Wx4Job j1, const Wx4Job j2, const int grid1, const int Bpad) {
+    const int lin = blockIdx.x;
+    if (lin < grid1) wgrad4x_body<false, 1>(lin, j1.evals, j1.n_evals, j1.per_chunk, j1.n_chunks, j1.M, j1.Nx, Bpad, j1.slab);
+    else wgrad4x_body<true, 1>(lin - grid1, j2.evals, j2.n_evals, j2.per_chunk, j2.n_chunks, j2.M, j2.Nx, Bpad, j2.slab);
 }
 
 }  // namespace rnde

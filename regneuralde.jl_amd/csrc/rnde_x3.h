@@ -125,14 +125,15 @@ __device__ __forceinline__ x3f4 x3_tile(const x3u4 (&wa)[NS][3], const unsigned 
 //   3 reverse  W2xt^T  (phase D): tile = hidden tile w * R + row block rb; m = 16 w + (l & 15) <= H (m == H: the time column); k as in image 1: W2[state row][m]
 // Parameter layout as stage_pack_elem: Flux.destructure order, W stored out x in column-major.  dst[0..1] forward, dst[2..3] reverse (nullptr: skipped).
 struct X3PackDst { x3u4* d[4]; };
-static __global__ void rnde_x3_pack_kernel(const float* __restrict__ p, const X3PackDst dst, int D, int H, int MT, int WT, int R, int HT) {
+// fragments of the images: x3_pack_count of them, fragment i split and stored by x3_pack_elem (rnde_x3_pack_kernel, and rnde_pack_all_kernel's job of this kind)
+__host__ __device__ __forceinline__ long long x3_pack_count(const X3PackDst& dst, int MT, int R, int HT) { return (dst.d[2] ? 2 : 1) * ((long long)MT * 4 * 64 + (long long)HT * R * 4 * 64); }
+__device__ __forceinline__ void x3_pack_elem(const float* __restrict__ p, const X3PackDst& dst, int D, int H, int MT, int WT, int R, int HT, long long i) {
     const float* W1 = p;
     const float* b1 = W1 + (size_t)H * (D + 1);
     const float* W2 = b1 + H;
     const float* b2 = W2 + (size_t)D * (H + 1);
     const long long nB = (long long)MT * 4 * 64, nD = (long long)HT * R * 4 * 64, per = nB + nD;
-    const int nimg = dst.d[2] ? 2 : 1;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nimg * per; i += (long long)gridDim.x * blockDim.x) {
+    {
         const int rev = (int)(i / per);
         const long long ii = i - rev * per;
         const bool isD = ii >= nB;
@@ -167,6 +168,10 @@ static __global__ void rnde_x3_pack_kernel(const float* __restrict__ p, const X3
         o[64] = (x3u4){mid[0], mid[1], mid[2], mid[3]};
         o[128] = (x3u4){lo[0], lo[1], lo[2], lo[3]};
     }
+}
+static __global__ void rnde_x3_pack_kernel(const float* __restrict__ p, const X3PackDst dst, int D, int H, int MT, int WT, int R, int HT) {
+    const long long total = x3_pack_count(dst, MT, R, HT);
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) x3_pack_elem(p, dst, D, H, MT, WT, R, HT, i);
 }
 
 }  // namespace rnde
