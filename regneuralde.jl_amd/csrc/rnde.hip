@@ -246,9 +246,8 @@ static hipError_t launch_mw(rnde_node* h, const MwParams& Q, int n, hipStream_t 
     return mw_variant(h, [&](auto nr, auto tab, auto lat) { return launch_mw_t<nr(), MODE, tab(), lat()>(h, Q, n, s); });
 }
 // the forward tapes every layer input of every evaluation into the slab: make room for `evals` evaluations (growing keeps what is there)
-static rnde_status ensure_mw_slab(rnde_node* h, long long evals, int Bpad, hipStream_t s) {
+static rnde_status ensure_mw_slab(rnde_node* h, long long evals, hipStream_t s) {
     const long long per_eval = (long long)(h->Bpad_max / 16) * h->mg.RS * 64;   // sized for max_batch so that ev_stride changes never outgrow it
-    (void)Bpad;
     if (h->mw_slab_evals >= evals) return RNDE_OK;
     long long want = std::max(evals, 2 * h->mw_slab_evals);
     {   // 288 GB of HBM: when the slab of a max_attempts solve is small next to what is free, take that at once -- growing it later costs a stream
@@ -394,7 +393,7 @@ extern "C" rnde_status rnde_node_create(const rnde_node_config* c, rnde_node** o
     if (h->persist == 1) {
         h->x3 = 1;      // default where the geometry fits (include/rnde.h: rnde_node_set_matrix_mode)
         if (const char* e7 = getenv("RNDE_X3")) h->x3 = atoi(e7) != 0;
-        if (h->sMT == 49 && h->sHT == 7 && h->sR == 7 && h->sWT == 7 && h->D == 784 && h->H == 100 && !h->stage_generic) {
+        if (stage_fix(h, h->sWT, h->sHT, h->sK2b, h->sMT, h->sR)) {
             const size_t img = (size_t)49 * 4 * 3 * 64 * 16;
             if (!(dm(h->x3B, img) && dm(h->x3D, img) && dm(h->x3Bt, img) && dm(h->x3Dt, img))) { g_create_err = "device allocation failed"; return RNDE_ERR_HIP; }
         } else h->x3 = 0;
@@ -512,8 +511,7 @@ hipError_t slab_prepare(rnde_node* h, int Bpad, hipStream_t s) {
 }
 // the two-tile attempt kernel serves this geometry (rnde_stage_persist2.h): the headline network, an even number of column tiles, enough of them
 static bool stage_two_tile(const rnde_node* h, const StageParams& Q) {
-    const bool fix = Q.WT == 7 && Q.HT == 7 && Q.K2b == 7 && Q.MT == 49 && Q.R == 7 && h->D == 784 && h->H == 100 && !h->stage_generic;
-    return h->persist == 1 && fix && Q.C % 2 == 0 && h->persist2 != 0 && (Q.C >= kPersist2MinTiles || h->persist2 >= 1);
+    return h->persist == 1 && stage_fix(h, Q.WT, Q.HT, Q.K2b, Q.MT, Q.R) && Q.C % 2 == 0 && h->persist2 != 0 && (Q.C >= kPersist2MinTiles || h->persist2 >= 1);
 }
 // large batches: the error partials of an attempt summed once behind its launch (rnde_epart_reduce_kernel) instead of in every workgroup's prologue of the next --
 // from ~900 partials on (B >= 2048), where the two-tile kernel runs; RNDE_NO_EPART_REDUCE=1: A/B
@@ -521,42 +519,39 @@ static bool stage_epart_reduce(const rnde_node* h, const StageParams& Q) {
     return stage_two_tile(h, Q) && Q.F.nwg >= 896 && !getenv("RNDE_NO_EPART_REDUCE");
 }
 static hipError_t stage_attempt(rnde_node* h, const StageParams& Q, int n, hipStream_t s) {
-    if (h->persist == 1) {   // one launch per attempt, slab hand-offs inside the kernel (rnde_stage_persist.h)
-        PersistSync Y{h->tslab, h->pabort, h->pxcc, h->persist_spins};
-        if (hipError_t e = slab_prepare(h, Q.Bpad16, s); e != hipSuccess) return e;
-        const dim3 grid(8 * Q.R * ((Q.C + 7) / 8));   // a column tile's row blocks share blockIdx % 8 (same XCD)
-        const bool fix = Q.WT == 7 && Q.HT == 7 && Q.K2b == 7 && Q.MT == 49 && Q.R == 7 && h->D == 784 && h->H == 100 && !h->stage_generic;
-        // batches that fill the chip more than once: two column tiles per workgroup (rnde_stage_persist2.h; bit-identical results).
-        // RNDE_PERSIST2=0 keeps one tile per workgroup (A/B and the bit-identity test), =1 takes two whenever the tile count is even.
-        static const bool x3_over_mt = !(getenv("RNDE_X3_MT") && atoi(getenv("RNDE_X3_MT")) == 0);      // (A/B: 0 = keep the fp32 two-tile kernel for large batches even in matrix mode 1)
-        if (stage_two_tile(h, Q)) {
-            const dim3 grid2(8 * Q.R * ((Q.C / 2 + 7) / 8));
-            if (h->x3_fwd && x3_over_mt) {      // matrix mode 1: the two-tile kernel in its x3 form (RNDE_X3_MT=0: the fp32 form, A/B)
-                const size_t xlds2 = sizeof(float) * ((size_t)2 * 2 * kX3ImageFloats + 32 * 3);
-                if (h->act2) hipLaunchKernelGGL((rnde_stage_attempt_mt_kernel<1, 2, 1>), grid2, dim3(64 * 7), xlds2, s, Q, n, Y, (const void*)h->x3B, (const void*)h->x3D);
-                else hipLaunchKernelGGL((rnde_stage_attempt_mt_kernel<0, 2, 1>), grid2, dim3(64 * 7), xlds2, s, Q, n, Y, (const void*)h->x3B, (const void*)h->x3D);
-                return hipGetLastError();
-            }
-            const size_t lds2 = sizeof(float) * (2 * 2 * 16 * (16 * 7 + 4) + 32 * 3);
-            if (h->act2) hipLaunchKernelGGL((rnde_stage_attempt_mt_kernel<1, 2>), grid2, dim3(64 * 7), lds2, s, Q, n, Y, (const void*)nullptr, (const void*)nullptr);
-            else hipLaunchKernelGGL((rnde_stage_attempt_mt_kernel<0, 2>), grid2, dim3(64 * 7), lds2, s, Q, n, Y, (const void*)nullptr, (const void*)nullptr);
-            return hipGetLastError();
-        }
-        if (fix && h->x3_fwd) {      // matrix mode 1: the same instruction sequence as the x3 one-launch solve (bit-identical to it)
-            const size_t xlds = sizeof(float) * ((size_t)2 * kX3ImageFloats + 64);
-            if (h->act2) hipLaunchKernelGGL((rnde_stage_attempt_kernel<1, 1, 1>), grid, dim3(64 * 7), xlds, s, Q, n, Y, (const void*)h->x3B, (const void*)h->x3D);
-            else hipLaunchKernelGGL((rnde_stage_attempt_kernel<0, 1, 1>), grid, dim3(64 * 7), xlds, s, Q, n, Y, (const void*)h->x3B, (const void*)h->x3D);
-        } else if (fix) {
-            if (h->act2) hipLaunchKernelGGL((rnde_stage_attempt_kernel<1, 1>), grid, dim3(64 * Q.WT), h->stage_lds, s, Q, n, Y, (const void*)nullptr, (const void*)nullptr);
-            else hipLaunchKernelGGL((rnde_stage_attempt_kernel<0, 1>), grid, dim3(64 * Q.WT), h->stage_lds, s, Q, n, Y, (const void*)nullptr, (const void*)nullptr);
-        } else if (h->act2) hipLaunchKernelGGL((rnde_stage_attempt_kernel<1, 0>), grid, dim3(64 * Q.WT), h->stage_lds, s, Q, n, Y, (const void*)nullptr, (const void*)nullptr);
-        else hipLaunchKernelGGL((rnde_stage_attempt_kernel<0, 0>), grid, dim3(64 * Q.WT), h->stage_lds, s, Q, n, Y, (const void*)nullptr, (const void*)nullptr);
-        return hipGetLastError();
+    if (h->persist != 1) {
+        hipError_t e = launch_stage<SM_START>(h, Q, n, 0, s);
+        for (int st = 1; st <= 5 && e == hipSuccess; ++st) e = launch_stage<SM_STAGE>(h, Q, n, st, s);
+        if (e == hipSuccess) e = launch_stage<SM_LAST>(h, Q, n, 6, s);
+        return e;
     }
-    hipError_t e = launch_stage<SM_START>(h, Q, n, 0, s);
-    for (int st = 1; st <= 5 && e == hipSuccess; ++st) e = launch_stage<SM_STAGE>(h, Q, n, st, s);
-    if (e == hipSuccess) e = launch_stage<SM_LAST>(h, Q, n, 6, s);
-    return e;
+    // one launch per attempt, slab hand-offs inside the kernel (rnde_stage_persist.h)
+    using AttemptKern = void (*)(StageParams, int, PersistSync, const void*, const void*);
+    // batches that fill the chip more than once: two column tiles per workgroup (rnde_stage_persist2.h; bit-identical results).
+    // RNDE_PERSIST2=0 keeps one tile per workgroup (A/B and the bit-identity test), =1 takes two whenever the tile count is even.
+    static constexpr AttemptKern kTwoTile[2][2] = {{rnde_stage_attempt_mt_kernel<0, 2>, rnde_stage_attempt_mt_kernel<0, 2, 1>},
+                                                   {rnde_stage_attempt_mt_kernel<1, 2>, rnde_stage_attempt_mt_kernel<1, 2, 1>}};      // [ACT2][x3]
+    static constexpr size_t lds2[2] = {sizeof(float) * (2 * 2 * 16 * (16 * 7 + 4) + 32 * 3), sizeof(float) * ((size_t)2 * 2 * kX3ImageFloats + 32 * 3)};      // [x3]
+    // one tile: the generic kernel, the headline geometry, and the headline geometry in matrix mode 1 -- the same instruction sequence as the x3
+    // one-launch solve (bit-identical to it)
+    static constexpr AttemptKern kOneTile[2][3] = {{rnde_stage_attempt_kernel<0, 0>, rnde_stage_attempt_kernel<0, 1>, rnde_stage_attempt_kernel<0, 1, 1>},
+                                                   {rnde_stage_attempt_kernel<1, 0>, rnde_stage_attempt_kernel<1, 1>, rnde_stage_attempt_kernel<1, 1, 1>}};      // [ACT2][generic | fixed | fixed x3]
+    const size_t lds1[3] = {h->stage_lds, h->stage_lds, sizeof(float) * ((size_t)2 * kX3ImageFloats + 64)};
+    PersistSync Y{h->tslab, h->pabort, h->pxcc, h->persist_spins};
+    if (hipError_t e = slab_prepare(h, Q.Bpad16, s); e != hipSuccess) return e;
+    static const bool x3_over_mt = !(getenv("RNDE_X3_MT") && atoi(getenv("RNDE_X3_MT")) == 0);      // (A/B: 0 = keep the fp32 two-tile kernel for large batches even in matrix mode 1)
+    const int a2 = h->act2 ? 1 : 0;
+    const bool two = stage_two_tile(h, Q);
+    const bool x3 = h->x3_fwd && (two ? x3_over_mt : stage_fix(h, Q.WT, Q.HT, Q.K2b, Q.MT, Q.R));
+    const void* const xB = x3 ? (const void*)h->x3B : nullptr;
+    const void* const xD = x3 ? (const void*)h->x3D : nullptr;
+    if (two) hipLaunchKernelGGL(kTwoTile[a2][x3], dim3(8 * Q.R * ((Q.C / 2 + 7) / 8)), dim3(64 * 7), lds2[x3], s, Q, n, Y, xB, xD);
+    else {
+        const int form = x3 ? 2 : (stage_fix(h, Q.WT, Q.HT, Q.K2b, Q.MT, Q.R) ? 1 : 0);
+        // a column tile's row blocks share blockIdx % 8 (same XCD)
+        hipLaunchKernelGGL(kOneTile[a2][form], dim3(8 * Q.R * ((Q.C + 7) / 8)), dim3(64 * Q.WT), lds1[form], s, Q, n, Y, xB, xD);
+    }
+    return hipGetLastError();
 }
 
 // The one-launch reverse sweep of the chain engine (rnde_bchainmw.h SWEEP) leaves its verdict in h_mw_bchk behind the sweep; looked at after the
@@ -574,10 +569,6 @@ bool bsweep_failed(rnde_node* h, hipStream_t s) {
     h->h_mw_bchk[0] = 0;
     return true;
 }
-
-static rnde_status forward_core(rnde_node* h, const float* x_dev, const float* p_dev, int32_t B, float t0, float t1,
-                                float* u_out_dev, const float* saveat_host, int32_t n_saveat, float* sv_out_dev,
-                                int64_t* nfe_out, float* saveval_host, int32_t* n_saveval_out, int32_t keep_tape, void* stream);
 
 // After a synchronisation point: did a persistent launch time out, or did a column tile's workgroups land on different
 // XCDs (then their slab hand-off through L2 would not be coherent)?  Either way the persistent kernels are disabled for
@@ -609,15 +600,316 @@ static bool persist_failed(rnde_node* h, int grid, int C, int R, hipStream_t s) 
     return persist_check_result(h, C, R, s);
 }
 
+// ---- one dispatch for the three engines (stage, one-wave chain, multi-wave chain): the forward solve, rnde_debug_attempt and rnde_bench_attempt* ----
+struct EngineParams { StepParams P; StageParams SQ; ChainParams CQ; MwParams MQ; };      // the engine's own blocks are filled, the others stay empty
+static EngineParams engine_params(rnde_node* h, const StepParams& P, const float* p_dev) {
+    EngineParams E{};
+    E.P = P;
+    if (h->engine != 3) E.SQ = make_stage_params(h, P, p_dev);
+    else { E.CQ = make_chain_params(h, P); if (h->mw) E.MQ = make_mw_params(h, P); }
+    return E;
+}
+static hipError_t launch_attempt(rnde_node* h, const EngineParams& E, int n, hipStream_t s) {
+    if (h->engine == 3 && h->mw) return launch_mw<MW_STEP>(h, E.MQ, n, s);
+    if (h->engine == 3) return launch_chain<CM_STEP>(h, E.CQ, n, nullptr, s);
+    return stage_attempt(h, E.SQ, n, s);
+}
+// controller state after n attempts to ctl_final, the end state to u_out (may be null)
+static hipError_t launch_finish(rnde_node* h, EngineParams& E, int n, float* u_out, hipStream_t s) {
+    if (h->engine == 3 && h->mw) { E.MQ.u_out = u_out; return launch_mw<MW_FINISH>(h, E.MQ, n, s); }
+    if (h->engine == 3) return launch_chain<CM_FINISH>(h, E.CQ, n, u_out, s);
+    hipLaunchKernelGGL(rnde_stage_finish_kernel, dim3(256), dim3(256), 0, s, E.SQ, n, u_out);
+    return hipGetLastError();
+}
+// the two halves of the initial-step rule: f(u0, t0) into f0 with the norms of u0 and f0, then f(u1, t0 + dt0) with the norm of f1 - f0
+static hipError_t launch_init(rnde_node* h, const EngineParams& E, int half, hipStream_t s) {
+    if (h->engine == 3 && h->mw) return half ? launch_mw<MW_INIT_B>(h, E.MQ, 0, s) : launch_mw<MW_INIT_A>(h, E.MQ, 0, s);
+    if (h->engine == 3) return half ? launch_chain<CM_INIT_B>(h, E.CQ, 0, nullptr, s) : launch_chain<CM_INIT_A>(h, E.CQ, 0, nullptr, s);
+    const hipError_t e = half ? launch_stage<SM_I3>(h, E.SQ, 0, 0, s) : launch_stage<SM_I1>(h, E.SQ, 0, 0, s);
+    return e != hipSuccess ? e : (half ? launch_stage<SM_I4>(h, E.SQ, 0, 0, s) : launch_stage<SM_I2>(h, E.SQ, 0, 0, s));
+}
+// weights in the engine's layout in front of an untaped call
+static rnde_status pack_untaped(rnde_node* h, const float* p_dev, hipStream_t s) { return h->engine == 3 ? chain_pack(h, p_dev, s) : stage_pack_weights(h, p_dev, s); }
+
+#ifdef RNDE_DIAG
+#include "rnde_diag.h"      // (tools/build_diag.sh) cycle-stamp reports of the forward: RNDE_DIAG_SOLVE, RNDE_DIAG_FWD, rnde_bench_attempt*
+#endif
+
+// controller state, the first n step records and the initial-step record on their way to the host (stage engine: contiguous in the mailbox, with
+// the persistent kernels' health words)
+static rnde_status fetch_log(rnde_node* h, int n, hipStream_t s) {
+    if (h->mbox) { HIPCHK(h, hipMemcpyAsync(h->h_mbox, h->mbox, h->mbox_meta_off + (size_t)n * sizeof(StepMeta), hipMemcpyDeviceToHost, s)); return RNDE_OK; }
+    HIPCHK(h, hipMemcpyAsync(h->h_ctl, h->ctl_final, sizeof(StepState), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(h->h_meta, h->meta, (size_t)n * sizeof(StepMeta), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(h->h_init, h->initrec, sizeof(InitRec), hipMemcpyDeviceToHost, s));
+    return RNDE_OK;
+}
+// The host waits for the copies behind a solve.  Fused training step (after_solve): for the copies only; what the hook queues runs while the host
+// wakes up.  A solve that needs another chunk, or is redone, calls the hook again: it only overwrites its outputs.
+static rnde_status wait_for_host(rnde_node* h, hipStream_t s) {
+    if (h->after_solve) {
+        HIPCHK(h, hipEventRecord(h->ev_host, s));
+        const rnde_status hs = h->after_solve(s);
+        if (hs != RNDE_OK) return hs;
+        HIPCHK(h, hipEventSynchronize(h->ev_host));
+    } else HIPCHK(h, hipStreamSynchronize(s));
+    return RNDE_OK;
+}
+// Behind that wait: did a one-launch kernel give up?  RNDE_ERR_HIP: one of the previous asynchronous backward call did (or may have), whose gradients
+// cannot be trusted; RNDE_INTERNAL_RETRY: a persistent kernel of this solve did, the handle fell back and the solve is to be redone.
+static rnde_status previous_backward_ok(rnde_node* h, hipStream_t s) {
+    if (bsweep_failed(h, s)) { h->err = "the one-launch reverse sweep of the previous asynchronous backward call was abandoned: the gradients of that step are invalid (one launch per reversed attempt now in use)"; return RNDE_ERR_HIP; }
+    if (!persist_check_result(h, h->Bpad / 16, h->sR, s)) return RNDE_OK;
+    if (h->pending_bwd) {   // the failure may belong to the asynchronous reverse pass before this forward: its outputs cannot be trusted
+        h->pending_bwd = false;
+        h->err = "a persistent kernel abandoned its hand-off during or after the previous asynchronous reverse pass: the gradients of that step are invalid (multi-launch kernels now in use)";
+        return RNDE_ERR_HIP;
+    }
+    return RNDE_INTERNAL_RETRY;
+}
+
+struct FwdCall {      // one forward solve: the caller's arguments; what forward_prepare made of them (cap: max_attempts; the one-launch stage solve applies, its start-up and finish run inside it)
+    const float *x_dev, *p_dev; int B; float t0, t1; float* u_out_dev; const float* saveat_host; int n_saveat; float* sv_out_dev; int keep_tape; hipStream_t s;
+    EngineParams E; int cap; bool stage_one_launch, solve_fold;
+};
+// Validation, the tape's copies, the parameter blocks, the pack launch and the launches of the initial-step rule.
+static rnde_status forward_prepare(rnde_node* h, FwdCall& c) {
+    hipStream_t s = c.s;
+    const int B = c.B, keep_tape = c.keep_tape, n_saveat = c.n_saveat;
+    if (n_saveat > 0) {
+        if (h->rk_tab == 2) { h->err = "saveat: this Runge-Kutta table carries no dense output (DOP853)"; return RNDE_ERR_BAD_ARG; }
+        if (!saveat_valid(c.saveat_host, n_saveat, c.t0, c.t1)) { h->err = "saveat must be increasing and inside [t0, t1]"; return RNDE_ERR_BAD_ARG; }
+        HIPCHK(h, h->sv_t_dev.reserve((size_t)n_saveat));
+        h->saveat.assign(c.saveat_host, c.saveat_host + n_saveat);
+        HIPCHK(h, hipMemcpyAsync(h->sv_t_dev, h->saveat.data(), (size_t)n_saveat * 4, hipMemcpyHostToDevice, s));
+    } else h->saveat.clear();
+    if (B < 1 || B > h->cfg.max_batch || !(c.t1 > c.t0)) { h->err = "bad B or tspan"; return RNDE_ERR_BAD_ARG; }
+    // the coupled controller all-reduces per-workgroup partial arrays element by element: every rank must hold the same number of columns
+    if (h->couple && (long long)B * h->couple_world != h->couple_batch) {
+        h->err = "coupled controller: equal shards only (B * world must equal the global batch given to rnde_node_set_coupling)";
+        return RNDE_ERR_BAD_ARG;
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->have_tape = false; h->rev_packed = false; h->x3_packed = false; h->x3_fwd = false;
+    const float* x_dev = c.x_dev;
+    const float* x_caller = nullptr;
+    if (keep_tape) {
+        rnde_status st = ensure_arena(h, h->cfg.max_attempts);
+        if (st != RNDE_OK) return st;
+        // the tape owns copies of x and p (the caller may free or overwrite its buffers before backward)
+        if (B % h->BT) HIPCHK(h, hipMemsetAsync(h->xcopy, 0, (size_t)h->D * (((B + h->BT - 1) / h->BT) * h->BT) * 4, s));
+        if (h->engine != 2) {   // (stage engine: both copies are part of the one pack launch below)
+            HIPCHK(h, hipMemcpyAsync(h->xcopy, x_dev, (size_t)h->D * B * 4, hipMemcpyDeviceToDevice, s));
+            HIPCHK(h, hipMemcpyAsync(h->pcopy, c.p_dev, (size_t)h->P * 4, hipMemcpyDeviceToDevice, s));
+        } else x_caller = x_dev;
+        x_dev = h->xcopy;
+    }
+    StepParams P = make_params(h, x_dev, B, c.t0, c.t1, keep_tape ? 1 : 0);
+    P.sv_t = n_saveat > 0 ? h->sv_t_dev : nullptr; P.nsave = n_saveat; P.sv_out = c.sv_out_dev;
+    if (h->n_replay > 0) {
+        HIPCHK(h, h->replay_dev.reserve((size_t)h->n_replay * 2));
+        HIPCHK(h, hipMemcpyAsync(h->replay_dev, h->replay_host, (size_t)h->n_replay * 8, hipMemcpyHostToDevice, s));
+        P.replay = h->replay_dev; P.n_replay = h->n_replay;
+    }
+    h->B = B; h->Bpad = P.Bpad; h->nwg = P.nwg; h->t0 = c.t0; h->t1 = c.t1;
+    const float* const p_tape = keep_tape ? h->pcopy : c.p_dev;
+    rnde_status st = RNDE_OK;
+    if (h->engine == 2 && keep_tape) st = stage_pack_all(h, c.p_dev, s, x_caller, (long long)h->D * B);   // forward + reverse packs of both engines' layouts and the tape's copy of p: one launch
+    else if (h->engine == 3) st = chain_pack(h, p_tape, s);
+    if (st != RNDE_OK) return st;
+    EngineParams& E = c.E;
+    c.stage_one_launch = c.solve_fold = false;
+    c.cap = h->cfg.max_attempts;
+    if (h->engine == 3 && h->mw && keep_tape) st = ensure_mw_slab(h, 2 + (long long)(h->rk_S - 1) * std::max(4, h->predicted), s);
+    if (h->engine == 2 && !keep_tape) st = stage_pack_weights(h, c.p_dev, s);
+    if (st != RNDE_OK) return st;
+    E = engine_params(h, P, p_tape);
+    if (h->engine == 2) {
+        StageParams& SQ = E.SQ;
+        if (stage_epart_reduce(h, SQ)) SQ.F.esum = (const double*)(h->errpart + 6 * (size_t)h->nwg_max + 256);      // (inside errpart's allocation, 8-byte aligned)
+        // the one-launch solve runs the initial-step rule and the copy-out of the final state inside its own launch; RNDE_SOLVE_FOLD=0, read per
+        // call, keeps the four start-up launches and the finish launch around it (a redo after a time-out takes them too: persist != 1 then)
+        c.stage_one_launch = h->persist == 1 && h->stage_solve && h->s_meet.xch && SQ.C <= 32 && n_saveat == 0 && h->n_replay == 0 && !h->couple &&
+                             stage_fix(h, SQ.WT, SQ.HT, SQ.K2b, SQ.MT, SQ.R);
+        if (c.stage_one_launch) { const char* e = getenv("RNDE_SOLVE_FOLD"); c.solve_fold = !(e && e[0] == '0'); }
+    }
+    if (!c.solve_fold) {      // (coupled controller: the partial norms summed over the ranks behind each half)
+        HIPCHK(h, launch_init(h, E, 0, s));
+        if ((st = couple_sum(h, P.initpart, 2LL * P.nwg, s)) != RNDE_OK) return st;            // norms of u0 and f0
+        HIPCHK(h, launch_init(h, E, 1, s));
+        if ((st = couple_sum(h, P.initpart + 2LL * P.nwg, P.nwg, s)) != RNDE_OK) return st;     // norm of f1 - f0
+    }
+    h->tev_fwd = false;
+    if (h->timing) HIPCHK(h, hipEventRecord(h->tev[0], s));
+    return RNDE_OK;
+}
+
+// The three forms of the solve, one signature: RNDE_OK = solved (the controller state, the step records and the initial-step record are on the
+// host), RNDE_INTERNAL_RETRY = redo the whole call, anything else = the error.
+
+// Chain engine, multi-wave kernels, every workgroup resident (<= 256 column tiles): the WHOLE adaptive solve is one launch (attempt loop,
+// controller and the once-per-attempt meeting of the workgroups inside the kernel).  <= 32 tiles: the workgroups are pinned to one XCD
+// and meet through its L2; more (B > 512, the throughput case): they spread over the chip and meet through agent-scope entries.
+static bool mw_one_launch(const rnde_node* h, const StepParams& P) { return h->engine == 3 && h->mw && h->mw_solve > 0 && !h->couple && P.Bpad / 16 <= kMwMeetMax; }
+static rnde_status solve_mw_one_launch(rnde_node* h, FwdCall& c) {
+    hipStream_t s = c.s;
+    MwParams& MQ = c.E.MQ;
+    const int n_limit = c.keep_tape ? mw_taped_attempt_limit(c.cap, h->predicted) : c.cap;
+    if (c.keep_tape) { const rnde_status st = ensure_mw_slab(h, 2 + (long long)(h->rk_S - 1) * n_limit, s); if (st != RNDE_OK) return st; MQ.slab = h->mw_slab; }
+    MQ.n_limit = n_limit;
+    MQ.meet = h->mw_meet.begin(c.E.P.Bpad / 16, true, s);
+    HIPCHK(h, h->mw_meet.err);
+    MQ.u_out = c.u_out_dev; MQ.xcc = h->mw_meet.xcc; MQ.xcd_slot = h->mw_meet.slot;
+    HIPCHK(h, launch_mw<MW_SOLVE>(h, MQ, 0, s));
+    if (h->timing) { HIPCHK(h, hipEventRecord(h->tev[1], s)); h->tev_fwd = true; }
+    rnde_status st = fetch_log(h, c.cap, s);
+    if (st != RNDE_OK) return st;
+    HIPCHK(h, h->mw_meet.queue_check(MQ.meet, s));
+    st = wait_for_host(h, s);
+    if (st == RNDE_OK) st = previous_backward_ok(h, s);
+    if (st != RNDE_OK) return st;
+    const MeetVerdict verdict = meet_verdict(h->mw_meet.chk, MQ.meet.n, MQ.meet.global != 0);
+    if (verdict != MEET_OK) {      // a meeting timed out, or the workgroups did not share an XCD: this handle goes back to one launch per attempt for the next mw_retry_after solves
+        fprintf(stderr, "[rnde] chain engine: one-launch solve abandoned (%s); one launch per attempted step for the next %d solves\n",
+                verdict == MEET_TIMED_OUT ? "a meeting timed out" : "workgroups pinned by block index landed on different XCDs", h->mw_retry_after);
+        h->mw_solve = -1; h->mw_clean = 0; ++h->persist_fallbacks;
+        h->mw_meet.clear_abort(s);
+        return RNDE_INTERNAL_RETRY;
+    }
+    if (!h->h_ctl->done && h->h_ctl->n_att >= n_limit && n_limit < c.cap) { h->predicted = c.cap; return RNDE_INTERNAL_RETRY; }
+    h->pending_bwd = false;
+    ++h->one_launch_solves;
+    return RNDE_OK;
+}
+
+// Stage engine, headline geometry, all workgroups resident at once (<= 32 column tiles): the WHOLE adaptive solve is one launch
+// (rnde_stage_solve.h: weights, uprev and k1 stay in registers across attempts, the error norm meets through agent-scope granules).
+static rnde_status solve_stage_one_launch(rnde_node* h, FwdCall& c) {
+    hipStream_t s = c.s;
+    const StageParams& SQ = c.E.SQ;
+    PersistSync Y{h->tslab, h->pabort, h->pxcc, h->persist_spins};
+    HIPCHK(h, slab_prepare(h, SQ.Bpad16, s));
+    const Meet SM = h->s_meet.begin(SQ.F.nwg, false, s);      // (the granules and the epoch; the abort word is Y's)
+    HIPCHK(h, h->s_meet.err);
+    const int x3 = h->x3_fwd ? 1 : 0;      // (the weights were split by this forward's pack launch: x3_pack)
+    SolveSync Z{SM.xch, SM.epoch, c.cap, h->x3B, h->x3D, c.solve_fold ? c.u_out_dev : nullptr, c.solve_fold ? 1 : 0};
+#ifdef RNDE_DIAG
+    const StageParams SD = diag_solve_params(h, SQ, s);      // (RNDE_DIAG_SOLVE: with a buffer for the cycle stamps)
+#else
+    const StageParams& SD = SQ;
+#endif
+    HIPCHK(h, rnde_launch_stage_solve(&SD, &Y, &Z, h->act2, x3, s));
+    if (h->timing) { HIPCHK(h, hipEventRecord(h->tev[1], s)); h->tev_fwd = true; }
+    if (!c.solve_fold) HIPCHK(h, launch_finish(h, c.E, -1, c.u_out_dev, s));
+    const int cnt = stage_speculative_records(c.cap, h->predicted);
+    rnde_status st = fetch_log(h, cnt, s);
+    if (st == RNDE_OK) st = wait_for_host(h, s);
+    if (st != RNDE_OK) return st;
+#ifdef RNDE_DIAG
+    diag_solve_report(h, SQ);
+#endif
+    if ((st = previous_backward_ok(h, s)) != RNDE_OK) return st;
+    h->pending_bwd = false;
+    if (h->h_ctl->n_att > cnt) {
+        HIPCHK(h, hipMemcpyAsync(h->h_meta + cnt, h->meta + cnt, (size_t)(h->h_ctl->n_att - cnt) * sizeof(StepMeta), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+    }
+    if (!h->h_ctl->done) { h->err = "max_attempts reached"; h->n_att = h->h_ctl->n_att; return RNDE_ERR_MAX_ATTEMPTS; }
+    ++h->one_launch_solves;
+    return RNDE_OK;
+}
+
+// Every engine: the attempts enqueued in chunks, one launch (stage engine without its persistent kernel: seven) per attempt, the controller state
+// looked at once per chunk.
+static rnde_status solve_chunked(rnde_node* h, FwdCall& c) {
+    hipStream_t s = c.s;
+    EngineParams& E = c.E;
+    const StepParams& P = E.P;
+    const bool mw_taped = h->engine == 3 && h->mw && c.keep_tape;
+    int launched = 0;
+    for (int chunk = first_chunk(h->couple != nullptr, h->predicted);; chunk = later_chunk(h->couple != nullptr)) {
+        rnde_status st = RNDE_OK;
+        if (mw_taped) {   // room in the activation slab for this chunk's evaluations (a regrowth keeps the taped ones)
+            st = ensure_mw_slab(h, 2 + (long long)(h->rk_S - 1) * std::min(c.cap, launched + chunk), s);
+            if (st != RNDE_OK) return st;
+            E.MQ.slab = h->mw_slab;
+        }
+        for (int i = 0; i < chunk && launched < c.cap; ++i) {
+#ifdef RNDE_DIAG
+            if (diag_fwd_wants(h, launched)) HIPCHK(h, launch_attempt(h, diag_fwd_params(h, E, s), launched, s)); else      // (RNDE_DIAG_FWD: cycle stamps of THIS attempt of a real solve)
+#endif
+            HIPCHK(h, launch_attempt(h, E, launched, s));
+            if ((st = couple_sum(h, P.errpart + (size_t)(launched & 1) * 3 * P.nwg, 3LL * P.nwg, s)) != RNDE_OK) return st;
+            if (h->engine == 2 && E.SQ.F.esum) { hipLaunchKernelGGL(rnde_epart_reduce_kernel, dim3(1), dim3(64), 0, s, E.SQ.F, launched, (double*)E.SQ.F.esum); HIPCHK(h, hipGetLastError()); }
+            ++launched;
+        }
+        if (h->timing && !h->tev_fwd) { HIPCHK(h, hipEventRecord(h->tev[1], s)); h->tev_fwd = true; }   // (first chunk: normally the whole solve)
+        HIPCHK(h, launch_finish(h, E, launched, c.u_out_dev, s));
+        // one synchronisation per chunk: controller state, the persistent kernels' health words, and (speculatively: the solve
+        // usually ends in the first chunk) the step metadata and the initial-step record the epilogue needs
+        if ((st = fetch_log(h, launched, s)) != RNDE_OK || (st = wait_for_host(h, s)) != RNDE_OK) return st;
+#ifdef RNDE_DIAG
+        diag_fwd_report(h);
+#endif
+        if (h->couple && rnde_comm_health(h->couple) != RNDE_OK) { h->err = std::string("coupled controller: ") + rnde_comm_last_error(h->couple); return RNDE_ERR_HIP; }
+        st = previous_backward_ok(h, s);
+        if (st == RNDE_INTERNAL_RETRY && h->couple) {   // a redo on this rank alone would leave the ranks' all-reduce sequences out of step
+            h->err = "coupled controller: a persistent kernel abandoned its hand-off; the ranks are out of step -- use cfg.persist = -1 (7-launch kernels) with rnde_node_set_coupling where other work shares the GPU";
+            return RNDE_ERR_HIP;
+        }
+        if (st != RNDE_OK) return st;
+        h->pending_bwd = false;
+        if (h->h_ctl->done) return RNDE_OK;
+        if (launched >= c.cap) { h->err = "max_attempts reached"; h->n_att = h->h_ctl->n_att; return RNDE_ERR_MAX_ATTEMPTS; }
+    }
+}
+
+// Attempt count and prediction, the two retry windows, NFE, the saved values, the controller's status.
+static rnde_status forward_epilogue(rnde_node* h, const FwdCall& c, int64_t* nfe_out, float* saveval_host, int32_t* n_saveval_out) {
+    h->n_att = h->h_ctl->n_att;
+    h->predicted = h->n_att + 1;
+    // a hand-off time-out (a co-tenant held CUs for a second, e.g. another process's kernels) must not halve the speed for good:
+    // after `persist_retry_after` clean multi-launch solves the one-launch kernels get another chance; each new failure doubles the wait
+    if (h->engine == 3 && (h->mw_solve == -1 || h->mw_bsweep == -1) && ++h->mw_clean >= h->mw_retry_after) {      // the same for the chain engine's one-launch kernels
+        if (h->mw_solve == -1) h->mw_solve = 1;
+        if (h->mw_bsweep == -1) h->mw_bsweep = 1;
+        h->mw_retry_after = next_retry_window(h->mw_retry_after);
+        h->mw_meet.slot = (h->mw_meet.slot + 1) & 7;                                           // (and another XCD: the one it was pinned to may be the contended one)
+    }
+    if (h->persist == -1 && h->engine == 2 && h->cfg.persist >= 0 && ++h->persist_clean >= h->persist_retry_after) {
+        h->persist = 1; h->persist_retry_after = next_retry_window(h->persist_retry_after);
+        h->tslab_Bpad = -1;                          // slabs are refilled with the empty pattern before the next persistent launch
+    }
+    if (nfe_out) *nfe_out = solve_nfe(h->rk_S, h->n_att);
+    h->sv_index.assign(h->n_att, -1);
+    h->n_saveval = gather_saved_values(h->h_meta, h->n_att, F_ACCEPT, h->cfg.regularize, h->cfg.cb_save_start != 0, h->sv_index.data(), saveval_host);
+    if (n_saveval_out) *n_saveval_out = h->n_saveval;
+    switch (h->h_ctl->status) {
+        case 0: break;
+        case 2: h->err = "max_attempts reached"; return RNDE_ERR_MAX_ATTEMPTS;
+        case 3: h->err = "dt underflow"; return RNDE_ERR_DT_UNDERFLOW;
+        default: h->err = "non-finite error estimate or dt"; return RNDE_ERR_NONFINITE;
+    }
+    h->have_tape = c.keep_tape != 0;
+    return RNDE_OK;
+}
+
+static rnde_status forward_core(rnde_node* h, FwdCall& c, int64_t* nfe_out, float* saveval_host, int32_t* n_saveval_out) {
+    rnde_status st = forward_prepare(h, c);
+    if (st == RNDE_OK) st = mw_one_launch(h, c.E.P) ? solve_mw_one_launch(h, c) : (c.stage_one_launch ? solve_stage_one_launch(h, c) : solve_chunked(h, c));
+    return st != RNDE_OK ? st : forward_epilogue(h, c, nfe_out, saveval_host, n_saveval_out);
+}
+
 rnde_status forward_impl(rnde_node* h, const float* x_dev, const float* p_dev, int32_t B, float t0, float t1,
                                 float* u_out_dev, const float* saveat_host, int32_t n_saveat, float* sv_out_dev,
                                 int64_t* nfe_out, float* saveval_host, int32_t* n_saveval_out, int32_t keep_tape, void* stream) {
-    if (h && h->engine == 4) return node_tiled_forward(h, x_dev, p_dev, B, t0, t1, u_out_dev, saveat_host, n_saveat, sv_out_dev, nfe_out, saveval_host, n_saveval_out, keep_tape, stream);
+    if (!h) return RNDE_ERR_BAD_ARG;
+    if (h->engine == 4) return node_tiled_forward(h, x_dev, p_dev, B, t0, t1, u_out_dev, saveat_host, n_saveat, sv_out_dev, nfe_out, saveval_host, n_saveval_out, keep_tape, stream);
+    FwdCall c{x_dev, p_dev, B, t0, t1, u_out_dev, saveat_host, n_saveat, sv_out_dev, keep_tape, (hipStream_t)stream, {}, 0, false, false};
     // a solve may ask to be redone for two independent reasons (the record slab has to grow; a one-launch kernel gave up and the handle fell back):
     // both can happen back to back, each at most once per cause -- anything beyond that is an error, not a status the caller should ever see
     rnde_status st = RNDE_INTERNAL_RETRY;
-    for (int tries = 0; tries < 4 && st == RNDE_INTERNAL_RETRY; ++tries)
-        st = forward_core(h, x_dev, p_dev, B, t0, t1, u_out_dev, saveat_host, n_saveat, sv_out_dev, nfe_out, saveval_host, n_saveval_out, keep_tape, stream);
+    for (int tries = 0; tries < 4 && st == RNDE_INTERNAL_RETRY; ++tries) st = forward_core(h, c, nfe_out, saveval_host, n_saveval_out);
     if (st == RNDE_INTERNAL_RETRY) { h->err = "the forward solve asked to be redone four times in a row (one-launch fallbacks and slab growth): giving up"; st = RNDE_ERR_HIP; }
     return st;
 }
@@ -661,334 +953,6 @@ extern "C" rnde_status rnde_debug_arm_replay(rnde_node* h, const float* steps_ho
     return RNDE_OK;
 }
 
-static rnde_status forward_core(rnde_node* h, const float* x_dev, const float* p_dev, int32_t B, float t0, float t1,
-                                float* u_out_dev, const float* saveat_host, int32_t n_saveat, float* sv_out_dev,
-                                int64_t* nfe_out, float* saveval_host, int32_t* n_saveval_out, int32_t keep_tape, void* stream) {
-    if (!h) return RNDE_ERR_BAD_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    if (n_saveat > 0) {
-        if (h->rk_tab == 2) { h->err = "saveat: this Runge-Kutta table carries no dense output (DOP853)"; return RNDE_ERR_BAD_ARG; }
-        for (int i = 0; i < n_saveat; ++i)
-            if (!(saveat_host[i] >= t0 && saveat_host[i] <= t1) || (i > 0 && !(saveat_host[i] > saveat_host[i - 1]))) {
-                h->err = "saveat must be increasing and inside [t0, t1]"; return RNDE_ERR_BAD_ARG;
-            }
-        HIPCHK(h, h->sv_t_dev.reserve((size_t)n_saveat));
-        h->saveat.assign(saveat_host, saveat_host + n_saveat);
-        HIPCHK(h, hipMemcpyAsync(h->sv_t_dev, h->saveat.data(), (size_t)n_saveat * 4, hipMemcpyHostToDevice, s));
-    } else h->saveat.clear();
-    if (B < 1 || B > h->cfg.max_batch || !(t1 > t0)) { h->err = "bad B or tspan"; return RNDE_ERR_BAD_ARG; }
-    // the coupled controller all-reduces per-workgroup partial arrays element by element: every rank must hold the same number of columns
-    if (h->couple && (long long)B * h->couple_world != h->couple_batch) {
-        h->err = "coupled controller: equal shards only (B * world must equal the global batch given to rnde_node_set_coupling)";
-        return RNDE_ERR_BAD_ARG;
-    }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->have_tape = false; h->rev_packed = false; h->x3_packed = false; h->x3_fwd = false;
-    const float* x_caller = nullptr;
-    if (keep_tape) {
-        rnde_status st = ensure_arena(h, h->cfg.max_attempts);
-        if (st != RNDE_OK) return st;
-        // the tape owns copies of x and p (the caller may free or overwrite its buffers before backward)
-        if (B % h->BT) HIPCHK(h, hipMemsetAsync(h->xcopy, 0, (size_t)h->D * (((B + h->BT - 1) / h->BT) * h->BT) * 4, s));
-        if (h->engine != 2) {   // (stage engine: both copies are part of the one pack launch below)
-            HIPCHK(h, hipMemcpyAsync(h->xcopy, x_dev, (size_t)h->D * B * 4, hipMemcpyDeviceToDevice, s));
-            HIPCHK(h, hipMemcpyAsync(h->pcopy, p_dev, (size_t)h->P * 4, hipMemcpyDeviceToDevice, s));
-        } else x_caller = x_dev;
-        x_dev = h->xcopy;
-    }
-    StepParams P = make_params(h, x_dev, B, t0, t1, keep_tape ? 1 : 0);
-    P.sv_t = n_saveat > 0 ? h->sv_t_dev : nullptr; P.nsave = n_saveat; P.sv_out = sv_out_dev;
-    if (h->n_replay > 0) {
-        HIPCHK(h, h->replay_dev.reserve((size_t)h->n_replay * 2));
-        HIPCHK(h, hipMemcpyAsync(h->replay_dev, h->replay_host, (size_t)h->n_replay * 8, hipMemcpyHostToDevice, s));
-        P.replay = h->replay_dev; P.n_replay = h->n_replay;
-    }
-    h->B = B; h->Bpad = P.Bpad; h->nwg = P.nwg; h->t0 = t0; h->t1 = t1;
-    rnde_status st = RNDE_OK;
-    if (h->engine == 2 && keep_tape) st = stage_pack_all(h, p_dev, s, x_caller, (long long)h->D * B);   // forward + reverse packs of both engines' layouts and the tape's copy of p: one launch
-    else if (h->engine == 3) st = chain_pack(h, keep_tape ? h->pcopy : p_dev, s);
-    if (st != RNDE_OK) return st;
-    StageParams SQ{};
-    ChainParams CQ{};
-    MwParams MQ{};
-    bool stage_one_launch = false, solve_fold = false;
-    if (h->engine == 3) {
-        CQ = make_chain_params(h, P);
-        if (h->mw) {
-            if (keep_tape) { st = ensure_mw_slab(h, 2 + (long long)(h->rk_S - 1) * std::max(4, h->predicted), P.Bpad, s); if (st != RNDE_OK) return st; }
-            MQ = make_mw_params(h, P);
-            HIPCHK(h, launch_mw<MW_INIT_A>(h, MQ, 0, s));
-            if ((st = couple_sum(h, P.initpart, 2LL * P.nwg, s)) != RNDE_OK) return st;            // (coupled controller: norms of u0 and f0)
-            HIPCHK(h, launch_mw<MW_INIT_B>(h, MQ, 0, s));
-            if ((st = couple_sum(h, P.initpart + 2LL * P.nwg, P.nwg, s)) != RNDE_OK) return st;     // norm of f1 - f0
-        } else {
-            HIPCHK(h, launch_chain<CM_INIT_A>(h, CQ, 0, nullptr, s));
-            HIPCHK(h, launch_chain<CM_INIT_B>(h, CQ, 0, nullptr, s));
-        }
-    } else if (h->engine == 2) {
-        if (!keep_tape) { st = stage_pack_weights(h, p_dev, s); if (st != RNDE_OK) return st; }
-        SQ = make_stage_params(h, P, keep_tape ? h->pcopy : p_dev);
-        if (stage_epart_reduce(h, SQ)) SQ.F.esum = (const double*)(h->errpart + 6 * (size_t)h->nwg_max + 256);      // (inside errpart's allocation, 8-byte aligned)
-        // the one-launch solve (below) runs the initial-step rule and the copy-out of the final state inside its own launch; RNDE_SOLVE_FOLD=0,
-        // read per call, keeps the four start-up launches and the finish launch around it (a redo after a time-out takes them too: persist != 1 then)
-        stage_one_launch = h->persist == 1 && h->stage_solve && h->s_meet.xch && SQ.C <= 32 && n_saveat == 0 && h->n_replay == 0 && !h->couple &&
-                           SQ.WT == 7 && SQ.HT == 7 && SQ.K2b == 7 && SQ.MT == 49 && SQ.R == 7 && h->D == 784 && h->H == 100 && !h->stage_generic;
-        if (stage_one_launch) { const char* e = getenv("RNDE_SOLVE_FOLD"); solve_fold = !(e && e[0] == '0'); }
-        if (!solve_fold) {
-            HIPCHK(h, launch_stage<SM_I1>(h, SQ, 0, 0, s));
-            HIPCHK(h, launch_stage<SM_I2>(h, SQ, 0, 0, s));
-            if ((st = couple_sum(h, P.initpart, 2LL * P.nwg, s)) != RNDE_OK) return st;            // norms of u0 and f0
-            HIPCHK(h, launch_stage<SM_I3>(h, SQ, 0, 0, s));
-            HIPCHK(h, launch_stage<SM_I4>(h, SQ, 0, 0, s));
-            if ((st = couple_sum(h, P.initpart + 2LL * P.nwg, P.nwg, s)) != RNDE_OK) return st;     // norm of f1 - f0
-        }
-    }
-    int launched = 0;
-    int chunk = h->couple ? 16 : std::max(4, h->predicted);   // (coupled: the same launch count on every rank, whatever its history)
-    const int cap = h->cfg.max_attempts;
-    h->tev_fwd = false;
-    if (h->timing) HIPCHK(h, hipEventRecord(h->tev[0], s));
-    // ---- chain engine, multi-wave kernels, every workgroup resident (<= 256 column tiles): the WHOLE adaptive solve is one launch (attempt loop,
-    // ---- controller and the once-per-attempt meeting of the workgroups inside the kernel).  <= 32 tiles: the workgroups are pinned to one XCD
-    // ---- and meet through its L2; more (B > 512, the throughput case): they spread over the chip and meet through agent-scope entries ----
-    bool solved = false;
-    if (h->engine == 3 && h->mw && h->mw_solve > 0 && !h->couple && P.Bpad / 16 <= kMwMeetMax) {
-        // a taped solve writes every layer input of every evaluation: the slab is sized for twice the last solve's attempts (at least 48); a solve
-        // that needs more ends at that limit and is redone with room for max_attempts
-        const int n_limit = keep_tape ? std::min(cap, std::max(48, 2 * h->predicted)) : cap;
-        if (keep_tape) { st = ensure_mw_slab(h, 2 + (long long)(h->rk_S - 1) * n_limit, P.Bpad, s); if (st != RNDE_OK) return st; MQ.slab = h->mw_slab; }
-        MQ.n_limit = n_limit;
-        MQ.meet = h->mw_meet.begin(P.Bpad / 16, true, s);
-        HIPCHK(h, h->mw_meet.err);
-        MQ.u_out = u_out_dev; MQ.xcc = h->mw_meet.xcc; MQ.xcd_slot = h->mw_meet.slot;
-        HIPCHK(h, launch_mw<MW_SOLVE>(h, MQ, 0, s));
-        if (h->timing) { HIPCHK(h, hipEventRecord(h->tev[1], s)); h->tev_fwd = true; }
-        HIPCHK(h, hipMemcpyAsync(h->h_ctl, h->ctl_final, sizeof(StepState), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(h->h_meta, h->meta, (size_t)cap * sizeof(StepMeta), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(h->h_init, h->initrec, sizeof(InitRec), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, h->mw_meet.queue_check(MQ.meet, s));
-        if (h->after_solve) {
-            HIPCHK(h, hipEventRecord(h->ev_host, s));
-            const rnde_status hs = h->after_solve(s);
-            if (hs != RNDE_OK) return hs;
-            HIPCHK(h, hipEventSynchronize(h->ev_host));
-        } else HIPCHK(h, hipStreamSynchronize(s));
-        if (bsweep_failed(h, s)) { h->err = "the one-launch reverse sweep of the previous asynchronous backward call was abandoned: the gradients of that step are invalid (one launch per reversed attempt now in use)"; return RNDE_ERR_HIP; }
-        const MeetVerdict verdict = meet_verdict(h->mw_meet.chk, MQ.meet.n, MQ.meet.global != 0);
-        if (verdict != MEET_OK) {      // a meeting timed out, or the workgroups did not share an XCD: this handle goes back to one launch per attempt for the next mw_retry_after solves
-            fprintf(stderr, "[rnde] chain engine: one-launch solve abandoned (%s); one launch per attempted step for the next %d solves\n",
-                    verdict == MEET_TIMED_OUT ? "a meeting timed out" : "workgroups pinned by block index landed on different XCDs", h->mw_retry_after);
-            h->mw_solve = -1; h->mw_clean = 0; ++h->persist_fallbacks;
-            h->mw_meet.clear_abort(s);
-            return RNDE_INTERNAL_RETRY;
-        }
-        if (!h->h_ctl->done && h->h_ctl->n_att >= n_limit && n_limit < cap) { h->predicted = cap; return RNDE_INTERNAL_RETRY; }
-        h->pending_bwd = false;
-        ++h->one_launch_solves;
-        solved = true;
-    }
-    // ---- stage engine, headline geometry, all workgroups resident at once (<= 32 column tiles): the WHOLE adaptive solve is one launch
-    // ---- (rnde_stage_solve.h: weights, uprev and k1 stay in registers across attempts, the error norm meets through agent-scope granules) ----
-    if (stage_one_launch) {
-        PersistSync Y{h->tslab, h->pabort, h->pxcc, h->persist_spins};
-        HIPCHK(h, slab_prepare(h, SQ.Bpad16, s));
-        const Meet SM = h->s_meet.begin(SQ.F.nwg, false, s);      // (the granules and the epoch; the abort word is Y's)
-        HIPCHK(h, h->s_meet.err);
-        const int x3 = h->x3_fwd ? 1 : 0;      // (the weights were split by this forward's pack launch: x3_pack)
-        SolveSync Z{SM.xch, SM.epoch, cap, h->x3B, h->x3D, solve_fold ? u_out_dev : nullptr, solve_fold ? 1 : 0};
-#ifdef RNDE_DIAG
-        StageParams SD = SQ;
-        if (getenv("RNDE_DIAG_SOLVE")) {      // cycle stamps of workgroup 0, every attempt (tools/diag_solve.py)
-            h->diag_buf.reset();
-            (void)h->diag_buf.alloc(4096);
-            hipMemsetAsync(h->diag_buf, 0, 16384, s);
-            SD.F.dbg_out = h->diag_buf;
-        }
-        HIPCHK(h, rnde_launch_stage_solve(&SD, &Y, &Z, h->act2, x3, s));
-#else
-        HIPCHK(h, rnde_launch_stage_solve(&SQ, &Y, &Z, h->act2, x3, s));
-#endif
-        if (h->timing) { HIPCHK(h, hipEventRecord(h->tev[1], s)); h->tev_fwd = true; }
-        if (!solve_fold) { hipLaunchKernelGGL(rnde_stage_finish_kernel, dim3(256), dim3(256), 0, s, SQ, -1, u_out_dev); HIPCHK(h, hipGetLastError()); }
-        const int cnt = std::min(cap, std::max(64, 2 * h->predicted));      // step records copied speculatively; a longer solve fetches the rest below
-        HIPCHK(h, hipMemcpyAsync(h->h_mbox, h->mbox, h->mbox_meta_off + (size_t)cnt * sizeof(StepMeta), hipMemcpyDeviceToHost, s));
-        if (h->after_solve) {
-            HIPCHK(h, hipEventRecord(h->ev_host, s));
-            const rnde_status hs = h->after_solve(s);
-            if (hs != RNDE_OK) return hs;
-            HIPCHK(h, hipEventSynchronize(h->ev_host));
-        } else HIPCHK(h, hipStreamSynchronize(s));
-#ifdef RNDE_DIAG
-        if (getenv("RNDE_DIAG_SOLVE") && h->diag_buf) {
-            static unsigned long long hst[1024];
-            hipMemcpy(hst, h->diag_buf, 8192, hipMemcpyDeviceToHost);
-            int na = 0; while (na < 119 && hst[(na + 1) * 8]) ++na;      // attempts with a successor
-            double acc[7] = {0}; int cnt = 0;
-            for (int a = 2; a + 1 < na; ++a, ++cnt) {
-                const unsigned long long* q = hst + a * 8;
-                acc[0] += (double)(q[1] - q[0]); acc[1] += (double)(q[2] - q[1]); acc[2] += (double)(q[3] - q[2]); acc[3] += (double)(q[4] - q[3]);
-                acc[4] += (double)(q[5] - q[4]); acc[5] += (double)(q[6] - q[5]); acc[6] += (double)(q[8] - q[0]);
-            }
-            static unsigned long long arr[512];
-            hipMemcpy(arr, (char*)h->diag_buf + 8192, 4096, hipMemcpyDeviceToHost);
-            {   // arrival spread and exchange latency of the meeting of attempt 10, all workgroups (100 MHz wall clock: 10 ns units)
-                std::vector<long long> a, o; const int nw = SQ.C * SQ.R;
-                for (int i = 0; i < nw && i < 256; ++i) if (arr[2 * i]) { a.push_back((long long)arr[2 * i]); o.push_back((long long)arr[2 * i + 1]); }
-                if (a.size() > 4) {
-                    std::vector<long long> sa = a; std::sort(sa.begin(), sa.end());
-                    const long long last = sa.back(), first = sa.front();
-                    std::vector<long long> so = o; std::sort(so.begin(), so.end());
-                    fprintf(stderr, "meeting of attempt 10, %zu workgroups (x10 ns): arrivals after the first: median %lld, 90%% %lld, last %lld | out after the LAST arrival: first %lld, median %lld, last %lld\n",
-                            a.size(), sa[sa.size() / 2] - first, sa[sa.size() * 9 / 10] - first, last - first, so.front() - last, so[so.size() / 2] - last, so.back() - last);
-                    int late[7] = {0}; for (size_t i = 0; i < a.size(); ++i) if (a[i] - first > (last - first) * 3 / 4) ++late[(i / SQ.C) % 7];
-                    fprintf(stderr, "  latest quarter of the spread by row block: %d %d %d %d %d %d %d\n", late[0], late[1], late[2], late[3], late[4], late[5], late[6]);
-                }
-            }
-            if (cnt) fprintf(stderr, "one-launch solve, workgroup 0, mean over %d attempts (cycles): controller %.0f | START %.0f | stages 1-6 %.0f | reduce + barrier %.0f | "
-                                     "meeting %.0f | barrier %.0f | attempt %.0f\n", cnt, acc[0] / cnt, acc[1] / cnt, acc[2] / cnt, acc[3] / cnt, acc[4] / cnt, acc[5] / cnt, acc[6] / cnt);
-        }
-#endif
-        if (persist_check_result(h, SQ.C, SQ.R, s)) {
-            if (h->pending_bwd) {
-                h->pending_bwd = false;
-                h->err = "a persistent kernel abandoned its hand-off during or after the previous asynchronous reverse pass: the gradients of that step are invalid (multi-launch kernels now in use)";
-                return RNDE_ERR_HIP;
-            }
-            return RNDE_INTERNAL_RETRY;
-        }
-        h->pending_bwd = false;
-        if (h->h_ctl->n_att > cnt) {
-            HIPCHK(h, hipMemcpyAsync(h->h_meta + cnt, h->meta + cnt, (size_t)(h->h_ctl->n_att - cnt) * sizeof(StepMeta), hipMemcpyDeviceToHost, s));
-            HIPCHK(h, hipStreamSynchronize(s));
-        }
-        if (!h->h_ctl->done) { h->err = "max_attempts reached"; h->n_att = h->h_ctl->n_att; return RNDE_ERR_MAX_ATTEMPTS; }
-        ++h->one_launch_solves;
-        solved = true;
-    }
-    while (!solved) {
-        if (h->engine == 3 && h->mw && keep_tape) {   // room in the activation slab for this chunk's evaluations (a regrowth keeps the taped ones)
-            st = ensure_mw_slab(h, 2 + (long long)(h->rk_S - 1) * std::min(cap, launched + chunk), P.Bpad, s);
-            if (st != RNDE_OK) return st;
-            MQ.slab = h->mw_slab;
-        }
-        for (int i = 0; i < chunk && launched < cap; ++i) {
-            if (h->engine == 3 && h->mw) HIPCHK(h, launch_mw<MW_STEP>(h, MQ, launched, s));
-            else if (h->engine == 3) HIPCHK(h, launch_chain<CM_STEP>(h, CQ, launched, nullptr, s));
-            else if (h->engine == 2) {
-#ifdef RNDE_DIAG
-                static const int diag_n = getenv("RNDE_DIAG_FWD") ? atoi(getenv("RNDE_DIAG_FWD")) : -1;   // cycle stamps of THIS attempt of a real solve
-                if (launched == diag_n) {
-                    (void)h->diag_buf.reserve(2048);
-                    hipMemsetAsync(h->diag_buf, 0, 8192, s);
-                    StageParams SD = SQ; SD.F.dbg_out = h->diag_buf;
-                    HIPCHK(h, stage_attempt(h, SD, launched, s));
-                } else
-#endif
-                HIPCHK(h, stage_attempt(h, SQ, launched, s));
-            }
-            if ((st = couple_sum(h, P.errpart + (size_t)(launched & 1) * 3 * P.nwg, 3LL * P.nwg, s)) != RNDE_OK) return st;
-            if (h->engine == 2 && SQ.F.esum) { hipLaunchKernelGGL(rnde_epart_reduce_kernel, dim3(1), dim3(64), 0, s, SQ.F, launched, (double*)SQ.F.esum); HIPCHK(h, hipGetLastError()); }
-            ++launched;
-        }
-        if (h->timing && !h->tev_fwd) { HIPCHK(h, hipEventRecord(h->tev[1], s)); h->tev_fwd = true; }   // (first chunk: normally the whole solve)
-        if (h->engine == 3 && h->mw) { MQ.u_out = u_out_dev; HIPCHK(h, launch_mw<MW_FINISH>(h, MQ, launched, s)); }
-        else if (h->engine == 3) HIPCHK(h, launch_chain<CM_FINISH>(h, CQ, launched, u_out_dev, s));
-        else { hipLaunchKernelGGL(rnde_stage_finish_kernel, dim3(256), dim3(256), 0, s, SQ, launched, u_out_dev); HIPCHK(h, hipGetLastError()); }
-        // one synchronisation per chunk: controller state, the persistent kernels' health words, and (speculatively: the solve
-        // usually ends in the first chunk) the step metadata and the initial-step record the epilogue needs
-        if (h->mbox) {
-            HIPCHK(h, hipMemcpyAsync(h->h_mbox, h->mbox, h->mbox_meta_off + (size_t)launched * sizeof(StepMeta), hipMemcpyDeviceToHost, s));
-        } else {
-            HIPCHK(h, hipMemcpyAsync(h->h_ctl, h->ctl_final, sizeof(StepState), hipMemcpyDeviceToHost, s));
-            HIPCHK(h, hipMemcpyAsync(h->h_meta, h->meta, (size_t)launched * sizeof(StepMeta), hipMemcpyDeviceToHost, s));
-            HIPCHK(h, hipMemcpyAsync(h->h_init, h->initrec, sizeof(InitRec), hipMemcpyDeviceToHost, s));
-        }
-        if (h->after_solve) {   // (fused training step) wait for the copy only; what the hook queues runs while the host wakes up.  A solve that
-            HIPCHK(h, hipEventRecord(h->ev_host, s));   // needs another chunk, or is redone, calls the hook again: it only overwrites its outputs
-            const rnde_status hs = h->after_solve(s);
-            if (hs != RNDE_OK) return hs;
-            HIPCHK(h, hipEventSynchronize(h->ev_host));
-        } else HIPCHK(h, hipStreamSynchronize(s));
-#ifdef RNDE_DIAG
-        if (h->engine == 2 && getenv("RNDE_DIAG_FWD") && h->diag_buf) {
-            unsigned long long hst[64] = {0};
-            hipMemcpy(hst, h->diag_buf, sizeof(hst), hipMemcpyDeviceToHost);
-            if (hst[34]) {
-                fprintf(stderr, "attempt %s of a real solve (workgroup 0 thread 0, cycles): controller %lld startC %lld startD %lld |", getenv("RNDE_DIAG_FWD"), (long long)(hst[1]-hst[0]), (long long)(hst[2]-hst[1]), (long long)(hst[3]-hst[2]));
-                for (int st_ = 0; st_ < 6; ++st_) fprintf(stderr, " poll %lld", (long long)(hst[4 + 5 * st_] - hst[3 + 5 * st_]));
-                fprintf(stderr, " | total %lld  (entry -> all loads issued %lld, -> controller state here %lld)\n", (long long)(hst[34]-hst[0]), (long long)(hst[35]-hst[0]), (long long)(hst[36]-hst[35]));
-            }
-        }
-#endif
-        if (h->couple && rnde_comm_health(h->couple) != RNDE_OK) { h->err = std::string("coupled controller: ") + rnde_comm_last_error(h->couple); return RNDE_ERR_HIP; }
-        if (bsweep_failed(h, s)) { h->err = "the one-launch reverse sweep of the previous asynchronous backward call was abandoned: the gradients of that step are invalid (one launch per reversed attempt now in use)"; return RNDE_ERR_HIP; }
-        if (h->engine == 2 && persist_check_result(h, SQ.C, SQ.R, s)) {
-            if (h->pending_bwd) {   // the failure may belong to the asynchronous reverse pass before this forward: its outputs cannot be trusted
-                h->pending_bwd = false;
-                h->err = "a persistent kernel abandoned its hand-off during or after the previous asynchronous reverse pass: the gradients of that step are invalid (multi-launch kernels now in use)";
-                return RNDE_ERR_HIP;
-            }
-            if (h->couple) {   // a redo on this rank alone would leave the ranks' all-reduce sequences out of step
-                h->err = "coupled controller: a persistent kernel abandoned its hand-off; the ranks are out of step -- use cfg.persist = -1 (7-launch kernels) with rnde_node_set_coupling where other work shares the GPU";
-                return RNDE_ERR_HIP;
-            }
-            return RNDE_INTERNAL_RETRY;
-        }
-        h->pending_bwd = false;
-        if (h->h_ctl->done) break;
-        if (launched >= cap) { h->err = "max_attempts reached"; h->n_att = h->h_ctl->n_att; return RNDE_ERR_MAX_ATTEMPTS; }
-        chunk = h->couple ? 16 : 4;
-    }
-    h->n_att = h->h_ctl->n_att;
-    h->predicted = h->n_att + 1;
-    // a hand-off time-out (a co-tenant held CUs for a second, e.g. another process's kernels) must not halve the speed for good:
-    // after `persist_retry_after` clean multi-launch solves the one-launch kernels get another chance; each new failure doubles the wait
-    if (h->engine == 3 && (h->mw_solve == -1 || h->mw_bsweep == -1) && ++h->mw_clean >= h->mw_retry_after) {      // the same for the chain engine's one-launch kernels
-        if (h->mw_solve == -1) h->mw_solve = 1;
-        if (h->mw_bsweep == -1) h->mw_bsweep = 1;
-        h->mw_retry_after = std::min(1024, 2 * h->mw_retry_after);
-        h->mw_meet.slot = (h->mw_meet.slot + 1) & 7;                                           // (and another XCD: the one it was pinned to may be the contended one)
-    }
-    if (h->persist == -1 && h->engine == 2 && h->cfg.persist >= 0 && ++h->persist_clean >= h->persist_retry_after) {
-        h->persist = 1; h->persist_retry_after = std::min(1024, 2 * h->persist_retry_after);
-        h->tslab_Bpad = -1;                          // slabs are refilled with the empty pattern before the next persistent launch
-    }
-    if (nfe_out) *nfe_out = 3 + (int64_t)(h->rk_S - 1) * h->n_att;  // 2 (initial dt) + 1 (fsalfirst) + 6 per attempt (S - 1 for an S-stage table), SURVEY.md B.1-B.2
-    // saving callback values (reference neural_ode.jl:116,:126-127): EEst*dt per accepted step
-    int nsv = 0;
-    h->sv_index.assign(h->n_att, -1);
-    // func(u, t, integrator) of the reference: EEst*dt (mnist_node.jl:67), stab*|eigen_est| (:74-79), their blend (:88-97)
-    const float stab = 1.0f / 3.5068f;   // 1 / alg_stability_size(Tsit5()), as recalled in SURVEY.md 8a row a9
-    auto cbval = [&](float eest, float dt, float eig) -> float {
-        const bool eg_ok = !(eig == 0.f || eig != eig);
-        switch (h->cfg.regularize) {
-            case RNDE_REG_ERR: return eest * dt;
-            case RNDE_REG_STIFF: return eg_ok ? stab * fabsf(eig) : 0.f;
-            case RNDE_REG_ERR_STIFF: { const float e = eest * dt; return ((e == 0.f || e != e) ? 0.f : e) + 0.1f * (eg_ok ? stab * eig : 0.f); }
-            case RNDE_REG_STIFF_DT: return fabsf(eig * dt);      // test/test_node.jl:75: abs(integrator.eigen_est * integrator.dt)
-            default: return 0.f;
-        }
-    };
-    if (h->cfg.regularize != RNDE_REG_NONE) {
-        if (h->cfg.cb_save_start) { if (saveval_host) saveval_host[nsv] = cbval(1.f, 0.f, 1.f); ++nsv; }   // EEst = 1, dt = 0, eigen_est = 1 at init
-        for (int i = 0; i < h->n_att; ++i)
-            if (h->h_meta[i].flags & F_ACCEPT) {
-                if (saveval_host) saveval_host[nsv] = cbval(h->h_meta[i].eest, h->h_meta[i].dt, h->h_meta[i].eigen);
-                h->sv_index[i] = nsv++;
-            }
-    }
-    h->n_saveval = nsv;
-    if (n_saveval_out) *n_saveval_out = nsv;
-    switch (h->h_ctl->status) {
-        case 0: break;
-        case 2: h->err = "max_attempts reached"; return RNDE_ERR_MAX_ATTEMPTS;
-        case 3: h->err = "dt underflow"; return RNDE_ERR_DT_UNDERFLOW;
-        default: h->err = "non-finite error estimate or dt"; return RNDE_ERR_NONFINITE;
-    }
-    h->have_tape = keep_tape != 0;
-    return RNDE_OK;
-}
-
 // save_everystep = true (reference src/models/neural_ode.jl:10-11: return_multiple = save_everystep || saveat): the state after every ACCEPTED step.
 // Which times those are is known only after the solve, so the call runs it twice -- once untaped for the step sequence, once with the accepted
 // step ends (and t0, if asked) as save times: the value saved at a step's end is u_new itself, no interpolation (dense_points, rnde_stage.h),
@@ -1002,12 +966,7 @@ extern "C" rnde_status rnde_node_forward_everystep(rnde_node* h, const float* x_
         RNDE_TILED_REFUSE(h, "rnde_node_forward_everystep is not served (the end state only; save_everystep runs on the engines of rnde_node_create)");
     rnde_status st = forward_impl(h, x_dev, p_dev, B, t0, t1, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, stream);
     if (st != RNDE_OK) return st;
-    std::vector<float> times;
-    if (save_start) times.push_back(t0);
-    for (int i = 0; i < h->n_att; ++i) {
-        const StepMeta& m = h->h_meta[i];
-        if (m.flags & F_ACCEPT) { float tn = m.t + m.dt; if (tn > t1) tn = t1; times.push_back(tn); }      // (fp32, as the controller forms t + dt; the last step ends at t1 exactly whenever t >= t1 / 2)
-    }
+    const std::vector<float> times = step_end_times(h->h_meta, h->n_att, F_ACCEPT, t0, t1, save_start != 0);
     *n_out = (int32_t)times.size();
     if ((int)times.size() > capacity) { h->err = "rnde_node_forward_everystep: more accepted steps than the output has room for"; return RNDE_ERR_BAD_ARG; }
     if (t_host_out) memcpy(t_host_out, times.data(), times.size() * sizeof(float));
@@ -1015,15 +974,9 @@ extern "C" rnde_status rnde_node_forward_everystep(rnde_node* h, const float* x_
     if (st != RNDE_OK) return st;
     // "the value at a step's end is u_new itself, no interpolation" holds only if the second solve (another kernel path: it saves) took exactly the steps
     // the first one took -- the same arithmetic, so it must; checked, not assumed (round-4 review)
-    size_t k = save_start ? 1 : 0;
-    for (int i = 0; i < h->n_att; ++i) {
-        const StepMeta& m = h->h_meta[i];
-        if (!(m.flags & F_ACCEPT)) continue;
-        float tn = m.t + m.dt; if (tn > t1) tn = t1;
-        if (k >= times.size() || times[k] != tn) { h->err = "rnde_node_forward_everystep: the saving solve did not retrace the steps of the first one"; return RNDE_ERR_HIP; }
-        ++k;
-    }
-    if (k != times.size()) { h->err = "rnde_node_forward_everystep: the saving solve took fewer accepted steps than the first one"; return RNDE_ERR_HIP; }
+    const std::vector<float> again = step_end_times(h->h_meta, h->n_att, F_ACCEPT, t0, t1, save_start != 0);
+    if (again.size() > times.size() || !std::equal(again.begin(), again.end(), times.begin())) { h->err = "rnde_node_forward_everystep: the saving solve did not retrace the steps of the first one"; return RNDE_ERR_HIP; }
+    if (again.size() != times.size()) { h->err = "rnde_node_forward_everystep: the saving solve took fewer accepted steps than the first one"; return RNDE_ERR_HIP; }
     return RNDE_OK;
 }
 
@@ -1118,25 +1071,18 @@ extern "C" rnde_status rnde_debug_feval(rnde_node* h, const float* u_dev, const 
     hipStream_t s = (hipStream_t)stream;
     StepParams P = make_params(h, u_dev, B, 0.f, 1.f, 0);
     P.forced = 1; P.forced_t = t; P.dbg_out = out_dev;
-    if (h->engine == 3) {
-        rnde_status st3 = chain_pack(h, p_dev, s);
-        if (st3 != RNDE_OK) return st3;
-        if (h->mw) HIPCHK(h, launch_mw<MW_FEVAL>(h, make_mw_params(h, P), 0, s));
-        else HIPCHK(h, launch_chain<CM_FEVAL>(h, make_chain_params(h, P), 0, nullptr, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        return RNDE_OK;
+    if (h->engine != 2 && h->engine != 3) { h->err = "rnde_debug_feval: unknown engine"; return RNDE_ERR_BAD_ARG; }
+    const rnde_status st = pack_untaped(h, p_dev, s);
+    if (st != RNDE_OK) return st;
+    const EngineParams E = engine_params(h, P, p_dev);
+    if (h->engine == 3 && h->mw) HIPCHK(h, launch_mw<MW_FEVAL>(h, E.MQ, 0, s));
+    else if (h->engine == 3) HIPCHK(h, launch_chain<CM_FEVAL>(h, E.CQ, 0, nullptr, s));
+    else {
+        HIPCHK(h, launch_stage<SM_FEVAL1>(h, E.SQ, 0, 0, s));
+        HIPCHK(h, launch_stage<SM_FEVAL2>(h, E.SQ, 0, 0, s));
     }
-    if (h->engine == 2) {
-        rnde_status st2 = stage_pack_weights(h, p_dev, s);
-        if (st2 != RNDE_OK) return st2;
-        StageParams SQ = make_stage_params(h, P, p_dev);
-        HIPCHK(h, launch_stage<SM_FEVAL1>(h, SQ, 0, 0, s));
-        HIPCHK(h, launch_stage<SM_FEVAL2>(h, SQ, 0, 0, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        return RNDE_OK;
-    }
-    h->err = "rnde_debug_feval: unknown engine";
-    return RNDE_ERR_BAD_ARG;
+    HIPCHK(h, hipStreamSynchronize(s));
+    return RNDE_OK;
 }
 
 extern "C" rnde_status rnde_debug_attempt(rnde_node* h, const float* uprev_dev, const float* k1_dev, const float* p_dev,
@@ -1148,40 +1094,34 @@ extern "C" rnde_status rnde_debug_attempt(rnde_node* h, const float* uprev_dev, 
     h->have_tape = false;
     StepParams P = make_params(h, uprev_dev, B, 0.f, 1.f, 0);
     P.forced = 1; P.forced_t = t; P.forced_dt = dt;
+    const int ntiles = P.Bpad / 16, nks = h->NKD;      // (chain engine: the fragment-order arrays)
+    // k1 goes to the f0 buffer: in fragment order (chain engine), or with column stride D as the caller holds it (stage engine)
     if (h->engine == 3) {
-        rnde_status st3 = chain_pack(h, p_dev, s);
-        if (st3 != RNDE_OK) return st3;
-        const ChainParams CQ = make_chain_params(h, P);
-        const int nks = h->NKD;
-        HIPCHK(h, chain_convert(k1_dev, h->f0, h->D, B, CQ.ntiles, nks, 0, s));
-        if (h->mw) { HIPCHK(h, launch_mw<MW_STEP>(h, make_mw_params(h, P), 0, s)); HIPCHK(h, launch_mw<MW_FINISH>(h, make_mw_params(h, P), 1, s)); }
-        else { HIPCHK(h, launch_chain<CM_STEP>(h, CQ, 0, nullptr, s)); HIPCHK(h, launch_chain<CM_FINISH>(h, CQ, 1, nullptr, s)); }
-        HIPCHK(h, hipMemcpyAsync(h->h_ctl, h->ctl_final, sizeof(StepState), hipMemcpyDeviceToHost, s));
-        const ChainRec CL{(long long)CQ.ntiles * nks * 64, h->rk_S};
-        for (int sidx = 2; sidx <= h->rk_S; ++sidx)      // (k_out: rk_S - 1 arrays)
-            HIPCHK(h, chain_convert(h->arena + CL.k(sidx), k_out_dev + (size_t)(sidx - 2) * h->D * B, h->D, B, CQ.ntiles, nks, 1, s));
-        HIPCHK(h, chain_convert(h->arena + CL.unew(), unew_out_dev, h->D, B, CQ.ntiles, nks, 1, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        if (eest_out) *eest_out = h->h_ctl->last_eest;
-        return RNDE_OK;
+        const rnde_status st = pack_untaped(h, p_dev, s);
+        if (st != RNDE_OK) return st;
+        HIPCHK(h, chain_convert(k1_dev, h->f0, h->D, B, ntiles, nks, 0, s));
+    } else {
+        HIPCHK(h, hipMemsetAsync(h->f0, 0, (size_t)h->D * P.Bpad * 4, s));
+        HIPCHK(h, hipMemcpyAsync(h->f0, k1_dev, (size_t)h->D * B * 4, hipMemcpyDeviceToDevice, s));
+        const rnde_status st = pack_untaped(h, p_dev, s);
+        if (st != RNDE_OK) return st;
     }
-    // k1 goes to the f0 buffer (column stride D in both layouts)
-    HIPCHK(h, hipMemsetAsync(h->f0, 0, (size_t)h->D * P.Bpad * 4, s));
-    HIPCHK(h, hipMemcpyAsync(h->f0, k1_dev, (size_t)h->D * B * 4, hipMemcpyDeviceToDevice, s));
-    {
-        rnde_status st2 = stage_pack_weights(h, p_dev, s);
-        if (st2 != RNDE_OK) return st2;
-        StageParams SQ = make_stage_params(h, P, p_dev);
-        HIPCHK(h, stage_attempt(h, SQ, 0, s));
-        hipLaunchKernelGGL(rnde_stage_finish_kernel, dim3(256), dim3(256), 0, s, SQ, 1, (float*)nullptr);
-        HIPCHK(h, hipGetLastError());
-    }
+    EngineParams E = engine_params(h, P, p_dev);
+    HIPCHK(h, launch_attempt(h, E, 0, s));
+    HIPCHK(h, launch_finish(h, E, 1, nullptr, s));
     HIPCHK(h, hipMemcpyAsync(h->h_ctl, h->ctl_final, sizeof(StepState), hipMemcpyDeviceToHost, s));
-    RecLayout L{(long long)h->D * P.Bpad, (long long)h->H * P.Bpad};
-    const float* R = h->arena;  // record 0 (no-tape: live == -1 -> rec 0)
-    for (int sidx = 2; sidx <= 7; ++sidx)
-        HIPCHK(h, hipMemcpyAsync(k_out_dev + (size_t)(sidx - 2) * h->D * B, R + L.k(sidx), (size_t)h->D * B * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(unew_out_dev, R + L.unew(), (size_t)h->D * B * 4, hipMemcpyDeviceToDevice, s));
+    // record 0 of the arena (no tape: live == -1 -> rec 0): k2 .. k_S and unew
+    if (h->engine == 3) {
+        const ChainRec CL{(long long)ntiles * nks * 64, h->rk_S};
+        for (int sidx = 2; sidx <= h->rk_S; ++sidx)      // (k_out: rk_S - 1 arrays)
+            HIPCHK(h, chain_convert(h->arena + CL.k(sidx), k_out_dev + (size_t)(sidx - 2) * h->D * B, h->D, B, ntiles, nks, 1, s));
+        HIPCHK(h, chain_convert(h->arena + CL.unew(), unew_out_dev, h->D, B, ntiles, nks, 1, s));
+    } else {
+        const RecLayout L{(long long)h->D * P.Bpad, (long long)h->H * P.Bpad};
+        for (int sidx = 2; sidx <= 7; ++sidx)
+            HIPCHK(h, hipMemcpyAsync(k_out_dev + (size_t)(sidx - 2) * h->D * B, h->arena + L.k(sidx), (size_t)h->D * B * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(unew_out_dev, h->arena + L.unew(), (size_t)h->D * B * 4, hipMemcpyDeviceToDevice, s));
+    }
     HIPCHK(h, hipStreamSynchronize(s));
     if (h->engine == 2 && persist_failed(h, h->sR * (P.Bpad / 16), P.Bpad / 16, h->sR, s)) { h->err = "persistent attempt kernel abandoned its hand-off; call again (multi-launch kernels now in use)"; return RNDE_ERR_HIP; }
     if (eest_out) *eest_out = h->h_ctl->last_eest;
@@ -1189,7 +1129,43 @@ extern "C" rnde_status rnde_debug_attempt(rnde_node* h, const float* uprev_dev, 
 }
 
 static rnde_status bench_attempt_impl(rnde_node* h, const float* x_dev, const float* p_dev, int32_t B, int32_t iters, int32_t taped,
-                                      float* mean_us_out, void* stream);
+                                      float* mean_us_out, void* stream) {
+    if (!h || B < 1 || B > h->cfg.max_batch || iters < 1) return RNDE_ERR_BAD_ARG;
+    RNDE_TILED_REFUSE(h, "rnde_bench_attempt* are not served (there is no per-attempt launch to time; rnde_node_timing reports the one-launch solve and the reverse sweep)");
+    hipStream_t s = (hipStream_t)stream;
+    h->have_tape = false;
+    if (taped > 1) { const rnde_status sa = ensure_arena(h, std::min<long long>(taped, h->cfg.max_attempts)); if (sa != RNDE_OK) return sa; }
+    StepParams P = make_params(h, x_dev, B, 0.f, 1.f, taped ? 1 : 0);   // taped: the variant a training step runs (record 0 of the arena)
+    P.forced = 1; P.forced_t = 0.f; P.forced_dt = 0.05f;
+    rnde_status st = pack_untaped(h, p_dev, s);
+    if (st != RNDE_OK) return st;
+    if (h->engine == 3 && h->mw && taped) { st = ensure_mw_slab(h, 8, s); if (st != RNDE_OK) return st; }
+    EngineParams E = engine_params(h, P, p_dev);
+    HIPCHK(h, launch_init(h, E, 0, s));      // k1 = f(x, 0) into f0
+    for (int i = 0; i < 3; ++i) HIPCHK(h, launch_attempt(h, E, 0, s));
+    Event e0, e1;
+    HIPCHK(h, e0.create()); HIPCHK(h, e1.create());
+    HIPCHK(h, hipEventRecord(e0, s));
+    const auto host_t0 = std::chrono::steady_clock::now();
+    // taped > 1 (stage engine): every attempt writes ANOTHER record of the arena, `taped` of them in turn -- what a solve does (31 records
+    // of 21.7 MB at B = 512: the tape leaves the chip); taped == 1 rewrites record 0, which then lives in the Infinity Cache
+    const int cyc = (taped > 1 && h->engine == 2) ? (int)std::min<long long>(taped, (long long)h->arena.cap() / h->rec_stride) : 1;
+    for (int i = 0; i < iters; ++i) {
+        E.SQ.F.rec_shift = i % cyc;
+        HIPCHK(h, launch_attempt(h, E, 0, s));
+    }
+    const double host_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - host_t0).count();
+    if (getenv("RNDE_TRACE_HOST")) fprintf(stderr, "[rnde] host enqueue: %.2f us per attempt (%d launches each)\n", host_us / iters, h->engine == 2 ? 7 : 1);
+    HIPCHK(h, hipEventRecord(e1, s));
+    HIPCHK(h, hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, e0, e1));
+    if (mean_us_out) *mean_us_out = ms * 1000.f / iters;
+#ifdef RNDE_DIAG
+    diag_bench_report(h, E, s);      // phase stamps of one more attempt
+#endif
+    return RNDE_OK;
+}
 extern "C" rnde_status rnde_bench_attempt(rnde_node* h, const float* x_dev, const float* p_dev, int32_t B, int32_t iters,
                                           float* mean_us_out, void* stream) {
     return bench_attempt_impl(h, x_dev, p_dev, B, iters, 0, mean_us_out, stream);
@@ -1202,94 +1178,4 @@ extern "C" rnde_status rnde_bench_attempt_cold_tape(rnde_node* h, const float* x
                                                     int32_t records, float* mean_us_out, void* stream) {
     if (records < 2) return RNDE_ERR_BAD_ARG;
     return bench_attempt_impl(h, x_dev, p_dev, B, iters, records, mean_us_out, stream);
-}
-static rnde_status bench_attempt_impl(rnde_node* h, const float* x_dev, const float* p_dev, int32_t B, int32_t iters, int32_t taped,
-                                      float* mean_us_out, void* stream) {
-    if (!h || B < 1 || B > h->cfg.max_batch || iters < 1) return RNDE_ERR_BAD_ARG;
-    RNDE_TILED_REFUSE(h, "rnde_bench_attempt* are not served (there is no per-attempt launch to time; rnde_node_timing reports the one-launch solve and the reverse sweep)");
-    hipStream_t s = (hipStream_t)stream;
-    h->have_tape = false;
-    if (taped > 1) { const rnde_status sa = ensure_arena(h, std::min<long long>(taped, h->cfg.max_attempts)); if (sa != RNDE_OK) return sa; }
-    StepParams P = make_params(h, x_dev, B, 0.f, 1.f, taped ? 1 : 0);   // taped: the variant a training step runs (record 0 of the arena)
-    P.forced = 1; P.forced_t = 0.f; P.forced_dt = 0.05f;
-    rnde_status st = h->engine == 3 ? chain_pack(h, p_dev, s) : RNDE_OK;
-    if (st != RNDE_OK) return st;
-    StageParams SQ{};
-    ChainParams CQ{};
-    MwParams MQ{};
-    if (h->engine == 3 && h->mw) {
-        if (taped) { st = ensure_mw_slab(h, 8, P.Bpad, s); if (st != RNDE_OK) return st; }
-        MQ = make_mw_params(h, P);
-        HIPCHK(h, launch_mw<MW_INIT_A>(h, MQ, 0, s));   // k1 = f(x, 0) into f0
-        for (int i = 0; i < 3; ++i) HIPCHK(h, launch_mw<MW_STEP>(h, MQ, 0, s));
-    } else if (h->engine == 3) {
-        CQ = make_chain_params(h, P);
-        HIPCHK(h, launch_chain<CM_INIT_A>(h, CQ, 0, nullptr, s));   // k1 = f(x, 0) into f0
-        for (int i = 0; i < 3; ++i) HIPCHK(h, launch_chain<CM_STEP>(h, CQ, 0, nullptr, s));
-    } else {
-        st = stage_pack_weights(h, p_dev, s);
-        if (st != RNDE_OK) return st;
-        SQ = make_stage_params(h, P, p_dev);
-        HIPCHK(h, launch_stage<SM_I1>(h, SQ, 0, 0, s));
-        HIPCHK(h, launch_stage<SM_I2>(h, SQ, 0, 0, s));   // k1 = f(x, 0) into f0
-        for (int i = 0; i < 3; ++i) HIPCHK(h, stage_attempt(h, SQ, 0, s));
-    }
-    Event e0, e1;
-    HIPCHK(h, e0.create()); HIPCHK(h, e1.create());
-    HIPCHK(h, hipEventRecord(e0, s));
-    const auto host_t0 = std::chrono::steady_clock::now();
-    // taped > 1 (stage engine): every attempt writes ANOTHER record of the arena, `taped` of them in turn -- what a solve does (31 records
-    // of 21.7 MB at B = 512: the tape leaves the chip); taped == 1 rewrites record 0, which then lives in the Infinity Cache
-    const int cyc = (taped > 1 && h->engine == 2) ? (int)std::min<long long>(taped, (long long)h->arena.cap() / h->rec_stride) : 1;
-    for (int i = 0; i < iters; ++i) {
-        if (h->engine == 3 && h->mw) HIPCHK(h, launch_mw<MW_STEP>(h, MQ, 0, s));
-        else if (h->engine == 3) HIPCHK(h, launch_chain<CM_STEP>(h, CQ, 0, nullptr, s));
-        else { SQ.F.rec_shift = i % cyc; HIPCHK(h, stage_attempt(h, SQ, 0, s)); }
-    }
-    const double host_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - host_t0).count();
-    if (getenv("RNDE_TRACE_HOST")) fprintf(stderr, "[rnde] host enqueue: %.2f us per attempt (%d launches each)\n", host_us / iters, h->engine == 2 ? 7 : 1);
-    HIPCHK(h, hipEventRecord(e1, s));
-    HIPCHK(h, hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, e0, e1));
-    if (mean_us_out) *mean_us_out = ms * 1000.f / iters;
-#ifdef RNDE_DIAG
-    {   // phase stamps of the LAST f evaluation of one launch (workgroup 0), in shader cycles relative to stamp 0 of wave 0
-        DevBuf<unsigned long long> d; unsigned long long hst[512] = {0};
-        (void)d.alloc(512); hipMemset(d, 0, sizeof(hst));
-        P.dbg_out = (float*)d.get();
-        if (h->engine == 3 && h->mw) {
-            MQ.F.dbg_out = (float*)d.get(); launch_mw<MW_STEP>(h, MQ, 0, s); hipStreamSynchronize(s); hipMemcpy(hst, d, sizeof(hst), hipMemcpyDeviceToHost);
-            fprintf(stderr, "mw chain stamps (cycles): LDS fill %lld, controller %lld, state load %lld |", (long long)(hst[1]-hst[0]), (long long)(hst[2]-hst[1]), (long long)(hst[3]-hst[2]));
-            for (int i = 4; i <= 9; ++i) fprintf(stderr, " eval%d %lld", i - 3, (long long)(hst[i]-hst[i-1]));
-            fprintf(stderr, " | tail %lld total %lld\n  first eval: input->L0 %lld", (long long)(hst[10]-hst[9]), (long long)(hst[10]-hst[0]), (long long)(hst[16]-hst[3]));
-            for (int l = 0; l < h->mg.n_layers; ++l) fprintf(stderr, " L%d %lld", l, (long long)(hst[17+l]-hst[16+l]));
-            fprintf(stderr, "\n");
-            return RNDE_OK; }
-        if (h->engine == 3) { CQ.F.dbg_out = (float*)d.get(); launch_chain<CM_STEP>(h, CQ, 0, nullptr, s); hipStreamSynchronize(s); hipMemcpy(hst, d, sizeof(hst), hipMemcpyDeviceToHost);
-            fprintf(stderr, "chain stamps (cycles): fill %lld ctl %lld loads %lld |", (long long)(hst[1]-hst[0]), (long long)(hst[2]-hst[1]), (long long)(hst[3]-hst[2]));
-            for (int i = 4; i <= 9; ++i) fprintf(stderr, " st%d %lld", i - 3, (long long)(hst[i]-hst[i-1]));
-            fprintf(stderr, " | tail %lld total %lld\n", (long long)(hst[10]-hst[9]), (long long)(hst[10]-hst[0]));
-            for (int l = 0; l < h->cg.n_layers; ++l) fprintf(stderr, "  layer %d: bias %lld mm %lld act %lld (gap to next %lld)\n", l, (long long)(hst[17+4*l]-hst[16+4*l]), (long long)(hst[18+4*l]-hst[17+4*l]), (long long)(hst[19+4*l]-hst[18+4*l]), l + 1 < h->cg.n_layers ? (long long)(hst[20+4*l]-hst[19+4*l]) : 0LL);
-            return RNDE_OK; }
-        if (h->engine == 2 && h->persist == 1) {
-            SQ.F.dbg_out = (float*)d.get(); stage_attempt(h, SQ, 0, s); hipStreamSynchronize(s);
-            hipMemcpy(hst, d, sizeof(hst), hipMemcpyDeviceToHost);
-            fprintf(stderr, "persistent attempt (workgroup 0 thread 0, cycles): prologue(weights) %lld ctl %lld startC %lld startD %lld\n", 0LL, (long long)(hst[1]-hst[0]), (long long)(hst[2]-hst[1]), (long long)(hst[3]-hst[2]));
-            for (int st = 1; st <= 6; ++st) { const unsigned long long* q = hst + 4 + 5 * (st - 1); const unsigned long long prev = st == 1 ? hst[3] : hst[8 + 5 * (st - 2)];
-                if (st < 6) fprintf(stderr, "  stage %d: poll %lld A %lld B %lld C %lld D+put %lld\n", st, (long long)(q[0]-prev), (long long)(q[1]-q[0]), (long long)(q[2]-q[1]), (long long)(q[3]-q[2]), (long long)(q[4]-q[3]));
-                else fprintf(stderr, "  stage %d: poll %lld A %lld B %lld C+err %lld | total %lld cycles\n", st, (long long)(q[0]-prev), (long long)(q[1]-q[0]), (long long)(q[2]-q[1]), (long long)(hst[34]-q[2]), (long long)(hst[34]-hst[0])); }
-            fprintf(stderr, "per wave, relative to wave 0's poll-done of the stage: poll-done | barrier A in, out | B done | C done (before the barrier of D) | after it | put done\n");
-            for (int st = 1; st <= 5; ++st) for (int w = 0; w < 7; ++w) { const unsigned long long* q = hst + 64 + ((st - 1) * 8 + w) * 8; const long long z = (long long)hst[64 + (st - 1) * 64];
-                fprintf(stderr, "  stage %d wave %d: %6lld | %6lld %6lld | %6lld | %6lld | %6lld | %6lld\n", st, w, (long long)q[0]-z, (long long)q[1]-z, (long long)q[2]-z, (long long)q[3]-z, (long long)q[4]-z, (long long)q[5]-z, (long long)q[6]-z); }
-            return RNDE_OK;
-        }
-        SQ.F.dbg_out = (float*)d.get(); stage_attempt(h, SQ, 0, s);
-        hipStreamSynchronize(s);
-        hipMemcpy(hst, d, sizeof(hst), hipMemcpyDeviceToHost);
-        fprintf(stderr, "stamps (cycles since wave0 stamp0); column-owner: start sync1 gemm1 sync2 reduce sync3 gemm2 tanh | stage: start scalars A sync B C sync D\n");
-        for (int w = 0; w < 8; ++w) { fprintf(stderr, "wave %d:", w); for (int i = 0; i < 8; ++i) fprintf(stderr, " %7lld", (long long)(hst[w * 8 + i] - hst[0])); fprintf(stderr, "\n"); }
-    }
-#endif
-    return RNDE_OK;
 }

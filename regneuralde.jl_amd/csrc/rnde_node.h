@@ -190,6 +190,9 @@ static auto mw_variant(const rnde_node* h, F&& f) {
     return by_tab(IC<0>{});
 }
 
+// the headline geometry ([784, 100, 784] as 7 row blocks of 7 waves, 7 hidden tiles, 7 k-blocks) the fixed-shape stage kernels, forward and reverse, are
+// compiled for; Kb: the k-blocks of the side in question (StageParams::K2b forward, BwdStageParams::KHb reverse)
+static inline bool stage_fix(const rnde_node* h, int WT, int HT, int Kb, int MT, int R) { return WT == 7 && HT == 7 && Kb == 7 && MT == 49 && R == 7 && h->D == 784 && h->H == 100 && !h->stage_generic; }
 static const rnde_status RNDE_INTERNAL_RETRY = static_cast<rnde_status>(100);
 // The launches around the two sweeps that are folded into a neighbour, one host switch each, read per call like RNDE_SOLVE_FOLD (tests and A/B
 // runs flip them inside one process; 0 = off, anything else = on): RNDE_REDUCE_FOLD (the two passes of the weight-gradient reduction as one launch),

@@ -1,6 +1,6 @@
 // rnde_rev_plan.h -- what the host derives from the attempt log of a recorded solve for the reverse sweeps, each rule stated once: which saveat
-// indices an attempt covers (save_plan), the eigen_est cotangent coefficients of an attempt (eig_cotangent), the evaluation times of the chain
-// engines' slabs (eval_times) and the saved-value cotangent per attempt (gather_svb).  Kernel-free: plain C++, no device symbol, templates over
+// indices an attempt covers (save_plan), the evaluation times of the chain engines' slabs (eval_times) and the saved-value cotangent per attempt
+// (gather_svb); the eigen_est cotangent coefficients of an attempt (eig_cotangent) sit beside the callback's value in rnde_fwd_plan.h.  Kernel-free: plain C++, no device symbol, templates over
 // the record type, so a host program can include it alone (tests/save_host/save_plan_check.cpp).
 //
 // The save rule, in the controller's own float comparisons (rnde_fwd.h, advance_state_t: next_save): index 0 belongs to the start when
@@ -9,7 +9,7 @@
 // interpolation) and not to the next one; a rejected attempt covers nothing.  The ranges [lo[n], hi[n]) are consecutive: together with the start
 // they partition 0 .. the value returned, which is n_save whenever the solve reached the last save time.
 #pragma once
-#include "../../include/rnde.h"      // rnde_reg
+#include "rnde_fwd_plan.h"           // callback_value and its derivative, eig_cotangent
 
 namespace rnde {
 
@@ -29,29 +29,6 @@ inline int save_plan(const float* sv, int n_save, float t0, const Rec* att, int 
         out[n].hi = ns;
     }
     return ns;
-}
-
-// Cotangent coefficients of eigen_est = n1 / n2 for one attempt: the kernels add c1 * (k7 - k6) and c2 * (unew - g6) (n1, n2: the norms of the
-// two differences), so c1 n1 and c2 n2 are the derivatives of the callback's value in n1 and n2.  svb: the cotangent of the value the callback
-// saved for this attempt; mm.eigen, mm.n1, mm.n2, mm.dt: the attempt's record (StepMeta).  The three stiffness callbacks:
-//   RNDE_REG_STIFF      svb |eigen| / S                (S = alg_stability_size(Tsit5()), the literal below)
-//   RNDE_REG_ERR_STIFF  0.1 svb eigen / S              (the stiffness term of the mixed callback)
-//   RNDE_REG_STIFF_DT   svb |eigen dt|                 (test/test_node.jl:75)
-// (0, 0) for every other kind, for an estimate that is zero or NaN and for a zero norm.  Arithmetic in double, rounded to fp32 at the end: the
-// results are kernel arguments.
-template <class Rec>
-inline void eig_cotangent(int reg_kind, float svb, const Rec& mm, float* c1, float* c2) {
-    *c1 = 0.f; *c2 = 0.f;
-    const bool eg_ok = !(mm.eigen == 0.f || mm.eigen != mm.eigen);
-    const double S = 3.5068;
-    double eigb = 0.0;
-    if (reg_kind == RNDE_REG_STIFF && eg_ok) eigb = (double)svb * (mm.eigen > 0 ? 1.0 : -1.0) / S;
-    if (reg_kind == RNDE_REG_ERR_STIFF && eg_ok) eigb = 0.1 * (double)svb / S;
-    if (reg_kind == RNDE_REG_STIFF_DT && eg_ok) eigb = (double)svb * ((double)mm.eigen * (double)mm.dt > 0 ? 1.0 : -1.0) * (double)mm.dt;
-    if (eigb != 0.0 && mm.n1 > 0.f && mm.n2 > 0.f) {
-        *c1 = (float)(eigb / ((double)mm.n2 * (double)mm.n1));
-        *c2 = (float)(-eigb * ((double)mm.n1 / (double)mm.n2) / ((double)mm.n2 * (double)mm.n2));
-    }
 }
 
 // Evaluation times of a chain engine's slab (the time column of TDChain layers in the weight-gradient kernel): E per attempt, stage s = 2 .. E + 1

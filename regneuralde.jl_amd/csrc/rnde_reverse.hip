@@ -366,7 +366,7 @@ static rnde_status bwd_run(rnde_node* h, const float* u_bar_dev, const float* sa
                 PersistSync Y{h->tslab, h->pabort, h->pxcc, h->persist_spins};
                 HIPCHK(h, slab_prepare(h, Q.F.Bpad, s));
                 const dim3 pgrid(8 * BQ.R * ((BQ.C + 7) / 8));
-                const bool fix = BQ.WT == 7 && BQ.HT == 7 && BQ.KHb == 7 && BQ.MT == 49 && BQ.R == 7 && h->D == 784 && h->H == 100 && !h->stage_generic;
+                const bool fix = stage_fix(h, BQ.WT, BQ.HT, BQ.KHb, BQ.MT, BQ.R);
                 BAttemptKern kern = kAttempt[a2][fix];
                 size_t lds = h->stage_lds;
                 if (fix) {

@@ -1,7 +1,6 @@
 // What the host derives from an attempt log for the reverse sweeps, checked by a program of its own (tests/test_node_tiled_saveat_host.py
-// compiles and runs it; no GPU is touched): csrc/rnde_rev_plan.h -- the save plan on written-down attempt logs, the eigen_est cotangent
-// coefficients against central differences of the callback's value, the chain engines' evaluation times, the saved-value cotangent gather --
-// and the Tsit5 dense-output weights of csrc/rnde_device.h (dense_weights, dense_weights_deriv; host and device functions) against the tableau
+// compiles and runs it; no GPU is touched): csrc/rnde_rev_plan.h -- the save plan on written-down attempt logs, the chain engines' evaluation
+// times, the saved-value cotangent gather (the eigen_est cotangent coefficients: fwd_plan_check.cpp, beside the callback's value) -- and the Tsit5 dense-output weights of csrc/rnde_device.h (dense_weights, dense_weights_deriv; host and device functions) against the tableau
 // and against central differences.
 // Prints one line per failed check; exit status 0 when there is none.
 #include "rnde_device.h"
@@ -139,79 +138,6 @@ static void dense_weight_checks() {
     }
 }
 
-// ---- eig_cotangent: the coefficients against central differences of the callback's own value ----------------------------------------------
-struct Eig { float eigen, n1, n2, dt; };
-
-// the value the callback saves, times its cotangent, as a function of the two norms (fp64)
-static double callback_value(int kind, double svb, double n1, double n2, double dt) {
-    const double S = 3.5068;      // alg_stability_size(Tsit5())
-    if (kind == RNDE_REG_STIFF) return svb * std::fabs(n1 / n2) / S;
-    if (kind == RNDE_REG_ERR_STIFF) return 0.1 * svb * (n1 / n2) / S;
-    return svb * std::fabs(n1 / n2 * dt);
-}
-
-static void eig_cotangent_checks() {
-    const int kinds[3] = {RNDE_REG_STIFF, RNDE_REG_ERR_STIFF, RNDE_REG_STIFF_DT};
-    // c1 n1 = d/dn1, c2 n2 = d/dn2.  The coefficients are fp32 roundings of fp64 expressions (2^-24 relative), the products here are exact in
-    // fp64 up to 2^-53, and a central difference with a relative step of 1e-5 of these rational functions is good to 1e-10 relative
-    // (truncation h^2 f'''/6 ~ 1e-10, rounding 1e-16 / 1e-5): 2^-23 covers all of it with a factor of two to spare.
-    const double tol = 1.1920929e-7;
-    for (int kind : kinds)
-        for (const Eig& r : {Eig{0.75f / 0.31f, 0.75f, 0.31f, 0.0625f}, Eig{3.0e-3f / 41.5f, 3.0e-3f, 41.5f, 0.4f}, Eig{17.f / 0.002f, 17.f, 0.002f, 1e-3f},
-                             Eig{0.75f / 0.31f, 0.75f, 0.31f, -0.0625f}})      // (the last: a solve that runs backwards in time, eigen * dt < 0)
-            for (float svb : {1.f, -0.37f, 250.f}) {
-                float c1 = 7.f, c2 = 7.f;
-                eig_cotangent(kind, svb, r, &c1, &c2);
-                const double n1 = r.n1, n2 = r.n2, h1 = 1e-5 * n1, h2 = 1e-5 * n2;
-                const double d1 = (callback_value(kind, svb, n1 + h1, n2, r.dt) - callback_value(kind, svb, n1 - h1, n2, r.dt)) / (2 * h1);
-                const double d2 = (callback_value(kind, svb, n1, n2 + h2, r.dt) - callback_value(kind, svb, n1, n2 - h2, r.dt)) / (2 * h2);
-                const bool ok1 = std::fabs((double)c1 * n1 - d1) <= tol * std::fabs(d1), ok2 = std::fabs((double)c2 * n2 - d2) <= tol * std::fabs(d2);
-                if (!ok1 || !ok2 || d1 == 0.0 || d2 == 0.0) {
-                    std::printf("FAILED eig_cotangent kind %d svb %g (n1 %g n2 %g dt %g): c1 n1 %.12g against %.12g, c2 n2 %.12g against %.12g\n", kind, (double)svb,
-                                n1, n2, (double)r.dt, (double)c1 * n1, d1, (double)c2 * n2, d2);
-                    ++failures;
-                }
-            }
-    // zero cases: no estimate (0 or NaN) and a zero norm give (0, 0) under every stiffness kind
-    const Eig good{2.f, 1.f, 0.5f, 0.1f};
-    for (int kind : kinds) {
-        for (const Eig& r : {Eig{0.f, 1.f, 0.5f, 0.1f}, Eig{std::nanf(""), 1.f, 0.5f, 0.1f}, Eig{2.f, 0.f, 0.5f, 0.1f}, Eig{2.f, 1.f, 0.f, 0.1f}}) {
-            float c1 = 7.f, c2 = 7.f;
-            eig_cotangent(kind, 1.5f, r, &c1, &c2);
-            CHECK(c1 == 0.f && c2 == 0.f);
-        }
-        float c1 = 7.f, c2 = 7.f;
-        eig_cotangent(kind, 0.f, good, &c1, &c2);      // (and a zero cotangent)
-        CHECK(c1 == 0.f && c2 == 0.f);
-        eig_cotangent(kind, 1.5f, good, &c1, &c2);
-        CHECK(c1 > 0.f && c2 < 0.f);                    // the value grows with n1 and falls with n2
-    }
-    // sign cases: |eigen| and |eigen dt| turn the coefficients round with the sign of what is inside; the mixed callback's term has no
-    // absolute value and does not
-    {
-        float p1, p2, m1, m2;
-        eig_cotangent(RNDE_REG_STIFF, 1.5f, good, &p1, &p2);
-        eig_cotangent(RNDE_REG_STIFF, 1.5f, Eig{-2.f, 1.f, 0.5f, 0.1f}, &m1, &m2);
-        CHECK(m1 == -p1 && m2 == -p2 && p1 != 0.f);
-        eig_cotangent(RNDE_REG_ERR_STIFF, 1.5f, good, &p1, &p2);
-        eig_cotangent(RNDE_REG_ERR_STIFF, 1.5f, Eig{-2.f, 1.f, 0.5f, 0.1f}, &m1, &m2);
-        CHECK(m1 == p1 && m2 == p2 && p1 != 0.f);
-        eig_cotangent(RNDE_REG_STIFF_DT, 1.5f, good, &p1, &p2);
-        eig_cotangent(RNDE_REG_STIFF_DT, 1.5f, Eig{-2.f, 1.f, 0.5f, 0.1f}, &m1, &m2);      // eigen * dt < 0 through eigen: sign -1, times dt > 0
-        CHECK(m1 == -p1 && m2 == -p2 && p1 > 0.f);
-        eig_cotangent(RNDE_REG_STIFF_DT, 1.5f, Eig{2.f, 1.f, 0.5f, -0.1f}, &m1, &m2);      // eigen * dt < 0 through dt: sign -1, times dt < 0
-        CHECK(m1 == p1 && m2 == p2);
-        eig_cotangent(RNDE_REG_STIFF_DT, 1.5f, Eig{-2.f, 1.f, 0.5f, -0.1f}, &m1, &m2);     // both negative: sign +1, times dt < 0
-        CHECK(m1 == -p1 && m2 == -p2);
-    }
-    // the callbacks without a stiffness estimate
-    for (int kind : {(int)RNDE_REG_NONE, (int)RNDE_REG_ERR}) {
-        float c1 = 7.f, c2 = 7.f;
-        eig_cotangent(kind, 1.5f, good, &c1, &c2);
-        CHECK(c1 == 0.f && c2 == 0.f);
-    }
-}
-
 // ---- eval_times: a written-down five-attempt log, both positions of the initial pair, 6 and 12 evaluations per attempt -------------------
 static void eval_time_checks() {
     const std::vector<Att> att = {{0.f, 0.25f, F_ACCEPT}, {0.25f, 0.5f, 0}, {0.25f, 0.125f, F_ACCEPT}, {0.375f, 0.5f, F_ACCEPT}, {0.875f, 0.125f, F_ACCEPT | F_CLAMP}};
@@ -261,7 +187,6 @@ static void gather_checks() {
 
 int main() {
     save_plan_checks();
-    eig_cotangent_checks();
     eval_time_checks();
     gather_checks();
     dense_weight_checks();

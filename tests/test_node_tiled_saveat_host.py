@@ -1,7 +1,7 @@
 """Saved points on the tiled TrackedNeuralODE engine, what needs no GPU: the layer's tiled_max_saveat keyword (acceptances, refusals, the create
 config untouched), the new exports, and the host side of the feature by a stand-alone program (tests/save_host/save_plan_check.cpp) compiled
-with the address and undefined-behaviour sanitizers: csrc/rnde_rev_plan.h (the save plan on written-down attempt logs, the eigen_est cotangent
-coefficients against central differences, the chain engines' evaluation times, the saved-value cotangent gather) and the Tsit5 dense-output
+with the address and undefined-behaviour sanitizers: csrc/rnde_rev_plan.h (the save plan on written-down attempt logs, the chain engines' evaluation
+times, the saved-value cotangent gather; the eigen_est cotangent coefficients are checked beside the callback's value, tests/test_fwd_plan_host.py) and the Tsit5 dense-output
 weights against the tableau and central differences."""
 import ctypes as C
 import os
