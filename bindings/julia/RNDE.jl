@@ -553,6 +553,68 @@ function nsde_classifier_grad!(p2bar::ROCVector{Float32}, p3bar::ROCVector{Float
     return ce, reg[], nfe1[], nfe2[]
 end
 
+# ---- ClassifierNSDE with several trajectories per input (src/models/supervised_classification.jl:82-100) ----------------
+# Column j = t * B + b of every D x (B * T) array is trajectory t of input b: what repeat(x, 1, T) gives (:92, :102-103).
+_nsde_err(h::NsdeHandle, who) = error(who, ": ", unsafe_string(ccall((:rnde_nsde_last_error, LIB), Cstring, (Ptr{Cvoid},), h.ptr)))
+
+# postsde + mean over the trajectories + logitcrossentropy and their reverse (:96-98): u, ubar are D x (B * T), y is C x B.
+# Returns (ce (1-element device array), logits (C x B, averaged)); ubar and p3bar are filled in stream order.
+function nsde_classifier_head_traj!(ubar::ROCMatrix{Float32}, p3bar::ROCVector{Float32}, h::NsdeHandle, u::ROCMatrix{Float32},
+                                    p3::ROCVector{Float32}, y::ROCMatrix{Float32}, trajectories::Integer)
+    ce = ROCVector{Float32}(undef, 1)
+    logits = ROCMatrix{Float32}(undef, size(y, 1), size(y, 2))
+    st = GC.@preserve ubar p3bar u p3 y ce logits begin
+        ccall((:rnde_nsde_classifier_head_traj, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              h.ptr, devptr(u), devptr(p3), devptr(y), size(y, 2), trajectories, size(y, 1), devptr(logits), devptr(ubar), devptr(p3bar),
+              devptr(ce), _stream())
+    end
+    st == 0 || _nsde_err(h, "rnde_nsde_classifier_head_traj")
+    return ce, logits
+end
+
+# nsde_classifier_grad! with `trajectories` sample paths per input: x (D x B, NOT repeated) is the presde layer's output, xbar (D x B) its
+# cotangent, already summed over the trajectories; noise = nothing or the caller's pool (D x (B * trajectories) x 2 x n_pool normals).
+function nsde_classifier_grad_traj!(p2bar::ROCVector{Float32}, p3bar::ROCVector{Float32}, xbar::ROCMatrix{Float32}, h::NsdeHandle,
+                                    x::ROCMatrix{Float32}, p2::ROCVector{Float32}, p3::ROCVector{Float32}, y::ROCMatrix{Float32}, tspan;
+                                    trajectories::Integer = 10, lambda = 1f1, noise = nothing, seed::Integer = 0)
+    ce = ROCVector{Float32}(undef, 1)
+    reg = Ref{Cfloat}(0); nfe1 = Ref{Int64}(0); nfe2 = Ref{Int64}(0)
+    npool = noise === nothing ? 0 : size(noise, 4)
+    st = GC.@preserve p2bar p3bar xbar x p2 p3 y ce noise begin
+        ccall((:rnde_nsde_classifier_grad_traj, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Int32, Cfloat, Cfloat, Ptr{Cvoid}, Int32, UInt64, Cfloat,
+               Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Cfloat}, Ref{Int64}, Ref{Int64}, Ptr{Cvoid}),
+              h.ptr, devptr(x), devptr(p2), devptr(p3), devptr(y), size(x, 2), trajectories, size(y, 1), Float32(tspan[1]), Float32(tspan[2]),
+              noise === nothing ? C_NULL : devptr(noise), npool, UInt64(seed), Float32(lambda),
+              devptr(p2bar), devptr(p3bar), devptr(xbar), devptr(ce), reg, nfe1, nfe2, _stream())
+    end
+    st == 0 || _nsde_err(h, "rnde_nsde_classifier_grad_traj")
+    return ce, reg[], nfe1[], nfe2[]
+end
+
+# The evaluation call (experiments/mnist_nsde.jl:154-155; src/metrics.jl:2-9): averaged logits (C x B) of x (D x B, the presde layer's
+# output) over `trajectories` untaped sample paths; with labels y (C x B) the matches of argmax(logits) against argmax(y) are ADDED to the
+# one-element device counter `correct` (zero it once per data set, read it once).  Returns (logits, nfe1, nfe2).
+function nsde_classifier_predict(h::NsdeHandle, x::ROCMatrix{Float32}, p2::ROCVector{Float32}, p3::ROCVector{Float32}, n_classes::Integer, tspan;
+                                 trajectories::Integer = 10, y::Union{Nothing, ROCMatrix{Float32}} = nothing,
+                                 correct::Union{Nothing, ROCVector{Int64}} = nothing, noise = nothing, seed::Integer = 0)
+    (y === nothing && correct !== nothing) && error("nsde_classifier_predict: a counter without labels")
+    logits = ROCMatrix{Float32}(undef, n_classes, size(x, 2))
+    nfe1 = Ref{Int64}(0); nfe2 = Ref{Int64}(0)
+    npool = noise === nothing ? 0 : size(noise, 4)
+    st = GC.@preserve x p2 p3 y correct noise logits begin
+        ccall((:rnde_nsde_classifier_predict, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Int32, Cfloat, Cfloat, Ptr{Cvoid}, Int32, UInt64,
+               Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ptr{Cvoid}),
+              h.ptr, devptr(x), devptr(p2), devptr(p3), y === nothing ? C_NULL : devptr(y), size(x, 2), trajectories, n_classes,
+              Float32(tspan[1]), Float32(tspan[2]), noise === nothing ? C_NULL : devptr(noise), npool, UInt64(seed),
+              devptr(logits), correct === nothing ? C_NULL : devptr(correct), nfe1, nfe2, _stream())
+    end
+    st == 0 || _nsde_err(h, "rnde_nsde_classifier_predict")
+    return logits, nfe1[], nfe2[]
+end
+
 # ---- optimiser step and the data-parallel collective -------------------------------------------------
 # Optimiser(InvDecay(gamma), Momentum(eta, rho)) on one flat group, in place (src/utils.jl:149-156, mnist_node.jl:130);
 # `n` is the group's InvDecay counter (starts at 1, the caller increments it); gscale = 1 / nworkers after a summed all-reduce.

@@ -547,7 +547,7 @@ rnde_status rnde_nsde_backward_async(rnde_nsde* h, const float* u_bar_dev, const
                                float* p_bar_dev, void* stream);
 /* postsde Dense(D, C) + Flux.Losses.logitcrossentropy and their reverse for ClassifierNSDE with ONE trajectory per input (reference
  * src/models/supervised_classification.jl:96-97, experiments/mnist_nsde.jl): same contract as rnde_classifier_head, D = the SDE's state
- * dimension.  (With several trajectories the logits are averaged first: that stays on the host side.) */
+ * dimension.  (With several trajectories the logits are averaged first: rnde_nsde_classifier_head_traj below.) */
 rnde_status rnde_nsde_classifier_head(rnde_nsde* h, const float* u_dev, const float* p3_dev, const float* y_dev, int32_t B, int32_t n_classes,
                                       float* logits_out_dev, float* u_bar_dev, float* p3_bar_dev, float* ce_out_dev, void* stream);
 
@@ -562,6 +562,45 @@ rnde_status rnde_nsde_classifier_grad(rnde_nsde* h, const float* x_dev, const fl
                                       int32_t B, int32_t n_classes, float t0, float t1, const float* noise_dev, int32_t n_pool,
                                       uint64_t seed, float lambda, float* p2_bar_dev, float* p3_bar_dev, float* x_bar_dev,
                                       float* ce_out_dev, float* reg_out_host, int64_t* nfe1_out, int64_t* nfe2_out, void* stream);
+/* ---- ClassifierNSDE with several trajectories per input (reference src/models/supervised_classification.jl:82-100, `trajectories`) ----
+ * Layout of the three calls: column j = t * B + b of the expanded batch is trajectory t of input b (Julia's repeat(x, 1, T), :92, :102-103);
+ * T trajectories, B inputs.  Limits, checked before anything is launched (RNDE_ERR_BAD_ARG, rnde_nsde_last_error names the limit):
+ * T >= 1, B >= 1, B * T <= cfg.max_batch, 2 <= n_classes <= 16.
+ *
+ * postsde Dense(D, C) on every trajectory, the mean of the logits over the trajectories (:96-98), Flux.Losses.logitcrossentropy (experiments/
+ * mnist_nsde.jl) and the Tracker reverse of all three:
+ *     z_tb = W3 u_tb + b3,  z_b = (1/T) sum_t z_tb,  ce = (1/B) sum_b -sum_i y_ib logsoftmax(z_b)_i
+ *     delta_b = (softmax(z_b) sum_i y_ib - y_b) / B      (y need not be one-hot)
+ *     u_bar_tb = W3^T delta_b / T,  W3_bar = (1/T) sum_{t,b} delta_b u_tb^T,  b3_bar = sum_b delta_b
+ * u_dev, u_bar_dev: D x (B T); y_dev: C x B; logits_out_dev: C x B, the averaged logits (may be NULL); p3 / p3_bar in the
+ * Flux.destructure(Dense(D, C)) layout of rnde_classifier_head; ce_out_dev: one float.  Every sum runs in a fixed order (csrc/rnde_head_traj.h
+ * states it), no float atomics: the same bits run to run.  At T = 1 it agrees with rnde_nsde_classifier_head to rounding.  Asynchronous on `stream`. */
+rnde_status rnde_nsde_classifier_head_traj(rnde_nsde* h, const float* u_dev, const float* p3_dev, const float* y_dev, int32_t B, int32_t T,
+                                           int32_t n_classes, float* logits_out_dev, float* u_bar_dev, float* p3_bar_dev, float* ce_out_dev,
+                                           void* stream);
+/* rnde_nsde_classifier_grad with T trajectories per input (reference src/models/supervised_classification.jl:92-98 around the solve, with
+ * experiments/mnist_nsde.jl's loss_function and Tracker.gradient): x_dev is the presde layer's output for the B inputs, D x B, NOT repeated.
+ *     xe = repeat(x, 1, T)  ->  u = TrackedNeuralDSDE(xe, p2)  ->  rnde_nsde_classifier_head_traj  ->  loss = ce + lambda * mean(sv.saveval)
+ * = the repeat, rnde_nsde_forward at B T columns (taped; bit for bit the solve of an explicitly repeated input on the same noise),
+ * rnde_nsde_classifier_head_traj queued before the forward's host wait, rnde_nsde_backward_async, and the fold
+ * x_bar_b = sum_t xe_bar_{tB+b} (added in the order t = 0 .. T-1).  Noise as in rnde_nsde_forward at B T columns: the caller's pool of
+ * 2 * D * B * T floats per draw, or NULL + seed.  x_bar_dev: D x B, folded (required).  *reg_out_host, *nfe1_out, *nfe2_out are valid on
+ * return; the gradients and ce_out_dev in stream order. */
+rnde_status rnde_nsde_classifier_grad_traj(rnde_nsde* h, const float* x_dev, const float* p2_dev, const float* p3_dev, const float* y_dev,
+                                           int32_t B, int32_t T, int32_t n_classes, float t0, float t1, const float* noise_dev, int32_t n_pool,
+                                           uint64_t seed, float lambda, float* p2_bar_dev, float* p3_bar_dev, float* x_bar_dev,
+                                           float* ce_out_dev, float* reg_out_host, int64_t* nfe1_out, int64_t* nfe2_out, void* stream);
+/* The evaluation call (reference src/models/supervised_classification.jl:82-100 behind the presde layer; src/metrics.jl:2-9 for the count;
+ * experiments/mnist_nsde.jl:154-155 calls it with 10 trajectories over the whole data set every epoch): the repeat of x_dev (D x B, NOT
+ * repeated), the UNTAPED solve at B T columns (noise as above), the averaged logits -> logits_out_dev (C x B, required) and, when y_dev
+ * (C x B) is given, the number of inputs whose predicted class -- the FIRST index of the largest averaged logit, Julia's argmax -- equals
+ * the first index of the largest entry of y's column, ADDED to the device int64 *correct_dev (the caller zeroes it once per data set and
+ * reads it once).  y_dev may be NULL; correct_dev may be NULL and must be NULL when y_dev is.  Nothing is read back except the NFE
+ * counters the solve returns; logits and the counter in stream order. */
+rnde_status rnde_nsde_classifier_predict(rnde_nsde* h, const float* x_dev, const float* p2_dev, const float* p3_dev, const float* y_dev,
+                                         int32_t B, int32_t T, int32_t n_classes, float t0, float t1, const float* noise_dev, int32_t n_pool,
+                                         uint64_t seed, float* logits_out_dev, int64_t* correct_dev, int64_t* nfe1_out, int64_t* nfe2_out,
+                                         void* stream);
 /* The moment-matching loss of reference experiments/sde_toy_problem.jl:27-40 on a D x T x B array of saved states (B trajectories):
  *     mu = mean over b of u[:, :, b],  var = sum over b of (u[:, :, b] - mu)^2 / (B - 1)   (Julia's var(...; dims = 3, mean = means): unbiased)
  *     loss_out_dev[0] = l2_means = mean((data_mean - mu)^2),  loss_out_dev[1] = l2_vars = mean((data_var - var)^2)   (means over D x T)

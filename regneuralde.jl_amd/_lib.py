@@ -178,6 +178,10 @@ def lib():
     L.rnde_nsde_backward_async.argtypes = [vp, vp, fp, vp, vp, vp]
     L.rnde_nsde_classifier_head.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.rnde_nsde_classifier_grad.argtypes = [vp, vp, vp, vp, vp, i32, i32, f, f, vp, i32, C.c_uint64, f, vp, vp, vp, vp, fp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]
+    if hasattr(L, "rnde_nsde_classifier_predict"):      # (an older build loaded through RNDE_LIB for an A/B run has no trajectory calls)
+        L.rnde_nsde_classifier_head_traj.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
+        L.rnde_nsde_classifier_grad_traj.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f, f, vp, i32, u64, f, vp, vp, vp, vp, fp, i64p, i64p, vp]
+        L.rnde_nsde_classifier_predict.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f, f, vp, i32, u64, vp, vp, i64p, i64p, vp]
     L.rnde_nsde_steps.argtypes = [vp, fp, i32, i32p, i32p]
     L.rnde_nsde_debug_attempt.argtypes = [vp, vp, vp, i32, f, vp, vp, vp, vp, fp, vp]
     L.rnde_nsde_set_pre_act.argtypes = [vp, i32, i32]
@@ -236,7 +240,8 @@ EXPORTS = ["rnde_version", "rnde_debug_poison_allocs", "rnde_debug_poison_bytes"
            "rnde_node_launches_per_attempt", "rnde_node_one_launch_solves", "rnde_node_tail_folds", "rnde_node_set_matrix_mode", "rnde_node_matrix_mode", "rnde_classifier_head", "rnde_node_classifier_grad", "rnde_momentum_step", "rnde_momentum_step_scaled", "rnde_adam_step",
            "rnde_comm_unique_id", "rnde_comm_create", "rnde_comm_destroy", "rnde_comm_world", "rnde_comm_last_error", "rnde_comm_library", "rnde_comm_allreduce", "rnde_comm_create_local_group", "rnde_comm_health", "rnde_comm_window_create", "rnde_comm_window_destroy", "rnde_comm_create_peers", "rnde_comm_path", "rnde_node_set_coupling", "rnde_tapes_create", "rnde_tapes_destroy", "rnde_tapes_last_error", "rnde_tapes_in_use", "rnde_tapes_node", "rnde_tapes_forward", "rnde_tapes_backward", "rnde_tapes_release",
            "rnde_nsde_param_count", "rnde_nsde_create", "rnde_nsde_destroy", "rnde_nsde_last_error", "rnde_nsde_forward",
-           "rnde_nsde_forward_saveat", "rnde_nsde_forward_everystep", "rnde_nsde_forward_replay", "rnde_nsde_backward", "rnde_nsde_backward_async", "rnde_nsde_classifier_head", "rnde_nsde_classifier_grad", "rnde_nsde_steps", "rnde_nsde_debug_attempt", "rnde_nsde_set_pre_act", "rnde_nsde_moment_grad", "rnde_moment_loss", "rnde_adabelief_step", "rnde_nsde_timing", "rnde_normal_fill", "rnde_latent_create", "rnde_latent_destroy", "rnde_latent_last_error", "rnde_latent_param_counts", "rnde_latent_encode",
+           "rnde_nsde_forward_saveat", "rnde_nsde_forward_everystep", "rnde_nsde_forward_replay", "rnde_nsde_backward", "rnde_nsde_backward_async", "rnde_nsde_classifier_head", "rnde_nsde_classifier_grad", "rnde_nsde_classifier_head_traj", "rnde_nsde_classifier_grad_traj",
+           "rnde_nsde_classifier_predict", "rnde_nsde_steps", "rnde_nsde_debug_attempt", "rnde_nsde_set_pre_act", "rnde_nsde_moment_grad", "rnde_moment_loss", "rnde_adabelief_step", "rnde_nsde_timing", "rnde_normal_fill", "rnde_latent_create", "rnde_latent_destroy", "rnde_latent_last_error", "rnde_latent_param_counts", "rnde_latent_encode",
            "rnde_latent_decode_loss", "rnde_latent_encode_backward", "rnde_adamax_step",
            "rnde_ffjord_param_count", "rnde_ffjord_create", "rnde_ffjord_destroy", "rnde_ffjord_last_error", "rnde_ffjord_forward",
            "rnde_ffjord_forward_replay", "rnde_ffjord_steps", "rnde_ffjord_backward", "rnde_ffjord_sample", "rnde_ffjord_debug_feval",

@@ -8,6 +8,7 @@
 #include "rnde_sde.h"
 #include "rnde_sdemw.h"
 #include "rnde_head.h"
+#include "rnde_head_traj.h"
 #include "rnde_moment.h"
 
 #include <algorithm>
@@ -32,6 +33,7 @@ struct rnde_nsde {
     // event that wait uses (ev_host), and the buffers of the fused step
     std::function<rnde_status(hipStream_t)> after_solve;
     DevBuf<float> cg_ws; std::vector<float> cg_sv;
+    DevBuf<float> traj_ws;   // rnde_nsde_classifier_grad_traj / _predict: the repeated input, and its cotangent or the solve's end state
     int mw = 0;    // 1: the four-waves-per-tile solve kernel (rnde_sdemw.h) for that shape, while a tile per workgroup still fits the chip
     size_t lds_mw = 0;
     int xch_wg = 0; // workgroups the meeting is sized for
@@ -650,6 +652,142 @@ extern "C" rnde_status rnde_nsde_classifier_grad(rnde_nsde* h, const float* x_de
     }
     if (reg_out_host) *reg_out_host = (float)reg;
     return nsde_backward_impl(h, ubar, regularize ? h->cg_sv.data() : nullptr, x_bar_dev, p2_bar_dev, stream, false);
+}
+
+// ---- several trajectories per input (rnde_head_traj.h) -------------------------------------------------------------------------------------
+// the limits of the three calls below, checked before anything is launched
+static rnde_status nsde_traj_check(rnde_nsde* h, const char* who, int32_t B, int32_t T, int32_t n_classes) {
+    if (T < 1) { h->err = std::string(who) + ": trajectories >= 1"; return RNDE_ERR_BAD_ARG; }
+    if (B < 1 || (long long)B * T > h->cfg.max_batch) {
+        h->err = std::string(who) + ": B >= 1 and B * trajectories <= max_batch (" + std::to_string(h->cfg.max_batch) + "), got " + std::to_string(B) + " * " +
+                 std::to_string(T);
+        return RNDE_ERR_BAD_ARG;
+    }
+    if (n_classes < 2 || n_classes > kHeadMaxC) {
+        h->err = std::string(who) + ": 2 <= n_classes <= " + std::to_string(kHeadMaxC) + ", got " + std::to_string(n_classes); return RNDE_ERR_BAD_ARG;
+    }
+    return RNDE_OK;
+}
+static unsigned traj_grid(size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 2048)); }
+// head_ws of the trajectory head: delta [C x B], the per-input cross entropy [B], the trajectory sums of u [D x B], the W-bar partials
+static rnde_status nsde_head_traj_reserve(rnde_nsde* h, int32_t B, int32_t n_classes) {
+    SCHK(h, h->head_ws.reserve((size_t)B * n_classes + B + (size_t)B * h->D + (size_t)kHeadChunks * n_classes * h->D));
+    return RNDE_OK;
+}
+
+// postsde Dense(D, C), the mean of the logits over the trajectories, Flux.Losses.logitcrossentropy and their reverse for ClassifierNSDE
+// with T trajectories per input (reference src/models/supervised_classification.jl:96-98 + experiments/mnist_nsde.jl's loss and its Tracker
+// reverse): three launches, every sum in the fixed order rnde_head_traj.h states
+extern "C" rnde_status rnde_nsde_classifier_head_traj(rnde_nsde* h, const float* u_dev, const float* p3_dev, const float* y_dev, int32_t B, int32_t T,
+                                                      int32_t n_classes, float* logits_out_dev, float* u_bar_dev, float* p3_bar_dev, float* ce_out_dev,
+                                                      void* stream) {
+    if (!h) return RNDE_ERR_BAD_ARG;
+    if (!u_dev || !p3_dev || !y_dev || !u_bar_dev || !p3_bar_dev || !ce_out_dev) { h->err = "rnde_nsde_classifier_head_traj: null pointer"; return RNDE_ERR_BAD_ARG; }
+    rnde_status st = nsde_traj_check(h, "rnde_nsde_classifier_head_traj", B, T, n_classes);
+    if (st != RNDE_OK) return st;
+    hipStream_t s = (hipStream_t)stream;
+    st = nsde_head_traj_reserve(h, B, n_classes);
+    if (st != RNDE_OK) return st;
+    float* delta = h->head_ws;
+    float* ce_col = delta + (size_t)B * n_classes;
+    float* usum = ce_col + B;
+    float* partial = usum + (size_t)B * h->D;
+    hipLaunchKernelGGL((rnde_head_traj_col_kernel<true>), dim3(B), dim3(256), 0, s, u_dev, p3_dev, y_dev, h->D, n_classes, B, T, logits_out_dev, u_bar_dev, delta,
+                       ce_col, usum);
+    hipLaunchKernelGGL(rnde_head_wgrad_kernel, dim3((h->D + 255) / 256, kHeadChunks), dim3(256), 0, s, (const float*)usum, (const float*)delta, h->D, n_classes, B, partial);
+    hipLaunchKernelGGL(rnde_head_traj_reduce_kernel, dim3((n_classes * h->D + 255) / 256), dim3(256), 0, s, (const float*)partial, (const float*)delta,
+                       (const float*)ce_col, h->D, n_classes, B, T, p3_bar_dev, ce_out_dev);
+    SCHK(h, hipGetLastError());
+    return RNDE_OK;
+}
+
+// One training-step gradient of ClassifierNSDE's loss around the solve with T trajectories per input, in ONE call (reference
+// src/models/supervised_classification.jl:82-103 with experiments/mnist_nsde.jl's loss_function and Tracker.gradient): the repeat of the
+// input, the taped solve at B T columns, the trajectory head queued before the forward's host wait, the reverse sweep, the fold of x-bar.
+extern "C" rnde_status rnde_nsde_classifier_grad_traj(rnde_nsde* h, const float* x_dev, const float* p2_dev, const float* p3_dev, const float* y_dev,
+                                                      int32_t B, int32_t T, int32_t n_classes, float t0, float t1, const float* noise_dev, int32_t n_pool,
+                                                      uint64_t seed, float lambda, float* p2_bar_dev, float* p3_bar_dev, float* x_bar_dev,
+                                                      float* ce_out_dev, float* reg_out_host, int64_t* nfe1_out, int64_t* nfe2_out, void* stream) {
+    if (!h) return RNDE_ERR_BAD_ARG;
+    if (!x_dev || !p2_dev || !p3_dev || !y_dev || !p2_bar_dev || !p3_bar_dev || !x_bar_dev || !ce_out_dev) {
+        h->err = "rnde_nsde_classifier_grad_traj: null pointer"; return RNDE_ERR_BAD_ARG;
+    }
+    rnde_status st = nsde_traj_check(h, "rnde_nsde_classifier_grad_traj", B, T, n_classes);
+    if (st != RNDE_OK) return st;
+    SCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t BT = B * T;
+    const size_t X = (size_t)h->D * B, A = X * T;
+    SCHK(h, h->cg_ws.reserve(2 * A));
+    SCHK(h, h->traj_ws.reserve(2 * A));
+    SCHK(h, h->ev_host.create(hipEventDisableTiming));
+    st = nsde_head_traj_reserve(h, B, n_classes);   // (the hook runs between an event record and the host's wait on it: it only enqueues)
+    if (st != RNDE_OK) return st;
+    float* u = h->cg_ws; float* ubar = h->cg_ws + A;
+    float* xe = h->traj_ws; float* xe_bar = h->traj_ws + A;
+    hipLaunchKernelGGL(rnde_traj_expand_kernel, dim3(traj_grid(A)), dim3(256), 0, s, x_dev, xe, (long long)X, (long long)A);
+    SCHK(h, hipGetLastError());
+    h->cg_sv.resize((size_t)h->cfg.max_attempts + 1);
+    int32_t nsv = 0;
+    h->after_solve = [&](hipStream_t q) -> rnde_status {
+        return rnde_nsde_classifier_head_traj(h, u, p3_dev, y_dev, B, T, n_classes, nullptr, ubar, p3_bar_dev, ce_out_dev, q);
+    };
+    st = nsde_forward_impl(h, xe, p2_dev, BT, t0, t1, noise_dev, n_pool, seed, nullptr, 0, u, nfe1_out, nfe2_out, h->cg_sv.data(), &nsv, 1, stream);
+    h->after_solve = nullptr;
+    if (st != RNDE_OK) return st;
+    double reg = 0.0;
+    const bool regularize = lambda != 0.f && nsv > 0 && h->cfg.regularize != RNDE_REG_NONE;
+    if (regularize) {   // lambda * mean(sv.saveval): every saved value carries the cotangent lambda / n
+        for (int i = 0; i < nsv; ++i) reg += h->cg_sv[i];
+        reg = (double)lambda * reg / nsv;
+        for (int i = 0; i < nsv; ++i) h->cg_sv[i] = lambda / (float)nsv;
+    }
+    if (reg_out_host) *reg_out_host = (float)reg;
+    st = nsde_backward_impl(h, ubar, regularize ? h->cg_sv.data() : nullptr, xe_bar, p2_bar_dev, stream, false);
+    if (st != RNDE_OK) return st;
+    hipLaunchKernelGGL(rnde_traj_fold_kernel, dim3(traj_grid(X)), dim3(256), 0, s, (const float*)xe_bar, x_bar_dev, (long long)X, T);
+    SCHK(h, hipGetLastError());
+    return RNDE_OK;
+}
+
+// The evaluation call of ClassifierNSDE (reference src/models/supervised_classification.jl:82-100 behind the presde layer, and src/metrics.jl:2-9
+// for the count; experiments/mnist_nsde.jl:154-155 evaluates with 10 trajectories): the repeat of the input, the UNTAPED solve at B T columns,
+// the logits averaged over the trajectories and, with labels, the number of inputs whose first largest logit sits at the first largest label
+// entry, ADDED to *correct_dev.  Nothing is read back but what the solve itself returns.
+extern "C" rnde_status rnde_nsde_classifier_predict(rnde_nsde* h, const float* x_dev, const float* p2_dev, const float* p3_dev, const float* y_dev,
+                                                    int32_t B, int32_t T, int32_t n_classes, float t0, float t1, const float* noise_dev, int32_t n_pool,
+                                                    uint64_t seed, float* logits_out_dev, int64_t* correct_dev, int64_t* nfe1_out, int64_t* nfe2_out,
+                                                    void* stream) {
+    if (!h) return RNDE_ERR_BAD_ARG;
+    if (!x_dev || !p2_dev || !p3_dev || !logits_out_dev) { h->err = "rnde_nsde_classifier_predict: null pointer"; return RNDE_ERR_BAD_ARG; }
+    if (!y_dev && correct_dev) { h->err = "rnde_nsde_classifier_predict: correct_dev without y_dev (nothing to count against)"; return RNDE_ERR_BAD_ARG; }
+    rnde_status st = nsde_traj_check(h, "rnde_nsde_classifier_predict", B, T, n_classes);
+    if (st != RNDE_OK) return st;
+    SCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    const int32_t BT = B * T;
+    const size_t X = (size_t)h->D * B, A = X * T;
+    SCHK(h, h->traj_ws.reserve(2 * A));
+    SCHK(h, h->ev_host.create(hipEventDisableTiming));
+    float* xe = h->traj_ws; float* u = h->traj_ws + A;
+    hipLaunchKernelGGL(rnde_traj_expand_kernel, dim3(traj_grid(A)), dim3(256), 0, s, x_dev, xe, (long long)X, (long long)A);
+    SCHK(h, hipGetLastError());
+    const int32_t D = h->D;
+    h->after_solve = [&](hipStream_t q) -> rnde_status {      // (overwrites its output: a solve that is redone queues it again)
+        hipLaunchKernelGGL((rnde_head_traj_col_kernel<false>), dim3(B), dim3(256), 0, q, (const float*)u, p3_dev, (const float*)nullptr, D, n_classes, B, T,
+                           logits_out_dev, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
+        SCHK(h, hipGetLastError());
+        return RNDE_OK;
+    };
+    st = nsde_forward_impl(h, xe, p2_dev, BT, t0, t1, noise_dev, n_pool, seed, nullptr, 0, u, nfe1_out, nfe2_out, nullptr, nullptr, 0, stream);
+    h->after_solve = nullptr;
+    if (st != RNDE_OK) return st;
+    if (y_dev && correct_dev) {      // (behind the solve's status: the counter accumulates, so it is queued exactly once)
+        hipLaunchKernelGGL(rnde_head_count_kernel, dim3((B + 255) / 256), dim3(256), 0, s, (const float*)logits_out_dev, y_dev, n_classes, B,
+                           (unsigned long long*)correct_dev);
+        SCHK(h, hipGetLastError());
+    }
+    return RNDE_OK;
 }
 
 // The leading element-wise map of each chain (include/rnde.h: rnde_pre_act; experiments/sde_toy_problem.jl:45 drifts through x -> x .^ 3).  The generic

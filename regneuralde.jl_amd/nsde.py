@@ -212,6 +212,9 @@ class TrackedNeuralDSDE:
         return u, nfe1, nfe2, (SavedValues(saveval) if self.regularize else None)
 
 
+MAX_HEAD_CLASSES = 16      # kHeadMaxC of csrc/rnde_head.h: the classes the device head serves
+
+
 def _expand(x, d):
     """supervised_classification.jl:102-103: repeat along the batch dimension (Julia's last dimension = torch's first)."""
     return x.repeat(d, *([1] * (x.dim() - 1)))
@@ -249,6 +252,82 @@ class ClassifierNSDE:
         z = z.reshape(trajectories, bsize, -1).mean(dim=0)                       # :98
         return z, nfe1, nfe2, sv
 
+    def predict(self, x, trajectories=10, y=None, noise=None, correct=None):
+        """The evaluation call (supervised_classification.jl:82-100 as experiments/mnist_nsde.jl:154-155 uses it, src/metrics.jl:2-9) through ONE
+        library call, rnde_nsde_classifier_predict: the pre-layer runs once on the B rows, the library repeats its output `trajectories` times,
+        solves UNTAPED, applies the post-layer and averages the logits over the trajectories.  No tape, no autograd graph.
+        Returns (z, nfe1, nfe2); with labels `y` (B, C) also the device int64 counter (1 element) to which the number of inputs whose first
+        largest logit sits at the first largest label entry was ADDED -- `correct` to go on accumulating into a caller's counter, else a fresh
+        zeroed one.  noise: a pool of standard normals (n_pool, 2, trajectories * B, D) in the trajectory-major order of `_expand`, or None for
+        the library's stream."""
+        nsde = self.nsde
+        bsize = x.shape[0]
+        n_in, n_h = self.pre_shape
+        n_u, n_c = self.post_shape
+        if int(trajectories) != trajectories or trajectories < 1:
+            raise ValueError(f"predict: trajectories must be an integer >= 1 (got {trajectories})")
+        trajectories = int(trajectories)
+        if not 2 <= n_c <= MAX_HEAD_CLASSES:
+            raise ValueError(f"predict: the device head serves 2 .. {MAX_HEAD_CLASSES} classes (the post-layer has {n_c})")
+        if bsize < 1 or bsize * trajectories > nsde.max_batch:
+            raise ValueError(f"predict: batch * trajectories = {bsize} * {trajectories} exceeds the layer's max_batch = {nsde.max_batch}")
+        if correct is not None and y is None:
+            raise ValueError("predict: a counter without labels y")
+        if not x.is_cuda:
+            raise RuntimeError("ClassifierNSDE.predict runs on the MI355X only: x must be a cuda tensor (no CPU fallback)")
+        _check_f32("x", x)
+        tensors = dict(p1=self.p1, p2=self.p2, p3=self.p3)
+        if y is not None:
+            _check_f32("y", y)
+            if tuple(y.shape) != (bsize, n_c):
+                raise ValueError(f"predict: y must be (B, C) = ({bsize}, {n_c})")
+            tensors["y"] = y
+        if noise is not None:
+            _check_f32("noise", noise)
+            if noise.dim() != 4 or tuple(noise.shape[1:]) != (2, bsize * trajectories, n_u):
+                raise ValueError("noise: cuda tensor of shape (n_pool, 2, trajectories * B, D)")
+            tensors["noise"] = noise
+        if correct is not None:
+            if correct.dtype != torch.int64 or correct.numel() != 1:
+                raise TypeError("predict: correct must be a one-element int64 tensor")
+            tensors["correct"] = correct
+        _check_on_device(x, **tensors)
+        L = _lib.lib()
+        with torch.no_grad():
+            p1, p2, p3 = self.p1.detach(), self.p2.detach().contiguous(), self.p3.detach().contiguous()
+            h = self._dense(x.reshape(bsize, -1), p1, self.pre_shape).contiguous()     # :93-94 as __call__ computes it, on the B rows
+            hd = nsde._acquire(h)
+            z = torch.empty((bsize, n_c), dtype=torch.float32, device=h.device)
+            if y is not None:
+                y = y.contiguous()
+                if correct is None:
+                    correct = torch.zeros(1, dtype=torch.int64, device=h.device)
+            if noise is not None:
+                noise = noise.contiguous()
+            n1, n2 = C.c_int64(0), C.c_int64(0)
+            stream = C.c_void_p(torch.cuda.current_stream(h.device).cuda_stream)
+            nsde.seed += 1
+            _lib.check_nsde(hd.ptr, L.rnde_nsde_classifier_predict(
+                hd.ptr, h.data_ptr(), p2.data_ptr(), p3.data_ptr(), y.data_ptr() if y is not None else None, bsize, trajectories, n_c,
+                nsde.tspan[0], nsde.tspan[1], noise.data_ptr() if noise is not None else None, 0 if noise is None else noise.shape[0], nsde.seed,
+                z.data_ptr(), correct.data_ptr() if y is not None else None, C.byref(n1), C.byref(n2), stream))
+            nsde.last_nfe = (int(n1.value), int(n2.value))
+            self._keep = (h, p2, p3, y, noise, correct)          # buffers the enqueued kernels still use
+        if y is None:
+            return z, int(n1.value), int(n2.value)
+        return z, int(n1.value), int(n2.value), correct
+
+
+def nsde_accuracy(model, batches, trajectories=10):
+    """reference src/metrics.jl:4-18 for ClassifierNSDE as experiments/mnist_nsde.jl:154-155 calls it (`trajectories = 10`): the fraction of
+    inputs classified correctly, as classifier.accuracy returns it.  Every batch is one ClassifierNSDE.predict call that adds its matches to
+    ONE device counter; the counter is read back once, behind the last batch."""
+    correct, total = None, 0
+    for x, y in batches:
+        correct = model.predict(x, trajectories=trajectories, y=y, correct=correct)[3]
+        total += x.shape[0]
+    return (int(correct.item()) if correct is not None else 0) / max(total, 1)
+
 
 def nsde_loss_function(x, y, model, p1=None, p2=None, p3=None, trajectories=1, lam=1.0e2, regularize=True, agg=torch.mean, func="error_est"):
     """experiments/mnist_nsde.jl:88-118 (without the logger): logitcrossentropy(pred, y) + lambda * agg(sv.saveval).  `func`: the experiment's
@@ -271,6 +350,8 @@ def fused_nsde_loss_and_grad(model, x, y, trajectories=1, lam=1.0e2, regularize=
     for name, t in (("x", x), ("y", y), ("p1", model.p1), ("p2", model.p2), ("p3", model.p3)):
         _check_f32(name, t)
     L = _lib.lib()
+    if trajectories > 1 and 2 <= model.post_shape[1] <= MAX_HEAD_CLASSES and os.environ.get("RNDE_ONE_CALL", "1") != "0":
+        return _fused_nsde_traj(model, x, y, int(trajectories), lam, regularize)     # (RNDE_ONE_CALL=0: the chain of torch products below, for A/B)
     with torch.no_grad():
         bsize = x.shape[0]
         xe = _expand(x.reshape(bsize, -1), trajectories).contiguous()
@@ -336,6 +417,38 @@ def fused_nsde_loss_and_grad(model, x, y, trajectories=1, lam=1.0e2, regularize=
         model._keep = (ubar, hbar, u, h)          # buffers the enqueued kernels still use
         model.p1.grad, model.p2.grad, model.p3.grad = p1bar, p2bar, p3bar
     return ce + reg, ce, reg, int(n1.value), int(n2.value)
+
+
+def _fused_nsde_traj(model, x, y, trajectories, lam, regularize):
+    """fused_nsde_loss_and_grad with several trajectories per input as ONE library call, rnde_nsde_classifier_grad_traj: the pre-layer runs on
+    the B rows, the library repeats its output, solves (taped), runs the trajectory head and the reverse sweep and folds the cotangent of
+    the repeated input back onto the B rows, from which the pre-layer's gradient follows."""
+    nsde = model.nsde
+    L = _lib.lib()
+    with torch.no_grad():
+        bsize = x.shape[0]
+        x2 = x.reshape(bsize, -1)
+        p1, p2, p3 = model.p1.detach(), model.p2.detach().contiguous(), model.p3.detach().contiguous()
+        n_in, n_h = model.pre_shape
+        n_c = model.post_shape[1]
+        h = torch.addmm(p1[n_in * n_h:], x2, p1[: n_in * n_h].view(n_in, n_h)).contiguous()      # supervised_classification.jl:93-94, on the B rows
+        hd = nsde._acquire(h)
+        stream = C.c_void_p(torch.cuda.current_stream(h.device).cuda_stream)
+        n1, n2, reg_h = C.c_int64(0), C.c_int64(0), C.c_float(0.0)
+        hbar, p2bar, p3bar = torch.empty_like(h), torch.empty_like(p2), torch.empty_like(p3)
+        ce_t = torch.empty(1, dtype=torch.float32, device=h.device)
+        yc = y.contiguous()
+        nsde.seed += 1
+        _lib.check_nsde(hd.ptr, L.rnde_nsde_classifier_grad_traj(
+            hd.ptr, h.data_ptr(), p2.data_ptr(), p3.data_ptr(), yc.data_ptr(), bsize, trajectories, n_c, nsde.tspan[0], nsde.tspan[1], None, 0,
+            nsde.seed, float(lam) if (regularize and nsde.regularize) else 0.0, p2bar.data_ptr(), p3bar.data_ptr(), hbar.data_ptr(),
+            ce_t.data_ptr(), C.byref(reg_h), C.byref(n1), C.byref(n2), stream))
+        nsde.last_nfe = (int(n1.value), int(n2.value))
+        p1bar = torch.cat([(x2.t() @ hbar).reshape(-1), hbar.sum(dim=0)])
+        model._keep = (hbar, h, p2, p3, yc)          # buffers the enqueued kernels still use
+        model.p1.grad, model.p2.grad, model.p3.grad = p1bar, p2bar, p3bar
+        reg = float(reg_h.value)
+        return ce_t[0] + reg, ce_t[0], reg, int(n1.value), int(n2.value)
 
 
 def _check_on_device(ref, **tensors):

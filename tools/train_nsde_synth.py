@@ -38,12 +38,9 @@ SETUPS = {"vanilla": ("SOSRI", 0.0, None), "error_est": ("SOSRI", 10.0, save_fun
 
 
 def accuracy(model, data, trajectories, func):
-    hit = n = 0
-    with torch.no_grad():
-        for xb, yb in data:
-            pred = model(xb.reshape(BATCH, -1), trajectories=trajectories, func=func)[0]
-            hit += int((pred.argmax(1) == yb.argmax(1)).sum()); n += BATCH
-    return 100.0 * hit / n
+    """percent correct: one rnde_nsde_classifier_predict per batch, the matches counted on the device and read back once (nsde.py::nsde_accuracy)"""
+    import regneuralde_jl_amd as rn
+    return 100.0 * rn.nsde_accuracy(model, ((xb.reshape(BATCH, -1), yb) for xb, yb in data), trajectories=trajectories)
 
 
 def run(reg, train, test, epochs, device, seed):
