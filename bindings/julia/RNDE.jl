@@ -615,6 +615,42 @@ function nsde_classifier_predict(h::NsdeHandle, x::ROCMatrix{Float32}, p2::ROCVe
     return logits, nfe1[], nfe2[]
 end
 
+# The evaluation call of ClassifierNODE (experiments/mnist_node.jl:185-186, :250-251; src/metrics.jl:2-18) with preode = identity: the untaped
+# solve of x (D x B), the logits (C x B) of the post-layer p3 on its end state and, with labels y (C x B), the matches of argmax(logits)
+# against argmax(y) ADDED to the one-element device counter `correct` (zero it once per data set, read it once).  Returns (logits, nfe).
+function classifier_predict(h::Handle, x::ROCMatrix{Float32}, p2::ROCVector{Float32}, p3::ROCVector{Float32}, n_classes::Integer, tspan;
+                            y::Union{Nothing, ROCMatrix{Float32}} = nothing, correct::Union{Nothing, ROCVector{Int64}} = nothing)
+    (y === nothing && correct !== nothing) && error("classifier_predict: a counter without labels")
+    logits = ROCMatrix{Float32}(undef, n_classes, size(x, 2))
+    nfe = Ref{Int64}(0)
+    st = GC.@preserve x p2 p3 y correct logits begin
+        ccall((:rnde_node_classifier_predict, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Cfloat, Cfloat, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int64}, Ptr{Cvoid}),
+              h.ptr, devptr(x), devptr(p2), devptr(p3), y === nothing ? C_NULL : devptr(y), size(x, 2), n_classes,
+              Float32(tspan[1]), Float32(tspan[2]), devptr(logits), correct === nothing ? C_NULL : devptr(correct), nfe, _stream())
+    end
+    st == 0 || error("rnde_node_classifier_predict: ", unsafe_string(ccall((:rnde_last_error, LIB), Cstring, (Ptr{Cvoid},), h.ptr)))
+    return logits, nfe[]
+end
+
+# One batch of total_loss_on_dataset (experiments/latent_ode.jl:271-292) behind the layer call: gen_to_data (p4) on the saved states res
+# (20 x T x B) and sum((pred .* m .- d .* m) .^ 2) ./ sum(m) per sample against x = vcat(d, m, _t) (75 x T x B).  `lat` is the rnde_latent*
+# of rnde_latent_create (this module wraps no latent handle: the pointer is passed as it is).  acc_sum (1 Float64) and acc_count (1 Int64):
+# the data set's running sum and count on the device, both or neither.  Returns the B per-sample values.
+function latent_decode_mse(lat::Ptr{Cvoid}, res::ROCArray{Float32, 3}, p4::ROCVector{Float32}, x::ROCArray{Float32, 3};
+                           acc_sum::Union{Nothing, ROCVector{Float64}} = nothing, acc_count::Union{Nothing, ROCVector{Int64}} = nothing)
+    ((acc_sum === nothing) != (acc_count === nothing)) && error("latent_decode_mse: acc_sum and acc_count go together")
+    mse = ROCVector{Float32}(undef, size(res, 3))
+    st = GC.@preserve res p4 x acc_sum acc_count mse begin
+        ccall((:rnde_latent_decode_mse, LIB), Cint,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+              lat, devptr(res), devptr(p4), devptr(x), size(res, 3), size(res, 2), devptr(mse),
+              acc_sum === nothing ? C_NULL : devptr(acc_sum), acc_count === nothing ? C_NULL : devptr(acc_count), _stream())
+    end
+    st == 0 || error("rnde_latent_decode_mse: ", unsafe_string(ccall((:rnde_latent_last_error, LIB), Cstring, (Ptr{Cvoid},), lat)))
+    return mse
+end
+
 # ---- optimiser step and the data-parallel collective -------------------------------------------------
 # Optimiser(InvDecay(gamma), Momentum(eta, rho)) on one flat group, in place (src/utils.jl:149-156, mnist_node.jl:130);
 # `n` is the group's InvDecay counter (starts at 1, the caller increments it); gscale = 1 / nworkers after a summed all-reduce.

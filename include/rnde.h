@@ -368,6 +368,24 @@ rnde_status rnde_node_classifier_grad(rnde_node* h, const float* x_dev, const fl
                                       float* p2_bar_dev, float* p3_bar_dev, float* x_bar_dev, float* ce_out_dev,
                                       float* reg_out_host, int64_t* nfe_out, rnde_comm* comm, void* stream);
 
+/* The evaluation call of ClassifierNODE (reference src/metrics.jl:2-18 around src/models/supervised_classification.jl:40-46;
+ * experiments/mnist_node.jl:185-186, :250-251 run it over both loaders at the end of every epoch): the UNTAPED solve (rnde_node_forward with
+ * keep_tape = 0, into a workspace the handle owns; like every untaped forward it drops a tape the handle holds), postode Dense(D, C) on the
+ * end state -> logits_out_dev (C x B, required) and, when y_dev (C x B) is given, the number of inputs whose predicted class -- the FIRST
+ * index of the largest logit, Julia's argmax -- equals the first index of the largest entry of y's column, ADDED to the device int64
+ * *correct_dev (the caller zeroes it once per data set and reads it once).  y_dev may be NULL; correct_dev may be NULL and must be NULL
+ * when y_dev is (RNDE_ERR_BAD_ARG).  The logits are the bits rnde_classifier_head computes from the same end state.
+ * ONE head launch does logits, both argmaxes and the count.  Without labels it is queued in front of the solve's host wait (a solve that is
+ * redone queues it again and only overwrites logits_out_dev); WITH labels the fused count is kept and the counting variant is queued exactly
+ * once, behind the solve's final status, so a redone solve never counts twice.
+ * Served on every engine rnde_node_forward(keep_tape = 0) serves: the stage engine in both matrix modes, the chain engine, the tiled engine.
+ * Limits, checked before anything is launched: 1 <= B <= cfg.max_batch, 2 <= n_classes <= 16, D <= 1024, t1 > t0.
+ * Nothing is read back except what the solve itself reads (its step log): *nfe_out is valid on return, the logits and the counter in
+ * stream order. */
+rnde_status rnde_node_classifier_predict(rnde_node* h, const float* x_dev, const float* p2_dev, const float* p3_dev,
+                                         const float* y_dev, int32_t B, int32_t n_classes, float t0, float t1,
+                                         float* logits_out_dev, int64_t* correct_dev, int64_t* nfe_out, void* stream);
+
 /* Optimiser update of the reference's training step, one launch per parameter group:
  * Flux.Optimise.Optimiser(InvDecay(gamma), Momentum(eta, rho)) applied by update_parameters! -- replaces reference
  * experiments/mnist_node.jl:130 + src/utils.jl:149-156 for one flat group:
@@ -661,6 +679,15 @@ rnde_status rnde_latent_encode(rnde_latent* h, const float* x_dev, const float* 
 /* loss2_out_dev[0] = -mean_b(ll_b), [1] = mean_b(KL_b); res_bar_out_dev (20 x T x B) and p4_bar_out_dev (777) are the cotangents of term [0]. */
 rnde_status rnde_latent_decode_loss(rnde_latent* h, const float* res_dev, const float* p4_dev, const float* x_dev, int32_t B, int32_t T,
                                     float* loss2_out_dev, float* res_bar_out_dev, float* p4_bar_out_dev, void* stream);
+/* The evaluation pass, total_loss_on_dataset (experiments/latent_ode.jl:271-292) for one batch: gen_to_data on every saved state (the same
+ * product, in the same order, as rnde_latent_decode_loss), then per sample
+ *     mse_b = sum_{f,t} (pred * mask - data * mask)^2 / sum_{f,t} mask                                          (latent_ode.jl:281-286)
+ * -> mse_out_dev (B floats, required); sum_b mse_b, added in increasing b in fp64, is ADDED to *sum_dev and B to *count_dev (both may be
+ * NULL, and one is NULL exactly when the other is: RNDE_ERR_BAD_ARG otherwise); the data set's loss is sum / count, read once.  Layouts as
+ * above; B <= max_batch, T <= max_T.  Needs no rnde_latent_encode of the same batch.  A sample with no observed entry gives what the
+ * reference gives, a division by zero (NaN, or Inf); it is not special-cased.  Every sum has a fixed order: the same bits run to run. */
+rnde_status rnde_latent_decode_mse(rnde_latent* h, const float* res_dev, const float* p4_dev, const float* x_dev, int32_t B, int32_t T,
+                                   float* mse_out_dev, double* sum_dev, int64_t* count_dev, void* stream);
 /* z0_bar_dev: 20 x B from the layer's reverse pass; the KL term enters with weight lambda_k (latent_ode.jl:178, :232). */
 /* Flux.Optimise.Optimiser(InvDecay(gamma), AdaMax(eta, (beta1, beta2))) on one flat parameter group, in place (experiments/latent_ode.jl:108).
  * m, u: the caller's state arrays (zeros at the first step); n: the InvDecay counter (1 at the first step); beta1_pow: Flux's running

@@ -126,6 +126,9 @@ def lib():
     L.rnde_node_matrix_mode.argtypes = [vp]
     L.rnde_classifier_head.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.rnde_node_classifier_grad.argtypes = [vp, vp, vp, vp, vp, i32, i32, f, f, f, vp, vp, vp, vp, fp, C.POINTER(C.c_int64), vp, vp]
+    if hasattr(L, "rnde_node_classifier_predict"):      # (an older build loaded through RNDE_LIB for an A/B run has no evaluation calls)
+        L.rnde_node_classifier_predict.argtypes = [vp, vp, vp, vp, vp, i32, i32, f, f, vp, vp, i64p, vp]
+        L.rnde_latent_decode_mse.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
     L.rnde_momentum_step.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, f, f, f, vp]
     u64 = C.c_uint64
     L.rnde_momentum_step_scaled.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, f, f, f, f, vp]
@@ -250,7 +253,8 @@ EXPORTS = ["rnde_version", "rnde_debug_poison_allocs", "rnde_debug_poison_bytes"
            "rnde_ffjord_chain_param_count", "rnde_ffjord_create_chain", "rnde_ffjord_forward_exact", "rnde_ffjord_forward_exact_replay",
            "rnde_ffjord_set_track_ctrl", "rnde_ffjord_track_ctrl",
            "rnde_node_create_tiled", "rnde_node_tiled_lds_bytes", "rnde_node_set_tracking", "rnde_node_tracking", "rnde_node_attempts_ext",
-           "rnde_node_tiled_reserve_saveat", "rnde_node_tiled_saveat_capacity", "rnde_debug_arm_replay"]
+           "rnde_node_tiled_reserve_saveat", "rnde_node_tiled_saveat_capacity", "rnde_debug_arm_replay",
+           "rnde_node_classifier_predict", "rnde_latent_decode_mse"]
 
 
 def check(h, status):

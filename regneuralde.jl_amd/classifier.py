@@ -15,6 +15,9 @@ import torch
 
 from .layers import Dense
 from .node import TrackedNeuralODE
+from .nsde import MAX_HEAD_CLASSES
+
+MAX_HEAD_ROWS = 1024      # 256 * kHeadRowsPerThread of csrc/rnde_head.h: the state rows the device head serves
 
 
 class ClassifierNODE:
@@ -40,6 +43,80 @@ class ClassifierNODE:
         W = p3[: n_in * n_out].view(n_in, n_out)                                    # (in, out) row-major == out x in col-major
         b = p3[n_in * n_out:]
         return u @ W + b, nfe, sv
+
+    def predict(self, x, y=None, correct=None, tspan=None):
+        """The evaluation call (supervised_classification.jl:40-46 as experiments/mnist_node.jl:185-186 uses it through src/metrics.jl:2-18)
+        through ONE library call, rnde_node_classifier_predict: the UNTAPED solve, the post-layer on its end state and, with labels, the
+        argmax match count.  No tape, no autograd graph; a tape this layer holds for a pending backward is left alone (the call runs on
+        an untaped handle).  Returns (logits (B, C), nfe, correct_or_None): with labels `y` (B, C) the device int64 counter (1 element) to
+        which the number of inputs whose first largest logit sits at the first largest label entry was ADDED -- `correct` to go on
+        accumulating into a caller's counter, else a fresh zeroed one.  The logits are the bits the training head (rnde_classifier_head)
+        computes from the same end state."""
+        import ctypes as C
+        from . import _lib
+        from .node import _check_f32
+        node = self.node
+        bsize = x.shape[0]
+        n_u, n_c = self.post_shape
+        if not 2 <= n_c <= MAX_HEAD_CLASSES:
+            raise ValueError(f"predict: the device head serves 2 .. {MAX_HEAD_CLASSES} classes (the post-layer has {n_c})")
+        if n_u > MAX_HEAD_ROWS:
+            raise ValueError(f"predict: the device head serves states of up to {MAX_HEAD_ROWS} rows (the post-layer reads {n_u})")
+        if bsize < 1 or bsize > node.max_batch:
+            raise ValueError(f"predict: batch = {bsize} is outside 1 .. the layer's max_batch = {node.max_batch}")
+        if correct is not None and y is None:
+            raise ValueError("predict: a counter without labels y")
+        ts = node.tspan if tspan is None else [float(tspan[0]), float(tspan[1])]
+        if not ts[1] > ts[0]:
+            raise ValueError(f"predict: tspan must increase (got {ts})")
+        if x.numel() != bsize * n_u:
+            raise ValueError(f"predict: x has {x.numel() // max(bsize, 1)} features per input, the layer's state has {n_u}")
+        tensors = dict(x=x, p2=self.p2, p3=self.p3)
+        if y is not None:
+            if tuple(y.shape) != (bsize, n_c):
+                raise ValueError(f"predict: y must be (B, C) = ({bsize}, {n_c})")
+            tensors["y"] = y
+        for name, t in tensors.items():
+            _check_f32(name, t)
+        if correct is not None:
+            if correct.dtype != torch.int64 or correct.numel() != 1:
+                raise TypeError("predict: correct must be a one-element int64 tensor")
+            tensors["correct"] = correct
+        for name, t in tensors.items():
+            if t.device != x.device:
+                raise ValueError(f"predict: {name} is on {t.device}, x on {x.device}: all of them must live on the same device")
+        if not x.is_cuda:
+            raise RuntimeError("ClassifierNODE.predict runs on the MI355X only: x must be a cuda tensor (no CPU fallback)")
+        x2 = x.reshape(bsize, -1).contiguous()
+        L = _lib.lib()
+        with torch.no_grad():
+            p2, p3 = self.p2.detach().contiguous(), self.p3.detach().contiguous()
+            node._func = node.resolve_func(None)
+            h = node._acquire(x2, False)
+            z = torch.empty((bsize, n_c), dtype=torch.float32, device=x2.device)
+            if y is not None:
+                y = y.contiguous()
+                if correct is None:
+                    correct = torch.zeros(1, dtype=torch.int64, device=x2.device)
+            nfe = C.c_int64(0)
+            stream = C.c_void_p(torch.cuda.current_stream(x2.device).cuda_stream)
+            _lib.check(h.ptr, L.rnde_node_classifier_predict(
+                h.ptr, x2.data_ptr(), p2.data_ptr(), p3.data_ptr(), y.data_ptr() if y is not None else None, bsize, n_c, ts[0], ts[1],
+                z.data_ptr(), correct.data_ptr() if y is not None else None, C.byref(nfe), stream))
+            node.last_nfe = int(nfe.value)
+            self._keep = (x2, p2, p3, y, correct)                 # buffers the enqueued head launch still uses
+        return z, int(nfe.value), (correct if y is not None else None)
+
+
+def node_accuracy(model, batches):
+    """reference src/metrics.jl:4-18 for ClassifierNODE as experiments/mnist_node.jl:185-186, :250-251 call it: the fraction of inputs
+    classified correctly, as `accuracy` returns it.  Every batch is one ClassifierNODE.predict call that adds its matches to ONE device
+    counter; the counter is read back once, behind the last batch."""
+    correct, total = None, 0
+    for x, y in batches:
+        correct = model.predict(x, y=y, correct=correct)[2]
+        total += x.shape[0]
+    return (int(correct.item()) if correct is not None else 0) / max(total, 1)
 
 
 def fused_loss_and_grad(model, x, y, lam=1.0e2, regularize=True, tspan=None, sync=True, flat=None, reducer=None, func=None, agg="mean"):

@@ -16,10 +16,13 @@
 //                                pass over whole records; per-workgroup partials summed in a fixed order (deterministic, no float atomics)
 //   rnde_latent_enc_*            Dense(100, 50, tanh) -> Dense(50, 40), z0 = eps * exp(logvar / 2) + mu0, KL per sample (+ reverse)
 //   rnde_latent_dec_loss_kernel  Dense(20, 37) on every saved state, masked Gaussian log likelihood / observed count, and the reverse of both
+//   rnde_latent_dec_mse_kernel   evaluation (latent_ode.jl:271-292): the same Dense(20, 37), masked squared error / observed count per sample;
+//                                rnde_latent_mse_sum_kernel adds the samples' values to the data set's running sum and count
 // Layouts: Julia's F x T x B arrays as they are (feature fastest): element (f, t, b) at (b * T + t) * F + f.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "rnde_device.h"      // wave_sum_f: the fixed DPP tree (rnde_latent_dec_mse_kernel)
 
 namespace rnde_lat {
 
@@ -723,6 +726,56 @@ __global__ __launch_bounds__(256) void rnde_latent_loss_kernel(const float* __re
         __syncthreads();
     }
     if (threadIdx.x == 0) { out[0] = (float)(-sa[0] / B); out[1] = (float)(sc[0] / B); }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The evaluation pass (latent_ode.jl:271-292, total_loss_on_dataset): gen_to_data + the masked squared error per sample, in the shape of
+// rnde_latent_dec_loss_kernel -- one workgroup (one wave) per sample, one thread per save time, the decoder product in the same order
+// (bias first, then one fmaf chain over the 20 latent rows), so pred is the same bits as training's.
+//   mse[b] = sum_{f,t} (pred * mask - data * mask)^2 / sum_{f,t} mask
+// Order of the sums: per thread (save time) over f = 0 .. 36 in order, the square added with one fmaf and the mask with one add; then both over
+// the 64 lanes by the fixed DPP tree (wave_sum_f; lanes t >= T carry zeros); then ONE division.  A sample with no observed entry gives what
+// the reference gives: 0 / 0.
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct DecMseParams {
+    const float* res;      // kLat x T x B
+    const float* p4; const float* x;      // x: kNX x T x B (data rows 0..36, mask rows 37..73)
+    float* mse;            // [B]
+    int B, T;
+};
+__global__ __launch_bounds__(64) void rnde_latent_dec_mse_kernel(const DecMseParams Q) {
+    __shared__ float Ws[kP4];
+    const int b = blockIdx.x, t = threadIdx.x;
+    for (int i = t; i < kP4; i += 64) Ws[i] = Q.p4[i];
+    __syncthreads();
+    float ssum = 0.f, msum = 0.f;
+    if (t < Q.T) {
+        const float* xp = Q.x + ((size_t)b * Q.T + t) * kNX;
+        const float* rp = Q.res + ((size_t)b * Q.T + t) * kLat;
+        float z[kLat];
+#pragma unroll
+        for (int j = 0; j < kLat; ++j) z[j] = rp[j];
+        for (int i = 0; i < kIn; ++i) {
+            float pr = Ws[kLat * kIn + i];
+#pragma unroll
+            for (int j = 0; j < kLat; ++j) pr = fmaf(Ws[j * kIn + i], z[j], pr);
+            const float mk = xp[kIn + i];
+            const float d = pr * mk - xp[i] * mk;
+            ssum = fmaf(d, d, ssum);
+            msum += mk;
+        }
+    }
+    const float S = rnde::wave_sum_f(ssum), M = rnde::wave_sum_f(msum);      // (all 64 lanes take part)
+    if (t == 0) Q.mse[b] = S / M;
+}
+// behind it, one workgroup: the B values added in increasing b in fp64, that sum ADDED to *sum and B to *count -- one thread, plain loads and
+// stores, no atomics (calls on one stream are serial: the accumulators are read and written by this launch alone)
+__global__ __launch_bounds__(64) void rnde_latent_mse_sum_kernel(const float* __restrict__ mse, int B, double* __restrict__ sum, long long* __restrict__ count) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double s = 0.0;
+    for (int b = 0; b < B; ++b) s += (double)mse[b];
+    *sum = *sum + s;
+    *count = *count + (long long)B;
 }
 
 // Flux.Optimise.Optimiser(InvDecay(gamma), AdaMax(eta, (beta1, beta2))) on one flat group, in place (latent_ode.jl:108; Flux 0.11 `apply!`):

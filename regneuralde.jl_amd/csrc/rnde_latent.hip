@@ -139,6 +139,22 @@ extern "C" rnde_status rnde_latent_decode_loss(rnde_latent* h, const float* res_
     return run_fused<kLat, 40>(h, Jl, res_dev, h->gD, B * T, s, h->raw, h->raw2);
 }
 
+// The evaluation pass (latent_ode.jl:278-286): mse_b per sample, then -- when the caller keeps accumulators -- their sum in increasing b (fp64) added
+// to *sum_dev and B to *count_dev by a second launch of one workgroup.  Needs no encode of the same batch: nothing of the KL term enters.
+extern "C" rnde_status rnde_latent_decode_mse(rnde_latent* h, const float* res_dev, const float* p4_dev, const float* x_dev, int32_t B, int32_t T,
+                                              float* mse_out_dev, double* sum_dev, int64_t* count_dev, void* stream) {
+    rnde_status st = check_shape(h, B, T);
+    if (st != RNDE_OK) return st;
+    if (!res_dev || !p4_dev || !x_dev || !mse_out_dev) { h->err = "rnde_latent_decode_mse: null pointer"; return RNDE_ERR_BAD_ARG; }
+    if (!sum_dev != !count_dev) { h->err = "rnde_latent_decode_mse: sum_dev and count_dev go together (both or neither)"; return RNDE_ERR_BAD_ARG; }
+    hipStream_t s = (hipStream_t)stream;
+    DecMseParams D{res_dev, p4_dev, x_dev, mse_out_dev, B, T};
+    hipLaunchKernelGGL(rnde_latent_dec_mse_kernel, dim3(B), dim3(64), 0, s, D);
+    if (sum_dev) hipLaunchKernelGGL(rnde_latent_mse_sum_kernel, dim3(1), dim3(64), 0, s, (const float*)mse_out_dev, B, sum_dev, (long long*)count_dev);
+    LCHK(h, hipGetLastError());
+    return RNDE_OK;
+}
+
 extern "C" rnde_status rnde_latent_encode_backward(rnde_latent* h, const float* z0_bar_dev, float lambda_k, const float* p1_dev, const float* p2_dev,
                                                    const float* x_dev, float* p1_bar_out_dev, float* p2_bar_out_dev, void* stream) {
     if (!h) return RNDE_ERR_BAD_ARG;

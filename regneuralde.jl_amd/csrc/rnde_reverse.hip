@@ -2,6 +2,7 @@
 // GEMMs, the classifier head and its fused training step, the optimiser steps.  The handle and what rnde.hip offers this file: rnde_node.h.
 #include "rnde_node.h"
 #include "rnde_wgradx.h"
+#include "rnde_head_eval.h"
 
 static rnde_status chain_bwd_run(rnde_node* h, const float* u_bar_dev, const float* saveval_bar_host, float* x_bar_dev,
                                  float* p_bar_dev, float* tspan_bar_host, hipStream_t s, bool sync = true, float* tspan_bar_dev = nullptr);
@@ -578,6 +579,49 @@ extern "C" rnde_status rnde_node_classifier_grad(rnde_node* h, const float* x_de
         if (st != RNDE_OK) { h->err = std::string("all-reduce: ") + rnde_comm_last_error(comm); return st; }
     }
     return RNDE_OK;
+}
+
+// ---- the evaluation call of ClassifierNODE (reference src/metrics.jl:2-18 around src/models/supervised_classification.jl:40-46) ------------
+// The untaped solve into a workspace of the handle, then ONE head launch (rnde_head_eval.h): logits, both argmaxes and the count.  Which
+// variant is queued where: without labels the launch only overwrites logits_out_dev, so it goes through h->after_solve in front of the host's
+// wait (as rnde_node_classifier_grad queues its head; a solve that is redone queues it again).  With labels the fused count is kept and the
+// counting variant is queued EXACTLY ONCE, behind the solve's final status: the counter accumulates, a redone solve must not count twice.
+// The tiled engine's solve does not pass through wait_for_host: its head is queued behind the solve in both cases.
+static rnde_status launch_head_eval(rnde_node* h, const float* u, const float* p3, const float* y, int32_t B, int32_t C, float* logits, int64_t* correct,
+                                    hipStream_t s) {
+    unsigned long long* cnt = (unsigned long long*)correct;
+    const dim3 grid(B), blk(256);
+    if (y && cnt) {
+        if (C == 10) hipLaunchKernelGGL((rnde_head_eval_kernel<10, true>), grid, blk, 0, s, u, p3, y, h->D, C, logits, cnt);
+        else hipLaunchKernelGGL((rnde_head_eval_kernel<0, true>), grid, blk, 0, s, u, p3, y, h->D, C, logits, cnt);
+    } else {
+        if (C == 10) hipLaunchKernelGGL((rnde_head_eval_kernel<10, false>), grid, blk, 0, s, u, p3, (const float*)nullptr, h->D, C, logits, (unsigned long long*)nullptr);
+        else hipLaunchKernelGGL((rnde_head_eval_kernel<0, false>), grid, blk, 0, s, u, p3, (const float*)nullptr, h->D, C, logits, (unsigned long long*)nullptr);
+    }
+    HIPCHK(h, hipGetLastError());
+    return RNDE_OK;
+}
+extern "C" rnde_status rnde_node_classifier_predict(rnde_node* h, const float* x_dev, const float* p2_dev, const float* p3_dev, const float* y_dev,
+                                                    int32_t B, int32_t n_classes, float t0, float t1, float* logits_out_dev, int64_t* correct_dev,
+                                                    int64_t* nfe_out, void* stream) {
+    if (!h) return RNDE_ERR_BAD_ARG;
+    if (!x_dev || !p2_dev || !p3_dev || !logits_out_dev) { h->err = "rnde_node_classifier_predict: null pointer"; return RNDE_ERR_BAD_ARG; }
+    if (!y_dev && correct_dev) { h->err = "rnde_node_classifier_predict: correct_dev without y_dev (nothing to count against)"; return RNDE_ERR_BAD_ARG; }
+    if (B < 1 || B > h->cfg.max_batch) { h->err = "rnde_node_classifier_predict: 1 <= B <= max_batch = " + std::to_string(h->cfg.max_batch); return RNDE_ERR_BAD_ARG; }
+    if (n_classes < 2 || n_classes > kHeadMaxC) { h->err = "rnde_node_classifier_predict: 2 <= n_classes <= " + std::to_string(kHeadMaxC); return RNDE_ERR_BAD_ARG; }
+    if (h->D > 256 * kHeadRowsPerThread) { h->err = "rnde_node_classifier_predict: D <= " + std::to_string(256 * kHeadRowsPerThread) + " (the head keeps its rows of W in registers)"; return RNDE_ERR_BAD_ARG; }
+    if (!(t1 > t0)) { h->err = "rnde_node_classifier_predict: t1 > t0"; return RNDE_ERR_BAD_ARG; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, h->cg_ws.reserve((size_t)h->D * B));
+    HIPCHK(h, h->ev_host.create(hipEventDisableTiming));
+    float* u = h->cg_ws;
+    const bool counting = y_dev && correct_dev;
+    const bool hooked = !counting && h->engine != 4;
+    if (hooked) h->after_solve = [&](hipStream_t s) -> rnde_status { return launch_head_eval(h, u, p3_dev, nullptr, B, n_classes, logits_out_dev, nullptr, s); };
+    const rnde_status st = forward_impl(h, x_dev, p2_dev, B, t0, t1, u, nullptr, 0, nullptr, nfe_out, nullptr, nullptr, 0, stream);
+    h->after_solve = nullptr;
+    if (st != RNDE_OK || hooked) return st;
+    return launch_head_eval(h, u, p3_dev, y_dev, B, n_classes, logits_out_dev, correct_dev, (hipStream_t)stream);
 }
 
 // ---- chain engine reverse pass ----------------------------------------------------------------------------

@@ -245,6 +245,37 @@ class _LatentHandle:
             pass
 
 
+_LATENT_ROWS = 20      # latent state rows (latent_ode.jl:112-124); the kernels are built for the reference's sizes
+
+
+def _check_latent_sizes(who, model, data, mask, t_row):
+    """rnde_latent_* is compiled for the experiment's own sizes (latent_ode.jl:39-124: LatentGRU(37, 40, 50), rec_to_gen 100-50-40, gen_to_data 20-37):
+    a model built with other sizes must not reach kernels that would read its parameter vectors out of bounds.  Checked on EVERY call: the widths
+    belong to the call's arrays, the parameter vectors can be replaced between calls; only the library's three counts are cached."""
+    import ctypes as C
+    from . import _lib
+    want_n = getattr(model, "_latent_want", None)
+    if want_n is None:
+        n1, n2, n4 = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        _lib.lib().rnde_latent_param_counts(C.byref(n1), C.byref(n2), C.byref(n4))
+        want_n = model._latent_want = (n1.value, n2.value, n4.value)
+    p1_, p2_, p3_, p4_ = model.trainable()
+    have = (p1_.numel(), p2_.numel(), p4_.numel(), data.shape[2], mask.shape[2], t_row.shape[2], model.node.model.dims()[0])
+    want = want_n + (37, 37, 1, _LATENT_ROWS)
+    if have != want:
+        raise ValueError(f"{who} runs the kernels built for the reference's latent-ODE sizes (experiments/latent_ode.jl:39-124): "
+                         f"(len p1, len p2, len p4, data width, mask width, time width, latent rows) must be {want}, this model has {have}; "
+                         "use latent_loss_function (torch autograd around the layer call) for other sizes")
+
+
+def _latent_handle(model, B, T, dev):
+    """The model's rnde_latent handle, regrown when a call needs a larger batch or more save times than it was created for."""
+    hl = getattr(model, "_latent_handle", None)
+    if hl is None or hl.max_batch < B or hl.max_T < T:
+        hl = model._latent_handle = _LatentHandle(max(B, getattr(hl, "max_batch", 0) if hl else 0), max(T, getattr(hl, "max_T", 0) if hl else 0), dev.index or 0)
+    return hl
+
+
 def fused_latent_loss_and_grad(model, data, mask, t_row, lam_r=1.0e2, lam_k=1.0, regularize=True, saveat=None, generator=None, eps=None, func=None, agg="mean"):
     """One training-step gradient of the latent-ODE model WITHOUT a tape library in the loop: every piece of
     loss_function (experiments/latent_ode.jl:206-236) and of its reverse runs in librnde.so --
@@ -266,25 +297,9 @@ def fused_latent_loss_and_grad(model, data, mask, t_row, lam_r=1.0e2, lam_k=1.0,
     B, T, _ = data.shape
     x_ = torch.cat([data, mask, t_row], dim=2).to(torch.float32).contiguous()
     node = model.node
-    lat = 20                                     # latent state rows (latent_ode.jl:112-124); the kernels are built for the reference's sizes
-    # rnde_latent_* is compiled for the experiment's own sizes (latent_ode.jl:39-124: LatentGRU(37, 40, 50), rec_to_gen 100-50-40, gen_to_data 20-37):
-    # a model built with other sizes must not reach kernels that would read its parameter vectors out of bounds
-    # (checked on EVERY call: the widths belong to the call's arrays, the parameter vectors can be replaced between calls; only the library's three counts are cached)
-    want_n = getattr(model, "_latent_want", None)
-    if want_n is None:
-        n1, n2, n4 = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-        L.rnde_latent_param_counts(C.byref(n1), C.byref(n2), C.byref(n4))
-        want_n = model._latent_want = (n1.value, n2.value, n4.value)
-    p1_, p2_, p3_, p4_ = model.trainable()
-    have = (p1_.numel(), p2_.numel(), p4_.numel(), data.shape[2], mask.shape[2], t_row.shape[2], node.model.dims()[0])
-    want = want_n + (37, 37, 1, lat)
-    if have != want:
-        raise ValueError("fused_latent_loss_and_grad runs the kernels built for the reference's latent-ODE sizes (experiments/latent_ode.jl:39-124): "
-                         f"(len p1, len p2, len p4, data width, mask width, time width, latent rows) must be {want}, this model has {have}; "
-                         "use latent_loss_function (torch autograd around the layer call) for other sizes")
-    hl = getattr(model, "_latent_handle", None)
-    if hl is None or hl.max_batch < B or hl.max_T < T:
-        hl = model._latent_handle = _LatentHandle(max(B, getattr(hl, "max_batch", 0) if hl else 0), max(T, getattr(hl, "max_T", 0) if hl else 0), dev.index or 0)
+    lat = _LATENT_ROWS
+    _check_latent_sizes("fused_latent_loss_and_grad", model, data, mask, t_row)
+    hl = _latent_handle(model, B, T, dev)
     if eps is None:
         eps = torch.randn(B, lat, dtype=torch.float32, device=dev, generator=generator)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
@@ -348,3 +363,94 @@ def fused_latent_loss_and_grad(model, data, mask, t_row, lam_r=1.0e2, lam_k=1.0,
     node.last_nfe = int(nfe.value)
     nll, kl = loss2[0], lam_k * loss2[1]
     return nll + kl + reg, nll, kl, reg, int(nfe.value)
+
+
+def latent_total_loss(model, batches, t_row=None, eps=None, generator=None):
+    """total_loss_on_dataset (experiments/latent_ode.jl:271-292) WITHOUT a tape library or eager torch ops in the loop: per batch
+
+        rnde_latent_encode          recognition GRU, rec_to_gen, z0 = eps * exp(logvar / 2) + mu0
+        rnde_node_forward_saveat    the layer call, UNTAPED, on a handle that holds no pending tape
+        rnde_latent_decode_mse      gen_to_data, sum((pred .* m - d .* m) .^ 2) ./ sum(m) per sample, added to ONE device sum and count
+
+    and `sum / count` read back ONCE behind the last batch.  batches: an iterable of (data, mask) or (data, mask, t_row) with data, mask
+    (B, T, 37) and t_row (B, T, 1) (the reference's constant `_t` row; the keyword `t_row`, anything that expands to (B, T, 1), serves the
+    batches that carry none).  eps: the standard-normal sample (B, 20) of each batch -- a list, or a callable of the batch index; default: drawn
+    here with `generator` (CUDA.randn of time_series.jl:58).  Returns the loss as a float (NaN for no batches, as 0 / 0 in the reference);
+    `model.last_eval_nfe` lists the NFE of every batch's solve."""
+    import ctypes as C
+    from . import _lib
+    from .node import _check_f32
+    L = _lib.lib()
+    node = model.node
+    lat = _LATENT_ROWS
+    if eps is not None and not callable(eps) and not isinstance(eps, (list, tuple)):
+        raise TypeError("latent_total_loss: eps must be None, a list of (B, 20) tensors (one per batch) or a callable of the batch index")
+    acc = None                                   # [sum (fp64 bits) | count (int64)] on the device: one 16-byte buffer, one read-back
+    grid = sa = None
+    nfes = []
+    for i, batch in enumerate(batches):
+        if len(batch) not in (2, 3):
+            raise ValueError(f"latent_total_loss: batch {i} must be (data, mask) or (data, mask, t_row); it has {len(batch)} entries")
+        data, mask = batch[0], batch[1]
+        tr = batch[2] if len(batch) == 3 else t_row
+        if tr is None:
+            raise ValueError(f"latent_total_loss: batch {i} carries no t_row and none was given (vcat(d, m, _t), latent_ode.jl:278)")
+        if data.dim() != 3 or tuple(mask.shape) != tuple(data.shape):
+            raise ValueError(f"latent_total_loss: batch {i}: data and mask must both be (B, T, 37); got {tuple(data.shape)} and {tuple(mask.shape)}")
+        B, T, _ = data.shape
+        try:
+            tr = tr.expand(B, T, 1)
+        except RuntimeError:
+            raise ValueError(f"latent_total_loss: batch {i}: t_row {tuple(tr.shape)} does not expand to (B, T, 1) = ({B}, {T}, 1)") from None
+        _check_latent_sizes("latent_total_loss", model, data, mask, tr)
+        if B < 1 or B > node.max_batch:
+            raise ValueError(f"latent_total_loss: batch {i}: B = {B} is outside 1 .. the layer's max_batch = {node.max_batch}")
+        if not 1 <= T <= 64:
+            raise ValueError(f"latent_total_loss: batch {i}: T = {T} save times; the kernels serve 1 .. 64")
+        if grid is None:
+            grid = node._saveat_times(node.kwargs["saveat"], node.tspan)      # (a layer built without saveat= has no grid: KeyError)
+            sa = (C.c_float * len(grid))(*grid)
+        if len(grid) != T:
+            raise ValueError("one save time per observation time (latent_ode.jl:137)")
+        e = eps(i) if callable(eps) else (eps[i] if eps is not None else None)
+        tensors = dict(data=data, mask=mask, t_row=tr)
+        if e is not None:
+            if tuple(e.shape) != (B, lat):
+                raise ValueError(f"latent_total_loss: batch {i}: eps must be (B, 20) = ({B}, {lat}); got {tuple(e.shape)}")
+            tensors["eps"] = e
+        for name, t in tensors.items():
+            _check_f32(name, t)
+            if t.device != data.device:
+                raise ValueError(f"latent_total_loss: batch {i}: {name} is on {t.device}, data on {data.device}")
+        if not data.is_cuda:
+            raise RuntimeError("latent_total_loss runs on the MI355X only: the batches must be cuda tensors (no CPU fallback)")
+        dev = data.device
+        with torch.no_grad():
+            x_ = torch.cat([data, mask, tr], dim=2).contiguous()
+            hl = _latent_handle(model, B, T, dev)
+            if e is None:
+                e = torch.randn(B, lat, dtype=torch.float32, device=dev, generator=generator)
+            if acc is None:
+                acc = torch.zeros(2, dtype=torch.int64, device=dev)
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            p1, p2, p3, p4 = (p.detach().contiguous() for p in model.trainable())
+            z0 = torch.empty(B, lat, dtype=torch.float32, device=dev)
+            mu0, logvar = torch.empty_like(z0), torch.empty_like(z0)
+            _lib.check_latent(hl.ptr, L.rnde_latent_encode(hl.ptr, x_.data_ptr(), p1.data_ptr(), p2.data_ptr(), e.contiguous().data_ptr(), B, T,
+                                                           z0.data_ptr(), mu0.data_ptr(), logvar.data_ptr(), stream))
+            node._func = node.resolve_func(None)
+            hn = node._acquire(z0, False)
+            res = torch.empty(B, T, lat, dtype=torch.float32, device=dev)
+            nfe = C.c_int64(0)
+            _lib.check(hn.ptr, L.rnde_node_forward_saveat(hn.ptr, z0.data_ptr(), p3.data_ptr(), B, node.tspan[0], node.tspan[1], sa, T, res.data_ptr(),
+                                                          C.byref(nfe), None, None, 0, stream))
+            mse = torch.empty(B, dtype=torch.float32, device=dev)
+            _lib.check_latent(hl.ptr, L.rnde_latent_decode_mse(hl.ptr, res.data_ptr(), p4.data_ptr(), x_.data_ptr(), B, T, mse.data_ptr(),
+                                                              acc.data_ptr(), acc.data_ptr() + 8, stream))
+        nfes.append(int(nfe.value))
+        node.last_nfe = int(nfe.value)
+    model.last_eval_nfe = nfes
+    if acc is None:
+        return float("nan")
+    host = acc.cpu()                             # the one read-back
+    return float(host[:1].view(torch.float64).item()) / int(host[1].item())

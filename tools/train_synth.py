@@ -79,8 +79,9 @@ def batches_of(x, y, device):
     return out
 
 
-def run(reg, train, test, epochs, device, seed, max_attempts, steer, lam_scale=1.0):
+def run(reg, train, test, epochs, device, seed, max_attempts, steer, lam_scale=1.0, device_eval=False):
     import regneuralde_jl_amd as rn
+    accuracy = rn.node_accuracy if device_eval else rn.accuracy      # --device-eval: one rnde_node_classifier_predict per batch, one read-back per pass
     g = torch.Generator().manual_seed(seed)
     regularize = reg != "vanilla"
     lam0, lam1, func, agg, solver = rn.REGULARISERS[reg] if regularize else (0.0, 0.0, None, torch.mean, "Tsit5")
@@ -101,7 +102,7 @@ def run(reg, train, test, epochs, device, seed, max_attempts, steer, lam_scale=1
             return int(nfe), time.perf_counter() - t0
     rec = {"regulariser": reg, "lambda0": lam0, "lambda1": lam1, "solver": solver, "epochs": []}
     nfe, inf_t = probe()
-    rec["epochs"].append({"epoch": 0, "nfe": nfe, "train_acc": 100 * rn.accuracy(model, train), "test_acc": 100 * rn.accuracy(model, test),
+    rec["epochs"].append({"epoch": 0, "nfe": nfe, "train_acc": 100 * accuracy(model, train), "test_acc": 100 * accuracy(model, test),
                           "train_time_s": 0.0, "inference_time_s": inf_t})
     failed = None
     for epoch in range(1, epochs + 1):
@@ -129,7 +130,7 @@ def run(reg, train, test, epochs, device, seed, max_attempts, steer, lam_scale=1
         except Exception as e:      # (a run that has diverged can exhaust max_attempts in the probe as well as in a training step)
             rec["failed"] = f"epoch {epoch} (NFE probe): {e}"
             break
-        e = {"epoch": epoch, "lambda": lam, "nfe": nfe, "train_acc": 100 * rn.accuracy(model, train), "test_acc": 100 * rn.accuracy(model, test),
+        e = {"epoch": epoch, "lambda": lam, "nfe": nfe, "train_acc": 100 * accuracy(model, train), "test_acc": 100 * accuracy(model, test),
              "train_time_s": timing, "inference_time_s": inf_t, "mean_ce": ce_sum / len(train), "mean_reg": reg_sum / len(train),
              "mean_train_nfe": nfe_sum / len(train)}
         rec["epochs"].append(e)
@@ -151,6 +152,7 @@ def main():
     ap.add_argument("--max-attempts", type=int, default=1000)
     ap.add_argument("--steer", action="store_true", help="STEER: t1 ~ U(0.5, 1.5) per training step (mnist_node.jl:104-105,:133)")
     ap.add_argument("--lam-scale", type=float, default=1.0, help="multiply the reference's lambda0 / lambda1 (diagnostics; the committed record uses 1)")
+    ap.add_argument("--device-eval", action="store_true", help="train / test accuracy through node_accuracy (the evaluation pass behind the C ABI) instead of accuracy")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
@@ -161,12 +163,12 @@ def main():
     else:
         tr, te, what = synthetic_set(args.batches * BATCH, args.test_batches * BATCH, args.seed)
     train, test = batches_of(*tr, device), batches_of(*te, device)
-    out = {"data": what, "batch": BATCH, "train_batches": len(train), "test_batches": len(test), "epochs": args.epochs, "steer": args.steer, "lam_scale": args.lam_scale,
+    out = {"data": what, "batch": BATCH, "train_batches": len(train), "test_batches": len(test), "epochs": args.epochs, "steer": args.steer, "lam_scale": args.lam_scale, "device_eval": args.device_eval,
            "loop": "experiments/mnist_node.jl:220-263 (lambda schedule :106-108, InvDecay/Momentum :130, NFE probe on the fixed first batch :245-247, accuracy src/metrics.jl:4-18)",
            "runs": {}}
     for spec in args.regs.split(","):          # "stiff_est@0.1": that regulariser with the reference's lambdas scaled by 0.1
         reg, _, sc = spec.partition("@")
-        out["runs"][spec] = run(reg, train, test, args.epochs, device, args.seed, args.max_attempts, args.steer, args.lam_scale * (float(sc) if sc else 1.0))
+        out["runs"][spec] = run(reg, train, test, args.epochs, device, args.seed, args.max_attempts, args.steer, args.lam_scale * (float(sc) if sc else 1.0), args.device_eval)
     f = {k: v["final"] for k, v in out["runs"].items()}
     out["summary"] = f
     print(json.dumps(f, indent=1))
