@@ -107,6 +107,8 @@ def lib():
     L.rnde_debug_arm_replay.argtypes = [vp, fp, i32]
     L.rnde_debug_feval.argtypes = [vp, vp, vp, i32, f, vp, vp]
     L.rnde_debug_attempt.argtypes = [vp, vp, vp, vp, i32, f, f, vp, vp, fp, vp]
+    if hasattr(L, "rnde_debug_elementwise"):      # (an older build loaded through RNDE_LIB for an A/B run has no such probe)
+        L.rnde_debug_elementwise.argtypes = [i32, i32, vp, vp, C.c_int64, vp, vp]
     L.rnde_bench_attempt.argtypes = [vp, vp, vp, i32, i32, fp, vp]
     L.rnde_bench_attempt_taped.argtypes = [vp, vp, vp, i32, i32, fp, vp]
     L.rnde_bench_attempt_cold_tape.argtypes = [vp, vp, vp, i32, i32, i32, fp, vp]
@@ -238,7 +240,7 @@ def lib():
 
 EXPORTS = ["rnde_version", "rnde_debug_poison_allocs", "rnde_debug_poison_bytes", "rnde_debug_live_allocs", "rnde_debug_live_bytes", "rnde_last_error", "rnde_param_count", "rnde_node_create", "rnde_node_destroy",
            "rnde_node_forward", "rnde_node_forward_saveat", "rnde_node_forward_everystep", "rnde_node_forward_replay", "rnde_node_backward", "rnde_node_backward_async", "rnde_node_release_tape", "rnde_node_forward_host",
-           "rnde_node_backward_host", "rnde_node_steps", "rnde_debug_feval", "rnde_debug_attempt",
+           "rnde_node_backward_host", "rnde_node_steps", "rnde_debug_feval", "rnde_debug_attempt", "rnde_debug_elementwise",
            "rnde_bench_attempt", "rnde_bench_attempt_taped", "rnde_bench_attempt_cold_tape", "rnde_node_set_timing", "rnde_node_timing", "rnde_node_last_attempts", "rnde_node_fallback_count",
            "rnde_node_launches_per_attempt", "rnde_node_one_launch_solves", "rnde_node_tail_folds", "rnde_node_set_matrix_mode", "rnde_node_matrix_mode", "rnde_classifier_head", "rnde_node_classifier_grad", "rnde_momentum_step", "rnde_momentum_step_scaled", "rnde_adam_step",
            "rnde_comm_unique_id", "rnde_comm_create", "rnde_comm_destroy", "rnde_comm_world", "rnde_comm_last_error", "rnde_comm_library", "rnde_comm_allreduce", "rnde_comm_create_local_group", "rnde_comm_health", "rnde_comm_window_create", "rnde_comm_window_destroy", "rnde_comm_create_peers", "rnde_comm_path", "rnde_node_set_coupling", "rnde_tapes_create", "rnde_tapes_destroy", "rnde_tapes_last_error", "rnde_tapes_in_use", "rnde_tapes_node", "rnde_tapes_forward", "rnde_tapes_backward", "rnde_tapes_release",

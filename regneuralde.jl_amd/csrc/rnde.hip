@@ -1085,6 +1085,46 @@ extern "C" rnde_status rnde_debug_feval(rnde_node* h, const float* u_dev, const 
     return RNDE_OK;
 }
 
+// The element-wise device functions, one at a time (include/rnde.h: rnde_debug_elementwise; rnde_probe.h).  The functor calls the functions of
+// rnde_device.h with a run-time selector, as the generic kernels do.
+static_assert(EW_TANH_FAST == RNDE_EW_TANH_FAST && EW_TANH_FAST2_X == RNDE_EW_TANH_FAST2_X && EW_TANH_FAST2_Y == RNDE_EW_TANH_FAST2_Y &&
+              EW_PRE_FWD == RNDE_EW_PRE_FWD && EW_PRE_BWD == RNDE_EW_PRE_BWD && EW_ACT_FWD == RNDE_EW_ACT_FWD && EW_ACT_DY == RNDE_EW_ACT_DY &&
+              EW_ACT_D2Y == RNDE_EW_ACT_D2Y && EW_TANH_F == RNDE_EW_TANH_F && EW_SIGMOID_F == RNDE_EW_SIGMOID_F &&
+              EW_FF_SOFTPLUS == RNDE_EW_FF_SOFTPLUS, "rnde_probe.h restates rnde_elementwise_fn");
+struct EwDevice {
+    int fn, code;
+    __device__ float operator()(float a, float b) const {
+        switch (fn) {
+            case EW_TANH_FAST: return tanh_fast(a);
+            case EW_TANH_FAST2_X: return tanh_fast2(f32x2{a, b}).x;
+            case EW_TANH_FAST2_Y: return tanh_fast2(f32x2{b, a}).y;
+            case EW_PRE_FWD: return pre_fwd(code, a);
+            case EW_PRE_BWD: return pre_bwd(code, a, b);
+            case EW_ACT_FWD: return act_fwd(code, a);
+            case EW_ACT_DY: return act_dy(code, a);
+            default: return act_d2y(code, a);
+        }
+    }
+};
+extern "C" rnde_status rnde_debug_elementwise(int32_t fn, int32_t code, const float* in_dev, const float* in2_dev, int64_t n, float* out_dev,
+                                              void* stream) {
+    const bool two = fn == EW_TANH_FAST2_X || fn == EW_TANH_FAST2_Y || fn == EW_PRE_BWD;
+    const int code_max = (fn == EW_PRE_FWD || fn == EW_PRE_BWD) ? RNDE_PRE_CUBE : ((fn == EW_ACT_FWD || fn == EW_ACT_DY || fn == EW_ACT_D2Y) ? RNDE_ACT_ELU : 0);
+    if (fn < EW_TANH_FAST || fn > EW_FF_SOFTPLUS) { rnde_set_create_error("rnde_debug_elementwise: unknown function selector"); return RNDE_ERR_BAD_ARG; }
+    if (code < 0 || code > code_max) { rnde_set_create_error("rnde_debug_elementwise: code out of range for this function"); return RNDE_ERR_BAD_ARG; }
+    if (n < 0) { rnde_set_create_error("rnde_debug_elementwise: negative n"); return RNDE_ERR_BAD_ARG; }
+    if (n == 0) return RNDE_OK;
+    if (!in_dev || !out_dev || (two && !in2_dev)) { rnde_set_create_error("rnde_debug_elementwise: null operand"); return RNDE_ERR_BAD_ARG; }
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e;
+    if (fn == EW_TANH_F || fn == EW_SIGMOID_F) e = elementwise_latent(fn, in_dev, (long long)n, out_dev, s);
+    else if (fn == EW_FF_SOFTPLUS) e = elementwise_ffjord(in_dev, (long long)n, out_dev, s);
+    else e = elementwise_launch(EwDevice{fn, code}, in_dev, two ? in2_dev : nullptr, (long long)n, out_dev, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { rnde_set_create_error(std::string("rnde_debug_elementwise: HIP: ") + hipGetErrorString(e)); return RNDE_ERR_HIP; }
+    return RNDE_OK;
+}
+
 extern "C" rnde_status rnde_debug_attempt(rnde_node* h, const float* uprev_dev, const float* k1_dev, const float* p_dev,
                                           int32_t B, float t, float dt, float* k_out_dev, float* unew_out_dev,
                                           float* eest_out, void* stream) {

@@ -309,10 +309,20 @@ __device__ __forceinline__ float act_apply(int act, float v) { return act ? tanh
 // Max error 1.65 ulp (mean 0.27) against fp64 on 5e6 samples with exact exp2/division (libm tanhf: 1.37);
 // the hardware v_exp_f32 / v_rcp_f32 add at most ~1 ulp.  Accuracy matters beyond parity: at the reference's
 // tolerance the step size is set by rounding noise, so a sloppy tanh would RAISE NFE.
+// On the device, hardware exp2 / rcp included: 1.62 ulp over every binade and every float around both seams (tests/test_gpu_elementwise.py; the
+// table in DESIGN.md 4.2).
+//
+// IEEE-754-2019 minimum / maximum (v_minimum3_f32 / v_maximum3_f32): NaN if either operand is.  fminf / fmaxf return the operand that is NOT a
+// NaN, so a clamp written with them turns NaN into the clamp's bound.
+__device__ __forceinline__ float nan_min(float a, float b) { return __builtin_elementwise_minimum(a, b); }
+__device__ __forceinline__ float nan_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
 __device__ __forceinline__ float tanh_fast(float x) {
     // (|x| clamped at 9.1 instead of a select behind the formula: the formula's value AT 9.1 is exactly 1.0f, so every result is the same
-    //  bit pattern as with the select, and |x| + clamp is ONE v_min_f32 with a source modifier where abs, compare and select were three)
-    const float ax = fminf(fabsf(x), 9.1f), x2 = x * x;
+    //  bit pattern as with the select, and |x| + clamp is ONE instruction with a source modifier where abs, compare and select were three.
+    //  The clamp must keep a NaN: with fminf, tanh_fast(NaN) was copysignf(1, NaN), and a NaN weight in front of a tanh layer never reached
+    //  the error estimate that raises RNDE_ERR_NONFINITE.  With nan_min a NaN stays in ax, goes through exp2 / rcp and comes out; every
+    //  other input has the bits it had with fminf.)
+    const float ax = nan_min(fabsf(x), 9.1f), x2 = x * x;
     float p = -0.00671552f;
     p = fmaf(p, x2, 0.02136713f);
     p = fmaf(p, x2, -0.05391917f);
@@ -336,7 +346,7 @@ __device__ __forceinline__ float tanh_fast(float x) {
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ f32x2 tanh_fast2(f32x2 x) {
-    const f32x2 ax = {fminf(fabsf(x.x), 9.1f), fminf(fabsf(x.y), 9.1f)}, x2 = x * x;
+    const f32x2 ax = {nan_min(fabsf(x.x), 9.1f), nan_min(fabsf(x.y), 9.1f)}, x2 = x * x;      // (nan_min: as in tanh_fast)
     f32x2 p = fma2((f32x2)(-0.00671552f), x2, (f32x2)(0.02136713f));
     p = fma2(p, x2, (f32x2)(-0.05391917f));
     p = fma2(p, x2, (f32x2)(0.13333165f));
@@ -371,15 +381,28 @@ __device__ __forceinline__ float pre_bwd(int sel, float g, float v) {
 
 // The Dense activations (rnde_node_config.act / rnde_nsde_config.*_act, include/rnde.h: rnde_act).  Each derivative is a function of the
 // layer's OUTPUT y, which is what the reverse passes read back from the tape (no pre-activation is ever kept): tanh 1 - y^2, relu y > 0,
-// sigmoid y (1 - y), softplus -expm1(-y) (= sigmoid(z)), elu (alpha = 1) y > 0 ? 1 : y + 1.  A NaN input stays NaN through every map.
+// sigmoid y (1 - y), softplus -expm1(-y) (= sigmoid(z)), elu (alpha = 1) y > 0 ? 1 : y + 1.  A NaN input stays NaN through every forward map (tanh_fast's and sigmoid_f's clamps once dropped it; held on the
+// device by tests/test_gpu_elementwise.py) and through every derivative but relu's, where y > 0 is false for a NaN.
 // The kernels keep their own paths for identity and tanh (tanh_fast2 on pairs); act_fwd / act_dy are what every other code runs through.
 enum { ACT_IDENTITY = 0, ACT_TANH = 1, ACT_RELU = 2, ACT_SIGMOID = 3, ACT_SOFTPLUS = 4, ACT_ELU = 5 };
+// softplus (act_fwd's and, through ff_softplus, the ConcatSquash dynamics').  log1p(exp(-|z|)) + max(z, 0) -- NNlib's form -- everywhere but on
+// (0, 1/2).  There that form is NOT monotone in fp32: exp(-z), and with it the log1p term, moves in steps larger than the steps of z, so z + (a
+// term that has just dropped a step) comes out one ulp below its left neighbour (1226 such pairs in the sweep of tests/test_gpu_elementwise.py,
+// on the device and in numpy alike).  On (0, 1/2) the value is therefore the fp64 log1p(exp(z)) rounded once: within 0.5 ulp, hence monotone.
+// Three fp32 forms were measured monotone as well (log1pf(expf(z)), logf(1 + expf(z)), ln 2 + log1pf(expm1f(z) / 2)), but each of them moves
+// softplus by an ulp in another direction than fp64 and parts the step sequences of the adaptive FFJORD solves from the fp64 controller's
+// (test_gpu_ffjord*.py::test_adaptive_solve_truncation_regime_and_reference_tolerance); the rounded fp64 value keeps them.  z <= 0, z >= 1/2 and
+// NaN have the bits they had.  DESIGN.md 4.2.
+__device__ __forceinline__ float softplus_f(float z) {
+    if (z >= 0.5f || !(z > 0.f)) return log1pf(expf(-fabsf(z))) + fmaxf(z, 0.f);      // (a NaN too)
+    return (float)log1p(exp((double)z));
+}
 __device__ __forceinline__ float act_fwd(int code, float z) {
     switch (code) {
         case ACT_TANH: return tanh_fast(z);
         case ACT_RELU: return z < 0.f ? 0.f : z;
         case ACT_SIGMOID: { const float t = expf(-fabsf(z)); return z >= 0.f ? 1.f / (1.f + t) : t / (1.f + t); }
-        case ACT_SOFTPLUS: return log1pf(expf(-fabsf(z))) + fmaxf(z, 0.f);
+        case ACT_SOFTPLUS: return softplus_f(z);
         case ACT_ELU: return z > 0.f ? z : expm1f(z);
         default: return z;
     }

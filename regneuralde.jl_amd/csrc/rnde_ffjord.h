@@ -50,7 +50,7 @@ __device__ __forceinline__ float ff_sig(float x) {
     const float t = expf(-fabsf(x));
     return x >= 0.f ? 1.f / (1.f + t) : t / (1.f + t);
 }
-__device__ __forceinline__ float ff_softplus(float x) { return x > 0.f ? x + log1pf(expf(-x)) : log1pf(expf(x)); }
+__device__ __forceinline__ float ff_softplus(float x) { return softplus_f(x); }
 
 // parameter views: W[o][i] = p[off + i * out + o]; then b, bw, bb, gw (each `out` long)
 struct FfLayer {

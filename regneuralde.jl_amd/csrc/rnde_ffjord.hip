@@ -17,6 +17,7 @@
 #include "rnde_bffjordc.h"
 #include "rnde_tile_driver.h"
 #include "rnde_tile_host.h"
+#include "rnde_probe.h"
 
 using namespace rnde;
 
@@ -74,6 +75,14 @@ struct rnde_ffjord {
         hipError_t e_ = (x);                                                                        \
         if (e_ != hipSuccess) { (h)->err = std::string("HIP: ") + hipGetErrorString(e_); return RNDE_ERR_HIP; } \
     } while (0)
+
+// rnde_debug_elementwise's share of this translation unit (rnde_probe.h): the private softplus of rnde_ffjord.h
+struct EwFfjord {
+    __device__ float operator()(float a, float) const { return ff_softplus(a); }
+};
+hipError_t rnde::elementwise_ffjord(const float* in, long long n, float* out, hipStream_t s) {
+    return elementwise_launch(EwFfjord{}, in, nullptr, n, out, s);
+}
 
 extern "C" const char* rnde_ffjord_last_error(const rnde_ffjord* h) { return h ? h->err.c_str() : g_ff_create_err.c_str(); }
 

@@ -70,7 +70,7 @@ __device__ __forceinline__ float tanh_f(float x) {
 // 1 / (1 + exp(-x)): exp2 with the argument split as above, one Newton step on the reciprocal
 __device__ __forceinline__ float sigmoid_f(float x) {
     constexpr float Lh = 1.4426950408889634f, Llo = (float)(1.4426950408889634 - (double)Lh);
-    const float a = fminf(fmaxf(-x, -87.f), 87.f);
+    const float a = rnde::nan_min(rnde::nan_max(-x, -87.f), 87.f);      // (not fminf / fmaxf: they drop a NaN, and sigmoid_f(NaN) was 1.0)
     const float yh = a * Lh, yl = fmaf(a, Lh, -yh) + a * Llo;
     float e = __builtin_amdgcn_exp2f(yh);
     e = fmaf(e, yl * 0.6931471805599453f, e);

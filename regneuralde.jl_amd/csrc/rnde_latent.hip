@@ -4,6 +4,7 @@
 #include "rnde_alloc.h"       // first among the project headers: every hipMalloc behind it goes through the RNDE_POISON wrapper
 #include "rnde_latent.h"
 #include "rnde_device.h"      // DeviceOnce
+#include "rnde_probe.h"
 
 #include <algorithm>
 #include <cmath>
@@ -33,6 +34,15 @@ static thread_local std::string g_latent_err;
         hipError_t e__ = (call);                                                                        \
         if (e__ != hipSuccess) { (h)->err = std::string(#call) + ": " + hipGetErrorString(e__); return RNDE_ERR_HIP; } \
     } while (0)
+
+// rnde_debug_elementwise's share of this translation unit (rnde_probe.h): the two private functions of rnde_latent.h
+struct EwLatent {
+    int fn;
+    __device__ float operator()(float a, float) const { return fn == rnde::EW_TANH_F ? tanh_f(a) : sigmoid_f(a); }
+};
+hipError_t rnde::elementwise_latent(int fn, const float* in, long long n, float* out, hipStream_t s) {
+    return rnde::elementwise_launch(EwLatent{fn}, in, nullptr, n, out, s);
+}
 
 extern "C" const char* rnde_latent_last_error(const rnde_latent* h) { return h ? h->err.c_str() : g_latent_err.c_str(); }
 extern "C" void rnde_latent_param_counts(int32_t* n_p1, int32_t* n_p2, int32_t* n_p4) {

@@ -24,6 +24,7 @@
 #include "rnde_chainmw.h"
 #include "rnde_bchainmw.h"
 #include "rnde_rev_plan.h"
+#include "rnde_probe.h"
 
 #include <chrono>
 #include <algorithm>
