@@ -99,24 +99,37 @@ def test_latent_handle_refuses_out_of_order_calls_and_bad_shapes():
     L.rnde_latent_destroy(h)
 
 
-@pytest.mark.parametrize("func,agg,lam_r", [("error_est", "mean", 50.0), ("stiff_est", "max", 10.0), ("error_stiff_est", "mean", 10.0)])
-def test_fused_latent_training_step_matches_the_autograd_form(func, agg, lam_r):
+RAGGED_ID = "error_est-mean-50.0-ragged-17x12"      # (the three first cases keep the ids they had)
+
+
+@pytest.mark.parametrize("func,agg,lam_r", [("error_est", "mean", 50.0), ("stiff_est", "max", 10.0), ("error_stiff_est", "mean", 10.0),
+                                            pytest.param("error_est", "mean", 50.0, id=RAGGED_ID)])
+def test_fused_latent_training_step_matches_the_autograd_form(func, agg, lam_r, request):
     """(Parametrised over the three `save_func`s / aggregators of experiments/latent_ode.jl:153-190: EEst*dt with mean, the stiffness estimate with
     `maximum`, their blend with mean.)
     `fused_latent_loss_and_grad` (every piece of loss_function, latent_ode.jl:206-236, and of its reverse through the C ABI) against
     `latent_loss_function` + torch.autograd on the same model, data and reparameterisation sample -- the layer call in the middle is the
     same device solve on both sides, so this checks the plumbing between the five library calls: loss terms 1e-5, gradients of the four
-    parameter groups 2e-4 of their largest entry (tol 1e-3 on the solve: its step sequence is not rounding noise)."""
+    parameter groups 2e-4 of their largest entry (tol 1e-3 on the solve: its step sequence is not rounding noise).
+    The fourth case, B = 17 and T = 12: the ragged batch of tests/latent_cases.py -- another set of empty save times per sample, a partial tile,
+    and a time row of real, per-sample, varying gaps with zeros at the dropped steps."""
     import torch
     import regneuralde_jl_amd as rn
     g = torch.Generator().manual_seed(5)
-    B, T = 48, 49
+    ragged = request.node.callspec.id == RAGGED_ID
+    B, T = (17, 12) if ragged else (48, 49)
     grid = torch.linspace(0, 1, T)
     model = rn.build_latent_ode(saveat=grid, regularize=True, generator=g, solver="Tsit5" if func == "error_est" else "AutoTsit5", reltol=1e-3, abstol=1e-3, max_batch=B, max_attempts=128)
-    data = torch.randn(B, T, 37, generator=g).cuda()
-    mask = (torch.rand(B, T, 37, generator=g) < 0.3).float().cuda()
-    mask[:, 0, 0] = 1.0
-    t_row = torch.full((B, T, 1), 1.0 / (T - 1)).cuda(); t_row[:, -1] = 0.0
+    if ragged:
+        from tests import latent_cases as lc
+        x = torch.from_numpy(lc.build(B, T, 15, ragged=True)[1]).float().cuda()
+        data, mask, t_row = x[:, :, :37].contiguous(), x[:, :, 37:74].contiguous(), x[:, :, 74:].contiguous()
+        assert float((torch.cat([mask, t_row], dim=2).sum(dim=2) == 0).float().mean()) >= 0.5      # (empty steps, as the GRU counts them)
+    else:
+        data = torch.randn(B, T, 37, generator=g).cuda()
+        mask = (torch.rand(B, T, 37, generator=g) < 0.3).float().cuda()
+        mask[:, 0, 0] = 1.0
+        t_row = torch.full((B, T, 1), 1.0 / (T - 1)).cuda(); t_row[:, -1] = 0.0
     eps = torch.randn(B, 20, generator=g).cuda()
 
     class _Gen:                      # hands the SAME sample to the autograd form (it draws with torch.randn(..., generator=))
