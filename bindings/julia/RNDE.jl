@@ -945,4 +945,46 @@ function ffjord_sample(h::FfjordHandle, p::ROCVector{Float32}, z::ROCMatrix{Floa
     return x
 end
 
+# Several batches per launch (the likelihood pass of src/metrics.jl:20-33; engines :tiled and chain handles).  The capacity is the switch:
+# ffjord_reserve_groups(h, max_groups, max_columns) (0, 0 releases it); every group takes ceil(B_g / 16) tiles of its own.
+function ffjord_reserve_groups(h::FfjordHandle, max_groups::Integer, max_columns::Integer)
+    st = ccall((:rnde_ffjord_reserve_groups, LIB), Cint, (Ptr{Cvoid}, Int32, Int32), h.ptr, Int32(max_groups), Int32(max_columns))
+    st == 0 || error("rnde_ffjord_reserve_groups status $st: ", _fferr(h.ptr))
+    return nothing
+end
+function ffjord_group_capacity(h::FfjordHandle)
+    g = Ref{Int32}(0); c = Ref{Int32}(0)
+    ccall((:rnde_ffjord_group_capacity, LIB), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}), h.ptr, g, c)
+    return Int(g[]), Int(c[])
+end
+# x, e: D x sum(Bs), the groups' columns back to back (e === nothing: the exact trace).  acc === nothing, or a ROCVector{Float64} of two
+# entries: acc[1] += sum(logpx), and the second entry, read as an Int64, += sum(Bs) -- queued, not waited for.  Returns logpx (sum(Bs)), the
+# NFEs and every group's status; each group bit for bit what ffjord_forward gives for its batch alone.  Untaped.
+function ffjord_forward_groups(h::FfjordHandle, x::ROCMatrix{Float32}, p::ROCVector{Float32}, e::Union{Nothing,ROCMatrix{Float32}},
+                               Bs::Vector{Int32}, tspan; acc::Union{Nothing,ROCVector{Float64}} = nothing)
+    n = length(Bs)
+    logpx = similar(x, size(x, 2))
+    nfe = Vector{Int64}(undef, n); status = Vector{Int32}(undef, n)
+    GC.@preserve x p e logpx acc begin
+        sum_ptr = acc === nothing ? C_NULL : devptr(acc)
+        cnt_ptr = acc === nothing ? C_NULL : devptr(acc) + 8
+        st = ccall((:rnde_ffjord_forward_groups, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Int32}, Float32, Float32, Int32, Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32},
+                    Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                   h.ptr, devptr(x), devptr(p), e === nothing ? C_NULL : devptr(e), n, Bs, Float32(tspan[1]), Float32(tspan[2]),
+                   e === nothing ? 1 : 0, devptr(logpx), nfe, status, sum_ptr, cnt_ptr, _stream())
+        st == 0 || error("rnde_ffjord_forward_groups status $st: ", _fferr(h.ptr))
+    end
+    return logpx, Int.(nfe), Int.(status)
+end
+# (dt, accepted) pairs of group g (0-based, as the library counts) of the last group call, flattened
+function ffjord_group_steps(h::FfjordHandle, g::Integer)
+    n = Ref{Int32}(0)
+    ccall((:rnde_ffjord_group_steps, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float32}, Int32, Ref{Int32}), h.ptr, Int32(g), C_NULL, 0, n)
+    steps = Vector{Float32}(undef, 2 * n[])
+    st = ccall((:rnde_ffjord_group_steps, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float32}, Int32, Ref{Int32}), h.ptr, Int32(g), steps, n[], n)
+    st == 0 || error("rnde_ffjord_group_steps status $st: ", _fferr(h.ptr))
+    return steps
+end
+
 end # module

@@ -861,6 +861,37 @@ rnde_status rnde_ffjord_forward_exact_replay(rnde_ffjord* h, const float* x_dev,
  * footprint (checked when tracking is first switched on). */
 rnde_status rnde_ffjord_set_track_ctrl(rnde_ffjord* h, int32_t on);
 int32_t     rnde_ffjord_track_ctrl(const rnde_ffjord* h);      /* the setting; -1 for NULL */
+/* Several batches per launch (opt-in; the likelihood pass of src/metrics.jl:20-33, whose batches do not depend on each other).  A tile is one
+ * workgroup on 16 columns and a 1024-column batch of the tabular widths is 64 of them, a quarter of the device; a group call places the
+ * tiles of several independent batches ("groups") in one launch.  Each group keeps the semantics of a call of its own: its own initial
+ * step, its own error norm over its own columns, its own controller and step log, and logpx, NFE and the (dt, accepted) log are bit for
+ * bit those of rnde_ffjord_forward (or _forward_exact) on that batch alone with the same p, e and span.  It is NOT a larger batch: no
+ * norm and no step is shared between groups, a group meets only with itself and leaves the launch when it is done.
+ * The capacity is the switch (as rnde_node_tiled_reserve_saveat): rnde_ffjord_reserve_groups(h, max_groups, max_columns) allocates the
+ * groups' workspace, control blocks, step logs and meeting granules for calls of up to max_groups groups and ceil(max_columns / 16)
+ * tiles in all (every group takes ceil(B_g / 16) tiles of its own); 0, 0 releases it, and a handle that never reserved runs the kernels it
+ * ran before.  Engines 1 and 2.  RNDE_ERR_BAD_ARG with a message that names the reason: a handle of rnde_ffjord_create (engine 0; the
+ * message points at the tiled engine), a handle that holds a tape, max_groups outside 1..16, max_columns outside max_groups..4096, and
+ * more tiles than the device keeps resident on the group kernel's footprint (the launch is at agent scope whatever the count).
+ * rnde_ffjord_group_capacity reads the reservation back (0, 0 without one). */
+rnde_status rnde_ffjord_reserve_groups(rnde_ffjord* h, int32_t max_groups, int32_t max_columns);
+rnde_status rnde_ffjord_group_capacity(const rnde_ffjord* h, int32_t* max_groups_out, int32_t* max_columns_out);
+/* The group call.  x_dev, e_dev, logpx_dev cover the groups' columns back to back in the caller layout (D x sum B, sum B); B_host: the
+ * n_groups column counts.  exact != 0: the exact trace of rnde_ffjord_forward_exact, and e_dev must be NULL; otherwise e_dev is required
+ * (the call draws no probes).  nfe_out_host, status_out_host: n_groups entries each (either may be NULL); status_out_host carries every
+ * group's own rnde_status, the call returns the first failing group's with a message that gives the group index.  sum_dev (a double) and
+ * count_dev (an int64), both or neither: when every group ended with RNDE_OK, sum_dev += the sum of logpx over all columns of the call (in
+ * double, one workgroup, a fixed order, no atomics: the same bits run to run) and count_dev += sum B, queued on the stream behind the
+ * solve and not waited for; a failed call adds nothing.  One launch and one stream synchronisation.  Forward only and untaped, as an
+ * untaped rnde_ffjord_forward: a tape the handle holds, its step log and its operands stay as they were, and so does what rnde_ffjord_steps
+ * / _step_log report; rnde_ffjord_timing's solve_ms becomes the group launch's.  Checked before any launch, each with a message naming
+ * the limit (RNDE_ERR_BAD_ARG): no capacity, n_groups outside 1..max_groups, a B_g outside 1..max_batch, more tiles than reserved,
+ * t1 <= t0, e_dev missing or (exact) given, only one of sum_dev / count_dev.  A meeting that times out ends every group: RNDE_ERR_HIP. */
+rnde_status rnde_ffjord_forward_groups(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t n_groups,
+                                       const int32_t* B_host, float t0, float t1, int32_t exact, float* logpx_dev, int64_t* nfe_out_host,
+                                       int32_t* status_out_host, double* sum_dev, int64_t* count_dev, void* stream);
+/* (dt, accepted) of every attempt of group g of the last group call, as rnde_ffjord_steps (steps_host NULL: the count only). */
+rnde_status rnde_ffjord_group_steps(rnde_ffjord* h, int32_t g, float* steps_host, int32_t capacity, int32_t* n_attempts_out);
 
 #ifdef __cplusplus
 }

@@ -68,6 +68,22 @@ struct rnde_ffjord {
     FcGeo CG{};                      // engine = 2: the Dense-chain dynamics on the tile layout (cfg holds the shared fields, in_dims = D)
     bool track_ctrl = false;         // rnde_ffjord_set_track_ctrl: taped forwards are reversed with the controller differentiated
     DevBuf<FfAttRec> att;            // [max_attempts]: the tracked sweep's attempt records (allocated when tracking is first switched on)
+    // several batches per launch (rnde_ffjord_reserve_groups): the capacity is the switch, NULL without one.  Everything a group call
+    // touches on the device is here; the handle's own workspace, tape and step log are not touched by it.
+    struct Groups {
+        int max_groups = 0, tiles = 0, max_columns = 0;
+        DevBuf<float> ws;                // [10][R][16 tiles]: the groups' columns side by side under the call's row stride
+        DevBuf<float> norm, qt;          // [tiles][8] + 512; [tiles][Dyn::scratch_floats] (the exact trace of engine 1)
+        DevBuf<StepState> ctl, fin, ctl_t;       // [max_groups][2] live states, [max_groups] final states, [tiles]
+        DevBuf<StepMeta> meta;           // [max_groups][max_attempts]
+        DevBuf<InitRec> initrec_t;       // [tiles]
+        DevBuf<TileGroup> table;         // [max_groups]
+        PinBuf<StepState> h_fin;         // pinned: [max_groups]
+        PinBuf<TileGroup> h_table;       // pinned: [max_groups]
+        MeetRes meet;                    // (max_attempts + 4) x 3 x tiles granules: a group's range lies behind those of the groups in front
+        std::vector<std::vector<StepMeta>> log;      // the step logs of the last group call
+    };
+    std::unique_ptr<Groups> gr;
 };
 
 #define FCHK(h, x)                                                                                  \
@@ -704,6 +720,146 @@ extern "C" rnde_status rnde_ffjord_debug_feval_kinetic(rnde_ffjord* h, const flo
         hipLaunchKernelGGL(rnde_ffjord_feval_kernel<true>, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->G, p_dev, x_dev, e_dev, t, B, 0,
                            h->rws, out_dev);
     FCHK(h, hipGetLastError());
+    return RNDE_OK;
+}
+
+// ---- several batches per launch (engines 1 and 2; the plan: rnde_group_plan.h, the kernel: rnde_tile_group_solve_kernel) ----
+template <class Dyn>
+static rnde_status groups_reserve(rnde_ffjord* h, const typename Dyn::Geo& G, int max_groups, int max_columns) {
+    const int tiles = group_reserved_tiles(max_columns);
+    const void* kern = (const void*)rnde_tile_group_solve_kernel<Dyn>;
+    FCHK(h, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+    hipError_t e;
+    // (up to 32 tiles the check counts one workgroup on each CU of an XCD, which the whole device holds as well: the launch is at agent scope)
+    const std::string why = tile_residency_refusal({kern}, kFtThreads, h->lds_bytes, tiles, h->cfg.device, "TrackedFFJORD groups: max_columns / 16: ",
+                                                   "the group solve's meetings", "the group kernel's footprint", &e);
+    FCHK(h, e);
+    if (!why.empty()) { h->err = why; return RNDE_ERR_BAD_ARG; }
+    auto gr = std::make_unique<rnde_ffjord::Groups>();
+    const size_t NT = (size_t)tiles, NG = (size_t)max_groups, MA = (size_t)h->cfg.max_attempts, RB = (size_t)h->R * 16 * NT;
+    FCHK(h, gr->ws.alloc(10 * RB));
+    FCHK(h, gr->norm.alloc(8 * NT + 512));
+    FCHK(h, hipMemset(gr->norm, 0, (8 * NT + 512) * 4));
+    if (Dyn::scratch_floats(G)) FCHK(h, gr->qt.alloc(NT * Dyn::scratch_floats(G)));
+    FCHK(h, gr->ctl.alloc(2 * NG));
+    FCHK(h, gr->fin.alloc(NG));
+    FCHK(h, gr->ctl_t.alloc(NT));
+    FCHK(h, gr->meta.alloc(NG * MA));
+    FCHK(h, gr->initrec_t.alloc(NT));
+    FCHK(h, gr->table.alloc(NG));
+    FCHK(h, gr->h_fin.alloc(NG));
+    FCHK(h, gr->h_table.alloc(NG));
+    FCHK(h, gr->meet.create(MA + 4, 3, tiles));
+    gr->max_groups = max_groups; gr->tiles = tiles; gr->max_columns = max_columns;
+    h->gr = std::move(gr);
+    return RNDE_OK;
+}
+
+extern "C" rnde_status rnde_ffjord_reserve_groups(rnde_ffjord* h, int32_t max_groups, int32_t max_columns) {
+    if (!h) return RNDE_ERR_BAD_ARG;
+    const std::string why = group_reserve_refusal(h->engine, h->tp.valid, max_groups, max_columns);
+    if (!why.empty()) { h->err = why; return RNDE_ERR_BAD_ARG; }
+    FCHK(h, hipDeviceSynchronize());           // (nothing of a call in flight reads what is released here)
+    h->gr.reset();
+    if (max_groups == 0) return RNDE_OK;
+    return h->engine == 2 ? groups_reserve<FcDyn>(h, h->CG, max_groups, max_columns) : groups_reserve<FtDyn>(h, h->TG, max_groups, max_columns);
+}
+
+extern "C" rnde_status rnde_ffjord_group_capacity(const rnde_ffjord* h, int32_t* max_groups_out, int32_t* max_columns_out) {
+    if (!h) return RNDE_ERR_BAD_ARG;
+    if (max_groups_out) *max_groups_out = h->gr ? h->gr->max_groups : 0;
+    if (max_columns_out) *max_columns_out = h->gr ? h->gr->max_columns : 0;
+    return RNDE_OK;
+}
+
+template <class Dyn>
+static void groups_launch(rnde_ffjord* h, const typename Dyn::Geo& G, const GroupPlan& plan, const float* x_dev, const float* p_dev, const float* e_dev,
+                          float t0, float t1, bool exact, float* logpx_dev, const Meet& meet, hipStream_t s) {
+    rnde_ffjord::Groups& W = *h->gr;
+    TileGroupParams<typename Dyn::Geo> Q{};
+    TileSolveParams<typename Dyn::Geo>& T = Q.T;
+    StepParams& P = T.F;             // (the fields of ff_solve's forward; B, Bn and the per-group pointers are set per group on the device)
+    P.x = x_dev; P.D = h->R; P.B = plan.g[0].B; P.Bn = plan.g[0].B; P.Bpad = plan.Bp; P.nwg = 1;
+    P.ctl = W.ctl; P.ctl_final = W.fin; P.meta = W.meta; P.initrec = W.initrec_t; P.initpart = W.norm;
+    P.reltol = h->cfg.reltol; P.abstol = h->cfg.abstol; P.t0 = t0; P.t1 = t1;
+    P.tape = 1; P.max_attempts = h->cfg.max_attempts; P.reg_kind = 0; P.nsave = 0; P.replay = nullptr; P.n_replay = 0;
+    P.beta1 = kBeta1; P.beta2 = kBeta2; P.rk_order = 5.f;
+    T.G = G; T.p = p_dev; T.x = x_dev; T.e = exact ? nullptr : e_dev; T.ws = W.ws; T.tape = nullptr; T.logpx = logpx_dev; T.x_out = nullptr;
+    T.norm = W.norm; T.initrec_t = W.initrec_t; T.ctl_t = W.ctl_t; T.exact = exact ? 1 : 0; T.scratch = exact ? (float*)W.qt : nullptr;
+    T.meet = meet; T.xcc = W.meet.xcc; T.xcd_slot = W.meet.slot; T.dir = 1; T.Bp = plan.Bp; T.ntiles = plan.g[0].ntiles; T.tbase = t1; T.reg = nullptr;
+    Q.table = W.table; Q.n_groups = plan.n_groups; Q.meet_rows = h->cfg.max_attempts + 4; Q.meta_stride = h->cfg.max_attempts;
+    Q.scratch_floats = Dyn::scratch_floats(G);
+    hipLaunchKernelGGL((rnde_tile_group_solve_kernel<Dyn>), dim3(plan.tiles), dim3(kFtThreads), h->lds_bytes, s, Q);
+}
+
+extern "C" rnde_status rnde_ffjord_forward_groups(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t n_groups,
+                                                  const int32_t* B_host, float t0, float t1, int32_t exact, float* logpx_dev, int64_t* nfe_out_host,
+                                                  int32_t* status_out_host, double* sum_dev, int64_t* count_dev, void* stream) {
+    if (!h) return RNDE_ERR_BAD_ARG;
+    if (h->engine == 0) { h->err = group_reserve_refusal(0, false, 0, 0); return RNDE_ERR_BAD_ARG; }
+    const std::string why = group_call_refusal(h->gr ? h->gr->max_groups : 0, h->gr ? h->gr->tiles : 0, h->cfg.max_batch, n_groups, B_host, t0, t1, exact != 0,
+                                               h->engine >= 1, e_dev != nullptr, sum_dev != nullptr, count_dev != nullptr);
+    if (!why.empty()) { h->err = why; return RNDE_ERR_BAD_ARG; }
+    if (!x_dev || !p_dev || !logpx_dev) { h->err = "TrackedFFJORD groups: x_dev, p_dev and logpx_dev are required"; return RNDE_ERR_BAD_ARG; }
+    rnde_ffjord::Groups& W = *h->gr;
+    hipStream_t s = (hipStream_t)stream;
+    const GroupPlan plan = group_plan(n_groups, B_host);
+    for (int g = 0; g < n_groups; ++g) W.h_table[g] = plan.g[g];
+    FCHK(h, hipMemcpyAsync(W.table, W.h_table, (size_t)n_groups * sizeof(TileGroup), hipMemcpyHostToDevice, s));
+    const Meet meet = W.meet.begin(plan.tiles, false, s);      // agent scope whatever the count
+    FCHK(h, W.meet.err);
+    W.log.clear();
+    FCHK(h, hipEventRecord(h->ev[0], s));
+    if (h->engine == 2) groups_launch<FcDyn>(h, h->CG, plan, x_dev, p_dev, e_dev, t0, t1, exact != 0, logpx_dev, meet, s);
+    else groups_launch<FtDyn>(h, h->TG, plan, x_dev, p_dev, e_dev, t0, t1, exact != 0, logpx_dev, meet, s);
+    FCHK(h, hipGetLastError());
+    FCHK(h, hipEventRecord(h->ev[1], s));
+    FCHK(h, hipMemcpyAsync(W.h_fin, W.fin, (size_t)n_groups * sizeof(StepState), hipMemcpyDeviceToHost, s));
+    FCHK(h, W.meet.queue_check(meet, s));
+    FCHK(h, hipStreamSynchronize(s));
+    (void)hipEventElapsedTime(&h->fwd_ms, h->ev[0], h->ev[1]);
+    {
+        hipError_t me;
+        const std::string bad = tile_meet_refusal(W.meet, meet, plan.tiles, s, "TrackedFFJORD groups: ", "the group solve", "every group was abandoned", &me);
+        FCHK(h, me);
+        if (!bad.empty()) { h->err = bad; return RNDE_ERR_HIP; }
+    }
+    W.log.resize(n_groups);
+    int first_bad = -1;
+    for (int g = 0; g < n_groups; ++g) {
+        const StepState& fin = W.h_fin[g];
+        W.log[g].resize(fin.n_att);
+        if (fin.n_att)
+            FCHK(h, hipMemcpy(W.log[g].data(), W.meta + (size_t)g * h->cfg.max_attempts, (size_t)fin.n_att * sizeof(StepMeta), hipMemcpyDeviceToHost));
+        if (nfe_out_host) nfe_out_host[g] = 3 + 6 * (int64_t)fin.n_att;
+        const rnde_status st = fin.status == 0 ? RNDE_OK : fin.status == 2 ? RNDE_ERR_MAX_ATTEMPTS : fin.status == 3 ? RNDE_ERR_DT_UNDERFLOW : RNDE_ERR_NONFINITE;
+        if (status_out_host) status_out_host[g] = st;
+        if (st != RNDE_OK && first_bad < 0) first_bad = g;
+    }
+    if (first_bad >= 0) {
+        const int cs = W.h_fin[first_bad].status;
+        h->err = group_failure(first_bad, cs);
+        return cs == 2 ? RNDE_ERR_MAX_ATTEMPTS : cs == 3 ? RNDE_ERR_DT_UNDERFLOW : RNDE_ERR_NONFINITE;
+    }
+    if (sum_dev) {                   // behind the final states, and only when every group ended well: a failed call adds nothing
+        hipLaunchKernelGGL(rnde_group_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)logpx_dev, plan.cols, sum_dev, (long long*)count_dev);
+        FCHK(h, hipGetLastError());
+    }
+    return RNDE_OK;
+}
+
+extern "C" rnde_status rnde_ffjord_group_steps(rnde_ffjord* h, int32_t g, float* steps_host, int32_t capacity, int32_t* n_attempts_out) {
+    if (!h || !n_attempts_out) return RNDE_ERR_BAD_ARG;
+    if (!h->gr || g < 0 || g >= (int)h->gr->log.size()) {
+        h->err = "group_steps: g must be a group of the last group call on this handle";
+        return RNDE_ERR_BAD_ARG;
+    }
+    const std::vector<StepMeta>& log = h->gr->log[g];
+    *n_attempts_out = (int32_t)log.size();
+    if (steps_host) {
+        if (capacity < (int)log.size()) { h->err = "group_steps: capacity below the attempt count"; return RNDE_ERR_BAD_ARG; }
+        for (size_t i = 0; i < log.size(); ++i) { steps_host[2 * i] = log[i].dt; steps_host[2 * i + 1] = (log[i].flags & F_ACCEPT) ? 1.f : 0.f; }
+    }
     return RNDE_OK;
 }
 

@@ -10,7 +10,8 @@
 // Forward solve: the whole adaptive Tsit5 solve in one launch.  Once per attempt every tile forms its partial of the error norm and the tiles
 // meet through rnde_meet.h's bounded meet_exchange (one XCD up to 32 tiles, agent scope above): partials are summed in tile order in
 // double, so every tile runs the same controller (advance_state_t over R rows) on the same bits, and a solve is bit-identical run to run.
-// A meeting that times out raises the abort word and ends the launch; the host reports it by name.
+// A meeting that times out raises the abort word and ends the launch; the host reports it by name.  A launch may also carry several
+// independent forward solves (rnde_tile_group_solve_kernel: the same body per group, agent scope, a group meeting only with itself).
 //
 // Reverse sweep: discretise-then-optimise through every Tsit5 stage of every accepted step, step sizes and times constants (track_ctrl =
 // track_initdt = 0; the saved value EEst * dt reaches the stages through EEst).  One workgroup per tile, every accepted step in one launch,
@@ -67,6 +68,7 @@
 #include "rnde_tile_meet.h"    // tile_meet, tile_place
 #include "rnde_track_rec.h"    // FfStepRec, FfAttRec, the initial-step rule's scalar reverse
 #include "rnde_rev_plan.h"    // SaveRange
+#include "rnde_group_plan.h"  // TileGroup
 
 namespace rnde {
 
@@ -136,12 +138,12 @@ struct TileRevParams {
 // arithmetic of chain_dense_points) -- into F.sv_out (R x nsave x B, caller layout).  Every tile holds the same controller bits, so the
 // range is uniform: no meeting and no barrier beyond the loop's.  The save times never enter the controller: a saving solve takes the
 // end-state solve's attempts bit for bit.
-template <class Dyn, bool KIN, bool SAVE = false>
-__global__ __launch_bounds__(kFtThreads) void rnde_tile_solve_kernel(const TileSolveParams<typename Dyn::Geo> Q) {
+// The body is tile_solve_body: what tile `tile` of the solve that Q describes does, from the load of the parameters to the last store.  Two
+// kernels run it: rnde_tile_solve_kernel (a launch is one solve, Q is the kernel argument) and rnde_tile_group_solve_kernel (a launch is
+// several solves, Q is the view of its group that a workgroup builds).
+template <class Dyn, bool KIN, bool SAVE>
+__device__ __forceinline__ void tile_solve_body(const TileSolveParams<typename Dyn::Geo>& Q, const int tile, float* ft_smem) {
     static_assert((Dyn::kAug || !KIN) && (Dyn::kSpan || !SAVE), "KIN needs the log-density row, SAVE a policy with kSpan");
-    extern __shared__ float ft_smem[];
-    int tile;
-    if (!tile_place(Q.meet, Q.xcd_slot, Q.xcc, &tile)) return;
     const int tid = threadIdx.x, lane = tid & 63;
     const typename Dyn::Geo& G = Q.G;
     constexpr bool AUG = Dyn::kAug > 0;
@@ -315,6 +317,80 @@ __global__ __launch_bounds__(kFtThreads) void rnde_tile_solve_kernel(const TileS
                 Q.reg[(size_t)B + col0 + tid] = U[(size_t)(D + 2) * Bp + tid];
             }
     }
+}
+
+template <class Dyn, bool KIN, bool SAVE = false>
+__global__ __launch_bounds__(kFtThreads) void rnde_tile_solve_kernel(const TileSolveParams<typename Dyn::Geo> Q) {
+    extern __shared__ float ft_smem[];
+    int tile;
+    if (!tile_place(Q.meet, Q.xcd_slot, Q.xcc, &tile)) return;
+    tile_solve_body<Dyn, KIN, SAVE>(Q, tile, ft_smem);
+}
+
+// Several independent forward solves ("groups") in one launch (rnde_ffjord_forward_groups; the table: rnde_group_plan.h).  Agent scope, every
+// block a tile: block b belongs to the group g with table[g].first_tile <= b < first_tile + ntiles and is tile b - first_tile of it.  It
+// builds the group's view of the parameters -- x / e / logpx from the group's first caller column, the workspace from workspace column
+// 16 first_tile under the launch's row stride Bp, the group's own controller states, step log, per-tile records, scratch and meeting
+// granules (meet_rows sequence numbers of three rows of ntiles granules, behind those of the groups in front), Meet::n = the group's tiles
+// -- and runs tile_solve_body on it: the arithmetic of a launch of its own for that batch, bit for bit.  A group meets only with itself and
+// leaves when its controller is done; nothing waits for another group.  The abort word is the launch's: a meeting that times out ends
+// every group.
+template <class Geo>
+struct TileGroupParams {
+    TileSolveParams<Geo> T;          // the launch: group 0's ranges, the common fields (G, p, exact, the tolerances and the span in F, Bp)
+    const TileGroup* table;          // [n_groups], device memory
+    int n_groups;
+    int meet_rows;                   // sequence numbers of a group's granule range
+    int meta_stride;                 // step-log records per group (max_attempts)
+    size_t scratch_floats;           // Dyn::scratch_floats per tile (0 without a scratch)
+};
+
+template <class Dyn>
+__global__ __launch_bounds__(kFtThreads) void rnde_tile_group_solve_kernel(const TileGroupParams<typename Dyn::Geo> Q) {
+    static_assert(Dyn::kDensity && Dyn::kAug == 1, "groups are forward solves of the log-density");
+    extern __shared__ float ft_smem[];
+    const int b = (int)blockIdx.x;
+    int g = -1;
+    TileGroup me{};
+    for (int i = 0; i < Q.n_groups; ++i) {
+        const TileGroup t = Q.table[i];
+        if (b >= t.first_tile && b < t.first_tile + t.ntiles) { g = i; me = t; }
+    }
+    if (g < 0) return;               // (a block behind the last group's tiles: the host launches none)
+    TileSolveParams<typename Dyn::Geo> V = Q.T;
+    const int D = V.G.D;
+    V.x += (size_t)me.col0 * D;
+    if (V.e) V.e += (size_t)me.col0 * D;
+    V.logpx += me.col0;
+    V.ws += (size_t)16 * me.first_tile;
+    V.F.x = V.x; V.F.B = me.B; V.F.Bn = me.B;
+    V.F.ctl += 2 * g; V.F.ctl_final += g; V.F.meta += (size_t)g * Q.meta_stride;
+    V.norm += (size_t)8 * me.first_tile;
+    V.initrec_t += me.first_tile; V.F.initrec = V.initrec_t;
+    V.ctl_t += me.first_tile;
+    if (V.scratch) V.scratch += (size_t)me.first_tile * Q.scratch_floats;
+    V.meet.xch += (size_t)Q.meet_rows * 3 * me.first_tile;
+    V.meet.n = me.ntiles; V.meet.global = 1;
+    V.ntiles = me.ntiles;
+    tile_solve_body<Dyn, false, false>(V, b - me.first_tile, ft_smem);
+}
+
+// sum[0] += the sum of logpx[0 .. n) in double, count[0] += n: what a likelihood pass accumulates over its calls.  One workgroup of 256
+// threads, one fixed order: thread t adds logpx[t], logpx[t + 256], logpx[t + 512], ... in that order into a double that starts at zero;
+// the 256 partials are then folded in LDS, entry i += entry i + s for s = 128, 64, ..., 1; thread 0 adds the total to *sum and n to
+// *count with a plain load and store.  No atomics, so two runs over the same values give the same bits.
+static __global__ __launch_bounds__(256) void rnde_group_sum_kernel(const float* __restrict__ logpx, int n, double* sum, long long* count) {
+    __shared__ double part[256];
+    const int t = threadIdx.x;
+    double s = 0.0;
+    for (int i = t; i < n; i += 256) s += (double)logpx[i];
+    part[t] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (t < w) part[t] += part[t + w];
+        __syncthreads();
+    }
+    if (t == 0) { *sum += part[0]; *count += (long long)n; }
 }
 
 // The reverse sweep of the taped solve; KIN: the stage cotangent is (lz, ll, l1, l2) over R = D + 3 rows.

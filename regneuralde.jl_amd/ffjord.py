@@ -476,6 +476,86 @@ class TrackedFFJORD:
         zero = torch.zeros(x.shape[0], device=x.device)
         return logpx, zero, zero, self.last_nfe, (SavedValues(saveval) if self.regularize else None)
 
+    # ---- several batches per launch (rnde_ffjord_reserve_groups / rnde_ffjord_forward_groups; engine="tiled") ----
+    def reserve_groups(self, max_groups, max_columns):
+        """Capacity of the untaped handle for group calls of up to max_groups batches and ceil(max_columns / 16) tiles; (0, 0) releases it.
+        The library's message (RndeError) when the device does not hold that many tiles or the engine has none."""
+        h = self._handle().h
+        _lib.check_ffjord(h, _lib.lib().rnde_ffjord_reserve_groups(h, int(max_groups), int(max_columns)))
+
+    def group_capacity(self):
+        """(max_groups, max_columns) of the untaped handle; (0, 0) without a reservation."""
+        a, b = C.c_int32(), C.c_int32()
+        h = self._handle().h
+        _lib.check_ffjord(h, _lib.lib().rnde_ffjord_group_capacity(h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def _grow_groups(self, n_groups, sizes):
+        """The reservation a call of these batches needs: every batch its own tiles.  Grows, never shrinks."""
+        need_g, need_c = n_groups, 16 * sum((b + 15) // 16 for b in sizes)
+        have_g, have_c = self.group_capacity()
+        if need_g > have_g or need_c > have_c:
+            self.reserve_groups(max(need_g, have_g), max(need_c, have_c))
+
+    @torch.no_grad()
+    def _forward_groups(self, xs, p, es, exact, acc=None):
+        """One group call: logpx (sum B,), the NFEs.  acc: a (2,) float64 cuda tensor whose first entry takes the sum of logpx and whose
+        second, read as an int64, the column count (the library's sum_dev / count_dev)."""
+        p = (self.p if p is None else p).contiguous()
+        if p.numel() != self.n_params or not p.is_cuda:
+            raise ValueError(f"p must be a cuda tensor of {self.n_params} parameters")
+        sizes = [int(x.shape[0]) for x in xs]
+        for x in xs:
+            if not x.is_cuda or x.dim() != 2 or x.shape[1] != self.in_dims:
+                raise ValueError(f"every batch must be a cuda tensor of shape (B, {self.in_dims})")
+        dev = xs[0].device
+        x = torch.cat([x.float() for x in xs]).contiguous()
+        e = None
+        if not exact:
+            for x_g, e_g in zip(xs, es):
+                if tuple(e_g.shape) != tuple(x_g.shape) or not e_g.is_cuda:
+                    raise ValueError(f"every probe must be a cuda tensor of its batch's shape; got {tuple(e_g.shape)} for {tuple(x_g.shape)}")
+            e = torch.cat([v.float() for v in es]).contiguous()
+        self._grow_groups(len(xs), sizes)
+        hd = self._handle()
+        n = len(xs)
+        logpx = torch.empty(x.shape[0], device=dev, dtype=torch.float32)
+        Bs, nfe, st = (C.c_int32 * n)(*sizes), (C.c_int64 * n)(), (C.c_int32 * n)()
+        sum_ptr = acc.data_ptr() if acc is not None else None
+        cnt_ptr = acc.data_ptr() + 8 if acc is not None else None
+        rc = _lib.lib().rnde_ffjord_forward_groups(hd.h, x.data_ptr(), p.data_ptr(), e.data_ptr() if e is not None else None, n, Bs, self.tspan[0],
+                                                  self.tspan[1], int(bool(exact)), logpx.data_ptr(), nfe, st, sum_ptr, cnt_ptr, _stream(dev))
+        self.last_group_status = list(st)
+        _lib.check_ffjord(hd.h, rc)
+        return logpx, [int(v) for v in nfe]
+
+    def logpx_batches(self, xs, p=None, es=None, exact=False):
+        """logpx of several independent batches from ONE launch: xs a list of (B_g, D) cuda tensors -> (list of logpx tensors, list of NFEs),
+        each bit for bit what self(x_g, p, e_g)[0] gives for that batch alone.  es=None draws the probes with draw_normal per batch, in
+        order, so a seeded layer gives the probes the loop over single calls gives.  exact=True: the exact trace, no probes.  Untaped."""
+        if self.engine != "tiled":
+            raise ValueError(f"TrackedFFJORD: several batches per launch are served on engine=\"tiled\" only; got engine={self.engine!r}")
+        xs = list(xs)
+        if not xs:
+            return [], []
+        if exact and es is not None:
+            raise ValueError("TrackedFFJORD: exact=True evaluates -tr J and takes no probes; call it without es")
+        if not exact:
+            es = [self.draw_normal(self.in_dims, x.shape[0], x.device) for x in xs] if es is None else list(es)
+            if len(es) != len(xs):
+                raise ValueError(f"es must hold one probe per batch; got {len(es)} for {len(xs)} batches")
+        logpx, nfe = self._forward_groups(xs, p, es, exact)
+        self.last_nfe = nfe[-1]
+        return list(torch.split(logpx, [int(x.shape[0]) for x in xs])), nfe
+
+    def group_steps(self, g):
+        """[(dt, accepted), ...] of every attempt of group g of the last group call (rnde_ffjord_group_steps), flattened."""
+        h, n = self._handle().h, C.c_int32()
+        _lib.check_ffjord(h, _lib.lib().rnde_ffjord_group_steps(h, int(g), None, 0, C.byref(n)))
+        arr = (C.c_float * max(2 * n.value, 1))()
+        _lib.check_ffjord(h, _lib.lib().rnde_ffjord_group_steps(h, int(g), arr, n.value, C.byref(n)))
+        return list(arr[:2 * n.value])
+
     def steps(self):
         """[(dt, accepted), ...] of every attempt of the last solve (rnde_ffjord_steps), flattened."""
         h, n = (self._last or self._handle()).h, C.c_int32()
@@ -546,8 +626,36 @@ def sample(ffjord, indims, p=None, nsamples=1, z=None):
 
 
 @torch.no_grad()
-def loglikelihood(model, batches, p=None, exact=False):
-    """src/metrics.jl:20-33: sum of logpx over the batches / the number of columns.  exact=True: logpx from the exact trace (no probe)."""
+def loglikelihood(model, batches, p=None, exact=False, groups=1):
+    """src/metrics.jl:20-33: sum of logpx over the batches / the number of columns.  exact=True: logpx from the exact trace (no probe).
+    groups=k > 1 (engine="tiled"): up to k consecutive batches share a launch (logpx_batches: every batch keeps its own solve, bit for bit;
+    the last call of a data set may carry fewer), the sum is kept on the device in double and read back once per data set.  The capacity
+    is reserved on first use from k and the largest batch; the library's message is raised when the device does not hold that many tiles."""
+    groups = int(groups)
+    if groups < 1:
+        raise ValueError(f"loglikelihood: groups must be at least 1; got {groups}")
+    if groups > 1:
+        if model.engine != "tiled":
+            raise ValueError(f"loglikelihood: groups > 1 is served on engine=\"tiled\" only; got engine={model.engine!r}")
+        acc, pending = None, []
+
+        def flush():
+            es = None if exact else [model.draw_normal(model.in_dims, x.shape[0], x.device) for x in pending]
+            model._forward_groups(pending, p, es, exact, acc)
+            pending.clear()
+        for xb in batches:
+            x = torch.as_tensor(xb, dtype=torch.float32).cuda(model.device)
+            if acc is None:
+                acc = torch.zeros(2, dtype=torch.float64, device=x.device)      # (the sum, and the column count as an int64)
+            pending.append(x)
+            if len(pending) == groups:
+                flush()
+        if pending:
+            flush()
+        if acc is None:
+            raise ZeroDivisionError("loglikelihood: no batches")      # (as the groups=1 path's 0.0 / 0)
+        host = acc.cpu()          # the one read-back of the data set
+        return float(host[0]) / int(host.view(torch.int64)[1])
     total, n = 0.0, 0
     for xb in batches:
         x = torch.as_tensor(xb, dtype=torch.float32).cuda(model.device)

@@ -52,6 +52,8 @@ def main():
     ap.add_argument("--track-ctrl", action="store_true",
                     help="differentiate the step controller in the reverse pass (engine=\"tiled\", needs --regularize 1; the equal-work comparison's "
                          "eager restatement keeps its constant steps)")
+    ap.add_argument("--eval-groups", type=int, default=1, metavar="K",
+                    help="train / test log-likelihood with K consecutive batches per launch (engine=\"tiled\"; 1: one solve per batch)")
     ap.add_argument("--out", default=None, help="default: profiles/ffjord_gaussian.json (profiles/ffjord_gaussian_kinetic.json with --kinetic, "
                                                 "profiles/ffjord_gaussian_exact.json with --exact-eval / --exact-train, "
                                                 "profiles/ffjord_gaussian_track.json with --track-ctrl)")
@@ -62,6 +64,8 @@ def main():
         ap.error("--exact-train does not go with --kinetic (the Jacobian norm row is defined on the probe)")
     if a.track_ctrl and not a.regularize:
         ap.error("--track-ctrl needs --regularize 1 (without a saved value the tracked and the constant-step sweep agree to O(tol))")
+    if a.eval_groups < 1:
+        ap.error("--eval-groups K needs K >= 1")
     exact_any = a.exact_eval or a.exact_train
     a.out = a.out or os.path.join(ROOT, "profiles", "ffjord_gaussian_kinetic.json" if a.kinetic else
                                   ("ffjord_gaussian_track.json" if a.track_ctrl else
@@ -76,9 +80,9 @@ def main():
     tr, te = rn.load_gaussian_mixture(a.batch, nsamples=2048, ngaussians=6, seed=a.seed)
     model = rn.ffjord.MLPDynamics(2, 16, generator=torch.Generator().manual_seed(a.seed))
     ff = rn.TrackedFFJORD(model, [0.0, 1.0], True, bool(a.regularize), "Tsit5", reltol=1.4e-8, abstol=1.4e-8, max_batch=a.batch,
-                          **(dict(engine="tiled") if exact_any or a.track_ctrl else {}), track_ctrl=a.track_ctrl)
+                          **(dict(engine="tiled") if exact_any or a.track_ctrl or a.eval_groups > 1 else {}), track_ctrl=a.track_ctrl)
     p = ff.p.clone().requires_grad_(True)
-    ll = lambda data: rn.loglikelihood(ff, data, p.detach(), exact=a.exact_eval)
+    ll = lambda data: rn.loglikelihood(ff, data, p.detach(), exact=a.exact_eval, groups=a.eval_groups)
     opt = rn.FluxADAM([p], eta=4e-2, weight_decay=1e-5)
     lam0, lam1 = 2.0e3, 1.0e3
     k = np.log(lam0 / lam1) / a.epochs

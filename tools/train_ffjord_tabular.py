@@ -86,6 +86,8 @@ def main():
     ap.add_argument("--exact-eval", action="store_true", help="train / test log-likelihood with the exact trace (needs --engine tiled)")
     ap.add_argument("--track-ctrl", action="store_true",
                     help="differentiate the step controller in the reverse pass (needs --engine tiled and --regularize 1)")
+    ap.add_argument("--eval-groups", type=int, default=1, metavar="K",
+                    help="train / test log-likelihood with K consecutive batches per launch (needs --engine tiled; 1: one solve per batch)")
     ap.add_argument("--out", default=None, help="default: profiles/ffjord_tabular.json (profiles/ffjord_tabular_kinetic.json with --kinetic, "
                                                 "profiles/ffjord_tabular_exact.json with --exact-eval, profiles/ffjord_tabular_track.json with "
                                                 "--track-ctrl)")
@@ -96,6 +98,8 @@ def main():
         ap.error("--exact-eval needs --engine tiled (the exact trace is served by the tiled engine only)")
     if a.track_ctrl and (a.engine != "tiled" or not a.regularize):
         ap.error("--track-ctrl needs --engine tiled and --regularize 1 (without a saved value the tracked and the constant-step sweep agree to O(tol))")
+    if a.eval_groups < 1 or (a.eval_groups > 1 and a.engine != "tiled"):
+        ap.error("--eval-groups K needs K >= 1, and --engine tiled for K > 1 (the one-workgroup engine has no tiles to share a launch between)")
     a.out = a.out or os.path.join(ROOT, "profiles", "ffjord_tabular_kinetic.json" if a.kinetic else
                                   ("ffjord_tabular_track.json" if a.track_ctrl else
                                    ("ffjord_tabular_exact.json" if a.exact_eval else "ffjord_tabular.json")))
@@ -115,7 +119,7 @@ def main():
     ff = rn.TrackedFFJORD(model, [0.0, 1.0], True, bool(a.regularize), "Tsit5", reltol=1.4e-8, abstol=1.4e-8, max_batch=a.batch, engine=a.engine,
                           track_ctrl=a.track_ctrl)
     p = ff.p.clone().requires_grad_(True)
-    ll = lambda data: rn.loglikelihood(ff, data, p.detach(), exact=a.exact_eval)
+    ll = lambda data: rn.loglikelihood(ff, data, p.detach(), exact=a.exact_eval, groups=a.eval_groups)
     opt = rn.FluxADAM([p], eta=1e-2, weight_decay=1e-5)
     lam0, lam1 = 5.0e3, 1.0e3
     k = np.log(lam0 / lam1) / a.epochs
