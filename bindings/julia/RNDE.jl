@@ -676,6 +676,18 @@ function adam_step!(p::ROCVector{Float32}, g::ROCVector{Float32}, m::ROCVector{F
     return p
 end
 
+# Flux.Optimise.Optimiser(WeightDecay(wd), ADAM(eta, (beta1, beta2))) on one flat group, one launch (experiments/ffjord_gaussian.jl:132,
+# ffjord_tabular.jl:133): g' = gscale * g + wd * p, then adam_step!'s recurrence
+function adam_wd_step!(p::ROCVector{Float32}, g::ROCVector{Float32}, m::ROCVector{Float32}, v::ROCVector{Float32}, t::Integer;
+                       eta = 0.001f0, beta = (0.9f0, 0.999f0), eps = 1f-8, gscale = 1f0, wd = 1f-5)
+    st = GC.@preserve p g m v begin
+        ccall((:rnde_adam_wd_step, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cfloat, Cfloat, Cfloat, Cfloat, Cfloat, Cfloat, Ptr{Cvoid}),
+              devptr(p), devptr(g), devptr(m), devptr(v), length(p), t, eta, beta[1], beta[2], eps, gscale, wd, _stream())
+    end
+    st == 0 || error("rnde_adam_wd_step: status $st")
+    return p
+end
+
 # one process per GPU (Distributed / MPI.jl carry the 128-byte id from rank 0 to the others)
 comm_unique_id() = (id = zeros(UInt8, 128); ccall((:rnde_comm_unique_id, LIB), Cint, (Ptr{UInt8},), id) == 0 || error("rnde_comm_unique_id"); id)
 function comm_create(id::Vector{UInt8}, rank::Integer, world::Integer, device::Integer)
@@ -861,6 +873,30 @@ function ffjord_backward_kinetic(h::FfjordHandle, logpx_bar::ROCVector{Float32},
         st == 0 || error("rnde_ffjord_backward_kinetic status $st: ", _fferr(h.ptr))
     end
     return pbar, xbar
+end
+
+# The gradient of the experiments' loss_function in one call (rnde_ffjord_nll_grad): the taped forward, the loss terms and the sweep's
+# seeds on the device, the reverse sweep.  mode 0: Hutchinson probe e (nothing: the library's draw from seed), 1: exact trace (e = nothing),
+# 2: the kinetic rows.  Returns (pbar, xbar, terms, reg, nfe): terms is a 3-vector on the device, (-mean(logpx), mean(lambda1), mean(lambda2)),
+# reg = lambda_r * mean(sv.saveval) on the host.  The handle holds no tape afterwards.
+function ffjord_nll_grad(h::FfjordHandle, x::ROCMatrix{Float32}, p::ROCVector{Float32}, e::Union{Nothing,ROCMatrix{Float32}}, tspan;
+                         mode::Integer = 0, lambda_r = 0f0, lambda_k = 0f0, lambda_j = 0f0, seed::Integer = 0, need_xbar::Bool = false)
+    D, B = size(x)
+    pbar = similar(p)
+    xbar = need_xbar ? similar(x) : nothing
+    terms = similar(p, 3)
+    reg = Ref{Float32}(0f0)
+    nfe = Ref{Int64}(0)
+    GC.@preserve x p e pbar xbar terms begin
+        st = ccall((:rnde_ffjord_nll_grad, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float32, Float32, UInt64, Int32, Float32, Float32, Float32, Ptr{Cvoid}, Ptr{Cvoid},
+                    Ptr{Cvoid}, Ptr{Cvoid}, Ref{Float32}, Ref{Int64}, Ptr{Cvoid}),
+                   h.ptr, devptr(x), devptr(p), e === nothing ? C_NULL : devptr(e), B, Float32(tspan[1]), Float32(tspan[2]), UInt64(seed), Int32(mode),
+                   Float32(lambda_r), Float32(lambda_k), Float32(lambda_j), devptr(pbar), xbar === nothing ? C_NULL : devptr(xbar), C_NULL, devptr(terms),
+                   reg, nfe, _stream())
+        st == 0 || error("rnde_ffjord_nll_grad status $st: ", _fferr(h.ptr))
+    end
+    return pbar, xbar, terms, reg[], Int(nfe[])
 end
 
 # Tracker glue of the kinetic call: (logpx, lambda1, lambda2) -> (x-bar, p-bar); a missing cotangent counts as zeros

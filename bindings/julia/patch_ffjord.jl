@@ -124,3 +124,18 @@ function RegNeuralDE.sample(n::TrackedFFJORD, indims::Int, p = n.p; nsamples::In
 end
 
 RNDE_randn(dims...) = AMDGPU.randn(Float32, dims...)
+
+# The training step in one call.  The two lines of the experiments' loop (experiments/ffjord_tabular.jl:225-229, ffjord_gaussian.jl:224-225)
+#
+#     gs = Tracker.gradient(p -> loss_function(x, ffjord, p; λᵣ = λᵣ, notrack = false), ps...)
+#     update_parameters!(ps, gs, opt)                    # opt = Optimiser(WeightDecay(1e-5), ADAM(1e-2))
+#
+# become, with m = zero(p), v = zero(p) made once and t = 1, 2, ... counted by the loop:
+#
+#     H = _ffjord_handle(ffjord, size(x, 2))
+#     pbar, _, terms, reg, nfe = RNDE.ffjord_nll_grad(H, x, Tracker.data(ffjord.p), nothing, _convert_tspan(ffjord.tspan, ffjord.p);
+#                                                     lambda_r = REGULARIZE ? λᵣ : 0f0, seed = t)     # terms[1] = -mean(logpx), on the device
+#     RNDE.adam_wd_step!(Tracker.data(ffjord.p), pbar, m, v, t; eta = 1f-2, wd = 1f-5)
+#
+# (the {false} method with regularize = true: mode = 2, lambda_k and lambda_j the weights of mean(r1) and mean(r2); exact = true: mode = 1.)
+# The logger's three numbers are Array(terms)[1] + reg, Array(terms)[1] and reg, read when they are wanted.

@@ -418,6 +418,11 @@ rnde_status rnde_momentum_step_scaled(float* p_dev, const float* g_dev, float* v
  * scaled by gscale first (1 / world after a sum-all-reduce).  t = 1, 2, ... is the step being taken; m, v start at zero. */
 rnde_status rnde_adam_step(float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t len, int64_t t, float eta, float beta1,
                            float beta2, float eps, float gscale, void* stream);
+/* Flux.Optimise.Optimiser(WeightDecay(wd), ADAM(eta, (beta1, beta2))) (the optimiser of reference experiments/ffjord_gaussian.jl:132 and
+ * ffjord_tabular.jl:133) on one flat group, one launch: g' = gscale * g + wd * p, then the recurrence of rnde_adam_step on g'.  With wd = 0
+ * and finite p it produces the bits of rnde_adam_step. */
+rnde_status rnde_adam_wd_step(float* p_dev, const float* g_dev, float* m_dev, float* v_dev, int64_t len, int64_t t, float eta, float beta1,
+                              float beta2, float eps, float gscale, float wd, void* stream);
 /* Flux.Optimise.AdaBelief(eta, (beta1, beta2)) (the optimiser of reference experiments/sde_toy_problem.jl:65, Flux 0.11.6 as pinned by the
  * reference's Manifest) on one flat parameter group, one launch, g scaled by gscale first:
  *     m = beta1 m + (1 - beta1) g ;  s = beta2 s + (1 - beta2) (g - m)^2 ;  p -= eta m / (sqrt(s) + eps)
@@ -892,6 +897,36 @@ rnde_status rnde_ffjord_forward_groups(rnde_ffjord* h, const float* x_dev, const
                                        int32_t* status_out_host, double* sum_dev, int64_t* count_dev, void* stream);
 /* (dt, accepted) of every attempt of group g of the last group call, as rnde_ffjord_steps (steps_host NULL: the count only). */
 rnde_status rnde_ffjord_group_steps(rnde_ffjord* h, int32_t g, float* steps_host, int32_t capacity, int32_t* n_attempts_out);
+/* The gradient of the experiments' loss_function (reference experiments/ffjord_tabular.jl:143-147, ffjord_gaussian.jl:142-146) in one call:
+ *     loss = -mean(logpx) + lambda_r * mean(sv.saveval) + lambda_k * mean(lambda1) + lambda_j * mean(lambda2)
+ * the second term on regularize = 1 handles (the {true} method), the last two in mode 2 (the {false} method called with regularize = true).
+ * It is the taped forward (mode 0: rnde_ffjord_forward, 1: _forward_exact, 2: _forward_kinetic), then the loss-and-seed kernel, then the
+ * reverse sweep (rnde_ffjord_backward; mode 2: _backward_kinetic) -- the same launches, so p_bar, x_bar, logpx, NFE and the step log are
+ * bit for bit those of the two calls, on every engine, with track_ctrl, with the library's probe draw (e_dev NULL, from seed), and
+ * rnde_ffjord_timing / _steps / _step_log report the solve as after a forward.  No host round trip remains between solve and sweep.
+ * The loss-and-seed kernel (one workgroup of 256 threads, queued directly behind the solve launch, in front of the forward's host wait):
+ * thread i adds elements i, i + 256, ... in double, in rising index; the 256 partials are combined in a fixed tree; the result depends on
+ * the values and on B only.  It writes
+ *     terms_dev[0] = (float)(-sum(logpx) / B)
+ *     terms_dev[1..2] = (float)(sum(lambda1) / B), (float)(sum(lambda2) / B), which are 0 outside mode 2
+ *     logpx_bar[b] = -1.0f / (float)B
+ *     in mode 2, reg_bar[0][b] = lambda_k / (float)B and reg_bar[1][b] = lambda_j / (float)B
+ * The two seed arrays are fp32, with one fp32 division each; they go into buffers the handle owns.  A NaN in logpx stays a NaN in the term.
+ * On the host, after the step log has been read (n = the number of saved values, including the 0 at init when cb_save_start is set):
+ *     *reg_out_host = (float)((double)lambda_r * sum(saveval) / n), summed in double in log order; 0 on regularize = 0 handles
+ *     saveval_bar[i] = lambda_r / (float)n, one fp32 division
+ * p_bar_dev: P (overwritten).  x_bar_dev: D x B, may be NULL.  logpx_dev: B, may be NULL (a buffer of the handle then).  terms_dev: 3 floats
+ * on the device, not read back.  The handle's buffers (logpx, logpx_bar, reg, reg_bar) are allocated at the first fused call.
+ * After the call the handle holds no valid tape: the call consumes its own, x, p and e need not outlive it, and a later
+ * rnde_ffjord_backward returns RNDE_ERR_NO_TAPE.  It synchronises where the two calls it replaces do.  A solve that ends with a non-zero
+ * status returns that status and launches no sweep.
+ * RNDE_ERR_BAD_ARG before any launch, each with a message naming the reason: mode outside 0..2; mode 1 on engine 0 (the message points at
+ * the tiled engine) or with e_dev given; mode 2 on a regularize = 1 handle or outside the kinetic limits; lambda_k or lambda_j non-zero
+ * outside mode 2; lambda_r non-zero on a regularize = 0 handle; p_bar_dev, terms_dev, reg_out_host or nfe_out NULL; B outside
+ * 1..max_batch; t1 <= t0. */
+rnde_status rnde_ffjord_nll_grad(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0, float t1,
+                                 uint64_t seed, int32_t mode, float lambda_r, float lambda_k, float lambda_j, float* p_bar_dev, float* x_bar_dev,
+                                 float* logpx_dev, float* terms_dev, float* reg_out_host, int64_t* nfe_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,4 +11,4 @@ from .classifier import ClassifierNODE, FluxADAM, FluxAdaBelief, FluxOptimiser, 
 from .dataparallel import FlatGrads, GradientAllReducer, shard_columns  # noqa: F401
 from .timeseries import FluxAdaMax, fused_latent_loss_and_grad, LatentGRU, LatentTimeSeriesModel, build_latent_ode, get_t_saveat, kl_divergence, lambda_k, latent_loss_function, latent_total_loss, log_likelihood, sample_tbounds  # noqa: F401
 from . import ffjord  # noqa: F401
-from .ffjord import ConcatSquashLinear, TrackedFFJORD, load_gaussian_mixture, load_miniboone, loglikelihood, sample  # noqa: F401
+from .ffjord import ConcatSquashLinear, TrackedFFJORD, fused_ffjord_loss_and_grad, load_gaussian_mixture, load_miniboone, loglikelihood, sample  # noqa: F401

@@ -239,6 +239,9 @@ def lib():
         L.rnde_ffjord_group_capacity.argtypes = [vp, i32p, i32p]
         L.rnde_ffjord_forward_groups.argtypes = [vp, vp, vp, vp, i32, i32p, f, f, i32, vp, i64p, i32p, vp, vp, vp]
         L.rnde_ffjord_group_steps.argtypes = [vp, i32, fp, i32, i32p]
+    if hasattr(L, "rnde_ffjord_nll_grad"):            # (as above: an older build has neither the one-call step nor its optimiser)
+        L.rnde_ffjord_nll_grad.argtypes = [vp, vp, vp, vp, i32, f, f, u64, i32, f, f, f, vp, vp, vp, vp, fp, i64p, vp]
+        L.rnde_adam_wd_step.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int64, f, f, f, f, f, f, vp]
     _lib = L
     return L
 
@@ -260,6 +263,7 @@ EXPORTS = ["rnde_version", "rnde_debug_poison_allocs", "rnde_debug_poison_bytes"
            "rnde_ffjord_chain_param_count", "rnde_ffjord_create_chain", "rnde_ffjord_forward_exact", "rnde_ffjord_forward_exact_replay",
            "rnde_ffjord_set_track_ctrl", "rnde_ffjord_track_ctrl",
            "rnde_ffjord_reserve_groups", "rnde_ffjord_group_capacity", "rnde_ffjord_forward_groups", "rnde_ffjord_group_steps",
+           "rnde_ffjord_nll_grad", "rnde_adam_wd_step",
            "rnde_node_create_tiled", "rnde_node_tiled_lds_bytes", "rnde_node_set_tracking", "rnde_node_tracking", "rnde_node_attempts_ext",
            "rnde_node_tiled_reserve_saveat", "rnde_node_tiled_saveat_capacity", "rnde_debug_arm_replay",
            "rnde_node_classifier_predict", "rnde_latent_decode_mse"]

@@ -270,11 +270,13 @@ class FluxADAM:
     """Flux.Optimise.ADAM(eta, (beta1, beta2)), optionally behind InvDecay (experiments/mnist_nsde.jl: Optimiser(InvDecay(1.0e-5), ADAM(0.01))), group by group, one launch per group through
     the C ABI (rnde_adam_step); same recurrence as torch.optim.Adam (tests/test_gpu_layer.py)."""
 
-    def __init__(self, params, eta=0.001, beta=(0.9, 0.999), eps=1.0e-8, gamma=0.0, weight_decay=0.0):
+    def __init__(self, params, eta=0.001, beta=(0.9, 0.999), eps=1.0e-8, gamma=0.0, weight_decay=0.0, one_launch=False):
         """gamma > 0: Flux.Optimise.Optimiser(InvDecay(gamma), ADAM(eta)) as experiments/mnist_nsde.jl builds it -- InvDecay scales the gradient
         by 1 / (1 + gamma n) (n = 1, 2, ... per group) BEFORE ADAM sees it; the factor rides in the launch's gradient scale.
         weight_decay > 0: Flux.Optimise.Optimiser(WeightDecay(weight_decay), ADAM(eta)) (experiments/ffjord_gaussian.jl) -- weight_decay * p is
-        added to the (scaled) gradient before ADAM sees it."""
+        added to the (scaled) gradient before ADAM sees it.  one_launch=True forms that sum inside the optimiser's launch (rnde_adam_wd_step);
+        the default composes it with two torch kernels in front of rnde_adam_step."""
+        self.one_launch = bool(one_launch)
         self.params = [p for p in params if p.numel() > 0]
         self.eta, self.beta, self.eps, self.gamma, self.weight_decay = eta, beta, eps, gamma, weight_decay
         self.n = [1 for _ in self.params]                 # InvDecay state starts at 1
@@ -295,6 +297,14 @@ class FluxADAM:
                 raise RuntimeError("FluxADAM runs on the device only")
             g = g.contiguous()
             gs = float(grad_scale) / (1.0 + self.gamma * self.n[i])
+            if self.weight_decay and self.one_launch and not self.gamma:
+                st = _lib.lib().rnde_adam_wd_step(p.data_ptr(), g.data_ptr(), self.m[i].data_ptr(), self.v[i].data_ptr(), p.numel(), self.t, self.eta,
+                                                  self.beta[0], self.beta[1], self.eps, float(grad_scale), float(self.weight_decay),
+                                                  C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream))
+                _lib.check(None, st)
+                self.n[i] += 1
+                p.grad = None
+                continue
             if self.weight_decay:
                 g = g.mul(float(grad_scale)).add_(p.data, alpha=float(self.weight_decay)).contiguous()
                 gs = 1.0 / (1.0 + self.gamma * self.n[i])

@@ -18,6 +18,7 @@
 #include "rnde_tile_driver.h"
 #include "rnde_tile_host.h"
 #include "rnde_probe.h"
+#include "rnde_ffjord_loss.h"
 
 using namespace rnde;
 
@@ -84,6 +85,8 @@ struct rnde_ffjord {
         std::vector<std::vector<StepMeta>> log;      // the step logs of the last group call
     };
     std::unique_ptr<Groups> gr;
+    // rnde_ffjord_nll_grad: logpx when the caller passes NULL, the kinetic rows and the reverse sweep's seeds (allocated at the first fused call)
+    DevBuf<float> f_logpx, f_logpx_bar, f_reg, f_reg_bar;      // [max_batch], [max_batch], [2][max_batch], [2][max_batch]
 };
 
 #define FCHK(h, x)                                                                                  \
@@ -447,7 +450,7 @@ static void tile_launch_feval(rnde_ffjord* h, const typename Dyn::Geo& G, const 
 // tau = t1 - t).  reg_out_dev != NULL: the kinetic forward (D + 3 rows; ff_kinetic_ready has run).
 static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0, float t1,
                             uint64_t seed, const float* steps_host, int32_t n_steps, float* logpx_dev, float* x_out_dev, int32_t keep_tape,
-                            hipStream_t s, float* reg_out_dev = nullptr, bool exact = false) {
+                            hipStream_t s, float* reg_out_dev = nullptr, bool exact = false, const FfLossSeed* ls = nullptr) {
     const bool kin = reg_out_dev != nullptr;
     if (!x_dev || !p_dev || B < 1 || B > h->cfg.max_batch) { h->err = "bad argument (B must be 1..max_batch)"; return RNDE_ERR_BAD_ARG; }
     if (!(t1 > t0)) { h->err = "TrackedFFJORD: tspan must satisfy t1 > t0 (sample() integrates t1 -> t0 itself)"; return RNDE_ERR_BAD_ARG; }
@@ -488,6 +491,10 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
     else hipLaunchKernelGGL(rnde_ffjord_solve_kernel<false>, dim3(1), dim3(h->T), h->lds_bytes, s, Q);
     FCHK(h, hipGetLastError());
     FCHK(h, hipEventRecord(h->ev[1], s));
+    if (ls) {                  // rnde_ffjord_nll_grad: the loss terms and the sweep's seeds, behind the solve and in front of the host wait
+        ff_launch_loss_seed(*ls, kin, s);
+        FCHK(h, hipGetLastError());
+    }
     const StepState& fin = *h->h_fin;
     FCHK(h, hipMemcpyAsync(h->h_fin, h->ctl + 2, sizeof(StepState), hipMemcpyDeviceToHost, s));
     if (tiles) FCHK(h, h->meet.queue_check(meet, s));
@@ -519,7 +526,7 @@ static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const f
 static rnde_status ff_forward(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0, float t1, uint64_t seed,
                               const float* steps_host, int32_t n_steps, float* logpx_dev, float* z_out_dev, int64_t* nfe_out, float* saveval_host,
                               int32_t* n_saveval_out, int32_t keep_tape, void* stream, bool kin = false, float* reg_out_dev = nullptr,
-                              bool exact = false) {
+                              bool exact = false, const FfLossSeed* ls = nullptr) {
     if (!h) return RNDE_ERR_BAD_ARG;
     if (exact && h->engine == 0) {
         h->err = "TrackedFFJORD exact trace: the one-workgroup engine does not serve the exact forward; create the handle with "
@@ -533,7 +540,7 @@ static rnde_status ff_forward(rnde_ffjord* h, const float* x_dev, const float* p
         if (rnde_status kst = ff_kinetic_ready(h)) return kst;
     }
     rnde_status st = ff_solve(h, +1, x_dev, p_dev, e_dev, B, t0, t1, seed, steps_host, n_steps, logpx_dev, z_out_dev, keep_tape, (hipStream_t)stream,
-                              kin ? reg_out_dev : nullptr, exact);
+                              kin ? reg_out_dev : nullptr, exact, ls);
     if (st != RNDE_OK) return st;
     if (nfe_out) *nfe_out = 3 + 6 * (int64_t)h->n_att;      // 2 (initial dt) + 1 (fsalfirst) + 6 per attempt, as rnde_node_forward
     int nsv = 0;
@@ -682,6 +689,54 @@ extern "C" rnde_status rnde_ffjord_backward_kinetic(rnde_ffjord* h, const float*
     }
     if (h->tp.valid && !h->tp.kin) { h->err = "backward_kinetic: the taped forward has no kinetic energy rows (use rnde_ffjord_backward)"; return RNDE_ERR_BAD_ARG; }
     return ff_backward(h, logpx_bar_dev, nullptr, reg_bar_dev, p_bar_dev, x_bar_dev, stream);
+}
+
+// The training step's gradient in one call (include/rnde.h; the formulas: rnde_ffjord_loss.h): the taped forward with the loss-and-seed
+// kernel behind its solve launch, the saved values' term on the host, the reverse sweep.  The call consumes its own tape.
+extern "C" rnde_status rnde_ffjord_nll_grad(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0, float t1,
+                                            uint64_t seed, int32_t mode, float lambda_r, float lambda_k, float lambda_j, float* p_bar_dev,
+                                            float* x_bar_dev, float* logpx_dev, float* terms_dev, float* reg_out_host, int64_t* nfe_out, void* stream) {
+    if (!h) return RNDE_ERR_BAD_ARG;
+    auto refuse = [&](const char* why) { h->err = why; return RNDE_ERR_BAD_ARG; };
+    if (mode < 0 || mode > 2) return refuse("nll_grad: mode must be 0 (Hutchinson probe), 1 (exact trace) or 2 (kinetic energy and Jacobian norm rows)");
+    if (mode == 1 && h->engine == 0)
+        return refuse("nll_grad mode 1: TrackedFFJORD exact trace: the one-workgroup engine does not serve the exact forward; create the handle with "
+                      "rnde_ffjord_create_tiled (engine = \"tiled\") or rnde_ffjord_create_chain");
+    if (mode == 1 && e_dev) return refuse("nll_grad mode 1: the exact trace takes no probe; e_dev must be NULL");
+    if (mode != 2 && (lambda_k != 0.f || lambda_j != 0.f))
+        return refuse("nll_grad: lambda_k and lambda_j weigh the kinetic energy and Jacobian norm rows, which exist in mode 2 only; they must be 0 outside it");
+    if (lambda_r != 0.f && !h->cfg.regularize)
+        return refuse("nll_grad: lambda_r weighs the saved values EEst * dt, which a regularize = 0 handle does not have; it must be 0 there");
+    if (!p_bar_dev || !terms_dev || !reg_out_host || !nfe_out) return refuse("nll_grad: p_bar_dev, terms_dev, reg_out_host and nfe_out are required");
+    if (!x_dev || !p_dev || B < 1 || B > h->cfg.max_batch) return refuse("nll_grad: bad argument (x_dev and p_dev are required, B must be 1..max_batch)");
+    if (!(t1 > t0)) return refuse("nll_grad: TrackedFFJORD: tspan must satisfy t1 > t0");
+    if (mode == 2)
+        if (rnde_status kst = ff_kinetic_ready(h)) return kst;
+    const bool kin = mode == 2;
+    const size_t MB = (size_t)h->cfg.max_batch;
+    if (!h->f_logpx_bar) {
+        DevBuf<float> a, b, c, d;      // (the handle takes all four or none)
+        hipError_t e = a.alloc(MB);
+        if (e == hipSuccess) e = b.alloc(MB);
+        if (e == hipSuccess) e = c.alloc(2 * MB);
+        if (e == hipSuccess) e = d.alloc(2 * MB);
+        FCHK(h, e);
+        h->f_logpx.swap(a); h->f_logpx_bar.swap(b); h->f_reg.swap(c); h->f_reg_bar.swap(d);
+    }
+    float* logpx = logpx_dev ? logpx_dev : (float*)h->f_logpx;
+    FfLossSeed ls{};
+    ls.logpx = logpx; ls.reg = kin ? (float*)h->f_reg : nullptr; ls.terms = terms_dev; ls.logpx_bar = h->f_logpx_bar;
+    ls.reg_bar = kin ? (float*)h->f_reg_bar : nullptr; ls.B = B; ls.lambda_k = lambda_k; ls.lambda_j = lambda_j;
+    std::vector<float> sv((size_t)h->cfg.max_attempts + 1), sv_bar;
+    int32_t nsv = 0;
+    rnde_status st = ff_forward(h, x_dev, p_dev, mode == 1 ? nullptr : e_dev, B, t0, t1, seed, nullptr, 0, logpx, nullptr, nfe_out, sv.data(), &nsv, 1, stream,
+                                kin, kin ? (float*)h->f_reg : nullptr, mode == 1, &ls);
+    if (st != RNDE_OK) { h->tp.valid = false; return st; }      // (no sweep behind a solve that failed)
+    *reg_out_host = h->cfg.regularize ? ff_saveval_term(sv.data(), nsv, lambda_r, sv_bar) : 0.f;
+    st = ff_backward(h, h->f_logpx_bar, h->cfg.regularize && nsv ? sv_bar.data() : nullptr, kin ? (const float*)h->f_reg_bar : nullptr, p_bar_dev, x_bar_dev,
+                     stream);
+    h->tp.valid = false;
+    return st;
 }
 
 extern "C" rnde_status rnde_ffjord_sample(rnde_ffjord* h, const float* p_dev, const float* z_dev, int32_t n, float t0, float t1, uint64_t seed,

@@ -165,4 +165,18 @@ static __global__ __launch_bounds__(256) void rnde_adam_kernel(float* __restrict
     p[i] = p[i] - mn / bc1 / (sqrtf(vn / bc2) + eps) * eta;
 }
 
+// Optimiser(WeightDecay(wd), ADAM(eta, (beta1, beta2))) on one flat parameter group (include/rnde.h: rnde_adam_wd_step; the optimiser of
+// the two FFJORD experiments): g' = gscale * g + wd * p, then rnde_adam_kernel's recurrence, written as it is there.
+static __global__ __launch_bounds__(256) void rnde_adam_wd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                           long long len, float gscale, float wd, float eta, float b1, float b2, float bc1, float bc2, float eps) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= len) return;
+    const float pi = p[i];
+    const float gs = g[i] * gscale + wd * pi;
+    const float mn = b1 * m[i] + (1.f - b1) * gs;
+    const float vn = b2 * v[i] + (1.f - b2) * gs * gs;
+    m[i] = mn; v[i] = vn;
+    p[i] = pi - mn / bc1 / (sqrtf(vn / bc2) + eps) * eta;
+}
+
 }  // namespace rnde

@@ -425,6 +425,12 @@ class TrackedFFJORD:
         self._pool.append(_Handle(self.config(), self.engine, self.track_ctrl))
         return self._pool[-1]
 
+    def _fused_handle(self):
+        """The handle of fused_ffjord_loss_and_grad: its own, so that a one-call step leaves the tape pool and the untaped handle alone."""
+        if getattr(self, "_fh", None) is None:
+            self._fh = _Handle(self.config(), self.engine, self.track_ctrl)
+        return self._fh
+
     def draw_normal(self, rows, cols, device):
         """(cols, rows) standard normals from the library's stream (a fresh seed per call: the reference's CUDA.randn default argument)."""
         out = torch.empty(cols, rows, device=device, dtype=torch.float32)
@@ -602,6 +608,75 @@ class TrackedFFJORD:
                                                                 e.contiguous().data_ptr() if e is not None else None, x.shape[0], float(t),
                                                                 int(e is None), out.data_ptr(), _stream(x.device)))
         return out
+
+
+def check_one_call_served(ff, e, lam_r, kinetic, exact):
+    """ValueError naming the reason for what rnde_ffjord_nll_grad would refuse (before a device is needed)."""
+    if exact and ff.engine != "tiled":
+        raise ValueError("fused_ffjord_loss_and_grad: exact=True is served on engine=\"tiled\" only (the tiled engine's solve and reverse sweep); "
+                         f"got engine={ff.engine!r}")
+    if exact and e is not None:
+        raise ValueError("fused_ffjord_loss_and_grad: exact=True evaluates -tr J and takes no probe; call it without e")
+    if kinetic is not None:
+        if ff.regularize:
+            raise ValueError("fused_ffjord_loss_and_grad: kinetic=(lam_k, lam_j) weighs the kinetic energy and Jacobian norm rows, which a "
+                             "regularize=True layer ({true}) does not have: its method never passes regularize on (ffjord.jl:119)")
+        if exact:
+            raise ValueError("fused_ffjord_loss_and_grad: exact=True together with the kinetic rows is not served: the Jacobian norm row is "
+                             "defined on the probe")
+        if len(kinetic) != 2:
+            raise ValueError("fused_ffjord_loss_and_grad: kinetic is None or the pair (lam_k, lam_j)")
+        check_kinetic_served(ff.model, ff.engine)
+    if float(lam_r) != 0.0 and not ff.regularize:
+        raise ValueError("fused_ffjord_loss_and_grad: lam_r weighs the saved values EEst * dt, which a regularize=False layer ({false}) does not "
+                         "have; lam_r must be 0 there")
+
+
+def fused_ffjord_loss_and_grad(ff, x, p=None, e=None, lam_r=0.0, kinetic=None, exact=False, need_x_grad=False):
+    """The gradient of the experiments' loss_function (ffjord_tabular.jl:143-147, ffjord_gaussian.jl:142-146) in ONE library call,
+    rnde_ffjord_nll_grad: the taped solve, the loss terms and the reverse sweep's seeds on the device, the reverse sweep -- no torch loss, no
+    autograd, no read-back of the cotangents.
+
+        loss = -mean(logpx) + lam_r * mean(sv.saveval) + lam_k * mean(lambda1) + lam_j * mean(lambda2)
+
+    lam_r: {true} layers; kinetic=(lam_k, lam_j): the {false} method's regularize = true rows; exact=True: the exact trace (engine="tiled", no
+    e).  e=None: the library's probe draw (a fresh seed per call).  Sets p.grad (and x.grad with need_x_grad=True); returns
+    (nll, reg, lam1_mean, lam2_mean, nfe): nll and the two means are 0-dim device tensors that are not read back, reg = lam_r * mean(saveval)
+    is the host float the library computes from the step log.  Runs on one handle of its own (ff._fused_handle()): the autograd tape pool
+    and the handle of the untaped calls are not touched."""
+    check_one_call_served(ff, e, lam_r, kinetic, exact)
+    p = ff.p if p is None else p
+    if not (x.is_cuda and p.is_cuda):
+        raise RuntimeError("fused_ffjord_loss_and_grad runs on the device only: x and p must be cuda tensors")
+    xd = x.detach().contiguous().float()
+    if xd.dim() != 2 or xd.shape[1] != ff.in_dims:
+        raise ValueError(f"x must be (B, {ff.in_dims})")
+    pd = p.detach().contiguous()
+    if pd.numel() != ff.n_params:
+        raise ValueError(f"p must hold {ff.n_params} parameters; got {pd.numel()}")
+    if e is not None:
+        if tuple(e.shape) != tuple(xd.shape) or not e.is_cuda:
+            raise ValueError(f"e must be a cuda tensor of x's shape {tuple(xd.shape)} (B, D); got {tuple(e.shape)}")
+        e = e.detach().contiguous().float()
+    hd = ff._fused_handle()
+    mode = 1 if exact else (2 if kinetic is not None else 0)
+    lam_k, lam_j = (float(kinetic[0]), float(kinetic[1])) if kinetic is not None else (0.0, 0.0)
+    pb = torch.empty_like(pd)
+    xb = torch.empty_like(xd) if need_x_grad else None
+    terms = torch.empty(3, device=xd.device, dtype=torch.float32)
+    reg, nfe = C.c_float(), C.c_int64()
+    ff._seed += 1
+    st = _lib.lib().rnde_ffjord_nll_grad(hd.h, xd.data_ptr(), pd.data_ptr(), e.data_ptr() if e is not None else None, xd.shape[0], ff.tspan[0],
+                                         ff.tspan[1], ff._seed, mode, float(lam_r), lam_k, lam_j, pb.data_ptr(),
+                                         xb.data_ptr() if xb is not None else None, None, terms.data_ptr(), C.byref(reg), C.byref(nfe),
+                                         _stream(xd.device))
+    ff._last = ff._last_bwd = hd
+    _lib.check_ffjord(hd.h, st)
+    ff.last_nfe = int(nfe.value)
+    p.grad = pb.view_as(p)
+    if need_x_grad:
+        x.grad = xb.view_as(x)
+    return terms[0], float(reg.value), terms[1], terms[2], ff.last_nfe
 
 
 @torch.no_grad()

@@ -54,6 +54,9 @@ def main():
                          "eager restatement keeps its constant steps)")
     ap.add_argument("--eval-groups", type=int, default=1, metavar="K",
                     help="train / test log-likelihood with K consecutive batches per launch (engine=\"tiled\"; 1: one solve per batch)")
+    ap.add_argument("--one-call", action="store_true",
+                    help="the training step through rnde_ffjord_nll_grad and rnde_adam_wd_step (fused_ffjord_loss_and_grad, "
+                         "FluxADAM(one_launch=True)) instead of the layer call, the torch loss, backward() and the composed optimiser")
     ap.add_argument("--out", default=None, help="default: profiles/ffjord_gaussian.json (profiles/ffjord_gaussian_kinetic.json with --kinetic, "
                                                 "profiles/ffjord_gaussian_exact.json with --exact-eval / --exact-train, "
                                                 "profiles/ffjord_gaussian_track.json with --track-ctrl)")
@@ -83,7 +86,7 @@ def main():
                           **(dict(engine="tiled") if exact_any or a.track_ctrl or a.eval_groups > 1 else {}), track_ctrl=a.track_ctrl)
     p = ff.p.clone().requires_grad_(True)
     ll = lambda data: rn.loglikelihood(ff, data, p.detach(), exact=a.exact_eval, groups=a.eval_groups)
-    opt = rn.FluxADAM([p], eta=4e-2, weight_decay=1e-5)
+    opt = rn.FluxADAM([p], eta=4e-2, weight_decay=1e-5, one_launch=a.one_call)
     lam0, lam1 = 2.0e3, 1.0e3
     k = np.log(lam0 / lam1) / a.epochs
     dummy = torch.from_numpy(tr.X[:a.batch]).to(dev)
@@ -109,11 +112,16 @@ def main():
             x = torch.from_numpy(xb).to(dev)
             _sync()
             t0 = time.perf_counter()
-            logpx, l1, l2, nfe, sv = ff(x, p, exact=True) if a.exact_train else ff(x, p, regularize=kin)
-            loss = -logpx.mean() + (lam * sv.saveval.mean() if a.regularize else 0.0)
-            if kin:
-                loss = loss + lk * l1.mean() + lj * l2.mean()
-            loss.backward()
+            if a.one_call:        # (the loss stays a device scalar; it is read once per epoch, below)
+                nll, reg, m1, m2, nfe = rn.fused_ffjord_loss_and_grad(ff, x, p, lam_r=float(lam) if a.regularize else 0.0,
+                                                                      kinetic=(lk, lj) if kin else None, exact=a.exact_train)
+                loss = nll + reg + lk * m1 + lj * m2
+            else:
+                logpx, l1, l2, nfe, sv = ff(x, p, exact=True) if a.exact_train else ff(x, p, regularize=kin)
+                loss = -logpx.mean() + (lam * sv.saveval.mean() if a.regularize else 0.0)
+                if kin:
+                    loss = loss + lk * l1.mean() + lj * l2.mean()
+                loss.backward()
             opt.step()
             _sync()
             dt = time.perf_counter() - t0

@@ -88,6 +88,9 @@ def main():
                     help="differentiate the step controller in the reverse pass (needs --engine tiled and --regularize 1)")
     ap.add_argument("--eval-groups", type=int, default=1, metavar="K",
                     help="train / test log-likelihood with K consecutive batches per launch (needs --engine tiled; 1: one solve per batch)")
+    ap.add_argument("--one-call", action="store_true",
+                    help="the training step through rnde_ffjord_nll_grad and rnde_adam_wd_step (fused_ffjord_loss_and_grad, "
+                         "FluxADAM(one_launch=True)) instead of the layer call, the torch loss, backward() and the composed optimiser")
     ap.add_argument("--out", default=None, help="default: profiles/ffjord_tabular.json (profiles/ffjord_tabular_kinetic.json with --kinetic, "
                                                 "profiles/ffjord_tabular_exact.json with --exact-eval, profiles/ffjord_tabular_track.json with "
                                                 "--track-ctrl)")
@@ -120,7 +123,7 @@ def main():
                           track_ctrl=a.track_ctrl)
     p = ff.p.clone().requires_grad_(True)
     ll = lambda data: rn.loglikelihood(ff, data, p.detach(), exact=a.exact_eval, groups=a.eval_groups)
-    opt = rn.FluxADAM([p], eta=1e-2, weight_decay=1e-5)
+    opt = rn.FluxADAM([p], eta=1e-2, weight_decay=1e-5, one_launch=a.one_call)
     lam0, lam1 = 5.0e3, 1.0e3
     k = np.log(lam0 / lam1) / a.epochs
     dummy = torch.from_numpy(tr.X[:a.batch]).to(dev)
@@ -146,11 +149,16 @@ def main():
             x = torch.from_numpy(xb).to(dev)
             _sync()
             t0 = time.perf_counter()
-            logpx, l1, l2, nfe, sv = ff(x, p, regularize=kin)
-            loss = -logpx.mean() + (lam * sv.saveval.mean() if a.regularize else 0.0)
-            if kin:
-                loss = loss + lk * l1.mean() + lj * l2.mean()
-            loss.backward()
+            if a.one_call:        # (the loss stays a device scalar; it is read once per epoch, below)
+                nll, reg, m1, m2, nfe = rn.fused_ffjord_loss_and_grad(ff, x, p, lam_r=float(lam) if a.regularize else 0.0,
+                                                                      kinetic=(lk, lj) if kin else None)
+                loss = nll + reg + lk * m1 + lj * m2
+            else:
+                logpx, l1, l2, nfe, sv = ff(x, p, regularize=kin)
+                loss = -logpx.mean() + (lam * sv.saveval.mean() if a.regularize else 0.0)
+                if kin:
+                    loss = loss + lk * l1.mean() + lj * l2.mean()
+                loss.backward()
             opt.step()
             _sync()
             dt = time.perf_counter() - t0
