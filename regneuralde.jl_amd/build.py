@@ -79,4 +79,7 @@ def build(force=False, verbose=False):
 
 if __name__ == "__main__":
     import sys
+    if "--print-units" in sys.argv:      # the translation units, for tools that link a variant (tools/build_variant.sh)
+        print(" ".join(s[:-4] for s in SOURCES))
+        sys.exit(0)
     print(build(force="--incremental" not in sys.argv, verbose=True))      # default: rebuild everything; --incremental: only what changed

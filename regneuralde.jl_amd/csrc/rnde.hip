@@ -884,12 +884,7 @@ static rnde_status forward_epilogue(rnde_node* h, const FwdCall& c, int64_t* nfe
     h->sv_index.assign(h->n_att, -1);
     h->n_saveval = gather_saved_values(h->h_meta, h->n_att, F_ACCEPT, h->cfg.regularize, h->cfg.cb_save_start != 0, h->sv_index.data(), saveval_host);
     if (n_saveval_out) *n_saveval_out = h->n_saveval;
-    switch (h->h_ctl->status) {
-        case 0: break;
-        case 2: h->err = "max_attempts reached"; return RNDE_ERR_MAX_ATTEMPTS;
-        case 3: h->err = "dt underflow"; return RNDE_ERR_DT_UNDERFLOW;
-        default: h->err = "non-finite error estimate or dt"; return RNDE_ERR_NONFINITE;
-    }
+    if (const SolveVerdict v = solve_verdict(h->h_ctl->status); v.st != RNDE_OK) { h->err = v.msg; return v.st; }
     h->have_tape = c.keep_tape != 0;
     return RNDE_OK;
 }
@@ -983,10 +978,7 @@ extern "C" rnde_status rnde_node_forward_everystep(rnde_node* h, const float* x_
 extern "C" rnde_status rnde_node_steps(rnde_node* h, float* steps_host, int32_t capacity, int32_t* n_out) {
     if (!h) return RNDE_ERR_BAD_ARG;
     const int n = std::min(capacity, h->n_att);
-    for (int i = 0; i < n; ++i) {
-        steps_host[4 * i + 0] = h->h_meta[i].t; steps_host[4 * i + 1] = h->h_meta[i].dt;
-        steps_host[4 * i + 2] = h->h_meta[i].eest; steps_host[4 * i + 3] = (h->h_meta[i].flags & F_ACCEPT) ? 1.f : 0.f;
-    }
+    export_step_log(h->h_meta, n, F_ACCEPT, steps_host);
     if (n_out) *n_out = h->n_att;
     return RNDE_OK;
 }

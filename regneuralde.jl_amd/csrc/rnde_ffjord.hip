@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rnde.h"
@@ -31,14 +32,12 @@ struct rnde_ffjord {
     int Bp = 0, T = 0, R = 0;
     size_t lds_bytes = 0;
     Event ev[4];                     // (ahead of the buffers: members go in reverse order, the buffers first)
-    // (every allocated member is an owner, rnde_alloc.h; initrec is the one view)
-    DevBuf<float> ws, tape, norm, e_buf, replay;
+    // (every allocated member is an owner, rnde_alloc.h)
+    // The solve's workspace (rnde_tile_host.h).  Engines 1 and 2: alloc'ed whole, with the tiles' meeting place; sw.scratch is the exact
+    // trace's matrix per tile of engine 1.  Engine 0 fills the members its one workgroup uses (ws, norm [512], ctl [3], meta, initrec_t [1], h_fin, Bp).
+    TileSolveWs sw;
+    DevBuf<float> tape, e_buf, replay;
     DevBuf<float> rws, pacc;
-    DevBuf<StepState> ctl;           // [3]: the two live states, then the final one
-    PinBuf<StepState> h_fin;         // pinned: the final state of the running solve (an asynchronous copy must not land in a dead stack frame)
-    DevBuf<StepMeta> meta;           // [max_attempts]
-    InitRec* initrec = nullptr;      // view: own_initrec (engine 0) or initrec_t
-    DevBuf<InitRec> own_initrec;
     DevBuf<FfStepRec> rec;           // [max_attempts]
     std::vector<StepMeta> h_meta;    // step log of the last solve (rnde_ffjord_steps / _timing)
     int n_att = 0, n_acc = 0, B = 0;
@@ -62,10 +61,6 @@ struct rnde_ffjord {
     int engine = 0;
     FtGeo TG{};
     int ntiles_max = 0;
-    DevBuf<float> qt;                // engine = 1: [ntiles][HP][HP], the exact trace's matrix per tile (the driver's scratch)
-    DevBuf<InitRec> initrec_t;       // [ntiles] (initrec = initrec_t)
-    DevBuf<StepState> ctl_t;         // [ntiles]
-    MeetRes meet;                    // the tiles' meeting place (rnde_meet.h)
     FcGeo CG{};                      // engine = 2: the Dense-chain dynamics on the tile layout (cfg holds the shared fields, in_dims = D)
     bool track_ctrl = false;         // rnde_ffjord_set_track_ctrl: taped forwards are reversed with the controller differentiated
     DevBuf<FfAttRec> att;            // [max_attempts]: the tracked sweep's attempt records (allocated when tracking is first switched on)
@@ -73,15 +68,11 @@ struct rnde_ffjord {
     // touches on the device is here; the handle's own workspace, tape and step log are not touched by it.
     struct Groups {
         int max_groups = 0, tiles = 0, max_columns = 0;
-        DevBuf<float> ws;                // [10][R][16 tiles]: the groups' columns side by side under the call's row stride
-        DevBuf<float> norm, qt;          // [tiles][8] + 512; [tiles][Dyn::scratch_floats] (the exact trace of engine 1)
-        DevBuf<StepState> ctl, fin, ctl_t;       // [max_groups][2] live states, [max_groups] final states, [tiles]
-        DevBuf<StepMeta> meta;           // [max_groups][max_attempts]
-        DevBuf<InitRec> initrec_t;       // [tiles]
+        // the groups' columns side by side under the call's row stride; a group's states, step log and meeting granules lie behind those
+        // of the groups in front
+        TileSolveWs sw;
         DevBuf<TileGroup> table;         // [max_groups]
-        PinBuf<StepState> h_fin;         // pinned: [max_groups]
         PinBuf<TileGroup> h_table;       // pinned: [max_groups]
-        MeetRes meet;                    // (max_attempts + 4) x 3 x tiles granules: a group's range lies behind those of the groups in front
         std::vector<std::vector<StepMeta>> log;      // the step logs of the last group call
     };
     std::unique_ptr<Groups> gr;
@@ -94,6 +85,14 @@ struct rnde_ffjord {
         hipError_t e_ = (x);                                                                        \
         if (e_ != hipSuccess) { (h)->err = std::string("HIP: ") + hipGetErrorString(e_); return RNDE_ERR_HIP; } \
     } while (0)
+
+// The dynamics of a handle of the tile layout: f(DynTag<Dyn>{}, geometry), Dyn = FcDyn with h->CG (engine 2) or FtDyn with h->TG (engine 1).
+template <class D> struct DynTag { using type = D; };
+template <class F>
+static auto with_dyn(rnde_ffjord* h, F&& f) { return h->engine == 2 ? f(DynTag<FcDyn>{}, h->CG) : f(DynTag<FtDyn>{}, h->TG); }
+// The KIN instantiation of a kernel: f(std::true_type{}) for the kinetic rows, f(std::false_type{}) without.
+template <class F>
+static void with_kin(bool kin, F&& f) { if (kin) f(std::true_type{}); else f(std::false_type{}); }
 
 // rnde_debug_elementwise's share of this translation unit (rnde_probe.h): the private softplus of rnde_ffjord.h
 struct EwFfjord {
@@ -150,30 +149,20 @@ static rnde_status tile_create(FfHold hold, const typename Dyn::Geo& G, rnde_ffj
     auto fail = [&](hipError_t e) { g_ff_create_err = std::string("HIP: ") + hipGetErrorString(e); return RNDE_ERR_HIP; };
     hipError_t e;
     const size_t RB = (size_t)R * h->Bp, MA = (size_t)c->max_attempts, NT = (size_t)h->ntiles_max;
-    if ((e = h->ws.alloc(10 * RB)) != hipSuccess) return fail(e);
+    if ((e = h->sw.alloc(R, h->ntiles_max, 1, c->max_attempts, Dyn::scratch_floats(G), kMwMeetMax, false)) != hipSuccess) return fail(e);
     if ((e = h->tape.alloc((MA + 1) * RB)) != hipSuccess) return fail(e);
-    if ((e = h->norm.alloc((8 * NT + 512))) != hipSuccess) return fail(e);
-    if ((e = hipMemset(h->norm, 0, (8 * NT + 512) * 4)) != hipSuccess) return fail(e);
     if ((e = h->e_buf.alloc((size_t)D * h->Bp)) != hipSuccess) return fail(e);
     if ((e = h->e_tape.alloc((size_t)D * h->Bp)) != hipSuccess) return fail(e);
     if ((e = h->replay.alloc(2 * MA)) != hipSuccess) return fail(e);
     if ((e = h->rws.alloc(NT * Dyn::rev_ws_floats(G))) != hipSuccess) return fail(e);
     if ((e = h->pacc.alloc(NT * G.P)) != hipSuccess) return fail(e);
-    if (Dyn::scratch_floats(G) && (e = h->qt.alloc(NT * Dyn::scratch_floats(G))) != hipSuccess) return fail(e);
-    if ((e = h->ctl.alloc(3)) != hipSuccess) return fail(e);
-    if ((e = h->ctl_t.alloc(NT)) != hipSuccess) return fail(e);
-    if ((e = h->meta.alloc(MA)) != hipSuccess) return fail(e);
-    if ((e = h->initrec_t.alloc(NT)) != hipSuccess) return fail(e);
-    h->initrec = h->initrec_t;
     if ((e = h->rec.alloc(MA)) != hipSuccess) return fail(e);
-    if ((e = h->meet.create(MA + 4, 3, kMwMeetMax)) != hipSuccess) return fail(e);
     for (const void* k : {(const void*)rnde_tile_solve_kernel<Dyn, false>, (const void*)rnde_tile_reverse_kernel<Dyn, false>,
                           (const void*)rnde_tile_feval_kernel<Dyn, false>, (const void*)rnde_tile_solve_kernel<Dyn, true>,
                           (const void*)rnde_tile_reverse_kernel<Dyn, true>, (const void*)rnde_tile_feval_kernel<Dyn, true>,
                           (const void*)rnde_tile_reverse_kernel<Dyn, false, true>})
         if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes)) != hipSuccess) return fail(e);
     for (auto& v : h->ev) if ((e = v.create()) != hipSuccess) return fail(e);
-    if ((e = h->h_fin.alloc(1)) != hipSuccess) return fail(e);
     *out = hold.release();
     return RNDE_OK;
 }
@@ -209,17 +198,6 @@ extern "C" rnde_status rnde_ffjord_create_tiled(const rnde_ffjord_config* c, rnd
 extern "C" int32_t rnde_ffjord_engine(const rnde_ffjord* h) { return h ? h->engine : -1; }
 
 // ---- the tracked-controller reverse sweep (engines 1 and 2, regularize = 1) ----
-// Its meeting needs every tile of the largest batch resident at once, on the tracked kernel's own footprint.
-template <class Dyn>
-static rnde_status trk_residency(rnde_ffjord* h) {
-    hipError_t e;
-    const std::string why = tile_residency_refusal({(const void*)rnde_tile_reverse_kernel<Dyn, false, true>}, kFtThreads, h->lds_bytes, h->ntiles_max,
-                                                   h->cfg.device, "TrackedFFJORD track_ctrl: ", "the reverse sweep's meeting", "the tracked sweep's footprint", &e);
-    FCHK(h, e);
-    if (!why.empty()) { h->err = why; return RNDE_ERR_BAD_ARG; }
-    return RNDE_OK;
-}
-
 extern "C" rnde_status rnde_ffjord_set_track_ctrl(rnde_ffjord* h, int32_t on) {
     if (!h) return RNDE_ERR_BAD_ARG;
     if (on != 0 && on != 1) { h->err = "TrackedFFJORD track_ctrl: the setting is 0 (step sizes and times are constants of the reverse sweep) or 1"; return RNDE_ERR_BAD_ARG; }
@@ -238,8 +216,14 @@ extern "C" rnde_status rnde_ffjord_set_track_ctrl(rnde_ffjord* h, int32_t on) {
                  "forward, change it before the forward";
         return RNDE_ERR_BAD_ARG;
     }
-    if (on && !h->att) {
-        if (rnde_status st = h->engine == 2 ? trk_residency<FcDyn>(h) : trk_residency<FtDyn>(h)) return st;
+    if (on && !h->att) {       // its meeting needs every tile of the largest batch resident at once, on the tracked kernel's own footprint
+        hipError_t e;
+        const std::string why = with_dyn(h, [&](auto dyn, const auto&) {
+            return tile_residency_refusal({(const void*)rnde_tile_reverse_kernel<typename decltype(dyn)::type, false, true>}, kFtThreads, h->lds_bytes, h->ntiles_max,
+                                          h->cfg.device, "TrackedFFJORD track_ctrl: ", "the reverse sweep's meeting", "the tracked sweep's footprint", &e);
+        });
+        FCHK(h, e);
+        if (!why.empty()) { h->err = why; return RNDE_ERR_BAD_ARG; }
         FCHK(h, h->att.alloc((size_t)h->cfg.max_attempts));
     }
     h->track_ctrl = on != 0;
@@ -322,10 +306,9 @@ extern "C" rnde_status rnde_ffjord_create(const rnde_ffjord_config* c, rnde_ffjo
     if (!c || !out) { g_ff_create_err = "null argument"; return RNDE_ERR_BAD_ARG; }
     *out = nullptr;
     if (const char* why = ff_refusal(c)) { g_ff_create_err = why; return RNDE_ERR_BAD_ARG; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= c->device) { g_ff_create_err = "no HIP device"; return RNDE_ERR_NO_DEVICE; }
-    if (hipSetDevice(c->device) != hipSuccess) { g_ff_create_err = "hipSetDevice failed"; return RNDE_ERR_NO_DEVICE; }
-    FfHold hold(new rnde_ffjord(), rnde_ffjord_destroy);
+    rnde_status st = RNDE_OK;
+    FfHold hold = ff_new_handle(c->device, &st);
+    if (!hold) return st;
     rnde_ffjord* h = hold.get();
     h->cfg = *c;
     h->G = ff_geo(c->in_dims, c->hidden);
@@ -341,24 +324,24 @@ extern "C" rnde_status rnde_ffjord_create(const rnde_ffjord_config* c, rnde_ffjo
     hipError_t e;
     if (!h->T) { g_ff_create_err = "TrackedFFJORD: parameters and per-column vectors do not fit in LDS"; return RNDE_ERR_BAD_ARG; }
     const size_t RB = (size_t)R * h->Bp, MA = (size_t)c->max_attempts;
-    if ((e = h->ws.alloc(10 * RB)) != hipSuccess) return fail(e);
+    h->sw.Bp = h->Bp;
+    if ((e = h->sw.ws.alloc(10 * RB)) != hipSuccess) return fail(e);
     if ((e = h->tape.alloc((MA + 1) * RB)) != hipSuccess) return fail(e);
-    if ((e = h->norm.alloc(512)) != hipSuccess) return fail(e);
-    if ((e = hipMemset(h->norm, 0, 512 * 4)) != hipSuccess) return fail(e);
+    if ((e = h->sw.norm.alloc(512)) != hipSuccess) return fail(e);
+    if ((e = hipMemset(h->sw.norm, 0, 512 * 4)) != hipSuccess) return fail(e);
     if ((e = h->e_buf.alloc((size_t)D * h->Bp)) != hipSuccess) return fail(e);
     if ((e = h->e_tape.alloc((size_t)D * h->Bp)) != hipSuccess) return fail(e);
     if ((e = h->replay.alloc(2 * MA)) != hipSuccess) return fail(e);
     if ((e = h->rws.alloc((size_t)(24 + kFfVjpVecs) * HR * h->Bp)) != hipSuccess) return fail(e);
     if ((e = h->pacc.alloc((size_t)h->G.P * h->Bp)) != hipSuccess) return fail(e);
-    if ((e = h->ctl.alloc(3)) != hipSuccess) return fail(e);
-    if ((e = h->meta.alloc(MA)) != hipSuccess) return fail(e);
-    if ((e = h->own_initrec.alloc(1)) != hipSuccess) return fail(e);
-    h->initrec = h->own_initrec;
+    if ((e = h->sw.ctl.alloc(3)) != hipSuccess) return fail(e);
+    if ((e = h->sw.meta.alloc(MA)) != hipSuccess) return fail(e);
+    if ((e = h->sw.initrec_t.alloc(1)) != hipSuccess) return fail(e);
     if ((e = h->rec.alloc(MA)) != hipSuccess) return fail(e);
     for (const void* k : {(const void*)rnde_ffjord_solve_kernel<false>, (const void*)rnde_ffjord_solve_kernel<true>})
         if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes)) != hipSuccess) return fail(e);
     for (auto& v : h->ev) if ((e = v.create()) != hipSuccess) return fail(e);
-    if ((e = h->h_fin.alloc(1)) != hipSuccess) return fail(e);
+    if ((e = h->sw.h_fin.alloc(1)) != hipSuccess) return fail(e);
     *out = hold.release();
     return RNDE_OK;
 }
@@ -386,169 +369,133 @@ static rnde_status ff_kinetic_ready(rnde_ffjord* h) {
     }
     if (h->kin_ready) return RNDE_OK;
     const size_t RBk = (size_t)Rk * h->Bp, RB = (size_t)h->R * h->Bp, MA = (size_t)h->cfg.max_attempts;
-    const size_t rws = h->engine == 2 ? (size_t)h->ntiles_max * FcDyn::rev_ws_floats(h->CG, true)
-                       : h->engine == 1 ? (size_t)h->ntiles_max * FtDyn::rev_ws_floats(h->TG, true)
-                                        : (size_t)(24 + kFfVjpVecsKin) * std::max(H, Rk) * h->Bp;
+    const size_t rws = h->engine == 0 ? (size_t)(24 + kFfVjpVecsKin) * std::max(H, Rk) * h->Bp
+                                      : with_dyn(h, [&](auto dyn, const auto& G) { return (size_t)h->ntiles_max * decltype(dyn)::type::rev_ws_floats(G, true); });
     FCHK(h, hipDeviceSynchronize());           // (rnde_ffjord_debug_feval does not wait for its launch)
-    DevBuf<float> ws, tape, rw;      // (the handle keeps what it has unless all three are there)
-    hipError_t e = ws.alloc(10 * RBk);
-    if (e == hipSuccess) e = tape.alloc((MA + 1) * RBk);
-    if (e == hipSuccess) e = rw.alloc(rws);
-    if (e == hipSuccess && h->tp.valid) e = hipMemcpy(tape, h->tape, ((size_t)h->tp.n_acc + 1) * RB * 4, hipMemcpyDeviceToDevice);
+    DevBuf<float> tape, rw;          // (the handle keeps what it has unless all three, the workspace in front, are there)
+    const hipError_t e = h->sw.grow_rows(Rk, [&] {
+        hipError_t e = tape.alloc((MA + 1) * RBk);
+        if (e == hipSuccess) e = rw.alloc(rws);
+        if (e == hipSuccess && h->tp.valid) e = hipMemcpy(tape, h->tape, ((size_t)h->tp.n_acc + 1) * RB * 4, hipMemcpyDeviceToDevice);
+        return e;
+    });
     if (e != hipSuccess) {
         h->err = std::string("TrackedFFJORD kinetic energy rows: HIP: ") + hipGetErrorString(e);
         return RNDE_ERR_HIP;
     }
-    h->ws.swap(ws); h->tape.swap(tape); h->rws.swap(rw);      // (the old three go with the locals)
+    h->tape.swap(tape); h->rws.swap(rw);      // (the old two go with the locals)
     h->kin_ready = true;
     return RNDE_OK;
 }
 
-// The tile driver's launches for the dynamics Dyn: the shared fields come from the one-workgroup engine's parameter structs, filled once.
-template <class Dyn>
-static void tile_launch_solve(rnde_ffjord* h, const typename Dyn::Geo& G, const FfSolveParams& Q, const Meet& meet, bool kin, bool exact,
-                              hipStream_t s) {
-    TileSolveParams<typename Dyn::Geo> T{};
-    T.F = Q.F; T.G = G; T.p = Q.p; T.x = Q.x; T.e = Q.e; T.ws = Q.ws; T.tape = Q.tape; T.logpx = Q.logpx; T.x_out = Q.x_out;
-    T.norm = Q.norm; T.initrec_t = h->initrec_t; T.ctl_t = h->ctl_t; T.exact = (Q.dir < 0 || exact) ? 1 : 0;
-    T.scratch = T.exact ? h->qt : nullptr;
-    T.meet = meet; T.xcc = h->meet.xcc; T.xcd_slot = h->meet.slot; T.dir = Q.dir; T.Bp = Q.Bp; T.ntiles = meet.n; T.tbase = Q.tbase; T.reg = Q.reg;
-    const dim3 grid(MeetRes::grid(meet));      // one XCD: every eighth block is a tile (the others return at once)
-    if (kin) hipLaunchKernelGGL((rnde_tile_solve_kernel<Dyn, true>), grid, dim3(kFtThreads), h->lds_bytes, s, T);
-    else hipLaunchKernelGGL((rnde_tile_solve_kernel<Dyn, false>), grid, dim3(kFtThreads), h->lds_bytes, s, T);
-}
+// One solve as its entry describes it: dir = +1 the forward (logpx; Hutchinson probe e, or exact: the exact trace and no probe), dir = -1
+// sampling (exact trace, tau = t1 - t).  kin: the kinetic forward (D + 3 rows, the two rows to reg_out; ff_kinetic_ready has run).
+// The leading members are what every rnde_ffjord_forward* entry takes (an aggregate); an entry then sets what is its own.
+struct FfCall {
+    const float *x, *p, *e; int32_t B; float t0, t1; uint64_t seed;
+    float *logpx, *x_out; int32_t keep_tape; hipStream_t s;
+    int dir = +1;
+    bool replay = false;                    // a *_replay entry: steps_host (n_steps pairs (dt, accepted)) is required
+    const float* steps_host = nullptr; int32_t n_steps = 0;
+    bool kin = false, exact = false;
+    float* reg_out = nullptr;
+    const FfLossSeed* ls = nullptr;         // rnde_ffjord_nll_grad: the loss-and-seed kernel behind the solve
+};
 
-// meet != NULL: the tracked sweep (Q.rec is unused; n_att attempt records in h->att), placed as the solve is.
-template <class Dyn>
-static void tile_launch_reverse(rnde_ffjord* h, const typename Dyn::Geo& G, const FfRevParams& Q, bool kin, bool exact, hipStream_t s,
-                                const Meet* meet = nullptr, int n_att = 0) {
-    TileRevParams<typename Dyn::Geo> T{};
-    T.G = G; T.p = Q.p; T.e = Q.e; T.tape = Q.tape; T.rec = Q.rec; T.out_bar = Q.logpx_bar; T.ws = Q.ws; T.pacc = Q.pacc;
-    T.x_bar = Q.x_bar; T.n_acc = Q.n_acc; T.B = Q.B; T.Bp = Q.Bp; T.reltol = Q.reltol; T.abstol = Q.abstol; T.reg_bar = Q.reg_bar;
-    T.exact = exact ? 1 : 0; T.scratch = exact ? h->qt : nullptr;
-    const int nt = (Q.B + 15) / 16;
-    if (meet) {
-        T.att = h->att; T.n_att = n_att; T.meet = *meet; T.xcc = h->meet.xcc; T.xcd_slot = h->meet.slot;
-        hipLaunchKernelGGL((rnde_tile_reverse_kernel<Dyn, false, true>), dim3(MeetRes::grid(*meet)), dim3(kFtThreads), h->lds_bytes, s, T);
-        return;
-    }
-    if (kin) hipLaunchKernelGGL((rnde_tile_reverse_kernel<Dyn, true>), dim3(nt), dim3(kFtThreads), h->lds_bytes, s, T);
-    else hipLaunchKernelGGL((rnde_tile_reverse_kernel<Dyn, false>), dim3(nt), dim3(kFtThreads), h->lds_bytes, s, T);
-}
-
-template <class Dyn>
-static void tile_launch_feval(rnde_ffjord* h, const typename Dyn::Geo& G, const float* p_dev, const float* x_dev, const float* e_dev, int B, float t,
-                              int exact, bool kin, float* out_dev, hipStream_t s) {
-    const dim3 grid((B + 15) / 16);
-    if (kin) hipLaunchKernelGGL((rnde_tile_feval_kernel<Dyn, true>), grid, dim3(kFtThreads), h->lds_bytes, s, G, p_dev, x_dev, e_dev, t, B, exact,
-                                h->rws, h->qt, out_dev);
-    else hipLaunchKernelGGL((rnde_tile_feval_kernel<Dyn, false>), grid, dim3(kFtThreads), h->lds_bytes, s, G, p_dev, x_dev, e_dev, t, B, exact,
-                            h->rws, h->qt, out_dev);
-}
-
-// One solve: dir = +1 the forward (logpx; Hutchinson probe e, or exact: the exact trace and no probe), dir = -1 sampling (exact trace,
-// tau = t1 - t).  reg_out_dev != NULL: the kinetic forward (D + 3 rows; ff_kinetic_ready has run).
-static rnde_status ff_solve(rnde_ffjord* h, int dir, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0, float t1,
-                            uint64_t seed, const float* steps_host, int32_t n_steps, float* logpx_dev, float* x_out_dev, int32_t keep_tape,
-                            hipStream_t s, float* reg_out_dev = nullptr, bool exact = false, const FfLossSeed* ls = nullptr) {
-    const bool kin = reg_out_dev != nullptr;
-    if (!x_dev || !p_dev || B < 1 || B > h->cfg.max_batch) { h->err = "bad argument (B must be 1..max_batch)"; return RNDE_ERR_BAD_ARG; }
-    if (!(t1 > t0)) { h->err = "TrackedFFJORD: tspan must satisfy t1 > t0 (sample() integrates t1 -> t0 itself)"; return RNDE_ERR_BAD_ARG; }
-    if (steps_host && (n_steps < 1 || n_steps > h->cfg.max_attempts)) { h->err = "replay: n_steps must be 1..max_attempts"; return RNDE_ERR_BAD_ARG; }
-    const bool taped = dir > 0 && keep_tape;
+static rnde_status ff_solve(rnde_ffjord* h, const FfCall& c) {
+    const int dir = c.dir, B = c.B;
+    const bool kin = c.kin, exact = c.exact;
+    hipStream_t s = c.s;
+    if (!c.x || !c.p || B < 1 || B > h->cfg.max_batch) { h->err = "bad argument (B must be 1..max_batch)"; return RNDE_ERR_BAD_ARG; }
+    if (!(c.t1 > c.t0)) { h->err = "TrackedFFJORD: tspan must satisfy t1 > t0 (sample() integrates t1 -> t0 itself)"; return RNDE_ERR_BAD_ARG; }
+    if (c.steps_host && (c.n_steps < 1 || c.n_steps > h->cfg.max_attempts)) { h->err = "replay: n_steps must be 1..max_attempts"; return RNDE_ERR_BAD_ARG; }
+    const bool taped = dir > 0 && c.keep_tape;
     if (taped) h->tp.valid = false;            // (only a taped forward replaces the tape)
-    const int D = h->G.D;
+    const float* e_dev = c.e;
     if (dir > 0 && !exact && !e_dev) {   // the library's normal stream, drawn once per call (the reference's default argument)
         float* eb = taped ? h->e_tape : h->e_buf;
-        rnde_status st = rnde_normal_fill(eb, (int64_t)D * B, seed, 0x46464A4FULL, s);
+        rnde_status st = rnde_normal_fill(eb, (int64_t)h->G.D * B, c.seed, 0x46464A4FULL, s);
         if (st != RNDE_OK) { h->err = "rnde_normal_fill failed"; return st; }
         e_dev = eb;
     }
-    if (steps_host) FCHK(h, hipMemcpyAsync(h->replay, steps_host, (size_t)2 * n_steps * 4, hipMemcpyHostToDevice, s));
-    FfSolveParams Q{};
-    StepParams& P = Q.F;
-    P.x = x_dev; P.D = kin ? h->G.D + 3 : h->R; P.B = B; P.Bn = B; P.Bpad = h->Bp; P.nwg = 1;
-    P.ctl = h->ctl; P.ctl_final = h->ctl + 2; P.meta = h->meta; P.initrec = h->initrec; P.initpart = h->norm;
-    P.reltol = h->cfg.reltol; P.abstol = h->cfg.abstol;
-    P.t0 = dir > 0 ? t0 : 0.f; P.t1 = dir > 0 ? t1 : t1 - t0;
-    P.tape = 1; P.max_attempts = h->cfg.max_attempts; P.reg_kind = 0; P.nsave = 0;
-    P.replay = steps_host ? h->replay : nullptr; P.n_replay = steps_host ? n_steps : 0;
-    P.beta1 = kBeta1; P.beta2 = kBeta2; P.rk_order = 5.f;
-    Q.G = h->G; Q.p = p_dev; Q.x = x_dev; Q.e = (dir > 0 && !exact) ? e_dev : nullptr; Q.ws = h->ws;
-    Q.tape = taped ? h->tape : nullptr; Q.logpx = dir > 0 ? logpx_dev : nullptr; Q.x_out = x_out_dev; Q.norm = h->norm;
-    Q.dir = dir; Q.T = h->T; Q.Bp = h->Bp; Q.tbase = t1; Q.reg = reg_out_dev;
-    const int nt = (B + 15) / 16;
+    if (c.steps_host) FCHK(h, hipMemcpyAsync(h->replay, c.steps_host, (size_t)2 * c.n_steps * 4, hipMemcpyHostToDevice, s));
+    const TileSolveWs& W = h->sw;
+    const StepParams F = tile_step_params(W, c.x, kin ? h->G.D + 3 : h->R, B, h->cfg.reltol, h->cfg.abstol, dir > 0 ? c.t0 : 0.f, dir > 0 ? c.t1 : c.t1 - c.t0,
+                                          h->cfg.max_attempts, c.steps_host ? (const float*)h->replay : nullptr, c.n_steps);
+    const float* e_solve = (dir > 0 && !exact) ? e_dev : nullptr;
+    float *tape = taped ? (float*)h->tape : nullptr, *logpx = dir > 0 ? c.logpx : nullptr;
     const bool tiles = h->engine >= 1;     // engines 1 and 2 share the tile layout, the meeting and its checks
-    Meet meet{};
-    if (tiles) {               // every tile resident, one meeting per attempt (one XCD up to 32 tiles, agent scope above)
-        meet = h->meet.begin(nt, true, s);
-        FCHK(h, h->meet.err);
+    auto launch = [&](const Meet& meet) {
+        if (!tiles) {
+            FfSolveParams Q{};
+            Q.F = F; Q.G = h->G; Q.p = c.p; Q.x = c.x; Q.e = e_solve; Q.ws = W.ws; Q.tape = tape; Q.logpx = logpx; Q.x_out = c.x_out; Q.norm = W.norm;
+            Q.dir = dir; Q.T = h->T; Q.Bp = h->Bp; Q.tbase = c.t1; Q.reg = c.reg_out;
+            with_kin(kin, [&](auto K) { hipLaunchKernelGGL(rnde_ffjord_solve_kernel<decltype(K)::value>, dim3(1), dim3(h->T), h->lds_bytes, s, Q); });
+        } else with_dyn(h, [&](auto dyn, const auto& G) {
+            using Dyn = typename decltype(dyn)::type;
+            TileSolveParams<typename Dyn::Geo> T{};
+            T.F = F; T.G = G; T.p = c.p; T.x = c.x; T.e = e_solve; T.tape = tape; T.logpx = logpx; T.x_out = c.x_out;
+            tile_bind_ws(T, W);
+            tile_bind_meet(T, h->sw.meet, meet);
+            T.exact = (dir < 0 || exact) ? 1 : 0; T.scratch = T.exact ? (float*)W.scratch : nullptr;
+            T.dir = dir; T.ntiles = meet.n; T.tbase = c.t1; T.reg = c.reg_out;
+            const dim3 grid(MeetRes::grid(meet));      // one XCD: every eighth block is a tile (the others return at once)
+            with_kin(kin, [&](auto K) { hipLaunchKernelGGL((rnde_tile_solve_kernel<Dyn, decltype(K)::value>), grid, dim3(kFtThreads), h->lds_bytes, s, T); });
+        });
+        return hipGetLastError();
+    };
+    auto behind = [&] {        // rnde_ffjord_nll_grad: the loss terms and the sweep's seeds, behind the solve and in front of the host wait
+        if (c.ls) {
+            ff_launch_loss_seed(*c.ls, kin, s);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+        return hipMemcpyAsync(W.h_fin, W.fin(), sizeof(StepState), hipMemcpyDeviceToHost, s);
+    };
+    const StepState& fin = *h->sw.h_fin;
+    std::string why;
+    if (tiles) {       // every tile resident, one meeting per attempt (one XCD up to 32 tiles, agent scope above)
+        FCHK(h, tile_run_met(h->sw.meet, (B + 15) / 16, true, h->ev[0], h->ev[1], s, launch, behind, "TrackedFFJORD tiled engine: ", "the solve", "the solve was abandoned", &why));
+    } else {           // the one workgroup meets nobody: the same order without the meeting's steps
+        FCHK(h, tile_run_timed(h->ev[0], h->ev[1], s, [&] { return launch(Meet{}); }));
+        FCHK(h, behind());
+        FCHK(h, hipStreamSynchronize(s));
     }
-    FCHK(h, hipEventRecord(h->ev[0], s));
-    if (h->engine == 2) tile_launch_solve<FcDyn>(h, h->CG, Q, meet, kin, exact, s);
-    else if (h->engine == 1) tile_launch_solve<FtDyn>(h, h->TG, Q, meet, kin, exact, s);
-    else if (kin) hipLaunchKernelGGL(rnde_ffjord_solve_kernel<true>, dim3(1), dim3(h->T), h->lds_bytes, s, Q);
-    else hipLaunchKernelGGL(rnde_ffjord_solve_kernel<false>, dim3(1), dim3(h->T), h->lds_bytes, s, Q);
-    FCHK(h, hipGetLastError());
-    FCHK(h, hipEventRecord(h->ev[1], s));
-    if (ls) {                  // rnde_ffjord_nll_grad: the loss terms and the sweep's seeds, behind the solve and in front of the host wait
-        ff_launch_loss_seed(*ls, kin, s);
-        FCHK(h, hipGetLastError());
-    }
-    const StepState& fin = *h->h_fin;
-    FCHK(h, hipMemcpyAsync(h->h_fin, h->ctl + 2, sizeof(StepState), hipMemcpyDeviceToHost, s));
-    if (tiles) FCHK(h, h->meet.queue_check(meet, s));
-    FCHK(h, hipStreamSynchronize(s));
     (void)hipEventElapsedTime(&h->fwd_ms, h->ev[0], h->ev[1]);
-    if (tiles) {
-        hipError_t me;
-        const std::string why = tile_meet_refusal(h->meet, meet, nt, s, "TrackedFFJORD tiled engine: ", "the solve", "the solve was abandoned", &me);
-        FCHK(h, me);
-        if (!why.empty()) { h->n_att = h->n_acc = 0; h->h_meta.clear(); h->err = why; return RNDE_ERR_HIP; }
-    }
+    if (!why.empty()) { h->n_att = h->n_acc = 0; h->h_meta.clear(); h->err = why; return RNDE_ERR_HIP; }
     h->n_att = fin.n_att; h->n_acc = fin.n_acc; h->B = B;
     h->h_meta.resize(fin.n_att);
-    if (fin.n_att) FCHK(h, hipMemcpy(h->h_meta.data(), h->meta, (size_t)fin.n_att * sizeof(StepMeta), hipMemcpyDeviceToHost));
-    switch (fin.status) {
-        case 0: break;
-        case 2: h->err = "max_attempts reached"; return RNDE_ERR_MAX_ATTEMPTS;
-        case 3: h->err = "dt underflow"; return RNDE_ERR_DT_UNDERFLOW;
-        default: h->err = "non-finite error estimate or dt"; return RNDE_ERR_NONFINITE;
-    }
+    FCHK(h, tile_fetch_log(W.meta, fin.n_att, h->h_meta.data()));
+    if (const SolveVerdict v = solve_verdict(fin.status); v.st != RNDE_OK) { h->err = v.msg; return v.st; }
     if (taped) {
         rnde_ffjord::Tape& T = h->tp;
         T.meta = h->h_meta; T.n_att = h->n_att; T.n_acc = h->n_acc; T.B = B;
-        T.reltol = P.reltol; T.abstol = P.abstol; T.e = exact ? nullptr : e_dev; T.p = p_dev; T.kin = kin; T.exact = exact; T.trk = h->track_ctrl; T.valid = true;
+        T.reltol = F.reltol; T.abstol = F.abstol; T.e = exact ? nullptr : e_dev; T.p = c.p; T.kin = kin; T.exact = exact; T.trk = h->track_ctrl; T.valid = true;
     }
     return RNDE_OK;
 }
 
-static rnde_status ff_forward(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0, float t1, uint64_t seed,
-                              const float* steps_host, int32_t n_steps, float* logpx_dev, float* z_out_dev, int64_t* nfe_out, float* saveval_host,
-                              int32_t* n_saveval_out, int32_t keep_tape, void* stream, bool kin = false, float* reg_out_dev = nullptr,
-                              bool exact = false, const FfLossSeed* ls = nullptr) {
+// A forward solve (c.dir = +1) behind its entry's checks, then what the entry hands back: nfe and the saved values.
+static rnde_status ff_forward(rnde_ffjord* h, const FfCall& c, int64_t* nfe_out, float* saveval_host, int32_t* n_saveval_out) {
     if (!h) return RNDE_ERR_BAD_ARG;
+    const bool exact = c.exact, kin = c.kin;
+    if (c.replay && !c.steps_host) { h->err = "replay: steps_host is required"; return RNDE_ERR_BAD_ARG; }
     if (exact && h->engine == 0) {
         h->err = "TrackedFFJORD exact trace: the one-workgroup engine does not serve the exact forward; create the handle with "
                  "rnde_ffjord_create_tiled (engine = \"tiled\") or rnde_ffjord_create_chain";
         return RNDE_ERR_BAD_ARG;
     }
     if (exact && kin) { h->err = "TrackedFFJORD exact trace: the kinetic energy rows are not served with it (the Jacobian norm row is defined on the probe)"; return RNDE_ERR_BAD_ARG; }
-    if (!logpx_dev) { h->err = "logpx_dev is required"; return RNDE_ERR_BAD_ARG; }
+    if (!c.logpx) { h->err = "logpx_dev is required"; return RNDE_ERR_BAD_ARG; }
     if (kin) {
-        if (!reg_out_dev) { h->err = "reg_out_dev (2 x B: the kinetic energy row, then the Jacobian norm row) is required"; return RNDE_ERR_BAD_ARG; }
+        if (!c.reg_out) { h->err = "reg_out_dev (2 x B: the kinetic energy row, then the Jacobian norm row) is required"; return RNDE_ERR_BAD_ARG; }
         if (rnde_status kst = ff_kinetic_ready(h)) return kst;
     }
-    rnde_status st = ff_solve(h, +1, x_dev, p_dev, e_dev, B, t0, t1, seed, steps_host, n_steps, logpx_dev, z_out_dev, keep_tape, (hipStream_t)stream,
-                              kin ? reg_out_dev : nullptr, exact, ls);
+    rnde_status st = ff_solve(h, c);
     if (st != RNDE_OK) return st;
     if (nfe_out) *nfe_out = 3 + 6 * (int64_t)h->n_att;      // 2 (initial dt) + 1 (fsalfirst) + 6 per attempt, as rnde_node_forward
-    int nsv = 0;
-    if (h->cfg.regularize) {       // SavingCallback(EEst * dt) (ffjord.jl:116): 0 at init when it fires there, then one per accepted step
-        if (h->cfg.cb_save_start) { if (saveval_host) saveval_host[nsv] = 0.f; ++nsv; }
-        for (int i = 0; i < h->n_att; ++i)
-            if (h->h_meta[i].flags & F_ACCEPT) { if (saveval_host) saveval_host[nsv] = h->h_meta[i].eest * h->h_meta[i].dt; ++nsv; }
-    }
+    // SavingCallback(EEst * dt) (ffjord.jl:116): 0 at init when it fires there, then one per accepted step
+    const int nsv = gather_saved_values(h->h_meta.data(), h->n_att, F_ACCEPT, h->cfg.regularize ? RNDE_REG_ERR : RNDE_REG_NONE, h->cfg.cb_save_start != 0, nullptr, saveval_host);
     if (n_saveval_out) *n_saveval_out = nsv;
     return RNDE_OK;
 }
@@ -556,68 +503,68 @@ static rnde_status ff_forward(rnde_ffjord* h, const float* x_dev, const float* p
 extern "C" rnde_status rnde_ffjord_forward(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0, float t1,
                                            uint64_t seed, float* logpx_dev, float* z_out_dev, int64_t* nfe_out, float* saveval_host,
                                            int32_t* n_saveval_out, int32_t keep_tape, void* stream) {
-    return ff_forward(h, x_dev, p_dev, e_dev, B, t0, t1, seed, nullptr, 0, logpx_dev, z_out_dev, nfe_out, saveval_host, n_saveval_out, keep_tape, stream);
+    return ff_forward(h, FfCall{x_dev, p_dev, e_dev, B, t0, t1, seed, logpx_dev, z_out_dev, keep_tape, (hipStream_t)stream}, nfe_out, saveval_host, n_saveval_out);
 }
 
 extern "C" rnde_status rnde_ffjord_forward_replay(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0,
                                                   float t1, uint64_t seed, const float* steps_host, int32_t n_steps, float* logpx_dev, float* z_out_dev,
                                                   int64_t* nfe_out, float* saveval_host, int32_t* n_saveval_out, int32_t keep_tape, void* stream) {
-    if (!steps_host) { if (h) h->err = "replay: steps_host is required"; return RNDE_ERR_BAD_ARG; }
-    return ff_forward(h, x_dev, p_dev, e_dev, B, t0, t1, seed, steps_host, n_steps, logpx_dev, z_out_dev, nfe_out, saveval_host, n_saveval_out, keep_tape, stream);
+    FfCall c{x_dev, p_dev, e_dev, B, t0, t1, seed, logpx_dev, z_out_dev, keep_tape, (hipStream_t)stream};
+    c.replay = true; c.steps_host = steps_host; c.n_steps = n_steps;
+    return ff_forward(h, c, nfe_out, saveval_host, n_saveval_out);
 }
 
 extern "C" rnde_status rnde_ffjord_forward_kinetic(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t0,
                                                    float t1, uint64_t seed, float* logpx_dev, float* reg_out_dev, float* z_out_dev, int64_t* nfe_out,
                                                    int32_t keep_tape, void* stream) {
-    return ff_forward(h, x_dev, p_dev, e_dev, B, t0, t1, seed, nullptr, 0, logpx_dev, z_out_dev, nfe_out, nullptr, nullptr, keep_tape, stream, true,
-                      reg_out_dev);
+    FfCall c{x_dev, p_dev, e_dev, B, t0, t1, seed, logpx_dev, z_out_dev, keep_tape, (hipStream_t)stream};
+    c.kin = true; c.reg_out = reg_out_dev;
+    return ff_forward(h, c, nfe_out, nullptr, nullptr);
 }
 
 extern "C" rnde_status rnde_ffjord_forward_kinetic_replay(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B,
                                                           float t0, float t1, uint64_t seed, const float* steps_host, int32_t n_steps,
                                                           float* logpx_dev, float* reg_out_dev, float* z_out_dev, int64_t* nfe_out,
                                                           int32_t keep_tape, void* stream) {
-    if (!steps_host) { if (h) h->err = "replay: steps_host is required"; return RNDE_ERR_BAD_ARG; }
-    return ff_forward(h, x_dev, p_dev, e_dev, B, t0, t1, seed, steps_host, n_steps, logpx_dev, z_out_dev, nfe_out, nullptr, nullptr, keep_tape, stream,
-                      true, reg_out_dev);
+    FfCall c{x_dev, p_dev, e_dev, B, t0, t1, seed, logpx_dev, z_out_dev, keep_tape, (hipStream_t)stream};
+    c.replay = true; c.steps_host = steps_host; c.n_steps = n_steps; c.kin = true; c.reg_out = reg_out_dev;
+    return ff_forward(h, c, nfe_out, nullptr, nullptr);
 }
 
 extern "C" rnde_status rnde_ffjord_forward_exact(rnde_ffjord* h, const float* x_dev, const float* p_dev, int32_t B, float t0, float t1, float* logpx_dev,
                                                  float* z_out_dev, int64_t* nfe_out, float* saveval_host, int32_t* n_saveval_out, int32_t keep_tape,
                                                  void* stream) {
-    return ff_forward(h, x_dev, p_dev, nullptr, B, t0, t1, 0, nullptr, 0, logpx_dev, z_out_dev, nfe_out, saveval_host, n_saveval_out, keep_tape, stream,
-                      false, nullptr, true);
+    FfCall c{x_dev, p_dev, nullptr, B, t0, t1, 0, logpx_dev, z_out_dev, keep_tape, (hipStream_t)stream};
+    c.exact = true;
+    return ff_forward(h, c, nfe_out, saveval_host, n_saveval_out);
 }
 
 extern "C" rnde_status rnde_ffjord_forward_exact_replay(rnde_ffjord* h, const float* x_dev, const float* p_dev, int32_t B, float t0, float t1,
                                                         const float* steps_host, int32_t n_steps, float* logpx_dev, float* z_out_dev, int64_t* nfe_out,
                                                         float* saveval_host, int32_t* n_saveval_out, int32_t keep_tape, void* stream) {
-    if (!steps_host) { if (h) h->err = "replay: steps_host is required"; return RNDE_ERR_BAD_ARG; }
-    return ff_forward(h, x_dev, p_dev, nullptr, B, t0, t1, 0, steps_host, n_steps, logpx_dev, z_out_dev, nfe_out, saveval_host, n_saveval_out, keep_tape,
-                      stream, false, nullptr, true);
+    FfCall c{x_dev, p_dev, nullptr, B, t0, t1, 0, logpx_dev, z_out_dev, keep_tape, (hipStream_t)stream};
+    c.replay = true; c.steps_host = steps_host; c.n_steps = n_steps; c.exact = true;
+    return ff_forward(h, c, nfe_out, saveval_host, n_saveval_out);
+}
+
+// The attempt count of a step log and, into out_host (may be NULL), its export: (t, dt, EEst, accepted) when wide, (dt, accepted) otherwise.
+static rnde_status ff_export(rnde_ffjord* h, const char* entry, const StepMeta* log, int n_att, bool wide, float* out_host, int32_t capacity, int32_t* n_attempts_out) {
+    *n_attempts_out = n_att;
+    if (!out_host) return RNDE_OK;
+    if (capacity < n_att) { h->err = std::string(entry) + ": capacity below the attempt count"; return RNDE_ERR_BAD_ARG; }
+    if (wide) export_step_log(log, n_att, F_ACCEPT, out_host);
+    else export_steps(log, n_att, F_ACCEPT, out_host);
+    return RNDE_OK;
 }
 
 extern "C" rnde_status rnde_ffjord_step_log(rnde_ffjord* h, float* log_host, int32_t capacity, int32_t* n_attempts_out) {
     if (!h || !n_attempts_out) return RNDE_ERR_BAD_ARG;
-    *n_attempts_out = h->n_att;
-    if (log_host) {
-        if (capacity < h->n_att) { h->err = "step_log: capacity below the attempt count"; return RNDE_ERR_BAD_ARG; }
-        for (int i = 0; i < h->n_att; ++i) {
-            const StepMeta& m = h->h_meta[i];
-            log_host[4 * i] = m.t; log_host[4 * i + 1] = m.dt; log_host[4 * i + 2] = m.eest; log_host[4 * i + 3] = (m.flags & F_ACCEPT) ? 1.f : 0.f;
-        }
-    }
-    return RNDE_OK;
+    return ff_export(h, "step_log", h->h_meta.data(), h->n_att, true, log_host, capacity, n_attempts_out);
 }
 
 extern "C" rnde_status rnde_ffjord_steps(rnde_ffjord* h, float* steps_host, int32_t capacity, int32_t* n_attempts_out) {
     if (!h || !n_attempts_out) return RNDE_ERR_BAD_ARG;
-    *n_attempts_out = h->n_att;
-    if (steps_host) {
-        if (capacity < h->n_att) { h->err = "steps: capacity below the attempt count"; return RNDE_ERR_BAD_ARG; }
-        for (int i = 0; i < h->n_att; ++i) { steps_host[2 * i] = h->h_meta[i].dt; steps_host[2 * i + 1] = (h->h_meta[i].flags & F_ACCEPT) ? 1.f : 0.f; }
-    }
-    return RNDE_OK;
+    return ff_export(h, "steps", h->h_meta.data(), h->n_att, false, steps_host, capacity, n_attempts_out);
 }
 
 // The reverse sweep of the taped forward; a kinetic tape runs the KIN = true kernels with reg_bar_dev (NULL: zeros), an exact tape the
@@ -635,43 +582,48 @@ static rnde_status ff_backward(rnde_ffjord* h, const float* logpx_bar_dev, const
     if (!rec.empty()) FCHK(h, hipMemcpyAsync(h->rec, rec.data(), rec.size() * sizeof(FfStepRec), hipMemcpyHostToDevice, s));
     const bool trk = T.trk && h->engine >= 1 && !T.kin;
     std::vector<FfAttRec> att;
-    Meet meet{};
     const int nt = (T.B + 15) / 16;
     if (trk) {
         tile_att_recs(T.meta.data(), T.n_att, rec, att);
         if (!att.empty()) FCHK(h, hipMemcpyAsync(h->att, att.data(), att.size() * sizeof(FfAttRec), hipMemcpyHostToDevice, s));
-        meet = h->meet.begin(nt, true, s);
-        FCHK(h, h->meet.err);
     }
-    FfRevParams Q{};
-    Q.G = h->G; Q.p = T.p; Q.e = T.e; Q.tape = h->tape; Q.rec = h->rec; Q.logpx_bar = logpx_bar_dev;
-    Q.ws = h->rws; Q.pacc = h->pacc; Q.x_bar = x_bar_dev; Q.n_acc = T.n_acc; Q.B = T.B; Q.Bp = h->Bp; Q.reltol = T.reltol; Q.abstol = T.abstol;
-    Q.reg_bar = reg_bar_dev;
-    FCHK(h, hipEventRecord(h->ev[2], s));
-    if (h->engine >= 1) {
-        if (h->engine == 2) tile_launch_reverse<FcDyn>(h, h->CG, Q, T.kin, T.exact, s, trk ? &meet : nullptr, (int)att.size());
-        else tile_launch_reverse<FtDyn>(h, h->TG, Q, T.kin, T.exact, s, trk ? &meet : nullptr, (int)att.size());
-        FCHK(h, hipGetLastError());
-        hipLaunchKernelGGL(rnde_tile_reduce_kernel, dim3((h->G.P + 255) / 256), dim3(256), 0, s, (const float*)h->pacc, h->G.P, (T.B + 15) / 16, p_bar_dev);
-    } else {
-        if (T.kin) hipLaunchKernelGGL(rnde_ffjord_reverse_kernel<true>, dim3((T.B + 255) / 256), dim3(256), 0, s, Q);
-        else hipLaunchKernelGGL(rnde_ffjord_reverse_kernel<false>, dim3((T.B + 255) / 256), dim3(256), 0, s, Q);
-        FCHK(h, hipGetLastError());
-        hipLaunchKernelGGL(rnde_ffjord_reduce_kernel, dim3((h->G.P + 255) / 256), dim3(256), 0, s, (const float*)h->pacc, h->G.P, T.B, h->Bp, p_bar_dev);
-    }
-    FCHK(h, hipGetLastError());
-    FCHK(h, hipEventRecord(h->ev[3], s));
-    if (trk) FCHK(h, h->meet.queue_check(meet, s));
+    // The sweep and the sum of its partial p-bars.  meet != NULL: the tracked sweep (the step records are unused; the attempt records
+    // are in h->att), placed as the solve is.
+    auto sweep = [&](const Meet* meet) {
+        auto fill = [&](auto& Q) {       // (what FfRevParams and TileRevParams share; the cotangent of logpx is set beside it)
+            Q.p = T.p; Q.e = T.e; Q.tape = h->tape; Q.rec = h->rec; Q.ws = h->rws; Q.pacc = h->pacc; Q.x_bar = x_bar_dev; Q.n_acc = T.n_acc; Q.B = T.B;
+            Q.Bp = h->Bp; Q.reltol = T.reltol; Q.abstol = T.abstol; Q.reg_bar = reg_bar_dev;
+        };
+        if (h->engine == 0) {
+            FfRevParams Q{};
+            fill(Q);
+            Q.G = h->G; Q.logpx_bar = logpx_bar_dev;
+            with_kin(T.kin, [&](auto K) { hipLaunchKernelGGL(rnde_ffjord_reverse_kernel<decltype(K)::value>, dim3((T.B + 255) / 256), dim3(256), 0, s, Q); });
+        } else with_dyn(h, [&](auto dyn, const auto& G) {
+            using Dyn = typename decltype(dyn)::type;
+            TileRevParams<typename Dyn::Geo> Q{};
+            fill(Q);
+            Q.G = G; Q.out_bar = logpx_bar_dev; Q.exact = T.exact ? 1 : 0; Q.scratch = T.exact ? (float*)h->sw.scratch : nullptr;
+            if (meet) {
+                Q.att = h->att; Q.n_att = (int)att.size();
+                tile_bind_meet(Q, h->sw.meet, *meet);
+                hipLaunchKernelGGL((rnde_tile_reverse_kernel<Dyn, false, true>), dim3(MeetRes::grid(*meet)), dim3(kFtThreads), h->lds_bytes, s, Q);
+            } else
+                with_kin(T.kin, [&](auto K) { hipLaunchKernelGGL((rnde_tile_reverse_kernel<Dyn, decltype(K)::value>), dim3(nt), dim3(kFtThreads), h->lds_bytes, s, Q); });
+        });
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        if (h->engine == 0) hipLaunchKernelGGL(rnde_ffjord_reduce_kernel, dim3((h->G.P + 255) / 256), dim3(256), 0, s, (const float*)h->pacc, h->G.P, T.B, h->Bp, p_bar_dev);
+        else hipLaunchKernelGGL(rnde_tile_reduce_kernel, dim3((h->G.P + 255) / 256), dim3(256), 0, s, (const float*)h->pacc, h->G.P, nt, p_bar_dev);
+        return hipGetLastError();
+    };
+    std::string why;
+    FCHK(h, trk ? tile_run_met(h->sw.meet, nt, true, h->ev[2], h->ev[3], s, [&](const Meet& meet) { return sweep(&meet); }, [] { return hipSuccess; },
+                               "TrackedFFJORD track_ctrl: ", "the tracked reverse sweep", "the sweep was abandoned, p_bar and x_bar are not valid", &why)
+                : tile_run_timed(h->ev[2], h->ev[3], s, [&] { return sweep(nullptr); }));      // (the tiles of the constant-step sweep do not meet)
     FCHK(h, hipEventSynchronize(h->ev[3]));
     (void)hipEventElapsedTime(&h->rev_ms, h->ev[2], h->ev[3]);
-    if (trk) {
-        FCHK(h, hipStreamSynchronize(s));
-        hipError_t me;
-        const std::string why = tile_meet_refusal(h->meet, meet, nt, s, "TrackedFFJORD track_ctrl: ", "the tracked reverse sweep",
-                                                  "the sweep was abandoned, p_bar and x_bar are not valid", &me);
-        FCHK(h, me);
-        if (!why.empty()) { h->err = why; return RNDE_ERR_HIP; }
-    }
+    if (!why.empty()) { h->err = why; return RNDE_ERR_HIP; }
     return RNDE_OK;
 }
 
@@ -729,8 +681,9 @@ extern "C" rnde_status rnde_ffjord_nll_grad(rnde_ffjord* h, const float* x_dev, 
     ls.reg_bar = kin ? (float*)h->f_reg_bar : nullptr; ls.B = B; ls.lambda_k = lambda_k; ls.lambda_j = lambda_j;
     std::vector<float> sv((size_t)h->cfg.max_attempts + 1), sv_bar;
     int32_t nsv = 0;
-    rnde_status st = ff_forward(h, x_dev, p_dev, mode == 1 ? nullptr : e_dev, B, t0, t1, seed, nullptr, 0, logpx, nullptr, nfe_out, sv.data(), &nsv, 1, stream,
-                                kin, kin ? (float*)h->f_reg : nullptr, mode == 1, &ls);
+    FfCall c{x_dev, p_dev, mode == 1 ? nullptr : e_dev, B, t0, t1, seed, logpx, nullptr, 1, (hipStream_t)stream};
+    c.kin = kin; c.reg_out = kin ? (float*)h->f_reg : nullptr; c.exact = mode == 1; c.ls = &ls;
+    rnde_status st = ff_forward(h, c, nfe_out, sv.data(), &nsv);
     if (st != RNDE_OK) { h->tp.valid = false; return st; }      // (no sweep behind a solve that failed)
     *reg_out_host = h->cfg.regularize ? ff_saveval_term(sv.data(), nsv, lambda_r, sv_bar) : 0.f;
     st = ff_backward(h, h->f_logpx_bar, h->cfg.regularize && nsv ? sv_bar.data() : nullptr, kin ? (const float*)h->f_reg_bar : nullptr, p_bar_dev, x_bar_dev,
@@ -750,66 +703,39 @@ extern "C" rnde_status rnde_ffjord_sample(rnde_ffjord* h, const float* p_dev, co
         if (st != RNDE_OK) { h->err = "rnde_normal_fill failed"; return st; }
         z_dev = h->e_buf;
     }
-    return ff_solve(h, -1, z_dev, p_dev, nullptr, n, t0, t1, seed, nullptr, 0, nullptr, x_out_dev, 0, s);
+    FfCall c{z_dev, p_dev, nullptr, n, t0, t1, seed, nullptr, x_out_dev, 0, s};
+    c.dir = -1;
+    return ff_solve(h, c);
+}
+
+// One evaluation of the dynamics on the handle's engine (the launch is not waited for).
+static rnde_status ff_feval(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t, int32_t exact, bool kin,
+                            float* out_dev, hipStream_t s) {
+    if (h->engine == 0) with_kin(kin, [&](auto K) {
+        hipLaunchKernelGGL(rnde_ffjord_feval_kernel<decltype(K)::value>, dim3((B + 255) / 256), dim3(256), 0, s, h->G, p_dev, x_dev, e_dev, t, B, exact, h->rws, out_dev);
+    });
+    else with_dyn(h, [&](auto dyn, const auto& G) { with_kin(kin, [&](auto K) {
+        hipLaunchKernelGGL((rnde_tile_feval_kernel<typename decltype(dyn)::type, decltype(K)::value>), dim3((B + 15) / 16), dim3(kFtThreads), h->lds_bytes, s, G, p_dev,
+                           x_dev, e_dev, t, B, exact, h->rws, h->sw.scratch, out_dev);
+    }); });
+    FCHK(h, hipGetLastError());
+    return RNDE_OK;
 }
 
 extern "C" rnde_status rnde_ffjord_debug_feval(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t,
                                                int32_t exact, float* out_dev, void* stream) {
     if (!h || !x_dev || !p_dev || !out_dev || B < 1 || B > h->cfg.max_batch || (!exact && !e_dev)) { if (h) h->err = "bad argument"; return RNDE_ERR_BAD_ARG; }
-    if (h->engine == 2) tile_launch_feval<FcDyn>(h, h->CG, p_dev, x_dev, e_dev, B, t, exact, false, out_dev, (hipStream_t)stream);
-    else if (h->engine == 1) tile_launch_feval<FtDyn>(h, h->TG, p_dev, x_dev, e_dev, B, t, exact, false, out_dev, (hipStream_t)stream);
-    else
-        hipLaunchKernelGGL(rnde_ffjord_feval_kernel<false>, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->G, p_dev, x_dev, e_dev, t, B, exact,
-                           h->rws, out_dev);
-    FCHK(h, hipGetLastError());
-    return RNDE_OK;
+    return ff_feval(h, x_dev, p_dev, e_dev, B, t, exact, false, out_dev, (hipStream_t)stream);
 }
 
 extern "C" rnde_status rnde_ffjord_debug_feval_kinetic(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t B, float t,
                                                        float* out_dev, void* stream) {
     if (!h || !x_dev || !p_dev || !e_dev || !out_dev || B < 1 || B > h->cfg.max_batch) { if (h) h->err = "bad argument"; return RNDE_ERR_BAD_ARG; }
     if (rnde_status kst = ff_kinetic_ready(h)) return kst;
-    if (h->engine == 2) tile_launch_feval<FcDyn>(h, h->CG, p_dev, x_dev, e_dev, B, t, 0, true, out_dev, (hipStream_t)stream);
-    else if (h->engine == 1) tile_launch_feval<FtDyn>(h, h->TG, p_dev, x_dev, e_dev, B, t, 0, true, out_dev, (hipStream_t)stream);
-    else
-        hipLaunchKernelGGL(rnde_ffjord_feval_kernel<true>, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->G, p_dev, x_dev, e_dev, t, B, 0,
-                           h->rws, out_dev);
-    FCHK(h, hipGetLastError());
-    return RNDE_OK;
+    return ff_feval(h, x_dev, p_dev, e_dev, B, t, 0, true, out_dev, (hipStream_t)stream);
 }
 
 // ---- several batches per launch (engines 1 and 2; the plan: rnde_group_plan.h, the kernel: rnde_tile_group_solve_kernel) ----
-template <class Dyn>
-static rnde_status groups_reserve(rnde_ffjord* h, const typename Dyn::Geo& G, int max_groups, int max_columns) {
-    const int tiles = group_reserved_tiles(max_columns);
-    const void* kern = (const void*)rnde_tile_group_solve_kernel<Dyn>;
-    FCHK(h, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
-    hipError_t e;
-    // (up to 32 tiles the check counts one workgroup on each CU of an XCD, which the whole device holds as well: the launch is at agent scope)
-    const std::string why = tile_residency_refusal({kern}, kFtThreads, h->lds_bytes, tiles, h->cfg.device, "TrackedFFJORD groups: max_columns / 16: ",
-                                                   "the group solve's meetings", "the group kernel's footprint", &e);
-    FCHK(h, e);
-    if (!why.empty()) { h->err = why; return RNDE_ERR_BAD_ARG; }
-    auto gr = std::make_unique<rnde_ffjord::Groups>();
-    const size_t NT = (size_t)tiles, NG = (size_t)max_groups, MA = (size_t)h->cfg.max_attempts, RB = (size_t)h->R * 16 * NT;
-    FCHK(h, gr->ws.alloc(10 * RB));
-    FCHK(h, gr->norm.alloc(8 * NT + 512));
-    FCHK(h, hipMemset(gr->norm, 0, (8 * NT + 512) * 4));
-    if (Dyn::scratch_floats(G)) FCHK(h, gr->qt.alloc(NT * Dyn::scratch_floats(G)));
-    FCHK(h, gr->ctl.alloc(2 * NG));
-    FCHK(h, gr->fin.alloc(NG));
-    FCHK(h, gr->ctl_t.alloc(NT));
-    FCHK(h, gr->meta.alloc(NG * MA));
-    FCHK(h, gr->initrec_t.alloc(NT));
-    FCHK(h, gr->table.alloc(NG));
-    FCHK(h, gr->h_fin.alloc(NG));
-    FCHK(h, gr->h_table.alloc(NG));
-    FCHK(h, gr->meet.create(MA + 4, 3, tiles));
-    gr->max_groups = max_groups; gr->tiles = tiles; gr->max_columns = max_columns;
-    h->gr = std::move(gr);
-    return RNDE_OK;
-}
-
 extern "C" rnde_status rnde_ffjord_reserve_groups(rnde_ffjord* h, int32_t max_groups, int32_t max_columns) {
     if (!h) return RNDE_ERR_BAD_ARG;
     const std::string why = group_reserve_refusal(h->engine, h->tp.valid, max_groups, max_columns);
@@ -817,7 +743,25 @@ extern "C" rnde_status rnde_ffjord_reserve_groups(rnde_ffjord* h, int32_t max_gr
     FCHK(h, hipDeviceSynchronize());           // (nothing of a call in flight reads what is released here)
     h->gr.reset();
     if (max_groups == 0) return RNDE_OK;
-    return h->engine == 2 ? groups_reserve<FcDyn>(h, h->CG, max_groups, max_columns) : groups_reserve<FtDyn>(h, h->TG, max_groups, max_columns);
+    const int tiles = group_reserved_tiles(max_columns);
+    return with_dyn(h, [&](auto dyn, const auto& G) {
+        using Dyn = typename decltype(dyn)::type;
+        const void* kern = (const void*)rnde_tile_group_solve_kernel<Dyn>;
+        FCHK(h, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+        hipError_t e;
+        // (up to 32 tiles the check counts one workgroup on each CU of an XCD, which the whole device holds as well: the launch is at agent scope)
+        const std::string full = tile_residency_refusal({kern}, kFtThreads, h->lds_bytes, tiles, h->cfg.device, "TrackedFFJORD groups: max_columns / 16: ",
+                                                        "the group solve's meetings", "the group kernel's footprint", &e);
+        FCHK(h, e);
+        if (!full.empty()) { h->err = full; return RNDE_ERR_BAD_ARG; }
+        auto gr = std::make_unique<rnde_ffjord::Groups>();
+        FCHK(h, gr->sw.alloc(h->R, tiles, max_groups, h->cfg.max_attempts, Dyn::scratch_floats(G), tiles, true));
+        FCHK(h, gr->table.alloc((size_t)max_groups));
+        FCHK(h, gr->h_table.alloc((size_t)max_groups));
+        gr->max_groups = max_groups; gr->tiles = tiles; gr->max_columns = max_columns;
+        h->gr = std::move(gr);
+        return RNDE_OK;
+    });
 }
 
 extern "C" rnde_status rnde_ffjord_group_capacity(const rnde_ffjord* h, int32_t* max_groups_out, int32_t* max_columns_out) {
@@ -825,26 +769,6 @@ extern "C" rnde_status rnde_ffjord_group_capacity(const rnde_ffjord* h, int32_t*
     if (max_groups_out) *max_groups_out = h->gr ? h->gr->max_groups : 0;
     if (max_columns_out) *max_columns_out = h->gr ? h->gr->max_columns : 0;
     return RNDE_OK;
-}
-
-template <class Dyn>
-static void groups_launch(rnde_ffjord* h, const typename Dyn::Geo& G, const GroupPlan& plan, const float* x_dev, const float* p_dev, const float* e_dev,
-                          float t0, float t1, bool exact, float* logpx_dev, const Meet& meet, hipStream_t s) {
-    rnde_ffjord::Groups& W = *h->gr;
-    TileGroupParams<typename Dyn::Geo> Q{};
-    TileSolveParams<typename Dyn::Geo>& T = Q.T;
-    StepParams& P = T.F;             // (the fields of ff_solve's forward; B, Bn and the per-group pointers are set per group on the device)
-    P.x = x_dev; P.D = h->R; P.B = plan.g[0].B; P.Bn = plan.g[0].B; P.Bpad = plan.Bp; P.nwg = 1;
-    P.ctl = W.ctl; P.ctl_final = W.fin; P.meta = W.meta; P.initrec = W.initrec_t; P.initpart = W.norm;
-    P.reltol = h->cfg.reltol; P.abstol = h->cfg.abstol; P.t0 = t0; P.t1 = t1;
-    P.tape = 1; P.max_attempts = h->cfg.max_attempts; P.reg_kind = 0; P.nsave = 0; P.replay = nullptr; P.n_replay = 0;
-    P.beta1 = kBeta1; P.beta2 = kBeta2; P.rk_order = 5.f;
-    T.G = G; T.p = p_dev; T.x = x_dev; T.e = exact ? nullptr : e_dev; T.ws = W.ws; T.tape = nullptr; T.logpx = logpx_dev; T.x_out = nullptr;
-    T.norm = W.norm; T.initrec_t = W.initrec_t; T.ctl_t = W.ctl_t; T.exact = exact ? 1 : 0; T.scratch = exact ? (float*)W.qt : nullptr;
-    T.meet = meet; T.xcc = W.meet.xcc; T.xcd_slot = W.meet.slot; T.dir = 1; T.Bp = plan.Bp; T.ntiles = plan.g[0].ntiles; T.tbase = t1; T.reg = nullptr;
-    Q.table = W.table; Q.n_groups = plan.n_groups; Q.meet_rows = h->cfg.max_attempts + 4; Q.meta_stride = h->cfg.max_attempts;
-    Q.scratch_floats = Dyn::scratch_floats(G);
-    hipLaunchKernelGGL((rnde_tile_group_solve_kernel<Dyn>), dim3(plan.tiles), dim3(kFtThreads), h->lds_bytes, s, Q);
 }
 
 extern "C" rnde_status rnde_ffjord_forward_groups(rnde_ffjord* h, const float* x_dev, const float* p_dev, const float* e_dev, int32_t n_groups,
@@ -856,45 +780,52 @@ extern "C" rnde_status rnde_ffjord_forward_groups(rnde_ffjord* h, const float* x
                                                h->engine >= 1, e_dev != nullptr, sum_dev != nullptr, count_dev != nullptr);
     if (!why.empty()) { h->err = why; return RNDE_ERR_BAD_ARG; }
     if (!x_dev || !p_dev || !logpx_dev) { h->err = "TrackedFFJORD groups: x_dev, p_dev and logpx_dev are required"; return RNDE_ERR_BAD_ARG; }
-    rnde_ffjord::Groups& W = *h->gr;
+    rnde_ffjord::Groups& GR = *h->gr;
     hipStream_t s = (hipStream_t)stream;
     const GroupPlan plan = group_plan(n_groups, B_host);
-    for (int g = 0; g < n_groups; ++g) W.h_table[g] = plan.g[g];
-    FCHK(h, hipMemcpyAsync(W.table, W.h_table, (size_t)n_groups * sizeof(TileGroup), hipMemcpyHostToDevice, s));
-    const Meet meet = W.meet.begin(plan.tiles, false, s);      // agent scope whatever the count
-    FCHK(h, W.meet.err);
-    W.log.clear();
-    FCHK(h, hipEventRecord(h->ev[0], s));
-    if (h->engine == 2) groups_launch<FcDyn>(h, h->CG, plan, x_dev, p_dev, e_dev, t0, t1, exact != 0, logpx_dev, meet, s);
-    else groups_launch<FtDyn>(h, h->TG, plan, x_dev, p_dev, e_dev, t0, t1, exact != 0, logpx_dev, meet, s);
-    FCHK(h, hipGetLastError());
-    FCHK(h, hipEventRecord(h->ev[1], s));
-    FCHK(h, hipMemcpyAsync(W.h_fin, W.fin, (size_t)n_groups * sizeof(StepState), hipMemcpyDeviceToHost, s));
-    FCHK(h, W.meet.queue_check(meet, s));
-    FCHK(h, hipStreamSynchronize(s));
+    for (int g = 0; g < n_groups; ++g) GR.h_table[g] = plan.g[g];
+    FCHK(h, hipMemcpyAsync(GR.table, GR.h_table, (size_t)n_groups * sizeof(TileGroup), hipMemcpyHostToDevice, s));
+    GR.log.clear();
+    const TileSolveWs& W = GR.sw;
+    // (the fields of ff_solve's forward under the call's row stride; B, Bn and the per-group pointers are set per group on the device)
+    StepParams F = tile_step_params(W, x_dev, h->R, plan.g[0].B, h->cfg.reltol, h->cfg.abstol, t0, t1, h->cfg.max_attempts, nullptr, 0);
+    F.Bpad = plan.Bp;
+    auto launch = [&](const Meet& meet) {
+        with_dyn(h, [&](auto dyn, const auto& G) {
+            using Dyn = typename decltype(dyn)::type;
+            TileGroupParams<typename Dyn::Geo> Q{};
+            TileSolveParams<typename Dyn::Geo>& T = Q.T;
+            T.F = F; T.G = G; T.p = p_dev; T.x = x_dev; T.e = exact ? nullptr : e_dev; T.logpx = logpx_dev;
+            tile_bind_ws(T, W);
+            tile_bind_meet(T, GR.sw.meet, meet);
+            T.exact = exact ? 1 : 0; T.scratch = exact ? (float*)W.scratch : nullptr; T.dir = 1; T.Bp = plan.Bp; T.ntiles = plan.g[0].ntiles; T.tbase = t1;
+            Q.table = GR.table; Q.n_groups = plan.n_groups; Q.meet_rows = h->cfg.max_attempts + 4; Q.meta_stride = h->cfg.max_attempts;
+            Q.scratch_floats = Dyn::scratch_floats(G);
+            hipLaunchKernelGGL((rnde_tile_group_solve_kernel<Dyn>), dim3(plan.tiles), dim3(kFtThreads), h->lds_bytes, s, Q);
+        });
+        return hipGetLastError();
+    };
+    std::string bad;
+    FCHK(h, tile_run_met(GR.sw.meet, plan.tiles, false, h->ev[0], h->ev[1], s, launch,      // agent scope whatever the count
+                         [&] { return hipMemcpyAsync(W.h_fin, W.fin(), (size_t)n_groups * sizeof(StepState), hipMemcpyDeviceToHost, s); },
+                         "TrackedFFJORD groups: ", "the group solve", "every group was abandoned", &bad));
     (void)hipEventElapsedTime(&h->fwd_ms, h->ev[0], h->ev[1]);
-    {
-        hipError_t me;
-        const std::string bad = tile_meet_refusal(W.meet, meet, plan.tiles, s, "TrackedFFJORD groups: ", "the group solve", "every group was abandoned", &me);
-        FCHK(h, me);
-        if (!bad.empty()) { h->err = bad; return RNDE_ERR_HIP; }
-    }
-    W.log.resize(n_groups);
+    if (!bad.empty()) { h->err = bad; return RNDE_ERR_HIP; }
+    GR.log.resize(n_groups);
     int first_bad = -1;
     for (int g = 0; g < n_groups; ++g) {
-        const StepState& fin = W.h_fin[g];
-        W.log[g].resize(fin.n_att);
-        if (fin.n_att)
-            FCHK(h, hipMemcpy(W.log[g].data(), W.meta + (size_t)g * h->cfg.max_attempts, (size_t)fin.n_att * sizeof(StepMeta), hipMemcpyDeviceToHost));
+        const StepState& fin = GR.sw.h_fin[g];
+        GR.log[g].resize(fin.n_att);
+        FCHK(h, tile_fetch_log(W.meta + (size_t)g * h->cfg.max_attempts, fin.n_att, GR.log[g].data()));
         if (nfe_out_host) nfe_out_host[g] = 3 + 6 * (int64_t)fin.n_att;
-        const rnde_status st = fin.status == 0 ? RNDE_OK : fin.status == 2 ? RNDE_ERR_MAX_ATTEMPTS : fin.status == 3 ? RNDE_ERR_DT_UNDERFLOW : RNDE_ERR_NONFINITE;
+        const rnde_status st = solve_verdict(fin.status).st;
         if (status_out_host) status_out_host[g] = st;
         if (st != RNDE_OK && first_bad < 0) first_bad = g;
     }
     if (first_bad >= 0) {
-        const int cs = W.h_fin[first_bad].status;
+        const int cs = GR.sw.h_fin[first_bad].status;
         h->err = group_failure(first_bad, cs);
-        return cs == 2 ? RNDE_ERR_MAX_ATTEMPTS : cs == 3 ? RNDE_ERR_DT_UNDERFLOW : RNDE_ERR_NONFINITE;
+        return solve_verdict(cs).st;
     }
     if (sum_dev) {                   // behind the final states, and only when every group ended well: a failed call adds nothing
         hipLaunchKernelGGL(rnde_group_sum_kernel, dim3(1), dim3(256), 0, s, (const float*)logpx_dev, plan.cols, sum_dev, (long long*)count_dev);
@@ -910,12 +841,7 @@ extern "C" rnde_status rnde_ffjord_group_steps(rnde_ffjord* h, int32_t g, float*
         return RNDE_ERR_BAD_ARG;
     }
     const std::vector<StepMeta>& log = h->gr->log[g];
-    *n_attempts_out = (int32_t)log.size();
-    if (steps_host) {
-        if (capacity < (int)log.size()) { h->err = "group_steps: capacity below the attempt count"; return RNDE_ERR_BAD_ARG; }
-        for (size_t i = 0; i < log.size(); ++i) { steps_host[2 * i] = log[i].dt; steps_host[2 * i + 1] = (log[i].flags & F_ACCEPT) ? 1.f : 0.f; }
-    }
-    return RNDE_OK;
+    return ff_export(h, "group_steps", log.data(), (int)log.size(), false, steps_host, capacity, n_attempts_out);
 }
 
 extern "C" rnde_status rnde_ffjord_timing(rnde_ffjord* h, float* solve_ms, float* reverse_ms, int32_t* attempts, int32_t* accepted) {

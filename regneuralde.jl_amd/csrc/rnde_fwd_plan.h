@@ -1,6 +1,7 @@
 // rnde_fwd_plan.h -- what the host decides around a forward solve and derives from its attempt log, each rule stated once: the value the saving
 // callback records (callback_value) beside its derivative (eig_cotangent, used by the reverse passes), which attempts saved a value
-// (gather_saved_values), where the accepted steps ended (step_end_times), and the sizing rules of the solve forms.  Kernel-free in the manner of
+// (gather_saved_values), where the accepted steps ended (step_end_times), what the controller's final status means to the caller (solve_verdict),
+// the two exports of an attempt log (export_steps, export_step_log), and the sizing rules of the solve forms.  Kernel-free in the manner of
 // rnde_rev_plan.h (which includes this header): plain C++, templates over the record type (StepMeta, or any record with the fields named), so
 // a host program can include it alone (tests/save_host/fwd_plan_check.cpp).
 #pragma once
@@ -54,19 +55,44 @@ inline void eig_cotangent(int reg_kind, float svb, const Rec& mm, float* c1, flo
 
 // Saving callback values (reference neural_ode.jl:116, :126-127): one per ACCEPTED attempt (att[n].flags & accept_flag; .eest, .dt, .eigen), in
 // front of them the value at init when cb_save_start (EEst = 1, dt = 0, eigen_est = 1: SURVEY B.5); none under RNDE_REG_NONE.  sv_index[n]: where
-// attempt n's value sits, or -1; values (may be null): the values themselves.  Returns their number.
+// attempt n's value sits, or -1 (may be null); values (may be null: the count alone): the values themselves.  Returns their number.
 template <class Rec>
 inline int gather_saved_values(const Rec* att, int n_att, int accept_flag, int reg_kind, bool cb_save_start, int* sv_index, float* values) {
     int nsv = 0;
-    for (int n = 0; n < n_att; ++n) sv_index[n] = -1;
+    if (sv_index) for (int n = 0; n < n_att; ++n) sv_index[n] = -1;
     if (reg_kind == RNDE_REG_NONE) return 0;
     if (cb_save_start) { if (values) values[nsv] = callback_value(reg_kind, 1.f, 0.f, 1.f); ++nsv; }
     for (int n = 0; n < n_att; ++n)
         if (att[n].flags & accept_flag) {
             if (values) values[nsv] = callback_value(reg_kind, att[n].eest, att[n].dt, att[n].eigen);
-            sv_index[n] = nsv++;
+            if (sv_index) sv_index[n] = nsv;
+            ++nsv;
         }
     return nsv;
+}
+
+// What the controller's final status (StepState.status, written by advance_state in rnde_fwd.h: 0 the span is done, 2 max_attempts, 3 dt at
+// or below kDtMin, 4 a non-finite dt or error estimate) means to the caller.  Any other nonzero value reads as non-finite, as it always has.
+struct SolveVerdict { rnde_status st; const char* msg; };
+inline SolveVerdict solve_verdict(int ctl_status) {
+    switch (ctl_status) {
+        case 0: return {RNDE_OK, ""};
+        case 2: return {RNDE_ERR_MAX_ATTEMPTS, "max_attempts reached"};
+        case 3: return {RNDE_ERR_DT_UNDERFLOW, "dt underflow"};
+        default: return {RNDE_ERR_NONFINITE, "non-finite error estimate or dt"};
+    }
+}
+
+// The exports of an attempt log: (dt, accepted) per attempt, what a replay takes back (out: 2 n floats), and (t, dt, EEst, accepted) (4 n).
+template <class Rec>
+inline void export_steps(const Rec* att, int n, int accept_flag, float* out) {
+    for (int i = 0; i < n; ++i) { out[2 * i] = att[i].dt; out[2 * i + 1] = (att[i].flags & accept_flag) ? 1.f : 0.f; }
+}
+template <class Rec>
+inline void export_step_log(const Rec* att, int n, int accept_flag, float* out) {
+    for (int i = 0; i < n; ++i) {
+        out[4 * i] = att[i].t; out[4 * i + 1] = att[i].dt; out[4 * i + 2] = att[i].eest; out[4 * i + 3] = (att[i].flags & accept_flag) ? 1.f : 0.f;
+    }
 }
 
 // Where the accepted steps of a solve ended: t + dt in fp32, as the controller forms it, clamped to t1 (the last step ends at t1 exactly whenever

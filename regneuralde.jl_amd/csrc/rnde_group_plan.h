@@ -12,6 +12,8 @@
 #include <cstdint>
 #include <string>
 
+#include "rnde_fwd_plan.h"      // solve_verdict
+
 namespace rnde {
 
 constexpr int kGroupMax = 16;             // groups one launch carries (the kernel finds its group by walking the table)
@@ -93,10 +95,9 @@ inline std::string group_call_refusal(int cap_groups, int cap_tiles, int max_bat
     return "";
 }
 
-// The call's status message when group g ended with controller status `status` (2: attempts, 3: dt underflow, otherwise non-finite).
+// The call's status message when group g ended with controller status `status` (nonzero; the words: solve_verdict).
 inline std::string group_failure(int g, int status) {
-    return "TrackedFFJORD groups: group " + std::to_string(g) + ": " +
-           (status == 2 ? "max_attempts reached" : status == 3 ? "dt underflow" : "non-finite error estimate or dt");
+    return "TrackedFFJORD groups: group " + std::to_string(g) + ": " + solve_verdict(status).msg;
 }
 
 }  // namespace rnde

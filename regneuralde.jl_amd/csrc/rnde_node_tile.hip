@@ -17,13 +17,9 @@ struct rnde_node_tiled {
     size_t lds_bytes = 0;
     Event ev[5];                     // (ahead of the buffers: members go in reverse order, the buffers and the meeting place first)
     // (every pointer member is an owner, rnde_alloc.h; h->h_meta, where the host reads the step log, is an owner of the rnde_node)
-    DevBuf<float> ws, tape, norm, replay, rws, pacc, pcopy;
-    DevBuf<StepState> ctl;           // [3]: the two live states, then the final one
-    DevBuf<StepState> ctl_t;         // [ntiles]
-    DevBuf<StepMeta> meta;           // [max_attempts]
-    DevBuf<InitRec> initrec_t;       // [ntiles]
+    TileSolveWs sw;                  // the solve's workspace and the tiles' meeting place (rnde_tile_host.h)
+    DevBuf<float> tape, replay, rws, pacc, pcopy;
     DevBuf<FfStepRec> rec;           // [max_attempts]
-    PinBuf<StepState> h_fin;         // pinned: the final controller state of the running solve (an asynchronous copy must not land in a dead stack frame)
     // rnde_node_set_tracking: taped forwards are reversed with the controller (and the initial step) differentiated
     bool track_ctrl = false, track_initdt = false;
     DevBuf<FfAttRec> att;            // [max_attempts]: the tracked sweep's attempt records (allocated when tracking is first switched on)
@@ -31,7 +27,6 @@ struct rnde_node_tiled {
     PinBuf<double> h_tsb;            // pinned [2]: where the host reads them (likewise)
     std::vector<FfStepRec> h_rec;    // the accepted steps' records of the last reverse sweep (likewise)
     std::vector<FfAttRec> h_att;     // the attempt records of the last tracked sweep (the source of an asynchronous copy: it outlives the call)
-    MeetRes meet;
     // the taped forward, kept apart from the last solve (an untaped probe between a taped forward and its backward leaves it alone)
     std::vector<StepMeta> tp_meta;
     int tp_n_att = 0, tp_n_acc = 0, tp_B = 0;
@@ -47,7 +42,6 @@ struct rnde_node_tiled {
     std::vector<float> h_sv, tp_saveat;      // the running solve's times (the source of an asynchronous copy); the taped forward's (empty: an end-state tape)
     std::vector<SaveRange> h_rng;            // (likewise a copy's source)
 };
-
 
 static FcGeo nt_geo(const rnde_node_config* c) { return fc_geo(c->n_layers, c->dims, c->act, c->time_dep); }
 static bool nt_shape_ok(const rnde_node_config* c) {
@@ -127,23 +121,15 @@ extern "C" rnde_status rnde_node_create_tiled(const rnde_node_config* c, rnde_no
     hipError_t e;
     const int D = h->D;
     const size_t RB = (size_t)D * T->Bp, MA = (size_t)c->max_attempts, NT = (size_t)T->ntiles_max;
-    if ((e = T->ws.alloc(10 * RB)) != hipSuccess) return fail(e);
+    if ((e = T->sw.alloc(D, T->ntiles_max, 1, c->max_attempts, 0, kMwMeetMax, false)) != hipSuccess) return fail(e);
     if ((e = T->tape.alloc((MA + 1) * RB)) != hipSuccess) return fail(e);
-    if ((e = T->norm.alloc(8 * NT + 512)) != hipSuccess) return fail(e);
-    if ((e = hipMemset(T->norm, 0, (8 * NT + 512) * 4)) != hipSuccess) return fail(e);
     if ((e = T->replay.alloc(2 * MA)) != hipSuccess) return fail(e);
     if ((e = T->rws.alloc(NT * NtDyn::rev_ws_floats(T->G))) != hipSuccess) return fail(e);
     if ((e = T->pacc.alloc(NT * T->G.P)) != hipSuccess) return fail(e);
     if ((e = T->pcopy.alloc((size_t)T->G.P)) != hipSuccess) return fail(e);
-    if ((e = T->ctl.alloc(3)) != hipSuccess) return fail(e);
-    if ((e = T->ctl_t.alloc(NT)) != hipSuccess) return fail(e);
-    if ((e = T->meta.alloc(MA)) != hipSuccess) return fail(e);
-    if ((e = T->initrec_t.alloc(NT)) != hipSuccess) return fail(e);
     if ((e = T->rec.alloc(MA)) != hipSuccess) return fail(e);
     if ((e = h->own_h_meta.alloc(MA)) != hipSuccess) return fail(e);
     h->h_meta = h->own_h_meta;
-    if ((e = T->h_fin.alloc(1)) != hipSuccess) return fail(e);
-    if ((e = T->meet.create(MA + 4, 3, kMwMeetMax)) != hipSuccess) return fail(e);
     const void* solve = (const void*)rnde_tile_solve_kernel<NtDyn, false, false>;
     for (const void* k : {solve, (const void*)rnde_tile_reverse_kernel<NtDyn, false, false, false>, (const void*)rnde_tile_feval_kernel<NtDyn, false>})
         if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)T->lds_bytes)) != hipSuccess) return fail(e);
@@ -195,49 +181,32 @@ rnde_status node_tiled_forward(rnde_node* h, const float* x_dev, const float* p_
         HIPCHK(h, hipMemcpyAsync(T->sv_t, T->h_sv.data(), (size_t)n_saveat * 4, hipMemcpyHostToDevice, s));
         if (taped) HIPCHK(h, hipMemcpyAsync(T->tp_sv_t, T->h_sv.data(), (size_t)n_saveat * 4, hipMemcpyHostToDevice, s));
     }
+    const TileSolveWs& W = T->sw;
     TileSolveParams<FcGeo> Q{};
-    StepParams& P = Q.F;
-    P.x = x_dev; P.D = h->D; P.B = B; P.Bn = B; P.Bpad = T->Bp; P.nwg = 1;
-    P.ctl = T->ctl; P.ctl_final = T->ctl + 2; P.meta = T->meta; P.initrec = T->initrec_t; P.initpart = T->norm;
-    P.reltol = h->cfg.reltol; P.abstol = h->cfg.abstol; P.t0 = t0; P.t1 = t1;
-    P.tape = 1; P.max_attempts = h->cfg.max_attempts; P.reg_kind = 0; P.nsave = 0;
-    if (saving) { P.sv_t = T->sv_t; P.nsave = n_saveat; P.sv_out = sv_out_dev; }
-    P.replay = steps_host ? T->replay : nullptr; P.n_replay = steps_host ? n_steps : 0;
-    P.beta1 = kBeta1; P.beta2 = kBeta2; P.rk_order = 5.f;
+    Q.F = tile_step_params(W, x_dev, h->D, B, h->cfg.reltol, h->cfg.abstol, t0, t1, h->cfg.max_attempts, steps_host ? (const float*)T->replay : nullptr, n_steps);
+    if (saving) { Q.F.sv_t = T->sv_t; Q.F.nsave = n_saveat; Q.F.sv_out = sv_out_dev; }
+    tile_bind_ws(Q, W);
     const int nt = (B + 15) / 16;
-    const Meet meet = T->meet.begin(nt, true, s);      // every tile resident, one meeting per attempt (one XCD up to 32 tiles, agent scope above)
-    HIPCHK(h, T->meet.err);
-    Q.G = T->G; Q.p = p_dev; Q.x = x_dev; Q.ws = T->ws; Q.tape = taped ? T->tape : nullptr; Q.x_out = u_out_dev; Q.norm = T->norm;
-    Q.initrec_t = T->initrec_t; Q.ctl_t = T->ctl_t; Q.meet = meet; Q.xcc = T->meet.xcc; Q.xcd_slot = T->meet.slot; Q.dir = 1; Q.Bp = T->Bp; Q.ntiles = nt;
-    HIPCHK(h, hipEventRecord(T->ev[0], s));
-    if (saving) hipLaunchKernelGGL((rnde_tile_solve_kernel<NtDyn, false, true>), dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
-    else hipLaunchKernelGGL((rnde_tile_solve_kernel<NtDyn, false, false>), dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(T->ev[1], s));
-    T->ev_fwd = true;
-    const StepState& fin = *T->h_fin;
-    HIPCHK(h, hipMemcpyAsync(T->h_fin, T->ctl + 2, sizeof(StepState), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, T->meet.queue_check(meet, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    hipError_t me;
-    const std::string why = tile_meet_refusal(T->meet, meet, nt, s, kNtPrefix, "the solve", "the solve was abandoned", &me);
-    HIPCHK(h, me);
+    Q.G = T->G; Q.p = p_dev; Q.x = x_dev; Q.tape = taped ? T->tape : nullptr; Q.x_out = u_out_dev; Q.dir = 1; Q.ntiles = nt;
+    const StepState& fin = *T->sw.h_fin;
+    std::string why;
+    // every tile resident, one meeting per attempt (one XCD up to 32 tiles, agent scope above)
+    HIPCHK(h, tile_run_met(T->sw.meet, nt, true, T->ev[0], T->ev[1], s,
+                           [&](const Meet& meet) {
+                               tile_bind_meet(Q, T->sw.meet, meet);
+                               if (saving) hipLaunchKernelGGL((rnde_tile_solve_kernel<NtDyn, false, true>), dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
+                               else hipLaunchKernelGGL((rnde_tile_solve_kernel<NtDyn, false, false>), dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
+                               return hipGetLastError();
+                           },
+                           [&] { T->ev_fwd = true; return hipMemcpyAsync(W.h_fin, W.fin(), sizeof(StepState), hipMemcpyDeviceToHost, s); },
+                           kNtPrefix, "the solve", "the solve was abandoned", &why));
     if (!why.empty()) { h->n_att = 0; h->err = why; return RNDE_ERR_HIP; }
     h->n_att = fin.n_att; h->B = B; h->Bpad = T->Bp; h->t0 = t0; h->t1 = t1;
-    if (fin.n_att) HIPCHK(h, hipMemcpy(h->h_meta, T->meta, (size_t)fin.n_att * sizeof(StepMeta), hipMemcpyDeviceToHost));
-    switch (fin.status) {
-        case 0: break;
-        case 2: h->err = "max_attempts reached"; return RNDE_ERR_MAX_ATTEMPTS;
-        case 3: h->err = "dt underflow"; return RNDE_ERR_DT_UNDERFLOW;
-        default: h->err = "non-finite error estimate or dt"; return RNDE_ERR_NONFINITE;
-    }
+    HIPCHK(h, tile_fetch_log(W.meta, fin.n_att, h->h_meta));
+    if (const SolveVerdict v = solve_verdict(fin.status); v.st != RNDE_OK) { h->err = v.msg; return v.st; }
     if (nfe_out) *nfe_out = 3 + 6 * (int64_t)fin.n_att;      // 2 (initial dt) + 1 (fsalfirst) + 6 per attempt
-    int nsv = 0;
-    if (h->cfg.regularize == RNDE_REG_ERR) {       // SavingCallback(EEst * dt): 0 at init when it fires there, then one per accepted step
-        if (h->cfg.cb_save_start) { if (saveval_host) saveval_host[nsv] = 0.f; ++nsv; }
-        for (int i = 0; i < fin.n_att; ++i)
-            if (h->h_meta[i].flags & F_ACCEPT) { if (saveval_host) saveval_host[nsv] = h->h_meta[i].eest * h->h_meta[i].dt; ++nsv; }
-    }
+    // SavingCallback(EEst * dt): 0 at init when it fires there, then one per accepted step
+    const int nsv = gather_saved_values(h->h_meta, fin.n_att, F_ACCEPT, h->cfg.regularize, h->cfg.cb_save_start != 0, nullptr, saveval_host);
     h->n_saveval = nsv;
     if (n_saveval_out) *n_saveval_out = nsv;
     if (taped) {
@@ -245,10 +214,20 @@ rnde_status node_tiled_forward(rnde_node* h, const float* x_dev, const float* p_
         T->tp_n_att = fin.n_att; T->tp_n_acc = fin.n_acc; T->tp_B = B;
         T->tp_track_ctrl = T->track_ctrl; T->tp_track_initdt = T->track_initdt; T->tp_t0 = t0;
         if (saving) T->tp_saveat = T->h_sv; else T->tp_saveat.clear();
-        if (T->track_initdt) HIPCHK(h, hipMemcpy(&T->tp_init, T->initrec_t, sizeof(InitRec), hipMemcpyDeviceToHost));      // (every tile's record is tile 0's)
+        if (T->track_initdt) HIPCHK(h, hipMemcpy(&T->tp_init, W.initrec_t, sizeof(InitRec), hipMemcpyDeviceToHost));      // (every tile's record is tile 0's)
         h->have_tape = true;
     }
     return RNDE_OK;
+}
+
+// Behind a sweep (ev[3]): the tiles' partial p-bars summed into p_bar_dev, then ev[4].
+static hipError_t node_tiled_reduce(rnde_node* h, int nt, float* p_bar_dev, hipStream_t s) {
+    rnde_node_tiled* T = h->tiled;
+    hipLaunchKernelGGL(rnde_tile_reduce_kernel, dim3((h->P + 255) / 256), dim3(256), 0, s, (const float*)T->pacc, h->P, nt, p_bar_dev);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(T->ev[4], s);
+    if (e == hipSuccess) T->ev_bwd = true;
+    return e;
 }
 
 // The tracked sweep of a tape whose forward ran under rnde_node_set_tracking(h, 1, *): launched as the solve is, one meeting per attempt
@@ -266,27 +245,22 @@ static rnde_status node_tiled_backward_tracked(rnde_node* h, const std::vector<F
         if (!att.empty()) HIPCHK(h, hipMemcpyAsync(T->sv_rng, T->h_rng.data(), att.size() * sizeof(SaveRange), hipMemcpyHostToDevice, s));
     }
     const int nt = (T->tp_B + 15) / 16;
-    const Meet meet = T->meet.begin(nt, true, s);      // a new epoch re-arms the rows the solve used
-    HIPCHK(h, T->meet.err);
     Q.att = T->att; Q.n_att = (int)att.size(); Q.track_initdt = T->tp_track_initdt ? 1 : 0; Q.init = T->tp_init; Q.t0 = T->tp_t0; Q.tspan_out = T->tsb;
-    Q.meet = meet; Q.xcc = T->meet.xcc; Q.xcd_slot = T->meet.slot;
-    HIPCHK(h, hipEventRecord(T->ev[2], s));
-    if (saving) hipLaunchKernelGGL((rnde_tile_reverse_kernel<NtDyn, false, true, true>), dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
-    else hipLaunchKernelGGL((rnde_tile_reverse_kernel<NtDyn, false, true, false>), dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(T->ev[3], s));
-    hipLaunchKernelGGL(rnde_tile_reduce_kernel, dim3((h->P + 255) / 256), dim3(256), 0, s, (const float*)T->pacc, h->P, nt, p_bar_dev);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(T->ev[4], s));
-    T->ev_bwd = true;
     double* tsb = T->h_tsb;
-    HIPCHK(h, hipMemcpyAsync(tsb, T->tsb, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, T->meet.queue_check(meet, s));
-    HIPCHK(h, hipStreamSynchronize(s));      // (att and tsb are members: a copy still in flight on an error return above touches live memory)
-    hipError_t me;
-    const std::string why = tile_meet_refusal(T->meet, meet, nt, s, kNtPrefix, "the tracked reverse sweep",
-                                              "the sweep was abandoned, x_bar, p_bar and tspan_bar are not valid", &me);
-    HIPCHK(h, me);
+    std::string why;
+    // (a new epoch re-arms the rows the solve used; att and tsb are members: a copy still in flight on an error return touches live memory)
+    HIPCHK(h, tile_run_met(T->sw.meet, nt, true, T->ev[2], T->ev[3], s,
+                           [&](const Meet& meet) {
+                               tile_bind_meet(Q, T->sw.meet, meet);
+                               if (saving) hipLaunchKernelGGL((rnde_tile_reverse_kernel<NtDyn, false, true, true>), dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
+                               else hipLaunchKernelGGL((rnde_tile_reverse_kernel<NtDyn, false, true, false>), dim3(MeetRes::grid(meet)), dim3(kFtThreads), T->lds_bytes, s, Q);
+                               return hipGetLastError();
+                           },
+                           [&] {
+                               const hipError_t e = node_tiled_reduce(h, nt, p_bar_dev, s);
+                               return e == hipSuccess ? hipMemcpyAsync(tsb, T->tsb, 2 * sizeof(double), hipMemcpyDeviceToHost, s) : e;
+                           },
+                           kNtPrefix, "the tracked reverse sweep", "the sweep was abandoned, x_bar, p_bar and tspan_bar are not valid", &why));
     if (!why.empty()) { h->err = why; return RNDE_ERR_HIP; }
     if (tspan_bar_host) { tspan_bar_host[0] = (float)tsb[0]; tspan_bar_host[1] = (float)tsb[1]; }
     return RNDE_OK;
@@ -413,15 +387,12 @@ rnde_status node_tiled_backward(rnde_node* h, const float* u_bar_dev, const floa
         for (int i = 0; i < T->tp_n_att; ++i) if (T->tp_meta[i].flags & F_ACCEPT) T->h_rng.push_back(by_att[i]);
         if (!T->h_rng.empty()) HIPCHK(h, hipMemcpyAsync(T->sv_rng, T->h_rng.data(), T->h_rng.size() * sizeof(SaveRange), hipMemcpyHostToDevice, s));
     }
-    HIPCHK(h, hipEventRecord(T->ev[2], s));
-    if (saving) hipLaunchKernelGGL((rnde_tile_reverse_kernel<NtDyn, false, false, true>), dim3(nt), dim3(kFtThreads), T->lds_bytes, s, Q);
-    else hipLaunchKernelGGL((rnde_tile_reverse_kernel<NtDyn, false, false, false>), dim3(nt), dim3(kFtThreads), T->lds_bytes, s, Q);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(T->ev[3], s));
-    hipLaunchKernelGGL(rnde_tile_reduce_kernel, dim3((h->P + 255) / 256), dim3(256), 0, s, (const float*)T->pacc, h->P, nt, p_bar_dev);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(T->ev[4], s));
-    T->ev_bwd = true;
+    HIPCHK(h, tile_run_timed(T->ev[2], T->ev[3], s, [&] {      // (the tiles of this sweep do not meet)
+        if (saving) hipLaunchKernelGGL((rnde_tile_reverse_kernel<NtDyn, false, false, true>), dim3(nt), dim3(kFtThreads), T->lds_bytes, s, Q);
+        else hipLaunchKernelGGL((rnde_tile_reverse_kernel<NtDyn, false, false, false>), dim3(nt), dim3(kFtThreads), T->lds_bytes, s, Q);
+        return hipGetLastError();
+    }));
+    HIPCHK(h, node_tiled_reduce(h, nt, p_bar_dev, s));
     HIPCHK(h, hipStreamSynchronize(s));      // (rec is a host vector: the copy must have left it)
     if (tspan_bar_host) { tspan_bar_host[0] = 0.f; tspan_bar_host[1] = 0.f; }      // step sizes and times are constants of this sweep
     return RNDE_OK;

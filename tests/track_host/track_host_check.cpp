@@ -2,13 +2,17 @@
 // GPU is touched): init_rev_phase1 / init_rev_phase2 against central finite differences of the initial-step rule, and ff_att_rec's eight
 // coefficients against finite differences of the PI controller, both forward rules written here in double beside them; and the two record
 // builders of csrc/rnde_tile_host.h (the accepted steps and the attempts a reverse sweep walks) on written-down step logs, against records
-// written out by hand.  Prints one line per failed check; exit status 0 when there is none.
+// written out by hand; the map from the controller's final status to the call's, the saved values and the two exports of written-down step
+// logs; and tile_step_params against the StepParams of its three users, written out by hand.  Prints one line per failed check; exit
+// status 0 when there is none.
+#include "rnde_group_plan.h"
 #include "rnde_tile_host.h"
 #include "rnde_track_rec.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 
 using namespace rnde;
 
@@ -188,7 +192,142 @@ static void check_builders() {
     CHECK(rec.empty() && att.empty());
 }
 
+// ---- behind a solve: the status map, the saved values and the two exports of a step log (rnde_fwd_plan.h, rnde_tile_host.h) ----
+static void check_status_map() {
+    // what advance_state (rnde_fwd.h) can write: 0, 2, 3, 4; and values it cannot
+    const struct { int ctl; rnde_status st; const char* msg; } want[] = {
+        {0, RNDE_OK, ""}, {2, RNDE_ERR_MAX_ATTEMPTS, "max_attempts reached"}, {3, RNDE_ERR_DT_UNDERFLOW, "dt underflow"},
+        {4, RNDE_ERR_NONFINITE, "non-finite error estimate or dt"}, {1, RNDE_ERR_NONFINITE, "non-finite error estimate or dt"},
+        {7, RNDE_ERR_NONFINITE, "non-finite error estimate or dt"}, {-1, RNDE_ERR_NONFINITE, "non-finite error estimate or dt"}};
+    for (const auto& w : want) {
+        const SolveVerdict v = solve_verdict(w.ctl);
+        CHECK(v.st == w.st && std::string(v.msg) == w.msg);
+    }
+    CHECK(group_failure(3, 2) == "TrackedFFJORD groups: group 3: max_attempts reached");
+    CHECK(group_failure(0, 3) == "TrackedFFJORD groups: group 0: dt underflow");
+    CHECK(group_failure(15, 4) == "TrackedFFJORD groups: group 15: non-finite error estimate or dt");
+}
+
+template <int NV>
+static void check_log(const char* what, const std::vector<StepMeta>& log, const float (&sv_on)[NV + 1], const float* steps, const float* wide) {
+    const int n = (int)log.size();
+    // the saved values: with the value at init in front (cb_save_start), without it, without a regulariser; each also count-only
+    float got[NV + 2];
+    for (int start = 0; start < 2; ++start) {
+        for (float& g : got) g = 77.f;
+        const int cnt = gather_saved_values(log.data(), n, F_ACCEPT, RNDE_REG_ERR, start != 0, nullptr, got);
+        bool ok = cnt == NV + start && gather_saved_values(log.data(), n, F_ACCEPT, RNDE_REG_ERR, start != 0, nullptr, (float*)nullptr) == cnt && got[cnt] == 77.f;
+        for (int i = 0; ok && i < cnt; ++i) ok = got[i] == sv_on[i + 1 - start];
+        if (!ok) { std::printf("FAILED %s: saved values, cb_save_start %d\n", what, start); ++failures; }
+        for (float& g : got) g = 77.f;
+        if (gather_saved_values(log.data(), n, F_ACCEPT, RNDE_REG_NONE, start != 0, nullptr, got) != 0 || gather_saved_values(log.data(), n, F_ACCEPT, RNDE_REG_NONE, start != 0, nullptr, (float*)nullptr) != 0 || got[0] != 77.f) {
+            std::printf("FAILED %s: saved values without a regulariser\n", what); ++failures;
+        }
+    }
+    std::vector<float> a(2 * n + 1, 77.f), b(4 * n + 1, 77.f);
+    export_steps(log.data(), n, F_ACCEPT, a.data());
+    export_step_log(log.data(), n, F_ACCEPT, b.data());
+    if (!std::equal(steps, steps + 2 * n, a.begin()) || a[2 * n] != 77.f) { std::printf("FAILED %s: the (dt, accepted) export\n", what); ++failures; }
+    if (!std::equal(wide, wide + 4 * n, b.begin()) || b[4 * n] != 77.f) { std::printf("FAILED %s: the (t, dt, eest, accepted) export\n", what); ++failures; }
+}
+static void check_logs() {
+    const int A = F_ACCEPT, J = F_REJQ11;
+    const float none_f[1] = {0.f};
+    check_log<0>("no attempt", {}, {0.f}, none_f, none_f);
+    {
+        const float s[2] = {0.25f, 1.f}, w[4] = {0.f, 0.25f, 0.5f, 1.f};
+        check_log<1>("one accepted attempt", {log_entry(0.f, 0.25f, 0.5f, A | F_CLAMP)}, {0.f, 0.125f}, s, w);
+    }
+    {
+        const float s[2] = {0.5f, 0.f}, w[4] = {0.f, 0.5f, 2.5f, 0.f};
+        check_log<0>("one rejected attempt", {log_entry(0.f, 0.5f, 2.5f, J)}, {0.f}, s, w);
+    }
+    {
+        const float s[8] = {0.25f, 1.f, 0.25f, 1.f, 0.25f, 1.f, 0.25f, 1.f};
+        const float w[16] = {0.f, 0.25f, 0.5f, 1.f, 0.25f, 0.25f, 0.25f, 1.f, 0.5f, 0.25f, 2.f, 1.f, 0.75f, 0.25f, 0.125f, 1.f};
+        check_log<4>("four accepted attempts", {log_entry(0.f, 0.25f, 0.5f, A), log_entry(0.25f, 0.25f, 0.25f, A), log_entry(0.5f, 0.25f, 2.f, A),
+                                                 log_entry(0.75f, 0.25f, 0.125f, A | F_CLAMP)},
+                     {0.f, 0.125f, 0.0625f, 0.5f, 0.03125f}, s, w);
+    }
+    {
+        const float s[8] = {0.5f, 0.f, 0.25f, 1.f, 1.f, 0.f, 0.75f, 1.f};
+        const float w[16] = {0.f, 0.5f, 2.5f, 0.f, 0.f, 0.25f, 0.5f, 1.f, 0.25f, 1.f, 3.f, 0.f, 0.25f, 0.75f, 0.125f, 1.f};
+        check_log<2>("four attempts, two rejected", {log_entry(0.f, 0.5f, 2.5f, J), log_entry(0.f, 0.25f, 0.5f, A), log_entry(0.25f, 1.f, 3.f, 0),
+                                                      log_entry(0.25f, 0.75f, 0.125f, A | F_CLAMP)},
+                     {0.f, 0.125f, 0.09375f}, s, w);
+    }
+}
+
+// ---- tile_step_params against the StepParams of its three users, written out by hand ----
+static bool same_params(const StepParams& a, const StepParams& b) {
+    return a.x == b.x && a.f0 == b.f0 && a.h0 == b.h0 && a.u1 == b.u1 && a.f1 == b.f1 && a.h1 == b.h1 && a.arena == b.arena && a.rec_stride == b.rec_stride &&
+           a.ctl == b.ctl && a.ctl_final == b.ctl_final && a.meta == b.meta && a.initrec == b.initrec && a.errpart == b.errpart && a.initpart == b.initpart &&
+           a.dbg_out == b.dbg_out && a.D == b.D && a.H == b.H && a.B == b.B && a.Bpad == b.Bpad && a.nwg == b.nwg && a.Bn == b.Bn && a.reltol == b.reltol &&
+           a.abstol == b.abstol && a.t0 == b.t0 && a.t1 == b.t1 && a.tape == b.tape && a.max_attempts == b.max_attempts && a.forced == b.forced &&
+           a.forced_t == b.forced_t && a.forced_dt == b.forced_dt && a.rec_shift == b.rec_shift && a.xvec == b.xvec && a.reg_kind == b.reg_kind && a.sv_t == b.sv_t &&
+           a.nsave == b.nsave && a.sv_out == b.sv_out && a.replay == b.replay && a.n_replay == b.n_replay && a.beta1 == b.beta1 && a.beta2 == b.beta2 &&
+           a.rk_order == b.rk_order && a.esum == b.esum;
+}
+// (host memory behind the workspace's owners; the members are allocated by hand, as the one-workgroup engine does: alloc() itself zeroes
+// norm on the device and creates the meeting place)
+struct HostAlloc {
+    static hipError_t get(void** p, size_t bytes) { *p = std::calloc(1, bytes ? bytes : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+    static void put(void* p) { std::free(p); }
+};
+using HostWs = TileSolveWsT<HostAlloc, HostAlloc>;
+static void host_ws(HostWs& W, int tiles, int n_solves, bool fin_apart) {
+    W.Bp = 16 * tiles; W.n_live = 2 * n_solves;
+    bool ok = W.norm.alloc(8 * tiles + 512) == hipSuccess && W.ctl.alloc(fin_apart ? 2 * n_solves : 3 * n_solves) == hipSuccess &&
+              W.meta.alloc(4 * n_solves) == hipSuccess && W.initrec_t.alloc(tiles) == hipSuccess;
+    if (fin_apart) ok = ok && W.fin_n.alloc(n_solves) == hipSuccess;
+    CHECK(ok);
+}
+static void check_step_params() {
+    static float x[8], replay[8], sv_t[4], sv_out[4];
+    const float b1 = (float)(7.0 / 50.0), b2 = (float)(2.0 / 25.0);
+    HostWs F, E, G, N;
+    host_ws(F, 3, 1, false);      // the tiled TrackedFFJORD handle, max_batch 40: three tiles, the final state behind the two live ones
+    host_ws(G, 7, 4, true);       // a reservation of 7 tiles for 4 groups: final states of their own
+    host_ws(N, 2, 1, false);      // the tiled TrackedNeuralODE, max_batch 32
+    E.Bp = 64;                    // the one-workgroup FFJORD engine: ctl [3] and one record by hand, n_live as it stands
+    CHECK(E.norm.alloc(512) == hipSuccess && E.ctl.alloc(3) == hipSuccess && E.meta.alloc(4) == hipSuccess && E.initrec_t.alloc(1) == hipSuccess);
+    for (const int B : {1, 16, 17}) {
+        // a forward along a replay, D = 2 and the kinetic rows
+        StepParams w{};
+        w.x = x; w.D = 5; w.B = B; w.Bn = B; w.Bpad = 48; w.nwg = 1; w.ctl = F.ctl.get(); w.ctl_final = F.ctl.get() + 2; w.meta = F.meta.get();
+        w.initrec = F.initrec_t.get(); w.initpart = F.norm.get();
+        w.reltol = 1e-5f; w.abstol = 1e-6f; w.t0 = 0.25f; w.t1 = 1.5f; w.tape = 1; w.max_attempts = 128; w.replay = replay; w.n_replay = 4;
+        w.beta1 = b1; w.beta2 = b2; w.rk_order = 5.f;
+        CHECK(same_params(tile_step_params(F, x, 5, B, 1e-5f, 1e-6f, 0.25f, 1.5f, 128, replay, 4), w));
+        // ... and sampling on the one-workgroup engine: tau runs from 0 to t1 - t0, no replay (its count is dropped)
+        w.D = 3; w.Bpad = 64; w.ctl = E.ctl.get(); w.ctl_final = E.ctl.get() + 2; w.meta = E.meta.get(); w.initrec = E.initrec_t.get(); w.initpart = E.norm.get();
+        w.t0 = 0.f; w.t1 = 1.25f; w.replay = nullptr; w.n_replay = 0;
+        CHECK(same_params(tile_step_params(E, x, 3, B, 1e-5f, 1e-6f, 0.f, 1.25f, 128, nullptr, 4), w));
+        // a group call: the call's row stride (three of the seven tiles) set by the caller, B the first group's
+        StepParams g = tile_step_params(G, x, 3, B, 1e-5f, 1e-5f, 0.f, 1.f, 64, nullptr, 0);
+        CHECK(g.Bpad == 16 * 7);
+        g.Bpad = 16 * 3;
+        StepParams wg{};
+        wg.x = x; wg.D = 3; wg.B = B; wg.Bn = B; wg.Bpad = 48; wg.nwg = 1; wg.ctl = G.ctl.get(); wg.ctl_final = G.fin_n.get(); wg.meta = G.meta.get();
+        wg.initrec = G.initrec_t.get(); wg.initpart = G.norm.get();
+        wg.reltol = 1e-5f; wg.abstol = 1e-5f; wg.t0 = 0.f; wg.t1 = 1.f; wg.tape = 1; wg.max_attempts = 64; wg.beta1 = b1; wg.beta2 = b2; wg.rk_order = 5.f;
+        CHECK(same_params(g, wg));
+        // the tiled TrackedNeuralODE: D rows, the saveat fields set afterwards
+        StepParams n = tile_step_params(N, x, 70, B, 1e-3f, 1e-4f, -1.f, 2.f, 8000, nullptr, 0);
+        n.sv_t = sv_t; n.nsave = 4; n.sv_out = sv_out;
+        StepParams wn{};
+        wn.x = x; wn.D = 70; wn.B = B; wn.Bn = B; wn.Bpad = 32; wn.nwg = 1; wn.ctl = N.ctl.get(); wn.ctl_final = N.ctl.get() + 2; wn.meta = N.meta.get();
+        wn.initrec = N.initrec_t.get(); wn.initpart = N.norm.get();
+        wn.reltol = 1e-3f; wn.abstol = 1e-4f; wn.t0 = -1.f; wn.t1 = 2.f; wn.tape = 1; wn.max_attempts = 8000; wn.sv_t = sv_t; wn.nsave = 4; wn.sv_out = sv_out;
+        wn.beta1 = b1; wn.beta2 = b2; wn.rk_order = 5.f;
+        CHECK(same_params(n, wn));
+    }
+}
+
 int main() {
+    check_status_map();
+    check_logs();
+    check_step_params();
     // ---- the initial step: every branch of the rule ----
     //                                   d0    d1   n2b    kd     kt    t0   t1     sel c1 mx c0 cl
     check_init("sel 0", InitIn{0.01, 1.0, 1e-5, 0.0, 0.0, 0.0, 1.0}, 0, 0, 0, 0, 0);

@@ -17,6 +17,10 @@ that holds a rejection, feval at t = 0 and 0.71; and the vetted naturally reject
 FFJORD (engines 1, 2): ConcatSquash (2, 16) and (43, 100), TD [2, 10, 2] and [5, 12, 9, 5], each at B = 17, 37, 513; per case a taped forward +
 backward, the kinetic pair, the exact-trace pair, track_ctrl on (free-running and along a log with a rejection), sample, feval (Hutchinson,
 exact, kinetic); and the vetted naturally rejecting cases of tests/test_gpu_ffjord_track.py (td2-B5, cs-B5) under track_ctrl.  tol = 1e-5.
+The host-side paths beside the single tiled solve: the one-workgroup engine (engine 0, ConcatSquash (2, 16) at B = 17: forward + backward and
+the kinetic pair); rnde_ffjord_forward_groups with three unequal groups (B = 1, 17, 37), probe and exact, adding into the sum / count
+accumulators, on ConcatSquash (2, 16) and TD [2, 10, 2]; rnde_ffjord_nll_grad in modes 0, 1 and 2 on engines 1 and 2 and modes 0 and 2 on
+engine 0, at B = 37.  --key names the key of the output file that takes the verdict ("bits" by default).
 The handles, inputs and vetted cases are those of the GPU suites (tests/test_gpu_node_tiled*.py, tests/test_gpu_ffjord_track.py, tests/act_ref.py,
 tests/ffjord_ref.py), imported from there: the tool moves with them.
 """
@@ -192,10 +196,106 @@ def ff_cases(out, logs):
         ff_case(out, logs, key, CASES[key][0], *_inputs(key), full=False)
 
 
+def ff_steps(hd, entry, *lead):
+    """The (dt, accepted) export of rnde_ffjord_steps / rnde_ffjord_group_steps (lead: the group)."""
+    n = C.c_int32()
+    hd.rn._lib.check_ffjord(hd.h, entry(hd.h, *lead, None, 0, C.byref(n)))
+    arr = (C.c_float * max(2 * n.value, 1))()
+    hd.rn._lib.check_ffjord(hd.h, entry(hd.h, *lead, arr, n.value, C.byref(n)))
+    return np.array(arr[:2 * n.value], dtype=np.float32)
+
+
+def ff_engine0_case(out, logs, name, dyn, p, x, e, g):
+    """The one-workgroup engine: a taped forward + backward (regularize = 1, a nonzero saved-value cotangent) and the kinetic pair."""
+    import torch
+    from tests.test_gpu_ffjord_track import DEV, Handle
+    B = x.shape[0]
+    hd = Handle(dyn, B, regularize=1, engine0=True)
+    logpx, sv, log = hd.forward(x, p, e)
+    pb, xb = hd.backward(g, 0.7)
+    for k, v in (("logpx", logpx.cpu().numpy()), ("saveval", sv), ("steps", np.array(log, dtype=np.float32)), ("p_bar", pb.numpy()), ("x_bar", xb.numpy())):
+        out[f"{name}/taped/{k}"] = v
+    logs.append((0, B, np.array([[t, dt, 0.0, acc] for t, dt, acc in log], dtype=np.float32)))
+    hd.close()
+    hk = Handle(dyn, B, regularize=0, engine0=True)
+    chk = lambda st: hk.rn._lib.check_ffjord(hk.h, st)
+    xd, pd, ed, gd = (v.to(DEV).contiguous() for v in (x, p, e, g))
+    logpx, reg, nfe = torch.empty(B, device=DEV), torch.empty(2 * B, device=DEV), C.c_int64()
+    chk(hk.L.rnde_ffjord_forward_kinetic(hk.h, xd.data_ptr(), pd.data_ptr(), ed.data_ptr(), B, 0.0, 1.0, 0, logpx.data_ptr(), reg.data_ptr(), None, C.byref(nfe), 1, None))
+    rb = torch.full((2 * B,), 0.01 / B, device=DEV)
+    pb, xb = torch.empty_like(pd), torch.empty_like(xd)
+    chk(hk.L.rnde_ffjord_backward_kinetic(hk.h, gd.data_ptr(), rb.data_ptr(), pb.data_ptr(), xb.data_ptr(), None))
+    torch.cuda.synchronize()
+    for k, v in (("logpx", logpx), ("reg", reg), ("p_bar", pb), ("x_bar", xb)):
+        out[f"{name}/kinetic/{k}"] = v.cpu().numpy()
+    out[f"{name}/kinetic/nfe"], out[f"{name}/kinetic/steps"] = np.array([nfe.value]), ff_steps(hk, hk.L.rnde_ffjord_steps)
+    hk.close()
+
+
+GROUP_SIZES = (1, 17, 37)
+
+
+def ff_groups_case(out, name, dyn, recipe):
+    """rnde_ffjord_forward_groups with three unequal groups, probe and exact, adding into the sum / count accumulators (twice: they accumulate)."""
+    import torch
+    from tests.test_gpu_ffjord_track import DEV, Handle
+    n, cols = len(GROUP_SIZES), sum(GROUP_SIZES)
+    p, x, e, _ = ff_inputs(dyn, recipe, cols)
+    hd = Handle(dyn, max(GROUP_SIZES), regularize=1)
+    chk = lambda st: hd.rn._lib.check_ffjord(hd.h, st)
+    chk(hd.L.rnde_ffjord_reserve_groups(hd.h, n, 16 * sum((b + 15) // 16 for b in GROUP_SIZES)))
+    xd, pd, ed = (v.to(DEV).contiguous() for v in (x, p, e))
+    acc = torch.zeros(2, dtype=torch.float64, device=DEV)      # (the sum, then the count's eight bytes)
+    for tag, exact in (("probe", 0), ("exact", 1), ("probe_again", 0)):
+        logpx = torch.full((cols,), float("nan"), device=DEV)
+        Bs, nfe, gst = (C.c_int32 * n)(*GROUP_SIZES), (C.c_int64 * n)(), (C.c_int32 * n)(*([-1] * n))
+        chk(hd.L.rnde_ffjord_forward_groups(hd.h, xd.data_ptr(), pd.data_ptr(), None if exact else ed.data_ptr(), n, Bs, 0.0, 1.0, exact, logpx.data_ptr(), nfe, gst,
+                                            acc.data_ptr(), acc.data_ptr() + 8, None))
+        torch.cuda.synchronize()
+        out[f"{name}/{tag}/logpx"], out[f"{name}/{tag}/nfe"], out[f"{name}/{tag}/status"] = logpx.cpu().numpy(), np.array(list(nfe)), np.array(list(gst))
+        out[f"{name}/{tag}/sum_count_bytes"] = acc.cpu().numpy().view(np.uint8)
+        for gi in range(n):
+            out[f"{name}/{tag}/steps{gi}"] = ff_steps(hd, hd.L.rnde_ffjord_group_steps, gi)
+    hd.close()
+
+
+def ff_nll_grad_case(out, name, dyn, recipe, B, modes, engine0=False):
+    """rnde_ffjord_nll_grad: mode 0 (probe) and 1 (exact) on a regularize = 1 handle with lambda_r, mode 2 (kinetic rows) on a regularize = 0 one."""
+    import torch
+    from tests.test_gpu_ffjord_track import DEV, Handle
+    p, x, e, _ = ff_inputs(dyn, recipe, B)
+    xd, pd, ed = (v.to(DEV).contiguous() for v in (x, p, e))
+    for mode in modes:
+        hd = Handle(dyn, B, regularize=0 if mode == 2 else 1, engine0=engine0)
+        pb, xb, lp, terms = torch.full_like(pd, float("nan")), torch.full_like(xd, float("nan")), torch.full((B,), float("nan"), device=DEV), torch.full((3,), float("nan"), device=DEV)
+        reg, nfe = C.c_float(float("nan")), C.c_int64(-1)
+        lam = (0.0, 0.01, 0.02) if mode == 2 else (0.5, 0.0, 0.0)
+        st = hd.L.rnde_ffjord_nll_grad(hd.h, xd.data_ptr(), pd.data_ptr(), None if mode == 1 else ed.data_ptr(), B, 0.0, 1.0, 0, mode, *lam, pb.data_ptr(), xb.data_ptr(),
+                                       lp.data_ptr(), terms.data_ptr(), C.byref(reg), C.byref(nfe), None)
+        hd.rn._lib.check_ffjord(hd.h, st)
+        torch.cuda.synchronize()
+        for k, v in (("p_bar", pb), ("x_bar", xb), ("logpx", lp), ("terms", terms)):
+            out[f"{name}/mode{mode}/{k}"] = v.cpu().numpy()
+        out[f"{name}/mode{mode}/reg_nfe"] = np.array([reg.value, nfe.value], dtype=np.float64)
+        out[f"{name}/mode{mode}/steps"] = ff_steps(hd, hd.L.rnde_ffjord_steps)
+        hd.close()
+
+
+def ff_host_side_cases(out, logs):
+    """What the host-side paths beside the single tiled solve need: engine 0, the group call, the one-call training step."""
+    cs, td = FF_DYN[0], FF_DYN[2]
+    ff_engine0_case(out, logs, "e0-cs2-B17", cs[1], *ff_inputs(cs[1], cs[2], 17))
+    for key, dyn, recipe in (cs, td):
+        ff_groups_case(out, f"groups-{key}", dyn, recipe)
+        ff_nll_grad_case(out, f"nll-{key}-B37", dyn, recipe, 37, (0, 1, 2))
+    ff_nll_grad_case(out, "nll-e0-cs2-B37", cs[1], cs[2], 37, (0, 2), engine0=True)
+
+
 def child(path):
     out, logs = {}, []
     node_cases(out, logs)
     ff_cases(out, logs)
+    ff_host_side_cases(out, logs)
     for i, (engine, B, steps) in enumerate(logs):
         out[f"_log/{i:04d}/e{engine}/B{B}"] = steps
     np.savez(path, **out)
@@ -209,6 +309,7 @@ def main():
     ap.add_argument("--timeout", type=int, default=420, help="seconds per child")
     ap.add_argument("--workdir", help="where the two children leave their arrays (default: a temporary directory)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tile_driver_three.json"))
+    ap.add_argument("--key", default="bits", help="the key of --out that takes the verdict")
     ap.add_argument("--child")
     a = ap.parse_args()
     if a.child:
@@ -247,7 +348,7 @@ def compare(a):
                new=os.path.basename(a.new), arrays=len(P), differing=differing, coverage_by_parent_step_logs=cover, covered=covered,
                equal=not differing and covered)
     doc = json.load(open(a.out)) if os.path.exists(a.out) else {}
-    doc["bits"] = res
+    doc[a.key] = res
     with open(a.out, "w") as f:
         json.dump(doc, f, indent=1)
     print(json.dumps({k: v for k, v in res.items() if k != "differing"}), flush=True)

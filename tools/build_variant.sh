@@ -8,7 +8,9 @@ L=regneuralde.jl_amd/lib
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value -Wno-undefined-internal -Wno-pass-failed"
 /opt/rocm/bin/hipcc $F "$@" -c regneuralde.jl_amd/csrc/$SRC -o $L/obj/${SRC%.hip}_$NAME.o
 OBJS=""
-for o in rnde rnde_reverse rnde_stage_solve rnde_latent rnde_sde rnde_comm rnde_tapes rnde_ffjord; do
+# (the translation units are build.py's SOURCES: one list, so that a new unit is linked here too)
+UNITS=$(python3 regneuralde.jl_amd/build.py --print-units)
+for o in $UNITS; do
   if [ "$o.hip" == "$SRC" ]; then OBJS="$OBJS $L/obj/${o}_$NAME.o"; else OBJS="$OBJS $L/obj/$o.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $L/librnde_$NAME.so $OBJS -ldl
